@@ -9,13 +9,21 @@ blocks of all the rank's sources (prep -> fused FFT/multiply/IFFT/crossfade -> m
 plus, for N > 1, the RCCL sum of the stereo mixes to rank 0.  Signals, HRTF table and
 trajectories are resident in HBM before the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
 
 prints ONE JSON line (rank 0).  metric = source-frames per second (sources x frames/s),
-whole job.  With --gpus N > 1 and no WORLD_SIZE in the environment it starts its own N
-ranks (python -m torch.distributed.run) as a child process before anything touches the GPU.
+whole job; ms_per_step = wall time of one timed step.  With --gpus N > 1 and no WORLD_SIZE in
+the environment it starts its own N ranks (python -m torch.distributed.run) as a child process
+before anything touches the GPU.
 
-`roofline`: the fused kernel is bound by fp32 vector issue, not by HBM (the 5.8 MB table is
+A plain run does only what the headline needs: set up, warm up, time K steps, print the line.
+--full adds everything else described below (counter passes, roofline, CPU baseline and the
+check against the oracle, the single-source latency, the "also" record of the other single-GPU
+configurations).  --dump-outputs DIR writes the last timed step's stereo mix (what a caller of
+jf_batch_run receives) as DIR/mix.npy, float32 [blocks_per_step][2 x block]; the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
+
+`roofline` (--full): the fused kernel is bound by fp32 vector issue, not by HBM (the 5.8 MB table is
 cache-resident), so `frac` is executed fp32 flops / kernel time / 157.3 TFLOP/s; the HBM side
 is reported next to it from counters collected on THIS box (two short rocprofv3 --pmc passes of
 this script, run as child processes before the parent touches the GPU), or, if that is not
@@ -312,6 +320,7 @@ def also_configurations(args):
     st = copy.copy(args)
     st.stationary, st.steps = True, max(20, args.steps)
     rv.also_leg = st.also_leg = True
+    rv.dump_outputs = st.dump_outputs = None   # the outputs written are the headline's
     return {"reverb": rv, "reverb_realtime_us": None, "stationary": st}
 
 
@@ -432,7 +441,8 @@ def run_leg(args, ctx, pmc, pmc_note):
         step(prewarm + i)
     fence()
     stride = args.event_stride
-    if not os.environ.get("JF_NO_EVENTS"):  # tuning runs: how much do the event records cost?
+    # the event records serve the roofline only: a plain run times its steps without them
+    if args.full and not os.environ.get("JF_NO_EVENTS"):  # tuning runs: how much do the event records cost?
         eng.profile_enable(2 if ir is not None else 1)  # level 1: two events around the fused kernel
         # A pair of event records costs ~7 us of stream time -- 2.7 % of a 0.25 ms step (1.30e11 against 1.33e11 with
         # JF_NO_EVENTS=1, profiles/r03_experiments.md): the fused launch is timed at every EVENT_STRIDE-th step of the timed
@@ -449,9 +459,10 @@ def run_leg(args, ctx, pmc, pmc_note):
         step(i)
     fence()
     dt = time.perf_counter() - t0
-    prof = eng.profile_read()
-    reverb_ms = eng.profile_read_reverb() if ir is not None else 0.0
-    eng.profile_enable(False)
+    if args.full:
+        prof = eng.profile_read()
+        reverb_ms = eng.profile_read_reverb() if ir is not None else 0.0
+        eng.profile_enable(False)
     kernels = eng.last_kernels()
     G = eng.last_source_group()
     order = eng.source_order()
@@ -459,15 +470,19 @@ def run_leg(args, ctx, pmc, pmc_note):
     # what the last timed step left behind (checked against the oracle below)
     i_last = prewarm + W + K - 1
     last_mix = mixes[i_last & 1].cpu().numpy().copy()
+    if args.dump_outputs and rank == 0:
+        # the stereo mix of the last timed step ([KB][2B] float32; at N > 1 the reduced one)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "mix.npy"), np.ascontiguousarray(last_mix, dtype=np.float32))
     groups = {}
-    if world == 1:
+    if world == 1 and args.full:
         part = eng.read_device(eng.partial_device_ptr(), (KB, S // G, 2 * B))
         for g in sorted({0, 1, (S // G) // 3, (S // G) // 2, S // G - 2, S // G - 1}):
             groups[int(g)] = part[:, g].copy()
 
     # prep / mix kernel times: a short untimed pass with every kernel bracketed by events
     other = {}
-    if ir is None:
+    if ir is None and args.full:
         eng.profile_enable(2)
         for i in range(prewarm + W + K, prewarm + W + K + 16):
             step(i)
@@ -483,7 +498,7 @@ def run_leg(args, ctx, pmc, pmc_note):
     # step's own collective, HIP events on that stream -- the first when the step's kernels are done, the second when the
     # reduced mix is there.
     comm_ms = None
-    if use_dist:
+    if use_dist and args.full:
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(16)]
         base_i = prewarm + W + K + (16 if ir is None else 0)
         for n, (e0, e1) in enumerate(evs):
@@ -512,120 +527,122 @@ def run_leg(args, ctx, pmc, pmc_note):
     if rank == 0:
         frames = world * S * KB * K * B
         value = frames / dt
-        # the launches that were timed (every --event-stride-th step); the workload totals below are over all K steps, so
-        # the timed launches' time is scaled to K launches: fused_s = K x the average timed launch
-        timed = max(prof["launches"], 1)
-        launches = K
-        fused_s = prof["fused_ms"] * 1e-3 / timed * K
-        first_step = prewarm + W
-        # the run walks the uploaded period cyclically: price each step of the period once (its predecessor block is
-        # the one before it on the circle) and count how often each was timed
-        pre_rows = bool(eng.last_run_used_rows())   # the timed runs read pre-interpolated rows (include/jefferson.h)
-        abytes, rows, items = wl.algorithmic_bytes_cyclic(jf, pos, KB, B, first_step, K, pre_rows=pre_rows)
-        pair = any("pair" in k for k in kernels)
-        flops_ex, flops_ref = wl.flops_cyclic(jf, pos, KB, B, G, first_step, K, old_sets_spectral=pair, pre_rows=pre_rows)
-        tf = flops_ex / fused_s / 1e12 if fused_s > 0 else 0.0
-        fused_name = next((k for k in kernels if k.startswith("fused_")), kernels[-1])
-        # "fused_pair_kernel<4>+prep": the launch's trailing workgroups prepare the next window's descriptors (same kernel
-        # symbol in rocprofv3: fused_pair_kernel<4>); its duration and its counters include them
-        fused_has_prep = fused_name.endswith("+prep")
-        fused_name = fused_name.split("+")[0]
-        roof = {"bound": "valu-fp32", "achieved": tf, "peak": FP32_VECTOR_PEAK_TF, "unit": "TFLOP/s",
-                "frac": tf / FP32_VECTOR_PEAK_TF, "traffic": None, "kernel": fused_name,
-                "avg_launch_ms": prof["fused_ms"] / timed,
-                "launches_timed": timed,
-                "launch_timing": ("HIP events on the engine's stream around every %d-th fused launch of the timed region (%d of %d"
-                                  " launches; a pair of event records costs ~7 us of stream time)" % (stride, timed, K)
-                                  if ir is None else
-                                  "HIP events around every kernel of every %d-th step of the timed region (%d of %d steps)"
-                                  % (stride, timed, K)),
-                "launch_includes": ("the next window's descriptors (index/weight rule for 131 072 items in trailing "
-                                    "workgroups, ~2.5 us of the launch, ~20 of the VALU instructions per source-block)"
-                                    if fused_has_prep else None),
-                "flops_per_launch_executed": flops_ex / launches,
-                "flop_model": "jefferson-2.0_amd/workload.py flops_window (textbook counts; tests/test_abi.py)",
-                "table_rows_per_source_block": rows / items,
-                "other_kernels": other,
-                "why_not_hbm": "the 5.8 MB HRTF table is cache-resident: compulsory HBM bytes are ~1.3 KB per source-block",
-                # what the vector unit sustains on this chip with every CU busy (profiles/micro/valu_rate.hip, 4 waves per
-                # SIMD, register operands): the spec figure assumes 2.4 GHz, the clock under that load is ~1.9-2.0 GHz
-                "peak_sustained_measured": {"v_fma_f32": 120.2, "v_pk_fma_f32": 137.4, "unit": "TFLOP/s",
-                                            "frac_of_v_fma_f32": tf / 120.2}}
-        # NOT a roofline fraction (it prices work the kernel does not do): the same output priced with the reference's own
-        # algorithm -- an unpruned inverse pair per filter set and source, GPUSoundSource.cu:320-385 --, comparable across
-        # kernels that skip different amounts of that work
-        ref_rate = {"flops_per_launch_reference_algorithm": flops_ref / launches,
-                    "tflops_if_the_reference_algorithm_were_executed": (flops_ref / fused_s / 1e12) if fused_s > 0 else 0.0,
-                    "note": "work-equivalent rate for comparisons between kernel generations, not an achieved figure"}
-        # SURVEY.md 8(d)'s algorithmic bytes (table rows re-read per item): a CACHE-level rate, not an HBM rate
-        roof["algorithmic_cache_gbps"] = abytes / fused_s / 1e9 if fused_s > 0 else 0.0
-        roof["algorithmic_bytes_per_launch"] = abytes / launches
-        hbm = {"peak": HBM_PEAK_GBS, "unit": "GB/s"}
-        fpmc = None if ir is not None else pmc   # with --reverb the counters are the multiply-accumulate kernel's
-        # How busy the compute units' vector-memory return path is (round 5, profiles/r05/l1_bound.md): a vector L1 returns 64
-        # bytes per clock (256 CUs x 64 B x ~2.1 GHz = the guide's 34.5 TB/s for the L2s, the same pipe from the other
-        # side).  From the kernel's own load count -- the algorithmic figure above counts 6.65 rows per source-block, the
-        # kernel loads ~4.2 (old and new filter sets mostly share their rows): 16-byte row loads of 1 KB per wave, eight
-        # 8-byte window loads of 512 B.  Half busy, and not what the kernel waits for (closer rows -3..-4.5 %, more loads in
-        # flight nothing): reported so that the third resource is on the line beside the vector unit and HBM.
-        if fpmc and fpmc.get("SQ_INSTS_VMEM_RD") and fpmc.get("GRBM_GUI_ACTIVE") and fused_s > 0:
-            loads = fpmc["SQ_INSTS_VMEM_RD"]                      # wave-instructions per launch
-            win = 8.0 * S * KB                                     # the windows' (8 B per lane)
-            l1_bytes = max(loads - win, 0.0) * 1024.0 + min(loads, win) * 512.0
-            cyc = fpmc["GRBM_GUI_ACTIVE"] / 8.0                   # (summed over the 8 XCDs) cycles of one launch under the counters
-            roof["l1"] = {"what": "bytes the vector L1s return to registers per launch, from the kernel's own load count",
-                          "bytes_per_launch": l1_bytes, "achieved": l1_bytes / (fused_s / launches) / 1e9, "unit": "GB/s",
-                          "peak": L2_PEAK_GBS, "peak_source": "MI355X_MICROARCH.md: L2 aggregate ~34.5 TB/s = 64 B per clock and CU",
-                          "frac": l1_bytes / (fused_s / launches) / 1e9 / L2_PEAK_GBS,
-                          "bytes_per_clock_and_cu": l1_bytes / cyc / 256.0,
-                          "clock_ghz_under_the_counters": cyc / (fused_s / launches) / 1e9,
-                          "loads_per_source_block": loads / (S * KB), "evidence": "profiles/r05/l1_bound.md", "source": pmc_note}
-        if fpmc and "FETCH_SIZE" in fpmc and "WRITE_SIZE" in fpmc:
-            # MI355X_MICROARCH.md (HBM): FETCH_SIZE / WRITE_SIZE are in KB; on gfx950 FETCH_SIZE reads 1/2 of a wide
-            # coalesced stream -> x2; WRITE_SIZE is exact for 16-B-per-lane stores
-            traffic = fpmc["FETCH_SIZE"] * 1024 * 2 + fpmc["WRITE_SIZE"] * 1024
-            src = pmc_note
-        else:
-            traffic, src = None, None   # never a figure from another run: null and the reason (`source`)
-        if traffic is not None:
-            roof["traffic"] = traffic
-            hbm.update({"bytes_per_launch": traffic, "achieved": traffic / (fused_s / launches) / 1e9,
-                        "frac": traffic / (fused_s / launches) / 1e9 / HBM_PEAK_GBS, "source": src})
-        else:
-            hbm.update({"bytes_per_launch": None, "source": f"unavailable: {pmc_note}"})
-        roof["hbm"] = hbm
-        if fpmc and "SQ_INSTS_VALU" in fpmc:
-            iss = {"valu_insts_per_source_block": fpmc["SQ_INSTS_VALU"] / (S * KB), "source": pmc_note}
-            if fpmc.get("GRBM_GUI_ACTIVE") and fpmc.get("SQ_INSTS_VALU"):
-                # A SIMD retires one wave64 vector instruction per ~2 cycles when two or more of its waves have one
-                # ready (MI355X_MICROARCH.md; profiles/micro/valu_rate.hip measures 1.09 ns at 4 waves per SIMD), one
-                # per 4 cycles from a single wave; packed-f32 instructions take twice that.  GRBM_GUI_ACTIVE is summed
-                # over the 8 XCDs, SQ_INSTS_VALU over the 1024 SIMDs.
-                per_simd = fpmc["SQ_INSTS_VALU"] / 1024
-                cycles = fpmc["GRBM_GUI_ACTIVE"] / 8
-                iss["valu_pipe_busy_share_at_2_cycles_per_inst"] = per_simd * 2 / cycles
-                iss["valu_issue_share_at_4_cycles_per_inst"] = per_simd * 4 / cycles
-                iss["valu_rate_note"] = ("2 cycles: what the SIMD needs with >= 2 waves ready (plain f32; packed f32 twice "
-                                         "that); 4 cycles: what one wave alone can issue")
-            if fpmc.get("SQ_ACTIVE_INST_VALU") and fpmc.get("GRBM_GUI_ACTIVE"):
-                # The bound the kernel actually sits on: the share of the launch in which a SIMD's vector pipe is executing a
-                # vector instruction (SQ_ACTIVE_INST_VALU counts quad-cycles, summed over the 1024 SIMDs; GRBM_GUI_ACTIVE
-                # cycles, summed over the 8 XCDs).  The flop fraction (`frac`) prices the same work at 2 cycles per
-                # instruction; executed, an instruction of this kernel's mix occupies the pipe for ~4.
-                iss["valu_active_share"] = (fpmc["SQ_ACTIVE_INST_VALU"] * 4.0 / 1024.0) / (fpmc["GRBM_GUI_ACTIVE"] / 8.0)
-            if fpmc.get("SQ_INSTS_VMEM_RD"):
-                iss["vmem_loads_per_source_block"] = fpmc["SQ_INSTS_VMEM_RD"] / (S * KB)
-            if fpmc.get("SQ_WAVE_CYCLES") and fpmc.get("SQ_WAIT_ANY"):
-                iss["wave_time_waiting_share"] = fpmc["SQ_WAIT_ANY"] / fpmc["SQ_WAVE_CYCLES"]
-            roof["issue"] = iss
-        if fpmc and fpmc.get("SQ_INSTS_VALU_FLOPS_FP32") and fused_s > 0:
-            # the hardware's own count of executed fp32 flops (per wave instruction: x 64 lanes), beside the textbook model
-            fl = fpmc["SQ_INSTS_VALU_FLOPS_FP32"] * 64.0
-            roof["frac_pmc"] = fl / (fused_s / launches) / 1e12 / FP32_VECTOR_PEAK_TF
-            roof["flops_per_launch_pmc"] = fl
-            roof["frac_pmc_source"] = "SQ_INSTS_VALU_FLOPS_FP32 x 64 lanes per launch / avg_launch_ms; " + pmc_note
-        else:
-            roof["frac_pmc"] = None
+        roof = ref_rate = None
+        if args.full:
+            # the launches that were timed (every --event-stride-th step); the workload totals below are over all K steps, so
+            # the timed launches' time is scaled to K launches: fused_s = K x the average timed launch
+            timed = max(prof["launches"], 1)
+            launches = K
+            fused_s = prof["fused_ms"] * 1e-3 / timed * K
+            first_step = prewarm + W
+            # the run walks the uploaded period cyclically: price each step of the period once (its predecessor block is
+            # the one before it on the circle) and count how often each was timed
+            pre_rows = bool(eng.last_run_used_rows())   # the timed runs read pre-interpolated rows (include/jefferson.h)
+            abytes, rows, items = wl.algorithmic_bytes_cyclic(jf, pos, KB, B, first_step, K, pre_rows=pre_rows)
+            pair = any("pair" in k for k in kernels)
+            flops_ex, flops_ref = wl.flops_cyclic(jf, pos, KB, B, G, first_step, K, old_sets_spectral=pair, pre_rows=pre_rows)
+            tf = flops_ex / fused_s / 1e12 if fused_s > 0 else 0.0
+            fused_name = next((k for k in kernels if k.startswith("fused_")), kernels[-1])
+            # "fused_pair_kernel<4>+prep": the launch's trailing workgroups prepare the next window's descriptors (same kernel
+            # symbol in rocprofv3: fused_pair_kernel<4>); its duration and its counters include them
+            fused_has_prep = fused_name.endswith("+prep")
+            fused_name = fused_name.split("+")[0]
+            roof = {"bound": "valu-fp32", "achieved": tf, "peak": FP32_VECTOR_PEAK_TF, "unit": "TFLOP/s",
+                    "frac": tf / FP32_VECTOR_PEAK_TF, "traffic": None, "kernel": fused_name,
+                    "avg_launch_ms": prof["fused_ms"] / timed,
+                    "launches_timed": timed,
+                    "launch_timing": ("HIP events on the engine's stream around every %d-th fused launch of the timed region (%d of %d"
+                                      " launches; a pair of event records costs ~7 us of stream time)" % (stride, timed, K)
+                                      if ir is None else
+                                      "HIP events around every kernel of every %d-th step of the timed region (%d of %d steps)"
+                                      % (stride, timed, K)),
+                    "launch_includes": ("the next window's descriptors (index/weight rule for 131 072 items in trailing "
+                                        "workgroups, ~2.5 us of the launch, ~20 of the VALU instructions per source-block)"
+                                        if fused_has_prep else None),
+                    "flops_per_launch_executed": flops_ex / launches,
+                    "flop_model": "jefferson-2.0_amd/workload.py flops_window (textbook counts; tests/test_abi.py)",
+                    "table_rows_per_source_block": rows / items,
+                    "other_kernels": other,
+                    "why_not_hbm": "the 5.8 MB HRTF table is cache-resident: compulsory HBM bytes are ~1.3 KB per source-block",
+                    # what the vector unit sustains on this chip with every CU busy (profiles/micro/valu_rate.hip, 4 waves per
+                    # SIMD, register operands): the spec figure assumes 2.4 GHz, the clock under that load is ~1.9-2.0 GHz
+                    "peak_sustained_measured": {"v_fma_f32": 120.2, "v_pk_fma_f32": 137.4, "unit": "TFLOP/s",
+                                                "frac_of_v_fma_f32": tf / 120.2}}
+            # NOT a roofline fraction (it prices work the kernel does not do): the same output priced with the reference's own
+            # algorithm -- an unpruned inverse pair per filter set and source, GPUSoundSource.cu:320-385 --, comparable across
+            # kernels that skip different amounts of that work
+            ref_rate = {"flops_per_launch_reference_algorithm": flops_ref / launches,
+                        "tflops_if_the_reference_algorithm_were_executed": (flops_ref / fused_s / 1e12) if fused_s > 0 else 0.0,
+                        "note": "work-equivalent rate for comparisons between kernel generations, not an achieved figure"}
+            # SURVEY.md 8(d)'s algorithmic bytes (table rows re-read per item): a CACHE-level rate, not an HBM rate
+            roof["algorithmic_cache_gbps"] = abytes / fused_s / 1e9 if fused_s > 0 else 0.0
+            roof["algorithmic_bytes_per_launch"] = abytes / launches
+            hbm = {"peak": HBM_PEAK_GBS, "unit": "GB/s"}
+            fpmc = None if ir is not None else pmc   # with --reverb the counters are the multiply-accumulate kernel's
+            # How busy the compute units' vector-memory return path is (round 5, profiles/r05/l1_bound.md): a vector L1 returns 64
+            # bytes per clock (256 CUs x 64 B x ~2.1 GHz = the guide's 34.5 TB/s for the L2s, the same pipe from the other
+            # side).  From the kernel's own load count -- the algorithmic figure above counts 6.65 rows per source-block, the
+            # kernel loads ~4.2 (old and new filter sets mostly share their rows): 16-byte row loads of 1 KB per wave, eight
+            # 8-byte window loads of 512 B.  Half busy, and not what the kernel waits for (closer rows -3..-4.5 %, more loads in
+            # flight nothing): reported so that the third resource is on the line beside the vector unit and HBM.
+            if fpmc and fpmc.get("SQ_INSTS_VMEM_RD") and fpmc.get("GRBM_GUI_ACTIVE") and fused_s > 0:
+                loads = fpmc["SQ_INSTS_VMEM_RD"]                      # wave-instructions per launch
+                win = 8.0 * S * KB                                     # the windows' (8 B per lane)
+                l1_bytes = max(loads - win, 0.0) * 1024.0 + min(loads, win) * 512.0
+                cyc = fpmc["GRBM_GUI_ACTIVE"] / 8.0                   # (summed over the 8 XCDs) cycles of one launch under the counters
+                roof["l1"] = {"what": "bytes the vector L1s return to registers per launch, from the kernel's own load count",
+                              "bytes_per_launch": l1_bytes, "achieved": l1_bytes / (fused_s / launches) / 1e9, "unit": "GB/s",
+                              "peak": L2_PEAK_GBS, "peak_source": "MI355X_MICROARCH.md: L2 aggregate ~34.5 TB/s = 64 B per clock and CU",
+                              "frac": l1_bytes / (fused_s / launches) / 1e9 / L2_PEAK_GBS,
+                              "bytes_per_clock_and_cu": l1_bytes / cyc / 256.0,
+                              "clock_ghz_under_the_counters": cyc / (fused_s / launches) / 1e9,
+                              "loads_per_source_block": loads / (S * KB), "evidence": "profiles/r05/l1_bound.md", "source": pmc_note}
+            if fpmc and "FETCH_SIZE" in fpmc and "WRITE_SIZE" in fpmc:
+                # MI355X_MICROARCH.md (HBM): FETCH_SIZE / WRITE_SIZE are in KB; on gfx950 FETCH_SIZE reads 1/2 of a wide
+                # coalesced stream -> x2; WRITE_SIZE is exact for 16-B-per-lane stores
+                traffic = fpmc["FETCH_SIZE"] * 1024 * 2 + fpmc["WRITE_SIZE"] * 1024
+                src = pmc_note
+            else:
+                traffic, src = None, None   # never a figure from another run: null and the reason (`source`)
+            if traffic is not None:
+                roof["traffic"] = traffic
+                hbm.update({"bytes_per_launch": traffic, "achieved": traffic / (fused_s / launches) / 1e9,
+                            "frac": traffic / (fused_s / launches) / 1e9 / HBM_PEAK_GBS, "source": src})
+            else:
+                hbm.update({"bytes_per_launch": None, "source": f"unavailable: {pmc_note}"})
+            roof["hbm"] = hbm
+            if fpmc and "SQ_INSTS_VALU" in fpmc:
+                iss = {"valu_insts_per_source_block": fpmc["SQ_INSTS_VALU"] / (S * KB), "source": pmc_note}
+                if fpmc.get("GRBM_GUI_ACTIVE") and fpmc.get("SQ_INSTS_VALU"):
+                    # A SIMD retires one wave64 vector instruction per ~2 cycles when two or more of its waves have one
+                    # ready (MI355X_MICROARCH.md; profiles/micro/valu_rate.hip measures 1.09 ns at 4 waves per SIMD), one
+                    # per 4 cycles from a single wave; packed-f32 instructions take twice that.  GRBM_GUI_ACTIVE is summed
+                    # over the 8 XCDs, SQ_INSTS_VALU over the 1024 SIMDs.
+                    per_simd = fpmc["SQ_INSTS_VALU"] / 1024
+                    cycles = fpmc["GRBM_GUI_ACTIVE"] / 8
+                    iss["valu_pipe_busy_share_at_2_cycles_per_inst"] = per_simd * 2 / cycles
+                    iss["valu_issue_share_at_4_cycles_per_inst"] = per_simd * 4 / cycles
+                    iss["valu_rate_note"] = ("2 cycles: what the SIMD needs with >= 2 waves ready (plain f32; packed f32 twice "
+                                             "that); 4 cycles: what one wave alone can issue")
+                if fpmc.get("SQ_ACTIVE_INST_VALU") and fpmc.get("GRBM_GUI_ACTIVE"):
+                    # The bound the kernel actually sits on: the share of the launch in which a SIMD's vector pipe is executing a
+                    # vector instruction (SQ_ACTIVE_INST_VALU counts quad-cycles, summed over the 1024 SIMDs; GRBM_GUI_ACTIVE
+                    # cycles, summed over the 8 XCDs).  The flop fraction (`frac`) prices the same work at 2 cycles per
+                    # instruction; executed, an instruction of this kernel's mix occupies the pipe for ~4.
+                    iss["valu_active_share"] = (fpmc["SQ_ACTIVE_INST_VALU"] * 4.0 / 1024.0) / (fpmc["GRBM_GUI_ACTIVE"] / 8.0)
+                if fpmc.get("SQ_INSTS_VMEM_RD"):
+                    iss["vmem_loads_per_source_block"] = fpmc["SQ_INSTS_VMEM_RD"] / (S * KB)
+                if fpmc.get("SQ_WAVE_CYCLES") and fpmc.get("SQ_WAIT_ANY"):
+                    iss["wave_time_waiting_share"] = fpmc["SQ_WAIT_ANY"] / fpmc["SQ_WAVE_CYCLES"]
+                roof["issue"] = iss
+            if fpmc and fpmc.get("SQ_INSTS_VALU_FLOPS_FP32") and fused_s > 0:
+                # the hardware's own count of executed fp32 flops (per wave instruction: x 64 lanes), beside the textbook model
+                fl = fpmc["SQ_INSTS_VALU_FLOPS_FP32"] * 64.0
+                roof["frac_pmc"] = fl / (fused_s / launches) / 1e12 / FP32_VECTOR_PEAK_TF
+                roof["flops_per_launch_pmc"] = fl
+                roof["frac_pmc_source"] = "SQ_INSTS_VALU_FLOPS_FP32 x 64 lanes per launch / avg_launch_ms; " + pmc_note
+            else:
+                roof["frac_pmc"] = None
         out = {
             "metric": "source-frames/s (sources x frames/sec) at 256-sample blocks",
             "value": value, "unit": "source-frames/s", "n_gpus": world, "steps": K, "warmup": W,
@@ -651,10 +668,11 @@ def run_leg(args, ctx, pmc, pmc_note):
                                        + " of the stereo mix") if use_dist else "1 GPU"},
             "real_time_factor": (KB * K * B / 44100.0) / dt,
             "us_per_source_block": dt / (S * KB * K) * 1e6,
-            "roofline": roof,
-            "reference_algorithm_rate": ref_rate,
         }
-        if use_dist:
+        if args.full:
+            out["roofline"] = roof
+            out["reference_algorithm_rate"] = ref_rate
+        if use_dist and args.full:
             # the only exchange of the path: the sum of the per-rank stereo mixes
             out["comm"] = {"collective": ("reduce(sum, dst=0)" if backend == "nccl" else "all_reduce(sum)")
                                          + " of float32[%d][%d] per step" % (KB, 2 * B),
@@ -677,7 +695,6 @@ def run_leg(args, ctx, pmc, pmc_note):
                                        "collective; max over ranks"}
         if ir is not None:
             P = -(-len(ir) // B)
-            t = reverb_ms / timed * 1e-3  # average time of the reverb stage's kernels over the steps that were timed
             n_tot, p_head, p_big, big_taps = eng.reverb_partitions()
             std = S == 256 and len(ir) == 88200
             parts = ((f"{p_head} partitions of {B} + {p_big} of {big_taps}" if args.realtime else
@@ -687,6 +704,9 @@ def run_leg(args, ctx, pmc, pmc_note):
                                          + f"{S} sources + {len(ir) / 44100.0:g} s convolution-reverb IR ({P} blocks long), "
                                            f"partitioned overlap-save ({parts}), {B}-sample blocks"
                                          + (", ONE block per call (real-time shape)" if args.realtime else ""))
+            out["metric"] = "source-frames/s (sources x frames/sec) at 128-sample blocks, reverb + spatialiser"
+        if ir is not None and args.full:
+            t = reverb_ms / timed * 1e-3  # average time of the reverb stage's kernels over the steps that were timed
             rv_kernels = [k for k in kernels if k.startswith("reverb_")]
             rv = {"kernel": " + ".join(rv_kernels), "kernels_are": "the reverb stage's kernels of the LAST timed step",
                   "avg_stage_ms": t * 1e3, "stage_timing": "HIP events around the stage's kernels on the engine's stream"}
@@ -759,18 +779,17 @@ def run_leg(args, ctx, pmc, pmc_note):
             out["roofline"] = rv
             out["step_split_ms"] = {"reverb_stage": t * 1e3, "spatialiser_fused_kernel": prof["fused_ms"] / timed,
                                     "whole_step": dt / K * 1e3}
-            out["metric"] = "source-frames/s (sources x frames/sec) at 128-sample blocks, reverb + spatialiser"
-        if world == 1 and ir is None and not getattr(args, "also_leg", False):
+        if args.full and world == 1 and ir is None and not getattr(args, "also_leg", False):
             try:
                 out["single_source_block_latency_us"] = single_source_latency_us(jf, hrir)
             except Exception as ex:
                 out["single_source_block_latency_us"] = {"error": str(ex)}
-        if world == 1 and ir is not None and args.realtime:
+        if args.full and world == 1 and ir is not None and args.realtime:
             try:
                 out["realtime_call_us"] = realtime_reverb_call_us(jf, hrir, S, B, ir, RV_GAIN)
             except Exception as ex:
                 out["realtime_call_us"] = {"error": str(ex)}
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             all_ids = np.arange(0, world * S)
             nb = max(KB + 4, min(args.cpu_sample_blocks, max(KB + 4, 262144 // len(all_ids))))
             if ir is not None:
@@ -820,12 +839,18 @@ def main():
                          "Infinity Cache: the HBM-bound measurement)")
     ap.add_argument("--rv-ir-seconds", type=float, default=2.0,
                     help="with --reverb: length of the impulse response (4.0 = media/s1_r1_b_441_mono.wav's: 1379 partitions)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: counter passes, roofline, CPU baseline and the check against the oracle, "
+                         "single-source latency, the \"also\" record (off: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's stereo mix as DIR/mix.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline and no check")
     ap.add_argument("--no-also", action="store_true",
-                    help="the default line without its \"also\" record (config 5 in batch form and in real time, the stationary variant)")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the two rocprofv3 counter passes")
+                    help="with --full: the default line without its \"also\" record (config 5 in batch form and in real time, "
+                         "the stationary variant)")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the two rocprofv3 counter passes")
     ap.add_argument("--event-stride", type=int, default=8,
-                    help="HIP events around every n-th fused launch of the timed region (1: around every one)")
+                    help="with --full: HIP events around every n-th fused launch of the timed region (1: around every one)")
     ap.add_argument("--cpu-sample-blocks", type=int, default=256)
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -846,9 +871,9 @@ def main():
     # variant of the headline -- run after the headline's timed region and verification, in this process, on fresh engines.
     default_line = not (args.reverb or args.stationary or args.realtime or args.move_every != 1 or args.pmc_child
                         or os.environ.get("JF_BENCH_NARROW") is not None)
-    also_legs = also_configurations(args) if (default_line and world == 1 and not args.no_also) else {}
+    also_legs = also_configurations(args) if (args.full and default_line and world == 1 and not args.no_also) else {}
     # every leg's hardware counters FIRST: the profiled children must have come and gone before this process touches the GPU
-    pmc, pmc_note = precollect_pmc(args, world)
+    pmc, pmc_note = precollect_pmc(args, world) if args.full else (None, "not collected (plain run: --full collects them)")
     also_pmc = {name: precollect_pmc(a, world) for name, a in also_legs.items() if name != "reverb_realtime_us"}
 
     backend = os.environ.get("JF_DIST_BACKEND", "nccl")
@@ -914,7 +939,7 @@ def main():
                 if isinstance(also[name], dict):
                     also[name]["leg_s"] = time.perf_counter() - t_leg
             out["also"] = also
-        elif default_line and world > 1:
+        elif args.full and default_line and world > 1:
             out["also"] = None
             out["also_null_because"] = "the secondary configurations are single-GPU ones: reported by the N = 1 line"
         print(json.dumps(out), flush=True)

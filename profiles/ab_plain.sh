@@ -5,7 +5,7 @@ OUT=$REPO/gpurun_out/ab_plain; mkdir -p $OUT
 for R in 1 2 3; do
   for T in "$@"; do
     if [ "$T" = "-" ]; then unset JF_LIB; N=product; else export JF_LIB=$REPO/jefferson-2.0_amd/libjefferson_hip_$T.so; N=$T; fi
-    timeout -k 10 200 python3 $REPO/bench.py ${RV_ARGS:---reverb --no-pmc --no-cpu-baseline --steps 512 --warmup 64} > $OUT/${N}_$R.json 2> $OUT/${N}_$R.err
+    timeout -k 10 200 python3 $REPO/bench.py --full ${RV_ARGS:---reverb --no-pmc --no-cpu-baseline --steps 512 --warmup 64} > $OUT/${N}_$R.json 2> $OUT/${N}_$R.err
     python3 -c "
 import json,sys
 d=json.loads(open('$OUT/${N}_$R.json').read().strip().splitlines()[-1])

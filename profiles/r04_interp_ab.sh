@@ -12,7 +12,7 @@ OUT=gpurun_out/r04_interp
 mkdir -p $OUT
 run() { # tag, env...
   tag=$1; shift
-  env "$@" python3 bench.py --no-pmc --steps 512 --cpu-sample-blocks 132 > $OUT/$tag.json 2> $OUT/$tag.err || { echo "$tag FAILED"; tail -5 $OUT/$tag.err; }
+  env "$@" python3 bench.py --full --no-pmc --steps 512 --cpu-sample-blocks 132 > $OUT/$tag.json 2> $OUT/$tag.err || { echo "$tag FAILED"; tail -5 $OUT/$tag.err; }
   python3 - "$OUT/$tag.json" "$tag" <<'PY'
 import json, sys
 try:

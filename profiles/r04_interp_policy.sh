@@ -7,7 +7,7 @@ OUT=gpurun_out/r04_policy
 mkdir -p $OUT
 run() { # tag, bench args (quoted), env...
   tag=$1; args=$2; shift 2
-  env "$@" python3 bench.py $args --steps 512 --cpu-sample-blocks 132 > $OUT/$tag.json 2> $OUT/$tag.err || { echo "$tag FAILED"; tail -5 $OUT/$tag.err; }
+  env "$@" python3 bench.py --full $args --steps 512 --cpu-sample-blocks 132 > $OUT/$tag.json 2> $OUT/$tag.err || { echo "$tag FAILED"; tail -5 $OUT/$tag.err; }
   python3 - "$OUT/$tag.json" "$tag" <<'PY'
 import json, sys
 try:

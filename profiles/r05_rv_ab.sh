@@ -9,7 +9,7 @@ ARGS=${RV_ARGS:---reverb --no-pmc --no-cpu-baseline --steps 64 --warmup 8}
 for T in "$@"; do
   if [ "$T" = "-" ]; then unset JF_LIB; N=product; else export JF_LIB=$REPO/jefferson-2.0_amd/libjefferson_hip_$T.so; N=$T; fi
   rm -rf $OUT/$N
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$N -- python3 $REPO/bench.py $ARGS > $OUT/$N.json 2> $OUT/$N.err
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$N -- python3 $REPO/bench.py --full $ARGS > $OUT/$N.json 2> $OUT/$N.err
   echo "== $N rc=$?"
   python3 - "$OUT/$N" "$OUT/$N.json" <<'PY'
 import csv, glob, json, sys

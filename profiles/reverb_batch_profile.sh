@@ -7,7 +7,7 @@ export JF_REVERB_BLOCKS_PER_STEP=${JF_REVERB_BLOCKS_PER_STEP:-32}  # the size th
 OUT=$REPO/gpurun_out/reverb_$TAG
 mkdir -p $OUT
 cd $REPO
-timeout -k 10 300 python3 bench.py --reverb --steps 256 --warmup 128 --no-pmc > $OUT/bench_reverb.json 2> $OUT/bench.err; echo "bench reverb rc=$?"
+timeout -k 10 300 python3 bench.py --full --reverb --steps 256 --warmup 128 --no-pmc > $OUT/bench_reverb.json 2> $OUT/bench.err; echo "bench reverb rc=$?"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $REPO/bench.py --reverb --steps 64 --warmup 128 --no-pmc --no-cpu-baseline > $OUT/trace.log 2>&1; echo "trace rc=$?"
 cd $REPO

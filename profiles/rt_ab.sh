@@ -14,7 +14,7 @@ done
 for T in "$@"; do
   if [ "$T" = "-" ]; then unset JF_LIB; N=product; else export JF_LIB=$REPO/jefferson-2.0_amd/libjefferson_hip_$T.so; N=$T; fi
   V=WGS_$N; if [ -n "${!V}" ]; then export JF_RV_SIDE_WGS=${!V}; else unset JF_RV_SIDE_WGS; fi
-  timeout -k 10 200 python3 $REPO/bench.py --reverb --realtime --steps 1000 --warmup 300 --no-pmc > $OUT/bench_$N.json 2> $OUT/bench_$N.err
+  timeout -k 10 200 python3 $REPO/bench.py --full --reverb --realtime --steps 1000 --warmup 300 --no-pmc > $OUT/bench_$N.json 2> $OUT/bench_$N.err
   python3 -c "
 import json
 d=json.loads(open('$OUT/bench_$N.json').read().strip().splitlines()[-1])

@@ -41,6 +41,24 @@ def jf():
     return mod
 
 
+def write_compact_dir(root, hrir):
+    """Re-create the reference's compact KEMAR layout (compact/elev%d/H%de%03da.wav, stereo int16)
+    from the committed table fixture, so the directory loader can be exercised off the build box."""
+    import wave
+    import model64
+    for j, (e, a) in enumerate(model64.table_positions()):
+        if a > 180:
+            continue
+        d = os.path.join(root, f"elev{e}")
+        os.makedirs(d, exist_ok=True)
+        pcm = np.round(hrir[j].T * 32768.0).astype(np.int16)  # [128][2], ch0 = left
+        with wave.open(os.path.join(d, f"H{e}e{a:03d}a.wav"), "wb") as w:
+            w.setnchannels(2)
+            w.setsampwidth(2)
+            w.setframerate(44100)
+            w.writeframes(pcm.tobytes())
+
+
 def sum_tol(tol, n, k=0.75):
     """Bound on the error of a sum of n per-source blocks each held to `tol` per sample (tol = a max over samples, i.e.
     about five standard deviations of a source's error).  The sources' rounding errors are independent, so they add like

@@ -253,16 +253,17 @@ def test_wav_writer_pcm24_roundtrip(jf, tmp_path):
     assert np.abs(v[1:] / 8388607.0 - y[1:]).max() <= 1.0 / 8388607
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/Jefferson/compact"),
-                    reason="the reference's compact KEMAR directory only exists in the build container")
-def test_compact_directory_loader_reproduces_the_fixture(jf, hrir):
-    """jf_engine_create_from_dir reads the reference's own data files: up to the point where a
-    GPU is needed, i.e. a complete, valid directory yields JF_ERR_DEVICE (not JF_ERR_IO)."""
+def test_compact_directory_loader_reproduces_the_fixture(jf, hrir, tmp_path):
+    """jf_engine_create_from_dir reads the reference's own data layout (re-created from the committed table fixture): up
+    to the point where a GPU is needed, i.e. a complete, valid directory yields JF_ERR_DEVICE (not JF_ERR_IO)."""
     import torch
+    from conftest import write_compact_dir
     if torch.cuda.is_available():
         pytest.skip("checked on the GPU by test_gpu_engine.py")
+    kemar = str(tmp_path / "compact")
+    write_compact_dir(kemar, hrir)
     with pytest.raises(jf.JfError) as ei:
-        jf.Engine(256, 512, 1, hrir_dir="/root/reference/Jefferson/compact")
+        jf.Engine(256, 512, 1, hrir_dir=kemar)
     assert ei.value.code == jf.JF_ERR_DEVICE
 
 

@@ -8,7 +8,7 @@ import pytest
 
 import model64
 import oracle_lib
-from conftest import assert_within, sum_tol
+from conftest import assert_within, sum_tol, write_compact_dir
 
 pytestmark = pytest.mark.gpu
 
@@ -372,23 +372,6 @@ def test_full_size_moving_workload_properties(jf, hrir):
         assert np.abs(grouped - mix).max() < 2e-5, G           # |mix| ~ 10
 
 
-def _write_compact_dir(root, hrir):
-    """Re-create the reference's compact KEMAR layout (compact/elev%d/H%de%03da.wav, stereo int16)
-    from the committed table fixture, so the directory loader can be exercised off the build box."""
-    import wave
-    for j, (e, a) in enumerate(model64.table_positions()):
-        if a > 180:
-            continue
-        d = os.path.join(root, f"elev{e}")
-        os.makedirs(d, exist_ok=True)
-        pcm = np.round(hrir[j].T * 32768.0).astype(np.int16)  # [128][2], ch0 = left
-        with wave.open(os.path.join(d, f"H{e}e{a:03d}a.wav"), "wb") as w:
-            w.setnchannels(2)
-            w.setsampwidth(2)
-            w.setframerate(44100)
-            w.writeframes(pcm.tobytes())
-
-
 def test_directory_loader_and_offline_driver(jf, hrir, castanets, tmp_path):
     """jf_engine_create_from_dir on a compact-layout directory, and the plain-C offline driver
     (jf_render: WAV in -> stereo 24-bit WAV out, benchmarkTesting trajectory) against the oracle."""
@@ -397,7 +380,7 @@ def test_directory_loader_and_offline_driver(jf, hrir, castanets, tmp_path):
     import wave
     from conftest import ROOT, scenario_positions
     kemar = str(tmp_path / "compact")
-    _write_compact_dir(kemar, hrir)
+    write_compact_dir(kemar, hrir)
     eng = jf.Engine(256, 512, 1, hrir_dir=kemar)
     ref_table = jf.Engine(256, 512, 1, hrir=hrir).read_table()
     assert np.array_equal(eng.read_table(), ref_table)
@@ -476,7 +459,7 @@ def test_scripted_motion_run_debugmode2(jf, hrir, castanets, tmp_path):
     import wave
     from conftest import ROOT
     kemar = str(tmp_path / "compact")
-    _write_compact_dir(kemar, hrir)
+    write_compact_dir(kemar, hrir)
     B = 256
     # 6.2 s of input: the 2 s excerpt three times over, each pass with another gain and a slow fade, + a bit more
     x = np.concatenate([castanets * g for g in (0.9, 0.6, 0.8)] + [castanets[:9000] * 0.5]).astype(np.float32)
@@ -836,7 +819,7 @@ def test_source_order_contract_when_a_run_resolves_to_single_sources(jf, hrir, c
 def test_whole_bench_under_the_launcher_with_one_rank():
     """bench.py exactly as the driver starts it for N > 1 -- `python -m torch.distributed.run --nproc-per-node=N
     bench.py --gpus N` -- with N = 1, the only N this box has: the ranks are started before anything touches the GPU,
-    the process group is RCCL, the mix goes through the asynchronous reduce, and rank 0 prints the line with
+    the process group is RCCL, the mix goes through the asynchronous reduce, and rank 0 prints the line (--full) with
     `verified` and a CPU baseline on every host core this process may use (the launcher exports OMP_NUM_THREADS=1)."""
     import json
     import socket
@@ -849,7 +832,8 @@ def test_whole_bench_under_the_launcher_with_one_rank():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "OMP_NUM_THREADS")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "2", "--no-pmc"]
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "2", "--no-pmc",
+           "--full"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode(errors="replace")[-3000:]
     line = [l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1]
@@ -875,6 +859,35 @@ def test_whole_bench_under_the_launcher_with_one_rank():
     assert also["reverb_realtime_us"]["calls"] == 1600 and 5 < also["reverb_realtime_us"]["median"] < 200
     st = also["stationary"]
     assert st["verified"] is True and st["value"] > out["value"] and st["config"]["interp_table"]["rows_read_by_the_timed_runs"] == 1
+
+
+def test_plain_bench_line_and_its_dumped_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the headline only (no counters, roofline, CPU baseline or
+    "also" record), K timed steps; --dump-outputs writes the last timed step's mix, and two runs with the same arguments
+    write the same array."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    mixes = []
+    for n in range(2):
+        d = tmp_path / f"run{n}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "2",
+               "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+        assert r.returncode == 0, r.stderr.decode(errors="replace")[-3000:]
+        out = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])
+        assert out["steps"] == 8 and out["warmup"] == 2 and out["n_gpus"] == 1
+        assert out["unit"] == "source-frames/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+        assert out["ms_per_step"] > 0 and out["value"] > 1e10
+        assert abs(out["value"] - 1024 * 128 * 256 / (out["ms_per_step"] * 1e-3)) <= 1e-6 * out["value"]
+        assert not {"roofline", "cpu_baseline", "verified", "also"} & set(out)
+        mix = np.load(d / "mix.npy")
+        assert mix.dtype == np.float32 and mix.shape == (128, 512)
+        assert np.isfinite(mix).all() and np.abs(mix).max() > 1e-3
+        mixes.append(mix)
+    assert np.array_equal(mixes[0], mixes[1])
 
 
 def test_a_live_engine_survives_bad_arguments_and_keeps_working(hrir):
