@@ -76,7 +76,10 @@ typedef struct jf_engine jf_engine;
 
 typedef struct jf_config {
     int frames_per_buffer; /* FRAMES_PER_BUFFER (Universal.cuh:10): 128 or 256 (any multiple of 64 up to 256) */
-    int hrtf_len;          /* HRTF_LEN (Universal.cuh:9): 512 -> PAD_LEN 1024 (Universal.cuh:12) */
+    int hrtf_len;          /* HRTF_LEN (Universal.cuh:9).  PAD_LEN = 2^ceil(log2(B + hrtf_len - 1)) (Universal.cuh:12) must be
+                              1024 or 2048: 513 - B < hrtf_len <= 1025 - B gives PAD_LEN 1024 (512 taps: the reference's
+                              own), 1025 - B < hrtf_len <= 2049 - B gives PAD_LEN 2048 (Nc = 1025 bins; jf_pad_len says
+                              which).  Other lengths (PAD_LEN 512, 4096) are refused with JF_ERR_ARG. */
     int n_sources;         /* num_sources (main.cu:60) */
     int device;            /* HIP device ordinal */
     int max_batch_blocks;  /* capacity of jf_process_batch / jf_batch_run (>= 1) */
@@ -90,8 +93,12 @@ typedef struct jf_config {
  * :248) and the GPUSoundSource constructors (GPUSoundSource.cu:17-71).
  * hrir: [JF_NUM_HRTF][2][taps] float32, row order of the reference loader
  * (elevation-major, azimuth ascending; ear 0 = left), taps <= hrtf_len.
- * The engine builds the unnormalised 513-bin spectra on the GPU and keeps its
+ * The engine builds the unnormalised Nc-bin spectra (Nc = PAD_LEN / 2 + 1: 513 or 1025) on the GPU and keeps its
  * own copies; the caller's buffer is not retained.
+ * JF_ERR_ARG: frames_per_buffer not a multiple of 64 in 64..256, or a hrtf_len whose PAD_LEN is neither 1024 nor 2048
+ * (jf_config.hrtf_len).  An engine at PAD_LEN 2048 runs every entry point of this header with the same semantics, with
+ * three exceptions: it has no convolution reverb (jf_reverb_set_ir returns JF_ERR_ARG), it never builds the
+ * pre-interpolated rows (JF_FLAG_NO_INTERP_TABLE is implied), and its one-block calls go through the batch kernels.
  */
 int jf_engine_create(const jf_config *cfg, const float *hrir, int taps, jf_engine **out);
 
@@ -173,7 +180,9 @@ int jf_table_rows(const jf_engine *e);
  *     (jf_kemar_grid: the rounded steps), so an engine created from it IS jf_engine_create -- the reference's rule and blocks.  Whole-sample delays shift their impulse response; fractional ones
  *     are refused (JF_ERR_IO), and so are sets with other than two receivers or a sampling rate other than 44100 Hz (the
  *     reference's own check of its HRIR files, hrtf_signals.cu:68-75: the distance factor is written for that rate).
- *   jf_engine_create_sofa: the two, then jf_engine_create_grid.  cfg->hrtf_len must hold jf_sofa_taps.
+ *   jf_engine_create_sofa: the two, then jf_engine_create_grid.  cfg->hrtf_len must hold jf_sofa_taps; responses of up to
+ *     2049 - frames_per_buffer taps are accepted (PAD_LEN 2048 above 1025 - frames_per_buffer: jf_config.hrtf_len),
+ *     longer ones are refused with JF_ERR_ARG.
  */
 typedef struct jf_sofa_set {
     int n_measurements;   /* M */

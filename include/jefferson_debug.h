@@ -89,6 +89,7 @@ int jf_debug_set_prep_ahead(jf_engine *e, int on);
  * dist[n][513][2]: D[k] of generateDistanceFactor (kernels.cu:116-125; bin 512: real part only, imaginary 0 --
  * c2r never reads it).  If spectra != NULL: windows[n][1024] -> spectra[n][2][513][2] = Y_ear[k] =
  * sum_t w_t X[k] H[row_t][ear][k] D[k] with X = rfft(window)/N, the filter set of positions[i].
+ * PAD_LEN 1024 engines only (JF_ERR_ARG at PAD_LEN 2048).
  */
 int jf_debug_stage_taps(jf_engine *e, int n, const float *positions, const float *windows, float *dist,
                         float *spectra);
@@ -150,7 +151,7 @@ int jf_debug_reverb_partitions(const jf_engine *e, int *head, int *big, int *big
  * move -- a source that stays reads its row out of the caches (12-18 % faster), one that moves streams 8 KB per block from
  * HBM, and a run in which every source moves every block is 2-5 % slower with the rows than with the weighting of the
  * cached measured rows; measured crossover: a third of the items moving --; calls without a trajectory take them.
- * on != 0 for an engine that may not build them (JF_FLAG_NO_INTERP_TABLE): JF_ERR_STATE.  on == 1 builds them now
+ * on != 0 for an engine that may not build them (JF_FLAG_NO_INTERP_TABLE): JF_ERR_STATE; at PAD_LEN 2048 (never built): JF_ERR_ARG.  on == 1 builds them now
  * (JF_ERR_NOMEM without room for them), on == 2 leaves that to the first run that takes them.  Results are bit-identical
  * whatever the choice (JF_INTERP_TABLE=0/1/2 in the environment sets it for every engine of a process). */
 int jf_debug_set_interp_table(jf_engine *e, int on);

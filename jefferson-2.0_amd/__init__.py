@@ -626,7 +626,7 @@ class Engine:
         return lib().jf_table_rows(self.h)
 
     def read_table(self):
-        t = np.zeros((self.table_rows(), 2, NC, 2), np.float32)
+        t = np.zeros((self.table_rows(), 2, self.N // 2 + 1, 2), np.float32)  # Nc bins per ear
         self._chk(lib().jf_debug_read_table(self.h, _fp(t)))
         return t.view(np.complex64)[..., 0]
 
@@ -652,8 +652,8 @@ class Engine:
         return n
 
     def read_table_rows(self, first_row, n):
-        """n rows in the device layout: [n][512][4] = {L.re, L.im, R.re, R.im} (bin 0: {L[0], L[512], R[0], R[512]})."""
-        t = np.zeros((n, 512, 4), np.float32)
+        """n rows in the device layout: [n][N/2][4] = {L.re, L.im, R.re, R.im} (bin 0: {L[0], L[N/2], R[0], R[N/2]})."""
+        t = np.zeros((n, self.N // 2, 4), np.float32)
         self._chk(lib().jf_debug_read_table_rows(self.h, int(first_row), int(n), _fp(t)))
         return t
 
@@ -670,7 +670,7 @@ class Engine:
     def rfft_device(self, windows):
         windows = np.ascontiguousarray(windows, np.float32)
         n = windows.shape[0]
-        assert windows.shape[1] == PAD_LEN
-        sp = np.zeros((n, NC, 2), np.float32)
+        assert windows.shape[1] == self.N  # the engine's PAD_LEN (1024 or 2048)
+        sp = np.zeros((n, self.N // 2 + 1, 2), np.float32)
         self._chk(lib().jf_debug_rfft_device(self.h, n, _fp(windows), _fp(sp)))
         return sp.view(np.complex64)[..., 0]

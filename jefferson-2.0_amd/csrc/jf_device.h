@@ -94,7 +94,7 @@ struct ItemDesc {
     float w_new[4];
     int rows_old[4];
     float w_old[4];
-    unsigned long long c_fix;  // frac(fsvs * r' / 513) * 2^64: distance-delay phase step per bin, in turns
+    unsigned long long c_fix;  // frac(fsvs * r' / Nc) * 2^64: distance-delay phase step per bin, in turns (Nc = 513 or 1025)
     float inv_frac;  // 1 / (1 + fsvs r'^2)
     int n_new;       // 1, 2 or 4 terms; 0 = position not interpolable -> silence
     int n_old;       // 0 = no crossfade

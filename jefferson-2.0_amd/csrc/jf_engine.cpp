@@ -33,10 +33,77 @@ int ensure_interp_rows(jf_engine *e) {
 
 
 
+// PAD_LEN 2048: prep -> fused2048_kernel -> mix on the engine stream.  No reverb stage (refused at this length), no
+// pre-interpolated rows, no descriptors prepared ahead: every run prepares its own window.
+static int run_blocks_2048(jf_engine *e, const float *d_pos, int K, float *d_mix_out) {
+    const int p = e->cur;
+    EventPair *ep = nullptr, *ef = nullptr, *em = nullptr;
+    const bool timed = e->profiling && (e->profile_stride <= 1 || e->profile_calls++ % e->profile_stride == 0);
+    e->timed_now = timed;
+    if (timed) {
+        ef = next_events(e, e->ev_fused);
+        if (!ef) return fail(e, JF_ERR_DEVICE, "hipEventCreate failed");
+    }
+    if (e->profiling >= 2 && timed) {
+        ep = next_events(e, e->ev_prep);
+        em = next_events(e, e->ev_mix);
+        if (!ep || !em) return fail(e, JF_ERR_DEVICE, "hipEventCreate failed");
+    }
+    // Sources a workgroup sums as spectra before its inverse transforms: as many as leave about four units for every
+    // compute unit (a unit is one workgroup of four waves).  G must divide S.
+    const long long n_items = (long long)K * e->S;
+    int G = 1;
+    for (const int g : {16, 8, 4, 2})
+        if (e->S % g == 0 && n_items / g >= 1024) {
+            G = g;
+            break;
+        }
+    if (e->src_group > 0 && e->S % e->src_group == 0) G = e->src_group;
+    e->ahead.valid = false;
+    e->last_prep_skipped = false;
+    e->last_rows = false;
+    e->last_mix_prep = e->last_fused_prep = false;
+    const int mode_now = kernel_mode(e);
+    if (ep) JF_HIP(e, hipEventRecord(ep->a, e->stream));
+    JF_HIP(e, launch_prep(e->rt, mode_now, d_pos, e->d_state[p], e->d_desc, e->S, K, 0, e->Nc, e->stream));
+    if (ep) JF_HIP(e, hipEventRecord(ep->b, e->stream));
+    FusedParams P;
+    P.htab = e->d_htab;
+    P.tw = e->d_tw2048;
+    P.desc = e->d_desc;
+    P.sigs = e->d_sigs;
+    P.st_in = e->d_state[p];
+    P.st_out = e->d_state[p ^ 1];
+    P.hist_in = e->d_hist[p];
+    P.hist_out = e->d_hist[p ^ 1];
+    P.pos = d_pos;
+    P.partial = e->d_partial;
+    P.S = e->S;
+    P.K = K;
+    P.B = e->B;
+    P.G = G;
+    P.mode = mode_now;
+    P.order = e->d_order;
+    P.err = e->hd_err;
+    P.rt = e->rt;
+    e->last_group = G;
+    if (ef) JF_HIP(e, hipEventRecord(ef->a, e->stream));
+    JF_HIP(e, launch_fused2048(P, e->stream));
+    if (ef) JF_HIP(e, hipEventRecord(ef->b, e->stream));
+    if (em) JF_HIP(e, hipEventRecord(em->a, e->stream));
+    JF_HIP(e, launch_mix(e->d_partial, d_mix_out, e->S / G, K, e->B, e->stream));
+    if (em) JF_HIP(e, hipEventRecord(em->b, e->stream));
+    if (timed) e->ev_used++;
+    e->cur = p ^ 1;
+    e->last_rt = false;
+    return JF_OK;
+}
+
 // prep -> [reverb] -> fused -> mix on the engine stream, K blocks starting at d_pos.
 // first_block: index of d_pos's first block in the uploaded trajectory (jf_batch_run), -1 for positions from elsewhere.
 int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int first_block) {
     if (device_fault(e)) return fail(e, JF_ERR_DEVICE, kHandOffMsg);  // fatal: see device_fault
+    if (e->N != kN) return run_blocks_2048(e, d_pos, K, d_mix_out);
     {
         const int rc = rv_ahead_discard(e);  // (a stage launched ahead by a one-block call: this call does its own)
         if (rc) return rc;
@@ -95,7 +162,7 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
     e->last_prep_skipped = have;
     if (have) std::swap(e->d_desc, e->d_desc_ahead);
     if (ep) JF_HIP(e, hipEventRecord(ep->a, e->stream));
-    if (!have) JF_HIP(e, launch_prep(e->rt, mode_now, d_pos, e->d_state[p], e->d_desc, e->S, K, canon, e->stream));
+    if (!have) JF_HIP(e, launch_prep(e->rt, mode_now, d_pos, e->d_state[p], e->d_desc, e->S, K, canon, kNc, e->stream));
     if (ep) JF_HIP(e, hipEventRecord(ep->b, e->stream));
     {
         const int rc = run_reverb_stage(e, p, K);
@@ -178,7 +245,7 @@ int reset_sources(jf_engine *e, int src) {
     const size_t s0 = src < 0 ? 0 : (size_t)src, ns = src < 0 ? (size_t)e->S : 1;
     const int p = e->cur;
     quiesce_side(e);  // (what it has left in the fut ring is zeroed below with the rest)
-    JF_HIP(e, hipMemsetAsync(e->d_hist[p] + s0 * kN, 0, sizeof(float) * kN * ns, e->stream));
+    JF_HIP(e, hipMemsetAsync(e->d_hist[p] + s0 * e->N, 0, sizeof(float) * e->N * ns, e->stream));
     JF_HIP(e, hipMemsetAsync(e->d_state[p] + s0, 0, sizeof(SrcState) * ns, e->stream));
     if (e->rv_P > 0) {
         const size_t B = (size_t)e->B;
@@ -210,6 +277,7 @@ void destroy_engine(jf_engine *e) {
         if (p) (void)hipFree(p);
     (void)hipFree(e->d_htab);
     (void)hipFree(e->d_tw);
+    (void)hipFree(e->d_tw2048);
     (void)hipFree(e->d_twpack);
     (void)hipFree(e->d_sigs);
     (void)hipFree(e->d_zero);
@@ -249,9 +317,13 @@ int create_engine(const jf_config *cfg, const RingTable *grid, const float *hrir
     if (B < 64 || B > 256 || B % 64) return fail(nullptr, JF_ERR_ARG, "frames_per_buffer must be 64, 128, 192 or 256");
     if (cfg->hrtf_len <= 0 || taps <= 0 || taps > cfg->hrtf_len)
         return fail(nullptr, JF_ERR_ARG, "need 0 < taps <= hrtf_len");
-    // PAD_LEN = 2^ceil(log2(B + L - 1)) (Universal.cuh:12); the kernels are built for 1024
+    // PAD_LEN = 2^ceil(log2(B + L - 1)) (Universal.cuh:12); kernels exist for 1024 (jf_kernels.hip) and 2048
+    // (jf_kernels2048.hip): 1 < B + L - 1 <= 2048 with B <= 256, i.e. hrtf_len <= 2049 - B
+    if (cfg->hrtf_len > 2049 - B)
+        return fail(nullptr, JF_ERR_ARG, "frames_per_buffer + hrtf_len - 1 must pad to 1024 or 2048 (hrtf_len <= 2049 - frames_per_buffer)");
     const int pad = (int)pow(2, ceil(log2((double)(B + cfg->hrtf_len - 1))));
-    if (pad != kN) return fail(nullptr, JF_ERR_ARG, "frames_per_buffer + hrtf_len - 1 must pad to 1024");
+    if (pad != kN && pad != 2 * kN)
+        return fail(nullptr, JF_ERR_ARG, "frames_per_buffer + hrtf_len - 1 must pad to 1024 or 2048 (hrtf_len >= 1025 - frames_per_buffer)");
     if (cfg->n_sources <= 0) return fail(nullptr, JF_ERR_ARG, "n_sources must be positive");
     if (cfg->max_batch_blocks <= 0) return fail(nullptr, JF_ERR_ARG, "max_batch_blocks must be positive");
     if (cfg->flags & ~(JF_FLAG_CORRECTED_INTERPOLATION | JF_FLAG_NO_INTERP_TABLE))
@@ -275,7 +347,9 @@ int create_engine(const jf_config *cfg, const RingTable *grid, const float *hrir
     e->B = B;
     e->S = cfg->n_sources;
     e->maxK = cfg->max_batch_blocks;
-    const size_t S = (size_t)e->S, K = (size_t)e->maxK;
+    e->N = pad;
+    e->Nc = pad / 2 + 1;
+    const size_t S = (size_t)e->S, K = (size_t)e->maxK, N = (size_t)e->N;
     int rc = JF_OK;
     int prev_dev = -1;
     (void)hipGetDevice(&prev_dev);
@@ -300,18 +374,19 @@ int create_engine(const jf_config *cfg, const RingTable *grid, const float *hrir
                 (void)hipGetLastError();
         }
         // (nothing of the engine's behaviour is read from the environment: jefferson_debug.h's setters are the overrides)
-        e->interp_avail = !(cfg->flags & JF_FLAG_NO_INTERP_TABLE);
+        // (never at PAD_LEN 2048: 773 MB of rows; JF_FLAG_NO_INTERP_TABLE is implied there)
+        e->interp_avail = !(cfg->flags & JF_FLAG_NO_INTERP_TABLE) && e->N == kN;
         e->interp_use = e->interp_avail ? 2 : 0;
         // the 710 measured rows only; the pre-interpolated ones come with the first run that takes them (ensure_interp_rows)
         e->rt = grid ? *grid : ring_table();
-        JF_HIP(e, hipMalloc(&e->d_htab, sizeof(float4) * (size_t)e->rt.n_rows * 512));
+        JF_HIP(e, hipMalloc(&e->d_htab, sizeof(float4) * (size_t)e->rt.n_rows * (N / 2)));
         JF_HIP(e, hipMalloc(&e->d_tw, sizeof(float2) * 1024));
         JF_HIP(e, hipMalloc(&e->d_sigs, sizeof(SrcSignal) * S));
         for (int i = 0; i < 2; i++) {
             JF_HIP(e, hipMalloc(&e->d_state[i], sizeof(SrcState) * S));
-            JF_HIP(e, hipMalloc(&e->d_hist[i], sizeof(float) * S * kN));
+            JF_HIP(e, hipMalloc(&e->d_hist[i], sizeof(float) * S * N));
             JF_HIP(e, hipMemsetAsync(e->d_state[i], 0, sizeof(SrcState) * S, e->stream));
-            JF_HIP(e, hipMemsetAsync(e->d_hist[i], 0, sizeof(float) * S * kN, e->stream));
+            JF_HIP(e, hipMemsetAsync(e->d_hist[i], 0, sizeof(float) * S * N, e->stream));
         }
         JF_HIP(e, hipMalloc(&e->d_desc, sizeof(ItemDesc) * S * K));
         JF_HIP(e, hipMalloc(&e->d_desc_ahead, sizeof(ItemDesc) * S * K));
@@ -348,9 +423,9 @@ int create_engine(const jf_config *cfg, const RingTable *grid, const float *hrir
         memset(e->h_err, 0, sizeof(int) * 4 + 65536);
         JF_HIP(e, hipHostGetDevicePointer((void **)&e->hd_err, e->h_err, 0));
         e->d_signal.assign(S, nullptr);
-        JF_HIP(e, hipMalloc(&e->d_zero, sizeof(float) * kN));
-        JF_HIP(e, hipMemsetAsync(e->d_zero, 0, sizeof(float) * kN, e->stream));
-        e->h_sigs.assign(S, SrcSignal{e->d_zero, kN, 0});
+        JF_HIP(e, hipMalloc(&e->d_zero, sizeof(float) * N));
+        JF_HIP(e, hipMemsetAsync(e->d_zero, 0, sizeof(float) * N, e->stream));
+        e->h_sigs.assign(S, SrcSignal{e->d_zero, e->N, 0});
         JF_HIP(e, h2d(e, e->d_sigs, e->h_sigs.data(), sizeof(SrcSignal) * S));
         // SoundSource::SoundSource() defaults (SoundSource.cu:3-16)
         e->pos.assign(S, HostPos{0.0f, 0.0f, 0.5f, 0.0f, 0.0f, 0.5f});
@@ -376,13 +451,25 @@ int create_engine(const jf_config *cfg, const RingTable *grid, const float *hrir
             for (int k = 0; k < 8; k++) pack[kTwWB + 8 * r + k] = tw[(16 * r * k) & 1023];
         JF_HIP(e, hipMalloc(&e->d_twpack, sizeof(float2) * kTwPack));
         JF_HIP(e, h2d(e, e->d_twpack, pack.data(), sizeof(float2) * kTwPack));
+        if (e->N != kN) {  // the 2048-point transforms' table: exp(+2 pi i j / 2048) from double
+            std::vector<float2> tw2(e->N);
+            for (int j = 0; j < e->N; j++) {
+                const double a = 2.0 * 3.14159265358979323846264338327950288 * j / (double)e->N;
+                tw2[j] = make_float2((float)cos(a), (float)sin(a));
+            }
+            JF_HIP(e, hipMalloc(&e->d_tw2048, sizeof(float2) * e->N));
+            JF_HIP(e, h2d(e, e->d_tw2048, tw2.data(), sizeof(float2) * e->N));
+        }
 
         // HRTF spectra on the GPU (read_hrtf_signals + transform_hrtfs)
         float *d_hrir = nullptr;
         const size_t hb = sizeof(float) * (size_t)e->rt.n_rows * 2 * (size_t)taps;
         JF_HIP(e, hipMalloc(&d_hrir, hb));
         hipError_t s1 = h2d(e, d_hrir, hrir, hb);
-        hipError_t s2 = s1 == hipSuccess ? launch_table_build(d_hrir, e->rt.n_rows, taps, e->d_twpack, e->d_htab, e->stream) : s1;
+        hipError_t s2 = s1;
+        if (s1 == hipSuccess)
+            s2 = e->N == kN ? launch_table_build(d_hrir, e->rt.n_rows, taps, e->d_twpack, e->d_htab, e->stream)
+                            : launch_table2048_build(d_hrir, e->rt.n_rows, taps, e->d_tw2048, e->d_htab, e->stream);
         hipError_t s3 = s2 == hipSuccess ? hipStreamSynchronize(e->stream) : s2;
         (void)hipFree(d_hrir);
         JF_HIP(e, s3);
@@ -554,7 +641,7 @@ void jf_engine_destroy(jf_engine *e) { destroy_engine(e); }
 const char *jf_last_error(const jf_engine *e) { return e ? e->err.c_str() : g_create_error.c_str(); }
 
 int jf_frames_per_buffer(const jf_engine *e) { return e ? e->B : JF_ERR_ARG; }
-int jf_pad_len(const jf_engine *e) { return e ? kN : JF_ERR_ARG; }
+int jf_pad_len(const jf_engine *e) { return e ? e->N : JF_ERR_ARG; }
 int jf_num_sources(const jf_engine *e) { return e ? e->S : JF_ERR_ARG; }
 int jf_table_rows(const jf_engine *e) { return e ? e->rt.n_rows : JF_ERR_ARG; }
 
@@ -576,8 +663,8 @@ int jf_source_set_signal(jf_engine *e, int src, const float *mono, size_t n) {
     if (n) {
         const float *src_host = mono;
         std::vector<float> tiled;
-        if (n < (size_t)kN) {
-            const size_t reps = ((size_t)kN + n - 1) / n;
+        if (n < (size_t)e->N) {
+            const size_t reps = ((size_t)e->N + n - 1) / n;
             tiled.resize(reps * n);
             for (size_t r = 0; r < reps; r++) memcpy(tiled.data() + r * n, mono, sizeof(float) * n);
             src_host = tiled.data();
@@ -592,7 +679,7 @@ int jf_source_set_signal(jf_engine *e, int src, const float *mono, size_t n) {
     }
     if (e->d_signal[src]) (void)hipFree(e->d_signal[src]);
     e->d_signal[src] = d_new;
-    e->h_sigs[src] = n ? SrcSignal{d_new, (int)n_dev, 0} : SrcSignal{e->d_zero, kN, 0};
+    e->h_sigs[src] = n ? SrcSignal{d_new, (int)n_dev, 0} : SrcSignal{e->d_zero, e->N, 0};
     JF_HIP(e, h2d(e, e->d_sigs + src, &e->h_sigs[src], sizeof(SrcSignal)));
     const int zero = 0;  // count = 0 (cudaPart.cu:198-199 run with a fresh source)
     if (e->rv_P > 0)  // the play position of the dry signal lives in the reverb stage
@@ -709,7 +796,7 @@ int jf_submit_block(jf_engine *e) {
         JF_HIP(e, hipMemsetAsync(e->d_mix, 0, sizeof(float) * 2 * e->B, e->stream));
     } else {
         snapshot_positions(e, e->h_pos_pinned);
-        if (e->S <= e->rt_max_sources && !e->profiling) {
+        if (e->S <= e->rt_max_sources && !e->profiling && e->N == kN) {  // (PAD_LEN 2048: the batch path with K = 1)
             // few sources: ONE launch does descriptors, spatialisation and mix, reading the positions
             // from and writing the stereo block to pinned host memory -- no copies, one sync
             const int p = e->cur;

@@ -166,6 +166,7 @@ int jf_debug_set_interp_table(jf_engine *e, int on) {
     DeviceGuard bind(e);
     if (!e) return JF_ERR_ARG;
     if (on < 0 || on > 2) return fail(e, JF_ERR_ARG, "0 = never, 1 = always, 2 = decided per run");
+    if (on && e->N != kN) return fail(e, JF_ERR_ARG, "no pre-interpolated rows at PAD_LEN 2048");
     if (on && !e->interp_avail) return fail(e, JF_ERR_STATE, "this engine was created without the pre-interpolated rows");
     e->interp_use = on;  // the mode word of the next run changes with it: descriptors prepared ahead no longer match
     if (on == 1) {       // "always" builds them now (a run under "per run" builds them when it first takes them)
@@ -205,8 +206,9 @@ int jf_debug_read_table_rows(jf_engine *e, int first_row, int n, float *out) {
     }
     const int total = e ? e->rt.n_rows + (e->interp_built ? kInterpRows : 0) : 0;
     if (!e || !out || n <= 0 || first_row < 0 || first_row > total - n) return fail(e, JF_ERR_ARG, "rows outside the table");
+    const size_t row = (size_t)e->N / 2;
     JF_HIP(e, hipStreamSynchronize(e->stream));
-    JF_HIP(e, hipMemcpy(out, e->d_htab + (size_t)first_row * 512, sizeof(float4) * 512 * (size_t)n, hipMemcpyDeviceToHost));
+    JF_HIP(e, hipMemcpy(out, e->d_htab + (size_t)first_row * row, sizeof(float4) * row * (size_t)n, hipMemcpyDeviceToHost));
     return JF_OK;
     });
 }
@@ -290,22 +292,23 @@ int jf_debug_read_table(jf_engine *e, float *out) {
     return jf_guard([&]() -> int {
     DeviceGuard bind(e);
     if (!e || !out) return JF_ERR_ARG;
-    std::vector<float4> h((size_t)e->rt.n_rows * 512);
+    const int H = e->N / 2, Nc = e->Nc;  // device row: H float4 (bin 0 carries bin H), reference row: Nc complex per ear
+    std::vector<float4> h((size_t)e->rt.n_rows * H);
     JF_HIP(e, hipStreamSynchronize(e->stream));
     JF_HIP(e, hipMemcpy(h.data(), e->d_htab, sizeof(float4) * h.size(), hipMemcpyDeviceToHost));
     for (int j = 0; j < e->rt.n_rows; j++) {
-        float *L = out + ((size_t)j * 2 + 0) * kNc * 2;
-        float *R = out + ((size_t)j * 2 + 1) * kNc * 2;
-        const float4 *row = h.data() + (size_t)j * 512;
+        float *L = out + ((size_t)j * 2 + 0) * Nc * 2;
+        float *R = out + ((size_t)j * 2 + 1) * Nc * 2;
+        const float4 *row = h.data() + (size_t)j * H;
         L[0] = row[0].x;
         L[1] = 0.0f;
-        L[1024] = row[0].y;
-        L[1025] = 0.0f;
+        L[2 * H] = row[0].y;
+        L[2 * H + 1] = 0.0f;
         R[0] = row[0].z;
         R[1] = 0.0f;
-        R[1024] = row[0].w;
-        R[1025] = 0.0f;
-        for (int k = 1; k < 512; k++) {
+        R[2 * H] = row[0].w;
+        R[2 * H + 1] = 0.0f;
+        for (int k = 1; k < H; k++) {
             L[2 * k] = row[k].x;
             L[2 * k + 1] = row[k].y;
             R[2 * k] = row[k].z;
@@ -355,12 +358,16 @@ int jf_debug_rfft_device(jf_engine *e, int n, const float *windows, float *spect
     float *d_w = nullptr;
     float2 *d_s = nullptr;
     auto body = [&]() -> int {
-        JF_HIP(e, hipMalloc(&d_w, sizeof(float) * (size_t)n * kN));
-        JF_HIP(e, hipMalloc(&d_s, sizeof(float2) * (size_t)n * kNc));
-        JF_HIP(e, h2d(e, d_w, windows, sizeof(float) * (size_t)n * kN));
-        JF_HIP(e, launch_rfft_debug(d_w, n, e->d_twpack, d_s, e->stream));
+        const size_t N = (size_t)e->N, Nc = (size_t)e->Nc;
+        JF_HIP(e, hipMalloc(&d_w, sizeof(float) * (size_t)n * N));
+        JF_HIP(e, hipMalloc(&d_s, sizeof(float2) * (size_t)n * Nc));
+        JF_HIP(e, h2d(e, d_w, windows, sizeof(float) * (size_t)n * N));
+        if (e->N == kN)
+            JF_HIP(e, launch_rfft_debug(d_w, n, e->d_twpack, d_s, e->stream));
+        else
+            JF_HIP(e, launch_rfft2048_debug(d_w, n, e->d_tw2048, d_s, e->stream));
         JF_HIP(e, hipStreamSynchronize(e->stream));
-        JF_HIP(e, hipMemcpy(spectra, d_s, sizeof(float2) * (size_t)n * kNc, hipMemcpyDeviceToHost));
+        JF_HIP(e, hipMemcpy(spectra, d_s, sizeof(float2) * (size_t)n * Nc, hipMemcpyDeviceToHost));
         return JF_OK;
     };
     int rc = body();
@@ -432,6 +439,7 @@ const char *jf_debug_last_kernels(jf_engine *e) {
                 k += ";reverb_big_fft_kernel<" + b1 + ",1>";
             }
         }
+        else if (e->N != kN) k += "fused2048_kernel<" + nb + ">" + mix_name;
         else k += std::string(e->last_group > 1 ? "fused_pair_kernel<" : "fused_block_kernel<") + nb +
                   (e->last_fused_prep ? ">+prep" : ">") + (e->last_mix_prep ? ";mix_prep_kernel" : mix_name);
         e->kernels = k;
@@ -463,6 +471,7 @@ int jf_debug_stage_taps(jf_engine *e, int n, const float *positions, const float
     return jf_guard([&]() -> int {
     DeviceGuard bind(e);
     if (!e || n <= 0 || !positions || !dist || (spectra && !windows)) return JF_ERR_ARG;
+    if (e->N != kN) return fail(e, JF_ERR_ARG, "jf_debug_stage_taps: PAD_LEN 1024 engines only");
     float *d_p = nullptr, *d_w = nullptr;
     float2 *d_d = nullptr, *d_s = nullptr;
     auto body = [&]() -> int {

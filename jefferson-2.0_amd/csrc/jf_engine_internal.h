@@ -35,7 +35,7 @@ hipError_t launch_rfft_debug(const float *d_win, int n, const float2 *d_tw, floa
 hipError_t launch_interp_debug(const RingTable &rt, const float *d_ele, const float *d_azi, int *d_rows,
                                float *d_w, int *d_nt, int n, int corrected, hipStream_t st);
 hipError_t launch_prep(const RingTable &rt, int mode, const float *d_pos, const SrcState *d_st, ItemDesc *d_desc,
-                       int S, int K, int canon, hipStream_t st);
+                       int S, int K, int canon, int nc, hipStream_t st);
 hipError_t launch_fused(const FusedParams &P, int max_wgs, hipStream_t st);
 hipError_t fused_resident_workgroups(int nb, int kind, int *out);
 hipError_t launch_stage_debug(const RingTable &rt, int mode, const float *d_pos, const float *d_win, int n,
@@ -57,6 +57,11 @@ hipError_t launch_reverb_big_side(const ReverbBigParams *transforms, const Rever
 hipError_t launch_reverb_big_ir(const float *d_ir, int n_ir, int t0, int P1, int B1, float scale, const float2 *d_tw1,
                                 float2 *d_hspec1, hipStream_t st);
 int kernels_build_kind();
+// the PAD_LEN 2048 path (jf_kernels2048.hip)
+hipError_t launch_fused2048(const FusedParams &P, hipStream_t st);
+hipError_t launch_table2048_build(const float *d_hrir, int n_rows, int taps, const float2 *d_tw2048, float4 *d_htab,
+                                  hipStream_t st);
+hipError_t launch_rfft2048_debug(const float *d_win, int n, const float2 *d_tw2048, float2 *d_spec, hipStream_t st);
 }  // namespace jf
 
 using namespace jf;
@@ -82,10 +87,15 @@ struct jf_engine {
     jf_config cfg{};
     int own_mix_blocks = 0;  // blocks the last jf_batch_run left in d_mix (0: it wrote to the caller's buffer, failed or has not run)
     int B = 0, S = 0, maxK = 0;
+    // PAD_LEN of this engine's configuration (2^ceil(log2(B + hrtf_len - 1)), Universal.cuh:9-12) and its Nc = N / 2 + 1.
+    // kN (1024): the kernels of jf_kernels.hip; 2048: those of jf_kernels2048.hip -- no real-time kernel, no reverb,
+    // no pre-interpolated rows (run_blocks_2048)
+    int N = kN, Nc = kNc;
+    float2 *d_tw2048 = nullptr;  // N = 2048: exp(+2 pi i j / 2048), j < 2048, from double
     hipStream_t stream = nullptr;
     std::string err;
 
-    float4 *d_htab = nullptr;
+    float4 *d_htab = nullptr;  // [n_rows][N / 2] (jf_device.h; jf_kernels2048.hip at N = 2048)
     // The kInterpRows pre-interpolated rows (jf_device.h; 386 MB behind the 710 measured rows) are built LAZILY: by the first
     // run whose policy takes them (run_blocks), or when jf_debug_set_interp_table(e, 1) / a read of those rows asks -- never for
     // an engine that only ever runs sources that move every block, and not for the eight shards of a job on one device.
@@ -103,7 +113,7 @@ struct jf_engine {
     float2 *d_tw = nullptr;
     float2 *d_twpack = nullptr;
     SrcSignal *d_sigs = nullptr;
-    float *d_zero = nullptr;  // PAD_LEN zeros: the "signal" of a source without one
+    float *d_zero = nullptr;  // N zeros: the "signal" of a source without one
     SrcState *d_state[2] = {nullptr, nullptr};
     float *d_hist[2] = {nullptr, nullptr};
     ItemDesc *d_desc = nullptr;

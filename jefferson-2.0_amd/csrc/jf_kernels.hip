@@ -34,6 +34,7 @@
 #include "jf_device.h"
 #include "jf_experiments.h"
 #include "jf_packed.h"
+#include "jf_phase.h"
 
 namespace jf {
 
@@ -401,39 +402,8 @@ JF_DEV void ifft1024_lastq_wave(float2 (&v)[16], float2 (&out)[NOUT], float2 *bu
 }
 
 // ------------------------------------------------------- distance factor --
-// D[k] = exp(-2 pi i * fsvs r' k / 513) * inv_frac (kernels.cu:116-125).  The phase is
-// exact integer arithmetic: c = frac(fsvs r'/513) as a 64-bit fraction of a turn, phase(k) =
-// k*c mod 1 (top 32 bits kept, 1.5e-9 rad), split into the nearest quarter turn and a
-// remainder |f| <= 1/2 quarter turn that goes through float minimax kernels with an exactly
-// represented argument (two floats).
-// p = the phase word.  Branch-free: the quarter only swaps sin/cos and sets sign bits.
-JF_DEV float2 distance_from_phase(unsigned p, float inv_frac) {
-    const unsigned p2 = p + 0x20000000u;  // + 1/8 turn: round to the nearest quarter
-    const int rem = (int)(p2 & 0x3FFFFFFFu) - 0x20000000;
-    // x + xl = remainder in radians, |x| <= pi/4, to ~1e-16: the 30-bit remainder does not fit a float (rf rounds, rl
-    // is what it drops) and neither does pi/2 / 2^30 (Kh + Kl); xl collects both residuals with exact FMAs
-    constexpr float Kh = 0x1.921fb6p-30f, Kl = -0x1.777a5cp-55f;
-    const float rf = (float)rem;
-    const float rl = (float)(rem - (int)rf);
-    const float x = rf * Kh;
-    const float xl = fmaf(rl, Kh, fmaf(rf, Kl, fmaf(rf, Kh, -x)));
-    const float x2 = x * x;
-    // Cephes sinf/cosf kernels, ~1 ulp, then the first-order correction for xl
-    const float s0 = x + x * x2 * (-1.6666654611e-1f + x2 * (8.3321608736e-3f + x2 * -1.9515295891e-4f));
-    const float c0 = 1.0f - 0.5f * x2 +
-                     x2 * x2 * (4.166664568298827e-2f + x2 * (-1.388731625493765e-3f + x2 * 2.443315711809948e-5f));
-    const float s = fmaf(xl, c0, s0);
-    const float c = fmaf(-xl, s0, c0);
-    // quarter q = p2 >> 30: (cos, sin) = (c, s), (-s, c), (-c, -s), (s, -c); the result is (cos, -sin) * inv_frac
-    const bool odd = (p2 & 0x40000000u) != 0;
-    const float cc = odd ? s : c, ss = odd ? c : s;
-    const unsigned neg_re = (p2 + 0x40000000u) & 0x80000000u;  // quarters 1, 2
-    const unsigned neg_im = ~p2 & 0x80000000u;                 // quarters 0, 1
-    return make_float2(__uint_as_float(__float_as_uint(cc * inv_frac) ^ neg_re),
-                       __uint_as_float(__float_as_uint(ss * inv_frac) ^ neg_im));
-}
-
-// The same from the FFT's own twiddle table (LDS, kTwU: exp(+2 pi i j / 1024), j = 0..511, rounded from double):
+// D[k] = exp(-2 pi i * fsvs r' k / 513) * inv_frac: distance_from_phase (jf_phase.h), or the same from the FFT's own
+// twiddle table (LDS, kTwU: exp(+2 pi i j / 1024), j = 0..511, rounded from double):
 // the phase is split into the nearest 1/1024 turn and a remainder |x| <= pi/1024, and the table value is corrected by
 // cos x - 1 = -x^2/2 (next term 4e-12) and sin x = x - x^3/6 (next term 2e-15) as small addends to it -- one rounding
 // on top of the table's, the argument needs no second float (x is known to 1.8e-10), 20 instructions and one LDS read
@@ -1068,7 +1038,7 @@ JF_DEV void ear_sums_to_z(const c2 (&sL)[4], const c2 (&sR)[4], bool special, c2
 #endif
 
 JF_DEV void prep_body(const RingTable &rt, int mode, const float *__restrict__ pos, const SrcState *__restrict__ st,
-                      ItemDesc *__restrict__ desc, int S, int K, int canon, int tid, ItemDesc *stage);
+                      ItemDesc *__restrict__ desc, int S, int K, int canon, int tid, ItemDesc *stage, double inv_nc);
 
 // ROWS: the instantiation for launches whose descriptors may carry pre-interpolated rows (ItemDesc flags bit 2); the other
 // one does not contain that path at all (its presence alone costs the per-block weighting path registers and ~4 % more
@@ -1114,7 +1084,7 @@ __global__ JF_FUSED_BOUNDS void fused_pair_kernel(const FusedParams Pin) {
         // 10 us chain of the index/weight rule hides in the kernel's tail instead of standing behind it as a launch.
         static_assert(sizeof(s_pair) >= sizeof(ItemDesc) * 32 * kWavesPerWg, "staging of 32 records per wave");
         prep_body(Pin.rt, Pin.mode, Pin.prep_pos, nullptr, Pin.prep_desc, Pin.S, Pin.prep_K, Pin.prep_canon,
-                  ((int)blockIdx.x - Pin.n_pair_wgs) * (64 * kWavesPerWg) + tid, reinterpret_cast<ItemDesc *>(s_pair));
+                  ((int)blockIdx.x - Pin.n_pair_wgs) * (64 * kWavesPerWg) + tid, reinterpret_cast<ItemDesc *>(s_pair), 1.0 / kNc);
         return;
     }
     for (int j = tid; j < kTwPack; j += 64 * kWavesPerWg) s_tw[j] = Pin.tw[j];
@@ -1750,7 +1720,7 @@ JF_DEV void make_desc(const RingTable &rt, int mode, const float *p /* ele, azi,
 // scattered 64 pieces of 16 B over 32 records 88 B apart, and those stores, not the arithmetic, were most of the kernel's
 // time (13 us for 131 072 items against 5 us for the chain of one wave).
 JF_DEV void prep_body(const RingTable &rt, int mode, const float *__restrict__ pos, const SrcState *__restrict__ st,
-                      ItemDesc *__restrict__ desc, int S, int K, int canon, int tid, ItemDesc *stage) {
+                      ItemDesc *__restrict__ desc, int S, int K, int canon, int tid, ItemDesc *stage, double inv_nc) {
     const int item = tid >> 1;
     const bool old_half = tid & 1;
     const bool live = item < S * K;  // both lanes of a pair agree; no early return before the shuffles
@@ -1843,7 +1813,7 @@ JF_DEV void prep_body(const RingTable &rt, int mode, const float *__restrict__ p
         const float frac = 1 + fsvs * (float)((double)r * (double)r);
         {
             // phase step per bin in turns, as a 64-bit fraction (double keeps 52+ fractional bits here)
-            double c = (double)fsvs * (double)r * (1.0 / 513.0);  // 1e-16 relative: far below the 2^-32 turn the phase word keeps
+            double c = (double)fsvs * (double)r * inv_nc;  // 1e-16 relative: far below the 2^-32 turn the phase word keeps
             c -= floor(c);
             d.c_fix = (unsigned long long)(c * 18446744073709551616.0);
         }
@@ -1942,9 +1912,9 @@ JF_DEV void prep_body(const RingTable &rt, int mode, const float *__restrict__ p
 constexpr int kPrepThreads = 256;
 __global__ __launch_bounds__(kPrepThreads) void prep_kernel(const RingTable rt, int mode, const float *__restrict__ pos,
                                                             const SrcState *__restrict__ st, ItemDesc *__restrict__ desc,
-                                                            int S, int K, int canon) {
+                                                            int S, int K, int canon, int nc) {
     __shared__ ItemDesc stage[kPrepThreads / 2];
-    prep_body(rt, mode, pos, st, desc, S, K, canon, blockIdx.x * kPrepThreads + threadIdx.x, stage);
+    prep_body(rt, mode, pos, st, desc, S, K, canon, blockIdx.x * kPrepThreads + threadIdx.x, stage, 1.0 / (double)nc);
 }
 
 // mix_kernel of one run and prep_kernel of the next window of the trajectory in ONE launch (the first workgroups
@@ -1963,7 +1933,8 @@ __global__ __launch_bounds__(64 * kMixGroups) void mix_prep_kernel(const float *
     // and dispatched last they would start when the mix is nearly over
     const int n_prep = (int)gridDim.x - n_mix;
     if ((int)blockIdx.x < n_prep)
-        prep_body(rt, mode, pos, nullptr, desc, S, K, canon, (int)blockIdx.x * (64 * kMixGroups) + (int)threadIdx.x, stage);
+        prep_body(rt, mode, pos, nullptr, desc, S, K, canon, (int)blockIdx.x * (64 * kMixGroups) + (int)threadIdx.x, stage,
+                  1.0 / kNc);
     else
         mix_body(partial, mix, S_groups, blk, (int)blockIdx.x - n_prep, red);
 }
@@ -2266,10 +2237,10 @@ hipError_t launch_interp_debug(const RingTable &rt, const float *d_ele, const fl
 }
 
 hipError_t launch_prep(const RingTable &rt, int mode, const float *d_pos, const SrcState *d_st, ItemDesc *d_desc,
-                       int S, int K, int canon, hipStream_t st) {
+                       int S, int K, int canon, int nc, hipStream_t st) {
     const int n = S * K;
     hipLaunchKernelGGL(prep_kernel, dim3((2 * n + kPrepThreads - 1) / kPrepThreads), dim3(kPrepThreads), 0, st, rt, mode,
-                       d_pos, d_st, d_desc, S, K, canon);
+                       d_pos, d_st, d_desc, S, K, canon, nc);
     return hipGetLastError();
 }
 
