@@ -38,44 +38,25 @@ constexpr int kMaxRings = 40;  // JF_MAX_RINGS (include/jefferson.h): elevation 
 constexpr int kInterpEleMin = -40, kInterpEleMax = 90, kInterpAzi = 360;
 constexpr int kInterpRows = (kInterpEleMax - kInterpEleMin + 1) * kInterpAzi;  // 47 160
 constexpr int kModeBasic = 1, kModeCorrected = 2, kModeInterpRows = 4;  // bits of the kernels' `mode`
-// Tuning knobs of the fused kernel (overridable at build time for A/B runs):
+// Tuning knobs of the fused kernel (overridable at build time for A/B runs: make variant KFLAGS=...):
 // waves (= work items) per workgroup, and the minimum waves per SIMD the register
 // allocator must leave room for (__launch_bounds__ second argument; 0 = unconstrained).
+// Numbers only -- the forms that were raced against each other are settled and have one code path each
+// (profiles/README.md, "Retired build switches"); the reverb's knobs are at the top of jf_reverb.hip.
 #ifndef JF_WAVES_PER_WG
 #define JF_WAVES_PER_WG 16
 #endif
 #ifndef JF_CHUNK_LOADS
 #define JF_CHUNK_LOADS 8  // table-row loads (16 B per lane each) a wave keeps in flight per round
 #endif
-#ifndef JF_TABLE_DISTANCE
-#define JF_TABLE_DISTANCE 1  // 1: distance factors from the twiddle table + small-angle correction; 0: minimax sin/cos
-#endif
 #ifndef JF_STAGE_LOADS
 #define JF_STAGE_LOADS 4  // pair kernel: table-row loads per stage of a half-filter; two stages are in flight
-#endif
-#ifndef JF_SPLIT_EXCHANGE
-#define JF_SPLIT_EXCHANGE 0  // 1: halve the per-wave LDS exchange buffer (re and im separately)
 #endif
 #ifndef JF_MIN_WAVES
 #define JF_MIN_WAVES 0
 #endif
-#ifndef JF_XCD_MAP
-#define JF_XCD_MAP 0  // group kernel: 1 = adjacent units on one XCD (stationary -2 %, moving +0.5 %: off)
-#endif
-#ifndef JF_UNIT_ORDER
-#define JF_UNIT_ORDER 1  // group kernel: 1 = consecutive waves take consecutive blocks of the same sources (rows and windows overlap in cache: 2.8 %)
-#endif
-#ifndef JF_PAIR_ROTATE_PRIO
-#define JF_PAIR_ROTATE_PRIO 1  // persistent kernels: 1 = progress-ordered wave priorities (0: the hardware's oldest-first: -5.5 %)
-#endif
-#ifndef JF_RV_BIG_MAC1_SHARED
-#define JF_RV_BIG_MAC1_SHARED 1  // reverb, single products of the big partitions IN LINE: the shared form (jf_reverb.hip: big_mac_single_shared)
-#endif
 #ifndef JF_STAGE_DEPTH
 #define JF_STAGE_DEPTH 2  // pair kernel: stages of a half-filter's row loads in flight
-#endif
-#ifndef JF_UNIT_ZIGZAG
-#define JF_UNIT_ZIGZAG 2  // order of the units over the rounds of the pair kernel (see there): 2 rotated, 1 zigzag, 0 plain
 #endif
 constexpr int kWavesPerWg = JF_WAVES_PER_WG;
 

@@ -394,8 +394,8 @@ const char *jf_debug_last_kernels(jf_engine *e) {
             auto products = [&](const ReverbBigParams &g) {
                 if (g.n_prod <= 0) return std::string();
                 const std::string mac = g.n_prod >= 4 ? "reverb_big_mac_kernel<" + b1 + ",16>"
-                                        : JF_RV_BIG_MAC1_SHARED && g.mac_wgs == 0 ? "reverb_big_mac1_kernel<" + b1 + ">"
-                                                                                  : "reverb_big_mac_kernel<" + b1 + ",1>";
+                                        : g.mac_wgs == 0 ? "reverb_big_mac1_kernel<" + b1 + ">"
+                                                         : "reverb_big_mac_kernel<" + b1 + ",1>";
                 return mac + ";reverb_big_ifft_kernel<" + b1 + per_wg(g.n_prod);
             };
             auto transforms = [&](const ReverbBigParams &g) {

@@ -10,7 +10,9 @@
 // RESULTS by design (NOCHAIN, NOWINLOAD, NOFRONT, NOROWLOAD, HALFROWLOAD, HALFTABLE, FASTGATHER, NO_SELECTS, NOWAIT,
 // NOFILTER, STAGGER, JF_RV_EXP_*) -- no longer live in the product's translation units: one of them read outside a
 // buffer in round 3.  They are kept as profiles/r03_timing_hooks.patch (apply to a scratch copy to repeat a measurement
-// of profiles/r02_experiments.md / r03_experiments.md; the patch also marks the build as an experiment).
+// of profiles/r02_experiments.md / r03_experiments.md; the patch also marks the build as an experiment).  The settled A/B
+// switches of the kernels (JF_PAIR_*, JF_UNIT_*, JF_RV_BIG_* and their like: one form shipped, the others measured slower or
+// outside the tolerance) followed them out: profiles/README.md, "Retired build switches".
 //
 //   JF_EXP_NO_OPAQUE     the lane index is not hidden from the optimiser (shows the spills that opaque() avoids)
 //   JF_EXP_PHASES        per-wave cycle counters of the pair kernel's phases: profiles/phases.py

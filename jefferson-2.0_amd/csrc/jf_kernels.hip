@@ -121,25 +121,11 @@ JF_DEV float2 ctw(float2 v, float2 w) {
 // The same products as a packed multiply + a packed FMA (jf_packed.h) where both operands already sit in aligned register
 // pairs (LDS reads, freshly computed values): 9.9 issue cycles instead of 14.0 for two multiplies (2.7 each) and two FMAs
 // (4.3 each: three vector-register sources) -- profiles/micro/pk_rate.hip, 4 waves per SIMD.
-#ifndef JF_PACKED_CMUL
-#define JF_PACKED_CMUL 1
-#endif
-#ifndef JF_PACKED_DTAIL
-#define JF_PACKED_DTAIL 0
-#endif
 JF_DEV float2 cmul_pk(float2 a, float2 b) {
-#if JF_PACKED_CMUL
     return f2_of(pcmul(c2_of(a), c2_of(b)));
-#else
-    return cmul(a, b);
-#endif
 }
 JF_DEV float2 cmulc_pk(float2 a, float2 b) {  // a * conj(b)
-#if JF_PACKED_CMUL
     return f2_of(pcmulc(c2_of(a), c2_of(b)));
-#else
-    return cmulc(a, b);
-#endif
 }
 
 // v * (c + i*DIR*s)
@@ -342,7 +328,8 @@ JF_DEV void rfft1024_wave(float2 (&z)[8], float2 (&X)[8], float2 *buf, const flo
 // In : Zin[r] = Z[lane + 64 r], r = 0..15.
 // Out: out[j] = y[1024 - B + (lane>>2) + 16 (NOUT a + j)], a = lane & 3, j < NOUT = B / 64: this lane's
 //      frames of the block.  buf: this wave's LDS, >= 1088 float2, or >= 544 with SPLIT (the exchange then
-//      moves real and imaginary parts one after the other through a float image of half the size).
+//      moves real and imaginary parts one after the other through a float image of half the size: the pair kernel's
+//      form, whose work space is kPairWork = 576 float2; the per-source kernels have the room and exchange whole values).
 template <int NOUT, bool SPLIT>
 JF_DEV void ifft1024_lastq_wave(float2 (&v)[16], float2 (&out)[NOUT], float2 *buf, const float2 *tw, int lane) {
     const int a = lane & 3, i = lane >> 2;
@@ -402,8 +389,8 @@ JF_DEV void ifft1024_lastq_wave(float2 (&v)[16], float2 (&out)[NOUT], float2 *bu
 }
 
 // ------------------------------------------------------- distance factor --
-// D[k] = exp(-2 pi i * fsvs r' k / 513) * inv_frac: distance_from_phase (jf_phase.h), or the same from the FFT's own
-// twiddle table (LDS, kTwU: exp(+2 pi i j / 1024), j = 0..511, rounded from double):
+// D[k] = exp(-2 pi i * fsvs r' k / 513) * inv_frac from the FFT's own twiddle table (LDS, kTwU: exp(+2 pi i j / 1024),
+// j = 0..511, rounded from double) instead of distance_from_phase's minimax sin/cos (jf_phase.h; the 2048 path uses it):
 // the phase is split into the nearest 1/1024 turn and a remainder |x| <= pi/1024, and the table value is corrected by
 // cos x - 1 = -x^2/2 (next term 4e-12) and sin x = x - x^3/6 (next term 2e-15) as small addends to it -- one rounding
 // on top of the table's, the argument needs no second float (x is known to 1.8e-10), 20 instructions and one LDS read
@@ -418,24 +405,11 @@ JF_DEV float2 distance_from_phase_tab(unsigned p, float inv_frac, const float2 *
     const float sd = x * fmaf(x2, -0x1.555556p-3f, 1.0f);  // sin x
     const float eh = 0.5f * x2;                            // 1 - cos x
     const float sf = __uint_as_float(__float_as_uint(inv_frac) | (p2 & 0x80000000u));  // inv_frac > 0; second half turn: -
-#if JF_PACKED_DTAIL
-    // cos(a + x) = cos a - (cos a (1 - cos x) + sin a sin x), sin(a + x) = sin a - (sin a (1 - cos x) - cos a sin x) on the
-    // pair (cos a, sin a) as it comes from the table: four packed instructions for the eight of the scalar form below,
-    // the same operations in the same order (bit-identical) -- and 0.4 % SLOWER (0.2488 against 0.2478 ms): the four
-    // are one dependent chain, the eight are two.  Off.
-    const c2 tt = c2_of(t), es = c2{eh, sd};
-    c2 sfp;  // only its low half is read
-    sfp.x = sf;
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wuninitialized"
-    const c2 corr = pfma_nrot_bhi(tt, es, pmul_blo(tt, es));  // (t.x eh + t.y sd, t.y eh - t.x sd)
-    return f2_of(pmul_blo_conj(tt - corr, sfp));               // (re sf, -im sf)
-#pragma clang diagnostic pop
-#else
+    // tried: the tail below as four packed instructions on the pair (cos a, sin a) (JF_PACKED_DTAIL) -- bit-identical and
+    // 0.4 % slower (0.2488 against 0.2478 ms): the four are one dependent chain, these eight are two -- in-source note only
     const float re = t.x - fmaf(t.y, sd, t.x * eh);
     const float im = t.y - fmaf(-t.x, sd, t.y * eh);
     return make_float2(re * sf, -im * sf);
-#endif
 }
 
 // D of this lane's bins lane + 64 q, q = 0..7, and Re D[512].  Phase words by 64-bit accumulation (two adds per bin
@@ -443,41 +417,24 @@ JF_DEV float2 distance_from_phase_tab(unsigned p, float inv_frac, const float2 *
 // Bin 512's factor is wave-uniform and was a ninth evaluation by all lanes; bin 0's is 1/frac exactly and needs none: LANE 0
 // EVALUATES D[512] IN ITS SLOT OF BIN 0 (one select on the phase word), so dq[0] on lane 0 is D[512], not D[0] -- its
 // callers take X[0] D[0] = X[0].x inv_frac and d512x there (distance_factor_bin0 restores the slot where D itself is wanted).
-// JF_FAST_DISTANCE (off): D[lane + 64 q] = D[lane] E^q with the wave-uniform step E = exp(-2 pi i 64 c), whose
-// powers lanes 0..8 evaluate and broadcast through scalar registers -- 135 fewer instructions per source-block, 4.5 %
-// of the batch kernel's time, but one more rounding per factor: on a full-scale signal (|y| ~ 1.2) the output error
-// against float64 grows from 2.06e-7 to 2.90e-7, past the reference's 2e-7 (profiles/r02_experiments.md).
+// tried: D[lane + 64 q] = D[lane] E^q with the wave-uniform step E = exp(-2 pi i 64 c), whose powers lanes 0..8 evaluate and
+// broadcast through scalar registers (JF_FAST_DISTANCE) -- 135 fewer instructions per source-block, -4.5 % of the batch
+// kernel's time, but one more rounding per factor: on a full-scale signal (|y| ~ 1.2) the output error against float64
+// grows from 2.06e-7 to 2.90e-7, past the reference's 2e-7: outside the tolerance, so not kept (profiles/r02_experiments.md).
 JF_DEV void distance_factors(unsigned c_hi, unsigned c_lo, float inv_frac, int lane, float2 (&dq)[8], float &d512x,
-                             [[maybe_unused]] const float2 *tw) {
+                             const float2 *tw) {
     const unsigned long long c64 = ((unsigned long long)c_hi << 32) | c_lo;
-#ifndef JF_FAST_DISTANCE
     unsigned long long ph = (unsigned long long)(unsigned)lane * c64;
     const unsigned long long step = c64 << 6;
 #pragma unroll
     for (int q = 0; q < 8; q++) {
         unsigned p = (unsigned)(ph >> 32);
         if (q == 0) p = lane == 0 ? (unsigned)((c64 << 9) >> 32) : p;
-#if JF_TABLE_DISTANCE
         dq[q] = distance_from_phase_tab(p, inv_frac, tw);
         if (q & 1) __builtin_amdgcn_sched_barrier(0);  // two table reads in flight, not eight (registers)
-#else
-        dq[q] = distance_from_phase(p, inv_frac);
-#endif
         ph += step;
     }
     d512x = dq[0].x;  // on lane 0 (the only lane that uses it)
-#else
-    const float2 d0 = distance_from_phase((unsigned)(((unsigned long long)(unsigned)lane * c64) >> 32), inv_frac);
-    const float2 e = distance_from_phase((unsigned)(((unsigned long long)(unsigned)(lane & 15) * (c64 << 6)) >> 32), 1.0f);
-    dq[0] = d0;
-#pragma unroll
-    for (int q = 1; q < 8; q++) {
-        const float ex = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(e.x), q));
-        const float ey = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(e.y), q));
-        dq[q] = cmul(d0, make_float2(ex, ey));
-    }
-    d512x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(e.x), 8)) * inv_frac;
-#endif
 }
 
 // ------------------------------------------------------ filter + inverse --
@@ -552,18 +509,18 @@ JF_DEV void filtered_bins_nt(int nt, const float4 *__restrict__ htab, const int 
 // The inverse of one spectrum given as this lane's Z[k] (zk) and Z[N-k] (zm), k = lane + 64 q: the upper
 // half Z[lane + 64 r], r = 8..15, lives mirrored on lane 64 - lane (lane 0: r = 8 -> Z[512], else
 // Z[N - 64 (16 - r)]).
-template <int NOUT, bool SPLIT>
+template <int NOUT>
 JF_DEV void inverse_of(float2 (&v)[16], const float2 (&zm)[8], float2 (&out)[NOUT], float2 *buf, const float2 *tw,
                        int lane) {
     float2 up[8];
     mirror8(buf, zm, up, lane);
 #pragma unroll
     for (int r = 8; r < 16; r++) v[r] = up[r - 8];
-    ifft1024_lastq_wave<NOUT, SPLIT>(v, out, buf, tw, lane);
+    ifft1024_lastq_wave<NOUT, false>(v, out, buf, tw, lane);
 }
 
 // One filter set for this lane's bins, then the inverse transform.
-template <int NOUT, bool SPLIT>
+template <int NOUT>
 JF_DEV void filter_set(int nt, const float4 *__restrict__ htab, const int *rows, const float *w,
                        const float2 (&xd)[8], float2 (&out)[NOUT], float2 *buf, const float2 *tw,
                        int lane) {
@@ -572,23 +529,18 @@ JF_DEV void filter_set(int nt, const float4 *__restrict__ htab, const int *rows,
         v[q] = zk;
         mir[q] = zm;
     });
-    inverse_of<NOUT, SPLIT>(v, mir, out, buf, tw, lane);
+    inverse_of<NOUT>(v, mir, out, buf, tw, lane);
 }
 
 // ------------------------------------------------------------ fused kernel --
-#ifndef JF_BLOCK_D_EARLY
-#define JF_BLOCK_D_EARLY 1  // per-source kernels: distance factors while the window loads are in flight
-#endif
-constexpr bool kSplit = JF_SPLIT_EXCHANGE != 0;
-constexpr int kWaveLds = kSplit ? 576 : 1088;  // float2 per wave: the inverse exchange (8704 B), or with the split
-                                               // exchange the forward passes (4608 B)
+constexpr int kWaveLds = 1088;  // float2 per wave: the inverse exchange (8704 B)
 
 // Front half of one (block b, source s) work item: window gather (Audio.cu:121-139,
 // GPUSoundSource.cu:472-513), write-back of the window and counters at the last block of a call, forward
 // FFT with its 1/N (GPUSoundSource.cu:344-346), times the distance factor: xd[q] = X[k] D[k], k = lane + 64 q
 // (lane 0: xd[0] = (X0 D0.re, X512 D512.re)).  D_EARLY: the distance factors are computed while the window
-// loads are in flight (16 more registers live across the FFT).  False if the item is silent (not
-// interpolable: the reference has no defined output there).
+// loads are in flight (16 more registers live across the FFT): the per-source kernels do, the pair kernel does
+// not.  False if the item is silent (not interpolable: the reference has no defined output there).
 // First part of the front half: the loads of the window, nothing that waits for them (the caller may put other work
 // between this and item_finish).  count0 / L: the source's play position and (stored) signal length.
 template <int NOUT>
@@ -717,7 +669,7 @@ JF_DEV void spatialise_item(const FusedParams &P, const ItemDesc *dp, const floa
     const int n_new = dp->n_new;
     const int n_old = dp->n_old;
     float2 xd[8];
-    if (!item_front<NOUT, JF_BLOCK_D_EARLY != 0>(P, dp, pos_rec, b, s, buf, s_tw, opaque(lane), xd)) return;
+    if (!item_front<NOUT, true>(P, dp, pos_rec, b, s, buf, s_tw, opaque(lane), xd)) return;
 
     // ---- filter set(s) + inverse + crossfade (GPUSoundSource.cu:351-381)
     float2 res[NOUT];
@@ -726,7 +678,7 @@ JF_DEV void spatialise_item(const FusedParams &P, const ItemDesc *dp, const floa
         const int *rows = set ? dp->rows_new : dp->rows_old;
         const float *w = set ? dp->w_new : dp->w_old;
         float2 mine[NOUT];  // frames i + 16 (NOUT a + j) of the block
-        filter_set<NOUT, kSplit>(set ? n_new : n_old, P.htab, rows, w, xd, mine, buf, s_tw, opaque(lane));
+        filter_set<NOUT>(set ? n_new : n_old, P.htab, rows, w, xd, mine, buf, s_tw, opaque(lane));
 #pragma unroll
         for (int j = 0; j < NOUT; j++) {
             float2 r1 = mine[j];
@@ -770,40 +722,31 @@ __global__ JF_FUSED_BOUNDS void fused_block_kernel(const FusedParams P) {
     const int G = P.G, SG = P.S / G;
     const int n_units = P.K * SG;
     const int a = lane & 3, i = lane >> 2;
-    [[maybe_unused]] int steps_done = 0;
+    int steps_done = 0;
 #pragma unroll 1
     for (int unit = blockIdx.x * kWavesPerWg + wave; unit < n_units; unit += gridDim.x * kWavesPerWg) {
-#if JF_UNIT_ORDER
-        // consecutive waves take consecutive BLOCKS of the same sources: their table rows and windows overlap
+        // consecutive waves take consecutive BLOCKS of the same sources: their table rows and windows overlap in cache
+        // (tried: consecutive groups of sources of one block, JF_UNIT_ORDER=0 -- 2.8 % slower here, 0.1676 ms in the pair
+        // kernel's table of profiles/r02_experiments.md)
         const int sg = unit / P.K;
         const int b = unit - sg * P.K;
         const int s0 = sg * G;
-#else
-        const int b = unit / SG;
-        const int s0 = (unit - b * SG) * G;
-#endif
         float2 acc[NOUT];
 #pragma unroll
         for (int j = 0; j < NOUT; j++) acc[j] = make_float2(0.f, 0.f);
 #pragma unroll 1
         for (int g = 0; g < G; g++) {
-#if JF_PAIR_ROTATE_PRIO
             switch (3 - (steps_done++ & 3)) {  // progress-ordered priorities, see fused_pair_kernel
             case 0: __builtin_amdgcn_s_setprio(0); break;
             case 1: __builtin_amdgcn_s_setprio(1); break;
             case 2: __builtin_amdgcn_s_setprio(2); break;
             default: __builtin_amdgcn_s_setprio(3); break;
             }
-#endif
             const int item = b * P.S + s0 + g;
             const ItemDesc dl = load_desc(P.desc + item);  // scalar loads
             spatialise_item<NOUT>(P, &dl, P.pos + (size_t)item * 5, b, s0 + g, buf, s_tw, lane, acc);
         }
-#if JF_UNIT_ORDER
         float2 *out = reinterpret_cast<float2 *>(P.partial) + ((size_t)b * SG + sg) * B;
-#else
-        float2 *out = reinterpret_cast<float2 *>(P.partial) + (size_t)unit * B;
-#endif
 #pragma unroll
         for (int j = 0; j < NOUT; j++) out[i + 16 * (NOUT * a + j)] = acc[j];
     }
@@ -1020,23 +963,6 @@ JF_DEV void ear_sums_to_z(const c2 (&sL)[4], const c2 (&sR)[4], bool special, c2
     zm[0] = special ? z512 : zm[0];
 }
 
-#ifndef JF_PAIR_MIX_AGES
-#define JF_PAIR_MIX_AGES 1  // which two waves of a workgroup form a pair: 1 = w and 15 - w, 2 = same SIMD, 0 = 2i and 2i + 1
-#endif
-#ifndef JF_PAIR_RELOAD_PARAMS
-#define JF_PAIR_RELOAD_PARAMS 1
-#endif
-#ifndef JF_PAIR_D_EARLY
-#define JF_PAIR_D_EARLY 0
-#endif
-#ifndef JF_PAIR_ACK_IN_VGPR
-#define JF_PAIR_ACK_IN_VGPR 1
-#endif
-#ifndef JF_PAIR_OVERLAP
-#define JF_PAIR_OVERLAP 0  // 1: a wave's window loads fly while it filters the partner's previous source -- 16 more live
-                           // registers, which spill (72 B) and cost more than the overlap gains: 0.195 vs 0.182 ms
-#endif
-
 JF_DEV void prep_body(const RingTable &rt, int mode, const float *__restrict__ pos, const SrcState *__restrict__ st,
                       ItemDesc *__restrict__ desc, int S, int K, int canon, int tid, ItemDesc *stage, double inv_nc);
 
@@ -1048,7 +974,6 @@ __global__ JF_FUSED_BOUNDS void fused_pair_kernel(const FusedParams Pin) {
     __shared__ float2 s_tw[kTwPack];
     __shared__ float2 s_pair[kPairsPerWg * kPairLds];
     const int tid = threadIdx.x;
-#if JF_PAIR_RELOAD_PARAMS
     // The launch parameters are read again from the kernel-argument segment (scalar loads, scalar cache) wherever the
     // source loop needs them, instead of being held in scalar registers from kernel entry: with ~30 parameter registers
     // live across the whole persistent loop the compiler ran out of scalar registers and kept 49 of them in the lanes of
@@ -1074,10 +999,6 @@ __global__ JF_FUSED_BOUNDS void fused_pair_kernel(const FusedParams Pin) {
         static_assert(sizeof(FusedParams) == 10 * 8 + 5 * 4 + 4 + 2 * 8 + 4 + 4 + 2 * 8 + 2 * 4 + sizeof(RingTable),
                       "a field was added to FusedParams: reload it here too");
     };
-#else
-    const FusedParams &P = Pin;
-    auto reload_params = []() {};
-#endif
     if ((int)blockIdx.x >= Pin.n_pair_wgs) {
         // The trailing workgroups of the grid: the descriptors of the window that follows this run (prep_kernel's work).
         // They are dispatched as compute units come free, i.e. while the slowest pairs are still on their last unit: the
@@ -1103,15 +1024,9 @@ __global__ JF_FUSED_BOUNDS void fused_pair_kernel(const FusedParams Pin) {
     // slower wave: as (2i, 2i + 1) the last pairs of a workgroup left the kernel 12 us after the first (profiles/stamps.py)
     // and the SIMDs ran half empty meanwhile.  As (w, 15 - w) -- an old wave with a young one, on different SIMDs -- every
     // pair is held back alike: units take 5 % longer, the pairs leave within 4 us of each other, the kernel is 5 % shorter.
-#if JF_PAIR_MIX_AGES == 2
-    // both waves of a pair on one SIMD (wave w runs on SIMD w % 4), oldest with youngest and the middle two together: 1 % slower
-    const int pair = 2 * (wave & 3) + (((wave >> 2) == 1 || (wave >> 2) == 2) ? 1 : 0), half = wave >> 3;
-    static_assert(kPairsPerWg == 8, "16 waves");
-#elif JF_PAIR_MIX_AGES
+    // tried: both waves of a pair on one SIMD (wave w runs on SIMD w % 4), oldest with youngest and the middle two together
+    // (JF_PAIR_MIX_AGES=2) -- 1 % slower -- in-source note only
     const int pair = wave < kPairsPerWg ? wave : 2 * kPairsPerWg - 1 - wave, half = wave < kPairsPerWg ? 0 : 1;
-#else
-    const int pair = wave >> 1, half = wave & 1;
-#endif
     JF_EXP_STAMP_SETUP(P, pair, half, lane);
     JF_EXP_PHASE_SETUP();
     float2 *base = s_pair + pair * kPairLds;
@@ -1120,18 +1035,14 @@ __global__ JF_FUSED_BOUNDS void fused_pair_kernel(const FusedParams Pin) {
     const float2 *pbuf = base + (half ^ 1) * kPairWave, *pmail = pbuf + kPairWork;  // the partner's
     const unsigned flags = (unsigned)(size_t)(base + 2 * kPairWave);  // LDS byte address of pub[2], ack[2]
     const unsigned my_pub = flags + 4 * half, his_pub = flags + 4 * (half ^ 1);
-#if JF_PAIR_ACK_IN_VGPR
     // my_ack is needed once per source (consumed()), as the ADDRESS operand of a ds_write -- a vector register anyway: held in a
     // scalar register it is one of the scalars the compiler keeps in lanes of a vector register (v_readlane + s_nop + v_mov
     // per use: 20 of the kernel's 63 v_readlane; 808.0 -> 806.3 vector instructions per source-block, -0.1 % time)
     unsigned my_ack = flags + 8 + 4 * half;
     asm volatile("" : "+v"(my_ack));
     const unsigned his_ack = flags + 8 + 4 * (half ^ 1);
-#else
-    const unsigned my_ack = flags + 8 + 4 * half, his_ack = flags + 8 + 4 * (half ^ 1);
-#endif
     int npub = 0, nseen = 0;  // hand-offs I published / the partner's I consumed (wave-uniform)
-    [[maybe_unused]] int steps_done = 0;  // sources I have run the front half of
+    int steps_done = 0;  // sources I have run the front half of
     bool dead = false;        // a wait timed out (pair_wait)
     auto publish = [&]() {  // my mailbox stores, then the flag: release
         JF_PAIR_RELEASE();
@@ -1161,32 +1072,22 @@ __global__ JF_FUSED_BOUNDS void fused_pair_kernel(const FusedParams Pin) {
     const int n_own = (G - half + 1) / 2, n_his = (G - (half ^ 1) + 1) / 2;  // sources g = 2 j + half / + (half ^ 1)
     // Rounds of units over the persistent pairs.  Units differ in cost -- the first blocks of a call gather their windows
     // the slow way -- and so do pairs: the SIMD's arbiter serves its oldest wave first on a tie, and the last pairs of a
-    // workgroup leave the kernel ~12 us after the first (profiles/stamps.py).  JF_UNIT_ZIGZAG = 2: every round the
+    // workgroup leave the kernel ~12 us after the first (profiles/stamps.py).  Every round the
     // pair -> unit map is rotated by one workgroup, so the expensive units (slots 0..2 of a group's blocks) always go to
-    // pairs 0..2 of a workgroup, and to another workgroup every round; 1: every other round in reverse (the expensive
-    // units then alternate between the first and the LAST pairs of a workgroup: 1.3 % slower); 0: plain.
+    // pairs 0..2 of a workgroup, and to another workgroup every round.
+    // tried: every other round in reverse (JF_UNIT_ZIGZAG=1) -- the expensive units then alternate between the first and the
+    // LAST pairs of a workgroup: 1.3 % slower than the rotation (0.2758 vs 0.2722 ms), itself 3 % faster than the plain map
+    // (0.1604 vs 0.1652 ms) -- profiles/r02_experiments.md; two more orders: profiles/r05/unit_order.md
     const int n_pairs = P.n_pair_wgs * kPairsPerWg, my_pair = blockIdx.x * kPairsPerWg + pair;
 #pragma unroll 1
     for (int round = 0; round * n_pairs < n_units; round++) {
-#if JF_UNIT_ZIGZAG == 2
         // rotation by one workgroup per round: the pair-in-workgroup index of a unit's slot stays what it is
         const int unit = round * n_pairs + (my_pair + 8 * round) % n_pairs;
-#elif JF_UNIT_ZIGZAG
-        const int unit = (round & 1) ? (round + 1) * n_pairs - 1 - my_pair : round * n_pairs + my_pair;
-#else
-        const int unit = round * n_pairs + my_pair;
-#endif
         if (unit >= n_units) continue;
         reload_params();
-#if JF_UNIT_ORDER
-        const int sg = unit / P.K;
+        const int sg = unit / P.K;  // consecutive blocks of the same sources, as in fused_block_kernel
         const int b = unit - sg * P.K;
         const int s0 = sg * G;
-#else
-        const int b = unit / SG;
-        const int sg = unit - b * SG;
-        const int s0 = sg * G;
-#endif
         // the unit's sources: slots s0 .. s0 + G - 1 of the engine's processing order (jf_engine.cpp: sources that read
         // the same table rows next to each other)
         const ItemDesc *db = P.desc + (size_t)b * P.S;
@@ -1254,18 +1155,18 @@ __global__ JF_FUSED_BOUNDS void fused_pair_kernel(const FusedParams Pin) {
         int jp = 0;
 #pragma unroll 1
         for (int j = 0; j < n_own; j++) {
-#if JF_PAIR_ROTATE_PRIO
             // The issue arbiter of a SIMD serves its oldest wave first: left alone, waves 0..7 of a workgroup run their
             // first unit in 54 us and waves 8..15 in 70-100 us (profiles/stamps.py), and the SIMDs are half empty while
             // the late ones finish.  A wave lowers its priority with every source it has done (mod 4): whoever is
             // behind is served first, and the waves of a SIMD advance together.
+            // tried: the hardware's oldest-first order, no s_setprio (JF_PAIR_ROTATE_PRIO=0) -- 0.1586 against 0.1477 ms
+            // (profiles/r02_experiments.md); 5.5 % slower when last measured
             switch (3 - (steps_done++ & 3)) {  // s_setprio takes an immediate
             case 0: __builtin_amdgcn_s_setprio(0); break;
             case 1: __builtin_amdgcn_s_setprio(1); break;
             case 2: __builtin_amdgcn_s_setprio(2); break;
             default: __builtin_amdgcn_s_setprio(3); break;
             }
-#endif
             reload_params();
             const int src = ord[2 * j + half];
             const ItemDesc dl = load_desc(db + src);
@@ -1277,12 +1178,8 @@ __global__ JF_FUSED_BOUNDS void fused_pair_kernel(const FusedParams Pin) {
             int count0, L;
             item_gather<NOUT>(P, b, src, opaque(lane), z, count0, L);
             JF_EXP_PHASE(0);  // own source: descriptor and signal records, window requests
-#if JF_PAIR_OVERLAP
-            if (jp < j && jp < n_his) take_partner_source(jp++);
-#endif
             float2 xd[8];
-            if (item_finish<NOUT, JF_PAIR_D_EARLY != 0>(P, dp, P.pos + (size_t)item * 5, b, src, buf, s_tw, opaque(lane), z,
-                                                        count0, L, xd)) {
+            if (item_finish<NOUT, false>(P, dp, P.pos + (size_t)item * 5, b, src, buf, s_tw, opaque(lane), z, count0, L, xd)) {
                 // (requesting my filter's first row loads before this hand-off would hold X D, 16 registers, across
                 // them: it spills)
                 JF_EXP_PHASE(1);  // window arrival, forward transform, distance factors
@@ -1319,12 +1216,13 @@ __global__ JF_FUSED_BOUNDS void fused_pair_kernel(const FusedParams Pin) {
                 });
                 JF_EXP_PHASE(3);  // own source's two half-filters
             }
-#if !JF_PAIR_OVERLAP
+            // tried: the partner's previous source taken in front of item_finish instead, so that my window loads fly while I
+            // filter it (JF_PAIR_OVERLAP=1) -- 16 more live registers, which spill (72 B) and cost more than the overlap
+            // gains: 0.195 vs 0.182 ms -- in-source note only
             if (jp < j && jp < n_his) {
                 take_partner_source(jp++);
                 JF_EXP_PHASE(4);  // the partner's source's two half-filters (after the hand-off arrived)
             }
-#endif
         }
 #pragma unroll 1
         for (; jp < n_his; jp++) {

@@ -25,6 +25,24 @@
 
 #include <algorithm>
 
+// Tuning knobs of the reverb kernels (overridable at build time for A/B runs: make variant KFLAGS=...).  Numbers only: the
+// forms that were raced against each other are settled (profiles/README.md, "Retired build switches").
+#ifndef JF_TILE_ATTR
+#define JF_TILE_ATTR __attribute__((amdgpu_waves_per_eu(4, 4)))  // reverb_mac_tiled_kernel: two workgroups per CU, 128 VGPRs
+#endif
+#ifndef JF_RV_BIG_PREFETCH
+#define JF_RV_BIG_PREFETCH 4  // reverb_big_mac_kernel: steps its loads run ahead of the products (2 / 4 / 8: 72.6 / 71.3 / 78.1 us)
+#endif
+#ifndef JF_RV_BIG_MAC_WAVES
+#define JF_RV_BIG_MAC_WAVES 4  // reverb_big_mac_kernel, tiled form: waves per workgroup (kBigMacWavesTiled)
+#endif
+#ifndef JF_RV_BIG_MAC1_AHEAD
+#define JF_RV_BIG_MAC1_AHEAD 8  // reverb_big_mac1_kernel: delay-line loads in flight per wave
+#endif
+#ifndef JF_RV_BIG_IFFT_WGS
+#define JF_RV_BIG_IFFT_WGS 6  // reverb_big_ifft_kernel: workgroups per compute unit the register allocator leaves room for
+#endif
+
 namespace jf {
 
 #include "jf_rv_small.h"
@@ -169,14 +187,6 @@ __global__ __launch_bounds__(64 * kMacWaves) void reverb_mac_kernel(const Reverb
 // KB, so that the window's register indices are static).  The packed pair in bin 0 is carried as if it
 // were complex; mac_finish recomputes it from the compact copies.  Waves then each finish two blocks.
 constexpr int kTileWaves = 8;
-#ifndef JF_RV_PROGRESS_PRIO
-#define JF_RV_PROGRESS_PRIO 1
-#endif
-
-
-#ifndef JF_TILE_ATTR
-#define JF_TILE_ATTR __attribute__((amdgpu_waves_per_eu(4, 4)))  // two workgroups per CU: 128 VGPRs
-#endif
 template <int B, int KB>
 __global__ __launch_bounds__(64 * kTileWaves) JF_TILE_ATTR void reverb_mac_tiled_kernel(const ReverbParams P) {
     constexpr int BH = B / 64;          // waves side by side over the bins
@@ -241,7 +251,9 @@ __global__ __launch_bounds__(64 * kTileWaves) JF_TILE_ATTR void reverb_mac_tiled
         // of 2 (profiles/micro/cmac_tile.hip: 114.8 against 104.6 TFLOP/s for this loop on registers alone; in the
         // kernel, where the loads set the pace, the same time at 90 VGPRs instead of 124).  The same operations on
         // every accumulator in the same order: bit-identical sums.
-#if JF_RV_SCALAR_MAC
+        // tried: two v_pk_fma_f32 per product (pcmac of jf_packed.h, JF_RV_SCALAR_MAC=0) -- the same time, but the window
+        // needs even-aligned register pairs: 128 VGPRs and 20 B of scratch against 124 and none -- profiles/r02_experiments.md
+        // section 4, profiles/r03_experiments.md
 #pragma unroll
         for (int i = 0; i < KB; i++) {
             const rv_v2 x = xr[(i + KB - j) % KB];
@@ -254,20 +266,16 @@ __global__ __launch_bounds__(64 * kTileWaves) JF_TILE_ATTR void reverb_mac_tiled
             acc[i].x = __builtin_fmaf(-x.y, h.y, acc[i].x);
             acc[i].y = __builtin_fmaf(x.y, h.x, acc[i].y);
         }
-#else
-#pragma unroll
-        for (int i = 0; i < KB; i++) rv_cmac(acc[i], xr[(i + KB - j) % KB], h);
-#endif
     };
     int p0 = pa;
-    [[maybe_unused]] int groups_done = 0;
+    int groups_done = 0;
     for (; p0 + KB <= pb; p0 += KB) {  // straight-line groups: loads of later steps may move above earlier MACs
 #pragma unroll
         for (int j = 0; j < KB; j++) {
-#if JF_RV_PROGRESS_PRIO
             // progress-ordered priorities (see fused_pair_kernel): the SIMD's arbiter serves its oldest wave first, and a
-            // workgroup finishes with its slowest wave
-            if (j % (KB / JF_RV_PROGRESS_PRIO) == 0) {
+            // workgroup finishes with its slowest wave -- once per group of KB partitions: 85.7 against 89.2 us (tried: 2 or 4
+            // steps per group, JF_RV_PROGRESS_PRIO=2 / 4 -- 88.9 / 86.1 -- profiles/r02_experiments.md)
+            if (j == 0) {
                 switch (3 - (groups_done++ & 3)) {
                 case 0: __builtin_amdgcn_s_setprio(0); break;
                 case 1: __builtin_amdgcn_s_setprio(1); break;
@@ -275,7 +283,6 @@ __global__ __launch_bounds__(64 * kTileWaves) JF_TILE_ATTR void reverb_mac_tiled
                 default: __builtin_amdgcn_s_setprio(3); break;
                 }
             }
-#endif
             step(j);
         }
     }
@@ -295,36 +302,24 @@ __global__ __launch_bounds__(64 * kTileWaves) JF_TILE_ATTR void reverb_mac_tiled
 // radix 2 or 4.  T2[j] = exp(+2 pi i j / (2 NPT)), j < 2 NPT.  The twiddles a thread needs do not depend on the data: they
 // are loaded into registers FIRST (BigTwiddles::load, before the caller fetches its input), so that a transform waits for
 // global memory once, not once per pass.
-#ifndef JF_RV_BIG_TW_LDS
-#define JF_RV_BIG_TW_LDS 1
-#endif
 template <int NPT, int NT>
 struct BigTwiddles {
     static constexpr int RL = NPT / 512;               // radix of the last pass
     static constexpr int NL = NPT / RL / NT;           // its butterflies per thread
     static_assert(NPT / 8 <= NT && NL >= 1, "one radix-8 butterfly per thread at most");
-    // passes with Ns = 8 and 64: exp(2 pi i r k / (8 Ns)), r = 1 .. 7 -- JF_RV_BIG_TW_LDS = 0: in registers (28 of them, held
-    // through the whole kernel); 1: in LDS (504 entries, 4 KB per workgroup, staged once by stage_w8: pass Ns = 8 reads
-    // eight distinct entries per wave -- broadcasts --, pass Ns = 64 one entry per lane).  The persistent transform kernels keep
-    // the next item's input in registers instead.
-#if !JF_RV_BIG_TW_LDS
-    float2 w8[2][7];
-#endif
+    // passes with Ns = 8 and 64: exp(2 pi i r k / (8 Ns)), r = 1 .. 7 -- in LDS (504 entries, 4 KB per workgroup, staged once
+    // by stage_w8: pass Ns = 8 reads eight distinct entries per wave -- broadcasts --, pass Ns = 64 one entry per lane).
+    // tried: in registers (JF_RV_BIG_TW_LDS=0) -- 28 of them, held through the whole kernel; the persistent transform kernels
+    // keep the next item's input in registers instead -- profiles/r05/reverb_batch.md
     float2 wl[NL][RL - 1];  // last pass (Ns = 512)
     static constexpr int kW8Len = 504;
     JF_DEV static void stage_w8(const float2 *__restrict__ T2, float2 *s_w8, int tid) {
-#if JF_RV_BIG_TW_LDS
         const float2 *__restrict__ pk = T2 + 2 * NPT;
         for (int k = tid; k < kW8Len; k += NT) s_w8[k] = pk[k];
-#endif
     }
     JF_DEV float2 w8_at(const float2 *s_w8, int p, int r, int tid) const {  // r = 1 .. 7
-#if JF_RV_BIG_TW_LDS
         const int Ns = p ? 64 : 8;
         return s_w8[(p ? 56 : 0) + (r - 1) * Ns + (tid & (Ns - 1))];
-#else
-        return w8[p][r - 1];
-#endif
     }
     // The values are entries of the circle T2, but a wave that fetches them there gathers 64 cache lines per load (strides of
     // 8 r .. 64 r entries between neighbouring lanes) -- 17 to 21 such loads per thread were a third of a transform kernel's
@@ -333,15 +328,6 @@ struct BigTwiddles {
     // inverse 43.5 -> 38.7 us per launch at config 5's batch shape (rocprofv3, 320 launches, twice).
     JF_DEV void load(const float2 *__restrict__ T2, int tid) {
         const float2 *__restrict__ pk = T2 + 2 * NPT;
-#if !JF_RV_BIG_TW_LDS
-        const int j = tid < NPT / 8 ? tid : 0;
-#pragma unroll
-        for (int p = 0; p < 2; p++) {
-            const int Ns = p ? 64 : 8;
-#pragma unroll
-            for (int r = 1; r < 8; r++) w8[p][r - 1] = pk[(p ? 56 : 0) + (r - 1) * Ns + (j & (Ns - 1))];
-        }
-#endif
 #pragma unroll
         for (int u = 0; u < NL; u++)
 #pragma unroll
@@ -351,24 +337,17 @@ struct BigTwiddles {
 
 // Where element i of a workgroup transform lies in its LDS buffer.  The passes read with unit stride and write with strides of
 // 8 (first pass: 8 j + r) and of 8 inside runs of 64 (second pass: 64 (j >> 3) + (j & 7) + 8 r); the later passes write with
-// unit stride.  JF_RV_BIG_XOR = 0: one float2 of padding per 8 (rv_at<true>) -- the strided stores are conflict-free, but a
+// unit stride.  One float2 of padding per 8 (rv_at<true>): the strided stores are conflict-free, but a
 // half-wave's unit-stride 8-byte reads then span 36 bank pairs of 32: one extra LDS cycle per read, 40 % of the transform
-// kernels' LDS cycles (round 4's counters).  1: no padding, the low five index bits XORed with index bits 5-7 (low three) and
-// 6-7 (bits 3-4): aligned unit-stride runs stay permutations of the 32 bank pairs, the first pass's 32 lanes (bits 3-4 =
-// j & 3, low bits r) get (j >> 2) & 7 in the low bits and ((j >> 3) ^ j) & 3 above -- injective in j -- and the second
-// pass's (low bits j & 7, bits 3-4 of r) get j >> 3 into bits 3-4: every access of every pass conflict-free, and a
-// transform takes 16 KB instead of 18.
-#ifndef JF_RV_BIG_XOR
-#define JF_RV_BIG_XOR 0
-#endif
+// kernels' LDS cycles (round 4's counters).
+// tried: no padding, the low five index bits XORed with index bits 5-7 (low three) and 6-7 (bits 3-4) (JF_RV_BIG_XOR=1) --
+// every access of every pass conflict-free and 16 KB per transform instead of 18, but the index arithmetic costs 9 registers
+// in the forward kernel and spills in the inverse: 28.2-28.4 against 26.1-26.2 us and 24.9-25.0 against 24.4-24.5 --
+// profiles/r06/reverb_transforms.md
 JF_DEV int rv_big_at(int i) {
-#if JF_RV_BIG_XOR
-    return i ^ ((i >> 5) & 7) ^ (((i >> 6) & 3) << 3);
-#else
     return rv_at<true>(i);
-#endif
 }
-constexpr int rv_big_len(int n) { return JF_RV_BIG_XOR ? n : rv_buf_len<true>(n); }
+constexpr int rv_big_len(int n) { return rv_buf_len<true>(n); }
 
 // NTR transforms of NPT points at once by one workgroup, IN PLACE in NTR buffers of LDS (layout rv_big_at): the
 // twiddles depend on the thread and the pass only, so the transforms share them (registers, loads) and the barriers -- and
@@ -379,10 +358,8 @@ constexpr int rv_big_len(int n) { return JF_RV_BIG_XOR ? n : rv_buf_len<true>(n)
 // second half of its 2 B1 samples = the upper half of the complex result: the last pass's other outputs are never read).
 template <int NPT, int DIR, int NT, bool UPPER_HALF = false, int NTR, int LEN>
 JF_DEV void cfft_wg(float2 (&v)[NTR][8], float2 (&buf)[NTR][LEN], const BigTwiddles<NPT, NT> &tw, const float2 *s_w8, int tid) {
-    static_assert(!(UPPER_HALF && JF_RV_BIG_XOR), "written for the padded layout");
     constexpr int N8 = NPT / 8;  // radix-8 butterflies per pass, one per thread
     const bool on = tid < N8;
-#if !JF_RV_BIG_XOR
     // Padded layout, every address spelled out as ONE per-thread base + a compile-time offset (the compiler does not see that
     // (tid + 256 r) >> 3 = (tid >> 3) + 32 r and recomputed every one of the ~70 addresses of a transform: a third of the
     // kernel's vector instructions, round 5's counters): at(i) = i + (i >> 3), so
@@ -462,68 +439,6 @@ JF_DEV void cfft_wg(float2 (&v)[NTR][8], float2 (&buf)[NTR][LEN], const BigTwidd
             for (int r = UPPER_HALF ? RL / 2 : 0; r < RL; r++) io[288 * u + r * 576] = v[t][u * RL + r];
     }
     __syncthreads();
-#else
-    auto store = [&](int j, int Ns) {  // Stockham: butterfly j's outputs go to j0 + r Ns
-        const int k = j & (Ns - 1), j0 = (j - k) * 8 + k;
-#pragma unroll
-        for (int t = 0; t < NTR; t++)
-#pragma unroll
-            for (int r = 0; r < 8; r++) buf[t][rv_big_at(j0 + r * Ns)] = v[t][r];
-    };
-    if (on) {
-#pragma unroll
-        for (int t = 0; t < NTR; t++) rv_fft8<DIR>(v[t]);
-        store(tid, 1);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int p = 0; p < 2; p++) {
-        const int Ns = p ? 64 : 8;
-        if (on) {
-#pragma unroll
-            for (int t = 0; t < NTR; t++) {
-#pragma unroll
-                for (int r = 0; r < 8; r++) v[t][r] = buf[t][rv_big_at(tid + r * (NPT / 8))];
-#pragma unroll
-                for (int r = 1; r < 8; r++) {
-                    const float2 w = tw.w8_at(s_w8, p, r, tid);
-                    v[t][r] = DIR > 0 ? rv_mul(v[t][r], w) : rv_mulc(v[t][r], w);
-                }
-                rv_fft8<DIR>(v[t]);
-            }
-        }
-        __syncthreads();  // every input of the pass has been read
-        if (on) store(tid, Ns);
-        __syncthreads();
-    }
-    // last pass: radix RL, NL butterflies per thread (RL NL = NPT / NT <= 8 values: the registers of v[t] again)
-    constexpr int RL = BigTwiddles<NPT, NT>::RL, NL = BigTwiddles<NPT, NT>::NL;
-    static_assert(RL * NL <= 8, "the registers of v[t] hold the last pass's values");
-#pragma unroll
-    for (int t = 0; t < NTR; t++)
-#pragma unroll
-        for (int u = 0; u < NL; u++) {
-            const int j = tid + u * NT;
-            float2 x[RL];
-#pragma unroll
-            for (int r = 0; r < RL; r++) x[r] = buf[t][rv_big_at(j + r * (NPT / RL))];
-#pragma unroll
-            for (int r = 1; r < RL; r++) x[r] = DIR > 0 ? rv_mul(x[r], tw.wl[u][r - 1]) : rv_mulc(x[r], tw.wl[u][r - 1]);
-            rv_fftR<RL, DIR>(x);
-#pragma unroll
-            for (int r = 0; r < RL; r++) v[t][u * RL + r] = x[r];
-        }
-    __syncthreads();
-#pragma unroll
-    for (int t = 0; t < NTR; t++)
-#pragma unroll
-        for (int u = 0; u < NL; u++) {
-            const int j = tid + u * NT, k = j & 511, j0 = (j - k) * RL + k;
-#pragma unroll
-            for (int r = 0; r < RL; r++) buf[t][rv_big_at(j0 + r * 512)] = v[t][u * RL + r];
-        }
-    __syncthreads();
-#endif
 }
 
 constexpr int kBigThreads = 256;
@@ -592,10 +507,6 @@ JF_DEV void big_fft_fetch(const ReverbBigParams &P, int i, int s, int tid, float
     }
 }
 
-#ifndef JF_RV_BIG_FFT_AHEAD
-#define JF_RV_BIG_FFT_AHEAD 1  // the next turn's samples requested before this turn's passes (0: round 5's order)
-#endif
-
 // X_m of transform i of the launch (m = first + i) for source s: spectrum of the 2 B1 dry samples of big blocks m - 2, m - 1
 // into fdl1 (packed: bin 0 = (X[0], X[B1])).  One transform per workgroup and turn; item g = i S + s (a source's transforms one
 // after the other -- memory order, which the inverse gains 11 % from -- cost THIS kernel 15 %: 33.3 against 28.9 us, round 5).
@@ -605,7 +516,8 @@ JF_DEV void big_fft_fetch(const ReverbBigParams &P, int i, int s, int tid, float
 // pointer), then its samples, then four passes, then the stores -- in which the vector unit was half idle and so was the
 // memory system (profiles/r06/reverb_transforms.md).  Now the record is a scalar load and turn w + gridDim.x's samples are
 // requested before turn w's passes begin: sixteen registers per thread hold them while the passes run: 29.0 -> 26.2-26.8 us per
-// launch at config 5's batch shape (one box, A B A B; JF_RV_BIG_FFT_AHEAD = 0 is the order of round 5: 28.7).
+// launch at config 5's batch shape (one box, A B A B; tried: without the request ahead, JF_RV_BIG_FFT_AHEAD=0, round 5's order -- 28.7 --
+// profiles/r06/reverb_transforms.md).
 template <int B1>
 __global__ __launch_bounds__(kBigThreads) void reverb_big_fft_kernel(const ReverbBigParams P) {
     __shared__ float2 s_buf[1][rv_big_len(B1)];
@@ -616,12 +528,12 @@ __global__ __launch_bounds__(kBigThreads) void reverb_big_fft_kernel(const Rever
     tw.load(P.tw1, tid0);
     const int n_items = P.n_tr * P.S;
     // the split's twiddles (they depend on the thread only): once per workgroup, no global load behind the last pass
-#ifndef JF_RV_BIG_WIDE_STORE
-#define JF_RV_BIG_WIDE_STORE 1  // the transforms' results as 16-byte stores (two adjacent values per lane); 0: 8-byte stores
-#endif
-    // bin q of the thread's u-th store: WIDE: q = 2 tid + (B1 / 4) u' + e with u = 2 u' + e (two adjacent bins, one 16-byte store);
-    // else q = tid + 256 u
-    auto split_bin = [](int tid, int u) { return JF_RV_BIG_WIDE_STORE ? 2 * tid + (u >> 1) * (2 * kBigThreads) + (u & 1) : tid + u * kBigThreads; };
+    // (loaded before the transform instead of behind its last pass: 45.4 -> 42.4 us per launch at config 5's batch shape,
+    // rocprofv3, 320 launches, twice; later made once per workgroup)
+    // bin q of the thread's u-th store: q = 2 tid + (B1 / 4) u' + e with u = 2 u' + e (two adjacent bins, one 16-byte store).
+    // tried: q = tid + 256 u, 8-byte stores (JF_RV_BIG_WIDE_STORE=0) -- forward 27.4 / 27.6 against 26.0 / 26.3 us, inverse
+    // 25.8 / 26.0 against 25.5 / 25.7 -- profiles/r06/reverb_transforms.md
+    auto split_bin = [](int tid, int u) { return 2 * tid + (u >> 1) * (2 * kBigThreads) + (u & 1); };
     float2 wsplit[B1 / kBigThreads];
 #pragma unroll
     for (int u = 0; u < B1 / kBigThreads; u++) wsplit[u] = P.tw1[split_bin(tid0, u)];
@@ -629,9 +541,7 @@ __global__ __launch_bounds__(kBigThreads) void reverb_big_fft_kernel(const Rever
     const int step_i = (int)gridDim.x / P.S, step_s = (int)gridDim.x - step_i * P.S;
     int ni = (int)blockIdx.x / P.S, ns = (int)blockIdx.x - ni * P.S;
     float2 vn[8];
-#if JF_RV_BIG_FFT_AHEAD
     if ((int)blockIdx.x < n_items) big_fft_fetch<B1>(P, ni, ns, tid0, vn);
-#endif
 #pragma unroll 1
     for (int turn = blockIdx.x; turn < n_items; turn += gridDim.x) {
         // (opaque per turn: the compiler otherwise hoists every LDS address of the four passes out of the loop: ~60 registers)
@@ -645,13 +555,9 @@ __global__ __launch_bounds__(kBigThreads) void reverb_big_fft_kernel(const Rever
             ni++;
         }
         float2 v[1][8];
-#if JF_RV_BIG_FFT_AHEAD
 #pragma unroll
         for (int r = 0; r < 8; r++) v[0][r] = vn[r];
         if (turn + (int)gridDim.x < n_items) big_fft_fetch<B1>(P, ni, ns, tid, vn);
-#else
-        big_fft_fetch<B1>(P, i, s, tid, v[0]);
-#endif
         // a call that puts its small transforms off: its last two big blocks of samples -- this source's last transform has them
         // in registers -- into the dry ring, its last block as `prev`, the play position behind it (ReverbBigParams::state_out)
         if (P.state_out && i == P.n_tr - 1 && tid < B1 / 8) {
@@ -696,14 +602,9 @@ __global__ __launch_bounds__(kBigThreads) void reverb_big_fft_kernel(const Rever
                 }
                 xo[u] = x;
             }
-#if JF_RV_BIG_WIDE_STORE
 #pragma unroll
             for (int u = 0; u < B1 / kBigThreads; u += 2)
                 *reinterpret_cast<float4 *>(out + split_bin(tid, u)) = make_float4(xo[u].x, xo[u].y, xo[u + 1].x, xo[u + 1].y);
-#else
-#pragma unroll
-            for (int u = 0; u < B1 / kBigThreads; u++) out[split_bin(tid, u)] = xo[u];
-#endif
         }
         __syncthreads();  // the buffer is read out before the next turn's first pass writes it
     }
@@ -713,13 +614,11 @@ __global__ __launch_bounds__(kBigThreads) void reverb_big_fft_kernel(const Rever
 // window of KB spectra in registers, per partition ONE new X load and one H load feed KB multiply-accumulates (the scheme
 // of reverb_mac_tiled_kernel).  A wave covers 64 bins (one per lane) of ALL partitions, in ascending order -- no reduction
 // between waves, and the sums are the same whatever KB is.  The packed pair in bin 0 is carried as if it were complex;
-// reverb_big_ifft_kernel recomputes it.
+// reverb_big_ifft_kernel recomputes it.  Only KB = 1 is instantiated (the side stream's single products); the tiles of 16
+// take big_mac_item_shared below.
 // Waves per workgroup: 8 for the single products of the side stream (a narrow launch beside the blocks' kernels:
 // profiles/r04/rt_waves.md), 4 for the batch form's tiles of 16 -- the same 16 waves per CU in twice as many workgroups that
 // start and end apart: 69.6 / 70.6 -> 67.4 / 68.2 us per launch at config 5's batch shape (profiles/r05/reverb_batch.md)
-#ifndef JF_RV_BIG_MAC_WAVES
-#define JF_RV_BIG_MAC_WAVES 4
-#endif
 constexpr int kBigMacWaves = 8, kBigMacWavesTiled = JF_RV_BIG_MAC_WAVES;
 template <int B1, int KB>
 JF_DEV void big_mac_item(const ReverbBigParams &P, int item) {
@@ -739,15 +638,11 @@ JF_DEV void big_mac_item(const ReverbBigParams &P, int item) {
         const float2 *q = reinterpret_cast<const float2 *>(base + voff);
         return rv_v2{q->x, q->y};
     };
-#if JF_RV_BIG_NT_X
     // the delay line is read once per launch: streamed past the caches' replacement order (non-temporal)
     auto load_x = [&](const char *base) {
         const rv_v2 *q = reinterpret_cast<const rv_v2 *>(base + voff);
         return __builtin_nontemporal_load(q);
     };
-#else
-    auto load_x = load_at;
-#endif
     auto slot_of = [&](int u) {  // slot of X_{anchor + i0 + u} (u may be far in the past)
         int slot = (P.anchor_slot_first + i0 + u) % P.R1;
         return slot < 0 ? slot + P.R1 : slot;
@@ -759,26 +654,6 @@ JF_DEV void big_mac_item(const ReverbBigParams &P, int item) {
 #pragma unroll
     for (int i = 1; i < KB; i++) xr[i] = i0 + i < P.n_prod ? load_x(fdl0 + (size_t)slot_of(i) * ((size_t)B1 * 8)) : rv_v2{0.f, 0.f};
     int xslot = slot_of(0);
-#if JF_RV_BIG_SCALAR_MAC
-    auto step = [&](int j) {  // j = q mod KB, a constant after unrolling
-        const rv_v2 h = load_at(hp);
-        xr[(KB - j) % KB] = load_at(fdl0 + (size_t)(unsigned)xslot * ((size_t)B1 * 8));  // X(-q)
-        xslot = xslot == 0 ? P.R1 - 1 : xslot - 1;
-        hp += (size_t)B1 * 8;
-#pragma unroll
-        for (int i = 0; i < KB; i++) {
-            const rv_v2 x = xr[(i + KB - j) % KB];
-            acc[i].x = __builtin_fmaf(x.x, h.x, acc[i].x);
-            acc[i].y = __builtin_fmaf(x.x, h.y, acc[i].y);
-        }
-#pragma unroll
-        for (int i = 0; i < KB; i++) {
-            const rv_v2 x = xr[(i + KB - j) % KB];
-            acc[i].x = __builtin_fmaf(-x.y, h.y, acc[i].x);
-            acc[i].y = __builtin_fmaf(x.y, h.x, acc[i].y);
-        }
-    };
-#else
     // The compiler does not move loads across the asm statements, so the loop fetches D steps ahead itself, in this order
     // (sched_barrier: nothing crosses)
     // (past the last group the H pointer stays on the last partition; the X slots just walk on round the ring)
@@ -807,7 +682,6 @@ JF_DEV void big_mac_item(const ReverbBigParams &P, int item) {
         for (int i = 0; i < KB; i++) acc[i] = pfma_im_rot(xr[(i + KB - j) % KB], h, acc[i]);
         __builtin_amdgcn_sched_barrier(0);
     };
-#endif
     // whole groups of KB partitions, straight-line (loads of later steps may move above earlier multiply-accumulates): the
     // partitions behind the response's last one are zeros (hspec1), the delay-line slots they meet hold older spectra
     for (int q0 = 0; q0 < P.n_part; q0 += KB) {
@@ -820,16 +694,13 @@ JF_DEV void big_mac_item(const ReverbBigParams &P, int item) {
         if (i0 + i < P.n_prod) y[(size_t)i * B1] = make_float2(acc[i].x, acc[i].y);
 }
 
-// The tiled form with the response's spectra through LDS (JF_RV_BIG_MAC_LDS_H): the waves of a workgroup take the SAME 64 bins
+// The tiled form with the response's spectra through LDS: the waves of a workgroup take the SAME 64 bins
 // of kBigMacWavesTiled different sources, so the H_q they multiply by are the same: each wave fetches a quarter of a group
 // of KB partitions' H into LDS a group ahead, and a step reads its H with one ds_read_b64.  A wave's vector-memory
 // instructions per step: 1.25 instead of 2 (the delay line's X, which nobody shares, and a quarter of an H).  Same sums in the
 // same order as big_mac_item.
 // 66.8 -> 59.2-60.5 us per launch at config 5's batch shape on one box, 70 -> 64.5 on another (profiles/r05/reverb_batch.md): a
 // compute unit tracks a bounded number of vector-memory INSTRUCTIONS in flight, and half of them were loads of H out of the L2.
-#ifndef JF_RV_BIG_MAC_LDS_H
-#define JF_RV_BIG_MAC_LDS_H 1
-#endif
 template <int B1, int KB>
 JF_DEV void big_mac_item_shared(const ReverbBigParams &P, int item) {
     constexpr int W = kBigMacWavesTiled, HPW = KB / W, kSlices = B1 / 64;
@@ -851,14 +722,10 @@ JF_DEV void big_mac_item_shared(const ReverbBigParams &P, int item) {
         const float2 *q = reinterpret_cast<const float2 *>(base + voff);
         return rv_v2{q->x, q->y};
     };
-#if JF_RV_BIG_NT_X
     auto load_x = [&](const char *base) {
         const rv_v2 *q = reinterpret_cast<const rv_v2 *>(base + voff);
         return __builtin_nontemporal_load(q);
     };
-#else
-    auto load_x = load_at;
-#endif
     auto slot_of = [&](int u) {
         int slot = (P.anchor_slot_first + i0 + u) % P.R1;
         return slot < 0 ? slot + P.R1 : slot;
@@ -929,16 +796,12 @@ JF_DEV void big_mac_item_shared(const ReverbBigParams &P, int item) {
         if (i0 + i < P.n_prod) y[(size_t)i * B1] = make_float2(acc[i].x, acc[i].y);
 }
 
-// Single products (one-block calls: the side stream) the same way -- JF_RV_BIG_MAC1_SHARED: the eight waves of a workgroup take
+// Single products (one-block calls: the side stream) the same way: the eight waves of a workgroup take
 // the same 64 bins of eight sources; the response's spectra for those bins go to LDS once per workgroup (up to 64 partitions
 // at a time); a wave then has nothing but the delay line's X to load, and loads it U partitions ahead (the plain form waits
 // for every partition's two loads before it asks for the next: 42 round trips in a row).  Same sums in the same order.
 // configs[4]'s shape: 82.9 -> 37.2 us per launch over 256 workgroups.  Used IN LINE (launch_big_products_t says why not
 // beside the blocks).
-// (JF_RV_BIG_MAC1_SHARED: jf_device.h)
-#ifndef JF_RV_BIG_MAC1_AHEAD
-#define JF_RV_BIG_MAC1_AHEAD 8
-#endif
 template <int B1>
 JF_DEV void big_mac_single_shared(const ReverbBigParams &P, int item, rv_v2 (*s_h)[64], int &h_slice) {
     constexpr int W = kBigMacWaves, kSlices = B1 / 64, U = JF_RV_BIG_MAC1_AHEAD, kChunk = 64;
@@ -957,14 +820,10 @@ JF_DEV void big_mac_single_shared(const ReverbBigParams &P, int item, rv_v2 (*s_
         const float2 *q = reinterpret_cast<const float2 *>(base + voff);
         return rv_v2{q->x, q->y};
     };
-#if JF_RV_BIG_NT_X
     auto load_x = [&](const char *base) {
         const rv_v2 *q = reinterpret_cast<const rv_v2 *>(base + voff);
         return __builtin_nontemporal_load(q);
     };
-#else
-    auto load_x = load_at;
-#endif
     int xslot = (P.anchor_slot_first + i0) % P.R1;
     xslot = xslot < 0 ? xslot + P.R1 : xslot;
     rv_v2 acc = rv_v2{0.f, 0.f};
@@ -1018,11 +877,7 @@ __global__ __launch_bounds__(64 * (KB == 1 ? kBigMacWaves : kBigMacWavesTiled)) 
 #pragma unroll 1
         for (int item = blockIdx.x; item < n_items; item += gridDim.x) big_mac_item<B1, KB>(P, item);
     } else {
-#if JF_RV_BIG_MAC_LDS_H
         big_mac_item_shared<B1, KB>(P, blockIdx.x);
-#else
-        big_mac_item<B1, KB>(P, blockIdx.x);
-#endif
     }
 }
 
@@ -1040,21 +895,16 @@ __global__ __launch_bounds__(64 * kBigMacWaves) void reverb_big_mac1_kernel(cons
 // spectrum Y[q], q = tid + r B1 / 8, and Y[B1 - q] (the second set of loads hits the lines the first one fetches); wave 0: the
 // compact bin-0 pairs X0[anchor + i - q] of up to 128 partitions (more are fetched when they are used); the source's wet-ring
 // position (a scalar load).
-// The spectrum requested and untangled four values at a time (1): the second half's loads go into the registers the first half
+// The spectrum requested and untangled four values at a time: the second half's loads go into the registers the first half
 // has freed -- 75 registers instead of 92, SIX workgroups per compute unit instead of five, one more memory round trip per
-// turn: 24.5-24.7 -> 23.7-23.8 us per launch at config 5's batch shape (one box, A B A B; profiles/r06/reverb_transforms.md)
-#ifndef JF_RV_BIG_IFFT_HALVES
-#define JF_RV_BIG_IFFT_HALVES 1
-#endif
-#ifndef JF_RV_BIG_IFFT_WGS
-#define JF_RV_BIG_IFFT_WGS 6
-#endif
+// turn: 24.5-24.7 -> 23.7-23.8 us per launch at config 5's batch shape (one box, A B A B; profiles/r06/reverb_transforms.md;
+// tried: all eight at once, JF_RV_BIG_IFFT_HALVES=0, the first figures)
 template <int B1>
 struct BigIfftInput {
     float2 yk[8], ym[8];
     float2 x0[2];  // wave 0: lane's partitions q = lane, lane + 64
     int c0;        // SrcState::count of the source (to_wet)
-    // the spectrum's values r0 .. r1 - 1 of the eight (JF_RV_BIG_IFFT_HALVES: requested and untangled four at a time)
+    // the spectrum's values r0 .. r1 - 1 of the eight (requested and untangled four at a time)
     JF_DEV void fetch_y(const ReverbBigParams &P, int g, int tid, int r0, int r1) {
         const c2 JF_RV_GLOBAL *y = (const c2 JF_RV_GLOBAL *)(P.ybig + (size_t)g * B1);
         auto ld = [](const c2 JF_RV_GLOBAL *p) {
@@ -1065,12 +915,7 @@ struct BigIfftInput {
 #pragma unroll
         for (int r = 0; r < 8; r++) {
             if (r < r0 || r >= r1) continue;
-#if JF_RV_BIG_NT_Y
-            const c2 t = __builtin_nontemporal_load(y + q0 + r * (B1 / 8));
-            yk[r] = make_float2(t.x, t.y);
-#else
             yk[r] = ld(y + q0 + r * (B1 / 8));
-#endif
         }
 #pragma unroll
         for (int r = 0; r < 8; r++)
@@ -1109,7 +954,7 @@ struct BigIfftInput {
 // ahead (126 registers, four workgroups per compute unit: 27.7 us), Y[B1 - q] from the mirror thread through LDS (28.2), W^q
 // fetched per turn (27.3), the register count forced down to six workgroups per compute unit (spills: 25.8).
 template <int B1>
-__global__ __launch_bounds__(kBigThreads, JF_RV_BIG_IFFT_HALVES ? JF_RV_BIG_IFFT_WGS : 0) void reverb_big_ifft_kernel(const ReverbBigParams P) {
+__global__ __launch_bounds__(kBigThreads, JF_RV_BIG_IFFT_WGS) void reverb_big_ifft_kernel(const ReverbBigParams P) {
     __shared__ float2 s_buf[1][rv_big_len(B1)];
     const int tid0 = threadIdx.x;
     BigTwiddles<B1, kBigThreads> tw;
@@ -1137,7 +982,7 @@ __global__ __launch_bounds__(kBigThreads, JF_RV_BIG_IFFT_HALVES ? JF_RV_BIG_IFFT
         const int g = turn;
         const int s = g / P.n_prod, i = g - s * P.n_prod;
         BigIfftInput<B1> in;
-        in.fetch(P, g, tid, JF_RV_BIG_IFFT_HALVES ? 4 : 8);
+        in.fetch(P, g, tid, 4);
         // the true packed pair of bin 0: sum_q X0[anchor + i - q] .* H0[h_first + q] from the compact copies, wave 0's lanes
         // over the partitions (thread 0, which owns bin 0 below, is one of them)
         float2 y0 = make_float2(0.f, 0.f);
@@ -1177,14 +1022,10 @@ __global__ __launch_bounds__(kBigThreads, JF_RV_BIG_IFFT_HALVES ? JF_RV_BIG_IFFT
                 v[0][r] = make_float2(e.x - o.y, e.y + o.x);
             }
         };
-#if JF_RV_BIG_IFFT_HALVES
         untangle(0, 4);
         __builtin_amdgcn_sched_barrier(0);  // (the second half's loads go into the registers the first half has freed)
         in.fetch_y(P, g, tid, 4, 8);
         untangle(4, 8);
-#else
-        untangle(0, 8);
-#endif
         if (tid == 0) v[0][0] = make_float2(0.5f * (y0.x + y0.y), 0.5f * (y0.x - y0.y));
         cfft_wg<B1, +1, kBigThreads, true>(v, s_buf, tw, s_w8, tid);  // (only z[m], m >= B1 / 2, is read below)
         {
@@ -1192,25 +1033,16 @@ __global__ __launch_bounds__(kBigThreads, JF_RV_BIG_IFFT_HALVES ? JF_RV_BIG_IFFT
             // overlap-save: time samples B1 .. 2 B1 - 1 = z[m], m >= B1 / 2
             if (!P.to_wet) {
                 float *fut = P.fut + (size_t)s * P.Fn * B1 + (size_t)((P.fut_first + i) % P.Fn) * B1;
-#if JF_RV_BIG_WIDE_STORE
 #pragma unroll
                 for (int u = 0; u < B1 / 4 / kBigThreads; u++) {  // z[m], z[m + 1]: four consecutive samples, one 16-byte store
                     const int m = B1 / 2 + 2 * tid + u * (2 * kBigThreads);
                     const float2 a = zt[rv_big_at(m)], b = zt[rv_big_at(m + 1)];
                     *reinterpret_cast<float4 *>(fut + (2 * m - B1)) = make_float4(a.x, a.y, b.x, b.y);
                 }
-#else
-#pragma unroll
-                for (int u = 0; u < B1 / 2 / kBigThreads; u++) {
-                    const int m = B1 / 2 + tid + u * kBigThreads;
-                    *reinterpret_cast<float2 *>(fut + (2 * m - B1)) = zt[rv_big_at(m)];
-                }
-#endif
             } else {
                 // the wet ring is a multiple of B long and is addressed block by block (mac_finish): a big block may wrap inside
                 float *wet = P.wet + (size_t)s * P.Wr;
                 const int lgB = 31 - __builtin_clz((unsigned)P.B);  // B is 64, 128 or 256
-#if JF_RV_BIG_WIDE_STORE
 #pragma unroll
                 for (int u = 0; u < B1 / 4 / kBigThreads; u++) {  // four consecutive samples (never across a block: B >= 64)
                     const int m = B1 / 2 + 2 * tid + u * (2 * kBigThreads);
@@ -1222,18 +1054,6 @@ __global__ __launch_bounds__(kBigThreads, JF_RV_BIG_IFFT_HALVES ? JF_RV_BIG_IFFT
                     const float2 a = zt[rv_big_at(m)], b = zt[rv_big_at(m + 1)];
                     *reinterpret_cast<float4 *>(wet + w0 + (n - kb * P.B)) = make_float4(a.x, a.y, b.x, b.y);
                 }
-#else
-#pragma unroll
-                for (int u = 0; u < B1 / 2 / kBigThreads; u++) {
-                    const int m = B1 / 2 + tid + u * kBigThreads;
-                    const int n = 2 * m - B1;                   // sample inside the big block
-                    const int kb = n >> lgB;                     // n / B (once per pair)
-                    const int k = P.wet_k0 + P.M * i + kb;       // block of the call
-                    int w0 = in.c0 + k * P.B;                    // c0 < Wr and k B < Wr: one conditional subtraction
-                    w0 = w0 >= P.Wr ? w0 - P.Wr : w0;
-                    *reinterpret_cast<float2 *>(wet + w0 + (n - kb * P.B)) = zt[rv_big_at(m)];
-                }
-#endif
             }
         }
         __syncthreads();  // the buffer is read out before the next turn writes it
@@ -1443,21 +1263,16 @@ static void launch_big_transforms_t(const ReverbBigParams &P, hipStream_t st) {
 // products of one launch (tiles of 16 when there are several, else one by one) and their inverse transforms
 template <int B1>
 static void launch_big_products_t(const ReverbBigParams &P, hipStream_t st) {
-    [[maybe_unused]] constexpr int per_spec = B1 / (64 * kBigMacWaves);
-    [[maybe_unused]] constexpr int per_spec_tiled = B1 / (64 * kBigMacWavesTiled);
+    constexpr int per_spec = B1 / (64 * kBigMacWaves);
     if (P.n_prod >= 4) {
         const int tiles = (P.n_prod + 15) / 16;
-#if JF_RV_BIG_MAC_LDS_H
         const int grid = (B1 / 64) * tiles * ((P.S + kBigMacWavesTiled - 1) / kBigMacWavesTiled);
-#else
-        const int grid = per_spec_tiled * tiles * P.S;
-#endif
         hipLaunchKernelGGL((reverb_big_mac_kernel<B1, 16>), dim3(grid), dim3(64 * kBigMacWavesTiled), 0, st, P);
     } else {
         // beside the blocks of one-block calls (mac_wgs > 0: the side stream) the plain form, narrow: 83 us per launch at
         // configs[4], spread thinly over four blocks -- the shared form is done in 37 us and the block it meets pays for it
         // (mean 23.9 against 24.5 us per block, p99 38 against 35.5: profiles/r05/reverb_realtime.md); in line the shared form
-        if (JF_RV_BIG_MAC1_SHARED && P.mac_wgs == 0) {
+        if (P.mac_wgs == 0) {
             const int n_items = (B1 / 64) * P.n_prod * ((P.S + kBigMacWaves - 1) / kBigMacWaves);
             hipLaunchKernelGGL((reverb_big_mac1_kernel<B1>), dim3(n_items), dim3(64 * kBigMacWaves), 0, st, P);
         } else {

@@ -13,60 +13,29 @@ JF_DEV float2 rv_sub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b
 JF_DEV float2 rv_mul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 JF_DEV float2 rv_mulc(float2 a, float2 b) { return make_float2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); }
 
-// acc += x * h (complex): four f32 FMAs.  The packed form (two v_pk_fma_f32 with op_sel broadcasts, pcmac of
-// jf_packed.h; JF_RV_SCALAR_MAC=0) runs the tiled kernel in the same time (profiles/r02_experiments.md section 4) but
-// needs even-aligned register pairs for the window: 128 VGPRs and 20 B of scratch where this form takes 124 and none.
 typedef c2 rv_v2;
-#ifndef JF_RV_SCALAR_MAC
-#define JF_RV_SCALAR_MAC 1
-#endif
-[[maybe_unused]] JF_DEV void rv_cmac(rv_v2 &acc, rv_v2 x, rv_v2 h) {
-#if JF_RV_SCALAR_MAC
-    acc.x = __builtin_fmaf(x.x, h.x, acc.x);
-    acc.y = __builtin_fmaf(x.x, h.y, acc.y);
-    acc.x = __builtin_fmaf(-x.y, h.y, acc.x);
-    acc.y = __builtin_fmaf(x.y, h.x, acc.y);
-#else
-    acc = pcmac(x, h, acc);
-#endif
-}
 
 // The big partitions' products (reverb_big_mac_kernel): the four FMAs of a complex product as two v_pk_fma_f32 with op_sel
 // broadcasts -- the same operations per product and component in the same order, so the sums are the same bit for bit as
-// with four v_fma_f32 (-DJF_RV_BIG_SCALAR_MAC=1).  Round 4, config 5's batch shape, rocprofv3, 320 launches each, twice:
+// with four v_fma_f32 (tried: JF_RV_BIG_SCALAR_MAC=1, the first line below).  Round 4, config 5's batch shape, rocprofv3, 320 launches each, twice:
 //   four v_fma_f32, loads scheduled by the compiler           77.4 us   (98 registers)
 //   two v_pk_fma_f32, loads left where the compiler puts them 120.2 us  (it does not move loads across the asm statements:
 //                                                                        every step waited for its own loads)
 //   two v_pk_fma_f32, loads JF_RV_BIG_PREFETCH steps ahead    72.6 / 71.3 / 78.1 us for 2 / 4 / 8 steps (86 registers at 4)
 // What is left is the stream itself: 247 MB of delay line and 67 MB of products per launch at 4.7 TB/s.
-#ifndef JF_RV_BIG_SCALAR_MAC
-#define JF_RV_BIG_SCALAR_MAC 0
-#endif
-#ifndef JF_RV_BIG_PREFETCH
-#define JF_RV_BIG_PREFETCH 4
-#endif
 // reverb_big_mac_kernel: the delay line's spectra -- 247 MB per launch at config 5's batch shape, each read ONCE -- as non-temporal
 // loads.  The product kernel itself gains 1-4 % (69.3 against 70.4-72.8 us); every kernel BEHIND it gains more, because the
 // stream no longer washes their data out of the L2 and the Infinity Cache: inverse transforms 29.5 -> 26.3 us, forward 28.2 ->
 // 25.9, small transforms 12.4 -> 10.8, the spatialiser 136.8 -> 132.9; the step 0.2877-0.2912 -> 0.2744 ms (one box, one
-// call, A B C A B: profiles/r05/reverb_batch.md)
-#ifndef JF_RV_BIG_NT_X
-#define JF_RV_BIG_NT_X 1
-#endif
-#ifndef JF_RV_BIG_NT_Y
-#define JF_RV_BIG_NT_Y 0  // the inverse transforms' reads of the products (each read once, by them)
-#endif
-// reverb_big_fft_kernel: the split's twiddles loaded before the transform instead of behind its last pass: 45.4 -> 42.4 us per
-// launch at config 5's batch shape (rocprofv3, 320 launches, twice; -DJF_RV_BIG_SPLIT_TW_EARLY=0 is the old form)
-#ifndef JF_RV_BIG_SPLIT_TW_EARLY
-#define JF_RV_BIG_SPLIT_TW_EARLY 1
-#endif
-[[maybe_unused]] JF_DEV c2 pfma_re(c2 x, c2 h, c2 acc) {  // acc + (x.re h.re, x.re h.im)
+// call, A B C A B: profiles/r05/reverb_batch.md; tried: plain loads, JF_RV_BIG_NT_X=0, the first figures).  The same hint on the
+// inverse transforms' reads of the products (tried: JF_RV_BIG_NT_Y=1) moves time from the forward transforms (29 -> 25 us)
+// to the inverse (26 -> 33): not kept (same file).
+JF_DEV c2 pfma_re(c2 x, c2 h, c2 acc) {  // acc + (x.re h.re, x.re h.im)
     c2 r;
     asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1]" : "=v"(r) : "v"(x), "v"(h), "v"(acc));
     return r;
 }
-[[maybe_unused]] JF_DEV c2 pfma_im_rot(c2 x, c2 h, c2 acc) {  // acc + (-x.im h.im, x.im h.re)
+JF_DEV c2 pfma_im_rot(c2 x, c2 h, c2 acc) {  // acc + (-x.im h.im, x.im h.re)
     c2 r;
     asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[0,1,0]" : "=v"(r) : "v"(x), "v"(h), "v"(acc));
     return r;

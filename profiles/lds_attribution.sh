@@ -2,7 +2,9 @@
 # Which stage owns the LDS bank conflicts of fused_pair_kernel?  (13.6 % of LDS-active cycles.)
 #  1. PMC of the debug kernels that run the same device code in isolation (profiles/lds_attribution.py)
 #  2. PMC of the fused kernel as shipped and with the table-based distance factor switched off
-#     (variant TABLE0 = -DJF_TABLE_DISTANCE=0: minimax sin/cos, no LDS gather)
+#     (variant TABLE0 = a `make variant TAG=TABLE0 KFLAGS=-DJF_TABLE_DISTANCE=0` build: minimax sin/cos, no LDS gather.
+#     The switch is retired: build the variant at commit cf3666395f6e, the last tree that carries it -- profiles/README.md,
+#     "Retired build switches")
 # usage (through gpurun): bash profiles/lds_attribution.sh
 REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/lds_attr
