@@ -202,6 +202,62 @@ int jf_sofa_taps(const jf_sofa_set *set);
 int jf_sofa_table(const jf_sofa_set *set, float tol_deg, jf_grid_layout *layout, float *hrir, int taps);
 int jf_engine_create_sofa(const jf_config *cfg, const char *path, float tol_deg, jf_engine **out);
 
+/*
+ * HRTF sets measured on ARBITRARY directions -- "any HRTF database" (FuturePlans.md:21) for the sets that are not rings of
+ * uniform azimuth steps (interaural-polar sets such as CIPIC, Lebedev / Gauss / Fibonacci grids, ring sets with missing or
+ * re-measured directions), which jf_grid_from_positions, jf_sofa_table and jf_engine_create_sofa refuse.  The reference
+ * hard-codes KEMAR's rings (hrtf_signals.cu:7-12) and its index/weight rule is a rule of those rings (SoundSource.cu:65-105);
+ * a cloud has its own rule:
+ *   - A cloud is n directions (azimuth, elevation) in degrees, 4 <= n <= JF_CLOUD_MAX_DIRECTIONS, elevations in [-90, 90],
+ *     azimuths in the engine's own sense (90 = right, as KEMAR's file names).  Direction i is table row i: hrir[i] belongs to
+ *     it, nothing is re-ordered.
+ *   - The directions are triangulated once, on the host, in double: the spherical Delaunay triangulation = the faces of the
+ *     convex hull of the unit vectors, 2n - 4 triangles oriented outward.  A gap in the coverage (no measurements below -40
+ *     degrees, say) is closed by the hull's own faces across it.  Directions that are coplanar in fours (two azimuths on two
+ *     rings: every latitude/longitude or interaural-polar set) are triangulated as they are, without jitter.  Refused with
+ *     JF_ERR_ARG and a text in jf_last_error(NULL): fewer than 4 or more than JF_CLOUD_MAX_DIRECTIONS directions, non-finite
+ *     values, elevations outside [-90, 90], two directions closer than tol_deg (tol_deg below 0.001 counts as 0.001; a pole
+ *     given twice is such a pair), and a set whose hull does not hold the origin strictly inside (a hemisphere only).
+ *   - A position p (unit vector of (ele, azi)) is filtered with the three measurements of the triangle (a, b, c) that contains
+ *     it, weights lambda = [a b c]^-1 p normalised to sum 1 (planar barycentric weights of the central projection: continuous
+ *     across edges).  THREE terms, in the triangle's vertex order (from its lowest row on, outward); a term of weight 0 is
+ *     carried, not dropped.  The triangle is found by a walk from a seed cell; where float32 puts p a hair outside every
+ *     triangle along an edge, the visited triangle of greatest minimum lambda answers, negative weights clamped to 0 and the
+ *     rest renormalised.  Every (ele, azi) with ele in [-90, 90] and |azi| < 1e6 gets an answer -- weights >= 0 that sum to 1
+ *     within a few ulp, the same answer every time; any other position is silence, as a position the ring rule cannot
+ *     interpolate.  No libm on this path: host and device run the same float32 steps (csrc/jf_cloud_rule.h), so
+ *     jf_cloud_interpolation / jf_cloud_pick give bit for bit what the kernels use.
+ *   - JF_MODE_FD_BASIC on a cloud takes the containing triangle's vertex of greatest weight (the lowest row on a tie): the
+ *     nearest measurement, except in strongly obtuse triangles.
+ *   - A cloud engine runs every entry point of this header as an engine on a grid of its own does (the setters accept
+ *     elevations in [-90, 90]; PAD_LEN 1024 and 2048; the reverb at PAD_LEN 1024), with two exceptions: it never builds the
+ *     pre-interpolated rows (JF_FLAG_NO_INTERP_TABLE is implied), and jefferson_group.h does not take clouds.
+ */
+#define JF_CLOUD_MAX_DIRECTIONS 16384
+typedef struct jf_cloud jf_cloud; /* directions + triangulation + the kernels' look-up tables, host memory */
+int jf_cloud_create(size_t n, const float *azimuth_deg, const float *elevation_deg, float tol_deg, jf_cloud **out);
+void jf_cloud_destroy(jf_cloud *c);
+/* n: the table rows of an engine on this cloud (NUM_HRTF, Universal.cuh:4, is KEMAR's 710), or JF_ERR_ARG */
+int jf_cloud_rows(const jf_cloud *c);
+/* the triangulation: returns 2n - 4 and, if tri != NULL, writes tri[2n - 4][3] table rows, every triangle outward and from
+ * its lowest row on, the triangles in ascending order (what hrtf_signals.cu:7-12 is for KEMAR's rings: the set's geometry) */
+int jf_cloud_triangles(const jf_cloud *c, int *tri);
+/* interpolationCalculations (SoundSource.cu:65-105) on a cloud: returns the number of terms (3; 0 for a position without
+ * an answer, rows and w then zero) -- the host twin of the kernels' rule */
+int jf_cloud_interpolation(const jf_cloud *c, float ele, float azi, int rows[3], float w[3]);
+/* pick_hrtf (hrtf_signals.cu:20-51) on a cloud: the row JF_MODE_FD_BASIC filters with, or JF_ERR_RANGE */
+int jf_cloud_pick(const jf_cloud *c, float ele, float azi);
+/* jf_engine_create (read_hrtf_signals + transform_hrtfs, hrtf_signals.cu:107-153, :248) for a set on a cloud: hrir
+ * [jf_cloud_rows][2][taps].  The engine keeps its own copy of the cloud's tables; the cloud may be destroyed afterwards. */
+int jf_engine_create_cloud(const jf_config *cfg, const jf_cloud *c, const float *hrir, int taps, jf_engine **out);
+/* A SOFA set as a cloud (the loader loop hrtf_signals.cu:107-153 for a file the ring door refuses): rows in FILE order, row
+ * azimuth = 360 - SOFA azimuth, hrir [M][2][taps] (may be NULL: the cloud only) with whole-sample Data.Delay applied; the
+ * same refusals as jf_sofa_table (two receivers, 44100 Hz, whole delays), and jf_cloud_create's for the directions. */
+int jf_sofa_cloud(const jf_sofa_set *set, float tol_deg, jf_cloud **out, float *hrir, int taps);
+/* jf_sofa_read, jf_sofa_cloud, jf_engine_create_cloud (read_hrtf_signals, hrtf_signals.cu:107-153, from a SOFA file of any
+ * directions); cfg->hrtf_len must hold jf_sofa_taps */
+int jf_engine_create_sofa_cloud(const jf_config *cfg, const char *path, float tol_deg, jf_engine **out);
+
 /* closeEverything() / cleanup_hrtf_buffers() / ~GPUSoundSource (hrtf_signals.cu:100-105, GPUSoundSource.cu:532-548). */
 void jf_engine_destroy(jf_engine *e);
 

@@ -169,11 +169,17 @@ int jf_debug_count_desc_flags(jf_engine *e, int n_items, int mask);
  * R[512]}), starting at `first_row`: rows 0..709 are the measured ones, row 710 + (ele + 40) * 360 + azi the
  * pre-interpolated filter of the whole-degree position (ele, azi). */
 int jf_debug_read_table_rows(jf_engine *e, int first_row, int n, float *out /* n*512*4 */);
+/* Triangle records the cloud rule's walk reads for the position (ele, azi) -- 1 = the seed cell's triangle holds it -- or 0
+ * for a position without an answer (profiles/cloud_bench.py: mean and maximum walk).  On a cloud engine
+ * jf_debug_set_interp_table(e, 1 or 2) returns JF_ERR_ARG: no pre-interpolated rows. */
+int jf_debug_cloud_walk(const jf_cloud *c, float ele, float azi);
 /* Copy of the device HRTF spectrum table in the REFERENCE layout
  * fft_hrtf[(j*2 + ear)*Nc + k] (hrtf_signals.cu:90-98), complex64 -> 2 floats. */
 int jf_debug_read_table(jf_engine *e, float *out /* 710*2*Nc*2 */);
 /* Runs only the index/weight kernel on n latched (ele, azi) pairs:
  * rows[n][4], weights[n][4], nterms[n] (<= 0: not interpolable). */
+/* On a cloud engine (jf_engine_create_cloud) the descriptor's form: 4 terms, the three of jf_cloud_interpolation in their
+ * order and the first row again with weight 0 (the fused kernels take 1, 2 or 4 terms). */
 int jf_debug_interp_device(jf_engine *e, int n, const float *ele, const float *azi,
                            int *rows, float *weights, int *nterms);
 /* Forward real FFT of n windows of PAD_LEN samples with the kernel's LDS FFT

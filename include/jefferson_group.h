@@ -11,6 +11,8 @@
  *
  * Implemented by libjefferson_group.so (jefferson-2.0_amd/csrc/jf_group.c), which links libjefferson_hip.so
  * and librccl.so.  Source indices below are GLOBAL (0 .. n_sources - 1 of the whole job).
+ * HRTF sets: KEMAR, grids of rings and SOFA files of rings (below).  Sets on arbitrary directions (jefferson.h: jf_cloud,
+ * jf_engine_create_cloud) are out of scope here: a group has no cloud door.
  */
 #ifndef JEFFERSON_GROUP_H
 #define JEFFERSON_GROUP_H

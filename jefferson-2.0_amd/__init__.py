@@ -53,6 +53,14 @@ class JfSofaSet(C.Structure):
                 ("distance", C.POINTER(C.c_float)), ("delay", C.POINTER(C.c_float)), ("conventions", C.c_char * 48)]
 
 
+class JfCloudOpaque(C.Structure):
+    """jf_cloud: an opaque handle of its own type, so that it cannot be mistaken for an engine's"""
+    _fields_ = []
+
+
+_cloud = C.POINTER(JfCloudOpaque)
+
+
 class JfError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"jefferson error {code}: {msg}")
@@ -72,6 +80,16 @@ _SIGS = {
     "jf_sofa_table": (C.c_int, [C.POINTER(JfSofaSet), C.c_float, C.c_void_p, _f, C.c_int]),
     "jf_debug_hdf5_read": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(C.POINTER(C.c_double)), _i, C.POINTER(C.c_ulonglong)]),
     "jf_debug_hdf5_attr": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t]),
+    "jf_cloud_create": (C.c_int, [C.c_size_t, _f, _f, C.c_float, C.POINTER(_cloud)]),
+    "jf_cloud_destroy": (None, [_cloud]),
+    "jf_cloud_rows": (C.c_int, [_cloud]),
+    "jf_cloud_triangles": (C.c_int, [_cloud, _i]),
+    "jf_cloud_interpolation": (C.c_int, [_cloud, C.c_float, C.c_float, _i, _f]),
+    "jf_cloud_pick": (C.c_int, [_cloud, C.c_float, C.c_float]),
+    "jf_engine_create_cloud": (C.c_int, [C.POINTER(JfConfig), _cloud, _f, C.c_int, C.POINTER(C.c_void_p)]),
+    "jf_sofa_cloud": (C.c_int, [C.POINTER(JfSofaSet), C.c_float, C.POINTER(_cloud), _f, C.c_int]),
+    "jf_engine_create_sofa_cloud": (C.c_int, [C.POINTER(JfConfig), C.c_char_p, C.c_float, C.POINTER(C.c_void_p)]),
+    "jf_debug_cloud_walk": (C.c_int, [_cloud, C.c_float, C.c_float]),
     "jf_kemar_grid": (C.c_int, [C.POINTER(JfHrtfGrid)]),
     "jf_grid_rows": (C.c_int, [C.POINTER(JfHrtfGrid)]),
     "jf_grid_from_positions": (C.c_int, [C.c_size_t, _f, _f, C.c_float, C.c_void_p, _i]),
@@ -306,6 +324,16 @@ class SofaSet:
         n = lay.n_rings
         return Grid(list(lay.ring_elevation[:n]), list(lay.ring_count[:n]), list(lay.ring_step[:n])), hrir
 
+    def cloud(self, tol_deg=0.05, taps=None):
+        """(Cloud, hrir [M][2][taps]) for Engine(..., hrir=, cloud=), rows in file order: include/jefferson.h: jf_sofa_cloud"""
+        taps = self.taps() if taps is None else taps
+        hrir = np.zeros((self.M, 2, taps), np.float32)
+        h = _cloud()
+        rc = lib().jf_sofa_cloud(C.byref(self.c), tol_deg, C.byref(h), _fp(hrir), taps)
+        if rc:
+            raise JfError(rc, lib().jf_last_error(None).decode())
+        return Cloud._adopt(h), hrir
+
     def close(self):
         if self.c is not None:
             lib().jf_sofa_release(C.byref(self.c))
@@ -392,15 +420,90 @@ class Grid:
         return lib().jf_grid_pick(C.byref(self.c), ele, azi)
 
 
+class Cloud:
+    """include/jefferson.h: jf_cloud -- a set on arbitrary directions: direction i is table row i."""
+
+    def __init__(self, azimuth_deg, elevation_deg, tol_deg=0.05):
+        self.h = None
+        az = np.ascontiguousarray(azimuth_deg, np.float32)
+        el = np.ascontiguousarray(elevation_deg, np.float32)
+        assert az.shape == el.shape and az.ndim == 1
+        h = _cloud()
+        rc = lib().jf_cloud_create(len(az), _fp(az), _fp(el), tol_deg, C.byref(h))
+        if rc:
+            raise JfError(rc, lib().jf_last_error(None).decode())
+        self.h = h
+
+    @classmethod
+    def _adopt(cls, h):
+        c = cls.__new__(cls)
+        c.h = h
+        return c
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().jf_cloud_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def rows(self):
+        return lib().jf_cloud_rows(self.h)
+
+    def triangles(self):
+        """[2n - 4][3] table rows, every triangle outward"""
+        n = lib().jf_cloud_triangles(self.h, None)
+        tri = np.zeros((n, 3), np.int32)
+        assert lib().jf_cloud_triangles(self.h, _ip(tri)) == n
+        return tri
+
+    def interpolation(self, ele, azi):
+        """(rows[3], w[3]) or None for a position without an answer"""
+        rows = np.zeros(3, np.int32)
+        w = np.zeros(3, np.float32)
+        n = lib().jf_cloud_interpolation(self.h, ele, azi, _ip(rows), _fp(w))
+        return (rows, w) if n > 0 else None
+
+    def interpolation_many(self, ele, azi):
+        """rows [n][3], w [n][3], terms [n] for arrays of positions"""
+        ele = np.ascontiguousarray(ele, np.float32)
+        azi = np.ascontiguousarray(azi, np.float32)
+        n = len(ele)
+        rows = np.zeros((n, 3), np.int32)
+        w = np.zeros((n, 3), np.float32)
+        nt = np.zeros(n, np.int32)
+        fn, h = lib().jf_cloud_interpolation, self.h
+        for i in range(n):
+            nt[i] = fn(h, ele[i], azi[i], rows[i].ctypes.data_as(_i), w[i].ctypes.data_as(_f))
+        return rows, w, nt
+
+    def pick(self, ele, azi):
+        return lib().jf_cloud_pick(self.h, ele, azi)
+
+    def walk(self, ele, azi):
+        """triangle records the rule's walk reads for this position (include/jefferson_debug.h: jf_debug_cloud_walk)"""
+        return lib().jf_debug_cloud_walk(self.h, ele, azi)
+
+
 class Engine:
     """Thin object wrapper; method names follow the C ABI."""
 
     def __init__(self, B, hrtf_len, n_sources, hrir=None, hrir_dir=None, device=0, max_batch_blocks=1, flags=0, grid=None,
-                 sofa=None, sofa_tol_deg=0.05):
+                 sofa=None, sofa_tol_deg=0.05, cloud=None, sofa_cloud=None):
         L = lib()
         cfg = JfConfig(B, hrtf_len, n_sources, device, max_batch_blocks, flags)
         h = C.c_void_p()
-        if sofa is not None:
+        if sofa_cloud is not None:
+            rc = L.jf_engine_create_sofa_cloud(C.byref(cfg), os.fsencode(sofa_cloud), sofa_tol_deg, C.byref(h))
+        elif cloud is not None:
+            hrir = np.ascontiguousarray(hrir, np.float32)
+            assert hrir.ndim == 3 and hrir.shape[0] == cloud.rows() and hrir.shape[1] == 2  # the C side reads rows x 2 x taps floats
+            rc = L.jf_engine_create_cloud(C.byref(cfg), cloud.h, _fp(hrir), hrir.shape[2], C.byref(h))
+        elif sofa is not None:
             rc = L.jf_engine_create_sofa(C.byref(cfg), os.fsencode(sofa), sofa_tol_deg, C.byref(h))
         elif grid is not None:
             hrir = np.ascontiguousarray(hrir, np.float32)

@@ -27,6 +27,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "jf_cloud_rule.h"
+
 namespace jf {
 
 constexpr int kN = 1024;       // PAD_LEN (Universal.cuh:12)
@@ -116,6 +118,9 @@ struct RingTable {
     // KEMAR only: [kNumElev][kPickAzi] device table (null: search): the table row nearest to integer azimuth a on ring e --
     // what pick_hrtf's search over a ring (hrtf_signals.cu:20-51) returns for (elevation of e, a); built by that search
     const short *pick;
+    // A set on arbitrary directions (jf_engine_create_cloud): cloud.tri != null, n_rings = 0, kemar = 0, n_rows = the cloud's
+    // directions; every rule of the rings above is replaced by jf_cloud_rule.h's (triangle records and seed cells in HBM)
+    CloudView cloud;
 };
 
 struct FusedParams {

@@ -293,6 +293,8 @@ void destroy_engine(jf_engine *e) {
     (void)hipFree(e->d_traj);
     (void)hipFree(e->d_order);
     (void)hipFree(e->d_pick);
+    (void)hipFree(e->d_cloud_tri);
+    (void)hipFree(e->d_cloud_seed);
     if (e->h_pos_pinned) (void)hipHostFree(e->h_pos_pinned);
     if (e->h_out_pinned) (void)hipHostFree(e->h_out_pinned);
     if (e->h_done) (void)hipHostFree(e->h_done);
@@ -309,8 +311,10 @@ void destroy_engine(jf_engine *e) {
     delete e;
 }
 
-// grid: the table of the HRTF set's measurement grid (null: the reference's KEMAR grid, 710 rows)
-int create_engine(const jf_config *cfg, const RingTable *grid, const float *hrir, int taps, jf_engine **out) {
+// grid: the table of the HRTF set's measurement grid (null: the reference's KEMAR grid, 710 rows); cloud: a set on arbitrary
+// directions instead (its rows and its rule replace the grid's)
+int create_engine(const jf_config *cfg, const RingTable *grid, const float *hrir, int taps, jf_engine **out,
+                  const jf_cloud *cloud = nullptr) {
     if (!cfg || !hrir || !out) return fail(nullptr, JF_ERR_ARG, "null argument");
     *out = nullptr;
     const int B = cfg->frames_per_buffer;
@@ -375,10 +379,28 @@ int create_engine(const jf_config *cfg, const RingTable *grid, const float *hrir
         }
         // (nothing of the engine's behaviour is read from the environment: jefferson_debug.h's setters are the overrides)
         // (never at PAD_LEN 2048: 773 MB of rows; JF_FLAG_NO_INTERP_TABLE is implied there)
-        e->interp_avail = !(cfg->flags & JF_FLAG_NO_INTERP_TABLE) && e->N == kN;
+        // (nor on a cloud: the rows are laid out for whole degrees on KEMAR's elevation range)
+        e->interp_avail = !(cfg->flags & JF_FLAG_NO_INTERP_TABLE) && e->N == kN && !cloud;
         e->interp_use = e->interp_avail ? 2 : 0;
         // the 710 measured rows only; the pre-interpolated ones come with the first run that takes them (ensure_interp_rows)
         e->rt = grid ? *grid : ring_table();
+        if (cloud) {
+            // the engine's own copies of the triangle records and the seed cells, on the host and in HBM
+            e->rt = RingTable{};
+            e->rt.n_rows = (int)cloud->azi.size();
+            e->cloud_tri = cloud->tri;
+            e->cloud_seed = cloud->seed;
+            e->cloud_host = cloud->view;
+            e->cloud_host.tri = e->cloud_tri.data();
+            e->cloud_host.seed = e->cloud_seed.data();
+            JF_HIP(e, hipMalloc(&e->d_cloud_tri, sizeof(CloudTri) * e->cloud_tri.size()));
+            JF_HIP(e, hipMalloc(&e->d_cloud_seed, sizeof(int) * e->cloud_seed.size()));
+            JF_HIP(e, h2d(e, e->d_cloud_tri, e->cloud_tri.data(), sizeof(CloudTri) * e->cloud_tri.size()));
+            JF_HIP(e, h2d(e, e->d_cloud_seed, e->cloud_seed.data(), sizeof(int) * e->cloud_seed.size()));
+            e->rt.cloud = cloud->view;
+            e->rt.cloud.tri = e->d_cloud_tri;
+            e->rt.cloud.seed = e->d_cloud_seed;
+        }
         JF_HIP(e, hipMalloc(&e->d_htab, sizeof(float4) * (size_t)e->rt.n_rows * (N / 2)));
         JF_HIP(e, hipMalloc(&e->d_tw, sizeof(float2) * 1024));
         JF_HIP(e, hipMalloc(&e->d_sigs, sizeof(SrcSignal) * S));
@@ -622,7 +644,87 @@ int jf_engine_create_sofa(const jf_config *cfg, const char *path, float tol_deg,
     });
 }
 
+// ---- sets on arbitrary directions (jf_cloud.cpp; the rule itself: jf_cloud_rule.h) ----
+int jf_cloud_create(size_t n, const float *azimuth_deg, const float *elevation_deg, float tol_deg, jf_cloud **out) {
+    return jf_guard([&]() -> int {
+    if (out) *out = nullptr;
+    if (!azimuth_deg || !elevation_deg || !out) return fail(nullptr, JF_ERR_ARG, "null argument");
+    std::unique_ptr<jf_cloud> c(new jf_cloud());
+    std::string err;
+    const int rc = cloud_build(n, azimuth_deg, elevation_deg, tol_deg, c.get(), &err);
+    if (rc) return fail(nullptr, rc, err);
+    *out = c.release();
+    return JF_OK;
+    });
+}
 
+void jf_cloud_destroy(jf_cloud *c) { delete c; }
+
+int jf_cloud_rows(const jf_cloud *c) { return c ? (int)c->azi.size() : JF_ERR_ARG; }
+
+int jf_cloud_triangles(const jf_cloud *c, int *tri) {
+    if (!c) return JF_ERR_ARG;
+    if (tri)
+        for (size_t t = 0; t < c->tri.size(); t++)
+            for (int k = 0; k < 3; k++) tri[3 * t + k] = c->tri[t].row[k];
+    return (int)c->tri.size();
+}
+
+int jf_cloud_interpolation(const jf_cloud *c, float ele, float azi, int rows[3], float w[3]) {
+    if (!c || !rows || !w) return JF_ERR_ARG;
+    return cloud_interpolation(c, ele, azi, rows, w, nullptr);
+}
+
+int jf_cloud_pick(const jf_cloud *c, float ele, float azi) {
+    if (!c) return JF_ERR_ARG;
+    const int row = cloud_pick_row(c, ele, azi);
+    return row < 0 ? JF_ERR_RANGE : row;
+}
+
+int jf_engine_create_cloud(const jf_config *cfg, const jf_cloud *c, const float *hrir, int taps, jf_engine **out) {
+    return jf_guard([&]() -> int {
+    if (out) *out = nullptr;
+    if (!c) return fail(nullptr, JF_ERR_ARG, "null cloud");
+    return create_engine(cfg, nullptr, hrir, taps, out, c);
+    });
+}
+
+int jf_sofa_cloud(const jf_sofa_set *set, float tol_deg, jf_cloud **out, float *hrir, int taps) {
+    return jf_guard([&]() -> int {
+    if (out) *out = nullptr;
+    if (!set || !out) return fail(nullptr, JF_ERR_ARG, "null argument");
+    std::unique_ptr<jf_cloud> c(new jf_cloud());
+    std::string err;
+    const int rc = sofa_cloud(set, tol_deg, c.get(), hrir, taps, &err);
+    if (rc) return fail(nullptr, rc, err);
+    *out = c.release();
+    return JF_OK;
+    });
+}
+
+int jf_engine_create_sofa_cloud(const jf_config *cfg, const char *path, float tol_deg, jf_engine **out) {
+    return jf_guard([&]() -> int {
+    if (out) *out = nullptr;
+    if (!cfg || !path || !out) return fail(nullptr, JF_ERR_ARG, "null argument");
+    jf_sofa_set set;
+    std::string err;
+    int rc = sofa_read(path, &set, &err);
+    if (rc) return fail(nullptr, rc, err);
+    struct Release {
+        jf_sofa_set *s;
+        ~Release() { sofa_release(s); }
+    } release{&set};
+    const int taps = sofa_taps(&set, &err);
+    if (taps < 0) return fail(nullptr, taps, std::string(path) + ": " + err);
+    if (taps > cfg->hrtf_len)
+        return fail(nullptr, JF_ERR_ARG, std::string(path) + ": impulse responses of " + std::to_string(taps) + " taps, hrtf_len is " + std::to_string(cfg->hrtf_len));
+    std::vector<float> hrir((size_t)set.n_measurements * 2 * (size_t)taps);
+    jf_cloud cloud;
+    rc = sofa_cloud(&set, tol_deg, &cloud, hrir.data(), taps, &err);
+    if (rc) return fail(nullptr, rc, std::string(path) + ": " + err);
+    return create_engine(cfg, nullptr, hrir.data(), taps, out, &cloud);
+    });
+}
 
 int jf_engine_create_from_dir(const jf_config *cfg, const char *hrir_dir, jf_engine **out) {
     return jf_guard([&]() -> int {
@@ -1019,7 +1121,9 @@ int jf_batch_upload_positions(jf_engine *e, int total_blocks, const float *posit
         for (int s = 0; s < e->S; s++) {
             const float *p = positions + 5 * (size_t)s;
             const bool ok = p[0] > -1.0e6f && p[0] < 1.0e6f && p[1] > -1.0e6f && p[1] < 1.0e6f;
-            key[s] = {want_sorted && ok ? host_grid_pick(e->rt, p[0], p[1]) : 0, s};
+            int near = 0;
+            if (want_sorted && ok) near = e->rt.cloud.tri ? std::max(0, cloud_pick(e->cloud_host, p[0], p[1])) : host_grid_pick(e->rt, p[0], p[1]);
+            key[s] = {near, s};
         }
         std::stable_sort(key.begin(), key.end());
         for (int s = 0; s < e->S; s++) e->order[s] = key[s].second;

@@ -167,6 +167,7 @@ int jf_debug_set_interp_table(jf_engine *e, int on) {
     if (!e) return JF_ERR_ARG;
     if (on < 0 || on > 2) return fail(e, JF_ERR_ARG, "0 = never, 1 = always, 2 = decided per run");
     if (on && e->N != kN) return fail(e, JF_ERR_ARG, "no pre-interpolated rows at PAD_LEN 2048");
+    if (on && e->rt.cloud.tri) return fail(e, JF_ERR_ARG, "no pre-interpolated rows on a cloud engine");
     if (on && !e->interp_avail) return fail(e, JF_ERR_STATE, "this engine was created without the pre-interpolated rows");
     e->interp_use = on;  // the mode word of the next run changes with it: descriptors prepared ahead no longer match
     if (on == 1) {       // "always" builds them now (a run under "per run" builds them when it first takes them)
@@ -176,6 +177,14 @@ int jf_debug_set_interp_table(jf_engine *e, int on) {
     }
     return JF_OK;
     });
+}
+
+int jf_debug_cloud_walk(const jf_cloud *c, float ele, float azi) {
+    if (!c) return JF_ERR_ARG;
+    int rows[3], steps = 0;
+    float w[3];
+    cloud_interpolation(c, ele, azi, rows, w, &steps);
+    return steps;
 }
 
 int jf_debug_interp_table(const jf_engine *e) { return e && e->interp_avail ? e->interp_use : 0; }

@@ -19,6 +19,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -136,6 +137,13 @@ struct jf_engine {
     float *d_traj = nullptr;    // [total][S][5]
     short *d_pick = nullptr;    // nearest-azimuth table of the index/weight kernels (RingTable::pick)
     RingTable rt{};             // ring_table() + this engine's device table
+    // a set on arbitrary directions (jf_engine_create_cloud): the engine's own copies of the cloud's triangle records and
+    // seed cells -- on the host (cloud_host: the processing order's nearest rows) and on the device (rt.cloud)
+    std::vector<CloudTri> cloud_tri;
+    std::vector<int> cloud_seed;
+    CloudView cloud_host{};
+    CloudTri *d_cloud_tri = nullptr;
+    int *d_cloud_seed = nullptr;
     int *d_order = nullptr;     // [S] processing order of the pair kernel (a permutation of the sources)
     std::vector<int> order;     // host copy
     bool sorted_order = false;  // d_order is not the identity

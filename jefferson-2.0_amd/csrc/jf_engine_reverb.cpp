@@ -189,7 +189,7 @@ int run_reverb_stage(jf_engine *e, int p, int K, ReverbParams *head_out, bool *h
         e->rv_small_stale = false;
         e->last_catchup = true;
     }
-    plan.head_fused = head_out != nullptr && K == 1 && e->rv_head_fused && e->rv_form == 0 && e->profiling < 2 &&
+    plan.head_fused = head_out != nullptr && K == 1 && e->rv_head_fused && !e->rt.cloud.tri && e->rv_form == 0 && e->profiling < 2 &&
                       e->rv_P <= kRvFusedHeadMax && rt_waves_per_wg(e->S) == 8 && (e->B == 64 || e->B == 128 || e->B == 256);
     {
         const hipError_t q = launch_reverb(R, &plan, e->stream, &e->last_rv_form);

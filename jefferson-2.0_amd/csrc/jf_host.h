@@ -56,11 +56,33 @@ struct ReverbSchedule {
 };
 ReverbSchedule host_reverb_schedule(long long j0, int K, int M, long long fut_m);
 
+}  // namespace jf
+
+// A set on arbitrary directions (include/jefferson.h: jf_cloud; jf_cloud.cpp): the directions as given (direction i = table
+// row i), the triangle records and the seed cells the rule walks (jf_cloud_rule.h) -- what an engine uploads as they are.
+// `view` points into tri and seed: a jf_cloud lives on the heap and is never copied.
+struct jf_cloud {
+    std::vector<float> azi, ele;
+    std::vector<jf::CloudTri> tri;
+    std::vector<int> seed;
+    jf::CloudView view{};
+    jf_cloud() = default;
+    jf_cloud(const jf_cloud &) = delete;
+    jf_cloud &operator=(const jf_cloud &) = delete;
+};
+namespace jf {
+// the spherical Delaunay triangulation (convex hull in double), records, seed cells; JF_ERR_ARG and a text for a set it refuses
+int cloud_build(size_t n, const float *azi, const float *ele, float tol_deg, jf_cloud *out, std::string *err);
+// host twins of the kernels' rule: terms (3, or 0 for a position without an answer) and the records the walk read
+int cloud_interpolation(const jf_cloud *c, float ele, float azi, int rows[3], float w[3], int *steps);
+int cloud_pick_row(const jf_cloud *c, float ele, float azi);  // -1: no answer
+
 // SOFA files (jf_sofa.cpp; include/jefferson.h: jf_sofa_*)
 }  // namespace jf
 struct jf_sofa_set;
 struct jf_grid_layout;
 namespace jf {
+int sofa_cloud(const ::jf_sofa_set *s, float tol_deg, ::jf_cloud *cloud, float *hrir, int taps, std::string *err);
 int sofa_read(const char *path, ::jf_sofa_set *out, std::string *err);
 void sofa_release(::jf_sofa_set *s);
 int sofa_taps(const ::jf_sofa_set *s, std::string *err);

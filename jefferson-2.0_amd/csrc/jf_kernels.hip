@@ -1425,7 +1425,15 @@ JF_DEV int dev_grid_pick(const RingTable &rt, float ele, float azi) {
 }
 
 // hrtf_signals.cu:20-51 in full: nearest elevation ring, then nearest azimuth on it
+// CLOUD (here, in dev_interp_terms and in make_desc): -1 = a set on rings or on arbitrary directions, decided at run time
+// (rt.cloud.tri); 0 = rings only -- the cloud's code is not compiled in (the real-time kernel's ring instantiations: they are
+// the code they were before clouds existed, registers and all); 1 = a cloud only.
+template <int CLOUD = -1>
 JF_DEV int dev_pick_hrtf(const RingTable &rt, float obj_ele, float obj_azi) {
+    if (CLOUD != 0 && (CLOUD == 1 || rt.cloud.tri != nullptr)) {  // the containing triangle's vertex of greatest weight
+        const int row = cloud_pick(rt.cloud, obj_ele, obj_azi);
+        return row < 0 ? 0 : row;
+    }
     if (!rt.kemar) return dev_grid_pick(rt, obj_ele, obj_azi);
     obj_ele = roundf(obj_ele / 10) * 10;
     float dmin = 1e37f;
@@ -1500,7 +1508,18 @@ JF_DEV bool dev_interp_corrected(const RingTable &rt, float ele, float azi, int 
 JF_DEV int dev_flatten_terms(int h0, int h1, int h2, int h3, float omegaA, float omegaB, float omegaC, float omegaD,
                              float omegaE, float omegaF, int rows[4], float w[4]);
 
+template <int CLOUD = -1>
 JF_DEV int dev_interp_terms(const RingTable &rt, float ele, float azi, int rows[4], float w[4], bool corrected = false) {
+    if (CLOUD != 0 && (CLOUD == 1 || rt.cloud.tri != nullptr)) {
+        // A set on arbitrary directions (jf_cloud_rule.h, shared with the host twin): the three vertices of the triangle that
+        // contains the position.  The fused kernels take 1, 2 or 4 terms: the three travel as four, the fourth the first row
+        // again with weight 0 (it adds +-0 to the sum).
+        int steps;
+        const int n = cloud_terms(rt.cloud, ele, azi, &rows[0], &rows[1], &rows[2], &w[0], &w[1], &w[2], &steps);
+        rows[3] = rows[0];
+        w[3] = 0.0f;
+        return n ? 4 : 0;
+    }
     if (corrected || !rt.kemar) {  // (the reference's rule is a rule of the reference's grid)
         int h[4];
         float om[6];
@@ -1556,6 +1575,7 @@ JF_DEV int dev_flatten_terms(int h0, int h1, int h2, int h3, float omegaA, float
 
 // Descriptor of one work item from its latched position record and the position of the block
 // before (GPUSoundSource.cu:81-90 and :325-335).
+template <int CLOUD = -1>
 JF_DEV void make_desc(const RingTable &rt, int mode, const float *p /* ele, azi, x, y, z */, float old_ele,
                       float old_azi, ItemDesc &d) {
     const float ele = p[0], azi = p[1];
@@ -1563,8 +1583,9 @@ JF_DEV void make_desc(const RingTable &rt, int mode, const float *p /* ele, azi,
     if (mode & 1) {
         // *_FD_BASIC (CPUSoundSource.cpp:50-52,113-142): the nearest table row, weight 1, no
         // distance factor (D = 1), no crossfade
-        const bool ok = (ele > -1.0e6f && ele < 1.0e6f) && (azi > -1.0e6f && azi < 1.0e6f);
-        const int row = ok ? dev_pick_hrtf(rt, ele, azi) : 0;
+        const bool ok = (ele > -1.0e6f && ele < 1.0e6f) && (azi > -1.0e6f && azi < 1.0e6f) &&
+                        (CLOUD == 0 || (CLOUD < 0 && rt.cloud.tri == nullptr) || cloud_position_ok(ele, azi));  // (a cloud answers [-90, 90] only)
+        const int row = ok ? dev_pick_hrtf<CLOUD>(rt, ele, azi) : 0;
 #pragma unroll
         for (int t = 0; t < 4; t++) {
             d.rows_new[t] = d.rows_old[t] = row;
@@ -1578,11 +1599,11 @@ JF_DEV void make_desc(const RingTable &rt, int mode, const float *p /* ele, azi,
         d.flags = 0;
         return;
     }
-    d.n_new = dev_interp_terms(rt, ele, azi, d.rows_new, d.w_new, corrected);
+    d.n_new = dev_interp_terms<CLOUD>(rt, ele, azi, d.rows_new, d.w_new, corrected);
     d.n_old = 0;
     // GPUSoundSource.cu:331-335
     if (old_azi != azi || old_ele != ele) {
-        d.n_old = dev_interp_terms(rt, old_ele, old_azi, d.rows_old, d.w_old, corrected);
+        d.n_old = dev_interp_terms<CLOUD>(rt, old_ele, old_azi, d.rows_old, d.w_old, corrected);
         if (d.n_old == 0) d.n_new = 0;
     } else {
 #pragma unroll
@@ -1646,7 +1667,8 @@ JF_DEV void prep_body(const RingTable &rt, int mode, const float *__restrict__ p
     if (mode & 1) {
         // *_FD_BASIC (CPUSoundSource.cpp:50-52,113-142): the nearest table row, weight 1, no
         // distance factor (D = 1), no crossfade
-        const bool ok = (ele > -1.0e6f && ele < 1.0e6f) && (azi > -1.0e6f && azi < 1.0e6f);
+        const bool ok = (ele > -1.0e6f && ele < 1.0e6f) && (azi > -1.0e6f && azi < 1.0e6f) &&
+                        (rt.cloud.tri == nullptr || cloud_position_ok(ele, azi));  // (a cloud answers [-90, 90] only)
         const int row = ok ? dev_pick_hrtf(rt, ele, azi) : 0;
         rows[0] = rows[1] = rows[2] = rows[3] = row;
         if (!old_half) {
@@ -1868,7 +1890,8 @@ constexpr int kRtWavesFew = 8, kRtWavesMany = 16, kRtFewMaxSources = 512;
 // RV: the reverb stage's head runs inside this kernel (jf_rv_small.h: rv_head_wave): the wave of source s first takes the
 // block through the P partitions of R -- the head of a non-uniformly partitioned response -- and leaves it in the wet ring,
 // then spatialises it: ONE launch per audio block with the reverb on (round 4: the head kernel, 8 us, a launch gap, this kernel).
-template <int NOUT, int RTW, bool RV>
+// CLOUD: the engine's set lies on arbitrary directions (make_desc<1>); the ring instantiations hold none of that code.
+template <int NOUT, int RTW, bool RV, bool CLOUD = false>
 // done (may be null): host-mapped words, one per workgroup; workgroup g stores `seq` into done[g] once its block lies in
 // `out` -- the host then polls these words instead of synchronising the stream (the runtime's completion path costs more
 // than the kernel's arithmetic at one source).
@@ -1893,7 +1916,7 @@ __global__ __launch_bounds__(64 * RTW) void rt_block_kernel(const FusedParams P,
     // weight rule is a long chain in one lane -- both overlap with the twiddle loads of the other lanes
     const int s_first = blockIdx.x * kRtWaves + wave;
     if (lane == 0 && s_first < P.S)
-        make_desc(rt, P.mode, pos + 5 * s_first, P.st_in[s_first].old_ele, P.st_in[s_first].old_azi, s_desc[wave]);
+        make_desc<CLOUD ? 1 : 0>(rt, P.mode, pos + 5 * s_first, P.st_in[s_first].old_ele, P.st_in[s_first].old_azi, s_desc[wave]);
     __syncthreads();
     float2 *buf = s_buf + wave * kWaveLds;
     const int a = lane & 3, i = lane >> 2;
@@ -1903,7 +1926,7 @@ __global__ __launch_bounds__(64 * RTW) void rt_block_kernel(const FusedParams P,
 #pragma unroll 1
     for (int s = s_first; s < P.S; s += gridDim.x * kRtWaves) {
         const float *p = pos + 5 * s;
-        if (lane == 0 && s != s_first) make_desc(rt, P.mode, p, P.st_in[s].old_ele, P.st_in[s].old_azi, s_desc[wave]);
+        if (lane == 0 && s != s_first) make_desc<CLOUD ? 1 : 0>(rt, P.mode, p, P.st_in[s].old_ele, P.st_in[s].old_azi, s_desc[wave]);
         JF_WAVE_LDS_SYNC();
         if constexpr (RV) {
             if constexpr (B == 64 || B == 128 || B == 256) rv_head_wave<B>(R, s, buf, s_tw1024, lane);
@@ -2243,8 +2266,10 @@ hipError_t launch_rt_block(const FusedParams &P, const RingTable &rt, const floa
     const bool few = rt_waves_per_wg(P.S) == kRtWavesFew;
     const dim3 grid(n_wgs), block(64 * (few ? kRtWavesFew : kRtWavesMany));
     float2 *o = reinterpret_cast<float2 *>(out);
+    const bool cloud = rt.cloud.tri != nullptr;
     if (head != nullptr) {
-        if (!few || head->B != P.B || head->K != 1) return hipErrorInvalidValue;
+        // (no instantiation with the reverb's head AND a cloud: run_reverb_stage does not ask for it)
+        if (!few || head->B != P.B || head->K != 1 || cloud) return hipErrorInvalidValue;
         switch (P.B / 64) {
         case 1: hipLaunchKernelGGL((rt_block_kernel<1, kRtWavesFew, true>), grid, block, 0, st, P, rt, pos, o, done, seq, *head); break;
         case 2: hipLaunchKernelGGL((rt_block_kernel<2, kRtWavesFew, true>), grid, block, 0, st, P, rt, pos, o, done, seq, *head); break;
@@ -2255,7 +2280,9 @@ hipError_t launch_rt_block(const FusedParams &P, const RingTable &rt, const floa
     }
     const ReverbParams none{};
 #define JF_RT_LAUNCH(NOUT)                                                                                                          \
-    if (few) hipLaunchKernelGGL((rt_block_kernel<NOUT, kRtWavesFew, false>), grid, block, 0, st, P, rt, pos, o, done, seq, none);  \
+    if (cloud && few) hipLaunchKernelGGL((rt_block_kernel<NOUT, kRtWavesFew, false, true>), grid, block, 0, st, P, rt, pos, o, done, seq, none);  \
+    else if (cloud) hipLaunchKernelGGL((rt_block_kernel<NOUT, kRtWavesMany, false, true>), grid, block, 0, st, P, rt, pos, o, done, seq, none);  \
+    else if (few) hipLaunchKernelGGL((rt_block_kernel<NOUT, kRtWavesFew, false>), grid, block, 0, st, P, rt, pos, o, done, seq, none);  \
     else hipLaunchKernelGGL((rt_block_kernel<NOUT, kRtWavesMany, false>), grid, block, 0, st, P, rt, pos, o, done, seq, none)
     switch (P.B / 64) {
     case 1: JF_RT_LAUNCH(1); break;

@@ -20,7 +20,11 @@
  *                  [--dwell 172] [--rounds 72] [--step 5] [--radius 0.5] [--latency] [--script debugmode2]
  *   <set.sofa>  a name that ends in ".sofa": the HRTF set of a SOFA file instead of the KEMAR directory
  *               (jf_engine_create_sofa; --sofa-tol T: degrees a measurement may lie off its ring's uniform steps, 0.51 --
- *               what sets whose azimuths were rounded to whole degrees, like KEMAR's, need)
+ *               what sets whose azimuths were rounded to whole degrees, like KEMAR's, need).  A set that is refused as
+ *               not a grid of rings (JF_ERR_ARG: interaural-polar sets, Lebedev / Gauss grids, missing directions) goes
+ *               through the cloud door instead (jf_engine_create_sofa_cloud: barycentric weights on the spherical Delaunay
+ *               triangulation of its directions; --cloud-tol T: directions closer than T degrees are refused, 0.05);
+ *               stderr says which rule is in use
  *   --latency  use jf_callback (the CUDA path's one-block latency, Audio.cu:104-117)
  *              instead of jf_process_block (the CPU path's ordering)
  *   --no-pin   leave the thread where the system put it (default: jf_pin_thread_to_device -- on a two-socket host a block
@@ -80,11 +84,13 @@ int main(int argc, char **argv) {
     if (argc < 4) {
         fprintf(stderr, "usage: %s <hrir_dir | set.sofa> <in.wav> <out.wav> [--block B] [--azi A] [--ele E] "
                         "[--dwell N] [--rounds R] [--step D] [--radius r] [--latency] [--batch N] [--script debugmode2] [--no-pin] "
-                        "[--sofa-tol T]\n", argv[0]);
+                        "[--sofa-tol T] [--cloud-tol T]\n"
+                        "  set.sofa: rings of uniform azimuth steps (the ring rule), or any other directions (the cloud rule: "
+                        "barycentric weights on their triangulation)\n", argv[0]);
         return 2;
     }
     int block = 256, dwell = 172, rounds = 72, latency = 0, batch = 0, script = 0, pin = 1;
-    float azi = 3, ele = 5, step = 5, radius = 0.5f, sofa_tol = 0.51f;
+    float azi = 3, ele = 5, step = 5, radius = 0.5f, sofa_tol = 0.51f, cloud_tol = 0.05f;
     for (int i = 4; i < argc; i++) {
         if (!strcmp(argv[i], "--latency")) latency = 1;
         else if (!strcmp(argv[i], "--no-pin")) pin = 0;
@@ -97,6 +103,7 @@ int main(int argc, char **argv) {
         else if (i + 1 < argc && !strcmp(argv[i], "--step")) step = (float)atof(argv[++i]);
         else if (i + 1 < argc && !strcmp(argv[i], "--radius")) radius = (float)atof(argv[++i]);
         else if (i + 1 < argc && !strcmp(argv[i], "--sofa-tol")) sofa_tol = (float)atof(argv[++i]);
+        else if (i + 1 < argc && !strcmp(argv[i], "--cloud-tol")) cloud_tol = (float)atof(argv[++i]);
         else if (i + 1 < argc && !strcmp(argv[i], "--script") && !strcmp(argv[i + 1], "debugmode2")) script = 1, i++;
         else {
             fprintf(stderr, "unknown option %s\n", argv[i]);
@@ -122,7 +129,15 @@ int main(int argc, char **argv) {
     jf_engine *e = NULL;
     const size_t len1 = strlen(argv[1]);
     const int sofa = len1 > 5 && !strcmp(argv[1] + len1 - 5, ".sofa");
-    if ((sofa ? jf_engine_create_sofa(&cfg, argv[1], sofa_tol, &e) : jf_engine_create_from_dir(&cfg, argv[1], &e)) != JF_OK) {
+    int made = sofa ? jf_engine_create_sofa(&cfg, argv[1], sofa_tol, &e) : jf_engine_create_from_dir(&cfg, argv[1], &e);
+    if (sofa && made == JF_OK) fprintf(stderr, "%s: rings of uniform azimuth steps, the ring rule\n", argv[1]);
+    if (sofa && made == JF_ERR_ARG) {
+        /* not a grid of rings: the directions as a cloud */
+        fprintf(stderr, "%s: not a grid of rings (%s)\n", argv[1], jf_last_error(NULL));
+        made = jf_engine_create_sofa_cloud(&cfg, argv[1], cloud_tol, &e);
+        if (made == JF_OK) fprintf(stderr, "%s: %d directions, the cloud rule (barycentric weights on their triangulation)\n", argv[1], jf_table_rows(e));
+    }
+    if (made != JF_OK) {
         fprintf(stderr, "engine: %s\n", jf_last_error(NULL));
         return 1;
     }

@@ -249,6 +249,47 @@ int sofa_table(const jf_sofa_set *s, float tol_deg, jf_grid_layout *layout, floa
     return JF_OK;
 }
 
+// The set as a cloud (include/jefferson.h: jf_sofa_cloud): rows in file order, azimuths in the table's clockwise sense, the
+// same checks of receivers, rate and delays as sofa_table.  hrir may be null (the cloud only).
+int sofa_cloud(const jf_sofa_set *s, float tol_deg, jf_cloud *cloud, float *hrir, int taps, std::string *err) {
+    if (!sofa_ok(s) || !cloud) {
+        *err = "null set or cloud";
+        return JF_ERR_ARG;
+    }
+    if (s->n_receivers != 2) {
+        *err = "a set of " + std::to_string(s->n_receivers) + " receivers (two ears are what the engine renders)";
+        return JF_ERR_IO;
+    }
+    if (s->sample_rate != 44100.0) {
+        *err = "a set sampled at " + std::to_string(s->sample_rate) + " Hz (44100 is what the engine is written for: hrtf_signals.cu:68-75)";
+        return JF_ERR_IO;
+    }
+    const int need = sofa_taps(s, err);
+    if (need < 0) return need;
+    if (hrir && taps < need) {
+        *err = "the set needs " + std::to_string(need) + " taps per impulse response, the table has " + std::to_string(taps);
+        return JF_ERR_ARG;
+    }
+    const size_t M = (size_t)s->n_measurements, N = (size_t)s->n_samples;
+    std::vector<float> az(M);
+    for (size_t i = 0; i < M; i++) {
+        float a = 360.0f - s->azimuth[i];  // counter-clockwise -> the table's clockwise sense
+        if (a >= 360.0f) a -= 360.0f;
+        az[i] = a;
+    }
+    const int rc = cloud_build(M, az.data(), s->elevation, tol_deg, cloud, err);
+    if (rc) return rc;
+    if (hrir) {
+        memset(hrir, 0, sizeof(float) * M * 2 * (size_t)taps);
+        for (size_t i = 0; i < M; i++)
+            for (int ear = 0; ear < 2; ear++) {
+                const size_t shift = (size_t)rintf(s->delay[i * 2 + ear]);
+                memcpy(hrir + (i * 2 + ear) * (size_t)taps + shift, s->ir + (i * 2 + ear) * N, sizeof(float) * N);
+            }
+    }
+    return JF_OK;
+}
+
 int hdf5_read(const char *path, const char *dataset, double **out, int *rank, unsigned long long *dims, std::string *err) {
     char text[256] = "";
     jf_h5 *raw = nullptr;
