@@ -295,6 +295,22 @@ int jf_num_sources(const jf_engine *e);       /* Data::num_sources (DataTag.cuh:
  */
 int jf_source_set_signal(jf_engine *e, int src, const float *mono, size_t n);
 
+/*
+ * LIVE INPUT.  The reference plays what cudaFFT() left resident (copyIncomingBlock, GPUSoundSource.cu:481-513, reads the next
+ * block of that looped buffer), opens its stream without input (Audio.cu:32-33) and ignores paCallback's `input` argument
+ * (Audio.cu:164-175).  A live source is fed block by block instead -- a microphone, a decoder, a mixer bus:
+ *   jf_source_set_live(e, s, 1): source s takes its next samples from the processing calls below (jf_*_in, jf_pa_callback's
+ *     input).  Like jf_source_set_signal it waits for the engine's stream and is called between blocks; the resident signal is
+ *     released and the window stays as it is (a swap mid-stream keeps the reference's window semantics, as a signal swap
+ *     does).  jf_source_set_live(e, s, 0) makes the source resident again and silent, jf_source_set_signal resident with
+ *     that signal.  JF_ERR_ARG for a bad index.  Memory for live sources is allocated when the first one turns live.
+ *   jf_num_live_sources: how many sources are live (n_live); row / channel j of an input feeds the j-th live source in
+ *     ascending source index.
+ * jf_source_reset does to a live source what it does to a resident one.  jefferson_group.h does not offer live sources.
+ */
+int jf_source_set_live(jf_engine *e, int src, int live);
+int jf_num_live_sources(const jf_engine *e);
+
 /* SoundSource::updateFromCartesian(float3) (SoundSource.cu:20-36); callable from a
  * different thread than the audio thread; latched at the next block boundary. */
 int jf_source_set_cartesian(jf_engine *e, int src, float x, float y, float z);
@@ -354,9 +370,28 @@ int jf_collect_block(jf_engine *e, float *out);
 int jf_callback(jf_engine *e, float *out);
 
 /*
+ * The same three calls with the live sources' next block -- the `input` argument paCallback drops (Audio.cu:164-175) as what
+ * copyIncomingBlock (GPUSoundSource.cu:481-513) copies in: in is planar [n_live][frames_per_buffer] float32, row j for the
+ * j-th live source (jf_num_live_sources).  in == NULL feeds every live source a block of zeros (an underrun: the window
+ * still slides).  The input is consumed before the call returns -- jf_submit_block_in included -- so the caller may reuse
+ * its buffer at once.  While paused, in is dropped and nothing is consumed.  On an engine without live sources in is ignored
+ * and the calls ARE the plain ones; on an engine with live sources the plain calls (jf_process_block, jf_submit_block,
+ * jf_callback, jf_process_batch) equal these with in == NULL.  A live source renders bit for bit what a resident source
+ * holding the same samples renders (before its loop point): only where the samples are loaded from differs.  With few
+ * sources and no reverb the block is still ONE kernel launch: the kernel reads the samples from pinned host memory as it
+ * reads the positions.
+ */
+int jf_submit_block_in(jf_engine *e, const float *in);
+int jf_process_block_in(jf_engine *e, const float *in, float *out);
+int jf_callback_in(jf_engine *e, const float *in, float *out);
+
+/*
  * paCallback (Audio.cu:164-175) with PortAudio's PaStreamCallback signature
  * (opaque pointers so portaudio.h is not needed); userData is the jf_engine*
  * (the reference passes &data).  Returns 0 (paContinue).
+ * On an engine with live sources, input != NULL is PortAudio's interleaved float32 [frames][n_live] of a stream opened with
+ * n_live input channels: channel j feeds the j-th live source (jf_callback_in with the same samples, bit for bit); input ==
+ * NULL feeds zeros.  Silence on any error and one block of latency, as without input.
  */
 int jf_pa_callback(const void *input, void *output, unsigned long frames_per_buffer,
                    const void *time_info, unsigned long status_flags, void *user_data);
@@ -411,6 +446,10 @@ float jf_reverb_rms_gain(const float *signal, size_t n, const float *ir, size_t 
  * what the setters held before the batch.  (Setter calls from another thread DURING the batch are overwritten by this.)
  */
 int jf_process_batch(jf_engine *e, int n_blocks, const float *positions, float *out_mix);
+/* callback_func (Audio.cu:94-163) n_blocks times with live input (the `input` of paCallback, Audio.cu:164-175): in is planar
+ * [n_live][n_blocks * frames_per_buffer], row j for the j-th live source; NULL feeds zeros; consumed before the call returns.
+ * Everything else as jf_process_batch, which equals this with in == NULL. */
+int jf_process_batch_in(jf_engine *e, int n_blocks, const float *in, const float *positions, float *out_mix);
 /* Every source's position := its latched record {ele, azi, x, y, z} in records[n_sources][JF_POS_FLOATS] -- what n_sources
  * setter calls (SoundSource.cu:20-54) with these (already rounded) values leave behind.  jf_batch_run, whose positions live on the device, does
  * not move the sources; a host that follows it with per-block calls says where they stand with this or with the setters. */
@@ -424,6 +463,8 @@ int jf_sources_set_latched(jf_engine *e, const float *records);
  * to [n_blocks][2*B] floats, or NULL -> the engine's own buffer, which
  * jf_batch_fetch below copies to the host.  Blocks first_block .. first_block + n_blocks - 1 of
  * the uploaded trajectory are consumed.
+ * The signals must be on the device already: while the engine has a live source (jf_source_set_live) jf_batch_upload_positions
+ * and jf_batch_run return JF_ERR_STATE.
  */
 int jf_batch_upload_positions(jf_engine *e, int total_blocks, const float *positions);
 int jf_batch_run(jf_engine *e, int first_block, int n_blocks, float *d_out_mix);

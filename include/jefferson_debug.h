@@ -136,6 +136,9 @@ int jf_debug_set_reverb_lazy_state(jf_engine *e, int on);
  * (the stream is waited for, the stage is done again by the call that needs it).  Bit-identical.  on = 0: every call runs its
  * own stage first. */
 int jf_debug_set_reverb_ahead(jf_engine *e, int on);
+/* 1 if the next block's stage has been launched and not yet consumed or taken back, else 0.  Never 1 while a source is live
+ * (include/jefferson.h: jf_source_set_live): the next block's input has not arrived. */
+int jf_debug_reverb_ahead_pending(const jf_engine *e);
 /* The schedule of the non-uniformly partitioned reverb for a call of K blocks that starts at absolute block j0, with big blocks
  * of M blocks and TAIL formed up to big block fut_m (host logic only: no engine, no GPU; tests/test_reverb_plan.py replays
  * runs of calls against a model of the rings).  out = {m_lo, n_tr, ma, n_mid, n_ranges, kb0, kn0, kb1, kn1, copy_lo, copy_hi,

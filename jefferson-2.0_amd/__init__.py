@@ -102,6 +102,12 @@ _SIGS = {
     "jf_pad_len": (C.c_int, [C.c_void_p]),
     "jf_num_sources": (C.c_int, [C.c_void_p]),
     "jf_source_set_signal": (C.c_int, [C.c_void_p, C.c_int, _f, C.c_size_t]),
+    "jf_source_set_live": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "jf_num_live_sources": (C.c_int, [C.c_void_p]),
+    "jf_submit_block_in": (C.c_int, [C.c_void_p, _f]),
+    "jf_process_block_in": (C.c_int, [C.c_void_p, _f, _f]),
+    "jf_callback_in": (C.c_int, [C.c_void_p, _f, _f]),
+    "jf_process_batch_in": (C.c_int, [C.c_void_p, C.c_int, _f, _f, _f]),
     "jf_source_set_cartesian": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float]),
     "jf_source_set_spherical": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float]),
     "jf_source_get_position": (C.c_int, [C.c_void_p, C.c_int, _f]),
@@ -155,6 +161,7 @@ _SIGS = {
     "jf_debug_set_reverb_head_fused": (C.c_int, [C.c_void_p, C.c_int]),
     "jf_debug_set_reverb_lazy_state": (C.c_int, [C.c_void_p, C.c_int]),
     "jf_debug_set_reverb_ahead": (C.c_int, [C.c_void_p, C.c_int]),
+    "jf_debug_reverb_ahead_pending": (C.c_int, [C.c_void_p]),
     "jf_debug_set_reverb_side_workgroups": (C.c_int, [C.c_void_p, C.c_int]),
     "jf_sources_set_latched": (C.c_int, [C.c_void_p, _f]),
     "jf_device_numa_node": (C.c_int, [C.c_int, C.POINTER(C.c_int)]),
@@ -555,22 +562,56 @@ class Engine:
     def reset(self, s):
         self._chk(lib().jf_source_reset(self.h, s))
 
-    def process_block(self):
+    def set_live(self, s, on=True):
+        """source s takes its samples from the processing calls' `inp` (include/jefferson.h: jf_source_set_live)"""
+        self._chk(lib().jf_source_set_live(self.h, s, int(bool(on))))
+
+    def n_live(self):
+        return lib().jf_num_live_sources(self.h)
+
+    def _inp(self, inp, n):
+        """[n_live][n] float32 for the *_in calls"""
+        inp = np.ascontiguousarray(inp, np.float32).reshape(-1, n)
+        assert inp.shape[0] == self.n_live(), (inp.shape, self.n_live())
+        return inp
+
+    def process_block(self, inp=None):
         out = np.zeros(2 * self.B, np.float32)
-        self._chk(lib().jf_process_block(self.h, _fp(out)))
+        if inp is None:
+            self._chk(lib().jf_process_block(self.h, _fp(out)))
+        else:
+            inp = self._inp(inp, self.B)
+            self._chk(lib().jf_process_block_in(self.h, _fp(inp), _fp(out)))
         return out
 
-    def submit_block(self):
-        return lib().jf_submit_block(self.h)
+    def submit_block(self, inp=None):
+        if inp is None:
+            return lib().jf_submit_block(self.h)
+        inp = self._inp(inp, self.B)
+        return lib().jf_submit_block_in(self.h, _fp(inp))
 
     def collect_block(self):
         out = np.zeros(2 * self.B, np.float32)
         rc = lib().jf_collect_block(self.h, _fp(out))
         return rc, out
 
-    def callback(self):
+    def callback(self, inp=None):
         out = np.zeros(2 * self.B, np.float32)
-        self._chk(lib().jf_callback(self.h, _fp(out)))
+        if inp is None:
+            self._chk(lib().jf_callback(self.h, _fp(out)))
+        else:
+            inp = self._inp(inp, self.B)
+            self._chk(lib().jf_callback_in(self.h, _fp(inp), _fp(out)))
+        return out
+
+    def pa_callback(self, inp=None):
+        """jf_pa_callback as PortAudio calls it; inp: interleaved [B][n_live] or None (a stream without input)"""
+        out = np.zeros(2 * self.B, np.float32)
+        if inp is not None:
+            inp = np.ascontiguousarray(inp, np.float32)
+            assert inp.size == self.B * self.n_live()
+        lib().jf_pa_callback(None if inp is None else inp.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), self.B,
+                             None, 0, self.h)
         return out
 
     def set_mode(self, mode):
@@ -579,12 +620,16 @@ class Engine:
     def set_pause(self, p):
         self._chk(lib().jf_set_pause(self.h, int(p)))
 
-    def process_batch(self, pos):
+    def process_batch(self, pos, inp=None):
         pos = np.ascontiguousarray(pos, np.float32)
         K, S = pos.shape[0], pos.shape[1]
         assert S == self.S and pos.shape[2] == 5
         mix = np.zeros((K, 2 * self.B), np.float32)
-        self._chk(lib().jf_process_batch(self.h, K, _fp(pos), _fp(mix)))
+        if inp is None:
+            self._chk(lib().jf_process_batch(self.h, K, _fp(pos), _fp(mix)))
+        else:
+            inp = self._inp(inp, K * self.B)
+            self._chk(lib().jf_process_batch_in(self.h, K, _fp(inp), _fp(pos), _fp(mix)))
         return mix
 
     def set_latched(self, records):
@@ -694,6 +739,10 @@ class Engine:
     def set_reverb_ahead(self, on):
         """one-block calls launch the next block's reverb stage behind their own spatialiser (default) or not"""
         self._chk(lib().jf_debug_set_reverb_ahead(self.h, int(bool(on))))
+
+    def reverb_ahead_pending(self):
+        """the next block's reverb stage has been launched ahead and is still pending"""
+        return bool(lib().jf_debug_reverb_ahead_pending(self.h))
 
     def set_reverb_side_workgroups(self, n):
         """workgroups of the product kernel on the reverb's side stream (tuning runs)"""

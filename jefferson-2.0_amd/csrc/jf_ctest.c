@@ -3,6 +3,10 @@
  *   jf_ctest pa      drives jf_pa_callback with PortAudio's argument list (paCallback, Audio.cu:164-175) for 200
  *                    blocks -- positions changed and the stream paused/resumed from the "UI side" in between -- and
  *                    compares every block with jf_callback on a twin engine fed the same calls
+ *   jf_ctest live    a stream opened WITH input: jf_pa_callback with PortAudio's interleaved two-channel input (the argument
+ *                    paCallback drops, Audio.cu:164-175) feeding two live sources beside a resident one, for 200 blocks with
+ *                    a pause and an underrun (input == NULL) in between, against jf_callback_in on a twin engine fed the
+ *                    same samples planar: bit for bit
  *   jf_ctest group N one job over N GPUs (jefferson_group.h: one engine per GPU, RCCL reduce of the mixes) against
  *                    one engine holding all sources: per-block calls (host sum) and batch calls (ncclReduce); then the
  *                    same with the job-wide controls -- mode switch, reverb stage, pause, source reset, clip peak
@@ -119,6 +123,64 @@ static int test_pa(void) {
     jf_engine_destroy(ref);
     free(hrir);
     return (worst == 0 && peak > 0.01 && silent_blocks == 11 && !bad) ? 0 : 1;
+}
+
+static int test_live(void) {
+    enum { B = 256, S = 3, NL = 2, BLOCKS = 200, TAPS = 128 };
+    float *hrir = make_hrir(TAPS);
+    jf_config cfg = {B, 512, S, 0, 1, 0};
+    jf_engine *pa = NULL, *ref = NULL;
+    CHECK(jf_engine_create(&cfg, hrir, TAPS, &pa));
+    CHECK(jf_engine_create(&cfg, hrir, TAPS, &ref));
+    float *sig = make_signal(20000);
+    jf_engine *both[2];
+    both[0] = pa, both[1] = ref;
+    for (int i = 0; i < 2; i++) {
+        /* sources 0 and 2 live (channels 0 and 1 of the stream's input), source 1 resident and looped */
+        CHECK(jf_source_set_signal(both[i], 1, sig, 20000));
+        CHECK(jf_source_set_live(both[i], 0, 1));
+        CHECK(jf_source_set_live(both[i], 2, 1));
+        if (jf_num_live_sources(both[i]) != NL) {
+            fprintf(stderr, "jf_num_live_sources != %d\n", NL);
+            return 1;
+        }
+    }
+    free(sig);
+    float out_pa[2 * B], out_ref[2 * B], inter[B * NL], planar[NL * B];
+    double worst = 0, peak = 0, pk = 0;
+    int silent_blocks = 0;
+    for (int k = 0; k < BLOCKS; k++) {
+        if (k % 7 == 0)
+            for (int s = 0; s < S; s++) {
+                const float azi = (float)((37 * s + 5 * k) % 360), ele = (float)(-20 + 10 * s);
+                CHECK(jf_source_set_spherical(pa, s, ele, azi, 0.5f + 0.2f * s));
+                CHECK(jf_source_set_spherical(ref, s, ele, azi, 0.5f + 0.2f * s));
+            }
+        if (k == 50 || k == 60) {
+            CHECK(jf_set_pause(pa, k == 50));
+            CHECK(jf_set_pause(ref, k == 50));
+        }
+        /* what the device hands PortAudio: [frames][channels] */
+        for (int n = 0; n < B; n++)
+            for (int c = 0; c < NL; c++) planar[c * B + n] = inter[n * NL + c] = frand();
+        const int underrun = k % 40 == 39; /* no input this time: the live sources get zeros */
+        memset(out_pa, 0x7f, sizeof(out_pa));
+        if (jf_pa_callback(underrun ? NULL : inter, out_pa, B, NULL, 0, pa) != 0) {
+            fprintf(stderr, "jf_pa_callback did not return paContinue\n");
+            return 1;
+        }
+        CHECK(jf_callback_in(ref, underrun ? NULL : planar, out_ref));
+        const double d = max_abs_diff(out_pa, out_ref, 2 * B, &pk);
+        if (d > worst) worst = d;
+        if (pk > peak) peak = pk;
+        if (pk == 0) silent_blocks++;
+    }
+    printf("live: %d blocks, max |jf_pa_callback(interleaved input) - jf_callback_in(planar)| = %g, peak %g, %d silent blocks "
+           "(1 primed + 10 paused)\n", BLOCKS, worst, peak, silent_blocks);
+    jf_engine_destroy(pa);
+    jf_engine_destroy(ref);
+    free(hrir);
+    return (worst == 0 && peak > 0.01 && silent_blocks == 11) ? 0 : 1;
 }
 
 static int test_group(int n_gpus) {
@@ -394,10 +456,11 @@ static int test_bench(int n_gpus, int steps) {
 
 int main(int argc, char **argv) {
     if (argc >= 2 && !strcmp(argv[1], "pa")) return test_pa();
+    if (argc >= 2 && !strcmp(argv[1], "live")) return test_live();
     if (argc >= 2 && !strcmp(argv[1], "group")) return test_group(argc >= 3 ? atoi(argv[2]) : 1);
     if (argc >= 2 && !strcmp(argv[1], "shards")) return test_shards(argc >= 3 ? atoi(argv[2]) : 2);
     if (argc >= 2 && !strcmp(argv[1], "bench"))
         return test_bench(argc >= 3 ? atoi(argv[2]) : 1, argc >= 4 ? atoi(argv[3]) : 256);
-    fprintf(stderr, "usage: jf_ctest pa | group [n_gpus] | shards [n_shards] | bench [n_gpus [steps]]\n");
+    fprintf(stderr, "usage: jf_ctest pa | live | group [n_gpus] | shards [n_shards] | bench [n_gpus [steps]]\n");
     return 64;
 }

@@ -265,6 +265,76 @@ int reset_sources(jf_engine *e, int src) {
     return JF_OK;
 }
 
+
+// ---- live input (jf_engine::live) -----------------------------------------------------------------------
+// After any change of which sources are live or of a signal record: the list of live sources, the staging (grown to hold a
+// whole batch window of every live source) and the real-time kernel's records.  The engine's stream is idle (the callers
+// have waited for it).
+static int live_refresh(jf_engine *e) {
+    if (e->live.empty()) return JF_OK;  // no source was ever live
+    e->live_idx.clear();
+    for (int s = 0; s < e->S; s++)
+        if (e->live[s]) e->live_idx.push_back(s);
+    e->n_live = (int)e->live_idx.size();
+    const size_t S = (size_t)e->S, B = (size_t)e->B;
+    size_t want = (size_t)e->n_live * (size_t)e->maxK * B;
+    if (want > e->in_cap) {
+        // (grown by doubling, up to what S live sources need: a host that turns its sources live one by one pins memory a few times)
+        want = std::min(std::max(want, 2 * e->in_cap), S * (size_t)e->maxK * B);
+        if (e->h_in) (void)hipHostFree(e->h_in);
+        e->h_in = e->hd_in = nullptr;
+        e->in_cap = 0;
+        JF_HIP(e, hipHostMalloc(&e->h_in, sizeof(float) * want, hipHostMallocMapped | hipHostMallocCoherent));
+        JF_HIP(e, hipHostGetDevicePointer((void **)&e->hd_in, e->h_in, 0));
+        memset(e->h_in, 0, sizeof(float) * want);
+        e->in_cap = want;
+    }
+    if (!e->d_live_idx) JF_HIP(e, hipMalloc(&e->d_live_idx, sizeof(int) * S));
+    if (!e->d_sigs_rt) JF_HIP(e, hipMalloc(&e->d_sigs_rt, sizeof(SrcSignal) * S));
+    if (e->n_live > 0) JF_HIP(e, h2d(e, e->d_live_idx, e->live_idx.data(), sizeof(int) * e->n_live));
+    std::vector<SrcSignal> rt = e->h_sigs;
+    for (int j = 0; j < e->n_live; j++) rt[e->live_idx[j]] = SrcSignal{e->hd_in + (size_t)j * B, e->B, 0};
+    JF_HIP(e, h2d(e, e->d_sigs_rt, rt.data(), sizeof(SrcSignal) * S));
+    return JF_OK;
+}
+
+// The call's n new samples of every live source: copied to the staging -- the caller's buffer is free when this returns --
+// and from there to the sources' device buffers at their play positions by ONE launch on the engine's stream.
+// in: planar rows of n samples, src_stride floats apart, or (interleaved) [n][n_live]; null: an underrun, zeros.
+static int live_ingest(jf_engine *e, const float *in, bool interleaved, int n, size_t src_stride) {
+    if ((size_t)e->n_live * (size_t)n > e->in_cap) return fail(e, JF_ERR_STATE, "live input: more samples than the staging holds");
+    if (in) {
+        if (interleaved)
+            memcpy(e->h_in, in, sizeof(float) * (size_t)n * e->n_live);
+        else
+            for (int j = 0; j < e->n_live; j++) memcpy(e->h_in + (size_t)j * n, in + (size_t)j * src_stride, sizeof(float) * n);
+    }
+    // the play position the kernels of this call start from: the dry signal's lives in the reverb stage while that is on
+    const int p = e->cur;
+    const int *count = e->rv_P > 0 ? e->d_rv_count[p] : &e->d_state[p][0].count;
+    const int stride = e->rv_P > 0 ? 1 : (int)(sizeof(SrcState) / sizeof(int));
+    JF_HIP(e, launch_live_ingest(e->d_sigs, e->d_live_idx, count, stride, in ? e->hd_in : nullptr, interleaved, e->n_live, n, n,
+                                 e->stream));
+    e->last_ingest = true;
+    return JF_OK;
+}
+
+// One block of every live source into the staging as the real-time kernel reads it: planar [n_live][B], in place.
+static void live_stage_rt(jf_engine *e, const float *in, bool interleaved) {
+    const size_t B = (size_t)e->B;
+    const int nl = e->n_live;
+    if (!in) {
+        memset(e->h_in, 0, sizeof(float) * B * nl);
+    } else if (!interleaved) {
+        memcpy(e->h_in, in, sizeof(float) * B * nl);
+    } else {
+        for (int j = 0; j < nl; j++) {
+            float *row = e->h_in + (size_t)j * B;
+            for (size_t n = 0; n < B; n++) row[n] = in[n * nl + j];
+        }
+    }
+}
+
 namespace {
 
 void destroy_engine(jf_engine *e) {
@@ -295,6 +365,9 @@ void destroy_engine(jf_engine *e) {
     (void)hipFree(e->d_pick);
     (void)hipFree(e->d_cloud_tri);
     (void)hipFree(e->d_cloud_seed);
+    (void)hipFree(e->d_live_idx);
+    (void)hipFree(e->d_sigs_rt);
+    if (e->h_in) (void)hipHostFree(e->h_in);
     if (e->h_pos_pinned) (void)hipHostFree(e->h_pos_pinned);
     if (e->h_out_pinned) (void)hipHostFree(e->h_out_pinned);
     if (e->h_done) (void)hipHostFree(e->h_done);
@@ -783,6 +856,11 @@ int jf_source_set_signal(jf_engine *e, int src, const float *mono, size_t n) {
     e->d_signal[src] = d_new;
     e->h_sigs[src] = n ? SrcSignal{d_new, (int)n_dev, 0} : SrcSignal{e->d_zero, e->N, 0};
     JF_HIP(e, h2d(e, e->d_sigs + src, &e->h_sigs[src], sizeof(SrcSignal)));
+    if (!e->live.empty()) {  // (a live source becomes resident again; the real-time kernel's records follow)
+        e->live[src] = 0;
+        const int rc = live_refresh(e);
+        if (rc) return rc;
+    }
     const int zero = 0;  // count = 0 (cudaPart.cu:198-199 run with a fresh source)
     if (e->rv_P > 0)  // the play position of the dry signal lives in the reverb stage
         JF_HIP(e, h2d(e, e->d_rv_count[e->cur] + src, &zero, sizeof(int)));
@@ -791,6 +869,57 @@ int jf_source_set_signal(jf_engine *e, int src, const float *mono, size_t n) {
     return JF_OK;
     });
 }
+
+int jf_source_set_live(jf_engine *e, int src, int live) {
+    return jf_guard([&]() -> int {
+    DeviceGuard bind(e);
+    if (!valid_src(e, src)) return fail(e, JF_ERR_ARG, "bad source index");
+    const bool is_live = !e->live.empty() && e->live[src];
+    if (is_live == (live != 0)) return JF_OK;
+    if (!live) return jf_source_set_signal(e, src, nullptr, 0);  // resident again, and silent
+    {
+        const int rc = rv_ahead_discard(e);  // (the stage launched ahead read the old signal)
+        if (rc) return rc;
+    }
+    JF_HIP(e, hipStreamSynchronize(e->stream));
+    if (e->rv_side && e->rv_side_busy) JF_HIP(e, hipStreamSynchronize(e->rv_side));
+    if (e->live_len == 0) {
+        // a multiple of B that holds a window's worth (the kernels wrap with one conditional subtract) and a whole batch call
+        const long long need = std::max<long long>(e->N, (long long)e->maxK * e->B);
+        const long long len = (need + e->B - 1) / e->B * e->B;
+        if (len > 0x7fffffff) return fail(e, JF_ERR_ARG, "max_batch_blocks too large for live sources");
+        e->live_len = (int)len;
+    }
+    float *d_new = nullptr;
+    JF_HIP(e, hipMalloc(&d_new, sizeof(float) * (size_t)e->live_len));
+    {
+        hipError_t st = hipMemsetAsync(d_new, 0, sizeof(float) * (size_t)e->live_len, e->stream);
+        if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
+        if (st != hipSuccess) {
+            (void)hipFree(d_new);
+            JF_HIP(e, st);
+        }
+    }
+    if (e->live.empty()) e->live.assign((size_t)e->S, 0);
+    if (e->d_signal[src]) (void)hipFree(e->d_signal[src]);  // the resident signal is released; the window stays as it is
+    e->d_signal[src] = d_new;
+    e->h_sigs[src] = SrcSignal{d_new, e->live_len, 0};
+    e->live[src] = 1;
+    JF_HIP(e, h2d(e, e->d_sigs + src, &e->h_sigs[src], sizeof(SrcSignal)));
+    {
+        const int rc = live_refresh(e);
+        if (rc) return rc;
+    }
+    const int zero = 0;  // the play position, as after a signal swap
+    if (e->rv_P > 0)
+        JF_HIP(e, h2d(e, e->d_rv_count[e->cur] + src, &zero, sizeof(int)));
+    else
+        JF_HIP(e, h2d(e, &e->d_state[e->cur][src].count, &zero, sizeof(int)));
+    return JF_OK;
+    });
+}
+
+int jf_num_live_sources(const jf_engine *e) { return e ? e->n_live : JF_ERR_ARG; }
 
 int jf_source_set_cartesian(jf_engine *e, int src, float x, float y, float z) {
     return jf_guard([&]() -> int {
@@ -888,13 +1017,16 @@ int jf_interpolation_ex(float ele, float azi, unsigned flags, int idx[4], float 
 int jf_pick_hrtf(float ele, float azi) { return host_pick_hrtf(ele, azi); }
 
 // ---- per-block -----------------------------------------------------------
-int jf_submit_block(jf_engine *e) {
+// in: one block for every live source -- planar [n_live][B], or (interleaved: jf_pa_callback) [B][n_live]; null: zeros.
+// Ignored by an engine without live sources.
+static int submit_block(jf_engine *e, const float *in, bool interleaved) {
     return jf_guard([&]() -> int {
     DeviceGuard bind(e);
     if (!e) return JF_ERR_ARG;
     if (e->in_flight) return fail(e, JF_ERR_STATE, "a block is already in flight");
     if (device_fault(e)) return fail(e, JF_ERR_DEVICE, kHandOffMsg);
-    if (e->paused.load(std::memory_order_relaxed)) {  // Audio.cu:101: nothing is consumed, output is silence
+    e->last_ingest = false;
+    if (e->paused.load(std::memory_order_relaxed)) {  // Audio.cu:101: nothing is consumed (live input is dropped), output is silence
         JF_HIP(e, hipMemsetAsync(e->d_mix, 0, sizeof(float) * 2 * e->B, e->stream));
     } else {
         snapshot_positions(e, e->h_pos_pinned);
@@ -906,6 +1038,15 @@ int jf_submit_block(jf_engine *e) {
             ReverbParams head;
             bool head_fused = false;
             e->kernels_use_frozen = false;
+            if (e->n_live > 0) {
+                if (e->rv_P > 0) {
+                    // the reverb stage reads the dry samples from the sources' device buffers
+                    const int rc = live_ingest(e, in, interleaved, e->B, (size_t)e->B);
+                    if (rc) return rc;
+                } else {
+                    live_stage_rt(e, in, interleaved);  // the kernel takes the block from the staging itself: still one launch
+                }
+            }
             if (e->rv_ahead) {
                 e->rv_ahead = false;  // the stage of this block was launched behind the last block's spatialiser: rv_ahead
             } else {
@@ -918,7 +1059,7 @@ int jf_submit_block(jf_engine *e) {
             P.htab = e->d_htab;
             P.tw = e->d_twpack;
             P.desc = nullptr;
-            P.sigs = e->rv_P > 0 ? e->d_sigs_wet : e->d_sigs;
+            P.sigs = e->rv_P > 0 ? e->d_sigs_wet : e->n_live > 0 ? e->d_sigs_rt : e->d_sigs;
             P.st_in = e->d_state[p];
             P.st_out = e->d_state[p ^ 1];
             P.hist_in = e->d_hist[p];
@@ -970,6 +1111,10 @@ int jf_submit_block(jf_engine *e) {
             }
             return JF_OK;
         }
+        if (e->n_live > 0) {
+            const int rc = live_ingest(e, in, interleaved, e->B, (size_t)e->B);
+            if (rc) return rc;
+        }
         JF_HIP(e, hipMemcpyAsync(e->d_pos_rt, e->h_pos_pinned, sizeof(float) * 5 * e->S, hipMemcpyHostToDevice,
                                  e->stream));
         int rc = run_blocks(e, e->d_pos_rt, 1, e->d_mix);
@@ -981,6 +1126,10 @@ int jf_submit_block(jf_engine *e) {
     return JF_OK;
     });
 }
+
+int jf_submit_block(jf_engine *e) { return submit_block(e, nullptr, false); }
+
+int jf_submit_block_in(jf_engine *e, const float *in) { return submit_block(e, in, false); }
 
 int jf_collect_block(jf_engine *e, float *out) {
     return jf_guard([&]() -> int {
@@ -1029,6 +1178,15 @@ int jf_collect_block(jf_engine *e, float *out) {
     });
 }
 
+int jf_process_block_in(jf_engine *e, const float *in, float *out) {
+    return jf_guard([&]() -> int {
+    if (!e || !out) return JF_ERR_ARG;
+    int rc = submit_block(e, in, false);
+    if (rc) return rc;
+    return jf_collect_block(e, out);
+    });
+}
+
 int jf_process_block(jf_engine *e, float *out) {
     return jf_guard([&]() -> int {
     int rc = jf_submit_block(e);
@@ -1037,7 +1195,7 @@ int jf_process_block(jf_engine *e, float *out) {
     });
 }
 
-int jf_callback(jf_engine *e, float *out) {
+static int callback_block(jf_engine *e, const float *in, bool interleaved, float *out) {
     return jf_guard([&]() -> int {
     if (!e || !out) return JF_ERR_ARG;
     int rc;
@@ -1047,19 +1205,25 @@ int jf_callback(jf_engine *e, float *out) {
     } else {
         memset(out, 0, sizeof(float) * 2 * e->B);  // intermediate[] before the first block
     }
-    rc = jf_submit_block(e);
+    rc = submit_block(e, in, interleaved);
     if (rc) return rc;
     e->have_prev = true;
     return JF_OK;
     });
 }
 
-int jf_pa_callback(const void *, void *output, unsigned long frames, const void *, unsigned long, void *user) {
+int jf_callback(jf_engine *e, float *out) { return callback_block(e, nullptr, false, out); }
+
+int jf_callback_in(jf_engine *e, const float *in, float *out) { return callback_block(e, in, false, out); }
+
+int jf_pa_callback(const void *input, void *output, unsigned long frames, const void *, unsigned long, void *user) {
     return jf_guard([&]() -> int {
     jf_engine *e = (jf_engine *)user;
     if (!output) return 0;
     // a stream opened with another buffer size, or an engine error: hand PortAudio silence, never garbage
-    if (!e || frames != (unsigned long)e->B || jf_callback(e, (float *)output) != JF_OK)
+    // (input: PortAudio's interleaved [frames][channels], a channel per live source; null -- a stream without input -- feeds
+    // the live sources zeros)
+    if (!e || frames != (unsigned long)e->B || callback_block(e, (const float *)input, true, (float *)output) != JF_OK)
         memset(output, 0, sizeof(float) * 2 * frames);
     return 0;
     });
@@ -1085,7 +1249,7 @@ int jf_set_pause(jf_engine *e, int paused) {
 
 
 // ---- batch -----------------------------------------------------------------
-int jf_batch_upload_positions(jf_engine *e, int total_blocks, const float *positions) {
+static int upload_positions(jf_engine *e, int total_blocks, const float *positions) {
     return jf_guard([&]() -> int {
     DeviceGuard bind(e);
     if (!e || total_blocks <= 0 || !positions) return fail(e, JF_ERR_ARG, "bad trajectory");
@@ -1134,7 +1298,7 @@ int jf_batch_upload_positions(jf_engine *e, int total_blocks, const float *posit
     });
 }
 
-int jf_batch_run(jf_engine *e, int first_block, int n_blocks, float *d_out_mix) {
+static int batch_run(jf_engine *e, int first_block, int n_blocks, float *d_out_mix) {
     return jf_guard([&]() -> int {
     DeviceGuard bind(e);
     if (!e) return JF_ERR_ARG;
@@ -1147,6 +1311,20 @@ int jf_batch_run(jf_engine *e, int first_block, int n_blocks, float *d_out_mix) 
     e->own_mix_blocks = rc == JF_OK && !d_out_mix ? n_blocks : 0;  // what jf_batch_fetch may hand out
     return rc;
     });
+}
+
+// The device-resident form works on signals that are on the device already: not while a source waits for its samples.
+static const char *kLiveResidentMsg = "the device-resident batch form does not take live sources (jf_process_batch_in does)";
+
+int jf_batch_upload_positions(jf_engine *e, int total_blocks, const float *positions) {
+    if (e && e->n_live > 0) return jf_guard([&]() -> int { return fail(e, JF_ERR_STATE, kLiveResidentMsg); });
+    return upload_positions(e, total_blocks, positions);
+}
+
+int jf_batch_run(jf_engine *e, int first_block, int n_blocks, float *d_out_mix) {
+    if (e && e->n_live > 0) return jf_guard([&]() -> int { return fail(e, JF_ERR_STATE, kLiveResidentMsg); });
+    if (e) e->last_ingest = false;
+    return batch_run(e, first_block, n_blocks, d_out_mix);
 }
 
 int jf_device_numa_node(int device, int *node) {
@@ -1221,16 +1399,25 @@ int jf_synchronize(jf_engine *e) {
     });
 }
 
-int jf_process_batch(jf_engine *e, int n_blocks, const float *positions, float *out_mix) {
+// in: [n_live][n_blocks B] (null: zeros), ignored by an engine without live sources
+static int process_batch(jf_engine *e, int n_blocks, const float *in, const float *positions, float *out_mix) {
     return jf_guard([&]() -> int {
     DeviceGuard bind(e);
     if (!e || !positions || !out_mix || n_blocks <= 0) return fail(e, JF_ERR_ARG, "bad batch arguments");
-    int rc = jf_batch_upload_positions(e, n_blocks, positions);
+    if (e->n_live > 0 && e->in_flight) return fail(e, JF_ERR_STATE, "a per-block call is in flight");  // (before its input is touched)
+    int rc = upload_positions(e, n_blocks, positions);
     if (rc) return rc;
     const size_t blk = (size_t)2 * e->B;
     for (int b0 = 0; b0 < n_blocks; b0 += e->maxK) {
         const int k = n_blocks - b0 < e->maxK ? n_blocks - b0 : e->maxK;
-        rc = jf_batch_run(e, b0, k, nullptr);
+        e->last_ingest = false;
+        if (e->n_live > 0) {
+            // this window's samples of every live source, ahead of its kernels (the staging is free: the window before
+            // has been waited for below)
+            rc = live_ingest(e, in ? in + (size_t)b0 * e->B : nullptr, false, k * e->B, (size_t)n_blocks * e->B);
+            if (rc) return rc;
+        }
+        rc = batch_run(e, b0, k, nullptr);
         if (rc) return rc;
         JF_HIP(e, hipMemcpyAsync(out_mix + (size_t)b0 * blk, e->d_mix, sizeof(float) * blk * k, hipMemcpyDeviceToHost,
                                  e->stream));
@@ -1240,6 +1427,14 @@ int jf_process_batch(jf_engine *e, int n_blocks, const float *positions, float *
     // n_blocks callbacks have run: the sources stand where the last of them read them
     return jf_sources_set_latched(e, positions + (size_t)(n_blocks - 1) * e->S * JF_POS_FLOATS);
     });
+}
+
+int jf_process_batch(jf_engine *e, int n_blocks, const float *positions, float *out_mix) {
+    return process_batch(e, n_blocks, nullptr, positions, out_mix);
+}
+
+int jf_process_batch_in(jf_engine *e, int n_blocks, const float *in, const float *positions, float *out_mix) {
+    return process_batch(e, n_blocks, in, positions, out_mix);
 }
 
 int jf_sources_set_latched(jf_engine *e, const float *records) {

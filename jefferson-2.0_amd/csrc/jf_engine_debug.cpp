@@ -241,6 +241,8 @@ int jf_debug_set_reverb_ahead(jf_engine *e, int on) {
     });
 }
 
+int jf_debug_reverb_ahead_pending(const jf_engine *e) { return e ? (e->rv_ahead ? 1 : 0) : JF_ERR_ARG; }
+
 int jf_debug_set_reverb_lazy_state(jf_engine *e, int on) {
     return jf_guard([&]() -> int {
     if (e) {
@@ -394,7 +396,8 @@ const char *jf_debug_last_kernels(jf_engine *e) {
     try {
         const std::string nb = std::to_string(e->B / 64), bs = std::to_string(e->B);
         std::string k;
-        if (!e->last_rt && !e->last_prep_skipped) k = "prep_kernel;";
+        if (e->last_ingest) k = "live_ingest_kernel;";
+        if (!e->last_rt && !e->last_prep_skipped) k += "prep_kernel;";
         if (e->rv_P > 0) {
             if (e->last_catchup) k += "reverb_fft_kernel<" + bs + ">@ring;";
             const ReverbPlan &pl = e->last_plan;

@@ -63,6 +63,9 @@ hipError_t launch_fused2048(const FusedParams &P, hipStream_t st);
 hipError_t launch_table2048_build(const float *d_hrir, int n_rows, int taps, const float2 *d_tw2048, float4 *d_htab,
                                   hipStream_t st);
 hipError_t launch_rfft2048_debug(const float *d_win, int n, const float2 *d_tw2048, float2 *d_spec, hipStream_t st);
+// live input (jf_live.hip)
+hipError_t launch_live_ingest(const SrcSignal *d_sigs, const int *d_live_idx, const int *d_count, int count_stride,
+                              const float *in, bool interleaved, int n_live, int n, int row_stride, hipStream_t st);
 }  // namespace jf
 
 using namespace jf;
@@ -165,6 +168,26 @@ struct jf_engine {
 
     std::vector<float *> d_signal;  // per source
     std::vector<SrcSignal> h_sigs;
+
+    // LIVE INPUT (jf_source_set_live).  A live source has no resident signal: every processing call brings its
+    // next samples.  Nothing below exists in an engine that never had a live source.
+    //   - d_signal[s] of a live source is a device buffer of live_len floats (a multiple of B, >= max(PAD_LEN, maxK B)), named
+    //     by the source's ordinary record in d_sigs: the batch kernels and the reverb stage read a call's new samples at the
+    //     source's play position with their loop-wrap rule, and live_ingest_kernel has put them exactly there (jf_live.hip).
+    //   - The one-launch real-time kernel reads its records from d_sigs_rt instead: a copy of d_sigs in which the j-th live
+    //     source is {hd_in + j B, B}, B floats of the pinned staging.  With a "loop" of one block the kernel's own count
+    //     write-back, (count + B) mod B, stays 0; counts are multiples of B everywhere, so the two kinds of call may alternate.
+    //   - h_in: the staging, pinned + mapped, n_live * max(maxK, 1) * B floats.  Only one call is ever in flight
+    //     (jf_submit_block refuses a second), so one staging is enough; the host has copied the caller's samples when a call returns.
+    std::vector<char> live;          // [S] the source is live
+    std::vector<int> live_idx;       // the live sources, ascending: row j of `in` feeds live_idx[j]
+    int n_live = 0;
+    int live_len = 0;                // floats of a live source's device buffer
+    int *d_live_idx = nullptr;       // [S]
+    SrcSignal *d_sigs_rt = nullptr;  // [S]
+    float *h_in = nullptr, *hd_in = nullptr;
+    size_t in_cap = 0;               // floats h_in holds
+    bool last_ingest = false;        // the last call launched live_ingest_kernel (jf_debug_last_kernels)
 
     std::mutex pos_mu;  // setters may come from another thread (graphics.cu:378)
     std::vector<HostPos> pos;

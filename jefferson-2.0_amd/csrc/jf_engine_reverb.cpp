@@ -189,7 +189,7 @@ int run_reverb_stage(jf_engine *e, int p, int K, ReverbParams *head_out, bool *h
         e->rv_small_stale = false;
         e->last_catchup = true;
     }
-    plan.head_fused = head_out != nullptr && K == 1 && e->rv_head_fused && !e->rt.cloud.tri && e->rv_form == 0 && e->profiling < 2 &&
+    plan.head_fused = head_out != nullptr && K == 1 && e->rv_head_fused && e->n_live == 0 && !e->rt.cloud.tri && e->rv_form == 0 && e->profiling < 2 &&
                       e->rv_P <= kRvFusedHeadMax && rt_waves_per_wg(e->S) == 8 && (e->B == 64 || e->B == 128 || e->B == 256);
     {
         const hipError_t q = launch_reverb(R, &plan, e->stream, &e->last_rv_form);
@@ -260,6 +260,7 @@ int rv_ahead_discard(jf_engine *e) {
 // May the stage of the block after the one just launched go ahead?  A plain head only: the block completes no big block (its
 // transforms would have to follow its spatialiser), owes no TAIL, the side stream has nothing urgent, nothing is put off.
 bool rv_ahead_possible(const jf_engine *e) {
+    if (e->n_live > 0) return false;  // the next block's input has not arrived
     if (e->rv_P <= 0 || !e->rv_ahead_on || e->rv_form != 0 || e->profiling || e->rv_head_fused || e->rv_small_stale) return false;
     if (e->S > e->rt_max_sources || e->S >= 2048) return false;  // (the one-launch path; the one-block head kernel's range)
     if (e->paused.load(std::memory_order_relaxed)) return false;

@@ -17,7 +17,7 @@
  *     first block that starts with `count` at or past its mark.  `count` follows Audio.cu:121-139 (wraps at `length`).
  *
  * usage: jf_render <hrir_dir | set.sofa> <in.wav> <out.wav> [--block 256] [--azi 3] [--ele 5]
- *                  [--dwell 172] [--rounds 72] [--step 5] [--radius 0.5] [--latency] [--script debugmode2]
+ *                  [--dwell 172] [--rounds 72] [--step 5] [--radius 0.5] [--latency] [--script debugmode2] [--live]
  *   <set.sofa>  a name that ends in ".sofa": the HRTF set of a SOFA file instead of the KEMAR directory
  *               (jf_engine_create_sofa; --sofa-tol T: degrees a measurement may lie off its ring's uniform steps, 0.51 --
  *               what sets whose azimuths were rounded to whole degrees, like KEMAR's, need).  A set that is refused as
@@ -29,6 +29,10 @@
  *              instead of jf_process_block (the CPU path's ordering)
  *   --no-pin   leave the thread where the system put it (default: jf_pin_thread_to_device -- on a two-socket host a block
  *              costs 1-5 us more from the socket the GPU does not hang off)
+ *   --live     feed the input block by block (jf_source_set_live and the *_in calls: what a host with a microphone, a decoder or
+ *              a mixer bus does) instead of making it resident (jf_source_set_signal); same blocks bit for bit, so the
+ *              written file is byte-identical to the plain render as long as the input does not loop (a live feed that
+ *              runs out goes on with zeros; a resident signal starts over).  Works with --latency, --batch and --script.
  *   --batch N  hand the engine N callbacks at a time (jf_process_batch: the same blocks, the positions the
  *              audio thread would have latched given up front) -- what an offline render should use: a
  *              single source cannot fill a GPU one block at a time
@@ -74,6 +78,16 @@ static size_t script_debugmode2(size_t length, int block, float radius, float **
     return n;
 }
 
+/* --live: the input as a feed -- the next `count` samples (zeros once the file has run out), or NULL for a resident run */
+static const float *g_feed_sig = NULL;
+static size_t g_feed_n = 0, g_feed_at = 0;
+static float *g_feed_buf = NULL;
+static const float *feed(size_t count) {
+    if (!g_feed_buf) return NULL;
+    for (size_t i = 0; i < count; i++, g_feed_at++) g_feed_buf[i] = g_feed_at < g_feed_n ? g_feed_sig[g_feed_at] : 0.0f;
+    return g_feed_buf;
+}
+
 static double now_s(void) {
     struct timespec ts;
     clock_gettime(CLOCK_MONOTONIC, &ts);
@@ -84,16 +98,18 @@ int main(int argc, char **argv) {
     if (argc < 4) {
         fprintf(stderr, "usage: %s <hrir_dir | set.sofa> <in.wav> <out.wav> [--block B] [--azi A] [--ele E] "
                         "[--dwell N] [--rounds R] [--step D] [--radius r] [--latency] [--batch N] [--script debugmode2] [--no-pin] "
-                        "[--sofa-tol T] [--cloud-tol T]\n"
+                        "[--sofa-tol T] [--cloud-tol T] [--live]\n"
+                        "  --live: feed the input block by block (jf_source_set_live) instead of making it resident\n"
                         "  set.sofa: rings of uniform azimuth steps (the ring rule), or any other directions (the cloud rule: "
                         "barycentric weights on their triangulation)\n", argv[0]);
         return 2;
     }
-    int block = 256, dwell = 172, rounds = 72, latency = 0, batch = 0, script = 0, pin = 1;
+    int block = 256, dwell = 172, rounds = 72, latency = 0, batch = 0, script = 0, pin = 1, live = 0;
     float azi = 3, ele = 5, step = 5, radius = 0.5f, sofa_tol = 0.51f, cloud_tol = 0.05f;
     for (int i = 4; i < argc; i++) {
         if (!strcmp(argv[i], "--latency")) latency = 1;
         else if (!strcmp(argv[i], "--no-pin")) pin = 0;
+        else if (!strcmp(argv[i], "--live")) live = 1;
         else if (i + 1 < argc && !strcmp(argv[i], "--block")) block = atoi(argv[++i]);
         else if (i + 1 < argc && !strcmp(argv[i], "--batch")) batch = atoi(argv[++i]);
         else if (i + 1 < argc && !strcmp(argv[i], "--azi")) azi = (float)atof(argv[++i]);
@@ -141,8 +157,18 @@ int main(int argc, char **argv) {
         fprintf(stderr, "engine: %s\n", jf_last_error(NULL));
         return 1;
     }
-    jf_source_set_signal(e, 0, sig, n);
-    jf_free(sig);
+    if (live) {
+        if (block <= 0 || jf_source_set_live(e, 0, 1) != JF_OK) {
+            fprintf(stderr, "live: %s\n", jf_last_error(e));
+            return 1;
+        }
+        g_feed_sig = sig;
+        g_feed_n = n;
+        g_feed_buf = (float *)malloc(sizeof(float) * (size_t)block * (size_t)cfg.max_batch_blocks);
+        if (!g_feed_buf) return 1;
+    } else {
+        jf_source_set_signal(e, 0, sig, n);
+    }
 
     if (script) {
         /* DEBUGMODE 2: the way-points as the blocks latch them; per block through the setter (what the main thread calls,
@@ -160,14 +186,18 @@ int main(int argc, char **argv) {
         if (batch > 0) {
             for (size_t k0 = 0; k0 < nb && src == JF_OK; k0 += (size_t)batch) {
                 const int kb = nb - k0 < (size_t)batch ? (int)(nb - k0) : batch;
-                src = jf_process_batch(e, kb, spos + JF_POS_FLOATS * k0, sout + 2 * (size_t)block * k0);
+                src = jf_process_batch_in(e, kb, feed((size_t)kb * (size_t)block), spos + JF_POS_FLOATS * k0, sout + 2 * (size_t)block * k0);
             }
         } else {
-            if (latency) src = jf_callback(e, sout); /* priming call: the CUDA path hands out block k - 1 */
+            if (latency) src = jf_callback_in(e, feed((size_t)block), sout); /* priming call: the CUDA path hands out block k - 1 */
             for (size_t k0 = 0; k0 < nb && src == JF_OK; k0++) {
                 const float *r = spos + JF_POS_FLOATS * k0; /* {ele, azi, x, y, z}: the setter takes (ele, azi, radius) */
                 jf_source_set_spherical(e, 0, r[0], r[1], radius);
-                src = latency ? jf_callback(e, sout + 2 * (size_t)block * k0) : jf_process_block(e, sout + 2 * (size_t)block * k0);
+                {
+                    const float *in = feed((size_t)block); /* NULL unless --live; an engine without live sources ignores it */
+                    src = latency ? jf_callback_in(e, in, sout + 2 * (size_t)block * k0)
+                                  : jf_process_block_in(e, in, sout + 2 * (size_t)block * k0);
+                }
             }
         }
         const double ds = now_s() - ts;
@@ -183,6 +213,8 @@ int main(int argc, char **argv) {
                 ds, 1e6 * ds / (double)nb, ((double)nb * block / 44100.0) / ds);
         free(spos);
         free(sout);
+        free(g_feed_buf);
+        jf_free(sig);
         jf_engine_destroy(e);
         return 0;
     }
@@ -214,21 +246,23 @@ int main(int argc, char **argv) {
         }
         for (k = 0; k < total && rc == JF_OK; k += (size_t)batch) {
             const int nb = total - k < (size_t)batch ? (int)(total - k) : batch;
-            rc = jf_process_batch(e, nb, pos + JF_POS_FLOATS * k, out + 2 * (size_t)block * k);
+            rc = jf_process_batch_in(e, nb, feed((size_t)nb * (size_t)block), pos + JF_POS_FLOATS * k, out + 2 * (size_t)block * k);
         }
         free(pos);
         rounds = -1; /* done: skip the per-block loop */
     }
-    if (latency && batch <= 0) rc = jf_callback(e, out); /* priming call, precision_test.cu:2110 */
+    if (latency && batch <= 0) rc = jf_callback_in(e, feed((size_t)block), out); /* priming call, precision_test.cu:2110 */
     for (int r = 0; r <= rounds && rc == JF_OK; r++) {
         if (r > 0) {
             azi += step;
             if (azi >= 360) azi -= 360;
             jf_source_set_spherical(e, 0, ele, azi, radius);
         }
-        for (int j = 0; j < dwell && rc == JF_OK; j++, k++)
-            rc = latency ? jf_callback(e, out + 2 * (size_t)block * k)
-                         : jf_process_block(e, out + 2 * (size_t)block * k);
+        for (int j = 0; j < dwell && rc == JF_OK; j++, k++) {
+            const float *in = feed((size_t)block); /* NULL unless --live */
+            rc = latency ? jf_callback_in(e, in, out + 2 * (size_t)block * k)
+                         : jf_process_block_in(e, in, out + 2 * (size_t)block * k);
+        }
     }
     const double dt = now_s() - t0;
     if (rc != JF_OK) {
@@ -242,6 +276,8 @@ int main(int argc, char **argv) {
     fprintf(stderr, "%zu blocks of %d frames in %.3f s: %.1f us per block, real-time factor %.1f\n", total, block, dt,
             1e6 * dt / (double)total, ((double)total * block / 44100.0) / dt);
     free(out);
+    free(g_feed_buf);
+    jf_free(sig);
     jf_engine_destroy(e);
     return 0;
 }
