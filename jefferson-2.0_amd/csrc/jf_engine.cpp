@@ -10,9 +10,9 @@
 // for the 386 MB the engine goes on without rows (per-block weighting), for good.
 int ensure_interp_rows(jf_engine *e) {
     if (e->interp_built || !e->interp_avail) return JF_OK;
-    float4 *big = nullptr;
+    DevBuf<float4> big;
     const size_t n_rows = (size_t)e->rt.n_rows;
-    if (hipMalloc(&big, sizeof(float4) * (n_rows + kInterpRows) * 512) != hipSuccess) {
+    if (big.alloc((n_rows + kInterpRows) * 512) != hipSuccess) {
         (void)hipGetLastError();
         e->interp_avail = false;
         e->interp_use = 0;
@@ -21,94 +21,46 @@ int ensure_interp_rows(jf_engine *e) {
     hipError_t q = hipMemcpyAsync(big, e->d_htab, sizeof(float4) * n_rows * 512, hipMemcpyDeviceToDevice, e->stream);
     if (q == hipSuccess) q = launch_table_interp_build(e->rt, corrected_rule(e) ? 1 : 0, big, e->stream);
     if (q == hipSuccess) q = hipStreamSynchronize(e->stream);  // (everything that reads the old table has finished as well)
-    if (q != hipSuccess) {
-        (void)hipFree(big);
-        JF_HIP(e, q);
-    }
-    (void)hipFree(e->d_htab);
-    e->d_htab = big;
+    JF_HIP(e, q);
+    e->d_htab = std::move(big);  // the 710-row table is freed here, after the synchronisation: both exist side by side till then
     e->interp_built = true;
     return JF_OK;
 }
 
-
-
-// PAD_LEN 2048: prep -> fused2048_kernel -> mix on the engine stream.  No reverb stage (refused at this length), no
-// pre-interpolated rows, no descriptors prepared ahead: every run prepares its own window.
-static int run_blocks_2048(jf_engine *e, const float *d_pos, int K, float *d_mix_out) {
-    const int p = e->cur;
-    EventPair *ep = nullptr, *ef = nullptr, *em = nullptr;
-    const bool timed = e->profiling && (e->profile_stride <= 1 || e->profile_calls++ % e->profile_stride == 0);
-    e->timed_now = timed;
-    if (timed) {
-        ef = next_events(e, e->ev_fused);
-        if (!ef) return fail(e, JF_ERR_DEVICE, "hipEventCreate failed");
+// Sources a unit sums as spectra before its inverse transforms (G divides S; jf_debug_set_source_group pins it and refuses
+// a size that does not divide S).  Larger groups mean fewer inverse transforms and fewer partial blocks for the mix.
+static int source_group(const jf_engine *e, long long n_items) {
+    const int S = e->S;
+    if (e->src_group > 0) return S % e->src_group == 0 ? e->src_group : 1;
+    if (e->N != kN) {
+        // PAD_LEN 2048, a unit is one workgroup of four waves: as many as leave about four units for every compute unit
+        for (const int g : {16, 8, 4, 2})
+            if (S % g == 0 && n_items / g >= 1024) return g;
+        return 1;
     }
-    if (e->profiling >= 2 && timed) {
-        ep = next_events(e, e->ev_prep);
-        em = next_events(e, e->ev_mix);
-        if (!ep || !em) return fail(e, JF_ERR_DEVICE, "hipEventCreate failed");
-    }
-    // Sources a workgroup sums as spectra before its inverse transforms: as many as leave about four units for every
-    // compute unit (a unit is one workgroup of four waves).  G must divide S.
-    const long long n_items = (long long)K * e->S;
-    int G = 1;
-    for (const int g : {16, 8, 4, 2})
-        if (e->S % g == 0 && n_items / g >= 1024) {
-            G = g;
-            break;
-        }
-    if (e->src_group > 0 && e->S % e->src_group == 0) G = e->src_group;
-    e->ahead.valid = false;
-    e->last_prep_skipped = false;
-    e->last_rows = false;
-    e->last_mix_prep = e->last_fused_prep = false;
-    const int mode_now = kernel_mode(e);
-    if (ep) JF_HIP(e, hipEventRecord(ep->a, e->stream));
-    JF_HIP(e, launch_prep(e->rt, mode_now, d_pos, e->d_state[p], e->d_desc, e->S, K, 0, e->Nc, e->stream));
-    if (ep) JF_HIP(e, hipEventRecord(ep->b, e->stream));
-    FusedParams P;
-    P.htab = e->d_htab;
-    P.tw = e->d_tw2048;
-    P.desc = e->d_desc;
-    P.sigs = e->d_sigs;
-    P.st_in = e->d_state[p];
-    P.st_out = e->d_state[p ^ 1];
-    P.hist_in = e->d_hist[p];
-    P.hist_out = e->d_hist[p ^ 1];
-    P.pos = d_pos;
-    P.partial = e->d_partial;
-    P.S = e->S;
-    P.K = K;
-    P.B = e->B;
-    P.G = G;
-    P.mode = mode_now;
-    P.order = e->d_order;
-    P.err = e->hd_err;
-    P.rt = e->rt;
-    e->last_group = G;
-    if (ef) JF_HIP(e, hipEventRecord(ef->a, e->stream));
-    JF_HIP(e, launch_fused2048(P, e->stream));
-    if (ef) JF_HIP(e, hipEventRecord(ef->b, e->stream));
-    if (em) JF_HIP(e, hipEventRecord(em->a, e->stream));
-    JF_HIP(e, launch_mix(e->d_partial, d_mix_out, e->S / G, K, e->B, e->stream));
-    if (em) JF_HIP(e, hipEventRecord(em->b, e->stream));
-    if (timed) e->ev_used++;
-    e->cur = p ^ 1;
-    e->last_rt = false;
-    return JF_OK;
+    // PAD_LEN 1024, a unit is a pair of wavefronts: as many as leave about two units for every resident pair (2048 on
+    // MI355X; profiles/group_sweep.py times every size against this choice)
+    return (S % 32 == 0 && n_items >= 131072) ? 32
+           : (S % 16 == 0 && n_items >= 32768) ? 16
+           : (S % 8 == 0 && n_items >= 16384) ? 8
+           : (S % 4 == 0 && n_items >= 8192) ? 4
+           : (S % 2 == 0 && (n_items >= 4096 || S >= 1024)) ? 2
+                                                           : 1;
 }
 
 // prep -> [reverb] -> fused -> mix on the engine stream, K blocks starting at d_pos.
 // first_block: index of d_pos's first block in the uploaded trajectory (jf_batch_run), -1 for positions from elsewhere.
+// What PAD_LEN 2048 differs in is decided here: its group rule (source_group), descriptors never in the pair-kernel layout
+// (canon), its own twiddle table and launcher, and nothing prepared ahead (ahead_ok) -- the pre-interpolated rows and the
+// reverb stage are off by themselves there (interp_avail is false, rv_P is 0).
 int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int first_block) {
     if (device_fault(e)) return fail(e, JF_ERR_DEVICE, kHandOffMsg);  // fatal: see device_fault
-    if (e->N != kN) return run_blocks_2048(e, d_pos, K, d_mix_out);
     {
         const int rc = rv_ahead_discard(e);  // (a stage launched ahead by a one-block call: this call does its own)
         if (rc) return rc;
     }
     const int p = e->cur;
+    const bool n1024 = e->N == kN;
     EventPair *ep = nullptr, *ef = nullptr, *em = nullptr;
     // a pair of event records costs ~7 us of stream time: they may be put around every n-th run only (the runs in
     // between launch the same kernels, untimed)
@@ -123,20 +75,9 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
         em = next_events(e, e->ev_mix);
         if (!ep || !em) return fail(e, JF_ERR_DEVICE, "hipEventCreate failed");
     }
-    // sources a pair of wavefronts sums before it stores a stereo block: as many as leave about two units for every
-    // resident pair (2048 on MI355X): larger groups mean fewer inverse transforms and fewer partial blocks for the
-    // mix (profiles/group_sweep.py times every size against this choice)
     const long long n_items = (long long)K * e->S;
-    const int G = e->src_group > 0 ? e->src_group
-                  : (e->S % 32 == 0 && n_items >= 131072) ? 32
-                  : (e->S % 16 == 0 && n_items >= 32768) ? 16
-                  : (e->S % 8 == 0 && n_items >= 16384) ? 8
-                  : (e->S % 4 == 0 && n_items >= 8192) ? 4
-                  : (e->S % 2 == 0 && (n_items >= 4096 || e->S >= 1024)) ? 2
-                                                         : 1;
-    FusedParams P;
-    P.G = (e->S % G == 0) ? G : 1;
-    const int canon = P.G > 1;  // descriptors in the pair-kernel layout
+    const int G = source_group(e, n_items);
+    const int canon = n1024 && G > 1;  // descriptors in the pair-kernel layout
     // whole-degree positions as pre-interpolated rows: the pair kernel's descriptors only
     bool rows = canon && e->interp_avail && e->interp_use != 0;
     if (rows && e->interp_use == 2 && first_block >= 0 && (size_t)(first_block + K) < e->traj_moved.size()) {
@@ -162,61 +103,53 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
     e->last_prep_skipped = have;
     if (have) std::swap(e->d_desc, e->d_desc_ahead);
     if (ep) JF_HIP(e, hipEventRecord(ep->a, e->stream));
-    if (!have) JF_HIP(e, launch_prep(e->rt, mode_now, d_pos, e->d_state[p], e->d_desc, e->S, K, canon, kNc, e->stream));
+    if (!have) JF_HIP(e, launch_prep(e->rt, mode_now, d_pos, e->d_state[p], e->d_desc, e->S, K, canon, e->Nc, e->stream));
     if (ep) JF_HIP(e, hipEventRecord(ep->b, e->stream));
     {
         const int rc = run_reverb_stage(e, p, K);
         if (rc) return rc;
     }
-    P.htab = e->d_htab;
-    P.tw = e->d_twpack;
+    FusedParams P = fused_params(e, p, K, mode_now);
+    P.tw = n1024 ? e->d_twpack : e->d_tw2048;
     P.desc = e->d_desc;
     P.sigs = e->rv_P > 0 ? e->d_sigs_wet : e->d_sigs;
-    P.st_in = e->d_state[p];
-    P.st_out = e->d_state[p ^ 1];
-    P.hist_in = e->d_hist[p];
-    P.hist_out = e->d_hist[p ^ 1];
     P.pos = d_pos;
     P.partial = e->d_partial;
-    P.S = e->S;
-    P.K = K;
-    P.B = e->B;
-    e->last_group = P.G;
-    P.mode = mode_now;
-    P.err = e->hd_err;
-    P.order = e->d_order;
+    P.G = G;
+    e->last_group = G;
     // the window that follows in the trajectory, if there is a whole one: its descriptors are prepared by this run --
     // inside the pair kernel's own launch (trailing workgroups, in the kernel's tail), else inside the mix launch
-    const bool ahead_ok = e->prep_ahead && e->profiling < 2 && first_block >= 0 && first_block + 2 * K <= e->traj_blocks;
-    const bool ahead_in_fused = ahead_ok && P.G > 1;
-    P.n_pair_wgs = 0;
+    const bool ahead_ok = n1024 && e->prep_ahead && e->profiling < 2 && first_block >= 0 && first_block + 2 * K <= e->traj_blocks;
+    const bool ahead_in_fused = ahead_ok && G > 1;
     P.prep_pos = ahead_in_fused ? d_pos + (size_t)K * e->S * 5 : nullptr;
     P.prep_desc = e->d_desc_ahead;
     P.prep_K = K;
     P.prep_canon = canon;
     P.rt = e->rt;
-    int max_wgs = e->resident_wgs[P.G > 1 ? (rows ? 2 : 1) : 0];
-    if (e->grid_limit > 0 && e->grid_limit < max_wgs) max_wgs = e->grid_limit;
     if (ef) JF_HIP(e, hipEventRecord(ef->a, e->stream));
-    JF_HIP(e, launch_fused(P, max_wgs, e->stream));
+    if (n1024) {
+        int max_wgs = e->resident_wgs[G > 1 ? (rows ? 2 : 1) : 0];
+        if (e->grid_limit > 0 && e->grid_limit < max_wgs) max_wgs = e->grid_limit;
+        JF_HIP(e, launch_fused(P, max_wgs, e->stream));
+    } else {
+        JF_HIP(e, launch_fused2048(P, e->stream));
+    }
     if (ef) JF_HIP(e, hipEventRecord(ef->b, e->stream));
     if (em) JF_HIP(e, hipEventRecord(em->a, e->stream));
     e->last_mix_prep = ahead_ok && !ahead_in_fused;
     e->last_fused_prep = ahead_in_fused;
+    if (e->last_mix_prep)
+        JF_HIP(e, launch_mix_prep(e->d_partial, d_mix_out, e->S / G, K, e->B, e->rt, mode_now, d_pos + (size_t)K * e->S * 5,
+                                  e->d_desc_ahead, e->S, K, canon, e->stream));
+    else
+        JF_HIP(e, launch_mix(e->d_partial, d_mix_out, e->S / G, K, e->B, e->stream));
     if (ahead_ok) {
-        if (ahead_in_fused)
-            JF_HIP(e, launch_mix(e->d_partial, d_mix_out, e->S / P.G, K, e->B, e->stream));
-        else
-            JF_HIP(e, launch_mix_prep(e->d_partial, d_mix_out, e->S / P.G, K, e->B, e->rt, mode_now,
-                                      d_pos + (size_t)K * e->S * 5, e->d_desc_ahead, e->S, K, canon, e->stream));
         e->ahead.valid = true;
         e->ahead.first = first_block + K;
         e->ahead.K = K;
         e->ahead.mode = mode_now;
         e->ahead.canon = canon;
         e->ahead.traj_gen = e->traj_gen;
-    } else {
-        JF_HIP(e, launch_mix(e->d_partial, d_mix_out, e->S / P.G, K, e->B, e->stream));
     }
     if (em) JF_HIP(e, hipEventRecord(em->b, e->stream));
     if (timed) e->ev_used++;
@@ -237,7 +170,6 @@ static void snapshot_positions(jf_engine *e, float *dst /* [S][5] */) {
         d[4] = q.z;
     }
 }
-
 
 // zero one source's (or every source's, src < 0) window, counters and reverb state
 int reset_sources(jf_engine *e, int src) {
@@ -265,7 +197,6 @@ int reset_sources(jf_engine *e, int src) {
     return JF_OK;
 }
 
-
 // ---- live input (jf_engine::live) -----------------------------------------------------------------------
 // After any change of which sources are live or of a signal record: the list of live sources, the staging (grown to hold a
 // whole batch window of every live source) and the real-time kernel's records.  The engine's stream is idle (the callers
@@ -281,16 +212,16 @@ static int live_refresh(jf_engine *e) {
     if (want > e->in_cap) {
         // (grown by doubling, up to what S live sources need: a host that turns its sources live one by one pins memory a few times)
         want = std::min(std::max(want, 2 * e->in_cap), S * (size_t)e->maxK * B);
-        if (e->h_in) (void)hipHostFree(e->h_in);
-        e->h_in = e->hd_in = nullptr;
+        e->h_in.reset();
+        e->hd_in = nullptr;
         e->in_cap = 0;
-        JF_HIP(e, hipHostMalloc(&e->h_in, sizeof(float) * want, hipHostMallocMapped | hipHostMallocCoherent));
+        JF_HIP(e, e->h_in.alloc(want));
         JF_HIP(e, hipHostGetDevicePointer((void **)&e->hd_in, e->h_in, 0));
         memset(e->h_in, 0, sizeof(float) * want);
         e->in_cap = want;
     }
-    if (!e->d_live_idx) JF_HIP(e, hipMalloc(&e->d_live_idx, sizeof(int) * S));
-    if (!e->d_sigs_rt) JF_HIP(e, hipMalloc(&e->d_sigs_rt, sizeof(SrcSignal) * S));
+    if (!e->d_live_idx) JF_HIP(e, e->d_live_idx.alloc(S));
+    if (!e->d_sigs_rt) JF_HIP(e, e->d_sigs_rt.alloc(S));
     if (e->n_live > 0) JF_HIP(e, h2d(e, e->d_live_idx, e->live_idx.data(), sizeof(int) * e->n_live));
     std::vector<SrcSignal> rt = e->h_sigs;
     for (int j = 0; j < e->n_live; j++) rt[e->live_idx[j]] = SrcSignal{e->hd_in + (size_t)j * B, e->B, 0};
@@ -337,41 +268,14 @@ static void live_stage_rt(jf_engine *e, const float *in, bool interleaved) {
 
 namespace {
 
+// KEMAR's elevation rings (hrtf_signals.cu:7); the kernels have their own copy (jf_kernels.hip)
+const float kKemarEle[kNumElev] = {-40, -30, -20, -10, 0, 10, 20, 30, 40, 50, 60, 70, 80, 90};
+
 void destroy_engine(jf_engine *e) {
     if (!e) return;
-    DeviceGuard bind(e);
+    DeviceGuard bind(e);  // (outlives the delete: the buffers are freed on the engine's device)
     if (e->rv_side) (void)hipStreamSynchronize(e->rv_side);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
-    free_reverb(e);
-    for (float *p : e->d_signal)
-        if (p) (void)hipFree(p);
-    (void)hipFree(e->d_htab);
-    (void)hipFree(e->d_tw);
-    (void)hipFree(e->d_tw2048);
-    (void)hipFree(e->d_twpack);
-    (void)hipFree(e->d_sigs);
-    (void)hipFree(e->d_zero);
-    for (int i = 0; i < 2; i++) {
-        (void)hipFree(e->d_state[i]);
-        (void)hipFree(e->d_hist[i]);
-    }
-    (void)hipFree(e->d_desc);
-    (void)hipFree(e->d_desc_ahead);
-    (void)hipFree(e->d_partial);
-    (void)hipFree(e->d_mix);
-    (void)hipFree(e->d_pos_rt);
-    (void)hipFree(e->d_traj);
-    (void)hipFree(e->d_order);
-    (void)hipFree(e->d_pick);
-    (void)hipFree(e->d_cloud_tri);
-    (void)hipFree(e->d_cloud_seed);
-    (void)hipFree(e->d_live_idx);
-    (void)hipFree(e->d_sigs_rt);
-    if (e->h_in) (void)hipHostFree(e->h_in);
-    if (e->h_pos_pinned) (void)hipHostFree(e->h_pos_pinned);
-    if (e->h_out_pinned) (void)hipHostFree(e->h_out_pinned);
-    if (e->h_done) (void)hipHostFree(e->h_done);
-    if (e->h_err) (void)hipHostFree(e->h_err);
     for (auto *pool : {&e->ev_prep, &e->ev_fused, &e->ev_mix, &e->ev_reverb})
         for (auto &p : *pool) {
             (void)hipEventDestroy(p.a);
@@ -381,13 +285,10 @@ void destroy_engine(jf_engine *e) {
     if (e->rv_ev_side) (void)hipEventDestroy(e->rv_ev_side);
     if (e->rv_side) (void)hipStreamDestroy(e->rv_side);
     if (e->stream) (void)hipStreamDestroy(e->stream);
-    delete e;
+    delete e;  // every buffer goes with its owner (DevBuf, PinnedBuf), after the streams have been waited for
 }
 
-// grid: the table of the HRTF set's measurement grid (null: the reference's KEMAR grid, 710 rows); cloud: a set on arbitrary
-// directions instead (its rows and its rule replace the grid's)
-int create_engine(const jf_config *cfg, const RingTable *grid, const float *hrir, int taps, jf_engine **out,
-                  const jf_cloud *cloud = nullptr) {
+int check_config(const jf_config *cfg, const float *hrir, int taps, jf_engine **out, int *pad_len) {
     if (!cfg || !hrir || !out) return fail(nullptr, JF_ERR_ARG, "null argument");
     *out = nullptr;
     const int B = cfg->frames_per_buffer;
@@ -413,164 +314,172 @@ int create_engine(const jf_config *cfg, const RingTable *grid, const float *hrir
                         "this library was built with an experiment switch that gives wrong results by design "
                         "(set JF_ALLOW_EXPERIMENT=1 to use it in a test)");
     }
-
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(nullptr, JF_ERR_DEVICE, "no HIP device available (this library has no CPU path)");
     if (cfg->device < 0 || cfg->device >= ndev) return fail(nullptr, JF_ERR_ARG, "device ordinal out of range");
+    *pad_len = pad;
+    return JF_OK;
+}
 
+// a set on arbitrary directions: the engine's own copies of the triangle records and the seed cells, on the host and in HBM
+int upload_cloud(jf_engine *e, const jf_cloud *cloud) {
+    e->rt = RingTable{};
+    e->rt.n_rows = (int)cloud->azi.size();
+    e->cloud_tri = cloud->tri;
+    e->cloud_seed = cloud->seed;
+    e->cloud_host = cloud->view;
+    e->cloud_host.tri = e->cloud_tri.data();
+    e->cloud_host.seed = e->cloud_seed.data();
+    JF_HIP(e, e->d_cloud_tri.alloc(e->cloud_tri.size()));
+    JF_HIP(e, e->d_cloud_seed.alloc(e->cloud_seed.size()));
+    JF_HIP(e, h2d(e, e->d_cloud_tri, e->cloud_tri.data(), sizeof(CloudTri) * e->cloud_tri.size()));
+    JF_HIP(e, h2d(e, e->d_cloud_seed, e->cloud_seed.data(), sizeof(int) * e->cloud_seed.size()));
+    e->rt.cloud = cloud->view;
+    e->rt.cloud.tri = e->d_cloud_tri;
+    e->rt.cloud.seed = e->d_cloud_seed;
+    return JF_OK;
+}
+
+// exp(+2 pi i j / 1024) as the reverb's transforms read it (d_tw), the same values re-laid per FFT pass for the spatialiser
+// (d_twpack; jf_device.h kTw*), and at PAD_LEN 2048 the 2048-point transforms' table
+int upload_twiddles(jf_engine *e) {
+    const std::vector<float2> tw = twiddles(1024);
+    JF_HIP(e, e->d_tw.alloc(1024));
+    JF_HIP(e, h2d(e, e->d_tw, tw.data(), sizeof(float2) * 1024));
+    std::vector<float2> pack(kTwPack);
+    for (int lane = 0; lane < 64; lane++) {
+        const int a = lane & 3, i = lane >> 2;
+        for (int t = 0; t < 16; t++) pack[kTwW3 + 64 * t + lane] = tw[(a * (i + 16 * t) + 768 * a) & 1023];
+        for (int q = 0; q < 8; q++) pack[kTwU + 64 * q + lane] = tw[lane + 64 * q];
+        for (int r = 0; r < 8; r++) pack[kTwWC + 64 * r + lane] = tw[(2 * r * lane) & 1023];
+    }
+    for (int m = 0; m < 16; m++)
+        for (int i = 0; i < 16; i++) pack[kTwW2 + 16 * m + i] = tw[(4 * i * m) & 1023];
+    for (int r = 0; r < 8; r++)
+        for (int k = 0; k < 8; k++) pack[kTwWB + 8 * r + k] = tw[(16 * r * k) & 1023];
+    JF_HIP(e, e->d_twpack.alloc(kTwPack));
+    JF_HIP(e, h2d(e, e->d_twpack, pack.data(), sizeof(float2) * kTwPack));
+    if (e->N != kN) {
+        const std::vector<float2> tw2 = twiddles(e->N);
+        JF_HIP(e, e->d_tw2048.alloc(e->N));
+        JF_HIP(e, h2d(e, e->d_tw2048, tw2.data(), sizeof(float2) * e->N));
+    }
+    return JF_OK;
+}
+
+// HRTF spectra on the GPU (read_hrtf_signals + transform_hrtfs)
+int build_table(jf_engine *e, const float *hrir, int taps) {
+    DevBuf<float> d_hrir;
+    const size_t n = (size_t)e->rt.n_rows * 2 * (size_t)taps;
+    JF_HIP(e, d_hrir.alloc(n));
+    JF_HIP(e, h2d(e, d_hrir, hrir, sizeof(float) * n));
+    JF_HIP(e, e->N == kN ? launch_table_build(d_hrir, e->rt.n_rows, taps, e->d_twpack, e->d_htab, e->stream)
+                         : launch_table2048_build(d_hrir, e->rt.n_rows, taps, e->d_tw2048, e->d_htab, e->stream));
+    JF_HIP(e, hipStreamSynchronize(e->stream));
+    return JF_OK;
+}
+
+// streams, buffers and tables of a new engine on cfg->device; whatever a failure leaves behind, destroy_engine takes
+int init_engine(jf_engine *e, const RingTable *grid, const float *hrir, int taps, const jf_cloud *cloud) {
+    const jf_config *cfg = &e->cfg;
+    const size_t S = (size_t)e->S, K = (size_t)e->maxK, N = (size_t)e->N, B = (size_t)e->B;
+    JF_HIP(e, hipSetDevice(cfg->device));
+    {
+        // the engine's stream at the highest priority the device offers, the side stream (the reverb's work ahead of time,
+        // run_reverb_stage) at the lowest: where the two meet, the block in hand goes first
+        int lo = 0, hi = 0;
+        JF_HIP(e, hipDeviceGetStreamPriorityRange(&lo, &hi));
+        JF_HIP(e, hipStreamCreateWithPriority(&e->stream, hipStreamNonBlocking, hi));
+        JF_HIP(e, hipStreamCreateWithPriority(&e->rv_side, hipStreamNonBlocking, lo));
+    }
+    JF_HIP(e, hipEventCreateWithFlags(&e->rv_ev_main, hipEventDisableTiming));
+    JF_HIP(e, hipEventCreateWithFlags(&e->rv_ev_side, hipEventDisableTiming));
+    for (int kind = 0; kind < 3; kind++) JF_HIP(e, fused_resident_workgroups(e->B / 64, kind, &e->resident_wgs[kind]));
+    {
+        int cus = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device) == hipSuccess && cus >= 16)
+            e->rv_side_wgs = 3 * cus / 4;
+        else
+            (void)hipGetLastError();
+    }
+    // (nothing of the engine's behaviour is read from the environment: jefferson_debug.h's setters are the overrides)
+    // (never at PAD_LEN 2048: 773 MB of rows; JF_FLAG_NO_INTERP_TABLE is implied there)
+    // (nor on a cloud: the rows are laid out for whole degrees on KEMAR's elevation range)
+    e->interp_avail = !(cfg->flags & JF_FLAG_NO_INTERP_TABLE) && e->N == kN && !cloud;
+    e->interp_use = e->interp_avail ? 2 : 0;
+    // the 710 measured rows only; the pre-interpolated ones come with the first run that takes them (ensure_interp_rows)
+    e->rt = grid ? *grid : ring_table();
+    if (cloud) {
+        const int rc = upload_cloud(e, cloud);
+        if (rc) return rc;
+    }
+    JF_HIP(e, e->d_htab.alloc((size_t)e->rt.n_rows * (N / 2)));
+    JF_HIP(e, e->d_sigs.alloc(S));
+    for (int i = 0; i < 2; i++) {
+        JF_HIP(e, e->d_state[i].alloc(S));
+        JF_HIP(e, e->d_hist[i].alloc(S * N));
+        JF_HIP(e, hipMemsetAsync(e->d_state[i], 0, sizeof(SrcState) * S, e->stream));
+        JF_HIP(e, hipMemsetAsync(e->d_hist[i], 0, sizeof(float) * S * N, e->stream));
+    }
+    JF_HIP(e, e->d_desc.alloc(S * K));
+    JF_HIP(e, e->d_desc_ahead.alloc(S * K));
+    JF_HIP(e, e->d_partial.alloc(S * K * 2 * B));
+    JF_HIP(e, e->d_mix.alloc(K * 2 * B));
+    JF_HIP(e, e->d_pos_rt.alloc(S * 5));
+    e->rt.pick = nullptr;
+    if (e->rt.kemar) {
+        // nearest table row per (ring, integer azimuth), by the search itself (host_pick_hrtf = hrtf_signals.cu:20-51)
+        std::vector<short> pick((size_t)kNumElev * kPickAzi);
+        for (int r = 0; r < kNumElev; r++)
+            for (int a = 0; a < kPickAzi; a++) pick[(size_t)r * kPickAzi + a] = (short)host_pick_hrtf(kKemarEle[r], (float)a);
+        JF_HIP(e, e->d_pick.alloc(pick.size()));
+        JF_HIP(e, h2d(e, e->d_pick, pick.data(), sizeof(short) * pick.size()));
+        e->rt.pick = e->d_pick;
+    }
+    JF_HIP(e, e->d_order.alloc(S));
+    e->order.resize(S);
+    for (size_t s = 0; s < S; s++) e->order[s] = (int)s;
+    JF_HIP(e, h2d(e, e->d_order, e->order.data(), sizeof(int) * S));
+    JF_HIP(e, e->h_pos_pinned.alloc(S * 5));
+    JF_HIP(e, e->h_out_pinned.alloc(2 * B * kRtMaxWgs));
+    JF_HIP(e, hipHostGetDevicePointer((void **)&e->hd_pos, e->h_pos_pinned, 0));
+    JF_HIP(e, hipHostGetDevicePointer((void **)&e->hd_out, e->h_out_pinned, 0));
+    JF_HIP(e, e->h_done.alloc(kRtMaxWgs));
+    memset(e->h_done, 0, sizeof(int) * kRtMaxWgs);
+    JF_HIP(e, hipHostGetDevicePointer((void **)&e->hd_done, e->h_done, 0));
+    // the error word, followed by 64 KB that timing experiments of the kernels may fill (JF_EXP_STAMPS)
+    JF_HIP(e, e->h_err.alloc(4 + 65536 / sizeof(int)));
+    memset(e->h_err, 0, sizeof(int) * 4 + 65536);
+    JF_HIP(e, hipHostGetDevicePointer((void **)&e->hd_err, e->h_err, 0));
+    e->d_signal.resize(S);
+    JF_HIP(e, e->d_zero.alloc(N));
+    JF_HIP(e, hipMemsetAsync(e->d_zero, 0, sizeof(float) * N, e->stream));
+    e->h_sigs.assign(S, SrcSignal{e->d_zero, e->N, 0});
+    JF_HIP(e, h2d(e, e->d_sigs, e->h_sigs.data(), sizeof(SrcSignal) * S));
+    // SoundSource::SoundSource() defaults (SoundSource.cu:3-16)
+    e->pos.assign(S, HostPos{0.0f, 0.0f, 0.5f, 0.0f, 0.0f, 0.5f});
+    const int rc = upload_twiddles(e);
+    return rc ? rc : build_table(e, hrir, taps);
+}
+
+// grid: the table of the HRTF set's measurement grid (null: the reference's KEMAR grid, 710 rows); cloud: a set on arbitrary
+// directions instead (its rows and its rule replace the grid's)
+int create_engine(const jf_config *cfg, const RingTable *grid, const float *hrir, int taps, jf_engine **out,
+                  const jf_cloud *cloud = nullptr) {
+    int pad = 0;
+    int rc = check_config(cfg, hrir, taps, out, &pad);
+    if (rc) return rc;
     jf_engine *e = new jf_engine();
     e->cfg = *cfg;
-    e->B = B;
+    e->B = cfg->frames_per_buffer;
     e->S = cfg->n_sources;
     e->maxK = cfg->max_batch_blocks;
     e->N = pad;
     e->Nc = pad / 2 + 1;
-    const size_t S = (size_t)e->S, K = (size_t)e->maxK, N = (size_t)e->N;
-    int rc = JF_OK;
     int prev_dev = -1;
     (void)hipGetDevice(&prev_dev);
-    auto body = [&]() -> int {
-        JF_HIP(e, hipSetDevice(cfg->device));
-        {
-            // the engine's stream at the highest priority the device offers, the side stream (the reverb's work ahead of time,
-            // run_reverb_stage) at the lowest: where the two meet, the block in hand goes first
-            int lo = 0, hi = 0;
-            JF_HIP(e, hipDeviceGetStreamPriorityRange(&lo, &hi));
-            JF_HIP(e, hipStreamCreateWithPriority(&e->stream, hipStreamNonBlocking, hi));
-            JF_HIP(e, hipStreamCreateWithPriority(&e->rv_side, hipStreamNonBlocking, lo));
-        }
-        JF_HIP(e, hipEventCreateWithFlags(&e->rv_ev_main, hipEventDisableTiming));
-        JF_HIP(e, hipEventCreateWithFlags(&e->rv_ev_side, hipEventDisableTiming));
-        for (int kind = 0; kind < 3; kind++) JF_HIP(e, fused_resident_workgroups(B / 64, kind, &e->resident_wgs[kind]));
-        {
-            int cus = 0;
-            if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device) == hipSuccess && cus >= 16)
-                e->rv_side_wgs = 3 * cus / 4;
-            else
-                (void)hipGetLastError();
-        }
-        // (nothing of the engine's behaviour is read from the environment: jefferson_debug.h's setters are the overrides)
-        // (never at PAD_LEN 2048: 773 MB of rows; JF_FLAG_NO_INTERP_TABLE is implied there)
-        // (nor on a cloud: the rows are laid out for whole degrees on KEMAR's elevation range)
-        e->interp_avail = !(cfg->flags & JF_FLAG_NO_INTERP_TABLE) && e->N == kN && !cloud;
-        e->interp_use = e->interp_avail ? 2 : 0;
-        // the 710 measured rows only; the pre-interpolated ones come with the first run that takes them (ensure_interp_rows)
-        e->rt = grid ? *grid : ring_table();
-        if (cloud) {
-            // the engine's own copies of the triangle records and the seed cells, on the host and in HBM
-            e->rt = RingTable{};
-            e->rt.n_rows = (int)cloud->azi.size();
-            e->cloud_tri = cloud->tri;
-            e->cloud_seed = cloud->seed;
-            e->cloud_host = cloud->view;
-            e->cloud_host.tri = e->cloud_tri.data();
-            e->cloud_host.seed = e->cloud_seed.data();
-            JF_HIP(e, hipMalloc(&e->d_cloud_tri, sizeof(CloudTri) * e->cloud_tri.size()));
-            JF_HIP(e, hipMalloc(&e->d_cloud_seed, sizeof(int) * e->cloud_seed.size()));
-            JF_HIP(e, h2d(e, e->d_cloud_tri, e->cloud_tri.data(), sizeof(CloudTri) * e->cloud_tri.size()));
-            JF_HIP(e, h2d(e, e->d_cloud_seed, e->cloud_seed.data(), sizeof(int) * e->cloud_seed.size()));
-            e->rt.cloud = cloud->view;
-            e->rt.cloud.tri = e->d_cloud_tri;
-            e->rt.cloud.seed = e->d_cloud_seed;
-        }
-        JF_HIP(e, hipMalloc(&e->d_htab, sizeof(float4) * (size_t)e->rt.n_rows * (N / 2)));
-        JF_HIP(e, hipMalloc(&e->d_tw, sizeof(float2) * 1024));
-        JF_HIP(e, hipMalloc(&e->d_sigs, sizeof(SrcSignal) * S));
-        for (int i = 0; i < 2; i++) {
-            JF_HIP(e, hipMalloc(&e->d_state[i], sizeof(SrcState) * S));
-            JF_HIP(e, hipMalloc(&e->d_hist[i], sizeof(float) * S * N));
-            JF_HIP(e, hipMemsetAsync(e->d_state[i], 0, sizeof(SrcState) * S, e->stream));
-            JF_HIP(e, hipMemsetAsync(e->d_hist[i], 0, sizeof(float) * S * N, e->stream));
-        }
-        JF_HIP(e, hipMalloc(&e->d_desc, sizeof(ItemDesc) * S * K));
-        JF_HIP(e, hipMalloc(&e->d_desc_ahead, sizeof(ItemDesc) * S * K));
-        JF_HIP(e, hipMalloc(&e->d_partial, sizeof(float) * S * K * 2 * B));
-        JF_HIP(e, hipMalloc(&e->d_mix, sizeof(float) * K * 2 * B));
-        JF_HIP(e, hipMalloc(&e->d_pos_rt, sizeof(float) * S * 5));
-        e->rt.pick = nullptr;
-        if (e->rt.kemar) {
-            // nearest table row per (ring, integer azimuth), by the search itself (host_pick_hrtf = hrtf_signals.cu:20-51)
-            static const int elev[kNumElev] = {-40, -30, -20, -10, 0, 10, 20, 30, 40, 50, 60, 70, 80, 90};
-            std::vector<short> pick((size_t)kNumElev * kPickAzi);
-            for (int r = 0; r < kNumElev; r++)
-                for (int a = 0; a < kPickAzi; a++) pick[(size_t)r * kPickAzi + a] = (short)host_pick_hrtf((float)elev[r], (float)a);
-            JF_HIP(e, hipMalloc(&e->d_pick, sizeof(short) * pick.size()));
-            JF_HIP(e, h2d(e, e->d_pick, pick.data(), sizeof(short) * pick.size()));
-            e->rt.pick = e->d_pick;
-        }
-        JF_HIP(e, hipMalloc(&e->d_order, sizeof(int) * S));
-        e->order.resize(S);
-        for (size_t s = 0; s < S; s++) e->order[s] = (int)s;
-        JF_HIP(e, h2d(e, e->d_order, e->order.data(), sizeof(int) * S));
-        // host memory the kernels read and write in place, and whose words the host polls while a kernel runs: mapped AND
-        // coherent (fine-grained) explicitly -- not left to the runtime's default or to HIP_HOST_COHERENT
-        const unsigned kHostFlags = hipHostMallocMapped | hipHostMallocCoherent;
-        JF_HIP(e, hipHostMalloc(&e->h_pos_pinned, sizeof(float) * S * 5, kHostFlags));
-        JF_HIP(e, hipHostMalloc(&e->h_out_pinned, sizeof(float) * 2 * B * kRtMaxWgs, kHostFlags));
-        JF_HIP(e, hipHostGetDevicePointer((void **)&e->hd_pos, e->h_pos_pinned, 0));
-        JF_HIP(e, hipHostGetDevicePointer((void **)&e->hd_out, e->h_out_pinned, 0));
-        JF_HIP(e, hipHostMalloc(&e->h_done, sizeof(int) * kRtMaxWgs, kHostFlags));
-        memset(e->h_done, 0, sizeof(int) * kRtMaxWgs);
-        JF_HIP(e, hipHostGetDevicePointer((void **)&e->hd_done, e->h_done, 0));
-        // the error word, followed by 64 KB that timing experiments of the kernels may fill (JF_EXP_STAMPS)
-        JF_HIP(e, hipHostMalloc(&e->h_err, sizeof(int) * 4 + 65536, kHostFlags));
-        memset(e->h_err, 0, sizeof(int) * 4 + 65536);
-        JF_HIP(e, hipHostGetDevicePointer((void **)&e->hd_err, e->h_err, 0));
-        e->d_signal.assign(S, nullptr);
-        JF_HIP(e, hipMalloc(&e->d_zero, sizeof(float) * N));
-        JF_HIP(e, hipMemsetAsync(e->d_zero, 0, sizeof(float) * N, e->stream));
-        e->h_sigs.assign(S, SrcSignal{e->d_zero, e->N, 0});
-        JF_HIP(e, h2d(e, e->d_sigs, e->h_sigs.data(), sizeof(SrcSignal) * S));
-        // SoundSource::SoundSource() defaults (SoundSource.cu:3-16)
-        e->pos.assign(S, HostPos{0.0f, 0.0f, 0.5f, 0.0f, 0.0f, 0.5f});
-
-        // twiddles exp(+2 pi i j / 1024) from double
-        std::vector<float2> tw(1024);
-        for (int j = 0; j < 1024; j++) {
-            const double a = 2.0 * 3.14159265358979323846264338327950288 * j / 1024.0;
-            tw[j] = make_float2((float)cos(a), (float)sin(a));
-        }
-        JF_HIP(e, h2d(e, e->d_tw, tw.data(), sizeof(float2) * 1024));
-        // the same values re-laid per FFT pass (jf_device.h kTw*)
-        std::vector<float2> pack(kTwPack);
-        for (int lane = 0; lane < 64; lane++) {
-            const int a = lane & 3, i = lane >> 2;
-            for (int t = 0; t < 16; t++) pack[kTwW3 + 64 * t + lane] = tw[(a * (i + 16 * t) + 768 * a) & 1023];
-            for (int q = 0; q < 8; q++) pack[kTwU + 64 * q + lane] = tw[lane + 64 * q];
-            for (int r = 0; r < 8; r++) pack[kTwWC + 64 * r + lane] = tw[(2 * r * lane) & 1023];
-        }
-        for (int m = 0; m < 16; m++)
-            for (int i = 0; i < 16; i++) pack[kTwW2 + 16 * m + i] = tw[(4 * i * m) & 1023];
-        for (int r = 0; r < 8; r++)
-            for (int k = 0; k < 8; k++) pack[kTwWB + 8 * r + k] = tw[(16 * r * k) & 1023];
-        JF_HIP(e, hipMalloc(&e->d_twpack, sizeof(float2) * kTwPack));
-        JF_HIP(e, h2d(e, e->d_twpack, pack.data(), sizeof(float2) * kTwPack));
-        if (e->N != kN) {  // the 2048-point transforms' table: exp(+2 pi i j / 2048) from double
-            std::vector<float2> tw2(e->N);
-            for (int j = 0; j < e->N; j++) {
-                const double a = 2.0 * 3.14159265358979323846264338327950288 * j / (double)e->N;
-                tw2[j] = make_float2((float)cos(a), (float)sin(a));
-            }
-            JF_HIP(e, hipMalloc(&e->d_tw2048, sizeof(float2) * e->N));
-            JF_HIP(e, h2d(e, e->d_tw2048, tw2.data(), sizeof(float2) * e->N));
-        }
-
-        // HRTF spectra on the GPU (read_hrtf_signals + transform_hrtfs)
-        float *d_hrir = nullptr;
-        const size_t hb = sizeof(float) * (size_t)e->rt.n_rows * 2 * (size_t)taps;
-        JF_HIP(e, hipMalloc(&d_hrir, hb));
-        hipError_t s1 = h2d(e, d_hrir, hrir, hb);
-        hipError_t s2 = s1;
-        if (s1 == hipSuccess)
-            s2 = e->N == kN ? launch_table_build(d_hrir, e->rt.n_rows, taps, e->d_twpack, e->d_htab, e->stream)
-                            : launch_table2048_build(d_hrir, e->rt.n_rows, taps, e->d_tw2048, e->d_htab, e->stream);
-        hipError_t s3 = s2 == hipSuccess ? hipStreamSynchronize(e->stream) : s2;
-        (void)hipFree(d_hrir);
-        JF_HIP(e, s3);
-        return JF_OK;
-    };
-    rc = body();
+    rc = init_engine(e, grid, hrir, taps, cloud);
     if (rc != JF_OK) {
         g_create_error = e->err;
         destroy_engine(e);
@@ -593,7 +502,6 @@ int jf_engine_create(const jf_config *cfg, const float *hrir, int taps, jf_engin
 }
 
 // ---- any grid of elevation rings ("SOFA / other HRTF sets", FuturePlans.md:21) ----
-static const float kKemarEle[kNumElev] = {-40, -30, -20, -10, 0, 10, 20, 30, 40, 50, 60, 70, 80, 90};
 static int g_kemar_count[kNumElev];
 
 int jf_kemar_grid(jf_hrtf_grid *out) {
@@ -690,25 +598,40 @@ int jf_sofa_table(const jf_sofa_set *set, float tol_deg, jf_grid_layout *layout,
     });
 }
 
-int jf_engine_create_sofa(const jf_config *cfg, const char *path, float tol_deg, jf_engine **out) {
-    return jf_guard([&]() -> int {
+// From a SOFA file to what an engine is created from: the set (released on every path by its owner), its taps checked
+// against the configuration, and the hrir vector sized for sofa_table / sofa_cloud to fill.
+struct SofaFile {
+    jf_sofa_set set;
+    bool open = false;
+    ~SofaFile() {
+        if (open) sofa_release(&set);
+    }
+};
+static int sofa_open(const jf_config *cfg, const char *path, jf_engine **out, SofaFile *f, int *taps, std::vector<float> *hrir) {
     if (out) *out = nullptr;
     if (!cfg || !path || !out) return fail(nullptr, JF_ERR_ARG, "null argument");
-    jf_sofa_set set;
     std::string err;
-    int rc = sofa_read(path, &set, &err);
+    const int rc = sofa_read(path, &f->set, &err);
     if (rc) return fail(nullptr, rc, err);
-    struct Release {
-        jf_sofa_set *s;
-        ~Release() { sofa_release(s); }
-    } release{&set};
-    const int taps = sofa_taps(&set, &err);
-    if (taps < 0) return fail(nullptr, taps, std::string(path) + ": " + err);
-    if (taps > cfg->hrtf_len)
-        return fail(nullptr, JF_ERR_ARG, std::string(path) + ": impulse responses of " + std::to_string(taps) + " taps, hrtf_len is " + std::to_string(cfg->hrtf_len));
-    std::vector<float> hrir((size_t)set.n_measurements * 2 * (size_t)taps);
+    f->open = true;
+    *taps = sofa_taps(&f->set, &err);
+    if (*taps < 0) return fail(nullptr, *taps, std::string(path) + ": " + err);
+    if (*taps > cfg->hrtf_len)
+        return fail(nullptr, JF_ERR_ARG, std::string(path) + ": impulse responses of " + std::to_string(*taps) + " taps, hrtf_len is " + std::to_string(cfg->hrtf_len));
+    hrir->resize((size_t)f->set.n_measurements * 2 * (size_t)*taps);
+    return JF_OK;
+}
+
+int jf_engine_create_sofa(const jf_config *cfg, const char *path, float tol_deg, jf_engine **out) {
+    return jf_guard([&]() -> int {
+    SofaFile f;
+    int taps = 0;
+    std::vector<float> hrir;
+    std::string err;
+    int rc = sofa_open(cfg, path, out, &f, &taps, &hrir);
+    if (rc) return rc;
     jf_grid_layout lay;
-    rc = sofa_table(&set, tol_deg, &lay, hrir.data(), taps, &err);
+    rc = sofa_table(&f.set, tol_deg, &lay, hrir.data(), taps, &err);
     if (rc) return fail(nullptr, rc, std::string(path) + ": " + err);
     RingTable rt;
     rc = host_grid_table(lay.n_rings, lay.ring_elevation, lay.ring_count, lay.ring_step, &rt, &err);
@@ -777,23 +700,14 @@ int jf_sofa_cloud(const jf_sofa_set *set, float tol_deg, jf_cloud **out, float *
 
 int jf_engine_create_sofa_cloud(const jf_config *cfg, const char *path, float tol_deg, jf_engine **out) {
     return jf_guard([&]() -> int {
-    if (out) *out = nullptr;
-    if (!cfg || !path || !out) return fail(nullptr, JF_ERR_ARG, "null argument");
-    jf_sofa_set set;
+    SofaFile f;
+    int taps = 0;
+    std::vector<float> hrir;
     std::string err;
-    int rc = sofa_read(path, &set, &err);
-    if (rc) return fail(nullptr, rc, err);
-    struct Release {
-        jf_sofa_set *s;
-        ~Release() { sofa_release(s); }
-    } release{&set};
-    const int taps = sofa_taps(&set, &err);
-    if (taps < 0) return fail(nullptr, taps, std::string(path) + ": " + err);
-    if (taps > cfg->hrtf_len)
-        return fail(nullptr, JF_ERR_ARG, std::string(path) + ": impulse responses of " + std::to_string(taps) + " taps, hrtf_len is " + std::to_string(cfg->hrtf_len));
-    std::vector<float> hrir((size_t)set.n_measurements * 2 * (size_t)taps);
+    int rc = sofa_open(cfg, path, out, &f, &taps, &hrir);
+    if (rc) return rc;
     jf_cloud cloud;
-    rc = sofa_cloud(&set, tol_deg, &cloud, hrir.data(), taps, &err);
+    rc = sofa_cloud(&f.set, tol_deg, &cloud, hrir.data(), taps, &err);
     if (rc) return fail(nullptr, rc, std::string(path) + ": " + err);
     return create_engine(cfg, nullptr, hrir.data(), taps, out, &cloud);
     });
@@ -820,20 +734,41 @@ int jf_pad_len(const jf_engine *e) { return e ? e->N : JF_ERR_ARG; }
 int jf_num_sources(const jf_engine *e) { return e ? e->S : JF_ERR_ARG; }
 int jf_table_rows(const jf_engine *e) { return e ? e->rt.n_rows : JF_ERR_ARG; }
 
+// The one way a source gets another signal: d_new (null: none, the shared zeros) of n_dev floats, live from now on or
+// resident.  The stage launched ahead read the old signal and so may the side stream's transforms: both are waited for
+// before the old buffer goes.
+static int swap_signal(jf_engine *e, int src, DevBuf<float> d_new, int n_dev, bool live) {
+    {
+        const int rc = rv_ahead_discard(e);
+        if (rc) return rc;
+    }
+    JF_HIP(e, hipStreamSynchronize(e->stream));
+    if (e->rv_side && e->rv_side_busy) JF_HIP(e, hipStreamSynchronize(e->rv_side));
+    if (live && e->live.empty()) e->live.assign((size_t)e->S, 0);
+    e->d_signal[src] = std::move(d_new);  // the old signal is released; the source's window stays as it is
+    e->h_sigs[src] = e->d_signal[src] ? SrcSignal{e->d_signal[src], n_dev, 0} : SrcSignal{e->d_zero, e->N, 0};
+    JF_HIP(e, h2d(e, e->d_sigs + src, &e->h_sigs[src], sizeof(SrcSignal)));
+    if (!e->live.empty()) {  // (the real-time kernel's records follow)
+        e->live[src] = live;
+        const int rc = live_refresh(e);
+        if (rc) return rc;
+    }
+    const int zero = 0;  // count = 0 (cudaPart.cu:198-199 run with a fresh source)
+    if (e->rv_P > 0)  // the play position of the dry signal lives in the reverb stage
+        JF_HIP(e, h2d(e, e->d_rv_count[e->cur] + src, &zero, sizeof(int)));
+    else
+        JF_HIP(e, h2d(e, &e->d_state[e->cur][src].count, &zero, sizeof(int)));
+    return JF_OK;
+}
+
 int jf_source_set_signal(jf_engine *e, int src, const float *mono, size_t n) {
     return jf_guard([&]() -> int {
     DeviceGuard bind(e);
     if (!valid_src(e, src) || (n && !mono) || n > 0x7fffffffu) return fail(e, JF_ERR_ARG, "bad source or signal");
-    {
-        const int rc = rv_ahead_discard(e);  // (the stage launched ahead read the old signal)
-        if (rc) return rc;
-    }
-    JF_HIP(e, hipStreamSynchronize(e->stream));
-    if (e->rv_side && e->rv_side_busy) JF_HIP(e, hipStreamSynchronize(e->rv_side));  // its transforms read the signals
     // The device copy always has length >= PAD_LEN so that the kernel wraps the loop with
     // one conditional subtract: a shorter signal is stored as whole repetitions of itself
     // (the looped stream is identical), an empty one as the shared zero buffer.
-    float *d_new = nullptr;
+    DevBuf<float> d_new;
     size_t n_dev = n;
     if (n) {
         const float *src_host = mono;
@@ -845,28 +780,10 @@ int jf_source_set_signal(jf_engine *e, int src, const float *mono, size_t n) {
             src_host = tiled.data();
             n_dev = reps * n;
         }
-        JF_HIP(e, hipMalloc(&d_new, sizeof(float) * n_dev));
-        hipError_t st = h2d(e, d_new, src_host, sizeof(float) * n_dev);
-        if (st != hipSuccess) {
-            (void)hipFree(d_new);
-            JF_HIP(e, st);
-        }
+        JF_HIP(e, d_new.alloc(n_dev));
+        JF_HIP(e, h2d(e, d_new, src_host, sizeof(float) * n_dev));
     }
-    if (e->d_signal[src]) (void)hipFree(e->d_signal[src]);
-    e->d_signal[src] = d_new;
-    e->h_sigs[src] = n ? SrcSignal{d_new, (int)n_dev, 0} : SrcSignal{e->d_zero, e->N, 0};
-    JF_HIP(e, h2d(e, e->d_sigs + src, &e->h_sigs[src], sizeof(SrcSignal)));
-    if (!e->live.empty()) {  // (a live source becomes resident again; the real-time kernel's records follow)
-        e->live[src] = 0;
-        const int rc = live_refresh(e);
-        if (rc) return rc;
-    }
-    const int zero = 0;  // count = 0 (cudaPart.cu:198-199 run with a fresh source)
-    if (e->rv_P > 0)  // the play position of the dry signal lives in the reverb stage
-        JF_HIP(e, h2d(e, e->d_rv_count[e->cur] + src, &zero, sizeof(int)));
-    else
-        JF_HIP(e, h2d(e, &e->d_state[e->cur][src].count, &zero, sizeof(int)));
-    return JF_OK;
+    return swap_signal(e, src, std::move(d_new), (int)n_dev, false);  // (a live source becomes resident again)
     });
 }
 
@@ -877,12 +794,6 @@ int jf_source_set_live(jf_engine *e, int src, int live) {
     const bool is_live = !e->live.empty() && e->live[src];
     if (is_live == (live != 0)) return JF_OK;
     if (!live) return jf_source_set_signal(e, src, nullptr, 0);  // resident again, and silent
-    {
-        const int rc = rv_ahead_discard(e);  // (the stage launched ahead read the old signal)
-        if (rc) return rc;
-    }
-    JF_HIP(e, hipStreamSynchronize(e->stream));
-    if (e->rv_side && e->rv_side_busy) JF_HIP(e, hipStreamSynchronize(e->rv_side));
     if (e->live_len == 0) {
         // a multiple of B that holds a window's worth (the kernels wrap with one conditional subtract) and a whole batch call
         const long long need = std::max<long long>(e->N, (long long)e->maxK * e->B);
@@ -890,32 +801,11 @@ int jf_source_set_live(jf_engine *e, int src, int live) {
         if (len > 0x7fffffff) return fail(e, JF_ERR_ARG, "max_batch_blocks too large for live sources");
         e->live_len = (int)len;
     }
-    float *d_new = nullptr;
-    JF_HIP(e, hipMalloc(&d_new, sizeof(float) * (size_t)e->live_len));
-    {
-        hipError_t st = hipMemsetAsync(d_new, 0, sizeof(float) * (size_t)e->live_len, e->stream);
-        if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
-        if (st != hipSuccess) {
-            (void)hipFree(d_new);
-            JF_HIP(e, st);
-        }
-    }
-    if (e->live.empty()) e->live.assign((size_t)e->S, 0);
-    if (e->d_signal[src]) (void)hipFree(e->d_signal[src]);  // the resident signal is released; the window stays as it is
-    e->d_signal[src] = d_new;
-    e->h_sigs[src] = SrcSignal{d_new, e->live_len, 0};
-    e->live[src] = 1;
-    JF_HIP(e, h2d(e, e->d_sigs + src, &e->h_sigs[src], sizeof(SrcSignal)));
-    {
-        const int rc = live_refresh(e);
-        if (rc) return rc;
-    }
-    const int zero = 0;  // the play position, as after a signal swap
-    if (e->rv_P > 0)
-        JF_HIP(e, h2d(e, e->d_rv_count[e->cur] + src, &zero, sizeof(int)));
-    else
-        JF_HIP(e, h2d(e, &e->d_state[e->cur][src].count, &zero, sizeof(int)));
-    return JF_OK;
+    DevBuf<float> d_new;
+    JF_HIP(e, d_new.alloc((size_t)e->live_len));
+    JF_HIP(e, hipMemsetAsync(d_new, 0, sizeof(float) * (size_t)e->live_len, e->stream));
+    JF_HIP(e, hipStreamSynchronize(e->stream));
+    return swap_signal(e, src, std::move(d_new), e->live_len, true);
     });
 }
 
@@ -1055,24 +945,10 @@ static int submit_block(jf_engine *e, const float *in, bool interleaved) {
                 const int rc = run_reverb_stage(e, p, 1, &head, &head_fused);
                 if (rc) return rc;
             }
-            FusedParams P;
-            P.htab = e->d_htab;
+            FusedParams P = fused_params(e, p, 1, kernel_mode(e));  // (no desc, no partial: the kernel keeps both to itself)
             P.tw = e->d_twpack;
-            P.desc = nullptr;
             P.sigs = e->rv_P > 0 ? e->d_sigs_wet : e->n_live > 0 ? e->d_sigs_rt : e->d_sigs;
-            P.st_in = e->d_state[p];
-            P.st_out = e->d_state[p ^ 1];
-            P.hist_in = e->d_hist[p];
-            P.hist_out = e->d_hist[p ^ 1];
             P.pos = e->hd_pos;
-            P.partial = nullptr;
-            P.S = e->S;
-            P.K = 1;
-            P.B = e->B;
-            P.G = 1;
-            P.err = e->hd_err;
-            P.order = e->d_order;
-            P.mode = kernel_mode(e);
             // a wave per source, 8 or 16 waves to the workgroup (jf_kernels.hip: rt_block_kernel); at most kRtMaxWgs workgroups
             // = 2048 sources: beyond that a wave takes several
             const int rtw = rt_waves_per_wg(e->S);
@@ -1096,14 +972,7 @@ static int submit_block(jf_engine *e, const float *in, bool interleaved) {
             if (rv_ahead_possible(e)) {
                 // the NEXT block's stage, behind this block's spatialiser (jf_engine::rv_ahead)
                 e->kernels_frozen = jf_debug_last_kernels(e);
-                e->rv_book.rv_head = e->rv_head;
-                e->rv_book.rv_blocks = e->rv_blocks;
-                e->rv_book.rv_fut_m = e->rv_fut_m;
-                e->rv_book.last_rv_form = e->last_rv_form;
-                e->rv_book.last_plan = e->last_plan;
-                e->rv_book.last_side = e->last_side;
-                e->rv_book.last_catchup = e->last_catchup;
-                e->rv_book.last_small_fft = e->last_small_fft;
+                e->rv_book = e->stage;
                 const int rc = run_reverb_stage(e, e->cur, 1);
                 if (rc) return rc;
                 e->rv_ahead = true;
@@ -1245,9 +1114,6 @@ int jf_set_pause(jf_engine *e, int paused) {
     });
 }
 
-
-
-
 // ---- batch -----------------------------------------------------------------
 static int upload_positions(jf_engine *e, int total_blocks, const float *positions) {
     return jf_guard([&]() -> int {
@@ -1258,10 +1124,9 @@ static int upload_positions(jf_engine *e, int total_blocks, const float *positio
     e->ahead.valid = false;
     const size_t bytes = sizeof(float) * 5 * (size_t)e->S * (size_t)total_blocks;
     if (total_blocks > e->traj_blocks) {
-        (void)hipFree(e->d_traj);
-        e->d_traj = nullptr;
+        e->d_traj.reset();  // (before the larger one is allocated: the two never exist side by side)
         e->traj_blocks = 0;
-        JF_HIP(e, hipMalloc(&e->d_traj, bytes));
+        JF_HIP(e, e->d_traj.alloc(bytes / sizeof(float)));
     }
     e->traj_blocks = total_blocks;
     JF_HIP(e, h2d(e, e->d_traj, positions, bytes));
@@ -1463,37 +1328,7 @@ int jf_batch_fetch(jf_engine *e, int n_blocks, float *out_mix) {
     });
 }
 
-
-
-
-
-
-
-
-
-
-
-
-
-
-
-
-
-
-
-
-
-
-
-
-
-
-
-
-
-
 float jf_last_block_peak(const jf_engine *e) { return e ? e->last_peak : 0.0f; }
-
 
 // ---- WAV -----------------------------------------------------------------------
 int jf_wav_read_mono(const char *path, float **out, size_t *n_frames, int *sample_rate) {

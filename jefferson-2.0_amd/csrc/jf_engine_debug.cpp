@@ -3,6 +3,19 @@
 // device buffers.  None of them is part of the drop-in boundary (include/jefferson.h: jf_engine.cpp, jf_engine_reverb.cpp).
 #include "jf_engine_internal.h"
 
+// The preamble of every setter that changes what a reverb stage does or which path a block takes: refuse a null engine
+// (without touching HIP), bind the device, take back the stage launched ahead (it may have gone ahead in the old form);
+// `set` then checks its own argument and stores it.
+template <class F>
+static int stage_setter(jf_engine *e, F &&set) {
+    return jf_guard([&]() -> int {
+    if (!e) return JF_ERR_ARG;
+    DeviceGuard bind(e);
+    const int rc = rv_ahead_discard(e);
+    return rc ? rc : set();
+    });
+}
+
 extern "C" {
 
 int jf_debug_hdf5_read(const char *path, const char *dataset, double **out, int *rank, unsigned long long *dims) {
@@ -52,14 +65,7 @@ float *jf_batch_partial_device(jf_engine *e) { return e ? e->d_partial : nullptr
 void *jf_engine_stream(jf_engine *e) { return e ? (void *)e->stream : nullptr; }
 
 int jf_profile_enable(jf_engine *e, int enable) {
-    return jf_guard([&]() -> int {
-    if (e) {
-        DeviceGuard bind_(e);
-        const int rc_ = rv_ahead_discard(e);  // (the next block's stage may have gone ahead in the old form)
-        if (rc_) return rc_;
-    }
-    DeviceGuard bind(e);
-    if (!e) return JF_ERR_ARG;
+    return stage_setter(e, [&]() -> int {
     JF_HIP(e, hipStreamSynchronize(e->stream));
     e->profiling = enable < 0 ? 0 : (enable > 2 ? 2 : enable);
     e->ev_used = 0;
@@ -114,13 +120,8 @@ int jf_debug_copy_from_device(jf_engine *e, const void *device_ptr, void *host, 
 }
 
 int jf_debug_set_rt_max_sources(jf_engine *e, int n) {
-    return jf_guard([&]() -> int {
-    if (e) {
-        DeviceGuard bind_(e);
-        const int rc_ = rv_ahead_discard(e);  // (the next block's stage may have gone ahead in the old form)
-        if (rc_) return rc_;
-    }
-    if (!e || n < 0) return JF_ERR_ARG;
+    return stage_setter(e, [&]() -> int {
+    if (n < 0) return JF_ERR_ARG;
     e->rt_max_sources = n;
     return JF_OK;
     });
@@ -149,13 +150,8 @@ int jf_debug_source_order(const jf_engine *e, int *order) {
 }
 
 int jf_debug_set_reverb_form(jf_engine *e, int form) {
-    return jf_guard([&]() -> int {
-    if (e) {
-        DeviceGuard bind_(e);
-        const int rc_ = rv_ahead_discard(e);  // (the next block's stage may have gone ahead in the old form)
-        if (rc_) return rc_;
-    }
-    if (!e || form < 0 || form > 3) return JF_ERR_ARG;
+    return stage_setter(e, [&]() -> int {
+    if (form < 0 || form > 3) return JF_ERR_ARG;
     e->rv_form = form;
     return JF_OK;
     });
@@ -231,11 +227,7 @@ int jf_debug_set_reverb_partitioning(jf_engine *e, int how) {
 }
 
 int jf_debug_set_reverb_ahead(jf_engine *e, int on) {
-    return jf_guard([&]() -> int {
-    if (!e) return JF_ERR_ARG;
-    DeviceGuard bind(e);
-    const int rc = rv_ahead_discard(e);
-    if (rc) return rc;
+    return stage_setter(e, [&]() -> int {
     e->rv_ahead_on = on != 0;
     return JF_OK;
     });
@@ -244,39 +236,21 @@ int jf_debug_set_reverb_ahead(jf_engine *e, int on) {
 int jf_debug_reverb_ahead_pending(const jf_engine *e) { return e ? (e->rv_ahead ? 1 : 0) : JF_ERR_ARG; }
 
 int jf_debug_set_reverb_lazy_state(jf_engine *e, int on) {
-    return jf_guard([&]() -> int {
-    if (e) {
-        DeviceGuard bind_(e);
-        const int rc_ = rv_ahead_discard(e);  // (the next block's stage may have gone ahead in the old form)
-        if (rc_) return rc_;
-    }
-    if (!e) return JF_ERR_ARG;
+    return stage_setter(e, [&]() -> int {
     e->rv_lazy_small = on != 0;  // (transforms already put off are still formed by the call that needs them)
     return JF_OK;
     });
 }
 
 int jf_debug_set_reverb_head_fused(jf_engine *e, int on) {
-    return jf_guard([&]() -> int {
-    if (e) {
-        DeviceGuard bind_(e);
-        const int rc_ = rv_ahead_discard(e);  // (the next block's stage may have gone ahead in the old form)
-        if (rc_) return rc_;
-    }
-    if (!e) return JF_ERR_ARG;
+    return stage_setter(e, [&]() -> int {
     e->rv_head_fused = on != 0;
     return JF_OK;
     });
 }
 
 int jf_debug_set_reverb_async(jf_engine *e, int on) {
-    return jf_guard([&]() -> int {
-    if (e) {
-        DeviceGuard bind_(e);
-        const int rc_ = rv_ahead_discard(e);  // (the next block's stage may have gone ahead in the old form)
-        if (rc_) return rc_;
-    }
-    if (!e) return JF_ERR_ARG;
+    return stage_setter(e, [&]() -> int {
     e->rv_async = on != 0;  // what the side stream has in flight is waited for by the next call's stage (run_reverb_stage)
     return JF_OK;
     });
@@ -335,30 +309,21 @@ int jf_debug_interp_device(jf_engine *e, int n, const float *ele, const float *a
     return jf_guard([&]() -> int {
     DeviceGuard bind(e);
     if (!e || n <= 0 || !ele || !azi || !rows || !weights || !nterms) return JF_ERR_ARG;
-    float *d_e = nullptr, *d_a = nullptr, *d_w = nullptr;
-    int *d_r = nullptr, *d_n = nullptr;
-    auto body = [&]() -> int {
-        JF_HIP(e, hipMalloc(&d_e, sizeof(float) * n));
-        JF_HIP(e, hipMalloc(&d_a, sizeof(float) * n));
-        JF_HIP(e, hipMalloc(&d_w, sizeof(float) * 4 * n));
-        JF_HIP(e, hipMalloc(&d_r, sizeof(int) * 4 * n));
-        JF_HIP(e, hipMalloc(&d_n, sizeof(int) * n));
-        JF_HIP(e, h2d(e, d_e, ele, sizeof(float) * n));
-        JF_HIP(e, h2d(e, d_a, azi, sizeof(float) * n));
-        JF_HIP(e, launch_interp_debug(e->rt, d_e, d_a, d_r, d_w, d_n, n, corrected_rule(e) ? 1 : 0, e->stream));
-        JF_HIP(e, hipStreamSynchronize(e->stream));
-        JF_HIP(e, hipMemcpy(rows, d_r, sizeof(int) * 4 * n, hipMemcpyDeviceToHost));
-        JF_HIP(e, hipMemcpy(weights, d_w, sizeof(float) * 4 * n, hipMemcpyDeviceToHost));
-        JF_HIP(e, hipMemcpy(nterms, d_n, sizeof(int) * n, hipMemcpyDeviceToHost));
-        return JF_OK;
-    };
-    int rc = body();
-    (void)hipFree(d_e);
-    (void)hipFree(d_a);
-    (void)hipFree(d_w);
-    (void)hipFree(d_r);
-    (void)hipFree(d_n);
-    return rc;
+    DevBuf<float> d_e, d_a, d_w;
+    DevBuf<int> d_r, d_n;
+    JF_HIP(e, d_e.alloc(n));
+    JF_HIP(e, d_a.alloc(n));
+    JF_HIP(e, d_w.alloc(4 * (size_t)n));
+    JF_HIP(e, d_r.alloc(4 * (size_t)n));
+    JF_HIP(e, d_n.alloc(n));
+    JF_HIP(e, h2d(e, d_e, ele, sizeof(float) * n));
+    JF_HIP(e, h2d(e, d_a, azi, sizeof(float) * n));
+    JF_HIP(e, launch_interp_debug(e->rt, d_e, d_a, d_r, d_w, d_n, n, corrected_rule(e) ? 1 : 0, e->stream));
+    JF_HIP(e, hipStreamSynchronize(e->stream));
+    JF_HIP(e, hipMemcpy(rows, d_r, sizeof(int) * 4 * n, hipMemcpyDeviceToHost));
+    JF_HIP(e, hipMemcpy(weights, d_w, sizeof(float) * 4 * n, hipMemcpyDeviceToHost));
+    JF_HIP(e, hipMemcpy(nterms, d_n, sizeof(int) * n, hipMemcpyDeviceToHost));
+    return JF_OK;
     });
 }
 
@@ -366,25 +331,19 @@ int jf_debug_rfft_device(jf_engine *e, int n, const float *windows, float *spect
     return jf_guard([&]() -> int {
     DeviceGuard bind(e);
     if (!e || n <= 0 || !windows || !spectra) return JF_ERR_ARG;
-    float *d_w = nullptr;
-    float2 *d_s = nullptr;
-    auto body = [&]() -> int {
-        const size_t N = (size_t)e->N, Nc = (size_t)e->Nc;
-        JF_HIP(e, hipMalloc(&d_w, sizeof(float) * (size_t)n * N));
-        JF_HIP(e, hipMalloc(&d_s, sizeof(float2) * (size_t)n * Nc));
-        JF_HIP(e, h2d(e, d_w, windows, sizeof(float) * (size_t)n * N));
-        if (e->N == kN)
-            JF_HIP(e, launch_rfft_debug(d_w, n, e->d_twpack, d_s, e->stream));
-        else
-            JF_HIP(e, launch_rfft2048_debug(d_w, n, e->d_tw2048, d_s, e->stream));
-        JF_HIP(e, hipStreamSynchronize(e->stream));
-        JF_HIP(e, hipMemcpy(spectra, d_s, sizeof(float2) * (size_t)n * Nc, hipMemcpyDeviceToHost));
-        return JF_OK;
-    };
-    int rc = body();
-    (void)hipFree(d_w);
-    (void)hipFree(d_s);
-    return rc;
+    DevBuf<float> d_w;
+    DevBuf<float2> d_s;
+    const size_t N = (size_t)e->N, Nc = (size_t)e->Nc;
+    JF_HIP(e, d_w.alloc((size_t)n * N));
+    JF_HIP(e, d_s.alloc((size_t)n * Nc));
+    JF_HIP(e, h2d(e, d_w, windows, sizeof(float) * (size_t)n * N));
+    if (e->N == kN)
+        JF_HIP(e, launch_rfft_debug(d_w, n, e->d_twpack, d_s, e->stream));
+    else
+        JF_HIP(e, launch_rfft2048_debug(d_w, n, e->d_tw2048, d_s, e->stream));
+    JF_HIP(e, hipStreamSynchronize(e->stream));
+    JF_HIP(e, hipMemcpy(spectra, d_s, sizeof(float2) * (size_t)n * Nc, hipMemcpyDeviceToHost));
+    return JF_OK;
     });
 }
 
@@ -399,8 +358,8 @@ const char *jf_debug_last_kernels(jf_engine *e) {
         if (e->last_ingest) k = "live_ingest_kernel;";
         if (!e->last_rt && !e->last_prep_skipped) k += "prep_kernel;";
         if (e->rv_P > 0) {
-            if (e->last_catchup) k += "reverb_fft_kernel<" + bs + ">@ring;";
-            const ReverbPlan &pl = e->last_plan;
+            if (e->stage.last_catchup) k += "reverb_fft_kernel<" + bs + ">@ring;";
+            const ReverbPlan &pl = e->stage.last_plan;
             const std::string b1 = std::to_string(e->rv_B1);
             auto per_wg = [&](int) { return std::string(",1>;"); };  // transforms per workgroup and turn (persistent since round 5)
             auto products = [&](const ReverbBigParams &g) {
@@ -421,32 +380,32 @@ const char *jf_debug_last_kernels(jf_engine *e) {
                 return "reverb_mac_kernel<" + bs + "," + std::to_string(form == 2 ? grp : 1) + ">;";
             };
             if (pl.big) k += products(pl.tail_early);
-            if (e->last_rv_form == 5) {
+            if (e->stage.last_rv_form == 5) {
                 // (the head ran inside the real-time kernel, named below; transforms left in line follow it)
-            } else if (e->last_rv_form == 4) {
+            } else if (e->stage.last_rv_form == 4) {
                 k += stage_b(4);
                 if (pl.big) k += transforms(pl.transforms);
             } else {
-                if (e->last_small_fft) k += "reverb_fft_kernel<" + bs + ">;";
+                if (e->stage.last_small_fft) k += "reverb_fft_kernel<" + bs + ">;";
                 if (pl.big) {
                     if (pl.n_ranges > 1) k += stage_b(pl.forms[0]);
                     k += transforms(pl.transforms);
                     k += products(pl.middle) + products(pl.tail_late);
                     k += stage_b(pl.forms[pl.n_ranges > 1 ? 1 : 0]);
                 } else {
-                    k += stage_b(e->last_rv_form);
+                    k += stage_b(e->stage.last_rv_form);
                 }
             }
         }
-        if (e->rv_P > 0) k += e->last_side;
+        if (e->rv_P > 0) k += e->stage.last_side;
         // launch_mix: few partial blocks per audio block (16, 32 or 64 groups) take the one-thread-per-float form
         const int n_part = e->last_group > 0 ? e->S / e->last_group : e->S;
         const std::string mix_name = (n_part == 16 || n_part == 32 || n_part == 64)
                                          ? ";mix_few_kernel<" + std::to_string(n_part / 16) + ">" : std::string(";mix_kernel");
         if (e->last_rt) {
-            const bool fused = e->rv_P > 0 && e->last_rv_form == 5;
+            const bool fused = e->rv_P > 0 && e->stage.last_rv_form == 5;
             k += "rt_block_kernel<" + nb + "," + std::to_string(rt_waves_per_wg(e->S)) + (fused ? ",reverb>" : ">");
-            if (fused && e->last_plan.big && e->last_plan.transforms.n_tr > 0) {
+            if (fused && e->stage.last_plan.big && e->stage.last_plan.transforms.n_tr > 0) {
                 const std::string b1 = std::to_string(e->rv_B1);
                 k += ";reverb_big_fft_kernel<" + b1 + ",1>";
             }
@@ -484,30 +443,21 @@ int jf_debug_stage_taps(jf_engine *e, int n, const float *positions, const float
     DeviceGuard bind(e);
     if (!e || n <= 0 || !positions || !dist || (spectra && !windows)) return JF_ERR_ARG;
     if (e->N != kN) return fail(e, JF_ERR_ARG, "jf_debug_stage_taps: PAD_LEN 1024 engines only");
-    float *d_p = nullptr, *d_w = nullptr;
-    float2 *d_d = nullptr, *d_s = nullptr;
-    auto body = [&]() -> int {
-        JF_HIP(e, hipMalloc(&d_p, sizeof(float) * 5 * (size_t)n));
-        JF_HIP(e, hipMalloc(&d_d, sizeof(float2) * (size_t)n * kNc));
-        JF_HIP(e, h2d(e, d_p, positions, sizeof(float) * 5 * (size_t)n));
-        if (spectra) {
-            JF_HIP(e, hipMalloc(&d_w, sizeof(float) * (size_t)n * kN));
-            JF_HIP(e, hipMalloc(&d_s, sizeof(float2) * (size_t)n * 2 * kNc));
-            JF_HIP(e, h2d(e, d_w, windows, sizeof(float) * (size_t)n * kN));
-        }
-        JF_HIP(e, launch_stage_debug(e->rt, kernel_mode(e), d_p, d_w, n, e->d_htab, e->d_twpack, d_d, d_s,
-                                     e->stream));
-        JF_HIP(e, hipStreamSynchronize(e->stream));
-        JF_HIP(e, hipMemcpy(dist, d_d, sizeof(float2) * (size_t)n * kNc, hipMemcpyDeviceToHost));
-        if (spectra) JF_HIP(e, hipMemcpy(spectra, d_s, sizeof(float2) * (size_t)n * 2 * kNc, hipMemcpyDeviceToHost));
-        return JF_OK;
-    };
-    int rc = body();
-    (void)hipFree(d_p);
-    (void)hipFree(d_w);
-    (void)hipFree(d_d);
-    (void)hipFree(d_s);
-    return rc;
+    DevBuf<float> d_p, d_w;
+    DevBuf<float2> d_d, d_s;
+    JF_HIP(e, d_p.alloc(5 * (size_t)n));
+    JF_HIP(e, d_d.alloc((size_t)n * kNc));
+    JF_HIP(e, h2d(e, d_p, positions, sizeof(float) * 5 * (size_t)n));
+    if (spectra) {
+        JF_HIP(e, d_w.alloc((size_t)n * kN));
+        JF_HIP(e, d_s.alloc((size_t)n * 2 * kNc));
+        JF_HIP(e, h2d(e, d_w, windows, sizeof(float) * (size_t)n * kN));
+    }
+    JF_HIP(e, launch_stage_debug(e->rt, kernel_mode(e), d_p, d_w, n, e->d_htab, e->d_twpack, d_d, d_s, e->stream));
+    JF_HIP(e, hipStreamSynchronize(e->stream));
+    JF_HIP(e, hipMemcpy(dist, d_d, sizeof(float2) * (size_t)n * kNc, hipMemcpyDeviceToHost));
+    if (spectra) JF_HIP(e, hipMemcpy(spectra, d_s, sizeof(float2) * (size_t)n * 2 * kNc, hipMemcpyDeviceToHost));
+    return JF_OK;
     });
 }
 
@@ -516,7 +466,7 @@ int jf_debug_read_stamps(jf_engine *e, unsigned long long *out, int n) {
     DeviceGuard bind(e);
     if (!e || !out || n < 0 || n > 8192) return JF_ERR_ARG;
     JF_HIP(e, hipStreamSynchronize(e->stream));
-    memcpy(out, (const char *)e->h_err + 16, sizeof(unsigned long long) * (size_t)n);
+    memcpy(out, (const char *)e->h_err.p + 16, sizeof(unsigned long long) * (size_t)n);
     return JF_OK;
     });
 }

@@ -1,6 +1,9 @@
 // jf_engine_internal.h -- what the translation units of the engine's host side share: the engine's state (struct jf_engine),
-// the kernels' launchers (jf_kernels.hip, jf_reverb.hip), the small helpers every ABI entry uses.  Three units since round 6:
-//   jf_engine.cpp         creation, the batch pipeline (run_blocks), the per-block calls: include/jefferson.h
+// the owners of its device and pinned memory (DevBuf, PinnedBuf: whatever the engine or a call allocates is freed by a
+// destructor, never by hand), the kernels' launchers (jf_kernels.hip, jf_reverb.hip), the small helpers every ABI entry uses
+// (among them fused_params, the one place that fills FusedParams).  Three units since round 6:
+//   jf_engine.cpp         creation in named steps, the ONE batch pipeline (run_blocks: PAD_LEN 1024 and 2048), the per-block
+//                         calls, the one way to swap a source's signal: include/jefferson.h
 //   jf_engine_reverb.cpp  the convolution reverb's schedule (run_reverb_stage, the side stream, the stage launched ahead) and
 //                         jf_reverb_set_ir / jf_reverb_rms_gain
 //   jf_engine_debug.cpp   every entry point of include/jefferson_debug.h (taps, timing hooks, tuning switches, accessors)
@@ -74,6 +77,47 @@ using namespace jf;
 
 inline thread_local std::string g_create_error;
 
+// Owners of the memory the engine and its calls allocate: move-only, freed by the destructor (or reset()), converting to T *
+// so that launch sites read as with a plain pointer.  Nothing else: no pool, no size -- a caller that needs one keeps it.
+template <class T, hipError_t (*Free)(void *)>
+struct OwnedBuf {
+    T *p = nullptr;
+    OwnedBuf() = default;
+    OwnedBuf(OwnedBuf &&o) noexcept : p(o.p) { o.p = nullptr; }
+    OwnedBuf &operator=(OwnedBuf &&o) noexcept {
+        if (this != &o) {
+            reset();
+            p = o.p;
+            o.p = nullptr;
+        }
+        return *this;
+    }
+    ~OwnedBuf() { reset(); }
+    void reset() {
+        if (p) (void)Free(p);
+        p = nullptr;
+    }
+    operator T *() const { return p; }
+};
+inline hipError_t jf_free_device(void *p) { return hipFree(p); }
+inline hipError_t jf_free_pinned(void *p) { return hipHostFree(p); }
+template <class T>
+struct DevBuf : OwnedBuf<T, jf_free_device> {  // device memory
+    hipError_t alloc(size_t count) {
+        this->reset();
+        return hipMalloc(&this->p, sizeof(T) * count);
+    }
+};
+// Host memory the kernels read and write in place, and whose words the host polls while a kernel runs: pinned, mapped AND
+// coherent (fine-grained) explicitly -- not left to the runtime's default or to HIP_HOST_COHERENT
+template <class T>
+struct PinnedBuf : OwnedBuf<T, jf_free_pinned> {
+    hipError_t alloc(size_t count) {
+        this->reset();
+        return hipHostMalloc(&this->p, sizeof(T) * count, hipHostMallocMapped | hipHostMallocCoherent);
+    }
+};
+
 struct HostPos {  // public fields of SoundSource (SoundSource.cuh:24-36)
     float ele, azi, r, x, y, z;
 };
@@ -87,19 +131,51 @@ constexpr long kRtPollNs = 2000000;  // jf_collect_block polls the real-time ker
 constexpr int kRvFusedHeadMax = 64;  // partitions of B a wave takes a block through by itself (rv_head_wave)
 constexpr int kRtMaxWgs = 128;  // workgroups (8 or 16 waves, a source per wave and turn) of the one-launch real-time kernel: 64 and 256 measure slower
 
-struct jf_engine {
+// The convolution reverb as jf_reverb_set_ir set it up: buffers and dimensions, all empty / 0 while the reverb is off
+// (free_reverb: `= {}`).  Off while rv_P == 0.
+struct ReverbSetup {
+    int rv_P = 0, rv_Rg = 0, rv_Wr = 0;
+    DevBuf<float2> d_rv_hspec;
+    DevBuf<float2> d_rv_fdl;
+    DevBuf<float> d_rv_wet;
+    DevBuf<float> d_rv_prev[2];
+    DevBuf<int> d_rv_count[2];
+    // non-uniform partitioning (ReverbBigParams, jf_device.h): rv_P is then the HEAD's partition count (rv_M) and the rest
+    // of the impulse response lies in rv_P1 partitions of rv_B1 = rv_M * B taps.  rv_P1 == 0: uniform partitioning.
+    int rv_P_total = 0;          // partitions of B the impulse response has (what rv_P is under uniform partitioning)
+    int rv_M = 0;                // blocks per big block (rv_big_blocks(B)): rv_B1 = rv_M * B
+    int rv_P1 = 0, rv_B1 = 0, rv_R1 = 0, rv_Rn = 0, rv_Fn = 0, rv_steps_max = 0;
+    DevBuf<float2> d_rv_tw1, d_rv_hspec1, d_rv_fdl1, d_rv_ybig;
+    DevBuf<float> d_rv_dryring, d_rv_fut;
+    DevBuf<SrcSignal> d_sigs_wet;  // [S] the wet rings as the spatialiser's signals
+    DevBuf<float2> d_rv_yacc;      // [S][2][B1] the side stream's product buffer (jf_engine::rv_side)
+};
+
+// What a reverb stage advances, and what rv_ahead_discard takes back when a stage launched ahead is discarded.
+struct RvProgress {
+    int rv_head = 0;             // slot of the delay line the next block's spectrum goes to
+    long long rv_blocks = 0;     // blocks the stage has processed since it was set up: big block m = blocks 16 m .. 16 m + 15
+    long long rv_fut_m = 1;      // TAIL(m) has been formed for every big block up to this one (big blocks 0 and 1 have none: zeros)
+    int last_rv_form = 0;        // form of the multiply-accumulate stage the last call took       } what the last call did
+    ReverbPlan last_plan;        //                                                                 } (jf_debug_last_kernels)
+    std::string last_side;       // the side stream's kernels of the last call
+    bool last_catchup = false;   // the last call began with the catch-up
+    bool last_small_fft = true;  // ... and launched the small transforms' kernel
+};
+
+struct jf_engine : ReverbSetup {
     jf_config cfg{};
     int own_mix_blocks = 0;  // blocks the last jf_batch_run left in d_mix (0: it wrote to the caller's buffer, failed or has not run)
     int B = 0, S = 0, maxK = 0;
     // PAD_LEN of this engine's configuration (2^ceil(log2(B + hrtf_len - 1)), Universal.cuh:9-12) and its Nc = N / 2 + 1.
     // kN (1024): the kernels of jf_kernels.hip; 2048: those of jf_kernels2048.hip -- no real-time kernel, no reverb,
-    // no pre-interpolated rows (run_blocks_2048)
+    // no pre-interpolated rows, no descriptors prepared ahead (run_blocks)
     int N = kN, Nc = kNc;
-    float2 *d_tw2048 = nullptr;  // N = 2048: exp(+2 pi i j / 2048), j < 2048, from double
+    DevBuf<float2> d_tw2048;  // N = 2048: exp(+2 pi i j / 2048), j < 2048, from double
     hipStream_t stream = nullptr;
     std::string err;
 
-    float4 *d_htab = nullptr;  // [n_rows][N / 2] (jf_device.h; jf_kernels2048.hip at N = 2048)
+    DevBuf<float4> d_htab;  // [n_rows][N / 2] (jf_device.h; jf_kernels2048.hip at N = 2048)
     // The kInterpRows pre-interpolated rows (jf_device.h; 386 MB behind the 710 measured rows) are built LAZILY: by the first
     // run whose policy takes them (run_blocks), or when jf_debug_set_interp_table(e, 1) / a read of those rows asks -- never for
     // an engine that only ever runs sources that move every block, and not for the eight shards of a job on one device.
@@ -114,18 +190,18 @@ struct jf_engine {
     int interp_use = 0;
     std::vector<unsigned> traj_moved;  // [traj_blocks + 1] prefix counts of the uploaded trajectory's items that move
     bool last_rows = false;     // the last batch run's descriptors could name pre-interpolated rows
-    float2 *d_tw = nullptr;
-    float2 *d_twpack = nullptr;
-    SrcSignal *d_sigs = nullptr;
-    float *d_zero = nullptr;  // N zeros: the "signal" of a source without one
-    SrcState *d_state[2] = {nullptr, nullptr};
-    float *d_hist[2] = {nullptr, nullptr};
-    ItemDesc *d_desc = nullptr;
+    DevBuf<float2> d_tw;
+    DevBuf<float2> d_twpack;
+    DevBuf<SrcSignal> d_sigs;
+    DevBuf<float> d_zero;  // N zeros: the "signal" of a source without one
+    DevBuf<SrcState> d_state[2];
+    DevBuf<float> d_hist[2];
+    DevBuf<ItemDesc> d_desc;
     // Descriptors of the window that follows the last jf_batch_run, written by that run itself (trailing workgroups of the
     // pair kernel's launch, or mix_prep_kernel) into the second buffer; the next run takes them instead of launching prep_kernel if it asks for exactly that window
     // of the same trajectory in the same mode and layout -- anything else that runs or touches the state in between
     // clears `ahead.valid`.
-    ItemDesc *d_desc_ahead = nullptr;
+    DevBuf<ItemDesc> d_desc_ahead;
     struct {
         bool valid = false;
         int first = 0, K = 0, mode = 0, canon = 0;
@@ -134,27 +210,26 @@ struct jf_engine {
     unsigned long traj_gen = 0;  // bumped by every jf_batch_upload_positions
     bool prep_ahead = true;      // jf_debug_set_prep_ahead
     bool last_prep_skipped = false, last_mix_prep = false, last_fused_prep = false;  // what the last run launched (jf_debug_last_kernels)
-    float *d_partial = nullptr;
-    float *d_mix = nullptr;
-    float *d_pos_rt = nullptr;  // [S][5]
-    float *d_traj = nullptr;    // [total][S][5]
-    short *d_pick = nullptr;    // nearest-azimuth table of the index/weight kernels (RingTable::pick)
+    DevBuf<float> d_partial;
+    DevBuf<float> d_mix;
+    DevBuf<float> d_pos_rt;  // [S][5]
+    DevBuf<float> d_traj;    // [total][S][5]
+    DevBuf<short> d_pick;    // nearest-azimuth table of the index/weight kernels (RingTable::pick)
     RingTable rt{};             // ring_table() + this engine's device table
     // a set on arbitrary directions (jf_engine_create_cloud): the engine's own copies of the cloud's triangle records and
     // seed cells -- on the host (cloud_host: the processing order's nearest rows) and on the device (rt.cloud)
     std::vector<CloudTri> cloud_tri;
     std::vector<int> cloud_seed;
     CloudView cloud_host{};
-    CloudTri *d_cloud_tri = nullptr;
-    int *d_cloud_seed = nullptr;
-    int *d_order = nullptr;     // [S] processing order of the pair kernel (a permutation of the sources)
+    DevBuf<CloudTri> d_cloud_tri;
+    DevBuf<int> d_cloud_seed;
+    DevBuf<int> d_order;        // [S] processing order of the pair kernel (a permutation of the sources)
     std::vector<int> order;     // host copy
     bool sorted_order = false;  // d_order is not the identity
     int traj_blocks = 0;
     int cur = 0;  // parity of the valid state/history
     int src_group = 0;  // 0 = automatic
     int last_group = 0; // G of the last batch pipeline run
-    int last_rv_form = 0;  // form of the reverb multiply-accumulate stage the last call took
     bool last_rt = false;  // the last block went through the one-launch real-time kernel
     std::string kernels;   // jf_debug_last_kernels
     int rv_form = 0;    // 0 = automatic
@@ -166,7 +241,7 @@ struct jf_engine {
     int grid_limit = 0;            // > 0: tests shrink the grid so that waves loop over several units
     float last_peak = 0.0f;        // max |sample| of the last block handed out (Audio.cu:111-113 clip alert)
 
-    std::vector<float *> d_signal;  // per source
+    std::vector<DevBuf<float>> d_signal;  // per source (null: none, the record names d_zero)
     std::vector<SrcSignal> h_sigs;
 
     // LIVE INPUT (jf_source_set_live).  A live source has no resident signal: every processing call brings its
@@ -183,24 +258,27 @@ struct jf_engine {
     std::vector<int> live_idx;       // the live sources, ascending: row j of `in` feeds live_idx[j]
     int n_live = 0;
     int live_len = 0;                // floats of a live source's device buffer
-    int *d_live_idx = nullptr;       // [S]
-    SrcSignal *d_sigs_rt = nullptr;  // [S]
-    float *h_in = nullptr, *hd_in = nullptr;
+    DevBuf<int> d_live_idx;          // [S]
+    DevBuf<SrcSignal> d_sigs_rt;     // [S]
+    PinnedBuf<float> h_in;
+    float *hd_in = nullptr;          // its device address
     size_t in_cap = 0;               // floats h_in holds
     bool last_ingest = false;        // the last call launched live_ingest_kernel (jf_debug_last_kernels)
 
     std::mutex pos_mu;  // setters may come from another thread (graphics.cu:378)
     std::vector<HostPos> pos;
 
-    float *h_pos_pinned = nullptr;  // [S][5]   pinned + mapped: the real-time kernel reads it in place
-    float *h_out_pinned = nullptr;  // [kRtMaxWgs][2B] pinned + mapped: ... and writes its workgroups' stereo blocks in place
+    PinnedBuf<float> h_pos_pinned;  // [S][5]   pinned + mapped: the real-time kernel reads it in place
+    PinnedBuf<float> h_out_pinned;  // [kRtMaxWgs][2B] pinned + mapped: ... and writes its workgroups' stereo blocks in place
     int rt_wgs = 0;                 // partial blocks the block in flight left there (0: one finished block)
     float *hd_pos = nullptr, *hd_out = nullptr;  // their device addresses
     // The real-time kernel's workgroups each store a sequence number into their word of h_done (pinned + mapped) when their
     // block lies in h_out_pinned; jf_collect_block polls the words instead of synchronising the stream.
-    int *h_done = nullptr, *hd_done = nullptr;
+    PinnedBuf<int> h_done;
+    int *hd_done = nullptr;
     int rt_seq = 0;
-    int *h_err = nullptr, *hd_err = nullptr;     // pinned + mapped error word of the fused kernels
+    PinnedBuf<int> h_err;           // pinned + mapped error word of the fused kernels
+    int *hd_err = nullptr;
     int rt_max_sources = 8192;      // per-block calls with at most this many sources take the one-launch path
                                     // (profiles/latency_rt_sweep.py: 32 against 54 us at 1024 sources, 75 against 105 at 8192)
     bool in_flight = false;         // a submitted block not yet collected
@@ -213,25 +291,10 @@ struct jf_engine {
     std::vector<EventPair> ev_prep, ev_fused, ev_mix, ev_reverb;
     size_t ev_used = 0;
 
-    // convolution reverb stage (jf_reverb.hip); off while rv_P == 0
-    int rv_P = 0, rv_Rg = 0, rv_Wr = 0, rv_head = 0;
-    float2 *d_rv_hspec = nullptr;
-    float2 *d_rv_fdl = nullptr;
-    float *d_rv_wet = nullptr;
-    float *d_rv_prev[2] = {nullptr, nullptr};
-    int *d_rv_count[2] = {nullptr, nullptr};
-    // non-uniform partitioning (ReverbBigParams, jf_device.h): rv_P is then the HEAD's partition count (rv_M) and the rest
-    // of the impulse response lies in rv_P1 partitions of rv_B1 = rv_M * B taps.  rv_P1 == 0: uniform partitioning.
+    // convolution reverb stage (jf_reverb.hip): its buffers and dimensions are the base ReverbSetup, what it advances is
+    // `stage`; the knobs below outlive a response
     int rv_partitioning = 0;     // jf_debug_set_reverb_partitioning: 0 by length, 1 uniform, 2 non-uniform (at the next set_ir)
-    int rv_P_total = 0;          // partitions of B the impulse response has (what rv_P is under uniform partitioning)
-    int rv_M = 0;                // blocks per big block (rv_big_blocks(B)): rv_B1 = rv_M * B
-    int rv_P1 = 0, rv_B1 = 0, rv_R1 = 0, rv_Rn = 0, rv_Fn = 0, rv_steps_max = 0;
-    long long rv_blocks = 0;     // blocks the stage has processed since it was set up: big block m = blocks 16 m .. 16 m + 15
-    long long rv_fut_m = 1;      // TAIL(m) has been formed for every big block up to this one (big blocks 0 and 1 have none: zeros)
-    ReverbPlan last_plan;        // what the last call did (jf_debug_last_kernels)
-    float2 *d_rv_tw1 = nullptr, *d_rv_hspec1 = nullptr, *d_rv_fdl1 = nullptr, *d_rv_ybig = nullptr;
-    float *d_rv_dryring = nullptr, *d_rv_fut = nullptr;
-    SrcSignal *d_sigs_wet = nullptr;  // [S] the wet rings as the spatialiser's signals
+    RvProgress stage;
     // One-block calls (the real-time shape) keep the big partitions off the block's critical path (run_reverb_stage): their
     // kernels go to a second stream, d_rv_yacc is that stream's product buffer.
     int rv_async = 1;            // jf_debug_set_reverb_async
@@ -239,8 +302,6 @@ struct jf_engine {
     hipEvent_t rv_ev_main = nullptr, rv_ev_side = nullptr;
     bool rv_side_busy = false;   // work was put on the side stream since the engine's stream last waited for it
     bool rv_side_urgent = false; // ... some of which the very next block reads
-    float2 *d_rv_yacc = nullptr; // [S][2][B1]
-    std::string last_side;       // the side stream's kernels of the last call (jf_debug_last_kernels)
     // what the last stage wants run on the side stream once the block's spatialiser has been launched (submit_side)
     bool side_tr = false;
     ReverbBigParams side_p[2];   // transforms, products
@@ -271,18 +332,10 @@ struct jf_engine {
     // done again).  Same kernels on the same data in the same order: bit-identical.
     int rv_ahead_on = 1;          // jf_debug_set_reverb_ahead
     bool rv_ahead = false;        // the next block's stage has been launched
-    struct {
-        int rv_head = 0, last_rv_form = 0;
-        long long rv_blocks = 0, rv_fut_m = 0;
-        ReverbPlan last_plan;
-        std::string last_side;
-        bool last_catchup = false, last_small_fft = true, rv_side_busy = false, rv_side_urgent = false;
-    } rv_book;                    // the stage's bookkeeping before that launch
+    RvProgress rv_book;           // `stage` before that launch: taking the stage back is one assignment
     std::string kernels_frozen;   // jf_debug_last_kernels of the call that launched it (the stage's fields describe the NEXT block)
     bool kernels_use_frozen = false;
     bool rv_small_stale = false;
-    bool last_catchup = false;   // the last call began with the catch-up (jf_debug_last_kernels)
-    bool last_small_fft = true;  // ... and launched the small transforms' kernel
     int rv_lazy_small = 1;       // jf_debug_set_reverb_lazy_state
     int rv_side_wgs = 192;       // workgroups of its product kernel (it runs beside later blocks' kernels: launched narrow;
                                  // 64 / 128 / 256 / all measure 34.5 / 34.1 / 34.1 / 35.0 us per block: profiles/r04/rt_async.md).
@@ -329,7 +382,7 @@ inline const char *elevation_msg(const jf_engine *e) { return e->rt.kemar ? "ele
 // call that hands out or produces audio afterwards returns JF_ERR_DEVICE (jf_pa_callback: silence); the engine can
 // only be destroyed.  Valid after a synchronisation of the engine's stream.
 constexpr const char *kHandOffMsg = "fused_pair_kernel: a wavefront hand-off timed out (fatal: destroy the engine)";
-inline bool device_fault(const jf_engine *e) { return e->h_err && *(volatile int *)e->h_err != 0; }
+inline bool device_fault(const jf_engine *e) { return e->h_err && *(volatile int *)e->h_err.p != 0; }
 
 // Every ABI entry that reaches HIP binds the engine's device for its duration: the callback runs on
 // PortAudio's thread, the setters on the UI thread, and a host with one engine per GPU switches devices
@@ -355,6 +408,35 @@ inline bool corrected_rule(const jf_engine *e) {  // (a grid that is not the ref
 }
 inline int kernel_mode(const jf_engine *e) {
     return e->mode.load(std::memory_order_relaxed) | (corrected_rule(e) ? 2 : 0);
+}
+
+// The fields of FusedParams that every launch of a spatialiser kernel sets the same way (state parity p, K blocks); each site
+// adds what is its own: desc, pos, partial, G, sigs, tw, rt, prep_*.
+inline FusedParams fused_params(const jf_engine *e, int p, int K, int mode) {
+    FusedParams P{};
+    P.htab = e->d_htab;
+    P.st_in = e->d_state[p];
+    P.st_out = e->d_state[p ^ 1];
+    P.hist_in = e->d_hist[p];
+    P.hist_out = e->d_hist[p ^ 1];
+    P.S = e->S;
+    P.K = K;
+    P.B = e->B;
+    P.G = 1;
+    P.mode = mode;
+    P.order = e->d_order;
+    P.err = e->hd_err;
+    return P;
+}
+
+// exp(+2 pi i j / n), j < n (a full circle), from double
+inline std::vector<float2> twiddles(int n) {
+    std::vector<float2> tw((size_t)n);
+    for (int j = 0; j < n; j++) {
+        const double a = 2.0 * 3.14159265358979323846264338327950288 * j / (double)n;
+        tw[j] = make_float2((float)cos(a), (float)sin(a));
+    }
+    return tw;
 }
 
 inline EventPair *next_events(jf_engine *e, std::vector<EventPair> &pool) {

@@ -38,7 +38,7 @@ int run_reverb_stage(jf_engine *e, int p, int K, ReverbParams *head_out, bool *h
     R.P = e->rv_P;
     R.Rg = e->rv_Rg;
     R.Wr = e->rv_Wr;
-    R.head = e->rv_head;
+    R.head = e->stage.rv_head;
     R.mac_form = e->rv_form;
     ReverbPlan plan;
     plan.big = e->rv_P1 > 0;
@@ -53,18 +53,18 @@ int run_reverb_stage(jf_engine *e, int p, int K, ReverbParams *head_out, bool *h
     // line, that block and the one before it cost 40 and 9 us more than the other fourteen at configs[4], 256 sources.)
     // Calls that pin a form, batch calls and profiled calls do everything in line on the engine's stream.
     const bool async_ok = plan.big && K == 1 && e->rv_async && e->rv_form == 0 && e->profiling < 2 && e->rv_side != nullptr;
-    const bool completes = plan.big && (e->rv_blocks + K) / e->rv_M > e->rv_blocks / e->rv_M;  // transforms in this call
+    const bool completes = plan.big && (e->stage.rv_blocks + K) / e->rv_M > e->stage.rv_blocks / e->rv_M;  // transforms in this call
     if (e->rv_side_busy && (!async_ok || completes || e->rv_side_urgent)) {
         JF_HIP(e, hipStreamWaitEvent(e->stream, e->rv_ev_side, 0));
         e->rv_side_busy = e->rv_side_urgent = false;
     }
     ReverbBigParams &s_tr = e->side_p[0], &s_prod = e->side_p[1];
-    e->last_side.clear();
-    const long long fut_m_before = e->rv_fut_m;
+    e->stage.last_side.clear();
+    const long long fut_m_before = e->stage.rv_fut_m;
     bool side_wanted = false;
     if (plan.big) {
         // Absolute block indices j0 .. j1 - 1; big block m = blocks 16 m .. 16 m + 15.
-        const long long j0 = e->rv_blocks;
+        const long long j0 = e->stage.rv_blocks;
         const int B1 = e->rv_B1, R1 = e->rv_R1, Rn = e->rv_Rn, Fn = e->rv_Fn, M = e->rv_M;
         R.dryring = e->d_rv_dryring;
         R.Rd = Rn * B1;
@@ -95,8 +95,8 @@ int run_reverb_stage(jf_engine *e, int p, int K, ReverbParams *head_out, bool *h
         G.M = M;
         G.NP = e->rv_P1 + 17;
         auto mod = [](long long a, int n) { return (int)(((a % n) + n) % n); };
-        const ReverbSchedule sc = host_reverb_schedule(j0, K, M, e->rv_fut_m);  // which X_m, FULL, TAIL and ranges: jf_host.cpp
-        e->rv_fut_m = sc.fut_m;
+        const ReverbSchedule sc = host_reverb_schedule(j0, K, M, e->stage.rv_fut_m);  // which X_m, FULL, TAIL and ranges: jf_host.cpp
+        e->stage.rv_fut_m = sc.fut_m;
         // whole big blocks up to the call's end: the small transforms of its last blocks are put off (rv_small_stale) ...
         defer_small = e->rv_lazy_small && sc.n_mid > 0 && sc.kn[1] == 0 && sc.n_tr > 0;
         // ... and a call that takes a block through the head needs the ones an earlier call put off, first
@@ -160,7 +160,7 @@ int run_reverb_stage(jf_engine *e, int p, int K, ReverbParams *head_out, bool *h
             s_tr.tr_rel_first -= e->B;
             // (if nobody has formed TAIL(mb + 1) -- the run of one-block calls began inside this big block -- both, and the
             // next call waits for them)
-            const bool both = e->rv_fut_m < mb + 1;
+            const bool both = e->stage.rv_fut_m < mb + 1;
             s_prod = tail_for(both ? mb + 1 : mb + 2);
             s_prod.n_prod = both ? 2 : 1;
             s_prod.ybig = e->d_rv_yacc;
@@ -168,33 +168,33 @@ int run_reverb_stage(jf_engine *e, int p, int K, ReverbParams *head_out, bool *h
             e->side_urgent = both;
             e->side_fut_m = mb + 2;
             side_wanted = true;
-            e->last_side = "reverb_big_fft_kernel<" + b1 + ",1>@side;reverb_big_mac_kernel<" + b1 + ",1>@side;reverb_big_ifft_kernel<" +
+            e->stage.last_side = "reverb_big_fft_kernel<" + b1 + ",1>@side;reverb_big_mac_kernel<" + b1 + ",1>@side;reverb_big_ifft_kernel<" +
                            b1 + ",1>@side;";
         }
         if (plan.transforms.n_tr > e->rv_steps_max || n_mid > e->rv_steps_max)
             return fail(e, JF_ERR_STATE, "reverb: more big-partition steps in a call than buffers");
     }
-    e->last_small_fft = K - (R.skip_hi - R.skip_lo) > 0;
-    e->last_catchup = false;
+    e->stage.last_small_fft = K - (R.skip_hi - R.skip_lo) > 0;
+    e->stage.last_catchup = false;
     if (e->rv_small_stale && need_small) {
         // the last 2 M - 1 blocks before this call, from the dry ring: block rv_blocks - n .. rv_blocks - 1, slots rv_head - n ..
         ReverbParams C = R;
         const int n = 2 * e->rv_M - 1;
         C.K = n;
         C.catchup = 1;
-        C.head = (int)((((long long)e->rv_head - n) % e->rv_Rg + e->rv_Rg) % e->rv_Rg);
-        C.dry_pos0 = (int)((((e->rv_blocks - n) * e->B) % R.Rd + R.Rd) % R.Rd);
+        C.head = (int)((((long long)e->stage.rv_head - n) % e->rv_Rg + e->rv_Rg) % e->rv_Rg);
+        C.dry_pos0 = (int)((((e->stage.rv_blocks - n) * e->B) % R.Rd + R.Rd) % R.Rd);
         C.copy_lo = C.copy_hi = C.skip_lo = C.skip_hi = 0;
         JF_HIP(e, launch_reverb_catchup(C, e->stream));
         e->rv_small_stale = false;
-        e->last_catchup = true;
+        e->stage.last_catchup = true;
     }
     plan.head_fused = head_out != nullptr && K == 1 && e->rv_head_fused && e->n_live == 0 && !e->rt.cloud.tri && e->rv_form == 0 && e->profiling < 2 &&
                       e->rv_P <= kRvFusedHeadMax && rt_waves_per_wg(e->S) == 8 && (e->B == 64 || e->B == 128 || e->B == 256);
     {
-        const hipError_t q = launch_reverb(R, &plan, e->stream, &e->last_rv_form);
+        const hipError_t q = launch_reverb(R, &plan, e->stream, &e->stage.last_rv_form);
         if (q != hipSuccess) {
-            e->rv_fut_m = fut_m_before;  // nothing of this call's schedule has been formed
+            e->stage.rv_fut_m = fut_m_before;  // nothing of this call's schedule has been formed
             JF_HIP(e, q);
         }
     }
@@ -208,12 +208,12 @@ int run_reverb_stage(jf_engine *e, int p, int K, ReverbParams *head_out, bool *h
             e->post_tr_p = plan.transforms;
         }
     }
-    e->last_plan = plan;
+    e->stage.last_plan = plan;
     e->side_tr = side_wanted;
 
     if (er) JF_HIP(e, hipEventRecord(er->b, e->stream));
-    e->rv_head = (e->rv_head + K) % e->rv_Rg;
-    e->rv_blocks += K;
+    e->stage.rv_head = (e->stage.rv_head + K) % e->rv_Rg;
+    e->stage.rv_blocks += K;
     if (defer_small) e->rv_small_stale = true;  // (a stale state from before is obsolete now: older than the head reaches)
     return JF_OK;
 }
@@ -230,7 +230,7 @@ int submit_side(jf_engine *e) {
     // launched: TAIL up to side_fut_m will be there (nothing before this line may claim so -- a stage whose launches failed
     // must leave the schedule asking for them again)
     e->side_tr = false;
-    if (e->rv_fut_m < e->side_fut_m) e->rv_fut_m = e->side_fut_m;
+    if (e->stage.rv_fut_m < e->side_fut_m) e->stage.rv_fut_m = e->side_fut_m;
     e->rv_side_urgent = e->side_urgent;
     e->rv_side_busy = true;
     JF_HIP(e, hipEventRecord(e->rv_ev_side, e->rv_side));
@@ -241,14 +241,7 @@ int submit_side(jf_engine *e) {
 int rv_ahead_discard(jf_engine *e) {
     if (!e->rv_ahead) return JF_OK;
     JF_HIP(e, hipStreamSynchronize(e->stream));  // nothing of it is still being written
-    e->rv_head = e->rv_book.rv_head;
-    e->rv_blocks = e->rv_book.rv_blocks;
-    e->rv_fut_m = e->rv_book.rv_fut_m;
-    e->last_rv_form = e->rv_book.last_rv_form;
-    e->last_plan = e->rv_book.last_plan;
-    e->last_side = e->rv_book.last_side;
-    e->last_catchup = e->rv_book.last_catchup;
-    e->last_small_fft = e->rv_book.last_small_fft;
+    e->stage = e->rv_book;
     e->side_tr = false;  // (what the stage wanted on the side stream had not been submitted yet)
     e->post_tr = false;
     // the stage may have made the engine's stream wait for the side stream (and cleared these): waited it has, so leave them
@@ -266,7 +259,7 @@ bool rv_ahead_possible(const jf_engine *e) {
     if (e->paused.load(std::memory_order_relaxed)) return false;
     if (e->rv_P1 > 0) {
         if (e->rv_side_urgent || e->side_tr) return false;
-        const ReverbSchedule sc = host_reverb_schedule(e->rv_blocks, 1, e->rv_M, e->rv_fut_m);
+        const ReverbSchedule sc = host_reverb_schedule(e->stage.rv_blocks, 1, e->rv_M, e->stage.rv_fut_m);
         if (sc.tail_early >= 0 || sc.tail_late >= 0) return false;
         // a block that completes a big block: only if its transforms and products go to the side stream (they are submitted
         // behind ITS spatialiser, by the call that consumes the stage: side_tr stays pending till then)
@@ -279,35 +272,12 @@ void free_reverb(jf_engine *e) {
     quiesce_side(e);
     e->side_tr = false;
     e->rv_small_stale = false;
-    e->last_side.clear();
-    (void)hipFree(e->d_rv_yacc);
-    e->d_rv_yacc = nullptr;
-    (void)hipFree(e->d_rv_hspec);
-    (void)hipFree(e->d_rv_fdl);
-    (void)hipFree(e->d_rv_wet);
-    (void)hipFree(e->d_sigs_wet);
-    for (int i = 0; i < 2; i++) {
-        (void)hipFree(e->d_rv_prev[i]);
-        (void)hipFree(e->d_rv_count[i]);
-        e->d_rv_prev[i] = nullptr;
-        e->d_rv_count[i] = nullptr;
-    }
-    (void)hipFree(e->d_rv_tw1);
-    (void)hipFree(e->d_rv_hspec1);
-    (void)hipFree(e->d_rv_fdl1);
-    (void)hipFree(e->d_rv_ybig);
-    (void)hipFree(e->d_rv_dryring);
-    (void)hipFree(e->d_rv_fut);
-    e->d_rv_tw1 = e->d_rv_hspec1 = e->d_rv_fdl1 = e->d_rv_ybig = nullptr;
-    e->d_rv_dryring = e->d_rv_fut = nullptr;
-    e->d_rv_hspec = nullptr;
-    e->d_rv_fdl = nullptr;
-    e->d_rv_wet = nullptr;
-    e->d_sigs_wet = nullptr;
-    e->rv_P = e->rv_Rg = e->rv_Wr = e->rv_head = 0;
-    e->rv_P_total = e->rv_P1 = e->rv_B1 = e->rv_M = e->rv_R1 = e->rv_Rn = e->rv_Fn = e->rv_steps_max = 0;
-    e->rv_blocks = e->rv_fut_m = 0;
-    e->last_plan = ReverbPlan();
+    static_cast<ReverbSetup &>(*e) = ReverbSetup{};  // every buffer freed, every dimension 0: the reverb is off
+    // (what the last call did -- form, catch-up, small transforms -- is left as it is: nothing reads it while the reverb is off)
+    e->stage.rv_head = 0;
+    e->stage.rv_blocks = e->stage.rv_fut_m = 0;
+    e->stage.last_plan = ReverbPlan();
+    e->stage.last_side.clear();
 }
 
 extern "C" {
@@ -349,75 +319,66 @@ int jf_reverb_set_ir(jf_engine *e, const float *ir, size_t n_ir, float gain) {
     const int R1 = P1 + 16 + steps_max + 4, Rn = steps_max + 3, Fn = 4;  // (+ 16: the product kernel reads whole groups of 16 slots)
     const int Rg = P + e->maxK;                          // slots a call may still read + the ones it writes
     const int Wr = (e->maxK + kN / B + 1) * B;           // >= PAD_LEN, multiple of B
-    float *d_ir = nullptr;
-    auto body = [&]() -> int {
-        // each followed by the compact copies of its packed bin-0 pairs: h0[P], fdl0[S][Rg]
-        JF_HIP(e, hipMalloc(&e->d_rv_hspec, sizeof(float2) * ((size_t)P * B + P)));
-        JF_HIP(e, hipMalloc(&e->d_rv_fdl, sizeof(float2) * (S * Rg * B + S * Rg)));
-        JF_HIP(e, hipMalloc(&e->d_rv_wet, sizeof(float) * S * Wr));
-        JF_HIP(e, hipMalloc(&e->d_sigs_wet, sizeof(SrcSignal) * S));
-        for (int i = 0; i < 2; i++) {
-            JF_HIP(e, hipMalloc(&e->d_rv_prev[i], sizeof(float) * S * B));
-            JF_HIP(e, hipMalloc(&e->d_rv_count[i], sizeof(int) * S));
-            JF_HIP(e, hipMemsetAsync(e->d_rv_prev[i], 0, sizeof(float) * S * B, e->stream));
-            JF_HIP(e, hipMemsetAsync(e->d_rv_count[i], 0, sizeof(int) * S, e->stream));
-        }
-        std::vector<SrcSignal> wet(S);
-        for (size_t s = 0; s < S; s++) wet[s] = SrcSignal{e->d_rv_wet + s * Wr, Wr, 0};
-        JF_HIP(e, h2d(e, e->d_sigs_wet, wet.data(), sizeof(SrcSignal) * S));
-        JF_HIP(e, hipMalloc(&d_ir, sizeof(float) * n_ir));
-        JF_HIP(e, h2d(e, d_ir, ir, sizeof(float) * n_ir));
-        // 1/B: normalisation of the B-point inverse used for the 2B-point real transform
-        JF_HIP(e, launch_reverb_ir(d_ir, (int)n_ir, P, B, gain / (float)B, e->d_tw, e->d_rv_hspec, e->stream));
-        if (P1 > 0) {
-            // twiddles exp(+2 pi i j / (2 B1)), j < 2 B1 (a full circle), from double
-            std::vector<float2> tw1((size_t)2 * B1);
-            for (int j = 0; j < 2 * B1; j++) {
-                const double a = 3.14159265358979323846264338327950288 * j / (double)B1;
-                tw1[j] = make_float2((float)cos(a), (float)sin(a));
-            }
-            // ... followed by the transforms' own selection of them, laid out the way their lanes read them (jf_reverb.hip:
-            // BigTwiddles::load)
-            const int n_pack = big_twiddle_pack_len(B1);
-            for (int k = 0; k < n_pack; k++) tw1.push_back(tw1[(size_t)big_twiddle_pack_index(B1, k)]);
-            JF_HIP(e, hipMalloc(&e->d_rv_tw1, sizeof(float2) * tw1.size()));
-            JF_HIP(e, h2d(e, e->d_rv_tw1, tw1.data(), sizeof(float2) * tw1.size()));
-            const size_t NP = (size_t)P1 + 17;  // H'_0 .. H'_P1 and 16 partitions of zeros
-            JF_HIP(e, hipMalloc(&e->d_rv_hspec1, sizeof(float2) * (NP * B1 + NP)));
-            JF_HIP(e, hipMemsetAsync(e->d_rv_hspec1, 0, sizeof(float2) * (NP * B1 + NP), e->stream));
-            JF_HIP(e, hipMalloc(&e->d_rv_fdl1, sizeof(float2) * (S * R1 * B1 + S * R1)));
-            JF_HIP(e, hipMalloc(&e->d_rv_ybig, sizeof(float2) * S * steps_max * B1));
-            JF_HIP(e, hipMalloc(&e->d_rv_dryring, sizeof(float) * S * Rn * B1));
-            JF_HIP(e, hipMalloc(&e->d_rv_fut, sizeof(float) * S * Fn * B1));
-            JF_HIP(e, hipMalloc(&e->d_rv_yacc, sizeof(float2) * S * 2 * B1));
-            // 1/B1: normalisation of the B1-point inverse used for the 2 B1-point real transform
-            // H'_0 .. H'_P1: the response from its first tap on in partitions of B1 (ReverbBigParams)
-            JF_HIP(e, launch_reverb_big_ir(d_ir, (int)n_ir, 0, P1 + 1, B1, gain / (float)B1, e->d_rv_tw1, e->d_rv_hspec1, e->stream));
-        }
-        JF_HIP(e, hipStreamSynchronize(e->stream));
-        return JF_OK;
-    };
-    int rc = body();
-    (void)hipFree(d_ir);
-    if (rc != JF_OK) {
-        const std::string msg = e->err;
-        free_reverb(e);
-        return fail(e, rc, msg);
+    // built aside and handed to the engine whole: a failure on the way leaves the reverb off and nothing allocated
+    ReverbSetup rv;
+    DevBuf<float> d_ir;
+    // each followed by the compact copies of its packed bin-0 pairs: h0[P], fdl0[S][Rg]
+    JF_HIP(e, rv.d_rv_hspec.alloc((size_t)P * B + P));
+    JF_HIP(e, rv.d_rv_fdl.alloc(S * Rg * B + S * Rg));
+    JF_HIP(e, rv.d_rv_wet.alloc(S * Wr));
+    JF_HIP(e, rv.d_sigs_wet.alloc(S));
+    for (int i = 0; i < 2; i++) {
+        JF_HIP(e, rv.d_rv_prev[i].alloc(S * B));
+        JF_HIP(e, rv.d_rv_count[i].alloc(S));
+        JF_HIP(e, hipMemsetAsync(rv.d_rv_prev[i], 0, sizeof(float) * S * B, e->stream));
+        JF_HIP(e, hipMemsetAsync(rv.d_rv_count[i], 0, sizeof(int) * S, e->stream));
     }
-    e->rv_P = P;
-    e->rv_Rg = Rg;
-    e->rv_Wr = Wr;
-    e->rv_head = 0;
-    e->rv_P_total = P_total;
-    e->rv_P1 = P1;
-    e->rv_B1 = P1 > 0 ? B1 : 0;
-    e->rv_M = P1 > 0 ? M : 0;
-    e->rv_R1 = R1;
-    e->rv_Rn = Rn;
-    e->rv_Fn = Fn;
-    e->rv_steps_max = steps_max;
-    e->rv_blocks = 0;
-    e->rv_fut_m = 1;  // TAIL(0) and TAIL(1) are sums over spectra of the time before the start: the zeros of the reset
+    std::vector<SrcSignal> wet(S);
+    for (size_t s = 0; s < S; s++) wet[s] = SrcSignal{rv.d_rv_wet + s * Wr, Wr, 0};
+    JF_HIP(e, h2d(e, rv.d_sigs_wet, wet.data(), sizeof(SrcSignal) * S));
+    JF_HIP(e, d_ir.alloc(n_ir));
+    JF_HIP(e, h2d(e, d_ir, ir, sizeof(float) * n_ir));
+    // 1/B: normalisation of the B-point inverse used for the 2B-point real transform
+    JF_HIP(e, launch_reverb_ir(d_ir, (int)n_ir, P, B, gain / (float)B, e->d_tw, rv.d_rv_hspec, e->stream));
+    if (P1 > 0) {
+        // twiddles exp(+2 pi i j / (2 B1)), j < 2 B1 (a full circle), from double ((2 pi j) / (2 B1) is (pi j) / B1 bit for
+        // bit: doubling both operands of a division is exact)
+        std::vector<float2> tw1 = twiddles(2 * B1);
+        // ... followed by the transforms' own selection of them, laid out the way their lanes read them (jf_reverb.hip:
+        // BigTwiddles::load)
+        const int n_pack = big_twiddle_pack_len(B1);
+        for (int k = 0; k < n_pack; k++) tw1.push_back(tw1[(size_t)big_twiddle_pack_index(B1, k)]);
+        JF_HIP(e, rv.d_rv_tw1.alloc(tw1.size()));
+        JF_HIP(e, h2d(e, rv.d_rv_tw1, tw1.data(), sizeof(float2) * tw1.size()));
+        const size_t NP = (size_t)P1 + 17;  // H'_0 .. H'_P1 and 16 partitions of zeros
+        JF_HIP(e, rv.d_rv_hspec1.alloc(NP * B1 + NP));
+        JF_HIP(e, hipMemsetAsync(rv.d_rv_hspec1, 0, sizeof(float2) * (NP * B1 + NP), e->stream));
+        JF_HIP(e, rv.d_rv_fdl1.alloc(S * R1 * B1 + S * R1));
+        JF_HIP(e, rv.d_rv_ybig.alloc(S * steps_max * B1));
+        JF_HIP(e, rv.d_rv_dryring.alloc(S * Rn * B1));
+        JF_HIP(e, rv.d_rv_fut.alloc(S * Fn * B1));
+        JF_HIP(e, rv.d_rv_yacc.alloc(S * 2 * B1));
+        // 1/B1: normalisation of the B1-point inverse used for the 2 B1-point real transform
+        // H'_0 .. H'_P1: the response from its first tap on in partitions of B1 (ReverbBigParams)
+        JF_HIP(e, launch_reverb_big_ir(d_ir, (int)n_ir, 0, P1 + 1, B1, gain / (float)B1, rv.d_rv_tw1, rv.d_rv_hspec1, e->stream));
+    }
+    JF_HIP(e, hipStreamSynchronize(e->stream));
+    d_ir.reset();
+    rv.rv_P = P;
+    rv.rv_Rg = Rg;
+    rv.rv_Wr = Wr;
+    rv.rv_P_total = P_total;
+    rv.rv_P1 = P1;
+    rv.rv_B1 = P1 > 0 ? B1 : 0;
+    rv.rv_M = P1 > 0 ? M : 0;
+    rv.rv_R1 = R1;
+    rv.rv_Rn = Rn;
+    rv.rv_Fn = Fn;
+    rv.rv_steps_max = steps_max;
+    static_cast<ReverbSetup &>(*e) = std::move(rv);
+    e->stage.rv_head = 0;
+    e->stage.rv_blocks = 0;
+    e->stage.rv_fut_m = 1;  // TAIL(0) and TAIL(1) are sums over spectra of the time before the start: the zeros of the reset
     return reset_sources(e, -1);
     });
 }
