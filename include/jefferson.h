@@ -415,6 +415,40 @@ int jf_set_pause(jf_engine *e, int paused);
  * of the last block handed out by jf_collect_block / jf_process_block / jf_callback / jf_pa_callback. */
 float jf_last_block_peak(const jf_engine *e);
 
+/* ---- output buses: several stereo mixes in one engine ------------------- */
+
+/*
+ * The reference sums every source into the one stereo `output` of its one listener (outputParams.channelCount = 2,
+ * Audio.cu:26; the mixing loop Audio.cu:109-110).  A host that renders for several outputs at once -- the listeners of a
+ * conference, stems, a dry/wet split -- gives the engine n_buses stereo mixes instead: a source belongs to exactly ONE bus
+ * (bus 0 until it is told otherwise), and every processing call returns all of them.
+ *
+ * Output shapes: wherever a call hands out [K][2 * frames_per_buffer] it hands out [n_buses][K][2 * frames_per_buffer] --
+ * each bus one contiguous interleaved-stereo stream of the call's K blocks; bus 0 of a one-bus engine is the layout described
+ * at every call.  That is jf_process_block[_in], jf_collect_block and jf_callback[_in] (K = 1), jf_process_batch[_in] (K =
+ * n_blocks, also beyond max_batch_blocks), jf_batch_run's d_out_mix and jf_batch_fetch (K = n_blocks of that call).
+ * jf_pa_callback writes PortAudio's interleaved [frames][2 * n_buses]: a stream opened with 2 * n_buses output channels,
+ * channels 2 b and 2 b + 1 being bus b; its silence on an error covers all of them.  jf_last_block_peak is the peak over all
+ * buses; a paused block is silence on every bus; a bus without sources is exact zeros.
+ *
+ * A bus's mix is bit for bit the mix of a one-bus engine that holds just that bus's sources (in their order, with the same
+ * group size).  An engine that never calls jf_engine_set_buses is unchanged in every respect.  With more than one bus the
+ * per-block calls go through the batch pipeline with one block instead of the one-launch kernel (DESIGN.md 4.11 has the cost).
+ *
+ * jf_engine_set_buses: n_buses in 1 .. JF_MAX_BUSES; (re)allocates the mix buffers.  JF_ERR_STATE while a submitted block has
+ * not been collected, and when a source sits on a bus that would disappear (move it first).
+ * jf_source_set_bus takes effect with the next processing call.  The source's window, play position, crossfade state, reverb
+ * state and live channel stay with it: it ends on one bus and starts on the other at the block boundary, WITHOUT A FADE (its
+ * window is continuous; a host that wants a fade moves the source between two blocks of silence or fades its signal).
+ * JF_ERR_ARG for a source or bus out of range, JF_ERR_STATE while a block is in flight.  On every refusal nothing changes
+ * and the stream continues bit for bit.
+ */
+#define JF_MAX_BUSES 1024
+int jf_engine_set_buses(jf_engine *e, int n_buses);
+int jf_num_buses(const jf_engine *e);
+int jf_source_set_bus(jf_engine *e, int src, int bus);
+int jf_source_bus(const jf_engine *e, int src);
+
 /* ---- convolution reverb -------------------------------- */
 
 /*
@@ -472,7 +506,9 @@ int jf_synchronize(jf_engine *e);
 /*
  * The mix of the last jf_batch_run into host memory: waits for the engine's stream, then copies blocks 0 .. n_blocks - 1 of
  * the engine's own mix buffer (the one jf_batch_run fills when d_out_mix == NULL) to out_mix[n_blocks][2 * frames_per_buffer].
- * JF_ERR_STATE if the last jf_batch_run was given a device pointer of the caller's, failed, or left fewer than n_blocks there.
+ * JF_ERR_STATE if the last jf_batch_run was given a device pointer of the caller's, failed, or left fewer than n_blocks there,
+ * and after anything else that wrote to that buffer since (a per-block call that went through the batch pipeline or was paused).
+ * With output buses: [n_buses][n_blocks][2 * frames_per_buffer], the first n_blocks of every bus.
  * With jf_batch_upload_positions / jf_batch_run / jf_synchronize this completes the device-resident form of callback_func's
  * loop (Audio.cu:104-117 over many callbacks) without a device pointer in the host's hands; hosts that keep the mix on the
  * device (a reduce over several GPUs: jf_group.c) use the accessors of jefferson_debug.h.

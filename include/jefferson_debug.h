@@ -19,7 +19,8 @@ extern "C" {
 /* ---- interop with HIP code of this repository ---------------------------------------------------------------------- */
 
 /* Device pointers owned by the engine (valid until destroy). */
-float *jf_batch_mix_device(jf_engine *e);     /* [max_batch_blocks][2*B] */
+float *jf_batch_mix_device(jf_engine *e);     /* [n_buses][n_blocks of the last run][2*B] (room for max_batch_blocks each;
+                                                 jf_engine_set_buses replaces the buffer) */
 float *jf_batch_partial_device(jf_engine *e); /* [blocks][n_sources / G][2*B]: stereo blocks of the last run, summed over
                                                  groups of G consecutive sources (jf_debug_set_source_group) */
 /* hipStream_t the engine launches on, as void*. */
@@ -59,6 +60,21 @@ int jf_debug_set_source_group(jf_engine *e, int group);
  * pinned group size, and whenever the last run resolved to G = 1 (per-source blocks: block u of
  * jf_batch_partial_device is source u), the identity.  Before the first run: the order a grouped run will take. */
 int jf_debug_source_order(const jf_engine *e, int *order);
+/*
+ * The plan of a batch run with output buses (jf_engine_set_buses), as the engine forms it -- a pure host function: no engine,
+ * no GPU.  In: bus[n_sources] (NULL: all 0), row_key[n_sources] the table row nearest to every source's first position (NULL:
+ * all 0), pinned_group (0 = automatic), n_items = blocks x sources of the run, pad_len 1024 or 2048.  Returns G (> 0) or
+ * JF_ERR_ARG; fills, where not NULL, order[n_sources], list[n_sources / G] -- indices into partial[k][.] in bus order -- and
+ * seg[n_buses + 1], the offsets of the buses in list.  UNITS NEVER SPAN BUSES:
+ *   automatic grouping at PAD_LEN 1024: order = the sources sorted by (bus, row_key, s); G = the largest size the one-bus
+ *     rule allows that divides every bus's source count (an odd count: 1);
+ *   a pinned group, and PAD_LEN 2048: consecutive sources, order = the identity; G = the one-bus choice if every aligned run
+ *     of G consecutive sources sits on one bus -- else 1 for a pinned size, the largest power of two below that does otherwise;
+ *   G = 1: partial[k][s] is source s, list = the sources sorted by (bus, s);
+ *   n_buses = 1: exactly the one-bus G and order.
+ */
+int jf_debug_bus_plan(int n_sources, const int *bus, int n_buses, const int *row_key, int pinned_group, long long n_items,
+                      int pad_len, int *order, int *list, int *seg);
 /* Form of the reverb's multiply-accumulate stage: 0 = by call size (default); 1 = one workgroup per
  * (block, source) -- what real-time calls use; 2 = groups of sources share each IR partition spectrum;
  * 3 = tiles of consecutive blocks share a sliding window of input spectra (large batch calls).  The

@@ -40,6 +40,7 @@ class JfHrtfGrid(C.Structure):
 
 
 JF_MAX_RINGS = 40
+JF_MAX_BUSES = 1024
 
 
 class JfGridLayout(C.Structure):
@@ -104,6 +105,11 @@ _SIGS = {
     "jf_source_set_signal": (C.c_int, [C.c_void_p, C.c_int, _f, C.c_size_t]),
     "jf_source_set_live": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "jf_num_live_sources": (C.c_int, [C.c_void_p]),
+    "jf_engine_set_buses": (C.c_int, [C.c_void_p, C.c_int]),
+    "jf_num_buses": (C.c_int, [C.c_void_p]),
+    "jf_source_set_bus": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "jf_source_bus": (C.c_int, [C.c_void_p, C.c_int]),
+    "jf_debug_bus_plan": (C.c_int, [C.c_int, _i, C.c_int, _i, C.c_int, C.c_longlong, C.c_int, _i, _i, _i]),
     "jf_submit_block_in": (C.c_int, [C.c_void_p, _f]),
     "jf_process_block_in": (C.c_int, [C.c_void_p, _f, _f]),
     "jf_callback_in": (C.c_int, [C.c_void_p, _f, _f]),
@@ -265,6 +271,19 @@ def reverb_schedule(j0, K, M, fut_m):
     names = ("m_lo", "n_tr", "ma", "n_mid", "n_ranges", "kb0", "kn0", "kb1", "kn1", "copy_lo", "copy_hi", "skip_lo", "skip_hi",
              "tail_early", "tail_late", "fut_m")
     return {n: int(v) for n, v in zip(names, out)}
+
+
+def bus_plan(bus, n_buses, row_key=None, pinned=0, n_items=0, pad_len=1024):
+    """jf_debug_bus_plan (host logic only): (G, order[S], list[S / G], seg[n_buses + 1])"""
+    bus = np.ascontiguousarray(bus, np.int32)
+    S = len(bus)
+    key = None if row_key is None else np.ascontiguousarray(row_key, np.int32)
+    order, lst, seg = np.zeros(S, np.int32), np.zeros(S, np.int32), np.zeros(n_buses + 1, np.int32)
+    G = lib().jf_debug_bus_plan(S, _ip(bus), int(n_buses), None if key is None else _ip(key), int(pinned), int(n_items),
+                                int(pad_len), _ip(order), _ip(lst), _ip(seg))
+    if G <= 0:
+        raise JfError(G, "bus_plan")
+    return G, order, lst[:S // G], seg
 
 
 def pick_hrtf(ele, azi):
@@ -569,6 +588,29 @@ class Engine:
     def n_live(self):
         return lib().jf_num_live_sources(self.h)
 
+    def set_buses(self, n):
+        """n stereo mixes (include/jefferson.h: jf_engine_set_buses); with more than one, every array a processing call
+        returns gains a leading bus axis"""
+        self._chk(lib().jf_engine_set_buses(self.h, int(n)))
+
+    def set_bus(self, s, b):
+        self._chk(lib().jf_source_set_bus(self.h, int(s), int(b)))
+
+    @property
+    def n_buses(self):
+        return lib().jf_num_buses(self.h)
+
+    def bus(self, s):
+        b = lib().jf_source_bus(self.h, int(s))
+        if b < 0:
+            raise JfError(b, "bad source index")
+        return b
+
+    def _out(self, *shape):
+        """zeros of a call's output shape, behind a bus axis when the engine has more than one bus"""
+        nb = self.n_buses
+        return np.zeros(shape if nb == 1 else (nb,) + shape, np.float32)
+
     def _inp(self, inp, n):
         """[n_live][n] float32 for the *_in calls"""
         inp = np.ascontiguousarray(inp, np.float32).reshape(-1, n)
@@ -576,7 +618,7 @@ class Engine:
         return inp
 
     def process_block(self, inp=None):
-        out = np.zeros(2 * self.B, np.float32)
+        out = self._out(2 * self.B)
         if inp is None:
             self._chk(lib().jf_process_block(self.h, _fp(out)))
         else:
@@ -591,12 +633,12 @@ class Engine:
         return lib().jf_submit_block_in(self.h, _fp(inp))
 
     def collect_block(self):
-        out = np.zeros(2 * self.B, np.float32)
+        out = self._out(2 * self.B)
         rc = lib().jf_collect_block(self.h, _fp(out))
         return rc, out
 
     def callback(self, inp=None):
-        out = np.zeros(2 * self.B, np.float32)
+        out = self._out(2 * self.B)
         if inp is None:
             self._chk(lib().jf_callback(self.h, _fp(out)))
         else:
@@ -605,8 +647,10 @@ class Engine:
         return out
 
     def pa_callback(self, inp=None):
-        """jf_pa_callback as PortAudio calls it; inp: interleaved [B][n_live] or None (a stream without input)"""
-        out = np.zeros(2 * self.B, np.float32)
+        """jf_pa_callback as PortAudio calls it; inp: interleaved [B][n_live] or None (a stream without input).
+        With more than one bus: [B][2 n_buses], the stream's interleaved output channels."""
+        nb = self.n_buses
+        out = np.zeros(2 * self.B, np.float32) if nb == 1 else np.zeros((self.B, 2 * nb), np.float32)
         if inp is not None:
             inp = np.ascontiguousarray(inp, np.float32)
             assert inp.size == self.B * self.n_live()
@@ -624,7 +668,7 @@ class Engine:
         pos = np.ascontiguousarray(pos, np.float32)
         K, S = pos.shape[0], pos.shape[1]
         assert S == self.S and pos.shape[2] == 5
-        mix = np.zeros((K, 2 * self.B), np.float32)
+        mix = self._out(K, 2 * self.B)
         if inp is None:
             self._chk(lib().jf_process_batch(self.h, K, _fp(pos), _fp(mix)))
         else:
@@ -651,7 +695,7 @@ class Engine:
 
     def batch_fetch(self, n_blocks):
         """the engine's own mix of the last batch_run (d_out_mix = NULL), [n_blocks][2B], on the host"""
-        out = np.empty((n_blocks, 2 * self.B), np.float32)
+        out = self._out(int(n_blocks), 2 * self.B)
         self._chk(lib().jf_batch_fetch(self.h, int(n_blocks), _fp(out)))
         return out
 

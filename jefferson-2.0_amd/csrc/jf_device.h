@@ -22,7 +22,8 @@
 //   desc   ItemDesc[K][S]     per (block, source) rows/weights/distance terms.
 //   partial float[K][S/G][2B] stereo blocks of groups of G consecutive sources (G = 1: the
 //                             reference's per-source `intermediate`).
-//   mix    float[K][2B]       sum over sources in source order.
+//   mix    float[K][2B]       sum over sources in source order; with output buses float[n_buses][K][2B], a bus's
+//                             sources each (bus_list int[S/G], bus_seg int[n_buses + 1]: which partial blocks a bus sums).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -32,6 +33,7 @@
 namespace jf {
 
 constexpr int kN = 1024;       // PAD_LEN (Universal.cuh:12)
+constexpr int kBusListPad = 64;  // entries behind the bus plan's list that bus_mix_kernel may read and never uses
 constexpr int kNc = 513;       // PAD_LEN / 2 + 1
 constexpr int kNumHrtf = 710;  // NUM_HRTF (Universal.cuh:4): rows of the reference's KEMAR table
 constexpr int kNumElev = 14;   // NUM_ELEV (hrtf_signals.cuh:25): its elevation rings

@@ -27,25 +27,37 @@ int ensure_interp_rows(jf_engine *e) {
     return JF_OK;
 }
 
-// Sources a unit sums as spectra before its inverse transforms (G divides S; jf_debug_set_source_group pins it and refuses
-// a size that does not divide S).  Larger groups mean fewer inverse transforms and fewer partial blocks for the mix.
-static int source_group(const jf_engine *e, long long n_items) {
-    const int S = e->S;
-    if (e->src_group > 0) return S % e->src_group == 0 ? e->src_group : 1;
-    if (e->N != kN) {
-        // PAD_LEN 2048, a unit is one workgroup of four waves: as many as leave about four units for every compute unit
-        for (const int g : {16, 8, 4, 2})
-            if (S % g == 0 && n_items / g >= 1024) return g;
-        return 1;
+// The processing order of the pair kernel from the row keys of the last upload, the sources' buses and the pinned group size
+// (host_bus_plan): uploaded where it differs from the one in place.  The engine's stream is idle.
+int form_order(jf_engine *e) {
+    std::vector<int> ord((size_t)e->S);
+    host_bus_plan(e->S, e->bus.empty() ? nullptr : e->bus.data(), e->n_buses, e->row_key.data(), e->src_group, 0, e->N, ord.data(),
+                  nullptr, nullptr);
+    e->plan_G = 0;
+    if (ord != e->order) {
+        e->order = ord;
+        JF_HIP(e, h2d(e, e->d_order, e->order.data(), sizeof(int) * e->S));
     }
-    // PAD_LEN 1024, a unit is a pair of wavefronts: as many as leave about two units for every resident pair (2048 on
-    // MI355X; profiles/group_sweep.py times every size against this choice)
-    return (S % 32 == 0 && n_items >= 131072) ? 32
-           : (S % 16 == 0 && n_items >= 32768) ? 16
-           : (S % 8 == 0 && n_items >= 16384) ? 8
-           : (S % 4 == 0 && n_items >= 8192) ? 4
-           : (S % 2 == 0 && (n_items >= 4096 || S >= 1024)) ? 2
-                                                           : 1;
+    return JF_OK;
+}
+
+// G of a run of n_items items; with output buses also the bus plan's list and seg on the device, formed again when a bus, the
+// order or G has changed since they were uploaded.
+static int plan_run(jf_engine *e, long long n_items, int *G) {
+    if (e->n_buses == 1) {
+        *G = host_source_group(e->S, e->src_group, n_items, e->N);
+        return JF_OK;
+    }
+    *G = host_bus_plan(e->S, e->bus.data(), e->n_buses, e->row_key.data(), e->src_group, n_items, e->N, nullptr, nullptr, nullptr);
+    if (*G == e->plan_G) return JF_OK;
+    std::vector<int> list((size_t)(e->S / *G) + kBusListPad, 0), seg((size_t)e->n_buses + 1);  // (the padding: index 0)
+    host_bus_plan(e->S, e->bus.data(), e->n_buses, e->row_key.data(), e->src_group, n_items, e->N, nullptr, list.data(), seg.data());
+    JF_HIP(e, h2d(e, e->d_bus_list, list.data(), sizeof(int) * list.size()));
+    JF_HIP(e, h2d(e, e->d_bus_seg, seg.data(), sizeof(int) * seg.size()));
+    e->plan_max_nb = 0;
+    for (int b = 0; b < e->n_buses; b++) e->plan_max_nb = std::max(e->plan_max_nb, seg[b + 1] - seg[b]);
+    e->plan_G = *G;
+    return JF_OK;
 }
 
 // prep -> [reverb] -> fused -> mix on the engine stream, K blocks starting at d_pos.
@@ -76,7 +88,11 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
         if (!ep || !em) return fail(e, JF_ERR_DEVICE, "hipEventCreate failed");
     }
     const long long n_items = (long long)K * e->S;
-    const int G = source_group(e, n_items);
+    int G = 1;
+    {
+        const int rc = plan_run(e, n_items, &G);
+        if (rc) return rc;
+    }
     const int canon = n1024 && G > 1;  // descriptors in the pair-kernel layout
     // whole-degree positions as pre-interpolated rows: the pair kernel's descriptors only
     bool rows = canon && e->interp_avail && e->interp_use != 0;
@@ -119,7 +135,9 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
     e->last_group = G;
     // the window that follows in the trajectory, if there is a whole one: its descriptors are prepared by this run --
     // inside the pair kernel's own launch (trailing workgroups, in the kernel's tail), else inside the mix launch
-    const bool ahead_ok = n1024 && e->prep_ahead && e->profiling < 2 && first_block >= 0 && first_block + 2 * K <= e->traj_blocks;
+    // (with output buses only there: mix_prep_kernel mixes one bus)
+    const bool ahead_ok = n1024 && e->prep_ahead && e->profiling < 2 && first_block >= 0 && first_block + 2 * K <= e->traj_blocks &&
+                          (e->n_buses == 1 || G > 1);
     const bool ahead_in_fused = ahead_ok && G > 1;
     P.prep_pos = ahead_in_fused ? d_pos + (size_t)K * e->S * 5 : nullptr;
     P.prep_desc = e->d_desc_ahead;
@@ -138,7 +156,11 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
     if (em) JF_HIP(e, hipEventRecord(em->a, e->stream));
     e->last_mix_prep = ahead_ok && !ahead_in_fused;
     e->last_fused_prep = ahead_in_fused;
-    if (e->last_mix_prep)
+    e->last_bus_mix = -1;
+    if (e->n_buses > 1)
+        JF_HIP(e, launch_bus_mix(e->d_partial, d_mix_out, e->d_bus_list, e->d_bus_seg, e->S / G, K, e->B, e->n_buses, e->plan_max_nb,
+                                 e->stream, &e->last_bus_mix));
+    else if (e->last_mix_prep)
         JF_HIP(e, launch_mix_prep(e->d_partial, d_mix_out, e->S / G, K, e->B, e->rt, mode_now, d_pos + (size_t)K * e->S * 5,
                                   e->d_desc_ahead, e->S, K, canon, e->stream));
     else
@@ -440,6 +462,7 @@ int init_engine(jf_engine *e, const RingTable *grid, const float *hrir, int taps
     JF_HIP(e, e->d_order.alloc(S));
     e->order.resize(S);
     for (size_t s = 0; s < S; s++) e->order[s] = (int)s;
+    e->row_key.assign(S, 0);
     JF_HIP(e, h2d(e, e->d_order, e->order.data(), sizeof(int) * S));
     JF_HIP(e, e->h_pos_pinned.alloc(S * 5));
     JF_HIP(e, e->h_out_pinned.alloc(2 * B * kRtMaxWgs));
@@ -811,6 +834,70 @@ int jf_source_set_live(jf_engine *e, int src, int live) {
 
 int jf_num_live_sources(const jf_engine *e) { return e ? e->n_live : JF_ERR_ARG; }
 
+// ---- output buses ----------------------------------------------------------
+int jf_engine_set_buses(jf_engine *e, int n_buses) {
+    return jf_guard([&]() -> int {
+    DeviceGuard bind(e);
+    if (!e) return JF_ERR_ARG;
+    if (n_buses < 1 || n_buses > JF_MAX_BUSES) return fail(e, JF_ERR_ARG, "n_buses must be 1 .. JF_MAX_BUSES");
+    if (e->in_flight) return fail(e, JF_ERR_STATE, "a block is in flight");
+    if (n_buses == e->n_buses) return JF_OK;
+    for (const int b : e->bus)
+        if (b >= n_buses) return fail(e, JF_ERR_STATE, "a source sits on a bus that would disappear");
+    {
+        const int rc = rv_ahead_discard(e);
+        if (rc) return rc;
+    }
+    JF_HIP(e, hipStreamSynchronize(e->stream));
+    // the new buffers first: a failed allocation leaves the engine as it was
+    const size_t blk = (size_t)2 * e->B, nb = (size_t)n_buses;
+    DevBuf<float> d_mix;
+    PinnedBuf<float> h_out;
+    DevBuf<int> d_list, d_seg;
+    float *hd_out = nullptr;
+    JF_HIP(e, d_mix.alloc(nb * (size_t)e->maxK * blk));
+    JF_HIP(e, h_out.alloc(blk * std::max<size_t>(kRtMaxWgs, nb)));
+    JF_HIP(e, hipHostGetDevicePointer((void **)&hd_out, h_out, 0));
+    if (n_buses > 1) {
+        JF_HIP(e, d_list.alloc((size_t)e->S + kBusListPad));
+        JF_HIP(e, d_seg.alloc(nb + 1));
+    }
+    std::vector<float> pa(n_buses > 1 ? nb * blk : 0);
+    if (n_buses > 1 && e->bus.empty()) e->bus.assign((size_t)e->S, 0);
+    e->d_mix = std::move(d_mix);
+    e->h_out_pinned = std::move(h_out);
+    e->hd_out = hd_out;
+    e->d_bus_list = std::move(d_list);
+    e->d_bus_seg = std::move(d_seg);
+    e->pa_block.swap(pa);
+    e->n_buses = n_buses;
+    e->own_mix_blocks = 0;
+    e->ahead.valid = false;
+    return form_order(e);
+    });
+}
+
+int jf_num_buses(const jf_engine *e) { return e ? e->n_buses : JF_ERR_ARG; }
+
+int jf_source_set_bus(jf_engine *e, int src, int bus) {
+    return jf_guard([&]() -> int {
+    DeviceGuard bind(e);
+    if (!e) return JF_ERR_ARG;
+    if (!valid_src(e, src) || bus < 0 || bus >= e->n_buses) return fail(e, JF_ERR_ARG, "bad source or bus index");
+    if (e->in_flight) return fail(e, JF_ERR_STATE, "a block is in flight");
+    if ((e->bus.empty() ? 0 : e->bus[src]) == bus) return JF_OK;
+    JF_HIP(e, hipStreamSynchronize(e->stream));
+    e->bus[src] = bus;
+    e->ahead.valid = false;  // descriptors prepared ahead were laid out for the old order
+    return form_order(e);
+    });
+}
+
+int jf_source_bus(const jf_engine *e, int src) {
+    if (!valid_src(e, src)) return JF_ERR_ARG;
+    return e->bus.empty() ? 0 : e->bus[src];
+}
+
 int jf_source_set_cartesian(jf_engine *e, int src, float x, float y, float z) {
     return jf_guard([&]() -> int {
     if (!valid_src(e, src)) return fail(e, JF_ERR_ARG, "bad source index");
@@ -917,10 +1004,11 @@ static int submit_block(jf_engine *e, const float *in, bool interleaved) {
     if (device_fault(e)) return fail(e, JF_ERR_DEVICE, kHandOffMsg);
     e->last_ingest = false;
     if (e->paused.load(std::memory_order_relaxed)) {  // Audio.cu:101: nothing is consumed (live input is dropped), output is silence
-        JF_HIP(e, hipMemsetAsync(e->d_mix, 0, sizeof(float) * 2 * e->B, e->stream));
+        JF_HIP(e, hipMemsetAsync(e->d_mix, 0, sizeof(float) * 2 * e->B * e->n_buses, e->stream));
+        e->own_mix_blocks = 0;  // (d_mix no longer holds the last jf_batch_run's blocks)
     } else {
         snapshot_positions(e, e->h_pos_pinned);
-        if (e->S <= e->rt_max_sources && !e->profiling && e->N == kN) {  // (PAD_LEN 2048: the batch path with K = 1)
+        if (e->S <= e->rt_max_sources && !e->profiling && e->N == kN && e->n_buses == 1) {  // (PAD_LEN 2048, buses: the batch path with K = 1)
             // few sources: ONE launch does descriptors, spatialisation and mix, reading the positions
             // from and writing the stereo block to pinned host memory -- no copies, one sync
             const int p = e->cur;
@@ -986,10 +1074,11 @@ static int submit_block(jf_engine *e, const float *in, bool interleaved) {
         }
         JF_HIP(e, hipMemcpyAsync(e->d_pos_rt, e->h_pos_pinned, sizeof(float) * 5 * e->S, hipMemcpyHostToDevice,
                                  e->stream));
+        e->own_mix_blocks = 0;  // (d_mix no longer holds the last jf_batch_run's blocks)
         int rc = run_blocks(e, e->d_pos_rt, 1, e->d_mix);
         if (rc) return rc;
     }
-    JF_HIP(e, hipMemcpyAsync(e->h_out_pinned, e->d_mix, sizeof(float) * 2 * e->B, hipMemcpyDeviceToHost, e->stream));
+    JF_HIP(e, hipMemcpyAsync(e->h_out_pinned, e->d_mix, sizeof(float) * 2 * e->B * e->n_buses, hipMemcpyDeviceToHost, e->stream));
     e->rt_wgs = 0;
     e->in_flight = true;
     return JF_OK;
@@ -1033,14 +1122,15 @@ int jf_collect_block(jf_engine *e, float *out) {
         e->in_flight = false;
         return fail(e, JF_ERR_DEVICE, kHandOffMsg);
     }
-    memcpy(out, e->h_out_pinned, sizeof(float) * 2 * e->B);
+    const int n_out = 2 * e->B * e->n_buses;  // [n_buses][2B] (the real-time kernel: one bus)
+    memcpy(out, e->h_out_pinned, sizeof(float) * n_out);
     // the real-time kernel's workgroups each left the sum of their sources: add them in workgroup order
     for (int g = 1; g < e->rt_wgs; g++) {
         const float *pg = e->h_out_pinned + (size_t)g * 2 * e->B;
         for (int n = 0; n < 2 * e->B; n++) out[n] += pg[n];
     }
     float peak = 0.0f;
-    for (int n = 0; n < 2 * e->B; n++) peak = fmaxf(peak, fabsf(out[n]));
+    for (int n = 0; n < n_out; n++) peak = fmaxf(peak, fabsf(out[n]));
     e->last_peak = peak;
     e->in_flight = false;
     return JF_OK;
@@ -1072,7 +1162,7 @@ static int callback_block(jf_engine *e, const float *in, bool interleaved, float
         rc = jf_collect_block(e, out);
         if (rc) return rc;
     } else {
-        memset(out, 0, sizeof(float) * 2 * e->B);  // intermediate[] before the first block
+        memset(out, 0, sizeof(float) * 2 * e->B * e->n_buses);  // intermediate[] before the first block
     }
     rc = submit_block(e, in, interleaved);
     if (rc) return rc;
@@ -1092,6 +1182,23 @@ int jf_pa_callback(const void *input, void *output, unsigned long frames, const 
     // a stream opened with another buffer size, or an engine error: hand PortAudio silence, never garbage
     // (input: PortAudio's interleaved [frames][channels], a channel per live source; null -- a stream without input -- feeds
     // the live sources zeros)
+    if (e && e->n_buses > 1) {
+        // a stream opened with 2 n_buses output channels: channels 2 b and 2 b + 1 are bus b
+        const size_t nb = (size_t)e->n_buses;
+        float *o = (float *)output;
+        if (frames != (unsigned long)e->B || callback_block(e, (const float *)input, true, e->pa_block.data()) != JF_OK) {
+            memset(output, 0, sizeof(float) * 2 * nb * frames);
+            return 0;
+        }
+        for (size_t b = 0; b < nb; b++) {
+            const float *blk = e->pa_block.data() + b * 2 * frames;
+            for (size_t n = 0; n < frames; n++) {
+                o[n * 2 * nb + 2 * b] = blk[2 * n];
+                o[n * 2 * nb + 2 * b + 1] = blk[2 * n + 1];
+            }
+        }
+        return 0;
+    }
     if (!e || frames != (unsigned long)e->B || callback_block(e, (const float *)input, true, (float *)output) != JF_OK)
         memset(output, 0, sizeof(float) * 2 * frames);
     return 0;
@@ -1144,21 +1251,21 @@ static int upload_positions(jf_engine *e, int total_blocks, const float *positio
     // automatic grouping the sources are ordered by the table row nearest to their first position, so that the units a
     // compute unit works on at a time read neighbouring rows of the 5.8 MB table (the L2 of an XCD holds 4 MB); the mix is
     // the same sum in another association.  jf_debug_set_source_group pins consecutive sources (identity order).
+    // With output buses the key is (bus, nearest row, s) and units never span buses (host_bus_plan); the keys stay in the
+    // engine, for the order to be formed again when a source changes its bus.
     const bool want_sorted = e->src_group == 0 && e->S > 1;
-    if (want_sorted || e->sorted_order) {
-        std::vector<std::pair<int, int>> key((size_t)e->S);
-        for (int s = 0; s < e->S; s++) {
-            const float *p = positions + 5 * (size_t)s;
-            const bool ok = p[0] > -1.0e6f && p[0] < 1.0e6f && p[1] > -1.0e6f && p[1] < 1.0e6f;
-            int near = 0;
-            if (want_sorted && ok) near = e->rt.cloud.tri ? std::max(0, cloud_pick(e->cloud_host, p[0], p[1])) : host_grid_pick(e->rt, p[0], p[1]);
-            key[s] = {near, s};
-        }
-        std::stable_sort(key.begin(), key.end());
-        for (int s = 0; s < e->S; s++) e->order[s] = key[s].second;
-        JF_HIP(e, h2d(e, e->d_order, e->order.data(), sizeof(int) * e->S));
-        e->sorted_order = want_sorted;
+    for (int s = 0; s < e->S; s++) {
+        const float *p = positions + 5 * (size_t)s;
+        const bool ok = p[0] > -1.0e6f && p[0] < 1.0e6f && p[1] > -1.0e6f && p[1] < 1.0e6f;
+        int near = 0;
+        if (want_sorted && ok) near = e->rt.cloud.tri ? std::max(0, cloud_pick(e->cloud_host, p[0], p[1])) : host_grid_pick(e->rt, p[0], p[1]);
+        e->row_key[s] = near;
     }
+    {
+        const int rc = form_order(e);
+        if (rc) return rc;
+    }
+    e->sorted_order = want_sorted && e->N == kN;
     return JF_OK;
     });
 }
@@ -1284,8 +1391,12 @@ static int process_batch(jf_engine *e, int n_blocks, const float *in, const floa
         }
         rc = batch_run(e, b0, k, nullptr);
         if (rc) return rc;
-        JF_HIP(e, hipMemcpyAsync(out_mix + (size_t)b0 * blk, e->d_mix, sizeof(float) * blk * k, hipMemcpyDeviceToHost,
-                                 e->stream));
+        if (e->n_buses == 1)
+            JF_HIP(e, hipMemcpyAsync(out_mix + (size_t)b0 * blk, e->d_mix, sizeof(float) * blk * k, hipMemcpyDeviceToHost,
+                                     e->stream));
+        else  // this window's [n_buses][k][2B] into the call's [n_buses][n_blocks][2B]: a row per bus
+            JF_HIP(e, hipMemcpy2DAsync(out_mix + (size_t)b0 * blk, sizeof(float) * blk * n_blocks, e->d_mix, sizeof(float) * blk * k,
+                                       sizeof(float) * blk * k, (size_t)e->n_buses, hipMemcpyDeviceToHost, e->stream));
         JF_HIP(e, hipStreamSynchronize(e->stream));
         if (device_fault(e)) return fail(e, JF_ERR_DEVICE, kHandOffMsg);
     }
@@ -1321,7 +1432,12 @@ int jf_batch_fetch(jf_engine *e, int n_blocks, float *out_mix) {
     if (n_blocks > e->own_mix_blocks)
         return fail(e, JF_ERR_STATE, "jf_batch_fetch: the last jf_batch_run did not leave that many blocks in the engine's own buffer "
                                      "(it was given a device pointer, failed, or has not run)");
-    JF_HIP(e, hipMemcpyAsync(out_mix, e->d_mix, sizeof(float) * 2 * e->B * (size_t)n_blocks, hipMemcpyDeviceToHost, e->stream));
+    if (e->n_buses == 1 || n_blocks == e->own_mix_blocks)
+        JF_HIP(e, hipMemcpyAsync(out_mix, e->d_mix, sizeof(float) * 2 * e->B * (size_t)n_blocks * e->n_buses, hipMemcpyDeviceToHost,
+                                 e->stream));
+    else  // the first n_blocks of every bus's stream of the run
+        JF_HIP(e, hipMemcpy2DAsync(out_mix, sizeof(float) * 2 * e->B * n_blocks, e->d_mix, sizeof(float) * 2 * e->B * e->own_mix_blocks,
+                                   sizeof(float) * 2 * e->B * n_blocks, (size_t)e->n_buses, hipMemcpyDeviceToHost, e->stream));
     JF_HIP(e, hipStreamSynchronize(e->stream));
     if (device_fault(e)) return fail(e, JF_ERR_DEVICE, kHandOffMsg);
     return JF_OK;

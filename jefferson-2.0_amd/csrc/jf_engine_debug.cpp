@@ -60,6 +60,19 @@ int jf_debug_set_reverb_side_workgroups(jf_engine *e, int workgroups) {
 
 float *jf_batch_mix_device(jf_engine *e) { return e ? e->d_mix : nullptr; }
 
+int jf_debug_bus_plan(int n_sources, const int *bus, int n_buses, const int *row_key, int pinned_group, long long n_items,
+                      int pad_len, int *order, int *list, int *seg) {
+    return jf_guard([&]() -> int {
+    if (n_sources <= 0 || n_buses < 1 || n_buses > JF_MAX_BUSES || pinned_group < 0 || n_items < 0 ||
+        (pad_len != kN && pad_len != 2 * kN))
+        return JF_ERR_ARG;
+    if (bus)
+        for (int s = 0; s < n_sources; s++)
+            if (bus[s] < 0 || bus[s] >= n_buses) return JF_ERR_ARG;
+    return host_bus_plan(n_sources, bus, n_buses, row_key, pinned_group, n_items, pad_len, order, list, seg);
+    });
+}
+
 float *jf_batch_partial_device(jf_engine *e) { return e ? e->d_partial : nullptr; }
 
 void *jf_engine_stream(jf_engine *e) { return e ? (void *)e->stream : nullptr; }
@@ -132,11 +145,13 @@ int jf_debug_set_source_group(jf_engine *e, int group) {
     DeviceGuard bind(e);
     if (!e || group < 0 || (group > 0 && e->S % group)) return JF_ERR_ARG;
     e->src_group = group;
-    if (group > 0 && e->sorted_order) {  // a pinned group size means consecutive sources
+    e->plan_G = 0;
+    if ((group > 0 && e->sorted_order) || e->n_buses > 1) {  // a pinned group size means consecutive sources
         JF_HIP(e, hipStreamSynchronize(e->stream));
-        for (int s = 0; s < e->S; s++) e->order[s] = s;
-        JF_HIP(e, h2d(e, e->d_order, e->order.data(), sizeof(int) * e->S));
-        e->sorted_order = false;
+        const int rc = form_order(e);  // (with output buses: sorted by bus again when the size is automatic)
+        if (rc) return rc;
+        e->sorted_order = group == 0 && e->S > 1 && e->N == kN;
+        e->ahead.valid = false;
     }
     return JF_OK;
     });
@@ -400,7 +415,8 @@ const char *jf_debug_last_kernels(jf_engine *e) {
         if (e->rv_P > 0) k += e->stage.last_side;
         // launch_mix: few partial blocks per audio block (16, 32 or 64 groups) take the one-thread-per-float form
         const int n_part = e->last_group > 0 ? e->S / e->last_group : e->S;
-        const std::string mix_name = (n_part == 16 || n_part == 32 || n_part == 64)
+        const std::string mix_name = e->last_bus_mix >= 0 ? ";bus_mix_kernel<" + std::to_string(e->last_bus_mix) + ">"
+                                     : (n_part == 16 || n_part == 32 || n_part == 64)
                                          ? ";mix_few_kernel<" + std::to_string(n_part / 16) + ">" : std::string(";mix_kernel");
         if (e->last_rt) {
             const bool fused = e->rv_P > 0 && e->stage.last_rv_form == 5;

@@ -48,6 +48,8 @@ hipError_t launch_stage_debug(const RingTable &rt, int mode, const float *d_pos,
 hipError_t launch_mix(const float *d_partial, float *d_mix, int S, int K, int B, hipStream_t st);
 hipError_t launch_mix_prep(const float *d_partial, float *d_mix, int S_groups, int K, int B, const RingTable &rt, int mode,
                            const float *d_pos_next, ItemDesc *d_desc_next, int S, int K_next, int canon, hipStream_t st);
+hipError_t launch_bus_mix(const float *d_partial, float *d_mix, const int *d_list, const int *d_seg, int n_part, int K, int B,
+                          int n_buses, int max_nb, hipStream_t st, int *form);
 int rt_waves_per_wg(int n_sources);
 hipError_t launch_rt_block(const FusedParams &P, const RingTable &rt, const float *pos, float *out, int *done, int seq,
                            int n_wgs, const ReverbParams *head, hipStream_t st);
@@ -226,6 +228,19 @@ struct jf_engine : ReverbSetup {
     DevBuf<int> d_order;        // [S] processing order of the pair kernel (a permutation of the sources)
     std::vector<int> order;     // host copy
     bool sorted_order = false;  // d_order is not the identity
+    std::vector<int> row_key;   // [S] nearest table row of every source's first position in the last jf_batch_upload_positions
+                                // with automatic grouping (zeros before one): what the order is re-formed from when a bus changes
+    // OUTPUT BUSES (jf_engine_set_buses).  One bus: nothing below is allocated and every path is the one-mix
+    // one.  More: d_mix is [n_buses][K of the call][2B], the mix step of run_blocks is bus_mix_kernel over the plan
+    // (host_bus_plan: units never span buses), and per-block calls go through the batch pipeline with K = 1.
+    int n_buses = 1;
+    std::vector<int> bus;       // [S] (empty: every source on bus 0)
+    DevBuf<int> d_bus_list;     // [S + kBusListPad] the plan's list: indices into partial[k][.] in bus order (+ padding)
+    DevBuf<int> d_bus_seg;      // [n_buses + 1] offsets into it
+    int plan_G = 0;             // group size the uploaded list and seg were formed for (0: none)
+    int plan_max_nb = 0;        // the most partial blocks a bus sums under that plan
+    int last_bus_mix = -1;      // PER of the last run's bus_mix_kernel (-1: the run mixed one bus)
+    std::vector<float> pa_block;  // [n_buses][2B] jf_pa_callback's block before it is interleaved
     int traj_blocks = 0;
     int cur = 0;  // parity of the valid state/history
     int src_group = 0;  // 0 = automatic
@@ -483,5 +498,6 @@ JF_INTERNAL void free_reverb(jf_engine *e);                // jf_engine_reverb.c
 JF_INTERNAL int ensure_interp_rows(jf_engine *e);
 JF_INTERNAL int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int first_block = -1);
 JF_INTERNAL int reset_sources(jf_engine *e, int src);
+JF_INTERNAL int form_order(jf_engine *e);  // the processing order from row_key, bus and src_group (the stream is idle)
 
 #endif  // JF_ENGINE_INTERNAL_H

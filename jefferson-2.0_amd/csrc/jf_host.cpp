@@ -650,4 +650,81 @@ int load_hrir_dir(const char *dir, std::vector<float> *hrir, int *taps_out, std:
     return JF_OK;
 }
 
+// ---- the plan of a batch run: group size, processing order, and which partial blocks each output bus sums ---------------
+// Sources a unit sums as spectra before its inverse transforms, for one mix (G divides S; jf_debug_set_source_group pins it
+// and refuses a size that does not divide S).  Larger groups mean fewer inverse transforms and fewer partial blocks for the mix.
+int host_source_group(int S, int pinned, long long n_items, int pad_len) {
+    if (pinned > 0) return S % pinned == 0 ? pinned : 1;
+    if (pad_len != kN) {
+        // PAD_LEN 2048, a unit is one workgroup of four waves: as many as leave about four units for every compute unit
+        for (const int g : {16, 8, 4, 2})
+            if (S % g == 0 && n_items / g >= 1024) return g;
+        return 1;
+    }
+    // PAD_LEN 1024, a unit is a pair of wavefronts: as many as leave about two units for every resident pair (2048 on
+    // MI355X; profiles/group_sweep.py times every size against this choice)
+    return (S % 32 == 0 && n_items >= 131072) ? 32
+           : (S % 16 == 0 && n_items >= 32768) ? 16
+           : (S % 8 == 0 && n_items >= 16384) ? 8
+           : (S % 4 == 0 && n_items >= 8192) ? 4
+           : (S % 2 == 0 && (n_items >= 4096 || S >= 1024)) ? 2
+                                                           : 1;
+}
+
+// Units never span buses (include/jefferson_debug.h: jf_debug_bus_plan).  bus and key may be null (all 0); order[S],
+// list[S / G] and seg[n_buses + 1] are written where given.  Returns G.
+int host_bus_plan(int S, const int *bus, int n_buses, const int *key, int pinned, long long n_items, int pad_len, int *order,
+                  int *list, int *seg) {
+    auto bus_of = [&](int s) { return bus ? bus[s] : 0; };
+    // automatic grouping at PAD_LEN 1024 takes the sources sorted; a pinned size and PAD_LEN 2048 take consecutive sources
+    const bool sorted = pinned == 0 && pad_len == kN && S > 1;
+    int G = host_source_group(S, pinned, n_items, pad_len);
+    if (n_buses > 1 && G > 1) {
+        if (sorted) {  // every bus's sources are next to each other in the order: G must divide every bus's count
+            std::vector<int> count((size_t)n_buses, 0);
+            for (int s = 0; s < S; s++) count[bus_of(s)]++;
+            auto divides = [&](int g) {
+                for (const int c : count)
+                    if (c % g) return false;
+                return true;
+            };
+            while (G > 1 && !divides(G)) G /= 2;
+        } else {  // every aligned run of G consecutive sources on one bus
+            auto runs_ok = [&](int g) {
+                for (int s = 0; s < S; s++)
+                    if (bus_of(s) != bus_of(s - s % g)) return false;
+                return true;
+            };
+            if (pinned > 0) {
+                if (!runs_ok(G)) G = 1;  // (as a pinned size that does not divide S)
+            } else {
+                while (G > 1 && !runs_ok(G)) G /= 2;
+            }
+        }
+    }
+    std::vector<int> ord;
+    if (order || (sorted && G > 1 && (list || seg))) {
+        ord.resize((size_t)S);
+        for (int s = 0; s < S; s++) ord[s] = s;
+        if (sorted)
+            std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) {
+                if (bus_of(a) != bus_of(b)) return bus_of(a) < bus_of(b);
+                return (key ? key[a] : 0) < (key ? key[b] : 0);
+            });
+        if (order) std::copy(ord.begin(), ord.end(), order);
+    }
+    if (list || seg) {
+        // unit u writes partial[k][u]: the sources order[G u ..] of a grouped run at PAD_LEN 1024, else sources G u ..
+        const int n_units = S / G;
+        auto unit_bus = [&](int u) { return bus_of(sorted && G > 1 ? ord[(size_t)G * u] : G * u); };
+        std::vector<int> at((size_t)n_buses + 1, 0);
+        for (int u = 0; u < n_units; u++) at[unit_bus(u) + 1]++;
+        for (int b = 0; b < n_buses; b++) at[b + 1] += at[b];
+        if (seg) std::copy(at.begin(), at.end(), seg);
+        if (list)
+            for (int u = 0; u < n_units; u++) list[at[unit_bus(u)]++] = u;
+    }
+    return G;
+}
+
 }  // namespace jf

@@ -56,6 +56,12 @@ struct ReverbSchedule {
 };
 ReverbSchedule host_reverb_schedule(long long j0, int K, int M, long long fut_m);
 
+// The plan of a batch run (include/jefferson_debug.h: jf_debug_bus_plan): the group size of one mix, and with output buses
+// the group size, the processing order and the partial blocks every bus sums.  No GPU state.
+int host_source_group(int S, int pinned, long long n_items, int pad_len);
+int host_bus_plan(int S, const int *bus, int n_buses, const int *key, int pinned, long long n_items, int pad_len, int *order,
+                  int *list, int *seg);
+
 }  // namespace jf
 
 // A set on arbitrary directions (include/jefferson.h: jf_cloud; jf_cloud.cpp): the directions as given (direction i = table

@@ -26,7 +26,8 @@
 // mix_kernel / mix_few_kernel sum the per-source (per-group) blocks in source order (a12), prep_kernel computes
 // indices/weights (a2, a3) for every item.  A run prepares the NEXT window's descriptors itself: the pair kernel in
 // trailing workgroups of its own launch (they run in the kernel's tail), the per-source kernel inside its mix launch
-// (mix_prep_kernel).
+// (mix_prep_kernel).  With output buses (jf_engine_set_buses) the mix is bus_mix_kernel: every bus's own blocks, in the same
+// association.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -1370,6 +1371,98 @@ __global__ __launch_bounds__(256) void mix_few_kernel(const float *__restrict__ 
     mix[t] = tot;
 }
 
+// OUTPUT BUSES (jf_engine_set_buses): mix[(b K + k) blk + n] for every bus b -- the sum of the bus's own
+// n_b = seg[b + 1] - seg[b] partial blocks partial[k][list[seg[b] + i]] in the association of mix_body applied to those n_b
+// blocks (per = ceil(n_b / 16); 16 group sums from 0.0f, added in group order), so that a bus equals bit for bit the mix of
+// a one-bus engine that holds just its sources.  An empty bus is written as zeros.  list and seg are read through the
+// constant address space (the bus and the group are uniform over a wave); list is followed by kBusListPad entries that may
+// be read and are never used, so that a bus's indices are fetched by a few wide scalar loads ahead of the vector loads.
+//   PER = 1, 2, 4: no bus has more than 16 PER partial blocks (the pair kernel's units, few sources per bus) -- one thread
+//                  per output float with all of its loads in flight at once, as mix_few_kernel
+//   PER = 0:       any size -- one workgroup per 64 output floats, a wave per group, as mix_kernel
+// One thread's sum over a bus of n_b <= 16 P blocks whose per is P: term (g, j) is block g P + j -- compile-time offsets into
+// the bus's indices; a term that is not there is + 0.0f, which leaves a sum that started from 0.0f as it is.
+template <int P>
+JF_DEV float bus_sum_few(const float *__restrict__ p, const int JF_CONST_AS *li, int nb, int blk) {
+    int u[kMixGroups * P];
+#pragma unroll
+    for (int i = 0; i < kMixGroups * P; i++) u[i] = li[i];  // (past n_b: the next bus's or the padding, loaded and not used)
+    float v[kMixGroups * P];
+#pragma unroll
+    for (int i = 0; i < kMixGroups * P; i++) {
+        v[i] = 0.0f;
+        if (i < nb) v[i] = p[(size_t)u[i] * blk];  // (wave-uniform)
+    }
+    float tot = 0.0f;
+#pragma unroll
+    for (int g = 0; g < kMixGroups; g++) {
+        float acc = 0.0f;  // as mix_body: every group's sum starts from 0
+#pragma unroll
+        for (int j = 0; j < P; j++) acc += v[g * P + j];
+        tot = g == 0 ? acc : tot + acc;
+    }
+    return tot;
+}
+template <int PER>
+__global__ __launch_bounds__(PER ? 256 : 64 * kMixGroups) void bus_mix_kernel(const float *__restrict__ partial,
+                                                                              float *__restrict__ mix,
+                                                                              const int *__restrict__ list,
+                                                                              const int *__restrict__ seg, int n_part, int K,
+                                                                              int blk /* 2B */, int total /* n_buses K blk */) {
+    if constexpr (PER > 0) {
+        const int t = blockIdx.x * 256 + threadIdx.x;
+        if (t >= total) return;
+        // blk is a multiple of 64 and so is a wave's first t: a wave lies within one (bus, block)
+        const int row = __builtin_amdgcn_readfirstlane(t / blk);
+        const int n = t - row * blk;
+        const int b = row / K, k = row - b * K;
+        const int i0 = as_const(seg)[b], nb = as_const(seg)[b + 1] - i0;
+        const int per = (nb + kMixGroups - 1) / kMixGroups;  // <= PER
+        const int JF_CONST_AS *li = as_const(list + i0);
+        const float *p = partial + (size_t)k * n_part * blk + n;
+        float tot;
+        if (per <= 1) tot = bus_sum_few<1>(p, li, nb, blk);
+        else if (PER >= 2 && per == 2) tot = bus_sum_few<(PER >= 2 ? 2 : 1)>(p, li, nb, blk);
+        else if (PER >= 4 && per == 3) tot = bus_sum_few<(PER >= 4 ? 3 : 1)>(p, li, nb, blk);
+        else tot = bus_sum_few<(PER >= 4 ? 4 : 1)>(p, li, nb, blk);
+        mix[t] = tot;
+    } else {
+        __shared__ float red[kMixGroups][64];
+        const int lane = threadIdx.x & 63, grp = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        const int chunks = blk / 64;
+        const int row = blockIdx.x / chunks, n = (blockIdx.x - row * chunks) * 64 + lane;
+        const int b = row / K, k = row - b * K;
+        const int i0 = as_const(seg)[b], nb = as_const(seg)[b + 1] - i0;
+        const int per = (nb + kMixGroups - 1) / kMixGroups;
+        const int JF_CONST_AS *li = as_const(list + i0);
+        const float *p = partial + (size_t)k * n_part * blk + n;
+        const int i1 = min(nb, grp * per + per);
+        int i = grp * per;
+        float acc = 0.0f;
+        int u0 = li[i], u1 = li[i + 1], u2 = li[i + 2], u3 = li[i + 3];  // (the padding: always there to read)
+        for (; i + 4 <= i1; i += 4) {  // four loads in flight and the next four indices behind them, added in order
+            const float x0 = p[(size_t)u0 * blk], x1 = p[(size_t)u1 * blk];
+            const float x2 = p[(size_t)u2 * blk], x3 = p[(size_t)u3 * blk];
+            u0 = li[i + 4], u1 = li[i + 5], u2 = li[i + 6], u3 = li[i + 7];
+            acc += x0;
+            acc += x1;
+            acc += x2;
+            acc += x3;
+        }
+        if (i < i1) acc += p[(size_t)u0 * blk];
+        if (i + 1 < i1) acc += p[(size_t)u1 * blk];
+        if (i + 2 < i1) acc += p[(size_t)u2 * blk];
+        red[grp][lane] = acc;
+        __syncthreads();
+        if (grp == 0) {
+            float t = red[0][lane];
+#pragma unroll
+            for (int g = 1; g < kMixGroups; g++) t += red[g][lane];
+            mix[(size_t)row * blk + n] = t;
+        }
+    }
+}
+
 // ----------------------------------------------- indices and weights (a2,a3)
 // SoundSource.cu:65-105 and hrtf_signals.cu:20-51, float32 exactly as written
 // (no contraction), the nearest-azimuth search done locally instead of over the
@@ -2318,6 +2411,25 @@ hipError_t launch_mix(const float *d_partial, float *d_mix, int S, int K, int B,
     }
     hipLaunchKernelGGL(mix_kernel, dim3(K * (blk / 64)), dim3(64 * kMixGroups), 0, st, d_partial, d_mix, S, K,
                        blk);
+    return hipGetLastError();
+}
+
+// max_nb: the most partial blocks any bus sums.  *form: the kernel's PER (jf_debug_last_kernels).
+hipError_t launch_bus_mix(const float *d_partial, float *d_mix, const int *d_list, const int *d_seg, int n_part, int K, int B,
+                          int n_buses, int max_nb, hipStream_t st, int *form) {
+    const int blk = 2 * B;
+    const long long total = (long long)n_buses * K * blk;
+    if (total <= 0 || total > 0x7fffffff) return hipErrorInvalidValue;
+    const int per = max_nb <= kMixGroups ? 1 : max_nb <= 2 * kMixGroups ? 2 : max_nb <= 4 * kMixGroups ? 4 : 0;
+    *form = per;
+    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+    const int tot = (int)total;
+    if (per == 1) hipLaunchKernelGGL(bus_mix_kernel<1>, grid, block, 0, st, d_partial, d_mix, d_list, d_seg, n_part, K, blk, tot);
+    else if (per == 2) hipLaunchKernelGGL(bus_mix_kernel<2>, grid, block, 0, st, d_partial, d_mix, d_list, d_seg, n_part, K, blk, tot);
+    else if (per == 4) hipLaunchKernelGGL(bus_mix_kernel<4>, grid, block, 0, st, d_partial, d_mix, d_list, d_seg, n_part, K, blk, tot);
+    else
+        hipLaunchKernelGGL(bus_mix_kernel<0>, dim3((unsigned)(total / 64)), dim3(64 * kMixGroups), 0, st, d_partial, d_mix, d_list,
+                           d_seg, n_part, K, blk, tot);
     return hipGetLastError();
 }
 
