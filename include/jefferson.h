@@ -338,7 +338,10 @@ int jf_interpolation(float ele, float azi, int hrtf_indices[4], float omegas[6])
 /* The same (SoundSource.cu:65-105) for an engine created with `flags` (JF_FLAG_CORRECTED_INTERPOLATION selects the corrected
  * rule). */
 int jf_interpolation_ex(float ele, float azi, unsigned flags, int hrtf_indices[4], float omegas[6]);
-/* pick_hrtf (hrtf_signals.cu:20-51): the nearest measurement's table row, what the *_FD_BASIC / *_TD modes filter with. */
+/* pick_hrtf (hrtf_signals.cu:20-51): the nearest measurement's table row, what the *_FD_BASIC / *_TD modes filter with.
+ * The one entry without a range check: a row in [0, 710) for every float.  For finite positions with |azi| < 1e6 -- all the
+ * engine ever picks for -- it is the kernels' own search; outside, a NaN azimuth counts as 0 and any other as the nearest end
+ * of that range (before the rule was shared with the kernels such inputs returned another, equally arbitrary row). */
 int jf_pick_hrtf(float ele, float azi);
 
 /* ---- per-block processing (Audio.cu:94-175) --------------------------- */

@@ -107,7 +107,8 @@ struct SrcSignal {
 // ring by ring, azimuth ascending.  For the reference's KEMAR grid (kemar = 1) these are the tables of hrtf_signals.cu:7-12,
 // filled on the host by the reference's own loop (the steps are the reference's ROUNDED ones: 6.43 for 360 / 56 ...), and the
 // reference's index/weight rule applies unless the corrected one is asked for; any other grid (jf_engine_create_grid)
-// is worked by the corrected rule in its general form (dev_interp_corrected) and a plain nearest-measurement search.
+// is worked by the corrected rule in its general form and a plain nearest-measurement search.  The rules themselves:
+// jf_ring_rule.h (ring_interp_reference, ring_interp_corrected, ring_pick_hrtf), compiled for the kernels and for the host.
 constexpr int kPickAzi = 401;  // integer azimuths 0 .. 400 of the nearest-azimuth table
 struct RingTable {
     int n_rings;  // 14 for KEMAR

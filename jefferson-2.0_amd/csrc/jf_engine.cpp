@@ -290,9 +290,6 @@ static void live_stage_rt(jf_engine *e, const float *in, bool interleaved) {
 
 namespace {
 
-// KEMAR's elevation rings (hrtf_signals.cu:7); the kernels have their own copy (jf_kernels.hip)
-const float kKemarEle[kNumElev] = {-40, -30, -20, -10, 0, 10, 20, 30, 40, 50, 60, 70, 80, 90};
-
 void destroy_engine(jf_engine *e) {
     if (!e) return;
     DeviceGuard bind(e);  // (outlives the delete: the buffers are freed on the engine's device)
@@ -451,10 +448,10 @@ int init_engine(jf_engine *e, const RingTable *grid, const float *hrir, int taps
     JF_HIP(e, e->d_pos_rt.alloc(S * 5));
     e->rt.pick = nullptr;
     if (e->rt.kemar) {
-        // nearest table row per (ring, integer azimuth), by the search itself (host_pick_hrtf = hrtf_signals.cu:20-51)
+        // nearest table row per (ring, integer azimuth), by the search itself (jf_ring_rule.h, shared with the kernels)
         std::vector<short> pick((size_t)kNumElev * kPickAzi);
         for (int r = 0; r < kNumElev; r++)
-            for (int a = 0; a < kPickAzi; a++) pick[(size_t)r * kPickAzi + a] = (short)host_pick_hrtf(kKemarEle[r], (float)a);
+            for (int a = 0; a < kPickAzi; a++) pick[(size_t)r * kPickAzi + a] = (short)ring_pick_azi(e->rt, r, (float)a);
         JF_HIP(e, e->d_pick.alloc(pick.size()));
         JF_HIP(e, h2d(e, e->d_pick, pick.data(), sizeof(short) * pick.size()));
         e->rt.pick = e->d_pick;
@@ -532,7 +529,7 @@ int jf_kemar_grid(jf_hrtf_grid *out) {
     const RingTable &k = ring_table();
     for (int r = 0; r < kNumElev; r++) g_kemar_count[r] = k.offset[r + 1] - k.offset[r];  // (the same values whoever writes them)
     out->n_rings = kNumElev;
-    out->ring_elevation = kKemarEle;
+    out->ring_elevation = k.ele;  // hrtf_signals.cu:7
     out->ring_count = g_kemar_count;
     out->ring_step = kemar_ring_steps();
     return JF_OK;
@@ -579,7 +576,7 @@ int jf_grid_pick(const jf_hrtf_grid *grid, float ele, float azi) {
     const int rc = grid_table(grid, &rt);
     if (rc) return rc;
     if (!(ele >= -1.0e6f && ele <= 1.0e6f) || !(azi > -1.0e6f && azi < 1.0e6f)) return JF_ERR_RANGE;
-    return host_grid_pick(rt, ele, azi);
+    return ring_pick_hrtf(rt, ele, azi);
     });
 }
 
@@ -986,7 +983,7 @@ int jf_interpolation(float ele, float azi, int idx[4], float omegas[6]) {
 int jf_interpolation_ex(float ele, float azi, unsigned flags, int idx[4], float omegas[6]) {
     return jf_guard([&]() -> int {
     if (!idx || !omegas) return JF_ERR_ARG;
-    return (flags & JF_FLAG_CORRECTED_INTERPOLATION) ? host_interpolation_corrected(ele, azi, idx, omegas)
+    return (flags & JF_FLAG_CORRECTED_INTERPOLATION) ? host_grid_interpolation(ring_table(), ele, azi, idx, omegas)
                                                      : host_interpolation(ele, azi, idx, omegas);
     });
 }
@@ -1258,7 +1255,7 @@ static int upload_positions(jf_engine *e, int total_blocks, const float *positio
         const float *p = positions + 5 * (size_t)s;
         const bool ok = p[0] > -1.0e6f && p[0] < 1.0e6f && p[1] > -1.0e6f && p[1] < 1.0e6f;
         int near = 0;
-        if (want_sorted && ok) near = e->rt.cloud.tri ? std::max(0, cloud_pick(e->cloud_host, p[0], p[1])) : host_grid_pick(e->rt, p[0], p[1]);
+        if (want_sorted && ok) near = e->rt.cloud.tri ? std::max(0, cloud_pick(e->cloud_host, p[0], p[1])) : ring_pick_hrtf(e->rt, p[0], p[1]);
         e->row_key[s] = near;
     }
     {

@@ -20,7 +20,6 @@ namespace jf {
 
 namespace {
 constexpr double kPi = 3.14159265358979323846264338327950288;  // Universal.cuh:14-16
-const int kElevPos[kNumElev] = {-40, -30, -20, -10, 0, 10, 20, 30, 40, 50, 60, 70, 80, 90};
 const float kAziInc[kNumElev] = {6.43f, 6.00f, 5.00f, 5.00f, 5.00f, 5.00f, 5.00f,
                                  6.00f, 6.43f, 8.00f, 10.00f, 15.00f, 30.00f, 361.0f};
 
@@ -36,11 +35,11 @@ struct Rings {
         rt.offset[0] = 0;
         for (int e = 0; e < kNumElev; e++) {
             rt.inc[e] = kAziInc[e];
-            rt.ele[e] = (float)kElevPos[e];
+            rt.ele[e] = (float)(-40 + 10 * e);
             // the reference steps a float azimuth; ring sizes follow from that
             for (float azi = 0; azi < 360; azi += kAziInc[e]) {
                 if (j < kNumHrtf) {
-                    pos_ele[j] = kElevPos[e];
+                    pos_ele[j] = -40 + 10 * e;
                     pos_azi[j] = (int)round(azi);
                 }
                 j++;
@@ -153,141 +152,26 @@ int host_grid_from_positions(size_t n, const float *azi, const float *ele, float
     return JF_OK;
 }
 
-// The nearest measurement of a general grid (twin of dev_grid_pick).
-int host_grid_pick(const RingTable &rt, float ele, float azi) {
-    if (rt.kemar) return host_pick_hrtf(ele, azi);
-    float dmin = 1e37f;
-    int ring = 0;
-    for (int r = 0; r < rt.n_rings; r++) {
-        float d = ele - rt.ele[r];
-        if (d < 0) d = -d;
-        if (d < dmin) {
-            dmin = d;
-            ring = r;
-        }
-    }
-    const int n = rt.offset[ring + 1] - rt.offset[ring];
-    float a = azi - 360.0f * floorf(azi / 360.0f);
-    if (!(a < 360.0f)) a = 0.0f;
-    int i = (int)floorf(a / rt.inc[ring] + 0.5f);
-    if (i >= n) i = 0;
-    return rt.offset[ring] + i;
-}
-
 void table_position(int j, int *ele, int *azi) {
     *ele = rings().pos_ele[j];
     *azi = rings().pos_azi[j];
 }
 
-int host_pick_hrtf(float obj_ele, float obj_azi) {
-    const RingTable &rt = ring_table();
-    obj_ele = roundf(obj_ele / 10) * 10;
-    int ring = 0;
-    float best = 1e37f;
-    for (int e = 0; e < kNumElev; e++) {
-        float d = obj_ele - kElevPos[e];
-        if (d < 0) d = -d;
-        if (d < best) {
-            best = d;
-            ring = e;
-        }
-    }
-    obj_azi = roundf(obj_azi);
-    best = 1e37f;
-    int pick = 0;
-    const int n = rt.offset[ring + 1] - rt.offset[ring];
-    for (int i = 0; i < n; i++) {
-        float d = obj_azi - i * rt.inc[ring];
-        if (d < 0) d = -d;
-        if (d < best) {
-            best = d;
-            pick = rt.offset[ring] + i;
-        }
-    }
-    return pick;
-}
-
+// The shared rule (jf_ring_rule.h) behind the C ABI's return codes
 int host_interpolation(float ele, float azi, int idx[4], float omegas[6]) {
-    // (-50, 91): where both truncated elevations name a measured ring.  The setters' whole degrees end at 90; a latched record
-    // may carry 90.x, which the reference's statements place on the 90-degree ring twice (weights 0.x and -0.x)
-    if (!(ele > -50.0f && ele < 91.0f) || !(azi > -1.0e6f && azi < 1.0e6f)) return JF_ERR_RANGE;
-    const int phi0 = (int)ele / 10 * 10;
-    const int phi1 = (int)(ele + 9) / 10 * 10;
-    int r0 = -1, r1 = -1;
-    for (int e = 0; e < kNumElev; e++) {
-        if (kElevPos[e] == phi0) r0 = e;
-        if (kElevPos[e] == phi1) r1 = e;
-    }
-    if (r0 < 0 || r1 < 0) return JF_ERR_RANGE;
-    const float dt1 = kAziInc[r0], dt2 = kAziInc[r1];
-    const int th0 = (int)((int)(azi / dt1) * dt1);
-    const int th1 = (int)((int)((azi + dt1 - 1) / dt1) * dt1);
-    const int th2 = (int)((int)(azi / dt2) * dt2);
-    const int th3 = (int)((int)((azi + dt2 - 1) / dt2) * dt2);
-    omegas[0] = (azi - th0) / dt1;
-    omegas[1] = (th1 - azi) / dt1;
-    omegas[2] = (azi - th2) / dt2;
-    omegas[3] = (th3 - azi) / dt2;
-    omegas[4] = (ele - phi0) / 10.0f;
-    omegas[5] = (phi1 - ele) / 10.0f;
-    idx[0] = host_pick_hrtf((float)phi0, (float)th0);
-    idx[1] = host_pick_hrtf((float)phi0, (float)th1);
-    idx[2] = host_pick_hrtf((float)phi1, (float)th2);
-    idx[3] = host_pick_hrtf((float)phi1, (float)th3);
-    return JF_OK;
+    return ring_interp_reference(ring_table(), ele, azi, idx, omegas) ? JF_OK : JF_ERR_RANGE;
 }
-
-// The corrected rule (include/jefferson.h JF_FLAG_CORRECTED_INTERPOLATION); twin of dev_interp_corrected.
-int host_interpolation_corrected(float ele, float azi, int idx[4], float omegas[6]) {
-    return host_grid_interpolation(ring_table(), ele, azi, idx, omegas);
-}
-
-// ... in its general form, for any grid of rings (twin of dev_interp_corrected, which says why the reference's grid keeps
-// its closed form: the same bits either way)
 int host_grid_interpolation(const RingTable &rt, float ele, float azi, int idx[4], float omegas[6]) {
-    if (!(ele <= 90.0f) || !(ele > -1.0e6f) || !(azi > -1.0e6f && azi < 1.0e6f)) return JF_ERR_RANGE;
-    float a = azi - 360.0f * floorf(azi / 360.0f);
-    if (!(a < 360.0f)) a = 0.0f;
-    int r0;
-    float phi0, span;
-    if (rt.kemar) {
-        if (ele < -40.0f) ele = -40.0f;
-        const float q = floorf(ele / 10.0f);
-        phi0 = 10.0f * q;
-        r0 = (int)q + 4;
-        span = 10.0f;
-    } else {
-        const int last = rt.n_rings - 1;
-        if (ele < rt.ele[0]) ele = rt.ele[0];
-        if (ele > rt.ele[last]) ele = rt.ele[last];
-        r0 = 0;
-        for (int r = 1; r <= last; r++) r0 = rt.ele[r] <= ele ? r : r0;
-        phi0 = rt.ele[r0];
-        span = rt.ele[r0 < last ? r0 + 1 : r0] - phi0;
-    }
-    const bool on_ring = ele == phi0;
-    const int ring[2] = {r0, on_ring ? r0 : r0 + 1};
-    const float omE = on_ring ? 0.0f : (ele - phi0) / span;
-    for (int j = 0; j < 2; j++) {
-        const int r = ring[j];
-        const float d = rt.inc[r];
-        const int n = rt.offset[r + 1] - rt.offset[r];
-        int i0 = (int)floorf(a / d);
-        if (i0 > n - 1) i0 = n - 1;
-        float wa = (a - (float)i0 * d) / d;
-        if (wa < 0.0f) wa = 0.0f;
-        if (wa > 1.0f) wa = 1.0f;
-        if (n == 1) wa = 0.0f;
-        int i1 = i0 + 1 == n ? 0 : i0 + 1;
-        if (wa == 0.0f) i1 = i0;
-        idx[2 * j] = rt.offset[r] + i0;
-        idx[2 * j + 1] = rt.offset[r] + i1;
-        omegas[2 * j] = wa;
-        omegas[2 * j + 1] = 1.0f - wa;
-    }
-    omegas[4] = omE;
-    omegas[5] = 1.0f - omE;
-    return JF_OK;
+    return ring_interp_corrected(rt, ele, azi, idx, omegas) ? JF_OK : JF_ERR_RANGE;
+}
+
+// include/jefferson.h: jf_pick_hrtf, the one entry without a range check -- a row for EVERY float.  The shared pick is
+// defined for |azi| < 1e6 (its float -> int conversion); outside, a NaN azimuth counts as 0 and the others as the nearest end
+// of that range.  (No elevation is converted: a NaN or infinite one leaves the first ring.)
+int host_pick_hrtf(float obj_ele, float obj_azi) {
+    if (obj_azi != obj_azi) obj_azi = 0.0f;
+    obj_azi = fminf(fmaxf(obj_azi, -999999.0f), 999999.0f);
+    return ring_pick_hrtf(ring_table(), obj_ele, obj_azi);
 }
 
 void host_from_spherical(float ele, float azi, float r, float out[5]) {

@@ -7,7 +7,7 @@
 #include <string>
 #include <vector>
 
-#include "jf_device.h"
+#include "jf_ring_rule.h"
 
 namespace jf {
 
@@ -16,16 +16,16 @@ const RingTable &ring_table();
 // (elevation, (int)round(azimuth)) of table row j (hrtf_signals.cu:121-124).
 void table_position(int j, int *ele, int *azi);
 
-int host_pick_hrtf(float obj_ele, float obj_azi);                             // hrtf_signals.cu:20-51
-int host_interpolation(float ele, float azi, int idx[4], float omegas[6]);    // SoundSource.cu:65-105
-int host_interpolation_corrected(float ele, float azi, int idx[4], float omegas[6]);  // JF_FLAG_CORRECTED_INTERPOLATION
-// any grid of elevation rings (include/jefferson.h: jf_hrtf_grid): its table, the corrected rule in its general form, the
-// nearest measurement
+// The index/weight rule and the picks are jf_ring_rule.h's, shared with the kernels, and are called as they are; here only
+// what wraps them for the C ABI: the return codes (JF_OK / JF_ERR_RANGE) and jf_pick_hrtf's guard.
+int host_interpolation(float ele, float azi, int idx[4], float omegas[6]);    // SoundSource.cu:65-105, on ring_table()
+// the corrected rule (JF_FLAG_CORRECTED_INTERPOLATION) in its general form, for any grid of rings
+int host_grid_interpolation(const RingTable &rt, float ele, float azi, int idx[4], float omegas[6]);
+int host_pick_hrtf(float obj_ele, float obj_azi);  // hrtf_signals.cu:20-51 for every float (jf_pick_hrtf)
+// any grid of elevation rings (include/jefferson.h: jf_hrtf_grid): its table
 const float *kemar_ring_steps();  // hrtf_signals.cu:8
 int host_grid_table(int n_rings, const float *ring_ele, const int *ring_count, const float *ring_step, RingTable *out,
                     std::string *err);
-int host_grid_interpolation(const RingTable &rt, float ele, float azi, int idx[4], float omegas[6]);
-int host_grid_pick(const RingTable &rt, float ele, float azi);
 int host_grid_from_positions(size_t n, const float *azi, const float *ele, float tol, int *n_rings, float *ring_ele,
                              int *ring_count, float *ring_step, int *row_of, std::string *err);
 void host_from_spherical(float ele, float azi, float r, float out[5]);        // SoundSource.cu:41-54

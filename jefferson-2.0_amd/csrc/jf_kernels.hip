@@ -36,6 +36,7 @@
 #include "jf_experiments.h"
 #include "jf_packed.h"
 #include "jf_phase.h"
+#include "jf_ring_rule.h"
 
 namespace jf {
 
@@ -1464,60 +1465,11 @@ __global__ __launch_bounds__(PER ? 256 : 64 * kMixGroups) void bus_mix_kernel(co
 }
 
 // ----------------------------------------------- indices and weights (a2,a3)
-// SoundSource.cu:65-105 and hrtf_signals.cu:20-51, float32 exactly as written
-// (no contraction), the nearest-azimuth search done locally instead of over the
-// whole ring.
+// The rule itself is jf_ring_rule.h (rings; shared with the host) and jf_cloud_rule.h (arbitrary directions); here the choice
+// between the two and the descriptors built from their answers.  Float32 exactly as written (no contraction).
 #pragma clang fp contract(off)
-__device__ static const int d_elev_pos[kNumElev] = {-40, -30, -20, -10, 0, 10, 20, 30, 40, 50, 60, 70, 80, 90};
 
-JF_DEV int dev_pick_azi(const RingTable &rt, int ring, float obj_azi) {
-    const float inc = rt.inc[ring];
-    const int n = rt.offset[ring + 1] - rt.offset[ring];
-    obj_azi = roundf(obj_azi);
-    int i0 = (int)floorf(obj_azi / inc) - 1;
-    if (i0 > n - 4) i0 = n - 4;
-    if (i0 < 0) i0 = 0;
-    float dmin = 1e37f;
-    int best = 0;
-    for (int i = i0; i < i0 + 4 && i < n; i++) {
-        float d = obj_azi - i * inc;
-        d = d > 0 ? d : -d;
-        if (d < dmin) {
-            dmin = d;
-            best = i;
-        }
-    }
-    return rt.offset[ring] + best;
-}
-
-// the same for an integer azimuth: one look-up in the table that search filled (jf_engine.cpp), the search itself outside it
-JF_DEV int dev_pick_int(const RingTable &rt, int ring, int th) {
-    if (rt.pick != nullptr && (unsigned)th < (unsigned)kPickAzi) return rt.pick[ring * kPickAzi + th];
-    return dev_pick_azi(rt, ring, (float)th);
-}
-
-// The nearest measurement of a grid that is not the reference's (jf_engine_create_grid; twin of host_grid_pick): the ring
-// whose elevation is nearest (the lower one on a tie), on it the azimuth nearest on the circle.
-JF_DEV int dev_grid_pick(const RingTable &rt, float ele, float azi) {
-    float dmin = 1e37f;
-    int ring = 0;
-    for (int r = 0; r < rt.n_rings; r++) {
-        float d = ele - rt.ele[r];
-        d = d > 0 ? d : -d;
-        if (d < dmin) {
-            dmin = d;
-            ring = r;
-        }
-    }
-    const int n = rt.offset[ring + 1] - rt.offset[ring];
-    float a = azi - 360.0f * floorf(azi / 360.0f);
-    if (!(a < 360.0f)) a = 0.0f;
-    int i = (int)floorf(a / rt.inc[ring] + 0.5f);
-    if (i >= n) i = 0;  // nearer to 360 = the ring's first entry
-    return rt.offset[ring] + i;
-}
-
-// hrtf_signals.cu:20-51 in full: nearest elevation ring, then nearest azimuth on it
+// hrtf_signals.cu:20-51: the nearest measurement's table row
 // CLOUD (here, in dev_interp_terms and in make_desc): -1 = a set on rings or on arbitrary directions, decided at run time
 // (rt.cloud.tri); 0 = rings only -- the cloud's code is not compiled in (the real-time kernel's ring instantiations: they are
 // the code they were before clouds existed, registers and all); 1 = a cloud only.
@@ -1527,84 +1479,14 @@ JF_DEV int dev_pick_hrtf(const RingTable &rt, float obj_ele, float obj_azi) {
         const int row = cloud_pick(rt.cloud, obj_ele, obj_azi);
         return row < 0 ? 0 : row;
     }
-    if (!rt.kemar) return dev_grid_pick(rt, obj_ele, obj_azi);
-    obj_ele = roundf(obj_ele / 10) * 10;
-    float dmin = 1e37f;
-    int ring = 0;
-    for (int e = 0; e < kNumElev; e++) {
-        float d = obj_ele - d_elev_pos[e];
-        d = d > 0 ? d : -d;
-        if (d < dmin) {
-            dmin = d;
-            ring = e;
-        }
-    }
-    return dev_pick_azi(rt, ring, obj_azi);
+    return ring_pick_hrtf(rt, obj_ele, obj_azi);
 }
 
-// returns number of terms (1, 2, 4) or 0 when the elevation ring does not exist
-// The corrected rule behind JF_FLAG_CORRECTED_INTERPOLATION (not in the reference):
-// true floor of the elevation, azimuth folded into [0, 360) with a ring's last interval wrapping to its first
-// entry, float azimuths (a ring's two weights sum to 1), elevations below the lowest ring clamped to it.
-// Same index order and weight meaning as the reference's rule.  Float32 step by step as in the oracles.
-// In its general form (any grid of rings, include/jefferson.h: jf_hrtf_grid): the ring pair is the one whose elevations
-// enclose the position (elevations outside the grid clamped to its first / last ring), the elevation weight is linear between
-// them.  For the reference's grid the closed form below gives the same ring, the same phi0 and the same divisor 10 -- bit for
-// bit the same indices and weights (tests/test_abi.py compares the two on the host, tests/test_gpu_grid.py on the GPU).
-JF_DEV bool dev_interp_corrected(const RingTable &rt, float ele, float azi, int h[4], float om[6]) {
-    if (!(ele <= 90.0f) || !(ele > -1.0e6f) || !(azi > -1.0e6f && azi < 1.0e6f)) return false;
-    float a = azi - 360.0f * floorf(azi / 360.0f);
-    if (!(a < 360.0f)) a = 0.0f;
-    int r0;
-    float phi0, span;
-    if (rt.kemar) {
-        if (ele < -40.0f) ele = -40.0f;
-        const float q = floorf(ele / 10.0f);
-        phi0 = 10.0f * q;
-        r0 = (int)q + 4;
-        span = 10.0f;
-    } else {
-        const int last = rt.n_rings - 1;
-        if (ele < rt.ele[0]) ele = rt.ele[0];
-        if (ele > rt.ele[last]) ele = rt.ele[last];
-        r0 = 0;
-        for (int r = 1; r <= last; r++) r0 = rt.ele[r] <= ele ? r : r0;
-        phi0 = rt.ele[r0];
-        span = rt.ele[r0 < last ? r0 + 1 : r0] - phi0;
-    }
-    const bool on_ring = ele == phi0;
-    const int ring[2] = {r0, on_ring ? r0 : r0 + 1};
-    const float omE = on_ring ? 0.0f : (ele - phi0) / span;
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-        const int r = ring[j];
-        const float d = rt.inc[r];
-        const int n = rt.offset[r + 1] - rt.offset[r];
-        int i0 = (int)floorf(a / d);
-        if (i0 > n - 1) i0 = n - 1;
-        float wa = (a - (float)i0 * d) / d;
-        if (wa < 0.0f) wa = 0.0f;
-        if (wa > 1.0f) wa = 1.0f;
-        if (n == 1) wa = 0.0f;
-        int i1 = i0 + 1 == n ? 0 : i0 + 1;
-        if (wa == 0.0f) i1 = i0;
-        h[2 * j] = rt.offset[r] + i0;
-        h[2 * j + 1] = rt.offset[r] + i1;
-        om[2 * j] = wa;
-        om[2 * j + 1] = 1.0f - wa;
-    }
-    om[4] = omE;
-    om[5] = 1.0f - omE;
-    return true;
-}
-
-JF_DEV int dev_flatten_terms(int h0, int h1, int h2, int h3, float omegaA, float omegaB, float omegaC, float omegaD,
-                             float omegaE, float omegaF, int rows[4], float w[4]);
-
+// returns number of terms (1, 2, 4) or 0 when the position has no answer (silence)
 template <int CLOUD = -1>
 JF_DEV int dev_interp_terms(const RingTable &rt, float ele, float azi, int rows[4], float w[4], bool corrected = false) {
     if (CLOUD != 0 && (CLOUD == 1 || rt.cloud.tri != nullptr)) {
-        // A set on arbitrary directions (jf_cloud_rule.h, shared with the host twin): the three vertices of the triangle that
+        // A set on arbitrary directions (jf_cloud_rule.h, shared with the host): the three vertices of the triangle that
         // contains the position.  The fused kernels take 1, 2 or 4 terms: the three travel as four, the fourth the first row
         // again with weight 0 (it adds +-0 to the sum).
         int steps;
@@ -1613,57 +1495,42 @@ JF_DEV int dev_interp_terms(const RingTable &rt, float ele, float azi, int rows[
         w[3] = 0.0f;
         return n ? 4 : 0;
     }
+    int h[4];
+    float om[6];
     if (corrected || !rt.kemar) {  // (the reference's rule is a rule of the reference's grid)
-        int h[4];
-        float om[6];
-        if (!dev_interp_corrected(rt, ele, azi, h, om)) return 0;
-        return dev_flatten_terms(h[0], h[1], h[2], h[3], om[0], om[1], om[2], om[3], om[4], om[5], rows, w);
+        if (!ring_interp_corrected(rt, ele, azi, h, om)) return 0;
+        return ring_flatten_terms(h[0], h[1], h[2], h[3], om[0], om[1], om[2], om[3], om[4], om[5], rows, w);
     }
-    if (!(ele > -50.0f && ele < 91.0f) || !(azi > -1.0e6f && azi < 1.0e6f)) return 0;  // as host_interpolation (jf_host.cpp)
-    const int phi0 = (int)(ele) / 10 * 10;
-    const int phi1 = (int)(ele + 9) / 10 * 10;
-    const float omegaE = (ele - phi0) / 10.0f;
-    const float omegaF = (phi1 - ele) / 10.0f;
-    // the rings with these elevations (multiples of 10 by construction; -40 .. 90 exist)
-    const int r0 = (phi0 >= -40 && phi0 <= 90) ? (phi0 + 40) / 10 : -1;
-    const int r1 = (phi1 >= -40 && phi1 <= 90) ? (phi1 + 40) / 10 : -1;
-    if (r0 < 0 || r1 < 0) return 0;
-    const float dt1 = rt.inc[r0], dt2 = rt.inc[r1];
-    const int th0 = (int)((int)(azi / dt1) * dt1);
-    const int th1 = (int)((int)((azi + dt1 - 1) / dt1) * dt1);
-    const int th2 = (int)((int)(azi / dt2) * dt2);
-    const int th3 = (int)((int)((azi + dt2 - 1) / dt2) * dt2);
-    const float omegaA = (azi - th0) / dt1;
-    const float omegaB = (th1 - azi) / dt1;
-    const float omegaC = (azi - th2) / dt2;
-    const float omegaD = (th3 - azi) / dt2;
-    const int h0 = dev_pick_int(rt, r0, th0);
-    const int h1 = dev_pick_int(rt, r0, th1);
-    const int h2 = dev_pick_int(rt, r1, th2);
-    const int h3 = dev_pick_int(rt, r1, th3);
-    return dev_flatten_terms(h0, h1, h2, h3, omegaA, omegaB, omegaC, omegaD, omegaE, omegaF, rows, w);
+    if (!ring_interp_reference(rt, ele, azi, h, om)) return 0;
+    return ring_flatten_terms(h[0], h[1], h[2], h[3], om[0], om[1], om[2], om[3], om[4], om[5], rows, w);
 }
 
-// GPUSoundSource.cu:301-316: the case by index equality, flattened to <= 4 (row, weight) terms.  Written with selects, not
-// branches: the compiler merges the branches' stores `w[i] = ..` into one store at a run-time index, which puts the
-// arrays into scratch memory (24 bytes that every kernel with this code inlined then carries).  The same values: the four
-// products are formed whether or not case 4 uses them.
-JF_DEV int dev_flatten_terms(int h0, int h1, int h2, int h3, float omegaA, float omegaB, float omegaC, float omegaD,
-                             float omegaE, float omegaF, int rows[4], float w[4]) {
-    const bool c1 = h0 == h1 && h1 == h2 && h2 == h3;    // one row
-    const bool c2 = !c1 && h0 == h2 && h1 == h3;          // elevation on a ring: two azimuths
-    const bool c3 = !c1 && !c2 && h0 == h1 && h0 != h2;   // azimuth on the grid: two rings
-    const bool c4 = !c1 && !c2 && !c3;
-    const float fb = omegaF * omegaB, fa = omegaF * omegaA, ed = omegaE * omegaD, ec = omegaE * omegaC;
-    rows[0] = h0;
-    w[0] = c1 ? 1.0f : c2 ? omegaB : c3 ? omegaF : fb;
-    rows[1] = c1 ? h0 : c3 ? h2 : h1;
-    w[1] = c1 ? 0.0f : c2 ? omegaA : c3 ? omegaE : fa;
-    rows[2] = c4 ? h2 : h0;
-    w[2] = c4 ? ed : 0.0f;
-    rows[3] = c4 ? h3 : h0;
-    w[3] = c4 ? ec : 0.0f;
-    return c1 ? 1 : c4 ? 4 : 2;
+// *_FD_BASIC (CPUSoundSource.cpp:50-52,113-142): the nearest table row, weight 1, no distance factor (D = 1), no
+// crossfade.  false (and row 0): a position without an answer.
+template <int CLOUD = -1>
+JF_DEV bool basic_row(const RingTable &rt, float ele, float azi, int *row) {
+    const bool ok = (ele > -1.0e6f && ele < 1.0e6f) && (azi > -1.0e6f && azi < 1.0e6f) &&
+                    (CLOUD == 0 || (CLOUD < 0 && rt.cloud.tri == nullptr) || cloud_position_ok(ele, azi));  // (a cloud answers [-90, 90] only)
+    *row = ok ? dev_pick_hrtf<CLOUD>(rt, ele, azi) : 0;
+    return ok;
+}
+
+// GPUSoundSource.cu:81-90: the distance part of a descriptor from the position record p {ele, azi, x, y, z}; inv_nc = 1 / Nc.
+// false: NaN / inf coordinates.
+JF_DEV bool distance_part(const float *p, double inv_nc, unsigned long long *c_fix, float *inv_frac) {
+    const float x = p[2], y = p[3], z = p[4];
+    float r = sqrtf(x * x + y * y + z * z);
+    r /= 5;
+    const float fsvs = (float)(44100.0 / 343.0);
+    const float frac = 1 + fsvs * (float)((double)r * (double)r);
+    {
+        // phase step per bin in turns, as a 64-bit fraction (double keeps 52+ fractional bits here)
+        double c = (double)fsvs * (double)r * inv_nc;  // 1e-16 relative: far below the 2^-32 turn the phase word keeps
+        c -= floor(c);
+        *c_fix = (unsigned long long)(c * 18446744073709551616.0);
+    }
+    *inv_frac = 1.0f / frac;
+    return frac >= 1.0f && frac < 3.0e38f;
 }
 
 // Descriptor of one work item from its latched position record and the position of the block
@@ -1674,11 +1541,8 @@ JF_DEV void make_desc(const RingTable &rt, int mode, const float *p /* ele, azi,
     const float ele = p[0], azi = p[1];
     const bool corrected = (mode & 2) != 0;  // mode: bit 0 FD_BASIC, bit 1 the corrected index/weight rule
     if (mode & 1) {
-        // *_FD_BASIC (CPUSoundSource.cpp:50-52,113-142): the nearest table row, weight 1, no
-        // distance factor (D = 1), no crossfade
-        const bool ok = (ele > -1.0e6f && ele < 1.0e6f) && (azi > -1.0e6f && azi < 1.0e6f) &&
-                        (CLOUD == 0 || (CLOUD < 0 && rt.cloud.tri == nullptr) || cloud_position_ok(ele, azi));  // (a cloud answers [-90, 90] only)
-        const int row = ok ? dev_pick_hrtf<CLOUD>(rt, ele, azi) : 0;
+        int row;
+        const bool ok = basic_row<CLOUD>(rt, ele, azi, &row);
 #pragma unroll
         for (int t = 0; t < 4; t++) {
             d.rows_new[t] = d.rows_old[t] = row;
@@ -1705,26 +1569,13 @@ JF_DEV void make_desc(const RingTable &rt, int mode, const float *p /* ele, azi,
             d.w_old[t] = 0.0f;
         }
     }
-    // GPUSoundSource.cu:81-90
-    const float x = p[2], y = p[3], z = p[4];
-    float r = sqrtf(x * x + y * y + z * z);
-    r /= 5;
-    const float fsvs = (float)(44100.0 / 343.0);
-    const float frac = 1 + fsvs * (float)((double)r * (double)r);
-    {
-        // phase step per bin in turns, as a 64-bit fraction (double keeps 52+ fractional bits here)
-        double c = (double)fsvs * (double)r * (1.0 / 513.0);  // 1e-16 relative: far below the 2^-32 turn the phase word keeps
-        c -= floor(c);
-        d.c_fix = (unsigned long long)(c * 18446744073709551616.0);
-    }
-    d.inv_frac = 1.0f / frac;
-    if (!(frac >= 1.0f) || !(frac < 3.0e38f)) d.n_new = 0;  // NaN / inf coordinates
+    if (!distance_part(p, 1.0 / kNc, &d.c_fix, &d.inv_frac)) d.n_new = 0;
     d.flags = 0;
 }
 
 // Two adjacent lanes per item: the even one does the new position's rule and the distance part, the odd one
 // the old position's rule (the kernel is a short dependent chain per thread at one wave per SIMD: halving
-// the chain halves its time).  Same arithmetic as make_desc, which the real-time kernel uses.
+// the chain halves its time).  The arithmetic is make_desc's, which the real-time kernel uses: the same parts above.
 // st == nullptr: the window continues the trajectory (the block before its first one is at pos - 5 S), as it does for a
 // window prepared ahead of its run (mix_prep_kernel); else the old position of block 0 is the state the last run left.
 // stage: 32 records per wave of the workgroup in LDS.  The lanes build their records there and the wave then writes its
@@ -1758,11 +1609,8 @@ JF_DEV void prep_body(const RingTable &rt, int mode, const float *__restrict__ p
     const bool corrected = (mode & 2) != 0;
     bool pre = false;  // this lane's set is a pre-interpolated row
     if (mode & 1) {
-        // *_FD_BASIC (CPUSoundSource.cpp:50-52,113-142): the nearest table row, weight 1, no
-        // distance factor (D = 1), no crossfade
-        const bool ok = (ele > -1.0e6f && ele < 1.0e6f) && (azi > -1.0e6f && azi < 1.0e6f) &&
-                        (rt.cloud.tri == nullptr || cloud_position_ok(ele, azi));  // (a cloud answers [-90, 90] only)
-        const int row = ok ? dev_pick_hrtf(rt, ele, azi) : 0;
+        int row;
+        const bool ok = basic_row(rt, ele, azi, &row);
         rows[0] = rows[1] = rows[2] = rows[3] = row;
         if (!old_half) {
             w[0] = 1.0f;
@@ -1813,26 +1661,14 @@ JF_DEV void prep_body(const RingTable &rt, int mode, const float *__restrict__ p
     }
     if (live && !old_half) {
     int flags = 0;
-    if (mode & 1) {
-        d.c_fix = 0;
-        d.inv_frac = 1.0f;
-    } else {
+    unsigned long long c_fix = 0;
+    float inv_frac = 1.0f;
+    if (!(mode & 1)) {
         if (moved && n_other == 0) n = 0;  // the old position is not interpolable
-        // GPUSoundSource.cu:81-90
-        const float x = p[2], y = p[3], z = p[4];
-        float r = sqrtf(x * x + y * y + z * z);
-        r /= 5;
-        const float fsvs = (float)(44100.0 / 343.0);
-        const float frac = 1 + fsvs * (float)((double)r * (double)r);
-        {
-            // phase step per bin in turns, as a 64-bit fraction (double keeps 52+ fractional bits here)
-            double c = (double)fsvs * (double)r * inv_nc;  // 1e-16 relative: far below the 2^-32 turn the phase word keeps
-            c -= floor(c);
-            d.c_fix = (unsigned long long)(c * 18446744073709551616.0);
-        }
-        d.inv_frac = 1.0f / frac;
-        if (!(frac >= 1.0f) || !(frac < 3.0e38f)) n = 0;  // NaN / inf coordinates
+        if (!distance_part(p, inv_nc, &c_fix, &inv_frac)) n = 0;
     }
+    d.c_fix = c_fix;
+    d.inv_frac = inv_frac;
     if (canon) {
         // Layout for fused_pair_kernel.  A source that did not move carries its new set as its old set (inside a
         // unit that crossfades it goes through both sums).  If the rows of one set are, in order, among the rows of
@@ -2087,7 +1923,7 @@ __global__ __launch_bounds__(64) void table_build_kernel(const float *__restrict
 }
 
 // The pre-interpolated rows (jf_device.h: htab): row n_rows + (ele + 40) 360 + azi = sum_t w_t H[row_t] for the whole-degree
-// position (ele, azi) -- the index/weight rule itself (dev_interp_terms, SoundSource.cu:65-105) and the half-filters' own
+// position (ele, azi) -- the index/weight rule itself (dev_interp_terms, jf_ring_rule.h: SoundSource.cu:65-105) and the half-filters' own
 // weighting (weighted_ears), one wave per row.  What GPUSoundSource.cu:118-292 recomputes for every block and source
 // (four scaled products summed by atomicAdd) is computed here once per position the setters can latch.
 __global__ __launch_bounds__(64) void table_interp_build_kernel(const RingTable rt, int corrected, float4 *__restrict__ htab) {

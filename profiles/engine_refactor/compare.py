@@ -8,7 +8,9 @@
 
 The sessions cover what bench.py does not: per-block calls through the one-launch kernel and through the batch path, batch
 runs with G > 1 (with and without the pre-interpolated rows, descriptors prepared ahead, per-kernel timing), PAD_LEN 2048,
-a cloud engine, live sources, and the reverb in both partitionings with the stage launched ahead, the side stream and a discard.
+a cloud engine, live sources, and the reverb in both partitionings with the stage launched ahead, the side stream and a discard;
+and (rule_sessions, profiles/ring_rule/README.md) both index/weight rules and FD_BASIC on KEMAR's grid and on a general grid, on
+fractional positions and positions without an answer, through every kernel that builds descriptors, and the rule's debug kernel.
 """
 import argparse
 import json
@@ -205,6 +207,63 @@ def reverb_sessions():
     e.close()
 
 
+def records(K, S, lo=-60.0, hi=100.0, every=2):
+    """[K][S][5] records as no setter latches them: fractional directions, azimuths outside [0, 360), elevations beyond both ends
+    of the interpolable range (silence); every third direction lies on a grid line (a whole multiple of 5 degrees)"""
+    pos = positions(K, S, every=every)
+    n = (K + every - 1) // every
+    ele, azi = rng.uniform(lo, hi, (n, S)), rng.uniform(-400.0, 800.0, (n, S))
+    line = rng.integers(0, 3, (n, S)) == 0
+    ele, azi = np.where(line, np.round(ele / 5.0) * 5.0, ele), np.where(line, np.round(azi / 5.0) * 5.0, azi)
+    pos[..., 0] = np.repeat(ele, every, axis=0)[:K]
+    pos[..., 1] = np.repeat(azi, every, axis=0)[:K]
+    return pos
+
+
+def windows(e, pos, K):
+    """batch runs over windows 0, K, 0 of one trajectory (the second window's descriptors come out of the first run's launch)"""
+    e.upload_positions(pos)
+    y, k = [], []
+    for first in (0, K, 0):
+        e.batch_run(first, K)
+        y.append(e.batch_fetch(K))
+        k.append(";".join(e.last_kernels()) + f"|G={e.last_source_group()}")
+    return np.stack(y), k
+
+
+def rule_sessions():
+    """The index/weight rule and the two descriptor builders (profiles/ring_rule/README.md): both rules and FD_BASIC on KEMAR's
+    grid and on a grid of its own, through the one-launch kernel (make_desc), prep_kernel, the pair kernel's trailing
+    workgroups and mix_prep_kernel (prep_body), on records(); then the rule's own debug kernel."""
+    K = 4
+    own = jf.Grid([-45.0, -20.0, 0.0, 15.0, 40.0, 65.0, 90.0], [12, 24, 36, 30, 20, 8, 1])
+    h_own = long_hrir(own.rows(), 128)
+    for name, kw in (("kemar", dict(hrir=kemar)), ("corrected", dict(hrir=kemar, flags=jf.JF_FLAG_CORRECTED_INTERPOLATION)),
+                     ("grid", dict(hrir=h_own, grid=own))):
+        for mode in (jf.JF_MODE_FD_COMPLEX, jf.JF_MODE_FD_BASIC):
+            tag = f"rule.{name}.mode{mode}"
+            e = jf.Engine(128, 512, 5, max_batch_blocks=K, **kw)  # per-block, then G = 1 batches
+            signals(e, 5)
+            e.set_mode(mode)
+            keep(tag + ".block", *blocks(e, records(8, 5)))
+            keep(tag + ".batch", *windows(e, records(3 * K, 5, every=3), K))
+            e.close()
+            e = jf.Engine(256, 512, 64, max_batch_blocks=K, **kw)  # the pair kernel, G = 8
+            signals(e, 64)
+            e.set_mode(mode)
+            e.set_source_group(8)
+            keep(tag + ".pair", *windows(e, records(3 * K, 64, every=3), K))
+            e.close()
+        e = jf.Engine(128, 512, 1, **kw)
+        n = 4000
+        ele, azi = rng.uniform(-60.0, 100.0, n), rng.uniform(-400.0, 800.0, n)
+        ele[:1500], azi[:1500] = np.round(ele[:1500] / 5.0) * 5.0, np.round(azi[:1500])  # on the rings' elevations, whole azimuths
+        azi[:500] = np.round(azi[:500] / 5.0) * 5.0
+        rows, w, nt = e.interp_device(ele, azi)
+        out[f"rule.{name}.interp.rows"], out[f"rule.{name}.interp.w"], out[f"rule.{name}.interp.n"] = rows, w, nt
+        e.close()
+
+
 def memory():
     """device memory in use before and after ten create / use / destroy cycles of the engines the leak test does not cover"""
     azi, ele = fibonacci(50)
@@ -250,6 +309,7 @@ pad2048_sessions()
 cloud_session()
 live_session()
 reverb_sessions()
+rule_sessions()
 np.savez(args.files[0], **out)
 print(json.dumps({"what": "render", "lib": os.path.relpath(jf.LIB_PATH, ROOT), "arrays": len(out)}), flush=True)
 if args.memory:

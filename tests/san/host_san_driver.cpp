@@ -62,7 +62,7 @@ int main(int argc, char **argv) {
         int e, a;
         table_position(j, &e, &a);
         CHECK(e >= -40 && e <= 90 && a >= 0 && a < 360);
-        CHECK(host_pick_hrtf((float)e, (float)a) == j);
+        CHECK(ring_pick_hrtf(rt, (float)e, (float)a) == j);
     }
     long n_ok = 0;
     for (int e2 = -140; e2 <= 220; e2++)
@@ -71,13 +71,13 @@ int main(int argc, char **argv) {
             int idx[4];
             float om[6];
             for (int rule = 0; rule < 2; rule++) {
-                const int rc = rule ? host_interpolation_corrected(ele, azi, idx, om) : host_interpolation(ele, azi, idx, om);
+                const int rc = rule ? host_grid_interpolation(rt, ele, azi, idx, om) : host_interpolation(ele, azi, idx, om);
                 if (rc == JF_OK) {
                     n_ok++;
                     for (int t = 0; t < 4; t++) CHECK(idx[t] >= 0 && idx[t] < kNumHrtf);
                 }
             }
-            const int p = host_pick_hrtf(ele, azi);
+            const int p = ring_pick_hrtf(rt, ele, azi);
             CHECK(p >= -1 && p < kNumHrtf);
         }
     CHECK(n_ok > 100000);
@@ -87,8 +87,9 @@ int main(int argc, char **argv) {
             int idx[4];
             float om[6], rec[5], r;
             (void)host_interpolation(e, a, idx, om);
-            (void)host_interpolation_corrected(e, a, idx, om);
-            (void)host_pick_hrtf(e, a);
+            (void)host_grid_interpolation(rt, e, a, idx, om);
+            const int p = host_pick_hrtf(e, a);  // (jf_pick_hrtf: the guard in front of the shared pick)
+            CHECK(p >= 0 && p < kNumHrtf);
             host_from_spherical(e, a, 0.5f, rec);
             (void)host_from_cartesian(e, a, 1.f, rec, &r);
         }
@@ -191,7 +192,7 @@ int main(int argc, char **argv) {
             int e, a;
             table_position(j, &e, &a);
             if (a == 0 || a >= 180) continue;
-            const int m = host_pick_hrtf((float)e, (float)(360 - a));
+            const int m = ring_pick_hrtf(rt, (float)e, (float)(360 - a));
             int e2, a2;
             table_position(m, &e2, &a2);
             if (e2 != e || a2 != 360 - a) continue;

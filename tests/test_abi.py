@@ -122,9 +122,11 @@ def test_host_interpolation_matches_oracle(jf):
             assert (a is None) == (b is None), (ele, azi)
             if a is not None:
                 assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]), (ele, azi)
-    for ele in (-40, 0, 37, 90):
-        for azi in range(0, 361):
-            assert jf.pick_hrtf(ele, azi) == oracle_lib.pick_hrtf(ele, azi)
+    # the pick: the product searches four candidates around the azimuth, the oracle the whole ring -- every ring, a few
+    # elevations off the rings, azimuths two turns either side of [0, 360]
+    for ele in list(range(-40, 91, 10)) + [37, -44.9, 4.9, 5.0, 85.1, 93.5]:
+        for azi in np.arange(-720, 1080.25, 0.25):
+            assert jf.pick_hrtf(ele, float(azi)) == oracle_lib.pick_hrtf(ele, float(azi)), (ele, azi)
 
 
 def test_host_corrected_interpolation_matches_oracle(jf):
