@@ -228,7 +228,13 @@ def test_config4_tiled_reverb_kernel_at_690_partitions(jf, hrir, castanets, S, K
     takes by itself for this response -- partitions of 2048 (44 of them for blocks inside a call of whole big blocks: these
     calls; 32 of 128 + 42 of 2048 for blocks worked on their own).  Per-source blocks of sampled sources
     against the float32 C oracle with its reverb stage (jfo_reverb_set_ir) and against gain * float64 convolution ->
-    float64 spatialiser model; the mix as the ordered sum of the blocks."""
+    float64 spatialiser model; the mix as the ordered sum of the blocks.
+
+    How many partitions these runs feed: 2 x 32 blocks = 8 192 samples reach small partitions 0 .. 63 (the head and big
+    partitions 0 and 1); 2 x 256 blocks = 65 536 samples of the 88 200-tap response reach small partitions 0 .. 511, i.e. big
+    partitions 0 .. 29 of 42.  Big partitions 30 .. 41 (small partitions 512 .. 689) never meet a non-zero input here:
+    dropping all of them leaves the expected output unchanged.  tests/test_gpu_probe_reverb.py runs this response for 725
+    blocks on inputs in which each of them counts."""
     B = 128
     ir = _ir(88200)
     assert -(-len(ir) // B) == 690
@@ -287,7 +293,10 @@ def test_config4_bench_shape_with_the_default_grouping(jf, hrir, castanets):
     grouping: the spatialiser behind the reverb stage is then fused_pair_kernel<2> over units of 16 sources in the engine's
     processing order, reading the wet ring -- as two consecutive calls.  Every unit's stereo blocks against the float32 C
     oracle's per-source blocks (reverb stage + spatialiser) summed over the unit's sources in that order; the mix as the
-    ordered sum of the units' blocks; sampled units against the float64 model as well."""
+    ordered sum of the units' blocks; sampled units against the float64 model as well.
+
+    2 x 256 blocks = 65 536 samples of the 88 200-tap response: big partitions 0 .. 29 of 42 are fed, big partitions
+    30 .. 41 (small partitions 512 .. 689) multiply zeros throughout (tests/test_gpu_probe_reverb.py feeds them all)."""
     B, S, K = 128, 256, 256
     ir = _ir(88200)
     gain = 0.5

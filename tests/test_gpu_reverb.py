@@ -90,7 +90,10 @@ def test_reverb_short_ir_vs_float64(jf, hrir, castanets, B):
 
 
 def test_reverb_two_second_ir(jf, hrir, castanets):
-    """configs[4] geometry: B = 128, 2.0 s IR = 88 200 taps = 690 partitions of 128."""
+    """configs[4] geometry: B = 128, 2.0 s IR = 88 200 taps = 690 partitions of 128 -- as a layout.  The run is 12 blocks =
+    1 536 samples, so only partitions 0 .. 11 ever meet a non-zero spectrum; partitions 12 .. 689 multiply zeros, and
+    dropping or swapping any of them leaves the expected output unchanged.  What is run until the last of the 690 has
+    spoken is tests/test_gpu_probe_reverb.py (725 blocks)."""
     B, S, K = 128, 2, 12
     ir = _ir(88200)
     assert -(-len(ir) // B) == 690
