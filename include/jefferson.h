@@ -452,6 +452,42 @@ int jf_num_buses(const jf_engine *e);
 int jf_source_set_bus(jf_engine *e, int src, int bus);
 int jf_source_bus(const jf_engine *e, int src);
 
+/* ---- shared inputs: sources that play one signal ---------------------------- */
+
+/*
+ * The reference gives every SoundSource a buf / length / count of its own (cudaPart.cu:198-199) and sums the sources one by
+ * one (the mixing loop, Audio.cu:109-110): a signal that several sources play -- one talker heard by every listener of a
+ * conference, each on a bus of their own -- is uploaded once per source.  After jf_source_share_input(e, f, r) source f (a
+ * FOLLOWER) plays the input of r (the ROOT) instead: r's signal or live channel, r's play position, r's window.  f keeps its
+ * own position, old position (crossfade state) and bus.
+ *
+ * THE CONTRACT: an engine in which every member of a share group is an independent source holding the same samples, given
+ * the same calls for every member, renders bit for bit the same output -- on every kind of engine, in both modes, through
+ * every processing call, with output buses.  What sharing saves is the upload, the memory, the live channel, and in the
+ * batch path at PAD_LEN 1024 the forward transform: formed once per block and group, read by every member (DESIGN.md 4.12;
+ * the one-launch real-time kernel and PAD_LEN 2048 run followers as aliases of the root's buffer).
+ *
+ * jf_source_share_input(e, src, of):
+ *   of names a follower: it stands for its root.  src takes the root's window and play position as they are at the call.
+ *   Like jf_source_reset the call waits for the engine's stream and discards what was prepared ahead: between blocks.
+ *   of < 0 or of == src: DETACH -- src is independent again and left as jf_source_set_signal(e, src, NULL, 0) leaves a
+ *     source in its state (silent, play position 0, its window kept); a source that follows nobody -- a root with
+ *     followers included -- stays as it is (JF_OK).
+ *   JF_ERR_ARG for a bad index; JF_ERR_STATE while a block is in flight, when src is to follow somebody and has followers of
+ *   its own (detach them first), and while a reverb response is set (the reverb keeps per-source state; jf_reverb_set_ir in turn returns
+ *   JF_ERR_STATE while any source follows another).  On a refusal nothing changes.
+ * jf_source_input_of: the source whose input src plays; src itself if it follows nobody.  JF_ERR_ARG for a bad index.
+ *
+ * jf_source_set_signal / jf_source_set_live on a ROOT act on the whole group: the followers follow the new input.  On a
+ *   FOLLOWER they detach it first and then act on it alone.  Only roots and unshared sources are live channels
+ *   (jf_num_live_sources counts them, the *_in calls are fed for them); a follower of a live root hears that channel.
+ * jf_source_reset on a member resets the input state (window, play position) of every member of its group -- they stay
+ *   equal -- and the crossfade state of that member only.
+ * jefferson_group.h does not offer shared inputs; jf_render and jf_ctest have no option for them.
+ */
+int jf_source_share_input(jf_engine *e, int src, int of);
+int jf_source_input_of(const jf_engine *e, int src);
+
 /* ---- convolution reverb -------------------------------- */
 
 /*

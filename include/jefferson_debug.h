@@ -39,6 +39,8 @@ int jf_profile_read(jf_engine *e, double *fused_ms, double *prep_ms, double *mix
  * counts the runs that were timed. */
 int jf_profile_set_stride(jf_engine *e, int every);
 int jf_profile_read_reverb(jf_engine *e, double *reverb_ms); /* the two reverb kernels, same launches */
+/* level 2: shared_spectrum_kernel of the timed runs that launched it (shared inputs; its time is part of fused_ms as well) */
+int jf_profile_read_spectrum(jf_engine *e, double *spectrum_ms);
 
 /* ---- HDF5 reader taps (tests/test_sofa.py) -------------------------------------------------------------------------- */
 
@@ -75,6 +77,15 @@ int jf_debug_source_order(const jf_engine *e, int *order);
  */
 int jf_debug_bus_plan(int n_sources, const int *bus, int n_buses, const int *row_key, int pinned_group, long long n_items,
                       int pad_len, int *order, int *list, int *seg);
+/*
+ * The plan of shared inputs (jf_source_share_input), as the engine forms it -- a pure host function: no engine, no GPU.
+ * In: root[n_sources], the source whose input every source plays (itself: unshared or a root; root[root[s]] == root[s]).
+ * Every share group of two or more members gets a spectrum slot, numbered in the order of the roots.  Returns the number of
+ * slots or JF_ERR_ARG; fills, where not NULL, xslot[n_sources] -- the slot of every member of such a group, -1 for everyone
+ * else --, seg[slots + 1] and list[seg[slots]]: the groups' member lists in CSR form, the root first and its followers
+ * behind it in ascending order (room for n_sources / 2 + 1 and n_sources entries is always enough).
+ */
+int jf_debug_share_plan(int n_sources, const int *root, int *xslot, int *seg, int *list);
 /* Form of the reverb's multiply-accumulate stage: 0 = by call size (default); 1 = one workgroup per
  * (block, source) -- what real-time calls use; 2 = groups of sources share each IR partition spectrum;
  * 3 = tiles of consecutive blocks share a sliding window of input spectra (large batch calls).  The

@@ -13,6 +13,8 @@
  * and librccl.so.  Source indices below are GLOBAL (0 .. n_sources - 1 of the whole job).
  * HRTF sets: KEMAR, grids of rings and SOFA files of rings (below).  Sets on arbitrary directions (jefferson.h: jf_cloud,
  * jf_engine_create_cloud) are out of scope here: a group has no cloud door.
+ * Shared inputs (jefferson.h: jf_source_share_input) are not offered: a group has no share call, and its engines' sources
+ * each play their own signal.
  * Output buses (jefferson.h: jf_engine_set_buses) are not offered either: a group has no bus call, its engines keep their one
  * mix and the exchange stays the sum of one stereo mix per GPU.
  */

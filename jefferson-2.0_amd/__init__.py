@@ -110,6 +110,9 @@ _SIGS = {
     "jf_source_set_bus": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "jf_source_bus": (C.c_int, [C.c_void_p, C.c_int]),
     "jf_debug_bus_plan": (C.c_int, [C.c_int, _i, C.c_int, _i, C.c_int, C.c_longlong, C.c_int, _i, _i, _i]),
+    "jf_source_share_input": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "jf_source_input_of": (C.c_int, [C.c_void_p, C.c_int]),
+    "jf_debug_share_plan": (C.c_int, [C.c_int, _i, _i, _i, _i]),
     "jf_submit_block_in": (C.c_int, [C.c_void_p, _f]),
     "jf_process_block_in": (C.c_int, [C.c_void_p, _f, _f]),
     "jf_callback_in": (C.c_int, [C.c_void_p, _f, _f]),
@@ -145,6 +148,7 @@ _SIGS = {
     "jf_reverb_set_ir": (C.c_int, [C.c_void_p, _f, C.c_size_t, C.c_float]),
     "jf_reverb_rms_gain": (C.c_float, [_f, C.c_size_t, _f, C.c_size_t]),
     "jf_profile_read_reverb": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "jf_profile_read_spectrum": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "jf_profile_set_stride": (C.c_int, [C.c_void_p, C.c_int]),
     "jf_debug_set_source_group": (C.c_int, [C.c_void_p, C.c_int]),
     "jf_debug_read_stamps": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]),
@@ -284,6 +288,17 @@ def bus_plan(bus, n_buses, row_key=None, pinned=0, n_items=0, pad_len=1024):
     if G <= 0:
         raise JfError(G, "bus_plan")
     return G, order, lst[:S // G], seg
+
+
+def share_plan(root):
+    """jf_debug_share_plan (host logic only): (n_slots, xslot[S], seg[n_slots + 1], list[seg[-1]])"""
+    root = np.ascontiguousarray(root, np.int32)
+    S = len(root)
+    xslot, seg, lst = np.zeros(S, np.int32), np.zeros(S // 2 + 2, np.int32), np.zeros(S, np.int32)
+    n = lib().jf_debug_share_plan(S, _ip(root), _ip(xslot), _ip(seg), _ip(lst))
+    if n < 0:
+        raise JfError(n, "share_plan")
+    return n, xslot, seg[:n + 1], lst[:seg[n]]
 
 
 def pick_hrtf(ele, azi):
@@ -606,6 +621,16 @@ class Engine:
             raise JfError(b, "bad source index")
         return b
 
+    def share_input(self, s, of):
+        """source s plays the input of source `of` (include/jefferson.h: jf_source_share_input); of < 0 or of == s detaches"""
+        self._chk(lib().jf_source_share_input(self.h, int(s), int(of)))
+
+    def input_of(self, s):
+        r = lib().jf_source_input_of(self.h, int(s))
+        if r < 0:
+            raise JfError(r, "bad source index")
+        return r
+
     def _out(self, *shape):
         """zeros of a call's output shape, behind a bus axis when the engine has more than one bus"""
         nb = self.n_buses
@@ -727,6 +752,12 @@ class Engine:
     def profile_read_reverb(self):
         r = C.c_double()
         self._chk(lib().jf_profile_read_reverb(self.h, C.byref(r)))
+        return r.value
+
+    def profile_read_spectrum(self):
+        """ms in shared_spectrum_kernel since profile_enable(2) (part of profile_read()'s fused_ms too)"""
+        r = C.c_double()
+        self._chk(lib().jf_profile_read_spectrum(self.h, C.byref(r)))
         return r.value
 
     def set_source_group(self, g):

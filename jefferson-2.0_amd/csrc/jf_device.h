@@ -22,6 +22,7 @@
 //   desc   ItemDesc[K][S]     per (block, source) rows/weights/distance terms.
 //   partial float[K][S/G][2B] stereo blocks of groups of G consecutive sources (G = 1: the
 //                             reference's per-source `intermediate`).
+//   xspec  float2[K][n_slots][512] shared inputs only (FusedParams::xspec): the forward transform of every share group's window
 //   mix    float[K][2B]       sum over sources in source order; with output buses float[n_buses][K][2B], a bus's
 //                             sources each (bus_list int[S/G], bus_seg int[n_buses + 1]: which partial blocks a bus sums).
 #pragma once
@@ -143,9 +144,17 @@ struct FusedParams {
                // where descriptors are built in-kernel (real-time kernel, the pair kernel's trailing workgroups)
     const int *order;  // [S] pair kernel: unit u works on sources order[G u .. G u + G - 1] (identity unless the engine sorted)
     int *err;  // host-mapped word: set to 1 if a pair hand-off of fused_pair_kernel ever times out (never, by construction)
+    // SHARED INPUTS (the SHARED instantiations and shared_spectrum_kernel only; null / 0 in every other launch): the forward
+    // transform of a share group's window is formed once per block by shared_spectrum_kernel and read by every member
+    float2 *xspec = nullptr;          // [K][n_slots][512] a slot's spectrum as rfft1024_wave leaves it, as 256 float4: entry
+                                      // 64 j + lane = (X[2 j], X[2 j + 1]) of that lane, j < 4 (a wave's access: a 1 KB line)
+    const int *xslot = nullptr;       // [S] the spectrum slot a source reads, -1: it transforms its own window
+    const int *share_seg = nullptr;   // [n_slots + 1] offsets of the slots' member lists in share_list
+    const int *share_list = nullptr;  // the members of every slot's group, the root first
     // fused_pair_kernel only: workgroups n_pair_wgs .. gridDim.x - 1 prepare the descriptors of the window that FOLLOWS this
     // run in the uploaded trajectory (prep_kernel's work, 512 items per workgroup) while the last pairs finish
     int n_pair_wgs = 0;                // workgroups that work on units (set by launch_fused)
+    int n_slots = 0;                   // spectrum slots of the launch (shared inputs, above)
     const float *prep_pos = nullptr;   // [prep_K][S][5] the following window's positions (null: nothing to prepare)
     ItemDesc *prep_desc = nullptr;     // [prep_K][S] where its descriptors go
     int prep_K = 0, prep_canon = 0;

@@ -73,7 +73,10 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
     }
     const int p = e->cur;
     const bool n1024 = e->N == kN;
-    EventPair *ep = nullptr, *ef = nullptr, *em = nullptr;
+    EventPair *ep = nullptr, *ef = nullptr, *em = nullptr, *es = nullptr;
+    // shared inputs: the groups' forward transforms once per block, ahead of the fused kernel's SHARED instantiation (the
+    // reverb stage keeps per-source state and refuses followers; PAD_LEN 2048 runs them as aliases)
+    const bool shared = n1024 && e->rv_P == 0 && e->n_slots > 0;
     // a pair of event records costs ~7 us of stream time: they may be put around every n-th run only (the runs in
     // between launch the same kernels, untimed)
     const bool timed = e->profiling && (e->profile_stride <= 1 || e->profile_calls++ % e->profile_stride == 0);
@@ -86,6 +89,16 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
         ep = next_events(e, e->ev_prep);
         em = next_events(e, e->ev_mix);
         if (!ep || !em) return fail(e, JF_ERR_DEVICE, "hipEventCreate failed");
+        e->ev_spec_on.resize(e->ev_used + 1, 0);
+        e->ev_spec_on[e->ev_used] = shared;
+        if (shared) {
+            while (e->ev_spec.size() <= e->ev_used) {
+                EventPair q;
+                if (hipEventCreate(&q.a) != hipSuccess || hipEventCreate(&q.b) != hipSuccess) return fail(e, JF_ERR_DEVICE, "hipEventCreate failed");
+                e->ev_spec.push_back(q);
+            }
+            es = &e->ev_spec[e->ev_used];
+        }
     }
     const long long n_items = (long long)K * e->S;
     int G = 1;
@@ -144,10 +157,23 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
     P.prep_K = K;
     P.prep_canon = canon;
     P.rt = e->rt;
+    e->last_shared = shared;
+    if (shared) {
+        P.xspec = e->d_xspec;
+        P.xslot = e->d_xslot;
+        P.share_seg = e->d_share_seg;
+        P.share_list = e->d_share_list;
+        P.n_slots = e->n_slots;
+    }
     if (ef) JF_HIP(e, hipEventRecord(ef->a, e->stream));
     if (n1024) {
-        int max_wgs = e->resident_wgs[G > 1 ? (rows ? 2 : 1) : 0];
+        int max_wgs = e->resident_wgs[(G > 1 ? (rows ? 2 : 1) : 0) + (shared ? 3 : 0)];
         if (e->grid_limit > 0 && e->grid_limit < max_wgs) max_wgs = e->grid_limit;
+        if (shared) {
+            if (es) JF_HIP(e, hipEventRecord(es->a, e->stream));
+            JF_HIP(e, launch_shared_spectrum(P, e->stream));
+            if (es) JF_HIP(e, hipEventRecord(es->b, e->stream));
+        }
         JF_HIP(e, launch_fused(P, max_wgs, e->stream));
     } else {
         JF_HIP(e, launch_fused2048(P, e->stream));
@@ -247,6 +273,7 @@ static int live_refresh(jf_engine *e) {
     if (e->n_live > 0) JF_HIP(e, h2d(e, e->d_live_idx, e->live_idx.data(), sizeof(int) * e->n_live));
     std::vector<SrcSignal> rt = e->h_sigs;
     for (int j = 0; j < e->n_live; j++) rt[e->live_idx[j]] = SrcSignal{e->hd_in + (size_t)j * B, e->B, 0};
+    for (int s = 0; s < e->S; s++) rt[s] = rt[root_of(e, s)];  // a follower of a live root hears that channel: the root's staging row
     JF_HIP(e, h2d(e, e->d_sigs_rt, rt.data(), sizeof(SrcSignal) * S));
     return JF_OK;
 }
@@ -295,7 +322,7 @@ void destroy_engine(jf_engine *e) {
     DeviceGuard bind(e);  // (outlives the delete: the buffers are freed on the engine's device)
     if (e->rv_side) (void)hipStreamSynchronize(e->rv_side);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
-    for (auto *pool : {&e->ev_prep, &e->ev_fused, &e->ev_mix, &e->ev_reverb})
+    for (auto *pool : {&e->ev_prep, &e->ev_fused, &e->ev_mix, &e->ev_reverb, &e->ev_spec})
         for (auto &p : *pool) {
             (void)hipEventDestroy(p.a);
             (void)hipEventDestroy(p.b);
@@ -414,7 +441,7 @@ int init_engine(jf_engine *e, const RingTable *grid, const float *hrir, int taps
     }
     JF_HIP(e, hipEventCreateWithFlags(&e->rv_ev_main, hipEventDisableTiming));
     JF_HIP(e, hipEventCreateWithFlags(&e->rv_ev_side, hipEventDisableTiming));
-    for (int kind = 0; kind < 3; kind++) JF_HIP(e, fused_resident_workgroups(e->B / 64, kind, &e->resident_wgs[kind]));
+    for (int kind = 0; kind < 6; kind++) JF_HIP(e, fused_resident_workgroups(e->B / 64, kind, &e->resident_wgs[kind]));
     {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device) == hipSuccess && cus >= 16)
@@ -766,25 +793,113 @@ static int swap_signal(jf_engine *e, int src, DevBuf<float> d_new, int n_dev, bo
     if (e->rv_side && e->rv_side_busy) JF_HIP(e, hipStreamSynchronize(e->rv_side));
     if (live && e->live.empty()) e->live.assign((size_t)e->S, 0);
     e->d_signal[src] = std::move(d_new);  // the old signal is released; the source's window stays as it is
-    e->h_sigs[src] = e->d_signal[src] ? SrcSignal{e->d_signal[src], n_dev, 0} : SrcSignal{e->d_zero, e->N, 0};
-    JF_HIP(e, h2d(e, e->d_sigs + src, &e->h_sigs[src], sizeof(SrcSignal)));
-    if (!e->live.empty()) {  // (the real-time kernel's records follow)
-        e->live[src] = live;
-        const int rc = live_refresh(e);
-        if (rc) return rc;
-    }
+    const SrcSignal rec = e->d_signal[src] ? SrcSignal{e->d_signal[src], n_dev, 0} : SrcSignal{e->d_zero, e->N, 0};
+    if (!e->live.empty()) e->live[src] = live;
     const int zero = 0;  // count = 0 (cudaPart.cu:198-199 run with a fresh source)
-    if (e->rv_P > 0)  // the play position of the dry signal lives in the reverb stage
-        JF_HIP(e, h2d(e, e->d_rv_count[e->cur] + src, &zero, sizeof(int)));
-    else
-        JF_HIP(e, h2d(e, &e->d_state[e->cur][src].count, &zero, sizeof(int)));
+    for (int s = 0; s < e->S; s++) {  // the source, and with a root its followers: they follow the new input
+        if (s != src && root_of(e, s) != src) continue;
+        e->h_sigs[s] = rec;
+        JF_HIP(e, h2d(e, e->d_sigs + s, &e->h_sigs[s], sizeof(SrcSignal)));
+        if (e->rv_P > 0)  // the play position of the dry signal lives in the reverb stage
+            JF_HIP(e, h2d(e, e->d_rv_count[e->cur] + s, &zero, sizeof(int)));
+        else
+            JF_HIP(e, h2d(e, &e->d_state[e->cur][s].count, &zero, sizeof(int)));
+    }
+    return live_refresh(e);  // (the real-time kernel's records follow)
+}
+
+// ---- shared inputs (jf_engine::root) -------------------------------------------------------------------
+// After the share groups changed: the plan (host_share_plan) on the device and room for its spectra.  Uploaded here, when it
+// changes, never per run.  The engine's stream is idle.
+static int share_refresh(jf_engine *e) {
+    if (e->root.empty()) return JF_OK;
+    const size_t S = (size_t)e->S;
+    std::vector<int> xslot(S), seg(S / 2 + 2), list(S);
+    const int n = host_share_plan(e->S, e->root.data(), xslot.data(), seg.data(), list.data());
+    e->n_followers = 0;
+    for (int s = 0; s < e->S; s++) e->n_followers += e->root[s] != s;
+    e->n_slots = 0;  // (whatever fails below leaves the engine on the aliases alone)
+    if (n == 0) return JF_OK;
+    if (!e->d_xslot) JF_HIP(e, e->d_xslot.alloc(S));
+    if (!e->d_share_seg) JF_HIP(e, e->d_share_seg.alloc(S / 2 + 2));
+    if (!e->d_share_list) JF_HIP(e, e->d_share_list.alloc(S));
+    if (n > e->xspec_slots) {
+        e->d_xspec.reset();  // (before the larger one is allocated: the two never exist side by side)
+        e->xspec_slots = 0;
+        JF_HIP(e, e->d_xspec.alloc((size_t)e->maxK * (size_t)n * (kN / 2)));
+        e->xspec_slots = n;
+    }
+    JF_HIP(e, h2d(e, e->d_xslot, xslot.data(), sizeof(int) * S));
+    JF_HIP(e, h2d(e, e->d_share_seg, seg.data(), sizeof(int) * ((size_t)n + 1)));
+    JF_HIP(e, h2d(e, e->d_share_list, list.data(), sizeof(int) * (size_t)seg[n]));
+    e->n_slots = n;
     return JF_OK;
 }
+
+static bool has_followers(const jf_engine *e, int src) {
+    for (int s = 0; s < e->S && !e->root.empty(); s++)
+        if (s != src && e->root[s] == src) return true;
+    return false;
+}
+
+int jf_source_share_input(jf_engine *e, int src, int of) {
+    return jf_guard([&]() -> int {
+    DeviceGuard bind(e);
+    if (!e) return JF_ERR_ARG;
+    if (!valid_src(e, src) || of >= e->S) return fail(e, JF_ERR_ARG, "bad source index");
+    if (e->in_flight) return fail(e, JF_ERR_STATE, "a block is in flight");
+    if (of < 0 || of == src) {  // detach: independent again, as jf_source_set_signal(e, src, NULL, 0) leaves a source
+        if (root_of(e, src) == src) return JF_OK;  // follows nobody (a root with followers included): stays as it is
+        JF_HIP(e, hipStreamSynchronize(e->stream));
+        e->root[src] = src;
+        const int rc = share_refresh(e);
+        return rc ? rc : swap_signal(e, src, DevBuf<float>(), e->N, false);
+    }
+    if (has_followers(e, src)) return fail(e, JF_ERR_STATE, "the source has followers of its own (detach them first)");
+    if (e->rv_P > 0)
+        return fail(e, JF_ERR_STATE, "shared inputs are not offered while a reverb response is set (the reverb keeps per-source state)");
+    const int r = root_of(e, of);  // a follower stands for its root
+    if (root_of(e, src) == r) return JF_OK;
+    // as reset_sources: descriptors prepared ahead are discarded, nothing is left in flight
+    {
+        const int rc = rv_ahead_discard(e);
+        if (rc) return rc;
+    }
+    JF_HIP(e, hipStreamSynchronize(e->stream));
+    quiesce_side(e);
+    e->ahead.valid = false;
+    if (e->root.empty()) {
+        e->root.resize((size_t)e->S);
+        for (int s = 0; s < e->S; s++) e->root[s] = s;
+    }
+    e->root[src] = r;
+    e->d_signal[src].reset();  // its own signal (or live buffer) is released: its record names the root's from now on
+    e->h_sigs[src] = e->h_sigs[r];
+    if (!e->live.empty()) e->live[src] = 0;  // only roots and unshared sources are live channels
+    JF_HIP(e, h2d(e, e->d_sigs + src, &e->h_sigs[src], sizeof(SrcSignal)));
+    // the root's window and play position at this moment; position, old position and bus stay the follower's
+    const int p = e->cur;
+    JF_HIP(e, hipMemcpyAsync(e->d_hist[p] + (size_t)src * e->N, e->d_hist[p] + (size_t)r * e->N, sizeof(float) * e->N,
+                             hipMemcpyDeviceToDevice, e->stream));
+    JF_HIP(e, hipMemcpyAsync(&e->d_state[p][src].count, &e->d_state[p][r].count, sizeof(int), hipMemcpyDeviceToDevice, e->stream));
+    JF_HIP(e, hipStreamSynchronize(e->stream));
+    // the plan and n_followers first: they follow root[] whatever the staging's allocation below does
+    int rc = share_refresh(e);
+    if (rc == JF_OK) rc = live_refresh(e);
+    return rc;
+    });
+}
+
+int jf_source_input_of(const jf_engine *e, int src) { return valid_src(e, src) ? root_of(e, src) : JF_ERR_ARG; }
 
 int jf_source_set_signal(jf_engine *e, int src, const float *mono, size_t n) {
     return jf_guard([&]() -> int {
     DeviceGuard bind(e);
     if (!valid_src(e, src) || (n && !mono) || n > 0x7fffffffu) return fail(e, JF_ERR_ARG, "bad source or signal");
+    if (root_of(e, src) != src) {  // on a follower: detached first, then the call acts on it alone
+        const int rc = jf_source_share_input(e, src, -1);
+        if (rc) return rc;
+    }
     // The device copy always has length >= PAD_LEN so that the kernel wraps the loop with
     // one conditional subtract: a shorter signal is stored as whole repetitions of itself
     // (the looped stream is identical), an empty one as the shared zero buffer.
@@ -811,6 +926,10 @@ int jf_source_set_live(jf_engine *e, int src, int live) {
     return jf_guard([&]() -> int {
     DeviceGuard bind(e);
     if (!valid_src(e, src)) return fail(e, JF_ERR_ARG, "bad source index");
+    if (root_of(e, src) != src) {  // on a follower: detached first (resident and silent), then the call acts on it alone
+        const int rc = jf_source_share_input(e, src, -1);
+        if (rc) return rc;
+    }
     const bool is_live = !e->live.empty() && e->live[src];
     if (is_live == (live != 0)) return JF_OK;
     if (!live) return jf_source_set_signal(e, src, nullptr, 0);  // resident again, and silent
@@ -946,7 +1065,17 @@ int jf_source_reset(jf_engine *e, int src) {
         if (rc) return rc;
     }
     JF_HIP(e, hipStreamSynchronize(e->stream));
-    return reset_sources(e, src);
+    const int rc = reset_sources(e, src);
+    if (rc) return rc;
+    // a member of a share group: the input state (window, play position) of EVERY member -- they stay equal --, the
+    // crossfade state of src alone
+    const int r = root_of(e, src), p = e->cur;
+    for (int s = 0; s < e->S && !e->root.empty(); s++) {
+        if (s == src || e->root[s] != r) continue;
+        JF_HIP(e, hipMemsetAsync(e->d_hist[p] + (size_t)s * e->N, 0, sizeof(float) * e->N, e->stream));
+        JF_HIP(e, hipMemsetAsync(&e->d_state[p][s].count, 0, sizeof(int), e->stream));
+    }
+    return JF_OK;
     });
 }
 

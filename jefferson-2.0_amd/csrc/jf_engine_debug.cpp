@@ -52,6 +52,23 @@ int jf_profile_read_reverb(jf_engine *e, double *reverb_ms) {
     });
 }
 
+int jf_profile_read_spectrum(jf_engine *e, double *spectrum_ms) {
+    return jf_guard([&]() -> int {
+    DeviceGuard bind(e);
+    if (!e || !spectrum_ms) return JF_ERR_ARG;
+    JF_HIP(e, hipStreamSynchronize(e->stream));
+    double r = 0;
+    for (size_t i = 0; e->profiling >= 2 && i < e->ev_used && i < e->ev_spec_on.size() && i < e->ev_spec.size(); i++) {
+        if (!e->ev_spec_on[i]) continue;
+        float ms = 0;
+        JF_HIP(e, hipEventElapsedTime(&ms, e->ev_spec[i].a, e->ev_spec[i].b));
+        r += ms;
+    }
+    *spectrum_ms = r;
+    return JF_OK;
+    });
+}
+
 int jf_debug_set_reverb_side_workgroups(jf_engine *e, int workgroups) {
     if (!e || workgroups < 8 || workgroups > 65536) return JF_ERR_ARG;
     e->rv_side_wgs = workgroups;
@@ -70,6 +87,15 @@ int jf_debug_bus_plan(int n_sources, const int *bus, int n_buses, const int *row
         for (int s = 0; s < n_sources; s++)
             if (bus[s] < 0 || bus[s] >= n_buses) return JF_ERR_ARG;
     return host_bus_plan(n_sources, bus, n_buses, row_key, pinned_group, n_items, pad_len, order, list, seg);
+    });
+}
+
+int jf_debug_share_plan(int n_sources, const int *root, int *xslot, int *seg, int *list) {
+    return jf_guard([&]() -> int {
+    if (n_sources <= 0 || !root) return JF_ERR_ARG;
+    for (int s = 0; s < n_sources; s++)
+        if (root[s] < 0 || root[s] >= n_sources || root[root[s]] != root[s]) return JF_ERR_ARG;
+    return host_share_plan(n_sources, root, xslot, seg, list);
     });
 }
 
@@ -427,7 +453,8 @@ const char *jf_debug_last_kernels(jf_engine *e) {
             }
         }
         else if (e->N != kN) k += "fused2048_kernel<" + nb + ">" + mix_name;
-        else k += std::string(e->last_group > 1 ? "fused_pair_kernel<" : "fused_block_kernel<") + nb +
+        else k += (e->last_shared ? "shared_spectrum_kernel<" + nb + ">;" : std::string()) +
+                  (e->last_group > 1 ? "fused_pair_kernel<" : "fused_block_kernel<") + nb + (e->last_shared ? ",shared" : "") +
                   (e->last_fused_prep ? ">+prep" : ">") + (e->last_mix_prep ? ";mix_prep_kernel" : mix_name);
         e->kernels = k;
         return e->kernels.c_str();

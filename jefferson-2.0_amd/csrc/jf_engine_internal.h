@@ -41,6 +41,7 @@ hipError_t launch_interp_debug(const RingTable &rt, const float *d_ele, const fl
 hipError_t launch_prep(const RingTable &rt, int mode, const float *d_pos, const SrcState *d_st, ItemDesc *d_desc,
                        int S, int K, int canon, int nc, hipStream_t st);
 hipError_t launch_fused(const FusedParams &P, int max_wgs, hipStream_t st);
+hipError_t launch_shared_spectrum(const FusedParams &P, hipStream_t st);
 hipError_t fused_resident_workgroups(int nb, int kind, int *out);
 hipError_t launch_stage_debug(const RingTable &rt, int mode, const float *d_pos, const float *d_win, int n,
                               const float4 *d_htab, const float2 *d_tw, float2 *d_dist, float2 *d_spec,
@@ -252,7 +253,8 @@ struct jf_engine : ReverbSetup {
     // block (Audio.cu:101,104)
     std::atomic<int> mode{0};  // 0 = FD_COMPLEX, 1 = FD_BASIC
     std::atomic<int> paused{0};
-    int resident_wgs[3] = {0, 0, 0};  // persistent-grid size of the per-source / the pair / the pair-with-rows kernel on this device
+    // persistent-grid size of the per-source / the pair / the pair-with-rows kernel on this device; [3..5]: of their SHARED instantiations
+    int resident_wgs[6] = {0, 0, 0, 0, 0, 0};
     int grid_limit = 0;            // > 0: tests shrink the grid so that waves loop over several units
     float last_peak = 0.0f;        // max |sample| of the last block handed out (Audio.cu:111-113 clip alert)
 
@@ -280,6 +282,22 @@ struct jf_engine : ReverbSetup {
     size_t in_cap = 0;               // floats h_in holds
     bool last_ingest = false;        // the last call launched live_ingest_kernel (jf_debug_last_kernels)
 
+    // SHARED INPUTS (jf_source_share_input).  A follower plays its root's input: its record in d_sigs (and in
+    // d_sigs_rt) is a copy of the root's, its window and play position were copied from the root's when the share was made
+    // and every kernel advances them alike ever since.  That alone meets the contract (the real-time kernel, PAD_LEN 2048
+    // and the reverb-free batch path all run followers as aliases); the batch path at PAD_LEN 1024 also forms the forward
+    // transform of a group's window ONCE per block (shared_spectrum_kernel into d_xspec) for the SHARED instantiations of the
+    // fused kernels to read.  Nothing below exists in an engine in which no source ever followed another.
+    std::vector<int> root;           // [S] the source whose input s plays (s itself: unshared, or a root); empty: never shared
+    int n_followers = 0;             // sources with root[s] != s
+    int n_slots = 0;                 // spectrum slots of the plan on the device (host_share_plan): groups of >= 2 members
+    DevBuf<int> d_xslot;             // [S] slot of every source, -1: none
+    DevBuf<int> d_share_seg;         // [S / 2 + 2] offsets of the slots' member lists
+    DevBuf<int> d_share_list;        // [S] the members, root first
+    DevBuf<float2> d_xspec;          // [maxK][n_slots][512], grown when a plan has more slots than it holds
+    int xspec_slots = 0;             // slots d_xspec has room for
+    bool last_shared = false;        // the last batch run took the shared path (jf_debug_last_kernels)
+
     std::mutex pos_mu;  // setters may come from another thread (graphics.cu:378)
     std::vector<HostPos> pos;
 
@@ -304,6 +322,8 @@ struct jf_engine : ReverbSetup {
     long profile_calls = 0;
     bool timed_now = false;    // this batch run carries event records
     std::vector<EventPair> ev_prep, ev_fused, ev_mix, ev_reverb;
+    std::vector<EventPair> ev_spec;   // profiling 2: around shared_spectrum_kernel (inside the fused kernel's pair)
+    std::vector<char> ev_spec_on;     // ... of the timed runs that launched it (jf_profile_read_spectrum)
     size_t ev_used = 0;
 
     // convolution reverb stage (jf_reverb.hip): its buffers and dimensions are the base ReverbSetup, what it advances is
@@ -385,6 +405,7 @@ inline int fail(jf_engine *e, int code, const std::string &msg) {
     } while (0)
 
 inline bool valid_src(const jf_engine *e, int s) { return e && s >= 0 && s < e->S; }
+inline int root_of(const jf_engine *e, int s) { return e->root.empty() ? s : e->root[s]; }  // jf_engine::root
 
 // Elevations the setters take: where the reference's rule names two measured rings, (-50, 90] (SoundSource.cu:67-68 with
 // the table of hrtf_signals.cu:7); with a grid of its own the engine clamps to the grid's first and last ring: [-90, 90].

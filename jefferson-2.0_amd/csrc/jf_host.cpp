@@ -611,4 +611,42 @@ int host_bus_plan(int S, const int *bus, int n_buses, const int *key, int pinned
     return G;
 }
 
+// ---- shared inputs: which forward transforms a run forms once ------------------------------------------------------------
+// root[s]: the source whose input s plays (itself: unshared or a root; roots are their own root).  A group = a root and its
+// followers.  Groups of two or more members get a spectrum slot each, numbered in the order of their roots; xslot[s] is the
+// slot of s's group, -1 for everyone else; list / seg are the slots' member lists in CSR form (seg[n_slots + 1] offsets,
+// list[seg[n_slots]] members): the root first, its followers behind it in ascending order.  xslot[S], seg[<= S / 2 + 1] and
+// list[<= S] are written where given.  Returns the number of slots.
+int host_share_plan(int S, const int *root, int *xslot, int *seg, int *list) {
+    std::vector<int> members((size_t)S, 0), slot_of((size_t)S, -1);
+    for (int s = 0; s < S; s++) members[root[s]]++;
+    int n_slots = 0, at = 0;
+    std::vector<int> first;  // where each slot's list begins
+    for (int r = 0; r < S; r++)
+        if (members[r] >= 2 && root[r] == r) {
+            slot_of[r] = n_slots++;
+            first.push_back(at);
+            at += members[r];
+        }
+    if (seg) {
+        std::copy(first.begin(), first.end(), seg);
+        seg[n_slots] = at;
+    }
+    if (list) {
+        std::vector<int> fill = first;
+        for (int k = 0; k < n_slots; k++) fill[k]++;  // (slot k's first entry is its root)
+        for (int s = 0; s < S; s++) {
+            const int k = slot_of[root[s]];
+            if (k < 0) continue;
+            if (root[s] == s)
+                list[first[k]] = s;
+            else
+                list[fill[k]++] = s;
+        }
+    }
+    if (xslot)
+        for (int s = 0; s < S; s++) xslot[s] = slot_of[root[s]];
+    return n_slots;
+}
+
 }  // namespace jf

@@ -61,6 +61,9 @@ ReverbSchedule host_reverb_schedule(long long j0, int K, int M, long long fut_m)
 int host_source_group(int S, int pinned, long long n_items, int pad_len);
 int host_bus_plan(int S, const int *bus, int n_buses, const int *key, int pinned, long long n_items, int pad_len, int *order,
                   int *list, int *seg);
+// Shared inputs (include/jefferson_debug.h: jf_debug_share_plan): the spectrum slots of the share groups with two or more
+// members and their member lists.  No GPU state.  root[] is valid: 0 <= root[s] < S and root[root[s]] == root[s].
+int host_share_plan(int S, const int *root, int *xslot, int *seg, int *list);
 
 }  // namespace jf
 

@@ -604,6 +604,29 @@ JF_DEV void item_gather(const FusedParams &P, int b, int s, int lane, float2 (&z
     L_out = L;
 }
 
+// What the last block of a call leaves of a source's counters: the play position behind the call's K blocks and the position
+// the block was rendered at (the next block's old position).  One lane writes the record.
+JF_DEV void item_state_out(const FusedParams &P, const float *pos_rec, int s, int count0, int L, int B) {
+    SrcState st;
+    st.count = (int)(((long long)count0 + (long long)P.K * B) % L);
+    const float *pp = pos_rec;
+    st.old_ele = pp[0];
+    st.old_azi = pp[1];
+    st.pad = 0;
+    P.st_out[s] = st;
+}
+
+// xd[q] = X[k] D[k], k = lane + 64 q, from the spectrum as rfft1024_wave leaves it (lane 0: bins 0 and 512, both real, travel
+// as the halves of X[0] and are scaled one by one).  The ONE place this product is written: an item that transformed its own
+// window (item_finish) and one that read a shared spectrum (item_front_shared) form the same bits.  A macro, not a function
+// over the arrays: as a function (inlined) it cost the per-source and the real-time kernels four vector registers each.
+#define JF_TIMES_DISTANCE(X, dq, sinv, d512x, lane, xd)                            \
+    do {                                                                           \
+        _Pragma("unroll") for (int q = 0; q < 8; q++) xd[q] = cmul_pk(X[q], dq[q]); \
+        const float2 x0 = make_float2(X[0].x * sinv, X[0].y * d512x);              \
+        xd[0] = lane == 0 ? x0 : xd[0];                                            \
+    } while (0)
+
 // Second part: write-back of the window and counters at the last block of a call, forward FFT, distance factor.
 template <int NOUT, bool D_EARLY>
 JF_DEV bool item_finish(const FusedParams &P, const ItemDesc *dp, const float *pos_rec, int b, int s, float2 *buf,
@@ -627,15 +650,7 @@ JF_DEV bool item_finish(const FusedParams &P, const ItemDesc *dp, const float *p
         float *ho = P.hist_out + (size_t)s * kN;
 #pragma unroll
         for (int r = 0; r < 8; r++) *reinterpret_cast<float2 *>(ho + 2 * (lane + 64 * r)) = z[r];
-        if (lane == 0) {
-            SrcState st;
-            st.count = (int)(((long long)count0 + (long long)P.K * B) % L);
-            const float *pp = pos_rec;
-            st.old_ele = pp[0];
-            st.old_azi = pp[1];
-            st.pad = 0;
-            P.st_out[s] = st;
-        }
+        if (lane == 0) item_state_out(P, pos_rec, s, count0, L, B);
     }
 
     if (n_new <= 0) return false;
@@ -643,10 +658,49 @@ JF_DEV bool item_finish(const FusedParams &P, const ItemDesc *dp, const float *p
     float2 X[8];
     rfft1024_wave(z, X, buf, s_tw, lane);
     if (!D_EARLY) distance_factors(c_hi, c_lo, sinv, lane, dq, d512x, s_tw);
+    JF_TIMES_DISTANCE(X, dq, sinv, d512x, lane, xd);
+    return true;
+}
+
+// ---- shared inputs: one forward transform per (block, share group) ------------------------------------------------------
+// A slot of xspec (FusedParams): 256 float4, entry 64 j + lane = (X[2 j], X[2 j + 1]) of that lane -- four 16-byte accesses
+// per lane, each a contiguous 1 KB line of the wave.
+JF_DEV size_t xspec_entry(const FusedParams &P, int b, int slot, int lane) {
+    return ((size_t)b * P.n_slots + slot) * 256 + lane;
+}
+
+// The front half of an item whose source follows a shared input (xslot[s] = slot >= 0, wave-uniform): no gather, no
+// transform -- X comes from the slot shared_spectrum_kernel filled for this block, the distance factors and the product are
+// the item's own (JF_TIMES_DISTANCE), and so are the counters it leaves at the last block of a call; the window is left to
+// every member of the group by shared_spectrum_kernel.  False if the item is silent, as item_finish.
+template <int NOUT, bool D_EARLY>
+JF_DEV bool item_front_shared(const FusedParams &P, const ItemDesc *dp, const float *pos_rec, int b, int s, int slot,
+                              const float2 *s_tw, int lane, float2 (&xd)[8]) {
+    constexpr int B = 64 * NOUT;
+    const int n_new = dp->n_new;
+    const unsigned c_hi = (unsigned)(dp->c_fix >> 32), c_lo = (unsigned)dp->c_fix;
+    const float sinv = dp->inv_frac * (1.0f / 2048.0f);
+    if (b == P.K - 1 && lane == 0)
+        item_state_out(P, pos_rec, s, as_const(P.st_in + s)->count, as_const(P.sigs + s)->length, B);
+    if (n_new <= 0) return false;
+    const float4 *xp = reinterpret_cast<const float4 *>(P.xspec) + xspec_entry(P, b, slot, lane);
+    float4 x4[4];
 #pragma unroll
-    for (int q = 0; q < 8; q++) xd[q] = cmul_pk(X[q], dq[q]);
-    const float2 x0 = make_float2(X[0].x * sinv, X[0].y * d512x);
-    xd[0] = lane == 0 ? x0 : xd[0];
+    for (int j = 0; j < 4; j++) x4[j] = xp[64 * j];
+    float2 dq[8];
+    float d512x;
+    if (D_EARLY) {  // while the spectrum's loads are in flight
+        distance_factors(c_hi, c_lo, sinv, lane, dq, d512x, s_tw);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    float2 X[8];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        X[2 * j] = make_float2(x4[j].x, x4[j].y);
+        X[2 * j + 1] = make_float2(x4[j].z, x4[j].w);
+    }
+    if (!D_EARLY) distance_factors(c_hi, c_lo, sinv, lane, dq, d512x, s_tw);
+    JF_TIMES_DISTANCE(X, dq, sinv, d512x, lane, xd);
     return true;
 }
 
@@ -663,7 +717,8 @@ JF_DEV bool item_front(const FusedParams &P, const ItemDesc *dp, const float *po
 // crossfaded stereo frames, which are ADDED to acc (B/64 frames per lane: frame i + 16 (NOUT a + j),
 // lane = 4 i + a).  dp: this item's descriptor (global memory in the batch kernel, LDS in the
 // real-time kernel); pos_rec: its latched position record.  buf: this wave's LDS; s_tw: twiddle pack.
-template <int NOUT>
+// SHARED: the launch has shared spectra (FusedParams::xslot); a source without a slot takes the front half above unchanged.
+template <int NOUT, bool SHARED = false>
 JF_DEV void spatialise_item(const FusedParams &P, const ItemDesc *dp, const float *pos_rec, int b, int s,
                             float2 *buf, const float2 *s_tw, int lane, float2 (&acc)[NOUT]) {
     constexpr int B = 64 * NOUT;
@@ -671,7 +726,14 @@ JF_DEV void spatialise_item(const FusedParams &P, const ItemDesc *dp, const floa
     const int n_new = dp->n_new;
     const int n_old = dp->n_old;
     float2 xd[8];
-    if (!item_front<NOUT, true>(P, dp, pos_rec, b, s, buf, s_tw, opaque(lane), xd)) return;
+    if constexpr (SHARED) {
+        const int slot = as_const(P.xslot + s)[0];  // wave-uniform: a scalar load
+        if (slot >= 0 ? !item_front_shared<NOUT, true>(P, dp, pos_rec, b, s, slot, s_tw, opaque(lane), xd)
+                      : !item_front<NOUT, true>(P, dp, pos_rec, b, s, buf, s_tw, opaque(lane), xd))
+            return;
+    } else {
+        if (!item_front<NOUT, true>(P, dp, pos_rec, b, s, buf, s_tw, opaque(lane), xd)) return;
+    }
 
     // ---- filter set(s) + inverse + crossfade (GPUSoundSource.cu:351-381)
     float2 res[NOUT];
@@ -700,7 +762,7 @@ JF_DEV void spatialise_item(const FusedParams &P, const ItemDesc *dp, const floa
     }
 }
 
-template <int NOUT>  // B / 64
+template <int NOUT, bool SHARED = false>  // B / 64; the launch follows a shared_spectrum_kernel (item_front_shared)
 #if JF_MIN_WAVES > 0
 #define JF_FUSED_BOUNDS __launch_bounds__(64 * kWavesPerWg, JF_MIN_WAVES)
 #else
@@ -746,12 +808,54 @@ __global__ JF_FUSED_BOUNDS void fused_block_kernel(const FusedParams P) {
             }
             const int item = b * P.S + s0 + g;
             const ItemDesc dl = load_desc(P.desc + item);  // scalar loads
-            spatialise_item<NOUT>(P, &dl, P.pos + (size_t)item * 5, b, s0 + g, buf, s_tw, lane, acc);
+            spatialise_item<NOUT, SHARED>(P, &dl, P.pos + (size_t)item * 5, b, s0 + g, buf, s_tw, lane, acc);
         }
         float2 *out = reinterpret_cast<float2 *>(P.partial) + ((size_t)b * SG + sg) * B;
 #pragma unroll
         for (int j = 0; j < NOUT; j++) out[i + 16 * (NOUT * a + j)] = acc[j];
     }
+}
+
+// One wavefront per (block b, spectrum slot): the window of the slot's share group, gathered from the group's root by the
+// fused kernels' own item_gather and transformed by their rfft1024_wave -- the same device functions, so the spectrum carries
+// the bits every member would have formed -- and stored as the transform leaves it (still twice the spectrum, lane 0's bins
+// 0 and 512 packed; layout: xspec_entry).  At the last block of a call the window goes to hist_out of EVERY member (the
+// members' items never hold it); their counters are their items' business.  Launched ahead of the SHARED instantiation of
+// a fused kernel on the same stream; consecutive waves take consecutive blocks of one slot (their windows overlap).
+constexpr int kSpecWaves = 4;
+constexpr int kSpecWork = 576;  // float2: a wave's work space for rfft1024_wave
+template <int NOUT>
+__global__ __launch_bounds__(64 * kSpecWaves) void shared_spectrum_kernel(const FusedParams P) {
+    __shared__ float2 s_tw[kTwPack];
+    __shared__ float2 s_buf[kSpecWaves * kSpecWork];
+    const int tid = threadIdx.x;
+    for (int j = tid; j < kTwPack; j += 64 * kSpecWaves) s_tw[j] = P.tw[j];
+    __syncthreads();
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int item = blockIdx.x * kSpecWaves + wave;
+    if (item >= P.K * P.n_slots) return;  // (no barrier behind this point)
+    const int slot = item / P.K;
+    const int b = item - slot * P.K;
+    const int JF_CONST_AS *seg = as_const(P.share_seg + slot);
+    const int m0 = seg[0], m1 = seg[1];
+    const int JF_CONST_AS *members = as_const(P.share_list);
+    float2 z[8];
+    int count0, L;
+    item_gather<NOUT>(P, b, members[m0], lane, z, count0, L);  // the root is the first of its list
+    if (b == P.K - 1) {
+#pragma unroll 1
+        for (int m = m0; m < m1; m++) {  // wave-uniform list
+            float *ho = P.hist_out + (size_t)members[m] * kN;
+#pragma unroll
+            for (int r = 0; r < 8; r++) *reinterpret_cast<float2 *>(ho + 2 * (lane + 64 * r)) = z[r];
+        }
+    }
+    float2 X[8];
+    rfft1024_wave(z, X, s_buf + wave * kSpecWork, s_tw, lane);
+    float4 *xp = reinterpret_cast<float4 *>(P.xspec) + xspec_entry(P, b, slot, lane);
+#pragma unroll
+    for (int j = 0; j < 4; j++) xp[64 * j] = make_float4(X[2 * j].x, X[2 * j].y, X[2 * j + 1].x, X[2 * j + 1].y);
 }
 
 // ------------------------------------------------------------- pair kernel --
@@ -971,7 +1075,9 @@ JF_DEV void prep_body(const RingTable &rt, int mode, const float *__restrict__ p
 // ROWS: the instantiation for launches whose descriptors may carry pre-interpolated rows (ItemDesc flags bit 2); the other
 // one does not contain that path at all (its presence alone costs the per-block weighting path registers and ~4 % more
 // instructions per source-block: profiles/r04/interp_table.md).
-template <int NOUT, bool ROWS>
+// SHARED: the instantiation for launches behind a shared_spectrum_kernel: the owner of a source with a spectrum slot reads
+// X there instead of gathering and transforming (item_front_shared); the hand-offs are where they are without.
+template <int NOUT, bool ROWS, bool SHARED = false>
 __global__ JF_FUSED_BOUNDS void fused_pair_kernel(const FusedParams Pin) {
     __shared__ float2 s_tw[kTwPack];
     __shared__ float2 s_pair[kPairsPerWg * kPairLds];
@@ -997,8 +1103,9 @@ __global__ JF_FUSED_BOUNDS void fused_pair_kernel(const FusedParams Pin) {
         P.S = q->S, P.K = q->K, P.B = q->B, P.G = q->G, P.mode = q->mode, P.order = q->order, P.err = q->err;
         P.n_pair_wgs = q->n_pair_wgs, P.prep_pos = q->prep_pos, P.prep_desc = q->prep_desc, P.prep_K = q->prep_K;
         P.prep_canon = q->prep_canon;
+        P.xspec = q->xspec, P.xslot = q->xslot, P.share_seg = q->share_seg, P.share_list = q->share_list, P.n_slots = q->n_slots;
         // (P.rt is not reloaded: nothing behind a reload reads it -- the workgroups that build descriptors take Pin.rt)
-        static_assert(sizeof(FusedParams) == 10 * 8 + 5 * 4 + 4 + 2 * 8 + 4 + 4 + 2 * 8 + 2 * 4 + sizeof(RingTable),
+        static_assert(sizeof(FusedParams) == 10 * 8 + 5 * 4 + 4 + 2 * 8 + 4 * 8 + 2 * 4 + 2 * 8 + 2 * 4 + sizeof(RingTable),
                       "a field was added to FusedParams: reload it here too");
     };
     if ((int)blockIdx.x >= Pin.n_pair_wgs) {
@@ -1176,12 +1283,20 @@ __global__ JF_FUSED_BOUNDS void fused_pair_kernel(const FusedParams Pin) {
             const int item = b * P.S + src;
             // the loads of my source's window first; the partner's previous source is filtered while they are in
             // flight (his hand-off has been waiting for a whole source), then my source's transform and filter
-            float2 z[8];
-            int count0, L;
-            item_gather<NOUT>(P, b, src, opaque(lane), z, count0, L);
-            JF_EXP_PHASE(0);  // own source: descriptor and signal records, window requests
             float2 xd[8];
-            if (item_finish<NOUT, false>(P, dp, P.pos + (size_t)item * 5, b, src, buf, s_tw, opaque(lane), z, count0, L, xd)) {
+            bool audible;
+            int slot = -1;
+            if constexpr (SHARED) slot = as_const(P.xslot + src)[0];  // wave-uniform: a scalar load
+            if (SHARED && slot >= 0) {
+                audible = item_front_shared<NOUT, false>(P, dp, P.pos + (size_t)item * 5, b, src, slot, s_tw, opaque(lane), xd);
+            } else {
+                float2 z[8];
+                int count0, L;
+                item_gather<NOUT>(P, b, src, opaque(lane), z, count0, L);
+                JF_EXP_PHASE(0);  // own source: descriptor and signal records, window requests
+                audible = item_finish<NOUT, false>(P, dp, P.pos + (size_t)item * 5, b, src, buf, s_tw, opaque(lane), z, count0, L, xd);
+            }
+            if (audible) {
                 // (requesting my filter's first row loads before this hand-off would hold X D, 16 registers, across
                 // them: it spills)
                 JF_EXP_PHASE(1);  // window arrival, forward transform, distance factors
@@ -2097,38 +2212,35 @@ hipError_t launch_prep(const RingTable &rt, int mode, const float *d_pos, const 
 // Resident workgroups of the fused kernel that a call with these parameters launches (per-source kernel for
 // G = 1, pair kernel otherwise), on the CURRENT device: CUs x workgroups per CU for this build's LDS and register
 // footprint.  The engine asks once per (kernel, block size) at creation and keeps the answer with its device.
-hipError_t fused_resident_workgroups(int nb, int kind /* 0 per-source kernel, 1 pair kernel, 2 pair kernel with rows */, int *out) {
+// kind: 0 per-source kernel, 1 pair kernel, 2 pair kernel with rows; + 3: their SHARED instantiations
+#define JF_FUSED_KERNEL_OF(NOUT, DO)                                                                                           \
+    switch (kind) {                                                                                                             \
+    case 0: DO((fused_block_kernel<NOUT, false>)); break;                                                                       \
+    case 1: DO((fused_pair_kernel<NOUT, false, false>)); break;                                                                 \
+    case 2: DO((fused_pair_kernel<NOUT, true, false>)); break;                                                                  \
+    case 3: DO((fused_block_kernel<NOUT, true>)); break;                                                                        \
+    case 4: DO((fused_pair_kernel<NOUT, false, true>)); break;                                                                  \
+    case 5: DO((fused_pair_kernel<NOUT, true, true>)); break;                                                                   \
+    default: return hipErrorInvalidValue;                                                                                       \
+    }
+#define JF_FUSED_KERNEL(DO)                                                                                                     \
+    switch (nb) {                                                                                                               \
+    case 1: JF_FUSED_KERNEL_OF(1, DO) break;                                                                                    \
+    case 2: JF_FUSED_KERNEL_OF(2, DO) break;                                                                                    \
+    case 3: JF_FUSED_KERNEL_OF(3, DO) break;                                                                                    \
+    case 4: JF_FUSED_KERNEL_OF(4, DO) break;                                                                                    \
+    default: return hipErrorInvalidValue;                                                                                       \
+    }
+hipError_t fused_resident_workgroups(int nb, int kind, int *out) {
     int dev = 0, per_cu = 0;
     hipDeviceProp_t prop;
     hipError_t q = hipGetDevice(&dev);
     if (q == hipSuccess) q = hipGetDeviceProperties(&prop, dev);
     if (q != hipSuccess) return q;
     const int threads = 64 * kWavesPerWg;
-    if (kind == 2) {
-        switch (nb) {
-        case 1: q = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fused_pair_kernel<1, true>, threads, 0); break;
-        case 2: q = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fused_pair_kernel<2, true>, threads, 0); break;
-        case 3: q = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fused_pair_kernel<3, true>, threads, 0); break;
-        case 4: q = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fused_pair_kernel<4, true>, threads, 0); break;
-        default: return hipErrorInvalidValue;
-        }
-    } else if (kind == 1) {
-        switch (nb) {
-        case 1: q = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fused_pair_kernel<1, false>, threads, 0); break;
-        case 2: q = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fused_pair_kernel<2, false>, threads, 0); break;
-        case 3: q = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fused_pair_kernel<3, false>, threads, 0); break;
-        case 4: q = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fused_pair_kernel<4, false>, threads, 0); break;
-        default: return hipErrorInvalidValue;
-        }
-    } else {
-        switch (nb) {
-        case 1: q = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fused_block_kernel<1>, threads, 0); break;
-        case 2: q = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fused_block_kernel<2>, threads, 0); break;
-        case 3: q = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fused_block_kernel<3>, threads, 0); break;
-        case 4: q = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fused_block_kernel<4>, threads, 0); break;
-        default: return hipErrorInvalidValue;
-        }
-    }
+#define JF_OCCUPANCY(KERNEL) q = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, KERNEL, threads, 0)
+    JF_FUSED_KERNEL(JF_OCCUPANCY)
+#undef JF_OCCUPANCY
     if (q != hipSuccess) return q;
     if (per_cu < 1) per_cu = 1;
     *out = prop.multiProcessorCount * per_cu;
@@ -2137,48 +2249,48 @@ hipError_t fused_resident_workgroups(int nb, int kind /* 0 per-source kernel, 1 
 
 // Persistent grid: at most max_wgs workgroups (what the GPU holds at once, fused_resident_workgroups; an
 // over-estimate only queues the surplus workgroups -- the unit loop is a plain stride, there is no grid
-// barrier, and every wave leaves the loop once unit >= n_units).
+// barrier, and every wave leaves the loop once unit >= n_units).  P.n_slots > 0: the SHARED instantiation (the caller has
+// launched shared_spectrum_kernel on the same stream).
 hipError_t launch_fused(const FusedParams &P, int max_wgs, hipStream_t st) {
     if (P.G <= 0 || P.S % P.G || max_wgs < 1) return hipErrorInvalidValue;
     const int n_items = P.K * (P.S / P.G);
     const int nb = P.B / 64;
     if (nb < 1 || nb > 4) return hipErrorInvalidValue;
+    if (P.n_slots > 0 && (!P.xspec || !P.xslot)) return hipErrorInvalidValue;
     const int per_wg = P.G > 1 ? kPairsPerWg : kWavesPerWg;  // units a workgroup works on at a time
     int wgs = (n_items + per_wg - 1) / per_wg;
     if (wgs > max_wgs) wgs = max_wgs;
     const dim3 block(64 * kWavesPerWg);
     // groups of sources are summed as spectra by wave pairs (two inverse transforms per group); single sources
     // keep the per-source kernel, whose blocks are the reference's per-source `intermediate`
+    FusedParams Q = P;
+    dim3 grid(wgs);
+    int kind = 0;
     if (P.G > 1) {
-        FusedParams Q = P;
         Q.n_pair_wgs = wgs;
         // + the workgroups that prepare the following window's descriptors (two lanes per item)
         const int n_prep = Q.prep_pos != nullptr ? (2 * Q.S * Q.prep_K + 64 * kWavesPerWg - 1) / (64 * kWavesPerWg) : 0;
-        const dim3 grid(wgs + n_prep);
-        const bool rows = (P.mode & kModeInterpRows) != 0;  // descriptors may name pre-interpolated rows
-        switch (P.B / 64) {
-        case 1: if (rows) hipLaunchKernelGGL((fused_pair_kernel<1, true>), grid, block, 0, st, Q);
-                else hipLaunchKernelGGL((fused_pair_kernel<1, false>), grid, block, 0, st, Q);
-                break;
-        case 2: if (rows) hipLaunchKernelGGL((fused_pair_kernel<2, true>), grid, block, 0, st, Q);
-                else hipLaunchKernelGGL((fused_pair_kernel<2, false>), grid, block, 0, st, Q);
-                break;
-        case 3: if (rows) hipLaunchKernelGGL((fused_pair_kernel<3, true>), grid, block, 0, st, Q);
-                else hipLaunchKernelGGL((fused_pair_kernel<3, false>), grid, block, 0, st, Q);
-                break;
-        case 4: if (rows) hipLaunchKernelGGL((fused_pair_kernel<4, true>), grid, block, 0, st, Q);
-                else hipLaunchKernelGGL((fused_pair_kernel<4, false>), grid, block, 0, st, Q);
-                break;
-        default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
+        grid = dim3(wgs + n_prep);
+        kind = (P.mode & kModeInterpRows) != 0 ? 2 : 1;  // descriptors may name pre-interpolated rows
     }
-    const dim3 grid(wgs);
+    if (P.n_slots > 0) kind += 3;
+#define JF_LAUNCH(KERNEL) hipLaunchKernelGGL(KERNEL, grid, block, 0, st, Q)
+    JF_FUSED_KERNEL(JF_LAUNCH)
+#undef JF_LAUNCH
+    return hipGetLastError();
+}
+#undef JF_FUSED_KERNEL
+#undef JF_FUSED_KERNEL_OF
+
+// The spectra of a SHARED launch (P as for launch_fused): P.K * P.n_slots wavefronts, kSpecWaves to the workgroup.
+hipError_t launch_shared_spectrum(const FusedParams &P, hipStream_t st) {
+    if (P.n_slots <= 0 || P.K <= 0 || !P.xspec || !P.share_seg || !P.share_list) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(((long long)P.K * P.n_slots + kSpecWaves - 1) / kSpecWaves)), block(64 * kSpecWaves);
     switch (P.B / 64) {
-    case 1: hipLaunchKernelGGL(fused_block_kernel<1>, grid, block, 0, st, P); break;
-    case 2: hipLaunchKernelGGL(fused_block_kernel<2>, grid, block, 0, st, P); break;
-    case 3: hipLaunchKernelGGL(fused_block_kernel<3>, grid, block, 0, st, P); break;
-    case 4: hipLaunchKernelGGL(fused_block_kernel<4>, grid, block, 0, st, P); break;
+    case 1: hipLaunchKernelGGL(shared_spectrum_kernel<1>, grid, block, 0, st, P); break;
+    case 2: hipLaunchKernelGGL(shared_spectrum_kernel<2>, grid, block, 0, st, P); break;
+    case 3: hipLaunchKernelGGL(shared_spectrum_kernel<3>, grid, block, 0, st, P); break;
+    case 4: hipLaunchKernelGGL(shared_spectrum_kernel<4>, grid, block, 0, st, P); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
