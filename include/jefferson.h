@@ -488,6 +488,60 @@ int jf_source_bus(const jf_engine *e, int src);
 int jf_source_share_input(jf_engine *e, int src, int of);
 int jf_source_input_of(const jf_engine *e, int src);
 
+/* ---- room sends: one stereo convolution reverb per output bus ------------------ */
+
+/*
+ * The reference's reverb sits on the INPUT: cudaFFT() convolves a source's mono signal with one mono response offline
+ * (cudaPart.cu:65-205), and jf_reverb_set_ir below does the same block by block -- one convolution per source.  A room as
+ * mixers and game engines build it is an AUXILIARY SEND instead: every source sends a scaled copy of its input to the room
+ * of its listener, the room is one stereo (binaural) response applied to the SUM of the sends, and the result is added to
+ * that listener's mix -- the reference's one stereo output (Audio.cu:26), after its mixing loop (Audio.cu:109-110).  Output
+ * buses are the listeners: the cost follows the number of buses, not of sources, and the stage never touches the spatialiser,
+ * so it works with live inputs, shared inputs, sets on arbitrary directions and PAD_LEN 2048.
+ *
+ * For bus b, block k of a call (B = frames_per_buffer), sample n, t = k B + n:
+ *   send_b[t]   = sum over the sources s on bus b, ascending s, of l_s[t] x_s[t]
+ *   wet_b,ear   = gain (send_b (*) ir_ear)     linear convolution over the engine's whole run, zero latency (tap 0 acts on
+ *                                              the same sample)
+ *   out_b[k][2 n + ear] = fl32(dry_b[k][2 n + ear] + wet_b,ear[t])
+ * x_s[t] is the sample the spatialiser's window takes in as NEW at that time (copyIncomingBlock, GPUSoundSource.cu:481-513):
+ * a resident signal at its play position with the loop's wrap, a live source's block of the call, a follower's root's input,
+ * zeros for a source without a signal.  dry_b is exactly what the engine renders without a room.  The send does not depend on
+ * the source's position or on the mode: a source at a position the rule cannot interpolate is silent in dry_b and still sends.
+ *
+ * l_s is the source's SEND LEVEL, 0 until jf_source_set_send says otherwise (negative levels are allowed).  A new level takes
+ * effect with the next processing call and is ramped over that call's first block, l_prev + (l_new - l_prev) (n + 1) / B;
+ * later blocks use l_new; after the call l_prev := l_new.  A source whose old and new level are 0 is not read at all.  A
+ * source that changes its bus sends to the new bus from that block on, without a fade (as for the dry path).
+ *
+ * jf_room_set_ir(e, ir_left, ir_right, n_ir, gain): n_ir taps per ear, at most JF_ROOM_MAX_TAPS; ir_right == NULL is a MONO
+ *   room: one response heard on both ears (one convolution, written twice); n_ir == 0 turns the room off and frees it.  There
+ *   is one room per engine, heard by every bus, with a delay line per bus.  The call waits for the engine's stream (between
+ *   blocks), clears the tail of every bus and -- unlike jf_reverb_set_ir -- does NOT reset the sources; the room starts
+ *   silent: every send ramps in from 0 over the next call's first block.
+ *   JF_ERR_ARG: n_ir > JF_ROOM_MAX_TAPS, a gain that is not finite, frames_per_buffer other than 64, 128 or 256;
+ *   JF_ERR_STATE: a block is in flight, or a jf_reverb_set_ir response is set (jf_reverb_set_ir in turn returns JF_ERR_STATE
+ *   while a room is set); JF_ERR_NOMEM: the delay lines do not fit.  jf_engine_set_buses returns JF_ERR_STATE while a room is
+ *   set (the delay lines are per bus: set the buses first).
+ * jf_room_taps: n_ir of the room in place, 0: off.
+ * jf_source_set_send: JF_ERR_ARG for a bad index or a level that is not finite, JF_ERR_STATE while a block is in flight.
+ * jf_source_send: the level last set; 0 for a bad index.
+ * On every refusal nothing changes and the stream continues bit for bit.
+ *
+ * Paused blocks are silence on every bus and the room does not advance: after the pause the tail continues as if those calls
+ * had not happened.  jf_source_reset leaves the room's tail alone (the tail is the bus's, not the source's).  An engine that
+ * never calls jf_room_set_ir allocates nothing for it and renders the same bits; with a room set, a bus nobody sends to is bit
+ * for bit the bus of the engine without the room, and the per-block calls go through the batch pipeline with one block (as
+ * with more than one bus).  The wet part is deterministic -- no atomics, one association -- and the same bits however a run
+ * is cut into calls.  DESIGN.md 4.13 has the stage and its cost.
+ * jefferson_group.h does not offer a room; jf_render and jf_ctest have no option for it.
+ */
+#define JF_ROOM_MAX_TAPS 262144
+int jf_room_set_ir(jf_engine *e, const float *ir_left, const float *ir_right, size_t n_ir, float gain);
+int jf_room_taps(const jf_engine *e); /* 0: off */
+int jf_source_set_send(jf_engine *e, int src, float level);
+float jf_source_send(const jf_engine *e, int src); /* the level last set; 0 for a bad index */
+
 /* ---- convolution reverb -------------------------------- */
 
 /*

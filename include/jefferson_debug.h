@@ -99,6 +99,17 @@ int jf_debug_set_rt_max_sources(jf_engine *e, int n);
 /* ';'-separated names of the kernels the last processing call launched, in launch order (bench.py labels its
  * roofline with them).  The string is owned by the engine and valid until the next call of this function. */
 const char *jf_debug_last_kernels(jf_engine *e);
+/* The room's wet contribution (jefferson.h: jf_room_set_ir) to the last run of the batch pipeline that ran it -- the last
+ * processing call, or the LAST CHUNK of a jf_process_batch[_in] of more than max_batch_blocks blocks, which runs in chunks of
+ * max_batch_blocks: out is [n_buses][n_blocks][2 * frames_per_buffer] float32, n_blocks at most that run's; its output is
+ * fl32(dry + wet) of exactly these values.  Waits for the engine's stream.  JF_ERR_STATE without a room or with more blocks
+ * than the run had.
+ * jf_debug_last_kernels names room_send_kernel, room_fft_kernel, room_mac_kernel (ahead of the spatialiser) and
+ * room_add_kernel (behind the mix) when they ran.
+ * Per-kernel timing (jf_profile_enable(e, 2)) has no event pair for the room: its send, transform and product kernels run
+ * between the prep pair and the fused pair and are counted in neither; room_add_kernel runs inside the mix pair and is counted
+ * as mix time.  Time an engine with a room against its twin without one (profiles/room/measure.py). */
+int jf_debug_room_wet(jf_engine *e, int n_blocks, float *out);
 /* G the last batch pipeline run used (1 = fused_block_kernel, > 1 = fused_pair_kernel). */
 int jf_debug_last_source_group(const jf_engine *e);
 /* Caps the persistent grid of the fused kernel at `workgroups` (0 = what the device holds): with a small cap every

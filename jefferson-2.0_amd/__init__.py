@@ -41,6 +41,7 @@ class JfHrtfGrid(C.Structure):
 
 JF_MAX_RINGS = 40
 JF_MAX_BUSES = 1024
+JF_ROOM_MAX_TAPS = 262144
 
 
 class JfGridLayout(C.Structure):
@@ -113,6 +114,11 @@ _SIGS = {
     "jf_source_share_input": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "jf_source_input_of": (C.c_int, [C.c_void_p, C.c_int]),
     "jf_debug_share_plan": (C.c_int, [C.c_int, _i, _i, _i, _i]),
+    "jf_room_set_ir": (C.c_int, [C.c_void_p, _f, _f, C.c_size_t, C.c_float]),
+    "jf_room_taps": (C.c_int, [C.c_void_p]),
+    "jf_source_set_send": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
+    "jf_source_send": (C.c_float, [C.c_void_p, C.c_int]),
+    "jf_debug_room_wet": (C.c_int, [C.c_void_p, C.c_int, _f]),
     "jf_submit_block_in": (C.c_int, [C.c_void_p, _f]),
     "jf_process_block_in": (C.c_int, [C.c_void_p, _f, _f]),
     "jf_callback_in": (C.c_int, [C.c_void_p, _f, _f]),
@@ -630,6 +636,33 @@ class Engine:
         if r < 0:
             raise JfError(r, "bad source index")
         return r
+
+    def set_room(self, ir_left, ir_right=None, gain=1.0):
+        """one stereo room per output bus (include/jefferson.h: jf_room_set_ir); ir_right None: a mono room; an empty
+        response turns the room off"""
+        left = np.ascontiguousarray(ir_left, np.float32).ravel()
+        right = None if ir_right is None else np.ascontiguousarray(ir_right, np.float32).ravel()
+        if right is not None and len(right) != len(left):
+            raise JfError(JF_ERR_ARG, "the two ears' responses differ in length")
+        self._chk(lib().jf_room_set_ir(self.h, _fp(left) if len(left) else None,
+                                       _fp(right) if right is not None and len(right) else None, len(left), gain))
+
+    @property
+    def room_taps(self):
+        return lib().jf_room_taps(self.h)
+
+    def set_send(self, s, level):
+        """source s sends level x its input to its bus's room, from the next processing call on (ramped over its first block)"""
+        self._chk(lib().jf_source_set_send(self.h, int(s), float(level)))
+
+    def send(self, s):
+        return float(lib().jf_source_send(self.h, int(s)))
+
+    def room_wet(self, n_blocks):
+        """the room's wet contribution to the last processing call, [n_buses][n_blocks][2B] (jefferson_debug.h)"""
+        out = np.zeros((self.n_buses, int(n_blocks), 2 * self.B), np.float32)
+        self._chk(lib().jf_debug_room_wet(self.h, int(n_blocks), _fp(out)))
+        return out
 
     def _out(self, *shape):
         """zeros of a call's output shape, behind a bus axis when the engine has more than one bus"""

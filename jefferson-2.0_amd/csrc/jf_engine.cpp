@@ -138,6 +138,10 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
         const int rc = run_reverb_stage(e, p, K);
         if (rc) return rc;
     }
+    if (e->room.P > 0) {  // the room's wet blocks of this call (jf_engine_room.cpp): they read the inputs, not the spatialiser
+        const int rc = run_room_stage(e, p, K);
+        if (rc) return rc;
+    }
     FusedParams P = fused_params(e, p, K, mode_now);
     P.tw = n1024 ? e->d_twpack : e->d_tw2048;
     P.desc = e->d_desc;
@@ -191,6 +195,10 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
                                   e->d_desc_ahead, e->S, K, canon, e->stream));
     else
         JF_HIP(e, launch_mix(e->d_partial, d_mix_out, e->S / G, K, e->B, e->stream));
+    if (e->room.P > 0) {
+        const int rc = run_room_add(e, K, d_mix_out);
+        if (rc) return rc;
+    }
     if (ahead_ok) {
         e->ahead.valid = true;
         e->ahead.first = first_block + K;
@@ -958,6 +966,7 @@ int jf_engine_set_buses(jf_engine *e, int n_buses) {
     if (n_buses < 1 || n_buses > JF_MAX_BUSES) return fail(e, JF_ERR_ARG, "n_buses must be 1 .. JF_MAX_BUSES");
     if (e->in_flight) return fail(e, JF_ERR_STATE, "a block is in flight");
     if (n_buses == e->n_buses) return JF_OK;
+    if (e->room.P > 0) return fail(e, JF_ERR_STATE, "a room is set: its delay lines are per bus (set the buses first, or turn the room off)");
     for (const int b : e->bus)
         if (b >= n_buses) return fail(e, JF_ERR_STATE, "a source sits on a bus that would disappear");
     {
@@ -1004,6 +1013,7 @@ int jf_source_set_bus(jf_engine *e, int src, int bus) {
     if ((e->bus.empty() ? 0 : e->bus[src]) == bus) return JF_OK;
     JF_HIP(e, hipStreamSynchronize(e->stream));
     e->bus[src] = bus;
+    e->room_dirty = true;    // the source sends to its new bus from the next block on
     e->ahead.valid = false;  // descriptors prepared ahead were laid out for the old order
     return form_order(e);
     });
@@ -1134,7 +1144,7 @@ static int submit_block(jf_engine *e, const float *in, bool interleaved) {
         e->own_mix_blocks = 0;  // (d_mix no longer holds the last jf_batch_run's blocks)
     } else {
         snapshot_positions(e, e->h_pos_pinned);
-        if (e->S <= e->rt_max_sources && !e->profiling && e->N == kN && e->n_buses == 1) {  // (PAD_LEN 2048, buses: the batch path with K = 1)
+        if (e->S <= e->rt_max_sources && !e->profiling && e->N == kN && e->n_buses == 1 && e->room.P == 0) {  // (PAD_LEN 2048, buses, a room: the batch path with K = 1)
             // few sources: ONE launch does descriptors, spatialisation and mix, reading the positions
             // from and writing the stereo block to pinned host memory -- no copies, one sync
             const int p = e->cur;

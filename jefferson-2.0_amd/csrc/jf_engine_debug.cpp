@@ -398,6 +398,8 @@ const char *jf_debug_last_kernels(jf_engine *e) {
         std::string k;
         if (e->last_ingest) k = "live_ingest_kernel;";
         if (!e->last_rt && !e->last_prep_skipped) k += "prep_kernel;";
+        const bool room = e->room.P > 0 && !e->last_rt && e->room.last_K > 0;  // (jf_engine_room.cpp)
+        if (room) k += "room_send_kernel<" + bs + ">;room_fft_kernel<" + bs + ">;room_mac_kernel<" + bs + "," + std::to_string(room_mac_waves(e->B)) + ">;";
         if (e->rv_P > 0) {
             if (e->stage.last_catchup) k += "reverb_fft_kernel<" + bs + ">@ring;";
             const ReverbPlan &pl = e->stage.last_plan;
@@ -456,6 +458,7 @@ const char *jf_debug_last_kernels(jf_engine *e) {
         else k += (e->last_shared ? "shared_spectrum_kernel<" + nb + ">;" : std::string()) +
                   (e->last_group > 1 ? "fused_pair_kernel<" : "fused_block_kernel<") + nb + (e->last_shared ? ",shared" : "") +
                   (e->last_fused_prep ? ">+prep" : ">") + (e->last_mix_prep ? ";mix_prep_kernel" : mix_name);
+        if (room) k += ";room_add_kernel";
         e->kernels = k;
         return e->kernels.c_str();
     } catch (...) {

@@ -1,11 +1,13 @@
 // jf_engine_internal.h -- what the translation units of the engine's host side share: the engine's state (struct jf_engine),
 // the owners of its device and pinned memory (DevBuf, PinnedBuf: whatever the engine or a call allocates is freed by a
 // destructor, never by hand), the kernels' launchers (jf_kernels.hip, jf_reverb.hip), the small helpers every ABI entry uses
-// (among them fused_params, the one place that fills FusedParams).  Three units since round 6:
+// (among them fused_params, the one place that fills FusedParams).  Its units:
 //   jf_engine.cpp         creation in named steps, the ONE batch pipeline (run_blocks: PAD_LEN 1024 and 2048), the per-block
 //                         calls, the one way to swap a source's signal: include/jefferson.h
 //   jf_engine_reverb.cpp  the convolution reverb's schedule (run_reverb_stage, the side stream, the stage launched ahead) and
 //                         jf_reverb_set_ir / jf_reverb_rms_gain
+//   jf_engine_room.cpp    the room stage's schedule (run_room_stage, run_room_add: an auxiliary send per output bus, jf_room.hip)
+//                         and jf_room_set_ir / jf_source_set_send
 //   jf_engine_debug.cpp   every entry point of include/jefferson_debug.h (taps, timing hooks, tuning switches, accessors)
 // Not part of any interface: nothing outside csrc/ includes this file.
 #ifndef JF_ENGINE_INTERNAL_H
@@ -31,6 +33,7 @@
 #include "../../include/jefferson_debug.h"
 #include "jf_device.h"
 #include "jf_host.h"
+#include "jf_room.h"
 
 namespace jf {
 hipError_t launch_table_build(const float *d_hrir, int n_rows, int taps, const float2 *d_tw, float4 *d_htab, hipStream_t st);
@@ -72,6 +75,10 @@ hipError_t launch_rfft2048_debug(const float *d_win, int n, const float2 *d_tw20
 // live input (jf_live.hip)
 hipError_t launch_live_ingest(const SrcSignal *d_sigs, const int *d_live_idx, const int *d_count, int count_stride,
                               const float *in, bool interleaved, int n_live, int n, int row_stride, hipStream_t st);
+// the room stage (jf_room.hip)
+hipError_t launch_room_stage(const RoomParams &P, hipStream_t st);
+hipError_t launch_room_add(float *d_mix, const float *d_wet, size_t n, hipStream_t st);
+int room_mac_waves(int B);
 }  // namespace jf
 
 using namespace jf;
@@ -164,6 +171,26 @@ struct RvProgress {
     std::string last_side;       // the side stream's kernels of the last call
     bool last_catchup = false;   // the last call began with the catch-up
     bool last_small_fft = true;  // ... and launched the small transforms' kernel
+};
+
+// The room stage as jf_room_set_ir set it up: buffers and dimensions, all empty / 0 while the room is off
+// (`= {}`).  Off while P == 0; nothing of it is allocated before the first jf_room_set_ir.
+struct RoomSetup {
+    int P = 0;                  // partitions of B taps
+    int Rg = 0;                 // slots of a bus's delay line: P + max_batch_blocks
+    int hstride = 0;            // float2 between the two responses' spectra
+    int n_ir = 0;
+    bool mono = false;          // one response, heard on both ears
+    int head = 0;               // slot the next block's spectrum goes to
+    int par = 0;                // which of d_prev holds the last send block
+    int last_K = 0;             // blocks the last call left in d_wet (0: none yet)
+    DevBuf<float2> d_hspec;     // [1 or 2][hstride]
+    DevBuf<float2> d_fdl;       // [n_buses][Rg][B]
+    DevBuf<float> d_send;       // [n_buses][maxK][B]
+    DevBuf<float> d_prev[2];    // [n_buses][B]
+    DevBuf<float> d_wet;        // [n_buses][maxK][2B]
+    DevBuf<int> d_seg, d_list;  // [n_buses + 1], [S]: the senders, bus by bus
+    DevBuf<float2> d_lv;        // [S] their (l_prev, l_new)
 };
 
 struct jf_engine : ReverbSetup {
@@ -297,6 +324,13 @@ struct jf_engine : ReverbSetup {
     DevBuf<float2> d_xspec;          // [maxK][n_slots][512], grown when a plan has more slots than it holds
     int xspec_slots = 0;             // slots d_xspec has room for
     bool last_shared = false;        // the last batch run took the shared path (jf_debug_last_kernels)
+
+    // ROOM SENDS (jf_room_set_ir, jf_source_set_send).  The levels are the sources' and outlive a room; the
+    // per-bus list of senders on the device is formed again by the first call after a level or a bus has changed.
+    RoomSetup room;
+    std::vector<float> send_new, send_prev;  // [S] l_new, l_prev (empty: no level was ever set, every one 0)
+    bool room_dirty = true;          // the device's list is not the one the levels and buses ask for
+    int room_senders = 0;            // entries of that list
 
     std::mutex pos_mu;  // setters may come from another thread (graphics.cu:378)
     std::vector<HostPos> pos;
@@ -516,6 +550,8 @@ JF_INTERNAL int submit_side(jf_engine *e);                 // jf_engine_reverb.c
 JF_INTERNAL int rv_ahead_discard(jf_engine *e);            // jf_engine_reverb.cpp
 JF_INTERNAL bool rv_ahead_possible(const jf_engine *e);    // jf_engine_reverb.cpp
 JF_INTERNAL void free_reverb(jf_engine *e);                // jf_engine_reverb.cpp
+JF_INTERNAL int run_room_stage(jf_engine *e, int p, int K);           // jf_engine_room.cpp: ahead of the spatialiser
+JF_INTERNAL int run_room_add(jf_engine *e, int K, float *d_mix_out);  // jf_engine_room.cpp: behind the mix
 JF_INTERNAL int ensure_interp_rows(jf_engine *e);
 JF_INTERNAL int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int first_block = -1);
 JF_INTERNAL int reset_sources(jf_engine *e, int src);

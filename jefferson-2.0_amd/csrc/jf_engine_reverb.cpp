@@ -289,6 +289,8 @@ int jf_reverb_set_ir(jf_engine *e, const float *ir, size_t n_ir, float gain) {
     if (!e || (n_ir && !ir) || n_ir > (size_t)1 << 26) return fail(e, JF_ERR_ARG, "bad impulse response");
     if (e->N != kN) return fail(e, JF_ERR_ARG, "the convolution reverb is not available at PAD_LEN 2048");
     if (e->in_flight) return fail(e, JF_ERR_STATE, "a per-block call is in flight");
+    if (n_ir && e->room.P > 0)  // (jf_room_set_ir)
+        return fail(e, JF_ERR_STATE, "the convolution reverb is not offered while a room is set");
     if (n_ir && e->n_followers > 0)  // (jf_source_share_input)
         return fail(e, JF_ERR_STATE, "the convolution reverb is not offered while a source follows another's input (it keeps per-source state)");
     {
