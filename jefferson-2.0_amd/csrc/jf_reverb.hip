@@ -134,6 +134,8 @@ __global__ __launch_bounds__(64 * kMacWaves) void reverb_mac_kernel(const Reverb
     if (slot < 0) slot += P.Rg;
 #pragma unroll 2
     for (int p = p_first; p < P.P; p += stride) {
+        // (not rv_load_bins, not a shared product: either moves which product of the imaginary part is rounded by itself
+        // -- at B = 64 the loads alone do -- and with it the last bit of the sums: profiles/rv_spectrum/README.md)
         float2 h[NB];
         const float2 *hp = hs + (size_t)p * B;
         if (NB == 2) {
@@ -592,12 +594,9 @@ __global__ __launch_bounds__(kBigThreads) void reverb_big_fft_kernel(const Rever
                 const int q = split_bin(tid, u);
                 const float2 zk = Z[rv_big_at(q)];
                 const float2 zm = Z[rv_big_at((B1 - q) & (B1 - 1))];
-                const float2 e = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
-                const float2 o = make_float2(0.5f * (zk.x - zm.x), 0.5f * (zk.y + zm.y));
-                const float2 wo = rv_mulc(o, wsplit[u]);
-                float2 x = make_float2(e.x + wo.y, e.y - wo.x);
+                float2 x = rv_split_bin(zk, zm, wsplit[u]);
                 if (q == 0) {
-                    x = make_float2(zk.x + zk.y, zk.x - zk.y);  // (X[0], X[B1]), both real
+                    x = rv_split_bin0(zk);
                     P.fdl1[(size_t)P.S * P.R1 * B1 + (size_t)s * P.R1 + slot] = x;  // compact copy of the packed pair
                 }
                 xo[u] = x;
@@ -1009,24 +1008,20 @@ __global__ __launch_bounds__(kBigThreads, JF_RV_BIG_IFFT_WGS) void reverb_big_if
                 y0.y += __shfl_xor(y0.y, m);
             }
         }
-        // Z[q] = E + j O with E = (Y[q] + conj Y[B1-q]) / 2, O = conj(W^q) (Y[q] - conj Y[B1-q]) / 2: the first pass's registers
+        // the spectrum untangled (rv_untangle_bin): the first pass's registers
         float2 v[1][8];
         auto untangle = [&](int r0, int r1) {
 #pragma unroll
             for (int r = 0; r < 8; r++) {
                 if (r < r0 || r >= r1) continue;
-                const float2 yk = in.yk[r], ym = in.ym[r];
-                const float2 e = make_float2(0.5f * (yk.x + ym.x), 0.5f * (yk.y - ym.y));
-                const float2 d = make_float2(0.5f * (yk.x - ym.x), 0.5f * (yk.y + ym.y));
-                const float2 o = rv_mul(d, wq[r]);
-                v[0][r] = make_float2(e.x - o.y, e.y + o.x);
+                v[0][r] = rv_untangle_bin(in.yk[r], in.ym[r], wq[r]);
             }
         };
         untangle(0, 4);
         __builtin_amdgcn_sched_barrier(0);  // (the second half's loads go into the registers the first half has freed)
         in.fetch_y(P, g, tid, 4, 8);
         untangle(4, 8);
-        if (tid == 0) v[0][0] = make_float2(0.5f * (y0.x + y0.y), 0.5f * (y0.x - y0.y));
+        if (tid == 0) v[0][0] = rv_untangle_bin0(y0);
         cfft_wg<B1, +1, kBigThreads, true>(v, s_buf, tw, s_w8, tid);  // (only z[m], m >= B1 / 2, is read below)
         {
             const float2 *zt = s_buf[0];
@@ -1086,12 +1081,8 @@ __global__ __launch_bounds__(kBigThreads) void reverb_big_ir_kernel(const float 
     const float2 *Z = s_buf[0];
     for (int q = tid; q < B1; q += kBigThreads) {
         const float2 zk = Z[rv_big_at(q)];
-        const float2 zm = Z[rv_big_at((B1 - q) & (B1 - 1))];
-        const float2 e = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
-        const float2 o = make_float2(0.5f * (zk.x - zm.x), 0.5f * (zk.y + zm.y));
-        const float2 wo = rv_mulc(o, tw1[q]);
-        float2 x = make_float2(e.x + wo.y, e.y - wo.x);
-        if (q == 0) x = make_float2(zk.x + zk.y, zk.x - zk.y);
+        float2 x = rv_split_bin(zk, Z[rv_big_at((B1 - q) & (B1 - 1))], tw1[q]);
+        if (q == 0) x = rv_split_bin0(zk);
         hspec1[(size_t)q0 * B1 + q] = make_float2(x.x * scale, x.y * scale);
         if (q == 0) h0[q0] = make_float2(x.x * scale, x.y * scale);
     }
@@ -1114,31 +1105,21 @@ __global__ __launch_bounds__(64) void reverb_ir_kernel(const float *__restrict__
         const float x1 = (n + 1 < B && i1 < n_ir) ? ir[i1] : 0.0f;
         a[m] = make_float2(x0, x1);
     }
-    JF_RV_SYNC();
-    const float2 *Z = cfft_small<B, -1>(a, b, tw, lane);
-    for (int q = lane; q < B; q += 64) {
-        const float2 zk = Z[q];
-        const float2 zm = Z[(B - q) & (B - 1)];
-        const float2 e = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
-        const float2 o = make_float2(0.5f * (zk.x - zm.x), 0.5f * (zk.y + zm.y));
-        const float2 wo = rv_mulc(o, tw[q * (512 / B)]);
-        float2 x = make_float2(e.x + wo.y, e.y - wo.x);
-        if (q == 0) x = make_float2(zk.x + zk.y, zk.x - zk.y);
-        hspec[(size_t)p * B + q] = make_float2(x.x * scale, x.y * scale);
-        if (q == 0) h0[p] = make_float2(x.x * scale, x.y * scale);
-    }
+    rv_rfft_packed<B>(a, b, tw, lane, [&](int q, float2 x) {
+        const float2 h = make_float2(x.x * scale, x.y * scale);
+        hspec[(size_t)p * B + q] = h;
+        if (q == 0) h0[p] = h;
+    });
 }
 
 // ---------------------------------------------------------------- launchers --
 hipError_t launch_reverb_ir(const float *d_ir, int n_ir, int P, int B, float scale, const float2 *d_tw,
                             float2 *d_hspec, hipStream_t st) {
-    switch (B) {
-    case 64: hipLaunchKernelGGL(reverb_ir_kernel<64>, dim3(P), dim3(64), 0, st, d_ir, n_ir, scale, d_tw, d_hspec, d_hspec + (size_t)P * 64); break;
-    case 128: hipLaunchKernelGGL(reverb_ir_kernel<128>, dim3(P), dim3(64), 0, st, d_ir, n_ir, scale, d_tw, d_hspec, d_hspec + (size_t)P * 128); break;
-    case 256: hipLaunchKernelGGL(reverb_ir_kernel<256>, dim3(P), dim3(64), 0, st, d_ir, n_ir, scale, d_tw, d_hspec, d_hspec + (size_t)P * 256); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    const bool known = rv_dispatch_block(B, [&](auto block) {
+        constexpr int kB = decltype(block)::value;
+        hipLaunchKernelGGL(reverb_ir_kernel<kB>, dim3(P), dim3(64), 0, st, d_ir, n_ir, scale, d_tw, d_hspec, d_hspec + (size_t)P * kB);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 static void launch_big_transforms(const ReverbBigParams &P, hipStream_t st);
@@ -1220,24 +1201,17 @@ static void launch_fft(const ReverbParams &P, hipStream_t st) {
 // the small transforms a batch call put off, from the dry ring (ReverbParams::catchup)
 hipError_t launch_reverb_catchup(const ReverbParams &P, hipStream_t st) {
     if (!P.catchup || P.K <= 0) return hipErrorInvalidValue;
-    switch (P.B) {
-    case 64: launch_fft<64>(P, st); break;
-    case 128: launch_fft<128>(P, st); break;
-    case 256: launch_fft<256>(P, st); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    const bool known = rv_dispatch_block(P.B, [&](auto block) { launch_fft<decltype(block)::value>(P, st); });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t launch_reverb_big_ir(const float *d_ir, int n_ir, int t0, int P1, int B1, float scale, const float2 *d_tw1,
                                 float2 *d_hspec1, hipStream_t st) {
     float2 *h0 = d_hspec1 + (size_t)(P1 + 16) * B1;  // behind the P1 partitions written here and 16 of zeros
-    switch (B1) {
-    case 1024: hipLaunchKernelGGL(reverb_big_ir_kernel<1024>, dim3(P1), dim3(kBigThreads), 0, st, d_ir, n_ir, t0, scale, d_tw1, d_hspec1, h0); break;
-    case 2048: hipLaunchKernelGGL(reverb_big_ir_kernel<2048>, dim3(P1), dim3(kBigThreads), 0, st, d_ir, n_ir, t0, scale, d_tw1, d_hspec1, h0); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    const bool known = rv_dispatch_big(B1, [&](auto big) {
+        hipLaunchKernelGGL(reverb_big_ir_kernel<decltype(big)::value>, dim3(P1), dim3(kBigThreads), 0, st, d_ir, n_ir, t0, scale, d_tw1, d_hspec1, h0);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // workgroups of kBigThreads of `kernel` the current device holds at once (1024 if it will not say)
@@ -1287,18 +1261,10 @@ static void launch_big_products_t(const ReverbBigParams &P, hipStream_t st) {
     hipLaunchKernelGGL((reverb_big_ifft_kernel<B1>), dim3(std::min(n, resident)), dim3(kBigThreads), 0, st, P);
 }
 static void launch_big_transforms(const ReverbBigParams &P, hipStream_t st) {
-    switch (P.B1) {
-    case 1024: launch_big_transforms_t<1024>(P, st); break;
-    case 2048: launch_big_transforms_t<2048>(P, st); break;
-    default: break;
-    }
+    rv_dispatch_big(P.B1, [&](auto big) { launch_big_transforms_t<decltype(big)::value>(P, st); });
 }
 static void launch_big_products(const ReverbBigParams &P, hipStream_t st) {
-    switch (P.B1) {
-    case 1024: launch_big_products_t<1024>(P, st); break;
-    case 2048: launch_big_products_t<2048>(P, st); break;
-    default: break;
-    }
+    rv_dispatch_big(P.B1, [&](auto big) { launch_big_products_t<decltype(big)::value>(P, st); });
 }
 
 // The big partitions' work of one-block calls on the engine's side stream (jf_engine_reverb.cpp: run_reverb_stage): X_m of the big
@@ -1322,12 +1288,12 @@ int big_twiddle_pack_index(int B1, int k) {
 // 0 = no block went through stage B (a batch call whose blocks the big partitions formed alone)
 hipError_t launch_reverb(const ReverbParams &P, ReverbPlan *plan, hipStream_t st, int *form_used) {
     int form = 0;
-    switch (P.B) {
-    case 64: form = launch_stage<64, 4, 16>(P, plan, st); break;
-    case 128: form = launch_stage<128, 4, 16>(P, plan, st); break;
-    case 256: form = launch_stage<256, 2, 8>(P, plan, st); break;
-    default: return hipErrorInvalidValue;
-    }
+    const bool known = rv_dispatch_block(P.B, [&](auto block) {
+        // (T sources a workgroup of form 2, KB blocks a tile of form 3: 4, 16 / 4, 16 / 2, 8 -- what the registers hold)
+        constexpr int B = decltype(block)::value, T = B == 256 ? 2 : 4, KB = B == 256 ? 8 : 16;
+        form = launch_stage<B, T, KB>(P, plan, st);
+    });
+    if (!known) return hipErrorInvalidValue;
     if (form_used) *form_used = form;
     return hipGetLastError();
 }

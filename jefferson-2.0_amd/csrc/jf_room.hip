@@ -2,17 +2,20 @@
 //
 //   room_send_kernel   send_b[k] = sum over the bus's sending sources of l_s x_s, the samples the spatialiser's window takes
 //                      in as new in block k (item_gather's rule, jf_kernels.hip), the level ramped over the call's first block
-//   room_fft_kernel    packed spectrum of [previous send block | send block] into the bus's delay line (rv_forward's transform)
-//   room_mac_kernel    Y_ear = sum_p X[k - p] H_ear[p] for both ears from one read of the delay line, the inverse transform,
-//                      the last B samples: the wet block, interleaved
+//   room_fft_kernel    packed spectrum of [previous send block | send block] into the bus's delay line (rv_fill_pair,
+//                      rv_rfft_packed: the transform rv_forward calls)
+//   room_mac_kernel    Y_ear = sum_p X[k - p] H_ear[p] for both ears from one read of the delay line (rv_load_bins; the
+//                      product is this kernel's own text), the inverse transform (rv_sum_partials, rv_irfft_packed: the calls
+//                      mac_finish makes), the last B samples: the wet block, interleaved
 //   room_add_kernel    mix += wet
 //
 // DETERMINISM: the wet part is the same bits however a run is cut into calls.  No atomics; every sum has ONE
 // association, fixed by the list of senders (send) or by P (products), never by the call's size K -- a (bus, block) is one
 // workgroup in every kernel, and what that workgroup does depends on K nowhere but in where it finds the previous block.
 //
-// The transforms, their twiddles and the packing of a real spectrum (bin 0 holds the two real bins 0 and B) are the reverb's
-// (jf_rv_small.h); the responses' spectra are built by the reverb's own kernel (launch_reverb_ir, once per ear).
+// The transforms, their twiddles, the packing of a real spectrum (bin 0 holds the two real bins 0 and B), its split and its
+// untangling are the reverb's: not copies of them but the same functions (jf_rv_small.h, the packed-spectrum toolkit); the
+// responses' spectra are built by the reverb's own kernel (launch_reverb_ir, once per ear).
 #include <hip/hip_runtime.h>
 
 #include "jf_room.h"
@@ -82,49 +85,23 @@ __global__ __launch_bounds__(kSendThreads) void room_send_kernel(RoomParams P) {
 }
 
 // ------------------------------------------------------------------------------------------- forward transform --
-// One wavefront per (block k, bus b): z[m] = x[2m] + j x[2m + 1] over x = [previous block, block], a B-point complex
-// transform, the real-transform split; bin 0 holds (X[0], X[B]).
+// One wavefront per (block k, bus b): the packed spectrum of x = [previous block, block] into slot head + k of the bus's
+// delay line.
 template <int B>
 __global__ __launch_bounds__(64) void room_fft_kernel(RoomParams P) {
     __shared__ float2 s_buf[2 * B];
     const int k = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
-    float2 *a = s_buf, *bb = s_buf + B;
     const float *cur = P.send + ((size_t)b * P.K + k) * B;
     const float *prv = k == 0 ? P.prev_in + (size_t)b * B : cur - B;
-    for (int m = lane; m < B; m += 64) {
-        const int n = 2 * m;
-        a[m] = *reinterpret_cast<const float2 *>(n < B ? prv + n : cur + (n - B));
-    }
-    JF_RV_SYNC();
-    const float2 *Z = cfft_small<B, -1>(a, bb, P.tw, lane);
-    float2 *out = P.fdl + ((size_t)b * P.Rg + (size_t)((P.head + k) % P.Rg)) * B;
-    for (int q = lane; q < B; q += 64) {
-        const float2 zk = Z[q];
-        const float2 zm = Z[(B - q) & (B - 1)];
-        const float2 e = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
-        const float2 o = make_float2(0.5f * (zk.x - zm.x), 0.5f * (zk.y + zm.y));
-        const float2 wo = rv_mulc(o, P.tw[q * (512 / B)]);
-        float2 x = make_float2(e.x + wo.y, e.y - wo.x);
-        if (q == 0) x = make_float2(zk.x + zk.y, zk.x - zk.y);
-        out[q] = x;
-    }
+    rv_fill_pair<B>(s_buf, prv, cur, lane);
+    // (the slot is worked out behind the transform, where the sink is called: ahead of it the division would wait for P.Rg
+    // before the block's samples are asked for)
+    rv_rfft_packed<B>(s_buf, s_buf + B, P.tw, lane, [&](int q, float2 x) {
+        P.fdl[((size_t)b * P.Rg + (size_t)((P.head + k) % P.Rg)) * B + q] = x;
+    });
 }
 
 // ---------------------------------------------------------------------------------------- multiply-accumulate --
-template <int NB>
-JF_DEV void load_bins(const float2 *p, float2 (&v)[NB]) {  // NB consecutive bins, 16 bytes at a time where there are two
-    if constexpr (NB == 1) {
-        v[0] = p[0];
-    } else {
-#pragma unroll
-        for (int i = 0; i < NB; i += 2) {
-            const float4 t = *reinterpret_cast<const float4 *>(p + i);
-            v[i] = make_float2(t.x, t.y);
-            v[i + 1] = make_float2(t.z, t.w);
-        }
-    }
-}
-
 // One workgroup of NW wavefronts per (block k, bus b).  Wave w takes the partitions p = w C .. (w + 1) C - 1, C = ceil(P /
 // NW), in ascending order, a lane B / 64 consecutive bins, BOTH ears from one read of the delay line; the waves' partial
 // spectra are added in ascending order of w out of LDS by the wave that then inverts the ear (wave 0 left, wave 1 right).
@@ -154,9 +131,9 @@ __global__ __launch_bounds__(64 * NW) void room_mac_kernel(RoomParams P) {
             const int p = p0 + c < p_hi ? p0 + c : p_hi - 1;  // (past the range: loaded inside the buffers, not added)
             int sl = slot0 - p;
             sl = sl < 0 ? sl + P.Rg : sl;
-            load_bins<NB>(fdl + (size_t)sl * B, x[c]);
-            load_bins<NB>(hL + (size_t)p * B, l[c]);
-            if (stereo) load_bins<NB>(hR + (size_t)p * B, r[c]);
+            rv_load_bins<NB>(fdl + (size_t)sl * B, x[c]);
+            rv_load_bins<NB>(hL + (size_t)p * B, l[c]);
+            if (stereo) rv_load_bins<NB>(hR + (size_t)p * B, r[c]);
         }
 #pragma unroll
         for (int c = 0; c < CH; c++) {
@@ -191,32 +168,9 @@ __global__ __launch_bounds__(64 * NW) void room_mac_kernel(RoomParams P) {
     __syncthreads();
     const int ear = w;
     if (ear >= (stereo ? 2 : 1)) return;  // (no barrier below: the finishing waves work in LDS of their own)
-    // the partial spectra in order, the packed spectrum untangled (mac_finish's arithmetic), the inverse transform
-    float2 *ybuf = s_fft[ear], *zbuf = s_fft[ear] + B;
-    for (int q = lane; q < B; q += 64) {
-        float2 a = s_part[ear][0][q];
-#pragma unroll
-        for (int v = 1; v < NW; v++) a = rv_add(a, s_part[ear][v][q]);
-        ybuf[q] = a;
-    }
-    JF_RV_SYNC();
-    for (int q = lane; q < B; q += 64) {
-        const float2 yk = ybuf[q];
-        const float2 ym = ybuf[(B - q) & (B - 1)];
-        float2 z;
-        if (q == 0) {
-            z = make_float2(0.5f * (yk.x + yk.y), 0.5f * (yk.x - yk.y));
-        } else {
-            const float2 e = make_float2(0.5f * (yk.x + ym.x), 0.5f * (yk.y - ym.y));
-            const float2 d = make_float2(0.5f * (yk.x - ym.x), 0.5f * (yk.y + ym.y));
-            const float2 o = rv_mul(d, P.tw[q * (512 / B)]);
-            z = make_float2(e.x - o.y, e.y + o.x);
-        }
-        zbuf[q] = z;
-    }
-    JF_RV_SYNC();
-    // (zbuf is read above through ybuf's indices only after the sync; the transform ping-pongs between the two halves)
-    const float2 *zt = cfft_small<B, +1>(zbuf, ybuf, P.tw, lane);
+    // the partial spectra in order, the packed spectrum untangled, the inverse transform: mac_finish's two calls
+    rv_sum_partials<B, NW>(s_part[ear][0], B, s_fft[ear], lane);
+    const float2 *zt = rv_irfft_packed<B>(s_fft[ear], s_fft[ear] + B, P.tw, lane);
     // overlap-save: time samples B .. 2B - 1 are z[m], m >= B / 2 (even, odd)
     float *wet = P.wet + ((size_t)b * P.K + k) * 2 * B;
     for (int m = B / 2 + lane; m < B; m += 64) {
@@ -256,31 +210,21 @@ __global__ __launch_bounds__(256) void room_add_scalar_kernel(float *__restrict_
 
 }  // namespace
 
-int room_mac_waves(int B) { return B == 256 ? 8 : 16; }  // (B = 256: 16 waves' partial spectra of two ears would not fit 64 KB of LDS)
+// wavefronts of room_mac_kernel's workgroup (B = 256: 16 waves' partial spectra of two ears would not fit 64 KB of LDS)
+constexpr int room_mac_waves_of(int B) { return B == 256 ? 8 : 16; }
+int room_mac_waves(int B) { return room_mac_waves_of(B); }
 
 // send -> forward transforms -> products and inverse: the K wet blocks of every bus, ahead of the spatialiser
 hipError_t launch_room_stage(const RoomParams &P, hipStream_t st) {
     if (P.K <= 0 || P.n_buses <= 0 || P.P <= 0) return hipErrorInvalidValue;
     const dim3 grid((unsigned)P.K, (unsigned)P.n_buses);
-    switch (P.B) {
-    case 64:
-        hipLaunchKernelGGL(room_send_kernel<64>, grid, dim3(kSendThreads), 0, st, P);
-        hipLaunchKernelGGL(room_fft_kernel<64>, grid, dim3(64), 0, st, P);
-        hipLaunchKernelGGL((room_mac_kernel<64, 16>), grid, dim3(64 * 16), 0, st, P);
-        break;
-    case 128:
-        hipLaunchKernelGGL(room_send_kernel<128>, grid, dim3(kSendThreads), 0, st, P);
-        hipLaunchKernelGGL(room_fft_kernel<128>, grid, dim3(64), 0, st, P);
-        hipLaunchKernelGGL((room_mac_kernel<128, 16>), grid, dim3(64 * 16), 0, st, P);
-        break;
-    case 256:
-        hipLaunchKernelGGL(room_send_kernel<256>, grid, dim3(kSendThreads), 0, st, P);
-        hipLaunchKernelGGL(room_fft_kernel<256>, grid, dim3(64), 0, st, P);
-        hipLaunchKernelGGL((room_mac_kernel<256, 8>), grid, dim3(64 * 8), 0, st, P);
-        break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    const bool known = rv_dispatch_block(P.B, [&](auto block) {
+        constexpr int B = decltype(block)::value, NW = room_mac_waves_of(B);
+        hipLaunchKernelGGL(room_send_kernel<B>, grid, dim3(kSendThreads), 0, st, P);
+        hipLaunchKernelGGL(room_fft_kernel<B>, grid, dim3(64), 0, st, P);
+        hipLaunchKernelGGL((room_mac_kernel<B, NW>), grid, dim3(64 * NW), 0, st, P);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // n floats of wet (the room's own buffer: 16-byte aligned) onto as many of mix; a mix at any float offset takes the scalar form

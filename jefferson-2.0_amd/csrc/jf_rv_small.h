@@ -1,7 +1,10 @@
 // jf_rv_small.h -- device code of the reverb stage that more than one translation unit needs: the small (one-wavefront)
-// transforms, stage A of a block (rv_forward) and the last step of stage B (mac_finish).  jf_reverb.hip builds its kernels
-// from them; jf_kernels.hip builds the one-launch real-time kernel's reverb head from them (rv_head_wave below: the head of a
-// non-uniformly partitioned response, by the wave that then spatialises the source).  Included inside namespace jf.
+// transforms, the PACKED-SPECTRUM TOOLKIT (below them: the one text of the real-transform split and its untangling, of the
+// wave-level transform pair rv_rfft_packed / rv_irfft_packed, of a lane's bin loads rv_load_bins, and the launchers'
+// rv_dispatch_block), stage A of a block (rv_forward) and the last step of stage B (mac_finish).  jf_reverb.hip and
+// jf_room.hip build their kernels from them; jf_kernels.hip builds the one-launch real-time kernel's reverb head from them
+// (rv_head_wave below: the head of a non-uniformly partitioned response, by the wave that then spatialises the source).
+// Included inside namespace jf.
 #pragma once
 
 #define JF_DEV __device__ __forceinline__
@@ -176,6 +179,128 @@ JF_DEV float2 *cfft_small(float2 *a, float2 *b, const float2 *__restrict__ tw, i
     return cfft_lds<NPT, DIR, 64, 1024, false>(a, b, tw, lane);
 }
 
+// ------------------------------------------------------------------------------------- packed-spectrum toolkit --
+// 2 N real samples are transformed as N complex points z[m] = x[2m] + j x[2m + 1]; their spectrum is stored PACKED: N complex
+// bins, bin 0 holding the two real bins (X[0], X[N]).  Every kernel that makes or inverts such a spectrum -- the reverb's small
+// and big partitions, the room, the real-time head -- does it with the functions below: the roundings that the tests hold
+// bit-equal between kernels have one text.  The product of two such spectra is NOT here: reverb_mac_kernel, rv_head_wave and
+// room_mac_kernel each hold the line acc += x h themselves (rv_head_wave says why).
+
+// One bin of the real-transform split: X[q] = E - j W^q O with E = (Z[q] + conj Z[N - q]) / 2, O = (Z[q] - conj Z[N - q]) / 2;
+// w = conj(W^q) = exp(+2 pi i q / 2N).  Bin 0 is rv_split_bin0 of Z[0]: (X[0], X[N]), both real.
+JF_DEV float2 rv_split_bin(float2 zk, float2 zm, float2 w) {
+    const float2 e = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
+    const float2 o = make_float2(0.5f * (zk.x - zm.x), 0.5f * (zk.y + zm.y));
+    const float2 wo = rv_mulc(o, w);
+    return make_float2(e.x + wo.y, e.y - wo.x);
+}
+JF_DEV float2 rv_split_bin0(float2 z) { return make_float2(z.x + z.y, z.x - z.y); }
+
+// One bin of the untangling ahead of the inverse transform: Z[q] = E + j O with E = (Y[q] + conj Y[N - q]) / 2,
+// O = w (Y[q] - conj Y[N - q]) / 2, w = W^-q = exp(+2 pi i q / 2N).  Bin 0 is rv_untangle_bin0 of the packed pair: E0 + j O0.
+JF_DEV float2 rv_untangle_bin(float2 yk, float2 ym, float2 w) {
+    const float2 e = make_float2(0.5f * (yk.x + ym.x), 0.5f * (yk.y - ym.y));
+    const float2 d = make_float2(0.5f * (yk.x - ym.x), 0.5f * (yk.y + ym.y));
+    const float2 o = rv_mul(d, w);
+    return make_float2(e.x - o.y, e.y + o.x);
+}
+JF_DEV float2 rv_untangle_bin0(float2 y) { return make_float2(0.5f * (y.x + y.y), 0.5f * (y.x - y.y)); }
+
+// a[m] = (x[2m], x[2m + 1]) over x = [prv | cur], B samples each at an 8-byte aligned address, by one wavefront
+template <int B>
+JF_DEV void rv_fill_pair(float2 *a, const float *prv, const float *cur, int lane) {
+    for (int m = lane; m < B; m += 64) {
+        const int n = 2 * m;
+        a[m] = *reinterpret_cast<const float2 *>(n < B ? prv + n : cur + (n - B));
+    }
+}
+
+struct rv_no_sink0 {
+    JF_DEV void operator()(float2) const {}
+};
+// Packed spectrum of the 2 B samples in a (rv_fill_pair's layout; a, b: 2 x B float2 of the wave's LDS), B = 64 / 128 / 256,
+// by one wavefront: sink(q, X[q]) for each of the lane's bins -- the caller decides where a bin goes; before it sink0(X[0]) for
+// a caller that keeps the packed pair of bin 0 somewhere else as well.  tw: exp(+2 pi i j / 1024), j < 1024.
+template <int B, class Sink, class Sink0 = rv_no_sink0>
+JF_DEV void rv_rfft_packed(float2 *a, float2 *b, const float2 *tw, int lane, Sink sink, Sink0 sink0 = Sink0()) {
+    JF_RV_SYNC();
+    const float2 *Z = cfft_small<B, -1>(a, b, tw, lane);
+    for (int q = lane; q < B; q += 64) {
+        const float2 zk = Z[q];
+        const float2 zm = Z[(B - q) & (B - 1)];
+        float2 x = rv_split_bin(zk, zm, tw[q * (512 / B)]);
+        if (q == 0) {
+            x = rv_split_bin0(zk);
+            sink0(x);
+        }
+        sink(q, x);
+    }
+}
+
+// ybuf[q] = red[q] + red[stride + q] + ...: NW partial spectra added in ascending order, by one wavefront
+template <int B, int NW>
+JF_DEV void rv_sum_partials(const float2 *red, int stride, float2 *ybuf, int lane) {
+    for (int q = lane; q < B; q += 64) {
+        float2 a = red[q];
+#pragma unroll
+        for (int w = 1; w < NW; w++) a = rv_add(a, red[(size_t)w * stride + q]);
+        ybuf[q] = a;
+    }
+}
+
+// The packed spectrum in ybuf (this wave's own stores, not yet synchronised) back to 2 B samples, by one wavefront: untangled
+// into zbuf, the inverse transform ping-pong between the two.  Returns z: time samples 2m and 2m + 1 are z[m] (overlap-save
+// keeps m >= B / 2).
+template <int B>
+JF_DEV const float2 *rv_irfft_packed(float2 *ybuf, float2 *zbuf, const float2 *tw, int lane) {
+    JF_RV_SYNC();
+    for (int q = lane; q < B; q += 64) {
+        const float2 yk = ybuf[q];
+        const float2 ym = ybuf[(B - q) & (B - 1)];
+        float2 z;
+        if (q == 0) z = rv_untangle_bin0(yk);
+        else z = rv_untangle_bin(yk, ym, tw[q * (512 / B)]);
+        zbuf[q] = z;
+    }
+    JF_RV_SYNC();
+    return cfft_small<B, +1>(zbuf, ybuf, tw, lane);
+}
+
+// NB consecutive bins of a lane, 16 bytes at a time where there are two
+template <int NB>
+JF_DEV void rv_load_bins(const float2 *p, float2 (&v)[NB]) {
+    if constexpr (NB == 1) {
+        v[0] = p[0];
+    } else {
+#pragma unroll
+        for (int i = 0; i < NB; i += 2) {
+            const float4 t = *reinterpret_cast<const float4 *>(p + i);
+            v[i] = make_float2(t.x, t.y);
+            v[i + 1] = make_float2(t.z, t.w);
+        }
+    }
+}
+
+// The launchers' switch: f(std::integral_constant<int, B>) for the run-time block size B if there are kernels for it, false if
+// not; rv_dispatch_big the same for the big partitions' B1.
+template <class F>
+bool rv_dispatch_block(int B, F &&f) {
+    switch (B) {
+    case 64: f(std::integral_constant<int, 64>()); return true;
+    case 128: f(std::integral_constant<int, 128>()); return true;
+    case 256: f(std::integral_constant<int, 256>()); return true;
+    default: return false;
+    }
+}
+template <class F>
+bool rv_dispatch_big(int B1, F &&f) {
+    switch (B1) {
+    case 1024: f(std::integral_constant<int, 1024>()); return true;
+    case 2048: f(std::integral_constant<int, 2048>()); return true;
+    default: return false;
+    }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------- stage A --
@@ -199,10 +324,7 @@ JF_DEV void rv_forward(const ReverbParams &P, int k, int s, float2 *a, float2 *b
         int pc = (P.dry_pos0 + k * B) % P.Rd;
         int pp = pc - B;
         pp = pp < 0 ? pp + P.Rd : pp;
-        for (int m = lane; m < B; m += 64) {
-            const int n = 2 * m;
-            a[m] = *reinterpret_cast<const float2 *>(ring + (n < B ? pp + n : pc + (n - B)));
-        }
+        rv_fill_pair<B>(a, ring + pp, ring + pc, lane);
     } else {
     if (k >= P.copy_lo && k < P.copy_hi) {
         // a block whose output the big partitions form directly (ReverbBigParams: FULL) and whose spectrum nobody will read:
@@ -255,25 +377,17 @@ JF_DEV void rv_forward(const ReverbParams &P, int k, int s, float2 *a, float2 *b
         if (lane == 0) P.dry_count_out[s] = (int)(((unsigned)dc0 + (unsigned)(P.K * B)) % (unsigned)L);
     }
     }
-    JF_RV_SYNC();
-    const float2 *Z = cfft_small<B, -1>(a, b, tw, lane);
-    // real-FFT split: X[k] = E + (-i) W^k O, W = exp(-2 pi i / 2B)
-    float2 *out = P.fdl + ((size_t)s * P.Rg + (size_t)((P.head + k) % P.Rg)) * B;
-    for (int q = lane; q < B; q += 64) {
-        const float2 zk = Z[q];
-        const float2 zm = Z[(B - q) & (B - 1)];
-        const float2 e = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
-        const float2 o = make_float2(0.5f * (zk.x - zm.x), 0.5f * (zk.y + zm.y));
-        const float2 wo = rv_mulc(o, tw[q * (512 / B)]);
-        float2 x = make_float2(e.x + wo.y, e.y - wo.x);
-        if (q == 0) {
-            x = make_float2(zk.x + zk.y, zk.x - zk.y);  // (X[0], X[B]), both real
-            // compact copy of the packed pair for the block-tiled form (fdl0[s][slot], behind the spectra)
-            P.fdl[(size_t)P.S * P.Rg * B + (size_t)s * P.Rg + (size_t)((P.head + k) % P.Rg)] = x;
-        }
-        out[q] = x;
-        if (x0) x0[q] = x;
-    }
+    // the packed spectrum into the delay line's slot; the packed pair of bin 0 also as a compact copy for the block-tiled
+    // form (fdl0[s][slot], behind the spectra)
+    const size_t slot = (size_t)((P.head + k) % P.Rg);
+    float2 *out = P.fdl + ((size_t)s * P.Rg + slot) * B;
+    rv_rfft_packed<B>(
+        a, b, tw, lane,
+        [&](int q, float2 x) {
+            out[q] = x;
+            if (x0) x0[q] = x;
+        },
+        [&](float2 x) { P.fdl[(size_t)P.S * P.Rg * B + (size_t)s * P.Rg + slot] = x; });
 }
 
 // Last step of stage B for one (block k, source s), by one wavefront: add the NW partial spectra
@@ -284,14 +398,8 @@ JF_DEV void rv_forward(const ReverbParams &P, int k, int s, float2 *a, float2 *b
 template <int B, int NW, bool FIX0 = false>
 JF_DEV void mac_finish(const float2 *red, int stride, float2 *fftbuf, const ReverbParams &P, int s, int k, int lane,
                        const float2 *tw) {
-    // Y[q] (packed), then Z[q] = E + j O with E = (Y[q] + conj Y[B-q])/2, O = conj(W^q) (Y[q] - conj Y[B-q])/2
     float2 *ybuf = fftbuf, *zbuf = fftbuf + B;
-    for (int q = lane; q < B; q += 64) {
-        float2 a = red[q];
-#pragma unroll
-        for (int w = 1; w < NW; w++) a = rv_add(a, red[(size_t)w * stride + q]);
-        ybuf[q] = a;
-    }
+    rv_sum_partials<B, NW>(red, stride, ybuf, lane);
     if (FIX0) {
         const float2 *x0 = P.fdl + (size_t)P.S * P.Rg * B + (size_t)s * P.Rg;
         const float2 *h0 = P.hspec + (size_t)P.P * B;
@@ -313,23 +421,7 @@ JF_DEV void mac_finish(const float2 *red, int stride, float2 *fftbuf, const Reve
         JF_RV_SYNC();  // every lane's sum of partials is in ybuf before lane 0 replaces bin 0
         if (lane == 0) ybuf[0] = y0;
     }
-    JF_RV_SYNC();
-    for (int q = lane; q < B; q += 64) {
-        const float2 yk = ybuf[q];
-        const float2 ym = ybuf[(B - q) & (B - 1)];
-        float2 z;
-        if (q == 0) {
-            z = make_float2(0.5f * (yk.x + yk.y), 0.5f * (yk.x - yk.y));  // E0 + j O0 from (Y[0], Y[B])
-        } else {
-            const float2 e = make_float2(0.5f * (yk.x + ym.x), 0.5f * (yk.y - ym.y));
-            const float2 d = make_float2(0.5f * (yk.x - ym.x), 0.5f * (yk.y + ym.y));
-            const float2 o = rv_mul(d, tw[q * (512 / B)]);  // W^-q = exp(+2 pi i q / 2B)
-            z = make_float2(e.x - o.y, e.y + o.x);
-        }
-        zbuf[q] = z;
-    }
-    JF_RV_SYNC();
-    const float2 *zt = cfft_small<B, +1>(zbuf, ybuf, tw, lane);
+    const float2 *zt = rv_irfft_packed<B>(ybuf, zbuf, tw, lane);
     // overlap-save: time samples B..2B-1 = z[m], m >= B/2 (even, odd interleaved)
     const int c0 = P.st_in[s].count;  // where the spatialiser will read the first new sample
     float *wet = P.wet + (size_t)s * P.Wr;
@@ -367,16 +459,11 @@ JF_DEV void rv_head_wave(const ReverbParams &P, int s, float2 *lds, const float2
     float2 acc0 = make_float2(0.f, 0.f);  // bin 0 is two packed real bins
     const float2 *fdl = P.fdl + (size_t)s * P.Rg * B + lane * NB;
     const float2 *hs = P.hspec + lane * NB;
-    auto load_nb = [&](const float2 *p, float2 (&v)[NB]) {
-        if (NB == 2) {
-            const float4 q = *reinterpret_cast<const float4 *>(p);
-            v[0] = make_float2(q.x, q.y);
-            v[NB - 1] = make_float2(q.z, q.w);
-        } else {
-#pragma unroll
-            for (int i = 0; i < NB; i++) v[i] = p[i];
-        }
-    };
+    // The product stays a copy of the line in reverb_mac_kernel and room_mac_kernel.  With contraction on, ONE product of
+    // x.x h.y + x.y h.x is rounded by itself and the other fused onto it, and which one follows the code around the line, not
+    // its text: the parent kernels do not agree (reverb_mac_kernel's forms 1 and 2 fuse x.y h.x, this wave does not), so one
+    // function -- its choice left to the compiler or pinned with fmaf -- changes the last bit of one of them
+    // (profiles/rv_spectrum/README.md).
     auto mac = [&](const float2 (&x)[NB], const float2 (&h)[NB]) {
 #pragma unroll
         for (int i = 0; i < NB; i++) {
@@ -393,7 +480,7 @@ JF_DEV void rv_head_wave(const ReverbParams &P, int s, float2 *lds, const float2
             x[i] = x0[lane * NB + i];
             acc[i] = make_float2(0.f, 0.f);
         }
-        load_nb(hs, h);
+        rv_load_bins<NB>(hs, h);
         mac(x, h);
     }
     // partitions 1 .. P - 1 from the delay line, eight at a time in flight
@@ -408,8 +495,8 @@ JF_DEV void rv_head_wave(const ReverbParams &P, int s, float2 *lds, const float2
         for (int c = 0; c < CH; c++) {
             // (partitions past the last one: their products are not added; the loads stay inside the buffers)
             const int p = p0 + c < P.P ? p0 + c : P.P - 1;
-            load_nb(hs + (size_t)p * B, h[c]);
-            load_nb(fdl + (size_t)sl * B, x[c]);
+            rv_load_bins<NB>(hs + (size_t)p * B, h[c]);
+            rv_load_bins<NB>(fdl + (size_t)sl * B, x[c]);
             sl = sl == 0 ? P.Rg - 1 : sl - 1;
         }
 #pragma unroll
