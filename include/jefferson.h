@@ -542,6 +542,53 @@ int jf_room_taps(const jf_engine *e); /* 0: off */
 int jf_source_set_send(jf_engine *e, int src, float level);
 float jf_source_send(const jf_engine *e, int src); /* the level last set; 0 for a bad index */
 
+/* ---- listener poses: head position and orientation per output bus --------------- */
+
+/*
+ * The reference has ONE listener, fixed: SoundSource::updateFromCartesian (SoundSource.cu:20-36) takes a position relative to
+ * a head that sits at the origin and looks down -z, and every source is summed into that listener's one stereo output
+ * (Audio.cu:26, the mixing loop Audio.cu:109-110).  With output buses there is a listener per bus; here each of them gets a
+ * POSE, and a source may be given a WORLD position instead of a head-relative one: the engine derives the latched record
+ * {ele, azi, x, y, z} from the two -- a listener who turns their head or walks is one call, not one per source.
+ *
+ * Conventions:
+ *   - A pose is 7 floats {cx, cy, cz, qw, qx, qy, qz}: c the head's centre in world coordinates, q the unit quaternion that
+ *     rotates head coordinates to world coordinates, v_world = q v_head q*.
+ *   - The head frame is exactly the frame jf_source_set_cartesian takes: ahead = -z, up = +y, azimuth = atan2(-x, -z) as
+ *     SoundSource.cu:20-36 is written (its handedness quirk included: azimuth 90 is the head's -x).
+ *   - The head-relative position of a source at p is rel = q* (p - c) q.  The pose {0,0,0, 1,0,0,0} is the reference's
+ *     listener and every bus's pose until it is told otherwise: rel = p.
+ *   - The record: {x, y, z} = rel, evaluated in double and rounded to float once; ele = atan2(rel.y, sqrt(rel.x^2 +
+ *     rel.z^2)), azi = atan2(-rel.x, -rel.z) folded into [0, 360], both in degrees from the double values and rounded to whole
+ *     degrees as the setters round (SoundSource.cu:33-34).  p == c gives {0, 0, 0, 0, 0}, which every kernel renders as a
+ *     source straight ahead at distance 0 (no delay, no attenuation).  One rule, compiled for the host and for the GPU
+ *     (csrc/jf_pose_rule.h: no libm call, nothing a compiler may contract): jf_position_from_world is bit for bit what the
+ *     batch calls compute on the device.  An elevation the index/weight rule cannot interpolate (below -50 degrees on
+ *     KEMAR's rings) is not an error here -- the source is silent while it is there, as with jf_process_batch.
+ *
+ * jf_listener_set_pose(e, bus, position[3], orientation[4] = {qw, qx, qy, qz}) and jf_source_set_world(e, src, x, y, z) are
+ *   setters like jf_source_set_cartesian: callable from another thread, latched at the next block boundary.  When a per-block
+ *   call snapshots the positions, a world-placed source's record is the rule of its bus's pose and its world position,
+ *   computed on the host.  jf_source_set_cartesian / jf_source_set_spherical / jf_sources_set_latched make a source
+ *   head-relative again: it ignores its listener.  jf_source_set_bus on a world-placed source makes it heard by the new bus's
+ *   listener from the next block on.  jf_engine_set_buses keeps the poses of the buses that remain; new ones are the
+ *   reference's listener.  Turning a listener by whole degrees crossfades exactly as moving its sources does.
+ * jf_listener_get_pose: the pose last set.  jf_source_get_world: the world position last set; JF_ERR_STATE if the source is
+ *   not world-placed.  jf_source_get_position on a world-placed source reads the record of the last block.
+ * jf_position_from_world: the rule without an engine -- the host twin of the GPU's kernel.
+ * JF_ERR_ARG: a bad bus or source index, NULL arrays, a non-finite value, a quaternion whose norm is further than 1e-3 from 1
+ *   (the rule normalises what is within that).  On every refusal nothing changes.
+ *
+ * Not offered: jefferson_group.h, jf_render and jf_ctest have no option for poses; the angles are whole degrees also for
+ * engines whose rule could use fractions (JF_FLAG_CORRECTED_INTERPOLATION, clouds); a world position per OBJECT with a
+ * source -> object map (one talker heard by many listeners: today one jf_source_set_world per (listener, talker) source).
+ */
+int jf_listener_set_pose(jf_engine *e, int bus, const float position[3], const float orientation[4]);
+int jf_listener_get_pose(const jf_engine *e, int bus, float out[7]);
+int jf_source_set_world(jf_engine *e, int src, float x, float y, float z);
+int jf_source_get_world(const jf_engine *e, int src, float out[3]);
+int jf_position_from_world(const float pose[7], float x, float y, float z, float out[JF_POS_FLOATS]);
+
 /* ---- convolution reverb -------------------------------- */
 
 /*
@@ -581,6 +628,23 @@ int jf_process_batch_in(jf_engine *e, int n_blocks, const float *in, const float
  * setter calls (SoundSource.cu:20-54) with these (already rounded) values leave behind.  jf_batch_run, whose positions live on the device, does
  * not move the sources; a host that follows it with per-block calls says where they stand with this or with the setters. */
 int jf_sources_set_latched(jf_engine *e, const float *records);
+
+/*
+ * callback_func (Audio.cu:94-163) n_blocks times for listeners that move: instead of latched records relative to the
+ * reference's fixed listener (SoundSource.cu:20-36) the call takes world [n_blocks][n_sources][3] world positions and poses
+ * [n_blocks][n_buses][7] listener poses (see "listener poses" above), uploads the two and forms the records ON THE GPU
+ * (pose_kernel, into the buffer the batch kernels read), then runs as jf_process_batch_in does: in as there (NULL is fine),
+ * out_mix as there.  Every source counts as world-placed for the call, on its bus's listener.
+ * Afterwards every source is world-placed at the last block's position, every listener stands at the last block's pose and the
+ * sources' latched records are the last block's: a per-block call that follows continues from there.
+ * JF_ERR_ARG, checked on the host before anything is launched: NULL arrays, n_blocks <= 0, a non-finite value, a quaternion
+ * whose norm is further than 1e-3 from 1.
+ * jf_batch_upload_world is jf_batch_upload_positions for such a trajectory (total_blocks of world positions and poses; the
+ * records are formed on the device); jf_batch_run / jf_batch_fetch are used unchanged and, as there, do not move the sources or
+ * the listeners.  JF_ERR_STATE while the engine has a live source.
+ */
+int jf_process_batch_world(jf_engine *e, int n_blocks, const float *in, const float *world, const float *poses, float *out_mix);
+int jf_batch_upload_world(jf_engine *e, int total_blocks, const float *world, const float *poses);
 
 /*
  * Device-resident form of the same loop of callbacks (Audio.cu:104-117; jf_synchronize is its

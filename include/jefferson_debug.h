@@ -110,6 +110,20 @@ const char *jf_debug_last_kernels(jf_engine *e);
  * between the prep pair and the fused pair and are counted in neither; room_add_kernel runs inside the mix pair and is counted
  * as mix time.  Time an engine with a room against its twin without one (profiles/room/measure.py). */
 int jf_debug_room_wet(jf_engine *e, int n_blocks, float *out);
+/* Listener poses (jefferson.h: jf_listener_set_pose, jf_process_batch_world).
+ * jf_debug_pose_device runs pose_kernel ALONE on arrays of the caller's sizes -- world [n_blocks][n_sources][3], bus
+ * [n_sources] (NULL: every source on bus 0), poses [n_blocks][n_buses][7] -- and copies its records back: out
+ * [n_blocks][n_sources][JF_POS_FLOATS].  The engine lends its device and stream; its own sources, buses and poses are neither
+ * read nor changed.  JF_ERR_ARG as jf_process_batch_world (NULL arrays, counts, a bad bus index, a non-finite value, a
+ * quaternion that is not a unit one).  jf_position_from_world is the host twin: the same bits.
+ * jf_debug_pose_device_bytes: device memory the engine holds for the feature -- 0 until the first jf_process_batch_world /
+ * jf_batch_upload_world.  jf_debug_last_kernels names pose_kernel, first, when the last call launched it. */
+int jf_debug_pose_device(jf_engine *e, int n_blocks, int n_sources, int n_buses, const int *bus, const float *world,
+                         const float *poses, float *out);
+long long jf_debug_pose_device_bytes(const jf_engine *e);
+/* Per-kernel timing (jf_profile_enable(e, 2)) puts an event pair around pose_kernel too: the milliseconds it took and the
+ * number of launches since jf_profile_enable (launches may be NULL).  Not part of jf_profile_read's figures. */
+int jf_profile_read_pose(jf_engine *e, double *pose_ms, long *launches);
 /* G the last batch pipeline run used (1 = fused_block_kernel, > 1 = fused_pair_kernel). */
 int jf_debug_last_source_group(const jf_engine *e);
 /* Caps the persistent grid of the fused kernel at `workgroups` (0 = what the device holds): with a small cap every

@@ -119,6 +119,16 @@ _SIGS = {
     "jf_source_set_send": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
     "jf_source_send": (C.c_float, [C.c_void_p, C.c_int]),
     "jf_debug_room_wet": (C.c_int, [C.c_void_p, C.c_int, _f]),
+    "jf_listener_set_pose": (C.c_int, [C.c_void_p, C.c_int, _f, _f]),
+    "jf_listener_get_pose": (C.c_int, [C.c_void_p, C.c_int, _f]),
+    "jf_source_set_world": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float]),
+    "jf_source_get_world": (C.c_int, [C.c_void_p, C.c_int, _f]),
+    "jf_position_from_world": (C.c_int, [_f, C.c_float, C.c_float, C.c_float, _f]),
+    "jf_process_batch_world": (C.c_int, [C.c_void_p, C.c_int, _f, _f, _f, _f]),
+    "jf_batch_upload_world": (C.c_int, [C.c_void_p, C.c_int, _f, _f]),
+    "jf_debug_pose_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _i, _f, _f, _f]),
+    "jf_debug_pose_device_bytes": (C.c_longlong, [C.c_void_p]),
+    "jf_profile_read_pose": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_long)]),
     "jf_submit_block_in": (C.c_int, [C.c_void_p, _f]),
     "jf_process_block_in": (C.c_int, [C.c_void_p, _f, _f]),
     "jf_callback_in": (C.c_int, [C.c_void_p, _f, _f]),
@@ -262,6 +272,34 @@ def position_from_cartesian(x, y, z):
     o = np.zeros(5, np.float32)
     rc = lib().jf_position_from_cartesian(x, y, z, _fp(o))
     return None if rc else o
+
+
+def position_from_world(pose, x, y, z):
+    """the latched record of a source at world (x, y, z) for a listener at pose {cx, cy, cz, qw, qx, qy, qz}
+    (include/jefferson.h: jf_position_from_world -- the host twin of pose_kernel); JfError for arguments it refuses"""
+    pose = np.ascontiguousarray(pose, np.float32)
+    assert pose.shape == (7,)
+    o = np.zeros(5, np.float32)
+    rc = lib().jf_position_from_world(_fp(pose), x, y, z, _fp(o))
+    if rc:
+        raise JfError(rc, "position_from_world")
+    return o
+
+
+def positions_from_world(poses, world):
+    """position_from_world over arrays: poses [..., 7] and world [..., 3] of equal leading shape -> [..., 5]"""
+    poses = np.ascontiguousarray(poses, np.float32)
+    world = np.ascontiguousarray(world, np.float32)
+    assert poses.shape[:-1] == world.shape[:-1] and poses.shape[-1] == 7 and world.shape[-1] == 3
+    out = np.zeros(world.shape[:-1] + (5,), np.float32)
+    q, w, o = poses.reshape(-1, 7), world.reshape(-1, 3), out.reshape(-1, 5)
+    fn = lib().jf_position_from_world
+    base_q, base_o = q.ctypes.data, o.ctypes.data
+    for i in range(len(w)):
+        rc = fn(C.cast(base_q + 28 * i, _f), w[i, 0], w[i, 1], w[i, 2], C.cast(base_o + 20 * i, _f))
+        if rc:
+            raise JfError(rc, f"position_from_world, record {i}")
+    return out
 
 
 def interpolation(ele, azi, flags=0):
@@ -733,6 +771,71 @@ class Engine:
             inp = self._inp(inp, K * self.B)
             self._chk(lib().jf_process_batch_in(self.h, K, _fp(inp), _fp(pos), _fp(mix)))
         return mix
+
+    def set_listener(self, bus, position, orientation):
+        """bus's listener: head centre `position` and unit quaternion `orientation` {qw, qx, qy, qz}, head -> world
+        (include/jefferson.h: jf_listener_set_pose)"""
+        p = np.ascontiguousarray(position, np.float32)
+        q = np.ascontiguousarray(orientation, np.float32)
+        assert p.shape == (3,) and q.shape == (4,)
+        self._chk(lib().jf_listener_set_pose(self.h, int(bus), _fp(p), _fp(q)))
+
+    def listener(self, bus):
+        o = np.zeros(7, np.float32)
+        self._chk(lib().jf_listener_get_pose(self.h, int(bus), _fp(o)))
+        return o
+
+    def set_world(self, s, x, y, z):
+        """source s at a world position: heard as its bus's listener hears it (jf_source_set_world)"""
+        self._chk(lib().jf_source_set_world(self.h, int(s), x, y, z))
+
+    def world(self, s):
+        o = np.zeros(3, np.float32)
+        self._chk(lib().jf_source_get_world(self.h, int(s), _fp(o)))
+        return o
+
+    def _world_args(self, world, poses):
+        world = np.ascontiguousarray(world, np.float32)
+        poses = np.ascontiguousarray(poses, np.float32)
+        K = world.shape[0]
+        assert world.shape == (K, self.S, 3) and poses.shape == (K, self.n_buses, 7), (world.shape, poses.shape)
+        return K, world, poses
+
+    def process_batch_world(self, world, poses, inp=None):
+        """world [K][S][3], poses [K][n_buses][7] -> the mix of K blocks (jf_process_batch_world)"""
+        K, world, poses = self._world_args(world, poses)
+        mix = self._out(K, 2 * self.B)
+        inp = None if inp is None else self._inp(inp, K * self.B)
+        self._chk(lib().jf_process_batch_world(self.h, K, None if inp is None else _fp(inp), _fp(world), _fp(poses), _fp(mix)))
+        return mix
+
+    def upload_world(self, world, poses):
+        """upload_positions for a trajectory of world positions and poses (jf_batch_upload_world)"""
+        K, world, poses = self._world_args(world, poses)
+        self._chk(lib().jf_batch_upload_world(self.h, K, _fp(world), _fp(poses)))
+
+    def pose_device(self, bus, world, poses):
+        """pose_kernel alone: bus [S] (or None), world [K][S][3], poses [K][n_buses][7] -> records [K][S][5]
+        (jefferson_debug.h: jf_debug_pose_device; the sizes are the arrays', not the engine's)"""
+        world = np.ascontiguousarray(world, np.float32)
+        poses = np.ascontiguousarray(poses, np.float32)
+        K, S, nb = world.shape[0], world.shape[1], poses.shape[1]
+        assert world.shape == (K, S, 3) and poses.shape == (K, nb, 7)
+        bus = None if bus is None else np.ascontiguousarray(bus, np.int32)
+        assert bus is None or bus.shape == (S,)
+        out = np.zeros((K, S, 5), np.float32)
+        self._chk(lib().jf_debug_pose_device(self.h, K, S, nb, None if bus is None else _ip(bus), _fp(world), _fp(poses), _fp(out)))
+        return out
+
+    def profile_read_pose(self):
+        """(ms in pose_kernel, launches) since profile_enable(2)"""
+        ms, n = C.c_double(), C.c_long()
+        self._chk(lib().jf_profile_read_pose(self.h, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    def pose_device_bytes(self):
+        """device memory held for listener poses (0 before the first world batch call)"""
+        return int(lib().jf_debug_pose_device_bytes(self.h))
 
     def set_latched(self, records):
         """every source's position := its latched record [S][5] (what S setter calls leave behind)"""

@@ -214,9 +214,23 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
     return submit_side(e);
 }
 
+// A listener's pose (the reference's fixed listener until jf_listener_set_pose says otherwise); under pos_mu
+static const float *pose_of(const jf_engine *e, int bus) {
+    static const float identity[kPoseFloats] = {0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f};
+    return e->pose.empty() ? identity : e->pose.data() + (size_t)kPoseFloats * bus;
+}
+
+// A world-placed source as the listener of its bus hears it now: the host twin of pose_kernel (jf_pose_rule.h); under pos_mu
+static void place_world_source(jf_engine *e, int s) {
+    const float *w = e->world.data() + 3 * (size_t)s;
+    const PoseRecord r = pose_rule(pose_of(e, e->bus.empty() ? 0 : e->bus[s]), w[0], w[1], w[2]);
+    e->pos[s] = HostPos{r.ele, r.azi, sqrtf(r.x * r.x + r.y * r.y + r.z * r.z), r.x, r.y, r.z};
+}
+
 static void snapshot_positions(jf_engine *e, float *dst /* [S][5] */) {
     std::lock_guard<std::mutex> lk(e->pos_mu);
     for (int s = 0; s < e->S; s++) {
+        if (!e->world_on.empty() && e->world_on[s]) place_world_source(e, s);
         const HostPos &q = e->pos[s];
         float *d = dst + 5 * s;
         d[0] = q.ele;
@@ -330,7 +344,7 @@ void destroy_engine(jf_engine *e) {
     DeviceGuard bind(e);  // (outlives the delete: the buffers are freed on the engine's device)
     if (e->rv_side) (void)hipStreamSynchronize(e->rv_side);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
-    for (auto *pool : {&e->ev_prep, &e->ev_fused, &e->ev_mix, &e->ev_reverb, &e->ev_spec})
+    for (auto *pool : {&e->ev_prep, &e->ev_fused, &e->ev_mix, &e->ev_reverb, &e->ev_spec, &e->ev_pose})
         for (auto &p : *pool) {
             (void)hipEventDestroy(p.a);
             (void)hipEventDestroy(p.b);
@@ -995,7 +1009,16 @@ int jf_engine_set_buses(jf_engine *e, int n_buses) {
     e->d_bus_list = std::move(d_list);
     e->d_bus_seg = std::move(d_seg);
     e->pa_block.swap(pa);
-    e->n_buses = n_buses;
+    {
+        // the listeners that remain keep their poses, new ones are the reference's
+        std::lock_guard<std::mutex> lk(e->pos_mu);
+        if (!e->pose.empty()) {
+            const size_t have = e->pose.size();
+            e->pose.resize((size_t)kPoseFloats * nb, 0.0f);
+            for (size_t i = have; i < e->pose.size(); i += kPoseFloats) e->pose[i + 3] = 1.0f;
+        }
+        e->n_buses = n_buses;
+    }
     e->own_mix_blocks = 0;
     e->ahead.valid = false;
     return form_order(e);
@@ -1033,6 +1056,7 @@ int jf_source_set_cartesian(jf_engine *e, int src, float x, float y, float z) {
     if (!elevation_ok(e, rec[0])) return fail(e, JF_ERR_RANGE, elevation_msg(e));
     std::lock_guard<std::mutex> lk(e->pos_mu);
     e->pos[src] = HostPos{rec[0], rec[1], r, x, y, z};
+    if (!e->world_on.empty()) e->world_on[src] = 0;  // head-relative again
     return JF_OK;
     });
 }
@@ -1046,6 +1070,7 @@ int jf_source_set_spherical(jf_engine *e, int src, float ele, float azi, float r
     if (!(fabsf(rec[1]) < 1.0e6f) || !(fabsf(r) < 3.0e38f)) return fail(e, JF_ERR_RANGE, "non-finite azimuth or radius");
     std::lock_guard<std::mutex> lk(e->pos_mu);
     e->pos[src] = HostPos{rec[0], rec[1], r, rec[2], rec[3], rec[4]};
+    if (!e->world_on.empty()) e->world_on[src] = 0;  // head-relative again
     return JF_OK;
     });
 }
@@ -1062,6 +1087,81 @@ int jf_source_get_position(const jf_engine *e, int src, float out[6]) {
     out[3] = q.x;
     out[4] = q.y;
     out[5] = q.z;
+    return JF_OK;
+    });
+}
+
+// ---- listener poses ------------------------------------------
+static const char *kPoseArgMsg = "a non-finite value, or a quaternion whose norm is further than 1e-3 from 1";
+
+int jf_listener_set_pose(jf_engine *e, int bus, const float position[3], const float orientation[4]) {
+    return jf_guard([&]() -> int {
+    if (!e) return JF_ERR_ARG;
+    if (!position || !orientation) return fail(e, JF_ERR_ARG, "null pose");
+    const float p[kPoseFloats] = {position[0], position[1], position[2], orientation[0], orientation[1], orientation[2], orientation[3]};
+    if (!pose_valid(p)) return fail(e, JF_ERR_ARG, kPoseArgMsg);
+    std::lock_guard<std::mutex> lk(e->pos_mu);
+    if (bus < 0 || bus >= e->n_buses) return fail(e, JF_ERR_ARG, "bad bus index");
+    if (e->pose.empty()) {
+        e->pose.assign((size_t)kPoseFloats * e->n_buses, 0.0f);
+        for (int b = 0; b < e->n_buses; b++) e->pose[(size_t)kPoseFloats * b + 3] = 1.0f;
+    }
+    std::copy(p, p + kPoseFloats, e->pose.begin() + (size_t)kPoseFloats * bus);
+    return JF_OK;
+    });
+}
+
+int jf_listener_get_pose(const jf_engine *e, int bus, float out[7]) {
+    return jf_guard([&]() -> int {
+    if (!e || !out) return JF_ERR_ARG;
+    jf_engine *m = const_cast<jf_engine *>(e);
+    std::lock_guard<std::mutex> lk(m->pos_mu);
+    if (bus < 0 || bus >= e->n_buses) return JF_ERR_ARG;
+    const float *p = pose_of(e, bus);
+    std::copy(p, p + kPoseFloats, out);
+    return JF_OK;
+    });
+}
+
+int jf_source_set_world(jf_engine *e, int src, float x, float y, float z) {
+    return jf_guard([&]() -> int {
+    if (!valid_src(e, src)) return fail(e, JF_ERR_ARG, "bad source index");
+    if (!pose_finite(x) || !pose_finite(y) || !pose_finite(z)) return fail(e, JF_ERR_ARG, "non-finite coordinates");
+    std::lock_guard<std::mutex> lk(e->pos_mu);
+    if (e->world_on.empty()) {
+        e->world.assign(3 * (size_t)e->S, 0.0f);
+        e->world_on.assign((size_t)e->S, 0);
+    }
+    float *w = e->world.data() + 3 * (size_t)src;
+    w[0] = x;
+    w[1] = y;
+    w[2] = z;
+    e->world_on[src] = 1;
+    return JF_OK;
+    });
+}
+
+int jf_source_get_world(const jf_engine *e, int src, float out[3]) {
+    return jf_guard([&]() -> int {
+    if (!valid_src(e, src) || !out) return JF_ERR_ARG;
+    jf_engine *m = const_cast<jf_engine *>(e);
+    std::lock_guard<std::mutex> lk(m->pos_mu);
+    if (e->world_on.empty() || !e->world_on[src]) return JF_ERR_STATE;
+    std::copy(e->world.begin() + 3 * (size_t)src, e->world.begin() + 3 * (size_t)src + 3, out);
+    return JF_OK;
+    });
+}
+
+int jf_position_from_world(const float pose[7], float x, float y, float z, float out[JF_POS_FLOATS]) {
+    return jf_guard([&]() -> int {
+    if (!pose || !out) return JF_ERR_ARG;
+    if (!pose_valid(pose) || !pose_finite(x) || !pose_finite(y) || !pose_finite(z)) return JF_ERR_ARG;
+    const PoseRecord r = pose_rule(pose, x, y, z);
+    out[0] = r.ele;
+    out[1] = r.azi;
+    out[2] = r.x;
+    out[3] = r.y;
+    out[4] = r.z;
     return JF_OK;
     });
 }
@@ -1139,6 +1239,7 @@ static int submit_block(jf_engine *e, const float *in, bool interleaved) {
     if (e->in_flight) return fail(e, JF_ERR_STATE, "a block is already in flight");
     if (device_fault(e)) return fail(e, JF_ERR_DEVICE, kHandOffMsg);
     e->last_ingest = false;
+    e->last_pose = false;
     if (e->paused.load(std::memory_order_relaxed)) {  // Audio.cu:101: nothing is consumed (live input is dropped), output is silence
         JF_HIP(e, hipMemsetAsync(e->d_mix, 0, sizeof(float) * 2 * e->B * e->n_buses, e->stream));
         e->own_mix_blocks = 0;  // (d_mix no longer holds the last jf_batch_run's blocks)
@@ -1358,40 +1459,31 @@ int jf_set_pause(jf_engine *e, int paused) {
 }
 
 // ---- batch -----------------------------------------------------------------
-static int upload_positions(jf_engine *e, int total_blocks, const float *positions) {
-    return jf_guard([&]() -> int {
-    DeviceGuard bind(e);
-    if (!e || total_blocks <= 0 || !positions) return fail(e, JF_ERR_ARG, "bad trajectory");
+// The trajectory buffer for total_blocks blocks; whatever was prepared for the trajectory before is void.
+static int traj_begin(jf_engine *e, int total_blocks) {
     JF_HIP(e, hipStreamSynchronize(e->stream));
     e->traj_gen++;
     e->ahead.valid = false;
-    const size_t bytes = sizeof(float) * 5 * (size_t)e->S * (size_t)total_blocks;
     if (total_blocks > e->traj_blocks) {
         e->d_traj.reset();  // (before the larger one is allocated: the two never exist side by side)
         e->traj_blocks = 0;
-        JF_HIP(e, e->d_traj.alloc(bytes / sizeof(float)));
+        JF_HIP(e, e->d_traj.alloc((size_t)5 * e->S * (size_t)total_blocks));
     }
     e->traj_blocks = total_blocks;
-    JF_HIP(e, h2d(e, e->d_traj, positions, bytes));
-    // how many items of every block move (their (ele, azi) differ from the block before; block 0 counts as staying):
-    // what decides whether a run reads pre-interpolated rows (jf_engine::interp_use)
-    e->traj_moved.assign((size_t)total_blocks + 1, 0u);
-    if (e->interp_avail)
-        for (int b = 1; b < total_blocks; b++) {
-            const float *p1 = positions + (size_t)b * e->S * 5, *p0 = p1 - (size_t)e->S * 5;
-            unsigned n = 0;
-            for (int s = 0; s < e->S; s++) n += p1[5 * s] != p0[5 * s] || p1[5 * s + 1] != p0[5 * s + 1];
-            e->traj_moved[(size_t)b + 1] = e->traj_moved[b] + n;
-        }
-    // Processing order of the pair kernel: a unit sums G sources that are next to each other in this order.  With
-    // automatic grouping the sources are ordered by the table row nearest to their first position, so that the units a
-    // compute unit works on at a time read neighbouring rows of the 5.8 MB table (the L2 of an XCD holds 4 MB); the mix is
-    // the same sum in another association.  jf_debug_set_source_group pins consecutive sources (identity order).
-    // With output buses the key is (bus, nearest row, s) and units never span buses (host_bus_plan); the keys stay in the
-    // engine, for the order to be formed again when a source changes its bus.
+    return JF_OK;
+}
+
+// Processing order of the pair kernel from a trajectory's first block of records, first[S][5]: a unit sums G sources that are
+// next to each other in this order.  With
+// automatic grouping the sources are ordered by the table row nearest to their first position, so that the units a
+// compute unit works on at a time read neighbouring rows of the 5.8 MB table (the L2 of an XCD holds 4 MB); the mix is
+// the same sum in another association.  jf_debug_set_source_group pins consecutive sources (identity order).
+// With output buses the key is (bus, nearest row, s) and units never span buses (host_bus_plan); the keys stay in the
+// engine, for the order to be formed again when a source changes its bus.
+static int traj_order(jf_engine *e, const float *first) {
     const bool want_sorted = e->src_group == 0 && e->S > 1;
     for (int s = 0; s < e->S; s++) {
-        const float *p = positions + 5 * (size_t)s;
+        const float *p = first + 5 * (size_t)s;
         const bool ok = p[0] > -1.0e6f && p[0] < 1.0e6f && p[1] > -1.0e6f && p[1] < 1.0e6f;
         int near = 0;
         if (want_sorted && ok) near = e->rt.cloud.tri ? std::max(0, cloud_pick(e->cloud_host, p[0], p[1])) : ring_pick_hrtf(e->rt, p[0], p[1]);
@@ -1403,6 +1495,109 @@ static int upload_positions(jf_engine *e, int total_blocks, const float *positio
     }
     e->sorted_order = want_sorted && e->N == kN;
     return JF_OK;
+}
+
+static int upload_positions(jf_engine *e, int total_blocks, const float *positions) {
+    return jf_guard([&]() -> int {
+    DeviceGuard bind(e);
+    if (!e || total_blocks <= 0 || !positions) return fail(e, JF_ERR_ARG, "bad trajectory");
+    {
+        const int rc = traj_begin(e, total_blocks);
+        if (rc) return rc;
+    }
+    JF_HIP(e, h2d(e, e->d_traj, positions, sizeof(float) * 5 * (size_t)e->S * (size_t)total_blocks));
+    // how many items of every block move (their (ele, azi) differ from the block before; block 0 counts as staying):
+    // what decides whether a run reads pre-interpolated rows (jf_engine::interp_use)
+    e->traj_moved.assign((size_t)total_blocks + 1, 0u);
+    if (e->interp_avail)
+        for (int b = 1; b < total_blocks; b++) {
+            const float *p1 = positions + (size_t)b * e->S * 5, *p0 = p1 - (size_t)e->S * 5;
+            unsigned n = 0;
+            for (int s = 0; s < e->S; s++) n += p1[5 * s] != p0[5 * s] || p1[5 * s + 1] != p0[5 * s + 1];
+            e->traj_moved[(size_t)b + 1] = e->traj_moved[b] + n;
+        }
+    return traj_order(e, positions);
+    });
+}
+
+// jf_batch_upload_world: the trajectory formed ON THE DEVICE (pose_kernel into d_traj) from world[K][S][3] and poses[K][n_buses][7].
+// Everything is checked on the host before anything is launched.
+static int upload_world(jf_engine *e, int total_blocks, const float *world, const float *poses) {
+    return jf_guard([&]() -> int {
+    DeviceGuard bind(e);
+    if (!e || total_blocks <= 0 || !world || !poses) return fail(e, JF_ERR_ARG, "bad world trajectory");
+    const size_t S = (size_t)e->S, nb = (size_t)e->n_buses, K = (size_t)total_blocks;
+    if (K * S > (size_t)0x7fffffff / 8) return fail(e, JF_ERR_ARG, "too many records for one call");
+    if (!world_args_ok(world, K * S, poses, K * nb)) return fail(e, JF_ERR_ARG, kPoseArgMsg);
+    {
+        const int rc = traj_begin(e, total_blocks);
+        if (rc) return rc;
+    }
+    if (total_blocks > e->pose_cap_blocks) {
+        e->d_world.reset();
+        e->pose_cap_blocks = 0;
+        JF_HIP(e, e->d_world.alloc(K * S * 3));
+        e->pose_cap_blocks = total_blocks;
+    }
+    if (K * nb * kPoseFloats > e->pose_cap_floats) {
+        e->d_poses.reset();
+        e->pose_cap_floats = 0;
+        JF_HIP(e, e->d_poses.alloc(K * nb * kPoseFloats));
+        e->pose_cap_floats = K * nb * kPoseFloats;
+    }
+    if (nb > 1 && e->bus != e->pose_bus_dev) {  // (one bus: the kernel takes bus 0 for every source)
+        if (!e->d_pose_bus) JF_HIP(e, e->d_pose_bus.alloc(S));
+        JF_HIP(e, hipMemcpyAsync(e->d_pose_bus, e->bus.data(), sizeof(int) * S, hipMemcpyHostToDevice, e->stream));
+        e->pose_bus_dev = e->bus;
+    }
+    JF_HIP(e, hipMemcpyAsync(e->d_world, world, sizeof(float) * K * S * 3, hipMemcpyHostToDevice, e->stream));
+    JF_HIP(e, hipMemcpyAsync(e->d_poses, poses, sizeof(float) * K * nb * kPoseFloats, hipMemcpyHostToDevice, e->stream));
+    const bool timed = e->profiling >= 2;
+    if (timed && e->ev_pose.empty()) {
+        EventPair q;
+        if (hipEventCreate(&q.a) != hipSuccess || hipEventCreate(&q.b) != hipSuccess) return fail(e, JF_ERR_DEVICE, "hipEventCreate failed");
+        e->ev_pose.push_back(q);
+    }
+    if (timed) JF_HIP(e, hipEventRecord(e->ev_pose[0].a, e->stream));
+    JF_HIP(e, launch_pose(e->d_world, nb > 1 ? e->d_pose_bus.p : nullptr, e->d_poses, e->d_traj, e->S, total_blocks, e->n_buses,
+                          e->stream));
+    if (timed) JF_HIP(e, hipEventRecord(e->ev_pose[0].b, e->stream));
+    // While the kernel runs: an UPPER bound of the items that move, from the inputs alone -- a source whose world position
+    // and whose listener's pose are the block before's, bit for bit, has the block before's record (jf_engine::interp_use; a
+    // source that moves within its whole degrees is counted as moving)
+    e->traj_moved.assign(K + 1, 0u);
+    if (e->interp_avail) {
+        std::vector<char> turned(nb);
+        for (size_t b = 1; b < K; b++) {
+            const float *q1 = poses + b * nb * kPoseFloats, *q0 = q1 - nb * kPoseFloats;
+            for (size_t u = 0; u < nb; u++) turned[u] = memcmp(q1 + u * kPoseFloats, q0 + u * kPoseFloats, sizeof(float) * kPoseFloats) != 0;
+            const float *w1 = world + b * S * 3, *w0 = w1 - S * 3;
+            unsigned n = 0;
+            for (size_t s2 = 0; s2 < S; s2++)
+                n += turned[nb > 1 ? (size_t)e->bus[s2] : 0] || memcmp(w1 + 3 * s2, w0 + 3 * s2, sizeof(float) * 3) != 0;
+            e->traj_moved[b + 1] = e->traj_moved[b] + n;
+        }
+    }
+    // ... and block 0's records by the host twin: the sort key of automatic grouping
+    std::vector<float> first(5 * S);
+    for (size_t s2 = 0; s2 < S; s2++) {
+        const PoseRecord r = pose_rule(poses + (nb > 1 ? (size_t)e->bus[s2] : 0) * kPoseFloats, world[3 * s2], world[3 * s2 + 1], world[3 * s2 + 2]);
+        float *d = first.data() + 5 * s2;
+        d[0] = r.ele;
+        d[1] = r.azi;
+        d[2] = r.x;
+        d[3] = r.y;
+        d[4] = r.z;
+    }
+    JF_HIP(e, hipStreamSynchronize(e->stream));  // (the caller's arrays are free again; form_order wants the stream idle)
+    if (timed) {
+        float ms = 0.0f;
+        JF_HIP(e, hipEventElapsedTime(&ms, e->ev_pose[0].a, e->ev_pose[0].b));
+        e->pose_ms += ms;
+        e->pose_launches++;
+    }
+    e->last_pose = true;
+    return traj_order(e, first.data());
     });
 }
 
@@ -1426,12 +1621,18 @@ static const char *kLiveResidentMsg = "the device-resident batch form does not t
 
 int jf_batch_upload_positions(jf_engine *e, int total_blocks, const float *positions) {
     if (e && e->n_live > 0) return jf_guard([&]() -> int { return fail(e, JF_ERR_STATE, kLiveResidentMsg); });
+    if (e) e->last_pose = false;
     return upload_positions(e, total_blocks, positions);
+}
+
+int jf_batch_upload_world(jf_engine *e, int total_blocks, const float *world, const float *poses) {
+    if (e && e->n_live > 0) return jf_guard([&]() -> int { return fail(e, JF_ERR_STATE, kLiveResidentMsg); });
+    return upload_world(e, total_blocks, world, poses);
 }
 
 int jf_batch_run(jf_engine *e, int first_block, int n_blocks, float *d_out_mix) {
     if (e && e->n_live > 0) return jf_guard([&]() -> int { return fail(e, JF_ERR_STATE, kLiveResidentMsg); });
-    if (e) e->last_ingest = false;
+    if (e) e->last_ingest = e->last_pose = false;
     return batch_run(e, first_block, n_blocks, d_out_mix);
 }
 
@@ -1508,14 +1709,18 @@ int jf_synchronize(jf_engine *e) {
 }
 
 // in: [n_live][n_blocks B] (null: zeros), ignored by an engine without live sources
-static int process_batch(jf_engine *e, int n_blocks, const float *in, const float *positions, float *out_mix) {
+// positions [n_blocks][S][5], or (positions == null) world [n_blocks][S][3] + poses [n_blocks][n_buses][7]: jf_process_batch_world
+static int process_batch(jf_engine *e, int n_blocks, const float *in, const float *positions, const float *world,
+                         const float *poses, float *out_mix) {
     return jf_guard([&]() -> int {
     DeviceGuard bind(e);
-    if (!e || !positions || !out_mix || n_blocks <= 0) return fail(e, JF_ERR_ARG, "bad batch arguments");
+    if (!e || (!positions && (!world || !poses)) || !out_mix || n_blocks <= 0) return fail(e, JF_ERR_ARG, "bad batch arguments");
     if (e->n_live > 0 && e->in_flight) return fail(e, JF_ERR_STATE, "a per-block call is in flight");  // (before its input is touched)
-    int rc = upload_positions(e, n_blocks, positions);
+    int rc = positions ? upload_positions(e, n_blocks, positions) : upload_world(e, n_blocks, world, poses);
     if (rc) return rc;
+    e->last_pose = positions == nullptr;
     const size_t blk = (size_t)2 * e->B;
+    std::vector<float> last_rec;  // a world call: the last block's records by the host twin
     for (int b0 = 0; b0 < n_blocks; b0 += e->maxK) {
         const int k = n_blocks - b0 < e->maxK ? n_blocks - b0 : e->maxK;
         e->last_ingest = false;
@@ -1533,20 +1738,52 @@ static int process_batch(jf_engine *e, int n_blocks, const float *in, const floa
         else  // this window's [n_buses][k][2B] into the call's [n_buses][n_blocks][2B]: a row per bus
             JF_HIP(e, hipMemcpy2DAsync(out_mix + (size_t)b0 * blk, sizeof(float) * blk * n_blocks, e->d_mix, sizeof(float) * blk * k,
                                        sizeof(float) * blk * k, (size_t)e->n_buses, hipMemcpyDeviceToHost, e->stream));
+        if (!positions && b0 + k == n_blocks) {
+            // while the last window runs: where the sources will stand afterwards (what pose_kernel wrote for the last block,
+            // bit for bit)
+            const float *w = world + (size_t)(n_blocks - 1) * e->S * 3, *q = poses + (size_t)(n_blocks - 1) * e->n_buses * kPoseFloats;
+            last_rec.resize((size_t)5 * e->S);
+            for (int s = 0; s < e->S; s++) {
+                const PoseRecord r = pose_rule(q + (size_t)kPoseFloats * (e->n_buses > 1 ? e->bus[s] : 0), w[3 * s], w[3 * s + 1], w[3 * s + 2]);
+                float *d = last_rec.data() + 5 * (size_t)s;
+                d[0] = r.ele;
+                d[1] = r.azi;
+                d[2] = r.x;
+                d[3] = r.y;
+                d[4] = r.z;
+            }
+        }
         JF_HIP(e, hipStreamSynchronize(e->stream));
         if (device_fault(e)) return fail(e, JF_ERR_DEVICE, kHandOffMsg);
     }
     // n_blocks callbacks have run: the sources stand where the last of them read them
-    return jf_sources_set_latched(e, positions + (size_t)(n_blocks - 1) * e->S * JF_POS_FLOATS);
+    if (positions) return jf_sources_set_latched(e, positions + (size_t)(n_blocks - 1) * e->S * JF_POS_FLOATS);
+    // ... every source world-placed at the last block's position, every listener at the last block's pose, the latched
+    // records the last block's (the host twin's)
+    std::lock_guard<std::mutex> lk(e->pos_mu);
+    const float *w = world + (size_t)(n_blocks - 1) * e->S * 3, *q = poses + (size_t)(n_blocks - 1) * e->n_buses * kPoseFloats;
+    e->pose.assign(q, q + (size_t)e->n_buses * kPoseFloats);
+    e->world.assign(w, w + (size_t)e->S * 3);
+    e->world_on.assign((size_t)e->S, 1);
+    for (int s = 0; s < e->S; s++) {
+        const float *r = last_rec.data() + 5 * (size_t)s;
+        e->pos[s] = HostPos{r[0], r[1], sqrtf(r[2] * r[2] + r[3] * r[3] + r[4] * r[4]), r[2], r[3], r[4]};
+    }
+    return JF_OK;
     });
 }
 
 int jf_process_batch(jf_engine *e, int n_blocks, const float *positions, float *out_mix) {
-    return process_batch(e, n_blocks, nullptr, positions, out_mix);
+    return process_batch(e, n_blocks, nullptr, positions, nullptr, nullptr, out_mix);
 }
 
 int jf_process_batch_in(jf_engine *e, int n_blocks, const float *in, const float *positions, float *out_mix) {
-    return process_batch(e, n_blocks, in, positions, out_mix);
+    return process_batch(e, n_blocks, in, positions, nullptr, nullptr, out_mix);
+}
+
+int jf_process_batch_world(jf_engine *e, int n_blocks, const float *in, const float *world, const float *poses, float *out_mix) {
+    if (e && (!world || !poses)) return jf_guard([&]() -> int { return fail(e, JF_ERR_ARG, "null world positions or poses"); });
+    return process_batch(e, n_blocks, in, nullptr, world, poses, out_mix);
 }
 
 int jf_sources_set_latched(jf_engine *e, const float *records) {
@@ -1557,6 +1794,7 @@ int jf_sources_set_latched(jf_engine *e, const float *records) {
         const float *r = records + (size_t)s * JF_POS_FLOATS;
         e->pos[s] = HostPos{r[0], r[1], sqrtf(r[2] * r[2] + r[3] * r[3] + r[4] * r[4]), r[2], r[3], r[4]};
     }
+    std::fill(e->world_on.begin(), e->world_on.end(), 0);  // head-relative again, every one
     return JF_OK;
     });
 }

@@ -109,6 +109,17 @@ int jf_profile_enable(jf_engine *e, int enable) {
     e->profiling = enable < 0 ? 0 : (enable > 2 ? 2 : enable);
     e->ev_used = 0;
     e->profile_calls = 0;
+    e->pose_ms = 0.0;
+    e->pose_launches = 0;
+    return JF_OK;
+    });
+}
+
+int jf_profile_read_pose(jf_engine *e, double *pose_ms, long *launches) {
+    return jf_guard([&]() -> int {
+    if (!e || !pose_ms) return JF_ERR_ARG;
+    *pose_ms = e->pose_ms;
+    if (launches) *launches = e->pose_launches;
     return JF_OK;
     });
 }
@@ -368,6 +379,43 @@ int jf_debug_interp_device(jf_engine *e, int n, const float *ele, const float *a
     });
 }
 
+// pose_kernel alone (jf_pose.hip) on arrays of the caller's sizes; the engine lends its device and stream, nothing of its state
+// is read or changed
+int jf_debug_pose_device(jf_engine *e, int n_blocks, int n_sources, int n_buses, const int *bus, const float *world,
+                         const float *poses, float *out) {
+    return jf_guard([&]() -> int {
+    DeviceGuard bind(e);
+    if (!e || n_blocks <= 0 || n_sources <= 0 || n_buses <= 0 || n_buses > JF_MAX_BUSES || !world || !poses || !out) return JF_ERR_ARG;
+    const size_t K = (size_t)n_blocks, S = (size_t)n_sources, nb = (size_t)n_buses;
+    if (K * S > (size_t)0x7fffffff / 8) return fail(e, JF_ERR_ARG, "too many records for one call");
+    for (size_t s = 0; bus && s < S; s++)
+        if (bus[s] < 0 || bus[s] >= n_buses) return fail(e, JF_ERR_ARG, "bad bus index");
+    if (!world_args_ok(world, K * S, poses, K * nb)) return fail(e, JF_ERR_ARG, "a non-finite value, or a quaternion whose norm is further than 1e-3 from 1");
+    DevBuf<float> d_w, d_q, d_o;
+    DevBuf<int> d_b;
+    JF_HIP(e, d_w.alloc(K * S * 3));
+    JF_HIP(e, d_q.alloc(K * nb * kPoseFloats));
+    JF_HIP(e, d_o.alloc(K * S * 5));
+    if (bus) {
+        JF_HIP(e, d_b.alloc(S));
+        JF_HIP(e, h2d(e, d_b, bus, sizeof(int) * S));
+    }
+    JF_HIP(e, h2d(e, d_w, world, sizeof(float) * K * S * 3));
+    JF_HIP(e, h2d(e, d_q, poses, sizeof(float) * K * nb * kPoseFloats));
+    JF_HIP(e, launch_pose(d_w, d_b, d_q, d_o, n_sources, n_blocks, n_buses, e->stream));
+    JF_HIP(e, hipStreamSynchronize(e->stream));
+    JF_HIP(e, hipMemcpy(out, d_o, sizeof(float) * K * S * 5, hipMemcpyDeviceToHost));
+    return JF_OK;
+    });
+}
+
+// bytes of device memory the engine holds for listener poses: 0 before the first world batch call
+long long jf_debug_pose_device_bytes(const jf_engine *e) {
+    if (!e) return JF_ERR_ARG;
+    return (long long)sizeof(float) * ((long long)e->pose_cap_blocks * e->S * 3 + (long long)e->pose_cap_floats) +
+           (e->d_pose_bus ? (long long)sizeof(int) * e->S : 0);
+}
+
 int jf_debug_rfft_device(jf_engine *e, int n, const float *windows, float *spectra) {
     return jf_guard([&]() -> int {
     DeviceGuard bind(e);
@@ -396,7 +444,8 @@ const char *jf_debug_last_kernels(jf_engine *e) {
     try {
         const std::string nb = std::to_string(e->B / 64), bs = std::to_string(e->B);
         std::string k;
-        if (e->last_ingest) k = "live_ingest_kernel;";
+        if (e->last_pose) k = "pose_kernel;";
+        if (e->last_ingest) k += "live_ingest_kernel;";
         if (!e->last_rt && !e->last_prep_skipped) k += "prep_kernel;";
         const bool room = e->room.P > 0 && !e->last_rt && e->room.last_K > 0;  // (jf_engine_room.cpp)
         if (room) k += "room_send_kernel<" + bs + ">;room_fft_kernel<" + bs + ">;room_mac_kernel<" + bs + "," + std::to_string(room_mac_waves(e->B)) + ">;";

@@ -33,6 +33,7 @@
 #include "../../include/jefferson_debug.h"
 #include "jf_device.h"
 #include "jf_host.h"
+#include "jf_pose_rule.h"
 #include "jf_room.h"
 
 namespace jf {
@@ -79,6 +80,9 @@ hipError_t launch_live_ingest(const SrcSignal *d_sigs, const int *d_live_idx, co
 hipError_t launch_room_stage(const RoomParams &P, hipStream_t st);
 hipError_t launch_room_add(float *d_mix, const float *d_wet, size_t n, hipStream_t st);
 int room_mac_waves(int B);
+// listener poses (jf_pose.hip): world positions + poses -> latched records
+hipError_t launch_pose(const float *d_world, const int *d_bus, const float *d_poses, float *d_pos, int S, int K, int n_buses,
+                       hipStream_t st);
 }  // namespace jf
 
 using namespace jf;
@@ -335,6 +339,25 @@ struct jf_engine : ReverbSetup {
     std::mutex pos_mu;  // setters may come from another thread (graphics.cu:378)
     std::vector<HostPos> pos;
 
+    // LISTENER POSES (jf_listener_set_pose, jf_source_set_world).  A world-placed source's latched record is
+    // pose_rule(pose of its bus, its world position) (jf_pose_rule.h): formed on the host when a per-block call snapshots the
+    // positions, by pose_kernel (jf_pose.hip) for the world batch calls.  The host state is under pos_mu like `pos`; all of it
+    // is empty in an engine that never set a pose or a world position, and the device buffers do not exist before the first
+    // world batch call.
+    std::vector<float> pose;         // [n_buses][7] (empty: every listener is the reference's, {0,0,0, 1,0,0,0})
+    std::vector<char> world_on;      // [S] the source is world-placed (empty: none ever was)
+    std::vector<float> world;        // [S][3] its world position
+    DevBuf<float> d_world;           // [pose_cap_blocks][S][3] a world batch call's positions
+    DevBuf<float> d_poses;           // [pose_cap_blocks][pose_cap_buses][7] ... and its poses
+    DevBuf<int> d_pose_bus;          // [S] the sources' buses as pose_kernel reads them
+    std::vector<int> pose_bus_dev;   // what d_pose_bus holds (empty: nothing yet)
+    int pose_cap_blocks = 0;         // blocks d_world holds
+    size_t pose_cap_floats = 0;      // floats d_poses holds
+    bool last_pose = false;          // the last call launched pose_kernel (jf_debug_last_kernels)
+    std::vector<EventPair> ev_pose;  // profiling 2: one pair around pose_kernel, read at the end of the call that launched it
+    double pose_ms = 0.0;            // ... summed since jf_profile_enable (jf_profile_read_pose)
+    long pose_launches = 0;
+
     PinnedBuf<float> h_pos_pinned;  // [S][5]   pinned + mapped: the real-time kernel reads it in place
     PinnedBuf<float> h_out_pinned;  // [kRtMaxWgs][2B] pinned + mapped: ... and writes its workgroups' stereo blocks in place
     int rt_wgs = 0;                 // partial blocks the block in flight left there (0: one finished block)
@@ -556,5 +579,18 @@ JF_INTERNAL int ensure_interp_rows(jf_engine *e);
 JF_INTERNAL int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int first_block = -1);
 JF_INTERNAL int reset_sources(jf_engine *e, int src);
 JF_INTERNAL int form_order(jf_engine *e);  // the processing order from row_key, bus and src_group (the stream is idle)
+// listener poses: the checks every entry that takes world positions / poses makes before anything is launched
+inline bool world_args_ok(const float *world, size_t n_points, const float *poses, size_t n_poses) {
+    // (the exponent field, as integers and without an early exit: the loop over a call's 190 000 floats vectorises)
+    unsigned bad = 0;
+    for (size_t i = 0; i < 3 * n_points; i++) {
+        unsigned u;
+        memcpy(&u, world + i, sizeof u);
+        bad |= (unsigned)((u & 0x7f800000u) == 0x7f800000u);
+    }
+    bool ok = bad == 0;
+    for (size_t i = 0; i < n_poses && ok; i++) ok = pose_valid(poses + kPoseFloats * i);
+    return ok;
+}
 
 #endif  // JF_ENGINE_INTERNAL_H
