@@ -580,14 +580,58 @@ float jf_source_send(const jf_engine *e, int src); /* the level last set; 0 for 
  *   (the rule normalises what is within that).  On every refusal nothing changes.
  *
  * Not offered: jefferson_group.h, jf_render and jf_ctest have no option for poses; the angles are whole degrees also for
- * engines whose rule could use fractions (JF_FLAG_CORRECTED_INTERPOLATION, clouds); a world position per OBJECT with a
- * source -> object map (one talker heard by many listeners: today one jf_source_set_world per (listener, talker) source).
+ * engines whose rule could use fractions (JF_FLAG_CORRECTED_INTERPOLATION, clouds).  (One talker heard by many listeners --
+ * a world position per OBJECT -- is "objects" below.)
  */
 int jf_listener_set_pose(jf_engine *e, int bus, const float position[3], const float orientation[4]);
 int jf_listener_get_pose(const jf_engine *e, int bus, float out[7]);
 int jf_source_set_world(jf_engine *e, int src, float x, float y, float z);
 int jf_source_get_world(const jf_engine *e, int src, float out[3]);
 int jf_position_from_world(const float pose[7], float x, float y, float z, float out[JF_POS_FLOATS]);
+
+/* ---- objects: one world position per talker, heard by every listener ------------- */
+
+/*
+ * The reference's SoundSource IS the thing in the room: one position (SoundSource::updateFromCartesian, SoundSource.cu:20-36),
+ * one buf / length / count (cudaPart.cu:198-199), one listener.  With a listener per bus, a talker whom n listeners hear is n
+ * sources -- one per (listener, talker), each on its listener's bus; shared inputs say that they play one signal, and an OBJECT
+ * says that they are one thing in the room: one world position, set once, read by every source attached to it.
+ *
+ * An engine has n_objects objects, 0 until jf_engine_set_objects says otherwise.  An object is a world position {x, y, z},
+ * {0, 0, 0} until it is set.  A source ATTACHED to an object is world-placed at the object's position and heard by its bus's
+ * listener, exactly as if jf_source_set_world had been given the object's coordinates before every block.
+ *
+ * THE CONTRACT: every call renders bit for bit what the same call renders on an engine whose sources were each given
+ * jf_source_set_world / jf_process_batch_world with their object's coordinates -- on every kind of engine (buses, live and
+ * shared inputs, PAD_LEN 2048, sets on arbitrary directions, the one-launch real-time kernel).  An engine that never sets
+ * objects allocates nothing for them, launches what it launched and renders the same bits.
+ *
+ * jf_engine_set_objects(e, n): 0 <= n <= JF_MAX_OBJECTS; the objects that remain keep their positions, new ones stand at
+ *   {0, 0, 0}.  JF_ERR_STATE while a submitted block has not been collected, and when a source is attached to an object that
+ *   would disappear (detach it first).  jf_num_objects: the count.
+ * jf_source_set_object(e, src, obj): attach src to object obj in [0, n).  obj < 0 DETACHES: the source stays world-placed, at
+ *   the position its object holds at that moment -- nothing jumps; a source that is not attached stays as it is (JF_OK).
+ *   A setter like jf_source_set_world: callable from another thread, latched at the next block boundary.  JF_ERR_ARG for a bad
+ *   source or obj >= n.  jf_source_object: the object src is attached to, -1 for none (and for a bad index: JF_ERR_ARG is -1).
+ * jf_object_set_world(e, obj, x, y, z) / jf_object_get_world(e, obj, out[3]): setters like jf_source_set_world -- callable
+ *   from another thread, latched at the next block boundary.  JF_ERR_ARG for a bad index or a non-finite value.
+ * With the other setters: jf_source_set_world, jf_source_set_cartesian, jf_source_set_spherical and jf_sources_set_latched on
+ *   an attached source detach it first, then act as they always do.  jf_source_get_world on an attached source reads its
+ *   object's position.  jf_source_set_bus hands an attached source to the new bus's listener, as it does for every
+ *   world-placed source.  jf_process_batch_world leaves every source world-placed at a position of its own: it detaches every
+ *   source.  jf_process_batch_objects and jf_batch_upload_objects are with the batch calls below.
+ * On every refusal nothing changes.
+ *
+ * Not offered: jefferson_group.h, jf_render and jf_ctest have no option for objects; a listener whose head centre follows an
+ * object (set the pose and the object from the same coordinates); a batch call that mixes attached and unattached sources.
+ */
+#define JF_MAX_OBJECTS 65536
+int jf_engine_set_objects(jf_engine *e, int n_objects);
+int jf_num_objects(const jf_engine *e);
+int jf_source_set_object(jf_engine *e, int src, int obj);
+int jf_source_object(const jf_engine *e, int src);
+int jf_object_set_world(jf_engine *e, int obj, float x, float y, float z);
+int jf_object_get_world(const jf_engine *e, int obj, float out[3]);
 
 /* ---- convolution reverb -------------------------------- */
 
@@ -645,6 +689,26 @@ int jf_sources_set_latched(jf_engine *e, const float *records);
  */
 int jf_process_batch_world(jf_engine *e, int n_blocks, const float *in, const float *world, const float *poses, float *out_mix);
 int jf_batch_upload_world(jf_engine *e, int total_blocks, const float *world, const float *poses);
+
+/*
+ * callback_func (Audio.cu:94-163) n_blocks times for OBJECTS that move (see "objects" above; the reference's source owns its
+ * one position, SoundSource.cu:20-36): objects is [n_blocks][n_objects][3] world positions, one per object and block, poses
+ * [n_blocks][n_buses][7] as for jf_process_batch_world.  The call uploads the two and forms the records ON THE GPU
+ * (pose_object_kernel): record (k, s) = the rule of poses[k][bus of s] and objects[k][object of s] -- what
+ * jf_process_batch_world computes from world[k][s] = objects[k][object of s], bit for bit, without the host expanding or the
+ * engine checking and uploading n_blocks x n_sources positions.  Then it runs as jf_process_batch_in does: in as there (NULL is
+ * fine), out_mix as there.
+ * EVERY source must be attached to an object: otherwise JF_ERR_STATE (jf_last_error names the first source that is not), with
+ * nothing uploaded, launched or changed.
+ * Afterwards every object stands at the last block's position, every listener at the last block's pose and the sources'
+ * latched records are the last block's: a per-block call that follows continues from there.
+ * JF_ERR_ARG, checked on the host before anything is launched: NULL arrays, n_blocks <= 0, an engine without objects, a
+ * non-finite value, a quaternion whose norm is further than 1e-3 from 1.
+ * jf_batch_upload_objects is jf_batch_upload_world for such a trajectory, with exactly its rules; jf_batch_run / jf_batch_fetch
+ * are used unchanged and do not move the objects, the sources or the listeners.  JF_ERR_STATE while the engine has a live source.
+ */
+int jf_process_batch_objects(jf_engine *e, int n_blocks, const float *in, const float *objects, const float *poses, float *out_mix);
+int jf_batch_upload_objects(jf_engine *e, int total_blocks, const float *objects, const float *poses);
 
 /*
  * Device-resident form of the same loop of callbacks (Audio.cu:104-117; jf_synchronize is its

@@ -121,6 +121,15 @@ int jf_debug_room_wet(jf_engine *e, int n_blocks, float *out);
 int jf_debug_pose_device(jf_engine *e, int n_blocks, int n_sources, int n_buses, const int *bus, const float *world,
                          const float *poses, float *out);
 long long jf_debug_pose_device_bytes(const jf_engine *e);
+/* Objects (jefferson.h: jf_engine_set_objects, jf_process_batch_objects).  jf_debug_pose_objects_device runs
+ * pose_object_kernel ALONE, as jf_debug_pose_device runs pose_kernel: objects [n_blocks][n_objects][3], object_of [n_sources]
+ * (every source's object), bus as there, poses as there -> out [n_blocks][n_sources][JF_POS_FLOATS]; the sizes are the arrays',
+ * not the engine's.  JF_ERR_ARG as there, and for an object index outside [0, n_objects).  jf_debug_pose_device_bytes counts
+ * the objects calls' buffers too (objects [n_blocks][n_objects][3] and the map; they never hold world [n_blocks][n_sources][3]);
+ * jf_debug_last_kernels names pose_object_kernel, first, when the last call launched it; jf_profile_read_pose counts both
+ * kernels. */
+int jf_debug_pose_objects_device(jf_engine *e, int n_blocks, int n_sources, int n_buses, int n_objects, const int *bus,
+                                 const int *object_of, const float *objects, const float *poses, float *out);
 /* Per-kernel timing (jf_profile_enable(e, 2)) puts an event pair around pose_kernel too: the milliseconds it took and the
  * number of launches since jf_profile_enable (launches may be NULL).  Not part of jf_profile_read's figures. */
 int jf_profile_read_pose(jf_engine *e, double *pose_ms, long *launches);

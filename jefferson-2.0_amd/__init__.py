@@ -129,6 +129,15 @@ _SIGS = {
     "jf_debug_pose_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _i, _f, _f, _f]),
     "jf_debug_pose_device_bytes": (C.c_longlong, [C.c_void_p]),
     "jf_profile_read_pose": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_long)]),
+    "jf_engine_set_objects": (C.c_int, [C.c_void_p, C.c_int]),
+    "jf_num_objects": (C.c_int, [C.c_void_p]),
+    "jf_source_set_object": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "jf_source_object": (C.c_int, [C.c_void_p, C.c_int]),
+    "jf_object_set_world": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float]),
+    "jf_object_get_world": (C.c_int, [C.c_void_p, C.c_int, _f]),
+    "jf_process_batch_objects": (C.c_int, [C.c_void_p, C.c_int, _f, _f, _f, _f]),
+    "jf_batch_upload_objects": (C.c_int, [C.c_void_p, C.c_int, _f, _f]),
+    "jf_debug_pose_objects_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _i, _i, _f, _f, _f]),
     "jf_submit_block_in": (C.c_int, [C.c_void_p, _f]),
     "jf_process_block_in": (C.c_int, [C.c_void_p, _f, _f]),
     "jf_callback_in": (C.c_int, [C.c_void_p, _f, _f]),
@@ -827,14 +836,73 @@ class Engine:
         self._chk(lib().jf_debug_pose_device(self.h, K, S, nb, None if bus is None else _ip(bus), _fp(world), _fp(poses), _fp(out)))
         return out
 
+    # ---- objects (include/jefferson.h: "objects") ----
+    def set_objects(self, n):
+        self._chk(lib().jf_engine_set_objects(self.h, int(n)))
+
+    @property
+    def n_objects(self):
+        return int(lib().jf_num_objects(self.h))
+
+    def set_object(self, s, obj):
+        """attach source s to object obj; obj < 0 detaches (jf_source_set_object)"""
+        self._chk(lib().jf_source_set_object(self.h, int(s), int(obj)))
+
+    def object_of(self, s):
+        """the object source s is attached to, -1: none"""
+        return int(lib().jf_source_object(self.h, int(s)))
+
+    def set_object_world(self, obj, x, y, z):
+        self._chk(lib().jf_object_set_world(self.h, int(obj), x, y, z))
+
+    def object_world(self, obj):
+        o = np.zeros(3, np.float32)
+        self._chk(lib().jf_object_get_world(self.h, int(obj), _fp(o)))
+        return o
+
+    def _object_args(self, objects, poses):
+        objects = np.ascontiguousarray(objects, np.float32)
+        poses = np.ascontiguousarray(poses, np.float32)
+        K = objects.shape[0]
+        assert objects.shape == (K, self.n_objects, 3) and poses.shape == (K, self.n_buses, 7), (objects.shape, poses.shape)
+        return K, objects, poses
+
+    def process_batch_objects(self, objects, poses, inp=None):
+        """objects [K][n_objects][3], poses [K][n_buses][7] -> the mix of K blocks (jf_process_batch_objects)"""
+        K, objects, poses = self._object_args(objects, poses)
+        mix = self._out(K, 2 * self.B)
+        inp = None if inp is None else self._inp(inp, K * self.B)
+        self._chk(lib().jf_process_batch_objects(self.h, K, None if inp is None else _fp(inp), _fp(objects), _fp(poses), _fp(mix)))
+        return mix
+
+    def upload_objects(self, objects, poses):
+        """upload_world for a trajectory of object positions and poses (jf_batch_upload_objects)"""
+        K, objects, poses = self._object_args(objects, poses)
+        self._chk(lib().jf_batch_upload_objects(self.h, K, _fp(objects), _fp(poses)))
+
+    def pose_objects_device(self, bus, object_of, objects, poses):
+        """pose_object_kernel alone: bus [S] (or None), object_of [S], objects [K][n_obj][3], poses [K][n_buses][7] -> records
+        [K][S][5] (jefferson_debug.h: jf_debug_pose_objects_device; the sizes are the arrays', not the engine's)"""
+        objects = np.ascontiguousarray(objects, np.float32)
+        poses = np.ascontiguousarray(poses, np.float32)
+        object_of = np.ascontiguousarray(object_of, np.int32)
+        K, no, nb, S = objects.shape[0], objects.shape[1], poses.shape[1], object_of.shape[0]
+        assert objects.shape == (K, no, 3) and poses.shape == (K, nb, 7) and object_of.shape == (S,)
+        bus = None if bus is None else np.ascontiguousarray(bus, np.int32)
+        assert bus is None or bus.shape == (S,)
+        out = np.zeros((K, S, 5), np.float32)
+        self._chk(lib().jf_debug_pose_objects_device(self.h, K, S, nb, no, None if bus is None else _ip(bus), _ip(object_of),
+                                                     _fp(objects), _fp(poses), _fp(out)))
+        return out
+
     def profile_read_pose(self):
-        """(ms in pose_kernel, launches) since profile_enable(2)"""
+        """(ms in pose_kernel and pose_object_kernel, launches) since profile_enable(2)"""
         ms, n = C.c_double(), C.c_long()
         self._chk(lib().jf_profile_read_pose(self.h, C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
     def pose_device_bytes(self):
-        """device memory held for listener poses (0 before the first world batch call)"""
+        """device memory held for listener poses and objects (0 before the first world / objects batch call)"""
         return int(lib().jf_debug_pose_device_bytes(self.h))
 
     def set_latched(self, records):

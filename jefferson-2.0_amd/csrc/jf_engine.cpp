@@ -221,8 +221,22 @@ static const float *pose_of(const jf_engine *e, int bus) {
 }
 
 // A world-placed source as the listener of its bus hears it now: the host twin of pose_kernel (jf_pose_rule.h); under pos_mu
+// (an attached source stands where its object stands: DESIGN.md 4.15)
+static const float *world_of(const jf_engine *e, int s) {
+    const int o = e->object_of.empty() ? -1 : e->object_of[s];
+    return o >= 0 ? e->object_world.data() + 3 * (size_t)o : e->world.data() + 3 * (size_t)s;
+}
+
+// the source leaves its object, if it has one, and keeps the position the object holds now; under pos_mu
+static void detach_object(jf_engine *e, int s) {
+    if (e->object_of.empty() || e->object_of[s] < 0) return;
+    const float *w = world_of(e, s);
+    std::copy(w, w + 3, e->world.begin() + 3 * (size_t)s);
+    e->object_of[s] = -1;
+}
+
 static void place_world_source(jf_engine *e, int s) {
-    const float *w = e->world.data() + 3 * (size_t)s;
+    const float *w = world_of(e, s);
     const PoseRecord r = pose_rule(pose_of(e, e->bus.empty() ? 0 : e->bus[s]), w[0], w[1], w[2]);
     e->pos[s] = HostPos{r.ele, r.azi, sqrtf(r.x * r.x + r.y * r.y + r.z * r.z), r.x, r.y, r.z};
 }
@@ -1056,6 +1070,7 @@ int jf_source_set_cartesian(jf_engine *e, int src, float x, float y, float z) {
     if (!elevation_ok(e, rec[0])) return fail(e, JF_ERR_RANGE, elevation_msg(e));
     std::lock_guard<std::mutex> lk(e->pos_mu);
     e->pos[src] = HostPos{rec[0], rec[1], r, x, y, z};
+    detach_object(e, src);
     if (!e->world_on.empty()) e->world_on[src] = 0;  // head-relative again
     return JF_OK;
     });
@@ -1070,6 +1085,7 @@ int jf_source_set_spherical(jf_engine *e, int src, float ele, float azi, float r
     if (!(fabsf(rec[1]) < 1.0e6f) || !(fabsf(r) < 3.0e38f)) return fail(e, JF_ERR_RANGE, "non-finite azimuth or radius");
     std::lock_guard<std::mutex> lk(e->pos_mu);
     e->pos[src] = HostPos{rec[0], rec[1], r, rec[2], rec[3], rec[4]};
+    detach_object(e, src);
     if (!e->world_on.empty()) e->world_on[src] = 0;  // head-relative again
     return JF_OK;
     });
@@ -1132,6 +1148,7 @@ int jf_source_set_world(jf_engine *e, int src, float x, float y, float z) {
         e->world.assign(3 * (size_t)e->S, 0.0f);
         e->world_on.assign((size_t)e->S, 0);
     }
+    detach_object(e, src);
     float *w = e->world.data() + 3 * (size_t)src;
     w[0] = x;
     w[1] = y;
@@ -1147,7 +1164,8 @@ int jf_source_get_world(const jf_engine *e, int src, float out[3]) {
     jf_engine *m = const_cast<jf_engine *>(e);
     std::lock_guard<std::mutex> lk(m->pos_mu);
     if (e->world_on.empty() || !e->world_on[src]) return JF_ERR_STATE;
-    std::copy(e->world.begin() + 3 * (size_t)src, e->world.begin() + 3 * (size_t)src + 3, out);
+    const float *w = world_of(e, src);  // (its object's position, if it is attached to one)
+    std::copy(w, w + 3, out);
     return JF_OK;
     });
 }
@@ -1162,6 +1180,77 @@ int jf_position_from_world(const float pose[7], float x, float y, float z, float
     out[2] = r.x;
     out[3] = r.y;
     out[4] = r.z;
+    return JF_OK;
+    });
+}
+
+// ---- objects ----------------------------------------------------
+int jf_engine_set_objects(jf_engine *e, int n_objects) {
+    return jf_guard([&]() -> int {
+    if (!e) return JF_ERR_ARG;
+    if (n_objects < 0 || n_objects > JF_MAX_OBJECTS) return fail(e, JF_ERR_ARG, "n_objects must be 0 .. JF_MAX_OBJECTS");
+    if (e->in_flight) return fail(e, JF_ERR_STATE, "a block is in flight");
+    std::lock_guard<std::mutex> lk(e->pos_mu);
+    for (const int o : e->object_of)
+        if (o >= n_objects) return fail(e, JF_ERR_STATE, "a source is attached to an object that would disappear");
+    e->object_world.resize(3 * (size_t)n_objects, 0.0f);  // the objects that remain keep their positions
+    e->n_objects = n_objects;
+    return JF_OK;
+    });
+}
+
+int jf_num_objects(const jf_engine *e) { return e ? e->n_objects : JF_ERR_ARG; }
+
+int jf_source_set_object(jf_engine *e, int src, int obj) {
+    return jf_guard([&]() -> int {
+    if (!valid_src(e, src)) return fail(e, JF_ERR_ARG, "bad source index");
+    std::lock_guard<std::mutex> lk(e->pos_mu);
+    if (obj < 0) {
+        detach_object(e, src);  // (stays world-placed, where the object stands now)
+        return JF_OK;
+    }
+    if (obj >= e->n_objects) return fail(e, JF_ERR_ARG, "bad object index");
+    if (e->world_on.empty()) {
+        e->world.assign(3 * (size_t)e->S, 0.0f);
+        e->world_on.assign((size_t)e->S, 0);
+    }
+    if (e->object_of.empty()) e->object_of.assign((size_t)e->S, -1);
+    e->object_of[src] = obj;
+    e->world_on[src] = 1;
+    return JF_OK;
+    });
+}
+
+int jf_source_object(const jf_engine *e, int src) {
+    return jf_guard([&]() -> int {
+    if (!valid_src(e, src)) return JF_ERR_ARG;
+    jf_engine *m = const_cast<jf_engine *>(e);
+    std::lock_guard<std::mutex> lk(m->pos_mu);
+    return e->object_of.empty() || e->object_of[src] < 0 ? -1 : e->object_of[src];
+    });
+}
+
+int jf_object_set_world(jf_engine *e, int obj, float x, float y, float z) {
+    return jf_guard([&]() -> int {
+    if (!e) return JF_ERR_ARG;
+    if (!pose_finite(x) || !pose_finite(y) || !pose_finite(z)) return fail(e, JF_ERR_ARG, "non-finite coordinates");
+    std::lock_guard<std::mutex> lk(e->pos_mu);
+    if (obj < 0 || obj >= e->n_objects) return fail(e, JF_ERR_ARG, "bad object index");
+    float *w = e->object_world.data() + 3 * (size_t)obj;
+    w[0] = x;
+    w[1] = y;
+    w[2] = z;
+    return JF_OK;
+    });
+}
+
+int jf_object_get_world(const jf_engine *e, int obj, float out[3]) {
+    return jf_guard([&]() -> int {
+    if (!e || !out) return JF_ERR_ARG;
+    jf_engine *m = const_cast<jf_engine *>(e);
+    std::lock_guard<std::mutex> lk(m->pos_mu);
+    if (obj < 0 || obj >= e->n_objects) return JF_ERR_ARG;
+    std::copy(e->object_world.begin() + 3 * (size_t)obj, e->object_world.begin() + 3 * (size_t)obj + 3, out);
     return JF_OK;
     });
 }
@@ -1239,7 +1328,7 @@ static int submit_block(jf_engine *e, const float *in, bool interleaved) {
     if (e->in_flight) return fail(e, JF_ERR_STATE, "a block is already in flight");
     if (device_fault(e)) return fail(e, JF_ERR_DEVICE, kHandOffMsg);
     e->last_ingest = false;
-    e->last_pose = false;
+    e->last_pose = 0;
     if (e->paused.load(std::memory_order_relaxed)) {  // Audio.cu:101: nothing is consumed (live input is dropped), output is silence
         JF_HIP(e, hipMemsetAsync(e->d_mix, 0, sizeof(float) * 2 * e->B * e->n_buses, e->stream));
         e->own_mix_blocks = 0;  // (d_mix no longer holds the last jf_batch_run's blocks)
@@ -1520,24 +1609,68 @@ static int upload_positions(jf_engine *e, int total_blocks, const float *positio
     });
 }
 
-// jf_batch_upload_world: the trajectory formed ON THE DEVICE (pose_kernel into d_traj) from world[K][S][3] and poses[K][n_buses][7].
+// The points a world call places its sources at: one per (block, source) -- jf_process_batch_world's world [K][S][3] -- or one
+// per (block, OBJECT) with the sources' object map -- jf_process_batch_objects' objects [K][n_objects][3]
+struct WorldPoints {
+    const float *p;
+    size_t n;        // points per block: S, or n_objects
+    const int *map;  // [S] the source's point; null: its own
+    const float *at(size_t k, size_t s) const { return p + (k * n + (map ? (size_t)map[s] : s)) * 3; }
+};
+static WorldPoints world_points(const jf_engine *e, const float *points, bool by_object) {
+    return by_object ? WorldPoints{points, (size_t)e->n_objects, e->object_of_dev.data()} : WorldPoints{points, (size_t)e->S, nullptr};
+}
+// the records of block k by the host twin, rec [S][5]
+static void twin_records(const jf_engine *e, const WorldPoints &pt, const float *poses, size_t k, float *rec) {
+    const float *q = poses + k * (size_t)e->n_buses * kPoseFloats;
+    for (int s = 0; s < e->S; s++) {
+        const float *w = pt.at(k, (size_t)s);
+        const PoseRecord r = pose_rule(q + (size_t)kPoseFloats * (e->n_buses > 1 ? e->bus[s] : 0), w[0], w[1], w[2]);
+        float *d = rec + 5 * (size_t)s;
+        d[0] = r.ele;
+        d[1] = r.azi;
+        d[2] = r.x;
+        d[3] = r.y;
+        d[4] = r.z;
+    }
+}
+
+// jf_batch_upload_world / jf_batch_upload_objects: the trajectory formed ON THE DEVICE (pose_kernel / pose_object_kernel into
+// d_traj) from points -- world[K][S][3], or (by_object) objects[K][n_objects][3] -- and poses[K][n_buses][7].
 // Everything is checked on the host before anything is launched.
-static int upload_world(jf_engine *e, int total_blocks, const float *world, const float *poses) {
+static int upload_world(jf_engine *e, int total_blocks, const float *points, const float *poses, bool by_object) {
     return jf_guard([&]() -> int {
     DeviceGuard bind(e);
-    if (!e || total_blocks <= 0 || !world || !poses) return fail(e, JF_ERR_ARG, "bad world trajectory");
+    if (!e || total_blocks <= 0 || !points || !poses) return fail(e, JF_ERR_ARG, "bad world trajectory");
     const size_t S = (size_t)e->S, nb = (size_t)e->n_buses, K = (size_t)total_blocks;
     if (K * S > (size_t)0x7fffffff / 8) return fail(e, JF_ERR_ARG, "too many records for one call");
-    if (!world_args_ok(world, K * S, poses, K * nb)) return fail(e, JF_ERR_ARG, kPoseArgMsg);
+    std::vector<int> map;  // by_object: the sources' objects as the call finds them
+    size_t n_pt = S;
+    if (by_object) {
+        std::lock_guard<std::mutex> lk(e->pos_mu);
+        if (e->n_objects == 0) return fail(e, JF_ERR_ARG, "the engine has no objects (jf_engine_set_objects)");
+        n_pt = (size_t)e->n_objects;
+        for (size_t s2 = 0; s2 < S; s2++)
+            if (e->object_of.empty() || e->object_of[s2] < 0)
+                return fail(e, JF_ERR_STATE, "source " + std::to_string(s2) + " is not attached to an object: an objects call takes every source attached");
+        map = e->object_of;
+    }
+    if (!world_args_ok(points, K * n_pt, poses, K * nb)) return fail(e, JF_ERR_ARG, kPoseArgMsg);
     {
         const int rc = traj_begin(e, total_blocks);
         if (rc) return rc;
     }
-    if (total_blocks > e->pose_cap_blocks) {
+    if (!by_object && total_blocks > e->pose_cap_blocks) {
         e->d_world.reset();
         e->pose_cap_blocks = 0;
         JF_HIP(e, e->d_world.alloc(K * S * 3));
         e->pose_cap_blocks = total_blocks;
+    }
+    if (by_object && K * n_pt * 3 > e->object_cap_floats) {
+        e->d_objects.reset();
+        e->object_cap_floats = 0;
+        JF_HIP(e, e->d_objects.alloc(K * n_pt * 3));
+        e->object_cap_floats = K * n_pt * 3;
     }
     if (K * nb * kPoseFloats > e->pose_cap_floats) {
         e->d_poses.reset();
@@ -1550,7 +1683,14 @@ static int upload_world(jf_engine *e, int total_blocks, const float *world, cons
         JF_HIP(e, hipMemcpyAsync(e->d_pose_bus, e->bus.data(), sizeof(int) * S, hipMemcpyHostToDevice, e->stream));
         e->pose_bus_dev = e->bus;
     }
-    JF_HIP(e, hipMemcpyAsync(e->d_world, world, sizeof(float) * K * S * 3, hipMemcpyHostToDevice, e->stream));
+    if (by_object && map != e->object_of_dev) {
+        if (!e->d_object_of) JF_HIP(e, e->d_object_of.alloc(S));
+        e->object_of_dev.clear();  // (nothing, should the copy fail)
+        JF_HIP(e, h2d(e, e->d_object_of, map.data(), sizeof(int) * S));  // (map is a temporary: landed when this returns)
+        e->object_of_dev = map;
+    }
+    float *d_points = by_object ? e->d_objects.p : e->d_world.p;
+    JF_HIP(e, hipMemcpyAsync(d_points, points, sizeof(float) * K * n_pt * 3, hipMemcpyHostToDevice, e->stream));
     JF_HIP(e, hipMemcpyAsync(e->d_poses, poses, sizeof(float) * K * nb * kPoseFloats, hipMemcpyHostToDevice, e->stream));
     const bool timed = e->profiling >= 2;
     if (timed && e->ev_pose.empty()) {
@@ -1559,36 +1699,37 @@ static int upload_world(jf_engine *e, int total_blocks, const float *world, cons
         e->ev_pose.push_back(q);
     }
     if (timed) JF_HIP(e, hipEventRecord(e->ev_pose[0].a, e->stream));
-    JF_HIP(e, launch_pose(e->d_world, nb > 1 ? e->d_pose_bus.p : nullptr, e->d_poses, e->d_traj, e->S, total_blocks, e->n_buses,
-                          e->stream));
+    const int *d_bus = nb > 1 ? e->d_pose_bus.p : nullptr;
+    if (by_object)
+        JF_HIP(e, launch_pose_objects(d_points, e->d_object_of, d_bus, e->d_poses, e->d_traj, e->S, total_blocks, e->n_buses, (int)n_pt,
+                                      e->stream));
+    else
+        JF_HIP(e, launch_pose(d_points, d_bus, e->d_poses, e->d_traj, e->S, total_blocks, e->n_buses, e->stream));
     if (timed) JF_HIP(e, hipEventRecord(e->ev_pose[0].b, e->stream));
-    // While the kernel runs: an UPPER bound of the items that move, from the inputs alone -- a source whose world position
-    // and whose listener's pose are the block before's, bit for bit, has the block before's record (jf_engine::interp_use; a
-    // source that moves within its whole degrees is counted as moving)
+    // While the kernel runs: an UPPER bound of the items that move, from the inputs alone -- a source whose world position (its
+    // object's) and whose listener's pose are the block before's, bit for bit, has the block before's record
+    // (jf_engine::interp_use; a source that moves within its whole degrees is counted as moving)
+    const WorldPoints pt = world_points(e, points, by_object);
     e->traj_moved.assign(K + 1, 0u);
     if (e->interp_avail) {
         std::vector<char> turned(nb);
         for (size_t b = 1; b < K; b++) {
             const float *q1 = poses + b * nb * kPoseFloats, *q0 = q1 - nb * kPoseFloats;
             for (size_t u = 0; u < nb; u++) turned[u] = memcmp(q1 + u * kPoseFloats, q0 + u * kPoseFloats, sizeof(float) * kPoseFloats) != 0;
-            const float *w1 = world + b * S * 3, *w0 = w1 - S * 3;
+            const float *w1 = pt.p + b * pt.n * 3, *w0 = w1 - pt.n * 3;
             unsigned n = 0;
-            for (size_t s2 = 0; s2 < S; s2++)
-                n += turned[nb > 1 ? (size_t)e->bus[s2] : 0] || memcmp(w1 + 3 * s2, w0 + 3 * s2, sizeof(float) * 3) != 0;
+            if (pt.map)
+                for (size_t s2 = 0; s2 < S; s2++)
+                    n += turned[nb > 1 ? (size_t)e->bus[s2] : 0] || memcmp(w1 + 3 * (size_t)pt.map[s2], w0 + 3 * (size_t)pt.map[s2], sizeof(float) * 3) != 0;
+            else
+                for (size_t s2 = 0; s2 < S; s2++)
+                    n += turned[nb > 1 ? (size_t)e->bus[s2] : 0] || memcmp(w1 + 3 * s2, w0 + 3 * s2, sizeof(float) * 3) != 0;
             e->traj_moved[b + 1] = e->traj_moved[b] + n;
         }
     }
     // ... and block 0's records by the host twin: the sort key of automatic grouping
     std::vector<float> first(5 * S);
-    for (size_t s2 = 0; s2 < S; s2++) {
-        const PoseRecord r = pose_rule(poses + (nb > 1 ? (size_t)e->bus[s2] : 0) * kPoseFloats, world[3 * s2], world[3 * s2 + 1], world[3 * s2 + 2]);
-        float *d = first.data() + 5 * s2;
-        d[0] = r.ele;
-        d[1] = r.azi;
-        d[2] = r.x;
-        d[3] = r.y;
-        d[4] = r.z;
-    }
+    twin_records(e, pt, poses, 0, first.data());
     JF_HIP(e, hipStreamSynchronize(e->stream));  // (the caller's arrays are free again; form_order wants the stream idle)
     if (timed) {
         float ms = 0.0f;
@@ -1596,7 +1737,7 @@ static int upload_world(jf_engine *e, int total_blocks, const float *world, cons
         e->pose_ms += ms;
         e->pose_launches++;
     }
-    e->last_pose = true;
+    e->last_pose = by_object ? 2 : 1;
     return traj_order(e, first.data());
     });
 }
@@ -1621,18 +1762,26 @@ static const char *kLiveResidentMsg = "the device-resident batch form does not t
 
 int jf_batch_upload_positions(jf_engine *e, int total_blocks, const float *positions) {
     if (e && e->n_live > 0) return jf_guard([&]() -> int { return fail(e, JF_ERR_STATE, kLiveResidentMsg); });
-    if (e) e->last_pose = false;
+    if (e) e->last_pose = 0;
     return upload_positions(e, total_blocks, positions);
 }
 
 int jf_batch_upload_world(jf_engine *e, int total_blocks, const float *world, const float *poses) {
     if (e && e->n_live > 0) return jf_guard([&]() -> int { return fail(e, JF_ERR_STATE, kLiveResidentMsg); });
-    return upload_world(e, total_blocks, world, poses);
+    return upload_world(e, total_blocks, world, poses, false);
+}
+
+int jf_batch_upload_objects(jf_engine *e, int total_blocks, const float *objects, const float *poses) {
+    if (e && e->n_live > 0) return jf_guard([&]() -> int { return fail(e, JF_ERR_STATE, kLiveResidentMsg); });
+    return upload_world(e, total_blocks, objects, poses, true);
 }
 
 int jf_batch_run(jf_engine *e, int first_block, int n_blocks, float *d_out_mix) {
     if (e && e->n_live > 0) return jf_guard([&]() -> int { return fail(e, JF_ERR_STATE, kLiveResidentMsg); });
-    if (e) e->last_ingest = e->last_pose = false;
+    if (e) {
+        e->last_ingest = false;
+        e->last_pose = 0;
+    }
     return batch_run(e, first_block, n_blocks, d_out_mix);
 }
 
@@ -1709,16 +1858,17 @@ int jf_synchronize(jf_engine *e) {
 }
 
 // in: [n_live][n_blocks B] (null: zeros), ignored by an engine without live sources
-// positions [n_blocks][S][5], or (positions == null) world [n_blocks][S][3] + poses [n_blocks][n_buses][7]: jf_process_batch_world
+// positions [n_blocks][S][5], or (positions == null) world [n_blocks][S][3] + poses [n_blocks][n_buses][7]: jf_process_batch_world,
+// or (by_object) world = objects [n_blocks][n_objects][3] + poses: jf_process_batch_objects
 static int process_batch(jf_engine *e, int n_blocks, const float *in, const float *positions, const float *world,
-                         const float *poses, float *out_mix) {
+                         const float *poses, float *out_mix, bool by_object = false) {
     return jf_guard([&]() -> int {
     DeviceGuard bind(e);
     if (!e || (!positions && (!world || !poses)) || !out_mix || n_blocks <= 0) return fail(e, JF_ERR_ARG, "bad batch arguments");
     if (e->n_live > 0 && e->in_flight) return fail(e, JF_ERR_STATE, "a per-block call is in flight");  // (before its input is touched)
-    int rc = positions ? upload_positions(e, n_blocks, positions) : upload_world(e, n_blocks, world, poses);
+    int rc = positions ? upload_positions(e, n_blocks, positions) : upload_world(e, n_blocks, world, poses, by_object);
     if (rc) return rc;
-    e->last_pose = positions == nullptr;
+    e->last_pose = positions ? 0 : by_object ? 2 : 1;
     const size_t blk = (size_t)2 * e->B;
     std::vector<float> last_rec;  // a world call: the last block's records by the host twin
     for (int b0 = 0; b0 < n_blocks; b0 += e->maxK) {
@@ -1739,31 +1889,31 @@ static int process_batch(jf_engine *e, int n_blocks, const float *in, const floa
             JF_HIP(e, hipMemcpy2DAsync(out_mix + (size_t)b0 * blk, sizeof(float) * blk * n_blocks, e->d_mix, sizeof(float) * blk * k,
                                        sizeof(float) * blk * k, (size_t)e->n_buses, hipMemcpyDeviceToHost, e->stream));
         if (!positions && b0 + k == n_blocks) {
-            // while the last window runs: where the sources will stand afterwards (what pose_kernel wrote for the last block,
-            // bit for bit)
-            const float *w = world + (size_t)(n_blocks - 1) * e->S * 3, *q = poses + (size_t)(n_blocks - 1) * e->n_buses * kPoseFloats;
+            // while the last window runs: where the sources will stand afterwards (what the pose kernel wrote for the last
+            // block, bit for bit)
             last_rec.resize((size_t)5 * e->S);
-            for (int s = 0; s < e->S; s++) {
-                const PoseRecord r = pose_rule(q + (size_t)kPoseFloats * (e->n_buses > 1 ? e->bus[s] : 0), w[3 * s], w[3 * s + 1], w[3 * s + 2]);
-                float *d = last_rec.data() + 5 * (size_t)s;
-                d[0] = r.ele;
-                d[1] = r.azi;
-                d[2] = r.x;
-                d[3] = r.y;
-                d[4] = r.z;
-            }
+            twin_records(e, world_points(e, world, by_object), poses, (size_t)n_blocks - 1, last_rec.data());
         }
         JF_HIP(e, hipStreamSynchronize(e->stream));
         if (device_fault(e)) return fail(e, JF_ERR_DEVICE, kHandOffMsg);
     }
     // n_blocks callbacks have run: the sources stand where the last of them read them
     if (positions) return jf_sources_set_latched(e, positions + (size_t)(n_blocks - 1) * e->S * JF_POS_FLOATS);
-    // ... every source world-placed at the last block's position, every listener at the last block's pose, the latched
-    // records the last block's (the host twin's)
+    // ... every source world-placed at the last block's position (a position of its own: no object has it any more), every
+    // listener at the last block's pose, the latched records the last block's (the host twin's); an objects call: every
+    // object at the last block's position, the sources attached as the call found them
     std::lock_guard<std::mutex> lk(e->pos_mu);
-    const float *w = world + (size_t)(n_blocks - 1) * e->S * 3, *q = poses + (size_t)(n_blocks - 1) * e->n_buses * kPoseFloats;
+    const WorldPoints pt = world_points(e, world, by_object);
+    const float *w = pt.p + (size_t)(n_blocks - 1) * pt.n * 3, *q = poses + (size_t)(n_blocks - 1) * e->n_buses * kPoseFloats;
     e->pose.assign(q, q + (size_t)e->n_buses * kPoseFloats);
-    e->world.assign(w, w + (size_t)e->S * 3);
+    if (by_object) {
+        e->object_world.assign(w, w + pt.n * 3);
+        e->object_of = e->object_of_dev;
+        if (e->world.empty()) e->world.assign((size_t)e->S * 3, 0.0f);
+    } else {
+        e->world.assign(w, w + (size_t)e->S * 3);
+        std::fill(e->object_of.begin(), e->object_of.end(), -1);
+    }
     e->world_on.assign((size_t)e->S, 1);
     for (int s = 0; s < e->S; s++) {
         const float *r = last_rec.data() + 5 * (size_t)s;
@@ -1786,6 +1936,11 @@ int jf_process_batch_world(jf_engine *e, int n_blocks, const float *in, const fl
     return process_batch(e, n_blocks, in, nullptr, world, poses, out_mix);
 }
 
+int jf_process_batch_objects(jf_engine *e, int n_blocks, const float *in, const float *objects, const float *poses, float *out_mix) {
+    if (e && (!objects || !poses)) return jf_guard([&]() -> int { return fail(e, JF_ERR_ARG, "null object positions or poses"); });
+    return process_batch(e, n_blocks, in, nullptr, objects, poses, out_mix, true);
+}
+
 int jf_sources_set_latched(jf_engine *e, const float *records) {
     return jf_guard([&]() -> int {
     if (!e || !records) return JF_ERR_ARG;
@@ -1795,6 +1950,7 @@ int jf_sources_set_latched(jf_engine *e, const float *records) {
         e->pos[s] = HostPos{r[0], r[1], sqrtf(r[2] * r[2] + r[3] * r[3] + r[4] * r[4]), r[2], r[3], r[4]};
     }
     std::fill(e->world_on.begin(), e->world_on.end(), 0);  // head-relative again, every one
+    std::fill(e->object_of.begin(), e->object_of.end(), -1);
     return JF_OK;
     });
 }

@@ -409,11 +409,46 @@ int jf_debug_pose_device(jf_engine *e, int n_blocks, int n_sources, int n_buses,
     });
 }
 
-// bytes of device memory the engine holds for listener poses: 0 before the first world batch call
+// pose_object_kernel alone, in the same way: objects [n_blocks][n_objects][3] and the sources' object map
+int jf_debug_pose_objects_device(jf_engine *e, int n_blocks, int n_sources, int n_buses, int n_objects, const int *bus,
+                                 const int *object_of, const float *objects, const float *poses, float *out) {
+    return jf_guard([&]() -> int {
+    DeviceGuard bind(e);
+    if (!e || n_blocks <= 0 || n_sources <= 0 || n_buses <= 0 || n_buses > JF_MAX_BUSES || n_objects <= 0 || n_objects > JF_MAX_OBJECTS ||
+        !object_of || !objects || !poses || !out)
+        return JF_ERR_ARG;
+    const size_t K = (size_t)n_blocks, S = (size_t)n_sources, nb = (size_t)n_buses, no = (size_t)n_objects;
+    if (K * S > (size_t)0x7fffffff / 8) return fail(e, JF_ERR_ARG, "too many records for one call");
+    for (size_t s = 0; s < S; s++) {
+        if (bus && (bus[s] < 0 || bus[s] >= n_buses)) return fail(e, JF_ERR_ARG, "bad bus index");
+        if (object_of[s] < 0 || object_of[s] >= n_objects) return fail(e, JF_ERR_ARG, "bad object index");
+    }
+    if (!world_args_ok(objects, K * no, poses, K * nb)) return fail(e, JF_ERR_ARG, "a non-finite value, or a quaternion whose norm is further than 1e-3 from 1");
+    DevBuf<float> d_w, d_q, d_o;
+    DevBuf<int> d_b, d_m;
+    JF_HIP(e, d_w.alloc(K * no * 3));
+    JF_HIP(e, d_q.alloc(K * nb * kPoseFloats));
+    JF_HIP(e, d_o.alloc(K * S * 5));
+    JF_HIP(e, d_m.alloc(S));
+    if (bus) {
+        JF_HIP(e, d_b.alloc(S));
+        JF_HIP(e, h2d(e, d_b, bus, sizeof(int) * S));
+    }
+    JF_HIP(e, h2d(e, d_m, object_of, sizeof(int) * S));
+    JF_HIP(e, h2d(e, d_w, objects, sizeof(float) * K * no * 3));
+    JF_HIP(e, h2d(e, d_q, poses, sizeof(float) * K * nb * kPoseFloats));
+    JF_HIP(e, launch_pose_objects(d_w, d_m, d_b, d_q, d_o, n_sources, n_blocks, n_buses, n_objects, e->stream));
+    JF_HIP(e, hipStreamSynchronize(e->stream));
+    JF_HIP(e, hipMemcpy(out, d_o, sizeof(float) * K * S * 5, hipMemcpyDeviceToHost));
+    return JF_OK;
+    });
+}
+
+// bytes of device memory the engine holds for listener poses and objects: 0 before the first world / objects batch call
 long long jf_debug_pose_device_bytes(const jf_engine *e) {
     if (!e) return JF_ERR_ARG;
-    return (long long)sizeof(float) * ((long long)e->pose_cap_blocks * e->S * 3 + (long long)e->pose_cap_floats) +
-           (e->d_pose_bus ? (long long)sizeof(int) * e->S : 0);
+    return (long long)sizeof(float) * ((long long)e->pose_cap_blocks * e->S * 3 + (long long)e->pose_cap_floats + (long long)e->object_cap_floats) +
+           (e->d_pose_bus ? (long long)sizeof(int) * e->S : 0) + (e->d_object_of ? (long long)sizeof(int) * e->S : 0);
 }
 
 int jf_debug_rfft_device(jf_engine *e, int n, const float *windows, float *spectra) {
@@ -444,7 +479,7 @@ const char *jf_debug_last_kernels(jf_engine *e) {
     try {
         const std::string nb = std::to_string(e->B / 64), bs = std::to_string(e->B);
         std::string k;
-        if (e->last_pose) k = "pose_kernel;";
+        if (e->last_pose) k = e->last_pose == 2 ? "pose_object_kernel;" : "pose_kernel;";
         if (e->last_ingest) k += "live_ingest_kernel;";
         if (!e->last_rt && !e->last_prep_skipped) k += "prep_kernel;";
         const bool room = e->room.P > 0 && !e->last_rt && e->room.last_K > 0;  // (jf_engine_room.cpp)

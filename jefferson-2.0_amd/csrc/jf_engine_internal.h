@@ -83,6 +83,9 @@ int room_mac_waves(int B);
 // listener poses (jf_pose.hip): world positions + poses -> latched records
 hipError_t launch_pose(const float *d_world, const int *d_bus, const float *d_poses, float *d_pos, int S, int K, int n_buses,
                        hipStream_t st);
+// ... the same from objects[K][n_objects][3] and the sources' object map (pose_object_kernel)
+hipError_t launch_pose_objects(const float *d_objects, const int *d_object_of, const int *d_bus, const float *d_poses, float *d_pos,
+                               int S, int K, int n_buses, int n_objects, hipStream_t st);
 }  // namespace jf
 
 using namespace jf;
@@ -353,10 +356,22 @@ struct jf_engine : ReverbSetup {
     std::vector<int> pose_bus_dev;   // what d_pose_bus holds (empty: nothing yet)
     int pose_cap_blocks = 0;         // blocks d_world holds
     size_t pose_cap_floats = 0;      // floats d_poses holds
-    bool last_pose = false;          // the last call launched pose_kernel (jf_debug_last_kernels)
+    int last_pose = 0;               // the last call launched pose_kernel (1) / pose_object_kernel (2) (jf_debug_last_kernels)
     std::vector<EventPair> ev_pose;  // profiling 2: one pair around pose_kernel, read at the end of the call that launched it
     double pose_ms = 0.0;            // ... summed since jf_profile_enable (jf_profile_read_pose)
     long pose_launches = 0;
+    // OBJECTS (jf_engine_set_objects, jf_source_set_object): a world position per object and a source ->
+    // object map.  An attached source is world-placed (world_on) at its object's position: place_world_source reads it there,
+    // the objects batch calls hand pose_object_kernel the call's objects[K][n_objects][3] and the map.  Host state under pos_mu,
+    // empty / 0 in an engine that never sets objects; the device buffers do not exist before the first objects batch call,
+    // which neither allocates nor touches d_world.
+    int n_objects = 0;
+    std::vector<float> object_world;    // [n_objects][3]
+    std::vector<int> object_of;         // [S] the source's object, -1: none (empty: none ever was attached)
+    DevBuf<float> d_objects;            // [..][n_objects][3] an objects batch call's positions
+    size_t object_cap_floats = 0;       // floats d_objects holds
+    DevBuf<int> d_object_of;            // [S] the map as pose_object_kernel reads it
+    std::vector<int> object_of_dev;     // what d_object_of holds: the map of the last objects batch call (empty: nothing yet)
 
     PinnedBuf<float> h_pos_pinned;  // [S][5]   pinned + mapped: the real-time kernel reads it in place
     PinnedBuf<float> h_out_pinned;  // [kRtMaxWgs][2B] pinned + mapped: ... and writes its workgroups' stereo blocks in place
