@@ -542,6 +542,70 @@ int jf_room_taps(const jf_engine *e); /* 0: off */
 int jf_source_set_send(jf_engine *e, int src, float level);
 float jf_source_send(const jf_engine *e, int src); /* the level last set; 0 for a bad index */
 
+/* ---- per-source gain: levels, mutes and click-free fades ------------------------ */
+
+/*
+ * The reference adds every source to the mix at unit weight (the mixing loop, Audio.cu:109-110) and can only report that the
+ * sum clipped (Audio.cu:111-113: "ALERT! CLIPPING AUDIO!").  Here every source has a LEVEL l_s, 1 until it is set, and a MUTE
+ * flag; its effective gain is g_s = muted ? 0 : l_s.  Any finite level is allowed: negative ones turn the polarity, levels
+ * above 1 amplify.  The gain is the SOURCE's, not its input's: a follower of a shared input, or one talker as each of many
+ * listeners hears them, has a level of its own; nothing of the source's delay, distance filter or position changes.
+ *
+ * THE CONTRACT.  The engine keeps g_prev[s], the gain the last rendered block ended at, and g_new[s], what the setters ask
+ * for.  For block k of a processing call the source's NEW filter set is weighted with g[k] and its OLD set with g[k - 1], where
+ * g[-1] = g_prev and g[k] = g_new for every block of a call without a gain trajectory: the weights w_t of a set become
+ * fl32(g w_t), one float32 product per term and nothing else.  Where g[k - 1] != g[k] the block is crossfaded even if the
+ * source did not move,
+ *     out[n] = (1 - fn) y(old position, g[k - 1])[n] + fn y(new position, g[k])[n],    fn = n / (B - 1),
+ * the reference's own crossfade (kernels.cu:132-137): a level change or a mute is a click-free ramp over ONE block, and it
+ * coincides with the position crossfade when the source also moves.  After a call g_prev := g of its last block.  A source
+ * whose old or new position cannot be interpolated is silent, as without gains.  A source whose gain is 0 before and after a
+ * block is skipped; its window, play position and crossfade state advance as always, so an unmute continues the signal where
+ * it would have been.
+ * SENDS ARE PRE-FADER: the room send (jf_source_set_send) and the convolution reverb (jf_reverb_set_ir) read the source's
+ * input, not its gain -- a muted source still sends; the reverb's wet signal is spatialised with the gained weights.
+ *
+ * jf_source_set_gain(e, src, level, fade): fade != 0 -- the new level is reached over the next processing call's first block;
+ *   fade == 0 -- at once, g_prev := g_new := g: for a source that starts at its level instead of blipping in from 1.
+ *   JF_ERR_ARG for a bad index or a level that is not finite.  jf_source_gain: the level last set; 1 for a bad index.
+ * jf_source_set_mute(e, src, muted, fade) / jf_source_muted (0 or 1; JF_ERR_ARG, negative, for a bad index): mute keeps the
+ *   level; unmuting returns to it, with or without the ramp.
+ * jf_sources_set_gains(e, levels[n_sources], fade): every source's level in one call (mute flags stay).  JF_ERR_ARG, with
+ *   nothing changed, for NULL or if any value is not finite.
+ * All of them are setters like jf_source_set_cartesian: callable from another thread, latched by the next processing call.
+ * jf_batch_set_gains(e, n_blocks, gains[n_blocks][n_sources]): stages a trajectory of EFFECTIVE gains for the NEXT
+ *   jf_process_batch / jf_process_batch_in / jf_process_batch_world / jf_process_batch_objects call: block k of that call uses
+ *   g[k] = gains[k] (and g[-1] = g_prev as always).  The call must have exactly n_blocks blocks; otherwise it returns
+ *   JF_ERR_STATE, the stage is dropped and nothing is rendered.  Afterwards every source's level is the last block's value and
+ *   every mute is cleared.  n_blocks == 0 drops a staged trajectory.  Consumed in chunks of max_batch_blocks, as the positions
+ *   are.  JF_ERR_ARG: NULL, n_blocks < 0, a value that is not finite.
+ * On every refusal nothing changes and the stream continues bit for bit.  A processing call that FAILS part-way (a device
+ * error in a later chunk of a batch call) leaves g_prev at the gains of the last block it launched, so the next call ramps from
+ * where the audio stopped; a trajectory staged for that call is consumed.
+ *
+ * jf_source_set_signal is a new start for the source: its level returns to 1 and its mute is cleared, at once -- give a source
+ * its signal first and its level (fade == 0) after.  Nothing else touches them:
+ * jf_source_reset, jf_source_set_bus, jf_source_share_input, jf_source_set_live, the position setters and jf_sources_set_latched
+ * leave levels and mutes alone; jf_engine_set_buses keeps them.  Paused calls do not advance g_prev: the ramp happens in the first block that
+ * is rendered.
+ *
+ * COST.  An engine is ACTIVE while some source has g_prev != 1 or g_new != 1, or a trajectory is staged.  An engine that is
+ * not active -- it never set a gain, or every gain has settled back at 1 -- allocates nothing for gains, launches exactly
+ * what it launched and renders the same bits.  While active, one small kernel rewrites the descriptors of every batch run
+ * ahead of the spatialiser, the per-block calls go through the batch pipeline with one block (as with more
+ * than one bus or a room), and whole-degree positions are weighted per block instead of read as pre-interpolated rows.
+ * Unit gain is exact: a level that is a power of two scales every sample exactly.
+ *
+ * Not offered: gain trajectories for jf_batch_run (it applies the standing gains, a changed one ramped over the run's first
+ * block); gains inside the one-launch real-time kernel; jefferson_group.h, jf_render and jf_ctest have no option for gains.
+ */
+int jf_source_set_gain(jf_engine *e, int src, float level, int fade);
+float jf_source_gain(const jf_engine *e, int src); /* the level last set; 1 for a bad index */
+int jf_source_set_mute(jf_engine *e, int src, int muted, int fade);
+int jf_source_muted(const jf_engine *e, int src);
+int jf_sources_set_gains(jf_engine *e, const float *levels /* [n_sources] */, int fade);
+int jf_batch_set_gains(jf_engine *e, int n_blocks, const float *gains /* [n_blocks][n_sources] */);
+
 /* ---- listener poses: head position and orientation per output bus --------------- */
 
 /*

@@ -255,6 +255,17 @@ int jf_debug_rfft_device(jf_engine *e, int n, const float *windows, float *spect
  * only (profiles/rt_ab.sh; was the environment variable JF_RV_SIDE_WGS until round 6). */
 int jf_debug_set_reverb_side_workgroups(jf_engine *e, int workgroups);
 
+/* Per-source gain (include/jefferson.h): the rule desc_gain_kernel applies to ONE descriptor, on the host --
+ * the header the kernel compiles (csrc/jf_gain_rule.h), so the CPU suite checks every case of it.  The arrays are a record's
+ * rows and weights of the new and the old set, *n_new / *n_old their term counts, *flags the pair-kernel layout's bits; g0 is
+ * the gain of the block before, g1 this block's, canon != 0 the pair kernel's layout.  Pure host code: no engine, no GPU.
+ * Returns 1 if the record changed, 0 if it is as it was, JF_ERR_ARG for a NULL pointer. */
+int jf_debug_gain_record(int rows_new[4], float w_new[4], int rows_old[4], float w_old[4], int *n_new, int *n_old, int *flags,
+                         float g0, float g1, int canon);
+/* ms in desc_gain_kernel since jf_profile_enable(e, 2) (beside jf_profile_read's prep_ms: the kernel runs right behind
+ * prep_kernel); 0 while no gain was active. */
+int jf_profile_read_gain(jf_engine *e, double *gain_ms);
+
 /* ---- libjefferson_group.so (jefferson_group.h): test support ------------------------------------------------------------ */
 
 typedef struct jf_group jf_group;

@@ -119,6 +119,14 @@ _SIGS = {
     "jf_source_set_send": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
     "jf_source_send": (C.c_float, [C.c_void_p, C.c_int]),
     "jf_debug_room_wet": (C.c_int, [C.c_void_p, C.c_int, _f]),
+    "jf_source_set_gain": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int]),
+    "jf_source_gain": (C.c_float, [C.c_void_p, C.c_int]),
+    "jf_source_set_mute": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "jf_source_muted": (C.c_int, [C.c_void_p, C.c_int]),
+    "jf_sources_set_gains": (C.c_int, [C.c_void_p, _f, C.c_int]),
+    "jf_batch_set_gains": (C.c_int, [C.c_void_p, C.c_int, _f]),
+    "jf_debug_gain_record": (C.c_int, [_i, _f, _i, _f, _i, _i, _i, C.c_float, C.c_float, C.c_int]),
+    "jf_profile_read_gain": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "jf_listener_set_pose": (C.c_int, [C.c_void_p, C.c_int, _f, _f]),
     "jf_listener_get_pose": (C.c_int, [C.c_void_p, C.c_int, _f]),
     "jf_source_set_world": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float]),
@@ -317,6 +325,20 @@ def interpolation(ele, azi, flags=0):
     rc = lib().jf_interpolation_ex(ele, azi, flags, _ip(idx), _fp(om)) if flags else \
         lib().jf_interpolation(ele, azi, _ip(idx), _fp(om))
     return None if rc else (idx, om)
+
+
+def gain_record(rows_new, w_new, rows_old, w_old, n_new, n_old, flags, g0, g1, canon):
+    """jf_debug_gain_record (host logic only): the per-source gain rule on one descriptor ->
+    (changed, rows_new, w_new, rows_old, w_old, n_new, n_old, flags)"""
+    rn, ro = np.array(rows_new, np.int32), np.array(rows_old, np.int32)
+    wn, wo = np.array(w_new, np.float32), np.array(w_old, np.float32)
+    assert rn.shape == ro.shape == wn.shape == wo.shape == (4,)
+    c = np.array([n_new, n_old, flags], np.int32)
+    rc = lib().jf_debug_gain_record(_ip(rn), _fp(wn), _ip(ro), _fp(wo), _ip(c[0:1]), _ip(c[1:2]), _ip(c[2:3]),
+                                    float(g0), float(g1), int(canon))
+    if rc < 0:
+        raise JfError(rc, "gain_record")
+    return bool(rc), rn, wn, ro, wo, int(c[0]), int(c[1]), int(c[2])
 
 
 def reverb_schedule(j0, K, M, fut_m):
@@ -704,6 +726,46 @@ class Engine:
 
     def send(self, s):
         return float(lib().jf_source_send(self.h, int(s)))
+
+    # ---- per-source gain (include/jefferson.h: "per-source gain") ----
+    def set_gain(self, s, level, fade=True):
+        """source s plays at `level` (1: as without gains): reached over the next call's first block, or (fade=False) at once"""
+        self._chk(lib().jf_source_set_gain(self.h, int(s), float(level), int(bool(fade))))
+
+    def gain(self, s):
+        return float(lib().jf_source_gain(self.h, int(s)))
+
+    def set_mute(self, s, on, fade=True):
+        """mute keeps the level: unmuting returns to it (jf_source_set_mute)"""
+        self._chk(lib().jf_source_set_mute(self.h, int(s), int(bool(on)), int(bool(fade))))
+
+    def muted(self, s):
+        m = lib().jf_source_muted(self.h, int(s))
+        if m < 0:
+            raise JfError(m, "bad source index")
+        return bool(m)
+
+    def set_gains(self, levels, fade=True):
+        """every source's level in one call, levels [S] (jf_sources_set_gains)"""
+        levels = np.ascontiguousarray(levels, np.float32)
+        assert levels.shape == (self.S,)
+        self._chk(lib().jf_sources_set_gains(self.h, _fp(levels), int(bool(fade))))
+
+    def stage_gains(self, gains):
+        """effective gains [K][S] for the next process_batch* call, which must have K blocks (jf_batch_set_gains); None or
+        an empty array drops a staged trajectory"""
+        if gains is None or len(gains) == 0:
+            self._chk(lib().jf_batch_set_gains(self.h, 0, None))
+            return
+        gains = np.ascontiguousarray(gains, np.float32)
+        assert gains.ndim == 2 and gains.shape[1] == self.S, gains.shape
+        self._chk(lib().jf_batch_set_gains(self.h, gains.shape[0], _fp(gains)))
+
+    def profile_read_gain(self):
+        """ms in desc_gain_kernel since profile_enable(2)"""
+        r = C.c_double()
+        self._chk(lib().jf_profile_read_gain(self.h, C.byref(r)))
+        return r.value
 
     def room_wet(self, n_blocks):
         """the room's wet contribution to the last processing call, [n_buses][n_blocks][2B] (jefferson_debug.h)"""

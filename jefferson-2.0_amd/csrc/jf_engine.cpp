@@ -91,6 +91,8 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
         if (!ep || !em) return fail(e, JF_ERR_DEVICE, "hipEventCreate failed");
         e->ev_spec_on.resize(e->ev_used + 1, 0);
         e->ev_spec_on[e->ev_used] = shared;
+        e->ev_gain_on.resize(e->ev_used + 1, 0);
+        e->ev_gain_on[e->ev_used] = 0;  // (run_gain_stage says otherwise)
         if (shared) {
             while (e->ev_spec.size() <= e->ev_used) {
                 EventPair q;
@@ -109,6 +111,9 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
     const int canon = n1024 && G > 1;  // descriptors in the pair-kernel layout
     // whole-degree positions as pre-interpolated rows: the pair kernel's descriptors only
     bool rows = canon && e->interp_avail && e->interp_use != 0;
+    // ... and never while a gain is active (jf_engine_gain.cpp): a whole row is read without its weight.  Descriptors prepared
+    // ahead WITH rows then differ in `mode` below and are prepared again
+    if (e->gain_on) rows = false;
     if (rows && e->interp_use == 2 && first_block >= 0 && (size_t)(first_block + K) < e->traj_moved.size()) {
         const double moved = (double)(e->traj_moved[first_block + K] - e->traj_moved[first_block]) / (double)n_items;
         rows = moved <= kInterpMovedMax;
@@ -134,6 +139,13 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
     if (ep) JF_HIP(e, hipEventRecord(ep->a, e->stream));
     if (!have) JF_HIP(e, launch_prep(e->rt, mode_now, d_pos, e->d_state[p], e->d_desc, e->S, K, canon, e->Nc, e->stream));
     if (ep) JF_HIP(e, hipEventRecord(ep->b, e->stream));
+    // per-source gain: the run's descriptors are settled (prepared just now, or ahead and swapped in: plain ones either way) --
+    // desc_gain_kernel rewrites them once, the kernels below read them as they read any
+    e->last_gain = false;
+    if (e->gain_on) {
+        const int rc = run_gain_stage(e, K, canon, timed);
+        if (rc) return rc;
+    }
     {
         const int rc = run_reverb_stage(e, p, K);
         if (rc) return rc;
@@ -358,13 +370,15 @@ void destroy_engine(jf_engine *e) {
     DeviceGuard bind(e);  // (outlives the delete: the buffers are freed on the engine's device)
     if (e->rv_side) (void)hipStreamSynchronize(e->rv_side);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
-    for (auto *pool : {&e->ev_prep, &e->ev_fused, &e->ev_mix, &e->ev_reverb, &e->ev_spec, &e->ev_pose})
+    for (auto *pool : {&e->ev_prep, &e->ev_fused, &e->ev_mix, &e->ev_reverb, &e->ev_spec, &e->ev_pose, &e->ev_gain})
         for (auto &p : *pool) {
             (void)hipEventDestroy(p.a);
             (void)hipEventDestroy(p.b);
         }
     if (e->rv_ev_main) (void)hipEventDestroy(e->rv_ev_main);
     if (e->rv_ev_side) (void)hipEventDestroy(e->rv_ev_side);
+    for (hipEvent_t ev : e->ev_g_copy)
+        if (ev) (void)hipEventDestroy(ev);
     if (e->rv_side) (void)hipStreamDestroy(e->rv_side);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;  // every buffer goes with its owner (DevBuf, PinnedBuf), after the streams have been waited for
@@ -928,7 +942,8 @@ int jf_source_share_input(jf_engine *e, int src, int of) {
 
 int jf_source_input_of(const jf_engine *e, int src) { return valid_src(e, src) ? root_of(e, src) : JF_ERR_ARG; }
 
-int jf_source_set_signal(jf_engine *e, int src, const float *mono, size_t n) {
+// jf_source_set_signal without what it means for the source's level (jf_source_set_live turns a live source resident through it)
+static int set_signal(jf_engine *e, int src, const float *mono, size_t n) {
     return jf_guard([&]() -> int {
     DeviceGuard bind(e);
     if (!valid_src(e, src) || (n && !mono) || n > 0x7fffffffu) return fail(e, JF_ERR_ARG, "bad source or signal");
@@ -958,6 +973,13 @@ int jf_source_set_signal(jf_engine *e, int src, const float *mono, size_t n) {
     });
 }
 
+int jf_source_set_signal(jf_engine *e, int src, const float *mono, size_t n) {
+    const int rc = set_signal(e, src, mono, n);
+    // a new signal is a new start: level 1, not muted, at once (include/jefferson.h: per-source gain)
+    if (rc == JF_OK) return jf_guard([&]() -> int { gain_reset_source(e, src); return JF_OK; });
+    return rc;
+}
+
 int jf_source_set_live(jf_engine *e, int src, int live) {
     return jf_guard([&]() -> int {
     DeviceGuard bind(e);
@@ -968,7 +990,7 @@ int jf_source_set_live(jf_engine *e, int src, int live) {
     }
     const bool is_live = !e->live.empty() && e->live[src];
     if (is_live == (live != 0)) return JF_OK;
-    if (!live) return jf_source_set_signal(e, src, nullptr, 0);  // resident again, and silent
+    if (!live) return set_signal(e, src, nullptr, 0);  // resident again, and silent
     if (e->live_len == 0) {
         // a multiple of B that holds a window's worth (the kernels wrap with one conditional subtract) and a whole batch call
         const long long need = std::max<long long>(e->N, (long long)e->maxK * e->B);
@@ -1334,7 +1356,12 @@ static int submit_block(jf_engine *e, const float *in, bool interleaved) {
         e->own_mix_blocks = 0;  // (d_mix no longer holds the last jf_batch_run's blocks)
     } else {
         snapshot_positions(e, e->h_pos_pinned);
-        if (e->S <= e->rt_max_sources && !e->profiling && e->N == kN && e->n_buses == 1 && e->room.P == 0) {  // (PAD_LEN 2048, buses, a room: the batch path with K = 1)
+        {
+            const int rc = gain_latch(e);  // the levels and mutes the setters hold (jf_engine_gain.cpp)
+            if (rc) return rc;
+        }
+        GainCall gains(e);  // (nothing to settle where the call is not active: the one-launch path below)
+        if (e->S <= e->rt_max_sources && !e->profiling && e->N == kN && e->n_buses == 1 && e->room.P == 0 && !e->gain_on) {  // (PAD_LEN 2048, buses, a room, an active gain: the batch path with K = 1)
             // few sources: ONE launch does descriptors, spatialisation and mix, reading the positions
             // from and writing the stereo block to pinned host memory -- no copies, one sync
             const int p = e->cur;
@@ -1403,6 +1430,7 @@ static int submit_block(jf_engine *e, const float *in, bool interleaved) {
         e->own_mix_blocks = 0;  // (d_mix no longer holds the last jf_batch_run's blocks)
         int rc = run_blocks(e, e->d_pos_rt, 1, e->d_mix);
         if (rc) return rc;
+        gains.settle();
     }
     JF_HIP(e, hipMemcpyAsync(e->h_out_pinned, e->d_mix, sizeof(float) * 2 * e->B * e->n_buses, hipMemcpyDeviceToHost, e->stream));
     e->rt_wgs = 0;
@@ -1782,7 +1810,17 @@ int jf_batch_run(jf_engine *e, int first_block, int n_blocks, float *d_out_mix) 
         e->last_ingest = false;
         e->last_pose = 0;
     }
-    return batch_run(e, first_block, n_blocks, d_out_mix);
+    // the standing gains (no trajectory of gains here): a level that changed ramps over the run's first block
+    return jf_guard([&]() -> int {
+    DeviceGuard bind(e);
+    if (!e) return JF_ERR_ARG;
+    int rc = gain_latch(e);
+    if (rc) return rc;
+    GainCall gains(e);
+    rc = batch_run(e, first_block, n_blocks, d_out_mix);
+    if (rc == JF_OK) gains.settle();
+    return rc;
+    });
 }
 
 int jf_device_numa_node(int device, int *node) {
@@ -1866,8 +1904,15 @@ static int process_batch(jf_engine *e, int n_blocks, const float *in, const floa
     DeviceGuard bind(e);
     if (!e || (!positions && (!world || !poses)) || !out_mix || n_blocks <= 0) return fail(e, JF_ERR_ARG, "bad batch arguments");
     if (e->n_live > 0 && e->in_flight) return fail(e, JF_ERR_STATE, "a per-block call is in flight");  // (before its input is touched)
-    int rc = positions ? upload_positions(e, n_blocks, positions) : upload_world(e, n_blocks, world, poses, by_object);
+    // a trajectory jf_batch_set_gains staged for another number of blocks: refused with nothing uploaded or rendered
+    int rc = gain_traj_check(e, n_blocks);
     if (rc) return rc;
+    rc = positions ? upload_positions(e, n_blocks, positions) : upload_world(e, n_blocks, world, poses, by_object);
+    if (rc) return rc;
+    // the gains of the call: the standing ones, or the staged trajectory (kept if the positions were refused above)
+    rc = gain_latch(e, n_blocks);
+    if (rc) return rc;
+    GainCall gains(e);  // a failure below settles the blocks that were launched
     e->last_pose = positions ? 0 : by_object ? 2 : 1;
     const size_t blk = (size_t)2 * e->B;
     std::vector<float> last_rec;  // a world call: the last block's records by the host twin
@@ -1882,6 +1927,7 @@ static int process_batch(jf_engine *e, int n_blocks, const float *in, const floa
         }
         rc = batch_run(e, b0, k, nullptr);
         if (rc) return rc;
+        gains.rendered = b0 + k;
         if (e->n_buses == 1)
             JF_HIP(e, hipMemcpyAsync(out_mix + (size_t)b0 * blk, e->d_mix, sizeof(float) * blk * k, hipMemcpyDeviceToHost,
                                      e->stream));
@@ -1897,6 +1943,7 @@ static int process_batch(jf_engine *e, int n_blocks, const float *in, const floa
         JF_HIP(e, hipStreamSynchronize(e->stream));
         if (device_fault(e)) return fail(e, JF_ERR_DEVICE, kHandOffMsg);
     }
+    gains.settle(n_blocks);
     // n_blocks callbacks have run: the sources stand where the last of them read them
     if (positions) return jf_sources_set_latched(e, positions + (size_t)(n_blocks - 1) * e->S * JF_POS_FLOATS);
     // ... every source world-placed at the last block's position (a position of its own: no object has it any more), every

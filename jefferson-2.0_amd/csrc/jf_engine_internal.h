@@ -8,6 +8,8 @@
 //                         jf_reverb_set_ir / jf_reverb_rms_gain
 //   jf_engine_room.cpp    the room stage's schedule (run_room_stage, run_room_add: an auxiliary send per output bus, jf_room.hip)
 //                         and jf_room_set_ir / jf_source_set_send
+//   jf_engine_gain.cpp    per-source gain: the levels and mutes, what a processing call latches of them, the stage that applies
+//                         them to a run's descriptors (run_gain_stage, jf_gain.hip) and jf_source_set_gain / jf_batch_set_gains
 //   jf_engine_debug.cpp   every entry point of include/jefferson_debug.h (taps, timing hooks, tuning switches, accessors)
 // Not part of any interface: nothing outside csrc/ includes this file.
 #ifndef JF_ENGINE_INTERNAL_H
@@ -32,6 +34,7 @@
 #include "../../include/jefferson.h"
 #include "../../include/jefferson_debug.h"
 #include "jf_device.h"
+#include "jf_gain_rule.h"
 #include "jf_host.h"
 #include "jf_pose_rule.h"
 #include "jf_room.h"
@@ -86,6 +89,9 @@ hipError_t launch_pose(const float *d_world, const int *d_bus, const float *d_po
 // ... the same from objects[K][n_objects][3] and the sources' object map (pose_object_kernel)
 hipError_t launch_pose_objects(const float *d_objects, const int *d_object_of, const int *d_bus, const float *d_poses, float *d_pos,
                                int S, int K, int n_buses, int n_objects, hipStream_t st);
+// per-source gain (jf_gain.hip): the gains of a run onto its descriptors, behind prep_kernel
+hipError_t launch_desc_gain(ItemDesc *d_desc, const float *d_g_prev, const float *d_g_new, const float *d_g_traj, int S, int K,
+                            int canon, hipStream_t st);
 }  // namespace jf
 
 using namespace jf;
@@ -150,6 +156,8 @@ constexpr int kRtMaxWgs = 128;  // workgroups (8 or 16 waves, a source per wave 
 
 // The convolution reverb as jf_reverb_set_ir set it up: buffers and dimensions, all empty / 0 while the reverb is off
 // (free_reverb: `= {}`).  Off while rv_P == 0.
+constexpr int kGainStageSlots = 4;  // level changes whose device copies may be in line before a setter-to-run sequence waits (jf_engine_gain.cpp)
+
 struct ReverbSetup {
     int rv_P = 0, rv_Rg = 0, rv_Wr = 0;
     DevBuf<float2> d_rv_hspec;
@@ -373,6 +381,35 @@ struct jf_engine : ReverbSetup {
     DevBuf<int> d_object_of;            // [S] the map as pose_object_kernel reads it
     std::vector<int> object_of_dev;     // what d_object_of holds: the map of the last objects batch call (empty: nothing yet)
 
+    // PER-SOURCE GAIN (jf_source_set_gain, jf_batch_set_gains).  A source's effective gain is g = muted ? 0 :
+    // level; g_new is what the setters ask for, g_prev what the last rendered block used.  Block k of a call weights its new
+    // filter set with g[k] and its old set with g[k - 1] (g[-1] = g_prev): desc_gain_kernel (jf_gain.hip) rewrites the run's
+    // descriptors behind prep_kernel, the spatialiser kernels are the ones of an engine without gains.  The host state is under
+    // pos_mu like `pos`; all of it is empty in an engine that never set a gain, and the device buffers do not exist before the
+    // first ACTIVE call: one that finds a g_prev or g_new other than 1, or a staged trajectory (gain_latch).
+    std::vector<float> level, g_prev, g_new;  // [S] (empty: no gain was ever set, every one 1)
+    std::vector<char> muted;                  // [S]
+    std::vector<char> gain_snapped;           // [S] g_prev was set at once (fade == 0) since the last call latched the gains
+    std::vector<float> gain_traj;             // [gain_traj_blocks][S] staged by jf_batch_set_gains for the next jf_process_batch*
+    int gain_traj_blocks = 0;
+    // what the processing call in hand latched (its thread's alone): run_blocks reads it, gain_settle gives it back
+    bool gain_on = false;                     // the call is active
+    std::vector<float> run_g0, run_g1;        // [S] g[-1] of the next run, and the standing gains of the call
+    int gain_traj_first = -1;                 // the next run's first block in d_g_traj; -1: the call has no trajectory
+    std::vector<float> run_traj;              // the call's trajectory on the host (what gain_abort settles a failed call from)
+    bool gain_ramp = false;                   // the call's next run is its first and g[-1] differs from the standing gains
+    PinnedBuf<float> h_g_stage;               // [kGainStageSlots][2][S] pinned staging of the asynchronous copies to d_g_new / d_g_prev
+    hipEvent_t ev_g_copy[kGainStageSlots] = {};  // ... recorded behind a slot's copies: the slot is free once its event has passed
+    bool g_copy_pending[kGainStageSlots] = {};
+    int g_stage_slot = 0;                     // the slot the next upload takes
+    DevBuf<float> d_g_prev, d_g_new;          // [S]
+    std::vector<float> dev_g_prev, dev_g_new; // what they hold (empty: nothing yet)
+    DevBuf<float> d_g_traj;                   // [gain_traj_cap / S][S] the trajectory of the jf_process_batch* call in hand
+    size_t gain_traj_cap = 0;                 // floats it holds
+    bool last_gain = false;                   // the last run launched desc_gain_kernel (jf_debug_last_kernels)
+    std::vector<EventPair> ev_gain;           // profiling 2: around desc_gain_kernel (jf_profile_read_gain)
+    std::vector<char> ev_gain_on;             // ... of the timed runs that launched it
+
     PinnedBuf<float> h_pos_pinned;  // [S][5]   pinned + mapped: the real-time kernel reads it in place
     PinnedBuf<float> h_out_pinned;  // [kRtMaxWgs][2B] pinned + mapped: ... and writes its workgroups' stereo blocks in place
     int rt_wgs = 0;                 // partial blocks the block in flight left there (0: one finished block)
@@ -590,6 +627,34 @@ JF_INTERNAL bool rv_ahead_possible(const jf_engine *e);    // jf_engine_reverb.c
 JF_INTERNAL void free_reverb(jf_engine *e);                // jf_engine_reverb.cpp
 JF_INTERNAL int run_room_stage(jf_engine *e, int p, int K);           // jf_engine_room.cpp: ahead of the spatialiser
 JF_INTERNAL int run_room_add(jf_engine *e, int K, float *d_mix_out);  // jf_engine_room.cpp: behind the mix
+// per-source gain (jf_engine_gain.cpp).  gain_latch: at the start of a processing call that is not paused -- what the setters
+// hold becomes the call's (e->gain_on, run_g0, run_g1); traj_blocks >= 0: a jf_process_batch* call of that many blocks, which
+// takes a staged trajectory (JF_ERR_STATE, the stage dropped, if it was staged for another count: gain_traj_check is that
+// check alone, for a call to make before it changes anything).  run_gain_stage: from
+// run_blocks, while e->gain_on.  gain_settle: after the call's last run -- g_prev := the gains of its last block.
+JF_INTERNAL int gain_traj_check(jf_engine *e, int traj_blocks);
+JF_INTERNAL int gain_latch(jf_engine *e, int traj_blocks = -1);
+JF_INTERNAL int run_gain_stage(jf_engine *e, int K, int canon, bool timed);
+JF_INTERNAL void gain_settle(jf_engine *e, int traj_blocks = -1);
+JF_INTERNAL void gain_abort(jf_engine *e, int rendered);
+// a processing call between gain_latch and its end: settles the gains when the call succeeds, and on every other way out
+// settles what was rendered (gain_abort)
+struct GainCall {
+    jf_engine *e;
+    int rendered = 0;  // blocks of the call launched so far
+    bool done = false;
+    explicit GainCall(jf_engine *e_) : e(e_) {}
+    ~GainCall() {
+        if (!done) gain_abort(e, rendered);
+    }
+    void settle(int traj_blocks = -1) {
+        gain_settle(e, traj_blocks);
+        done = true;
+    }
+    GainCall(const GainCall &) = delete;
+    GainCall &operator=(const GainCall &) = delete;
+};
+JF_INTERNAL void gain_reset_source(jf_engine *e, int src);  // level 1, not muted, at once (jf_source_set_signal)
 JF_INTERNAL int ensure_interp_rows(jf_engine *e);
 JF_INTERNAL int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int first_block = -1);
 JF_INTERNAL int reset_sources(jf_engine *e, int src);
