@@ -606,6 +606,62 @@ int jf_source_muted(const jf_engine *e, int src);
 int jf_sources_set_gains(jf_engine *e, const float *levels /* [n_sources] */, int fade);
 int jf_batch_set_gains(jf_engine *e, int n_blocks, const float *gains /* [n_blocks][n_sources] */);
 
+/* ---- bus masters: a gain, a safety limiter and meters per output bus -------------- */
+
+/*
+ * The reference adds every source at unit weight and prints "ALERT! CLIPPING AUDIO!" when a mixed sample exceeds 1.0
+ * (Audio.cu:109-113); nothing stands on the sum.  Here every output bus has a MASTER SECTION on its finished mix -- the dry sum
+ * plus the room's wet part: a master gain, a safety limiter and meters, in that order, computed on the GPU for every form of
+ * call (per-block, jf_process_batch*, jf_batch_run -- into the engine's mix or a caller's device buffer).
+ *
+ * THE LIMITER IS A SAFETY DEVICE, NOT A MASTERING TOOL: a brick-wall limiter at BLOCK granularity.  It looks at the peak of a
+ * whole block, turns the whole block down at once when that peak is over the ceiling, and lets the gain return by `release`
+ * per block, ramped inside the block.  No look-ahead, no knee.  Its contract: NO SAMPLE OF A LIMITED BUS EXCEEDS ITS CEILING.
+ *
+ * THE RULE (csrc/jf_master_rule.h, float32, one rounding per written operation).  Per bus: m_prev, the master gain the last
+ * rendered block ended on; m_new, the gain asked for; c, the ceiling (0: limiter off); r, the release (0 < r <= 1); and the
+ * state g_prev, the limiter gain at the end of the last rendered block (initially 1).  For a block x[n][ch], n < B:
+ *   1. m[n] = m_new; on the first block of a call with m_prev != m_new, m[n] = m_prev + (m_new - m_prev) ((n + 1) (1 / B));
+ *      v = m[n] x
+ *   2. p = max |v| over the block
+ *   3. limiter on: t = p > c ? c / p : 1; g = min(t, g_prev + r); attack (g < g_prev): a[n] = g for the whole block; else
+ *      a[n] = min(g, g_prev + (g - g_prev) ((n + 1) (1 / B))); out = min(max(a[n] v, -c), c).  Limiter off: g = 1, out = v
+ *   4. the block's meters, four floats: {peak_in = p, peak_out = max |out|, sumsq_out = sum of out^2, gain = g}
+ *   5. g_prev := g; after the call m_prev := m_new
+ * With m = 1 and the limiter off out is x bit for bit.  The limiter's recurrence is sequential in float32: a run gives the
+ * same bits however it is cut into calls.
+ *
+ * jf_bus_set_master(e, bus, gain, fade): gain > 0 and finite (0 is refused with the negative values: a call with zeroed
+ *   arguments must not silence a bus for good; a bus is silenced by muting its sources).  fade != 0 -- reached over the next
+ *   rendered block; fade == 0 -- at once (m_prev := m_new := gain).  jf_bus_master: the gain last set; 1 for a bad index.
+ * jf_bus_set_limiter(e, bus, ceiling, release): ceiling 0 turns the limiter off, else finite and > 0; 0 < release <= 1 always.
+ *   Turning a limiter off and on again starts from g = 1; a new ceiling or release of a running limiter keeps g.
+ *   jf_bus_limiter reads both back (0 and 1 before anything was set).
+ * jf_engine_set_meters(e, on): the meters of every rendered call are kept.  jf_bus_meters(e, n_blocks, out): the meters of the
+ *   LAST RENDERED CALL, out[n_buses][n_blocks][4]: n_blocks is 1 for the per-block calls (for jf_callback: of the block it
+ *   handed out), else the call's.  After a jf_batch_run it brings them over from the device itself (it waits for the engine's
+ *   stream).  JF_ERR_STATE if meters are off or nothing has been rendered with them; JF_ERR_ARG for another count.
+ * The setters are setters like jf_source_set_cartesian: callable from another thread, latched by the next processing call.
+ * Refusals (JF_ERR_ARG: a bad bus index, a gain that is not positive and finite, a negative or non-finite ceiling or release,
+ * a release outside (0, 1]) change
+ * nothing.  Paused calls latch nothing and leave state and meters alone.  jf_engine_set_buses keeps the master sections of the
+ * buses that remain; new buses are neutral.  jf_last_block_peak looks at what is handed out: the mastered block.
+ *
+ * COST.  An engine is ACTIVE while some bus has m_prev or m_new != 1, some bus has a limiter on, or meters are enabled.  An
+ * engine that is not active allocates nothing for masters, launches exactly what it launched and renders the same bits.
+ * While active, three small kernels run on the mix behind the mix step of every batch run and the per-block
+ * calls go through the batch pipeline with one block (as with more than one bus, a room or a gain).
+ *
+ * Not offered: look-ahead; masters inside the one-launch real-time kernel; jefferson_group.h, jf_render and jf_ctest have no
+ * option for masters.
+ */
+int jf_bus_set_master(jf_engine *e, int bus, float gain, int fade);
+float jf_bus_master(const jf_engine *e, int bus); /* the gain last set; 1 for a bad index */
+int jf_bus_set_limiter(jf_engine *e, int bus, float ceiling, float release);
+int jf_bus_limiter(const jf_engine *e, int bus, float *ceiling, float *release);
+int jf_engine_set_meters(jf_engine *e, int on);
+int jf_bus_meters(jf_engine *e, int n_blocks, float *out /* [n_buses][n_blocks][4] */);
+
 /* ---- listener poses: head position and orientation per output bus --------------- */
 
 /*

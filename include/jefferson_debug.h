@@ -266,6 +266,17 @@ int jf_debug_gain_record(int rows_new[4], float w_new[4], int rows_old[4], float
  * prep_kernel); 0 while no gain was active. */
 int jf_profile_read_gain(jf_engine *e, double *gain_ms);
 
+/* Bus masters (include/jefferson.h): the rule the master kernels apply to ONE block, on the host -- the header
+ * the kernels compile (csrc/jf_master_rule.h), so the CPU suite checks it against a float32 model.  x and out are a block,
+ * [B][2] interleaved (out may be x); *g_state is the limiter gain before the block and, on return, after it; the block counts
+ * as a call's first: the master gain ramps iff m_prev != m_new.  meters = {peak_in, peak_out, sumsq_out, gain}; sumsq_out is
+ * summed sample by sample in float32.  Pure host code: no engine, no GPU.  JF_ERR_ARG for a NULL pointer or B <= 0. */
+int jf_debug_master_block(const float *x, int B, float m_prev, float m_new, float ceiling, float release, float *g_state, float *out,
+                          float meters[4]);
+/* ms in the master stage (master_peak_kernel, master_gain_kernel, master_apply_kernel) since jf_profile_enable(e, 2): part of
+ * jf_profile_read's mix_ms too (the stage runs inside the mix's event pair); 0 while no master was active. */
+int jf_profile_read_master(jf_engine *e, double *master_ms);
+
 /* ---- libjefferson_group.so (jefferson_group.h): test support ------------------------------------------------------------ */
 
 typedef struct jf_group jf_group;

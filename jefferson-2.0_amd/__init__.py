@@ -127,6 +127,14 @@ _SIGS = {
     "jf_batch_set_gains": (C.c_int, [C.c_void_p, C.c_int, _f]),
     "jf_debug_gain_record": (C.c_int, [_i, _f, _i, _f, _i, _i, _i, C.c_float, C.c_float, C.c_int]),
     "jf_profile_read_gain": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "jf_bus_set_master": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int]),
+    "jf_bus_master": (C.c_float, [C.c_void_p, C.c_int]),
+    "jf_bus_set_limiter": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float]),
+    "jf_bus_limiter": (C.c_int, [C.c_void_p, C.c_int, _f, _f]),
+    "jf_engine_set_meters": (C.c_int, [C.c_void_p, C.c_int]),
+    "jf_bus_meters": (C.c_int, [C.c_void_p, C.c_int, _f]),
+    "jf_debug_master_block": (C.c_int, [_f, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, _f, _f, _f]),
+    "jf_profile_read_master": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "jf_listener_set_pose": (C.c_int, [C.c_void_p, C.c_int, _f, _f]),
     "jf_listener_get_pose": (C.c_int, [C.c_void_p, C.c_int, _f]),
     "jf_source_set_world": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float]),
@@ -378,6 +386,18 @@ def share_plan(root):
 
 def pick_hrtf(ele, azi):
     return lib().jf_pick_hrtf(ele, azi)
+
+
+def master_block(x, m_prev=1.0, m_new=1.0, ceiling=0.0, release=1.0, g_prev=1.0):
+    """jf_debug_master_block (host logic only): the bus-master rule on one block x [B][2] (or [2B]) ->
+    (out [2B], meters [4] = {peak_in, peak_out, sumsq_out, gain}, the limiter gain after the block)"""
+    x = np.ascontiguousarray(x, np.float32).ravel()
+    assert x.size % 2 == 0
+    out, m, g = np.zeros_like(x), np.zeros(4, np.float32), np.array([g_prev], np.float32)
+    rc = lib().jf_debug_master_block(_fp(x), x.size // 2, m_prev, m_new, ceiling, release, _fp(g), _fp(out), _fp(m))
+    if rc:
+        raise JfError(rc, "master_block")
+    return out, m, g[0]
 
 
 def reverb_rms_gain(signal, ir):
@@ -765,6 +785,41 @@ class Engine:
         """ms in desc_gain_kernel since profile_enable(2)"""
         r = C.c_double()
         self._chk(lib().jf_profile_read_gain(self.h, C.byref(r)))
+        return r.value
+
+    # ---- bus masters (include/jefferson.h: "bus masters") ----
+    def set_master(self, bus, gain, fade=True):
+        """bus's master gain (1: neutral): reached over the next rendered block, or (fade=False) at once"""
+        self._chk(lib().jf_bus_set_master(self.h, int(bus), float(gain), int(bool(fade))))
+
+    def master(self, bus):
+        return float(lib().jf_bus_master(self.h, int(bus)))
+
+    def set_limiter(self, bus, ceiling, release=1.0):
+        """bus's safety limiter: no sample above `ceiling` (0: off); `release`: gain regained per block, in (0, 1]"""
+        self._chk(lib().jf_bus_set_limiter(self.h, int(bus), float(ceiling), float(release)))
+
+    def limiter(self, bus):
+        """(ceiling, release)"""
+        c, r = np.zeros(1, np.float32), np.zeros(1, np.float32)
+        self._chk(lib().jf_bus_limiter(self.h, int(bus), _fp(c), _fp(r)))
+        return float(c[0]), float(r[0])
+
+    def set_meters(self, on=True):
+        self._chk(lib().jf_engine_set_meters(self.h, int(bool(on))))
+
+    def meters(self, n_blocks=1):
+        """the last rendered call's meters, [n_buses][n_blocks][4] = {peak_in, peak_out, sumsq_out, gain} (jf_bus_meters)"""
+        out = np.zeros((self.n_buses, int(n_blocks), 4), np.float32)
+        self._chk(lib().jf_bus_meters(self.h, int(n_blocks), _fp(out)))
+        return out
+
+    master_block = staticmethod(master_block)
+
+    def profile_read_master(self):
+        """ms in the master stage's kernels since profile_enable(2)"""
+        r = C.c_double()
+        self._chk(lib().jf_profile_read_master(self.h, C.byref(r)))
         return r.value
 
     def room_wet(self, n_blocks):

@@ -93,6 +93,8 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
         e->ev_spec_on[e->ev_used] = shared;
         e->ev_gain_on.resize(e->ev_used + 1, 0);
         e->ev_gain_on[e->ev_used] = 0;  // (run_gain_stage says otherwise)
+        e->ev_master_on.resize(e->ev_used + 1, 0);
+        e->ev_master_on[e->ev_used] = 0;  // (run_master_stage says otherwise)
         if (shared) {
             while (e->ev_spec.size() <= e->ev_used) {
                 EventPair q;
@@ -209,6 +211,12 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
         JF_HIP(e, launch_mix(e->d_partial, d_mix_out, e->S / G, K, e->B, e->stream));
     if (e->room.P > 0) {
         const int rc = run_room_add(e, K, d_mix_out);
+        if (rc) return rc;
+    }
+    // bus masters: the finished mix -- dry sum plus the room's wet part -- through each bus's master section, in place
+    e->last_master = false;
+    if (e->master_on) {
+        const int rc = run_master_stage(e, K, d_mix_out, timed);
         if (rc) return rc;
     }
     if (ahead_ok) {
@@ -370,7 +378,7 @@ void destroy_engine(jf_engine *e) {
     DeviceGuard bind(e);  // (outlives the delete: the buffers are freed on the engine's device)
     if (e->rv_side) (void)hipStreamSynchronize(e->rv_side);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
-    for (auto *pool : {&e->ev_prep, &e->ev_fused, &e->ev_mix, &e->ev_reverb, &e->ev_spec, &e->ev_pose, &e->ev_gain})
+    for (auto *pool : {&e->ev_prep, &e->ev_fused, &e->ev_mix, &e->ev_reverb, &e->ev_spec, &e->ev_pose, &e->ev_gain, &e->ev_master})
         for (auto &p : *pool) {
             (void)hipEventDestroy(p.a);
             (void)hipEventDestroy(p.b);
@@ -378,6 +386,8 @@ void destroy_engine(jf_engine *e) {
     if (e->rv_ev_main) (void)hipEventDestroy(e->rv_ev_main);
     if (e->rv_ev_side) (void)hipEventDestroy(e->rv_ev_side);
     for (hipEvent_t ev : e->ev_g_copy)
+        if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : e->ev_m_copy)
         if (ev) (void)hipEventDestroy(ev);
     if (e->rv_side) (void)hipStreamDestroy(e->rv_side);
     if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -1053,6 +1063,7 @@ int jf_engine_set_buses(jf_engine *e, int n_buses) {
             e->pose.resize((size_t)kPoseFloats * nb, 0.0f);
             for (size_t i = have; i < e->pose.size(); i += kPoseFloats) e->pose[i + 3] = 1.0f;
         }
+        master_set_buses(e, n_buses);  // ... and their master sections, new ones are neutral
         e->n_buses = n_buses;
     }
     e->own_mix_blocks = 0;
@@ -1354,6 +1365,7 @@ static int submit_block(jf_engine *e, const float *in, bool interleaved) {
     if (e->paused.load(std::memory_order_relaxed)) {  // Audio.cu:101: nothing is consumed (live input is dropped), output is silence
         JF_HIP(e, hipMemsetAsync(e->d_mix, 0, sizeof(float) * 2 * e->B * e->n_buses, e->stream));
         e->own_mix_blocks = 0;  // (d_mix no longer holds the last jf_batch_run's blocks)
+        e->meters_stage_blocks = 0;  // (a paused call leaves the masters and the meters alone)
     } else {
         snapshot_positions(e, e->h_pos_pinned);
         {
@@ -1361,7 +1373,13 @@ static int submit_block(jf_engine *e, const float *in, bool interleaved) {
             if (rc) return rc;
         }
         GainCall gains(e);  // (nothing to settle where the call is not active: the one-launch path below)
-        if (e->S <= e->rt_max_sources && !e->profiling && e->N == kN && e->n_buses == 1 && e->room.P == 0 && !e->gain_on) {  // (PAD_LEN 2048, buses, a room, an active gain: the batch path with K = 1)
+        {
+            const int rc = master_latch(e);  // the bus masters the setters hold (jf_engine_master.cpp)
+            if (rc) return rc;
+        }
+        MasterCall masters(e);
+        e->meters_stage_blocks = 0;
+        if (e->S <= e->rt_max_sources && !e->profiling && e->N == kN && e->n_buses == 1 && e->room.P == 0 && !e->gain_on && !e->master_on) {  // (PAD_LEN 2048, buses, a room, an active gain or master: the batch path with K = 1)
             // few sources: ONE launch does descriptors, spatialisation and mix, reading the positions
             // from and writing the stereo block to pinned host memory -- no copies, one sync
             const int p = e->cur;
@@ -1431,6 +1449,11 @@ static int submit_block(jf_engine *e, const float *in, bool interleaved) {
         int rc = run_blocks(e, e->d_pos_rt, 1, e->d_mix);
         if (rc) return rc;
         gains.settle();
+        if (e->master_on && e->master_meters) {  // the block's meters come with the block (jf_collect_block)
+            rc = master_meters_copy(e, 1);
+            if (rc) return rc;
+            e->meters_stage_blocks = 1;
+        }
     }
     JF_HIP(e, hipMemcpyAsync(e->h_out_pinned, e->d_mix, sizeof(float) * 2 * e->B * e->n_buses, hipMemcpyDeviceToHost, e->stream));
     e->rt_wgs = 0;
@@ -1475,6 +1498,10 @@ int jf_collect_block(jf_engine *e, float *out) {
     if (device_fault(e)) {  // per-block calls with more than rt_max_sources sources run the pair kernel too
         e->in_flight = false;
         return fail(e, JF_ERR_DEVICE, kHandOffMsg);
+    }
+    if (e->meters_stage_blocks > 0) {
+        master_meters_land(e, 1, 0, 1);
+        e->meters_stage_blocks = 0;
     }
     const int n_out = 2 * e->B * e->n_buses;  // [n_buses][2B] (the real-time kernel: one bus)
     memcpy(out, e->h_out_pinned, sizeof(float) * n_out);
@@ -1817,8 +1844,17 @@ int jf_batch_run(jf_engine *e, int first_block, int n_blocks, float *d_out_mix) 
     int rc = gain_latch(e);
     if (rc) return rc;
     GainCall gains(e);
+    rc = master_latch(e);  // (its parameter copies are asynchronous as well: the call does not wait for the stream)
+    if (rc) return rc;
+    MasterCall masters(e);
     rc = batch_run(e, first_block, n_blocks, d_out_mix);
     if (rc == JF_OK) gains.settle();
+    // the run's meters stay on the device until jf_batch_fetch or jf_bus_meters brings them over
+    if (rc == JF_OK && e->master_on && e->master_meters) {
+        e->meters_dev_blocks = n_blocks;
+        std::lock_guard<std::mutex> lk(e->pos_mu);
+        e->meters_blocks = 0;
+    }
     return rc;
     });
 }
@@ -1913,6 +1949,9 @@ static int process_batch(jf_engine *e, int n_blocks, const float *in, const floa
     rc = gain_latch(e, n_blocks);
     if (rc) return rc;
     GainCall gains(e);  // a failure below settles the blocks that were launched
+    rc = master_latch(e);
+    if (rc) return rc;
+    MasterCall masters(e);  // (the limiter's state carries from run to run on the device; only the first run ramps)
     e->last_pose = positions ? 0 : by_object ? 2 : 1;
     const size_t blk = (size_t)2 * e->B;
     std::vector<float> last_rec;  // a world call: the last block's records by the host twin
@@ -1934,6 +1973,11 @@ static int process_batch(jf_engine *e, int n_blocks, const float *in, const floa
         else  // this window's [n_buses][k][2B] into the call's [n_buses][n_blocks][2B]: a row per bus
             JF_HIP(e, hipMemcpy2DAsync(out_mix + (size_t)b0 * blk, sizeof(float) * blk * n_blocks, e->d_mix, sizeof(float) * blk * k,
                                        sizeof(float) * blk * k, (size_t)e->n_buses, hipMemcpyDeviceToHost, e->stream));
+        const bool metered = e->master_on && e->master_meters;
+        if (metered) {
+            rc = master_meters_copy(e, k);
+            if (rc) return rc;
+        }
         if (!positions && b0 + k == n_blocks) {
             // while the last window runs: where the sources will stand afterwards (what the pose kernel wrote for the last
             // block, bit for bit)
@@ -1942,6 +1986,7 @@ static int process_batch(jf_engine *e, int n_blocks, const float *in, const floa
         }
         JF_HIP(e, hipStreamSynchronize(e->stream));
         if (device_fault(e)) return fail(e, JF_ERR_DEVICE, kHandOffMsg);
+        if (metered) master_meters_land(e, k, b0, n_blocks);
     }
     gains.settle(n_blocks);
     // n_blocks callbacks have run: the sources stand where the last of them read them
@@ -2017,7 +2062,7 @@ int jf_batch_fetch(jf_engine *e, int n_blocks, float *out_mix) {
                                    sizeof(float) * 2 * e->B * n_blocks, (size_t)e->n_buses, hipMemcpyDeviceToHost, e->stream));
     JF_HIP(e, hipStreamSynchronize(e->stream));
     if (device_fault(e)) return fail(e, JF_ERR_DEVICE, kHandOffMsg);
-    return JF_OK;
+    return master_meters_fetch(e);  // the run's meters come with its mix (none: nothing to do)
     });
 }
 

@@ -10,6 +10,8 @@
 //                         and jf_room_set_ir / jf_source_set_send
 //   jf_engine_gain.cpp    per-source gain: the levels and mutes, what a processing call latches of them, the stage that applies
 //                         them to a run's descriptors (run_gain_stage, jf_gain.hip) and jf_source_set_gain / jf_batch_set_gains
+//   jf_engine_master.cpp  bus masters: the per-bus master gains, limiters and meters, what a processing call latches of them, the
+//                         stage behind the mix (run_master_stage, jf_master.hip) and jf_bus_set_master / jf_bus_meters
 //   jf_engine_debug.cpp   every entry point of include/jefferson_debug.h (taps, timing hooks, tuning switches, accessors)
 // Not part of any interface: nothing outside csrc/ includes this file.
 #ifndef JF_ENGINE_INTERNAL_H
@@ -92,6 +94,9 @@ hipError_t launch_pose_objects(const float *d_objects, const int *d_object_of, c
 // per-source gain (jf_gain.hip): the gains of a run onto its descriptors, behind prep_kernel
 hipError_t launch_desc_gain(ItemDesc *d_desc, const float *d_g_prev, const float *d_g_new, const float *d_g_traj, int S, int K,
                             int canon, hipStream_t st);
+// bus masters (jf_master.hip): master gain, limiter and meters on a run's finished mix, in place
+hipError_t launch_master(float *d_mix, const float *d_par, float *d_state, float *d_t, float *d_gg, float *d_meters, int B, int K,
+                         int n_buses, int ramp, hipStream_t st);
 }  // namespace jf
 
 using namespace jf;
@@ -410,6 +415,39 @@ struct jf_engine : ReverbSetup {
     std::vector<EventPair> ev_gain;           // profiling 2: around desc_gain_kernel (jf_profile_read_gain)
     std::vector<char> ev_gain_on;             // ... of the timed runs that launched it
 
+    // BUS MASTERS (jf_bus_set_master, jf_bus_set_limiter, jf_engine_set_meters).  Per bus a master gain (m_prev
+    // the last rendered block ended on, m_new asked for), a limiter (ceiling c, 0: off; release r) and meters; the rule for a
+    // block is jf_master_rule.h, the stage (jf_master.hip) runs on the run's mix behind run_room_add.  The host state is under
+    // pos_mu like `pos` and empty until first use; an engine is ACTIVE while some bus has m_prev or m_new != 1, some limiter is
+    // on or meters are enabled -- otherwise nothing below is allocated and nothing is launched (master_latch).  The limiter
+    // gain g_prev depends on the audio and lives on the device (d_mstate).
+    std::vector<float> mst_prev, mst_new, lim_c, lim_r;  // [n_buses] (empty: every bus neutral: 1, 1, 0, 1)
+    std::vector<char> mst_snapped;            // [n_buses] m_prev was set at once (fade == 0) since the last call latched the masters
+    std::vector<char> lim_restart;            // [n_buses] the limiter was turned on or off since: its gain starts over at 1
+    bool meters_want = false;                 // jf_engine_set_meters
+    std::vector<float> meters_last;           // [n_buses][meters_blocks][4] the last rendered call's meters on the host
+    int meters_blocks = 0;                    // (0: none)
+    // what the processing call in hand latched (its thread's alone)
+    bool master_on = false;                   // the call is active
+    bool master_meters = false;               // ... with meters
+    bool master_ramp = false;                 // the call's next run is its first and some m_prev differs from its m_new
+    bool master_rendered = false;             // a run of the call has launched the stage (master_settle: m_prev := m_new)
+    std::vector<float> run_mpar;              // [n_buses][4] {m_prev, m_new, c, r} of the call
+    int meters_dev_blocks = 0;                // blocks whose meters the last jf_batch_run left in d_meters, not yet fetched (0: none)
+    int meters_stage_blocks = 0;              // blocks whose meters a submitted block's copy brings to h_meters (jf_collect_block)
+    DevBuf<float> d_mpar, d_mstate;           // [JF_MAX_BUSES][4], [JF_MAX_BUSES]
+    DevBuf<float> d_mt, d_mgg, d_meters;      // [master_cap][1], [..][2], [..][4]: per (bus, block) of a run
+    size_t master_cap = 0;                    // items they hold (n_buses maxK when they were allocated)
+    std::vector<float> dev_mpar;              // what d_mpar holds (empty: nothing yet)
+    PinnedBuf<float> h_m_stage;               // [kGainStageSlots][JF_MAX_BUSES][4] pinned staging of the asynchronous copies to d_mpar
+    hipEvent_t ev_m_copy[kGainStageSlots] = {};  // ... as ev_g_copy
+    bool m_copy_pending[kGainStageSlots] = {};
+    int m_stage_slot = 0;
+    PinnedBuf<float> h_meters;                // [master_cap][4] where a call's meters land on the host
+    bool last_master = false;                 // the last run launched the stage (jf_debug_last_kernels)
+    std::vector<EventPair> ev_master;         // profiling 2: around the stage (jf_profile_read_master)
+    std::vector<char> ev_master_on;           // ... of the timed runs that launched it
+
     PinnedBuf<float> h_pos_pinned;  // [S][5]   pinned + mapped: the real-time kernel reads it in place
     PinnedBuf<float> h_out_pinned;  // [kRtMaxWgs][2B] pinned + mapped: ... and writes its workgroups' stereo blocks in place
     int rt_wgs = 0;                 // partial blocks the block in flight left there (0: one finished block)
@@ -654,7 +692,27 @@ struct GainCall {
     GainCall(const GainCall &) = delete;
     GainCall &operator=(const GainCall &) = delete;
 };
-JF_INTERNAL void gain_reset_source(jf_engine *e, int src);  // level 1, not muted, at once (jf_source_set_signal)
+JF_INTERNAL void gain_reset_source(jf_engine *e, int src);
+// bus masters (jf_engine_master.cpp).  master_latch: at the start of a processing call that is not paused, beside gain_latch --
+// what the setters hold becomes the call's (e->master_on, run_mpar), the device copies that differ are enqueued.
+// run_master_stage: from run_blocks behind run_room_add, while e->master_on.  master_settle: when the call is over, however
+// it ends (MasterCall) -- m_prev := m_new if a run was launched.  master_meters_copy enqueues the copy of a run's meters to
+// the pinned staging, master_meters_land takes them from there (the stream has been waited for) into the call's host copy
+// at block b0 of n_blocks; master_meters_fetch does both for what a jf_batch_run left on the device.
+JF_INTERNAL int master_latch(jf_engine *e);
+JF_INTERNAL int run_master_stage(jf_engine *e, int K, float *d_mix_out, bool timed);
+JF_INTERNAL void master_settle(jf_engine *e);
+JF_INTERNAL int master_meters_copy(jf_engine *e, int K);
+JF_INTERNAL void master_meters_land(jf_engine *e, int K, int b0, int n_blocks);
+JF_INTERNAL int master_meters_fetch(jf_engine *e);
+JF_INTERNAL void master_set_buses(jf_engine *e, int n_buses);  // under pos_mu: the buses that remain keep their sections
+struct MasterCall {
+    jf_engine *e;
+    explicit MasterCall(jf_engine *e_) : e(e_) {}
+    ~MasterCall() { master_settle(e); }
+    MasterCall(const MasterCall &) = delete;
+    MasterCall &operator=(const MasterCall &) = delete;
+};  // level 1, not muted, at once (jf_source_set_signal)
 JF_INTERNAL int ensure_interp_rows(jf_engine *e);
 JF_INTERNAL int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int first_block = -1);
 JF_INTERNAL int reset_sources(jf_engine *e, int src);

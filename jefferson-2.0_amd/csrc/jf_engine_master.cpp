@@ -1,0 +1,339 @@
+// jf_engine_master.cpp -- the host side of the bus masters (include/jefferson.h: "bus masters"): a master gain,
+// a block-rate safety limiter and meters per output bus, applied to the bus's finished mix.  The setters (jf_bus_set_master,
+// jf_bus_set_limiter, jf_engine_set_meters) only write host state under the positions' mutex; a processing call latches it
+// (master_latch), run_blocks launches the stage on the mix it has just formed (run_master_stage: jf_master.hip) and the call
+// gives m_new back as m_prev when it is over (master_settle).  jf_debug_master_block is the rule for one block on the host --
+// the header the kernels compile (jf_master_rule.h).
+//
+// Who reads what: mst_prev / mst_new / lim_c / lim_r / mst_snapped / lim_restart / meters_want / meters_last / meters_blocks
+// are touched under pos_mu only; master_on, run_mpar, master_ramp and the device buffers belong to the thread that makes the
+// processing calls.  The limiter's gain is on the device only (d_mstate): it depends on the audio.
+#include "jf_engine_internal.h"
+#include "jf_master_rule.h"
+
+// the vectors of an engine that sets its first master or limiter: every bus neutral; under pos_mu
+static void master_vectors(jf_engine *e) {
+    if (!e->mst_new.empty()) return;
+    const size_t nb = (size_t)e->n_buses;
+    e->mst_prev.assign(nb, 1.0f);
+    e->mst_new.assign(nb, 1.0f);
+    e->lim_c.assign(nb, 0.0f);
+    e->lim_r.assign(nb, 1.0f);
+    e->mst_snapped.assign(nb, 0);
+    e->lim_restart.assign(nb, 0);
+}
+
+// jf_engine_set_buses: the buses that remain keep their master sections, new ones are neutral; under pos_mu.  The device's
+// parameters are uploaded again by the next active call; a new bus's limiter gain starts at 1 when its limiter is turned on.
+void master_set_buses(jf_engine *e, int n_buses) {
+    const size_t nb = (size_t)n_buses;
+    if (!e->mst_new.empty()) {
+        e->mst_prev.resize(nb, 1.0f);
+        e->mst_new.resize(nb, 1.0f);
+        e->lim_c.resize(nb, 0.0f);
+        e->lim_r.resize(nb, 1.0f);
+        e->mst_snapped.resize(nb, 0);
+        e->lim_restart.resize(nb, 1);
+    }
+    e->dev_mpar.clear();
+    e->meters_last.clear();  // (the shape of a call's meters changes with the buses)
+    e->meters_blocks = 0;
+    e->meters_dev_blocks = 0;
+    e->meters_stage_blocks = 0;
+}
+
+// The device copy of the call's parameters, where it differs from what the device holds: an asynchronous copy out of a pinned
+// staging, enqueued by master_latch BEFORE anything of the call -- the host never waits for the stream's work (gain_upload's
+// scheme: kGainStageSlots slots taken in turn, a slot reused only when the copy out of it has run).  m_prev matters only to a
+// call that ramps: a call that does not leaves the device's alone.
+static int master_upload(jf_engine *e) {
+    const size_t n = e->run_mpar.size();
+    bool need = e->dev_mpar.size() != n;
+    for (size_t i = 0; i < n && !need; i++) need = (e->master_ramp || i % 4 != 0) && e->dev_mpar[i] != e->run_mpar[i];
+    if (!need) return JF_OK;
+    if (!e->h_m_stage) {
+        JF_HIP(e, e->h_m_stage.alloc((size_t)kGainStageSlots * 4 * JF_MAX_BUSES));
+        for (int i = 0; i < kGainStageSlots; i++) JF_HIP(e, hipEventCreateWithFlags(&e->ev_m_copy[i], hipEventDisableTiming));
+    }
+    const int slot = e->m_stage_slot;
+    e->m_stage_slot = (slot + 1) % kGainStageSlots;
+    if (e->m_copy_pending[slot]) JF_HIP(e, hipEventSynchronize(e->ev_m_copy[slot]));
+    float *stage = e->h_m_stage + (size_t)slot * 4 * JF_MAX_BUSES;
+    memcpy(stage, e->run_mpar.data(), sizeof(float) * n);
+    JF_HIP(e, hipMemcpyAsync(e->d_mpar, stage, sizeof(float) * n, hipMemcpyHostToDevice, e->stream));
+    JF_HIP(e, hipEventRecord(e->ev_m_copy[slot], e->stream));
+    e->m_copy_pending[slot] = true;
+    e->dev_mpar = e->run_mpar;
+    return JF_OK;
+}
+
+int master_latch(jf_engine *e) {
+    e->master_on = e->master_meters = e->master_ramp = e->master_rendered = false;
+    std::vector<char> restart;
+    {
+        std::lock_guard<std::mutex> lk(e->pos_mu);
+        if (e->mst_new.empty() && !e->meters_want) return JF_OK;  // nothing was ever set
+        const size_t nb = (size_t)e->n_buses;
+        bool active = e->meters_want;
+        for (size_t b = 0; b < e->mst_new.size() && !active; b++)
+            active = e->mst_prev[b] != 1.0f || e->mst_new[b] != 1.0f || e->lim_c[b] > 0.0f;
+        std::fill(e->mst_snapped.begin(), e->mst_snapped.end(), 0);  // (what was set at once is in mst_prev: latched below)
+        if (!active) return JF_OK;  // every master has settled at 1, no limiter is on, no meters
+        e->run_mpar.assign(4 * nb, 1.0f);
+        for (size_t b = 0; b < nb; b++) {
+            float *q = e->run_mpar.data() + 4 * b;
+            q[2] = 0.0f;
+            if (e->mst_new.empty()) continue;
+            q[1] = e->mst_new[b];
+            q[0] = e->mst_prev[b];
+            q[2] = e->lim_c[b];
+            q[3] = e->lim_r[b];
+            e->master_ramp = e->master_ramp || q[0] != q[1];
+        }
+        restart = e->lim_restart;
+        std::fill(e->lim_restart.begin(), e->lim_restart.end(), 0);
+        e->master_meters = e->meters_want;
+        e->master_on = true;
+    }
+    e->meters_dev_blocks = 0;  // (what a jf_batch_run left on the device is overwritten by this call)
+    const size_t items = (size_t)e->n_buses * (size_t)e->maxK;
+    if (!e->d_mpar) {
+        JF_HIP(e, e->d_mpar.alloc((size_t)4 * JF_MAX_BUSES));
+        JF_HIP(e, e->d_mstate.alloc(JF_MAX_BUSES));
+        restart.assign((size_t)e->n_buses, 1);  // every limiter gain starts at 1
+    }
+    if (items > e->master_cap) {
+        // (the first active call, or the first one after jf_engine_set_buses has grown the mix: hipFree waits for the device)
+        e->master_cap = 0;
+        e->d_mt.reset();
+        e->d_mgg.reset();
+        e->d_meters.reset();
+        e->h_meters.reset();
+        JF_HIP(e, e->d_mt.alloc(items));
+        JF_HIP(e, e->d_mgg.alloc(2 * items));
+        JF_HIP(e, e->d_meters.alloc(kMeterFloats * items));
+        JF_HIP(e, e->h_meters.alloc(kMeterFloats * items));
+        e->master_cap = items;
+    }
+    {
+        const int rc = master_upload(e);
+        if (rc) return rc;
+    }
+    // a limiter that was turned on or off since the last call starts over at gain 1: 1.0f as a 32-bit pattern, in stream order
+    for (size_t b = 0; b < restart.size() && b < (size_t)e->n_buses; b++)
+        if (restart[b]) JF_HIP(e, hipMemsetD32Async((hipDeviceptr_t)(e->d_mstate + b), 0x3f800000, 1, e->stream));
+    return JF_OK;
+}
+
+// The stage on the run's mix, d_mix_out [n_buses][K][2B] (the engine's or a jf_batch_run caller's), behind run_room_add and
+// inside the mix's event pair; an event pair of its own at profiling >= 2.
+int run_master_stage(jf_engine *e, int K, float *d_mix_out, bool timed) {
+    if ((size_t)K * (size_t)e->n_buses > e->master_cap) return fail(e, JF_ERR_STATE, "bus masters: the run has more blocks than the stage holds");
+    EventPair *eg = nullptr;
+    if (timed && e->profiling >= 2) {
+        while (e->ev_master.size() <= e->ev_used) {
+            EventPair q;
+            if (hipEventCreate(&q.a) != hipSuccess || hipEventCreate(&q.b) != hipSuccess) return fail(e, JF_ERR_DEVICE, "hipEventCreate failed");
+            e->ev_master.push_back(q);
+        }
+        e->ev_master_on.resize(e->ev_used + 1, 0);
+        e->ev_master_on[e->ev_used] = 1;
+        eg = &e->ev_master[e->ev_used];
+    }
+    if (eg) JF_HIP(e, hipEventRecord(eg->a, e->stream));
+    JF_HIP(e, launch_master(d_mix_out, e->d_mpar, e->d_mstate, e->d_mt, e->d_mgg, e->d_meters, e->B, K, e->n_buses, e->master_ramp ? 1 : 0,
+                            e->stream));
+    if (eg) JF_HIP(e, hipEventRecord(eg->b, e->stream));
+    e->last_master = true;
+    e->master_ramp = false;  // the run that follows in this call continues at m_new
+    e->master_rendered = true;
+    return JF_OK;
+}
+
+void master_settle(jf_engine *e) {
+    if (!e->master_on) return;
+    e->master_on = false;
+    if (!e->master_rendered) return;  // nothing was launched: as latched
+    std::lock_guard<std::mutex> lk(e->pos_mu);
+    for (size_t b = 0; b < e->mst_prev.size() && 4 * b + 1 < e->run_mpar.size(); b++)
+        // (a setter that came in with fade == 0 while the call ran has said where the next block starts: left alone)
+        if (!e->mst_snapped[b]) e->mst_prev[b] = e->run_mpar[4 * b + 1];
+}
+
+int master_meters_copy(jf_engine *e, int K) {
+    JF_HIP(e, hipMemcpyAsync(e->h_meters, e->d_meters, sizeof(float) * kMeterFloats * (size_t)K * (size_t)e->n_buses, hipMemcpyDeviceToHost,
+                             e->stream));
+    return JF_OK;
+}
+
+// h_meters holds [n_buses][K][4] of a run: blocks b0 .. b0 + K of a call of n_blocks
+void master_meters_land(jf_engine *e, int K, int b0, int n_blocks) {
+    std::lock_guard<std::mutex> lk(e->pos_mu);
+    const size_t nb = (size_t)e->n_buses, rec = kMeterFloats;
+    if (b0 == 0 || e->meters_last.size() != nb * (size_t)n_blocks * rec) e->meters_last.assign(nb * (size_t)n_blocks * rec, 0.0f);
+    for (size_t b = 0; b < nb; b++)
+        memcpy(e->meters_last.data() + (b * (size_t)n_blocks + (size_t)b0) * rec, e->h_meters + b * (size_t)K * rec, sizeof(float) * rec * (size_t)K);
+    e->meters_blocks = b0 + K == n_blocks ? n_blocks : 0;
+}
+
+// what the last jf_batch_run left in d_meters (jf_batch_fetch, jf_bus_meters): brought over once, the stream waited for
+int master_meters_fetch(jf_engine *e) {
+    const int K = e->meters_dev_blocks;
+    if (K <= 0) return JF_OK;
+    const int rc = master_meters_copy(e, K);
+    if (rc) return rc;
+    JF_HIP(e, hipStreamSynchronize(e->stream));
+    e->meters_dev_blocks = 0;
+    master_meters_land(e, K, 0, K);
+    return JF_OK;
+}
+
+static bool bus_ok(const jf_engine *e, int bus) { return bus >= 0 && bus < e->n_buses; }
+
+extern "C" {
+
+int jf_bus_set_master(jf_engine *e, int bus, float gain, int fade) {
+    return jf_guard([&]() -> int {
+    if (!e) return JF_ERR_ARG;
+    // (0 is refused with the negative values: a setter called with zeroed arguments must not silence a bus for good -- no
+    // other call of the boundary would bring it back -- and a bus is silenced by muting its sources, jf_source_set_mute)
+    if (!std::isfinite(gain) || !(gain > 0.0f)) return fail(e, JF_ERR_ARG, "the master gain is not positive and finite");
+    std::lock_guard<std::mutex> lk(e->pos_mu);
+    if (!bus_ok(e, bus)) return fail(e, JF_ERR_ARG, "bad bus index");
+    if (e->mst_new.empty() && gain == 1.0f) return JF_OK;  // (every master is 1 until it is set)
+    master_vectors(e);
+    e->mst_new[bus] = gain;
+    if (!fade) {
+        e->mst_prev[bus] = gain;
+        e->mst_snapped[bus] = 1;
+    }
+    return JF_OK;
+    });
+}
+
+float jf_bus_master(const jf_engine *e, int bus) {
+    if (!e) return 1.0f;
+    try {
+        jf_engine *m = const_cast<jf_engine *>(e);
+        std::lock_guard<std::mutex> lk(m->pos_mu);
+        return !bus_ok(e, bus) || e->mst_new.empty() ? 1.0f : e->mst_new[bus];
+    } catch (...) {
+        return 1.0f;
+    }
+}
+
+int jf_bus_set_limiter(jf_engine *e, int bus, float ceiling, float release) {
+    return jf_guard([&]() -> int {
+    if (!e) return JF_ERR_ARG;
+    if (!std::isfinite(ceiling) || ceiling < 0.0f) return fail(e, JF_ERR_ARG, "the ceiling is negative or not finite");
+    if (!std::isfinite(release) || !(release > 0.0f && release <= 1.0f)) return fail(e, JF_ERR_ARG, "the release is outside (0, 1]");
+    std::lock_guard<std::mutex> lk(e->pos_mu);
+    if (!bus_ok(e, bus)) return fail(e, JF_ERR_ARG, "bad bus index");
+    if (e->mst_new.empty() && ceiling == 0.0f) return JF_OK;  // (every limiter is off until it is set)
+    master_vectors(e);
+    // off -> on and on -> off start the gain over at 1; a new ceiling or release of a running limiter keeps it
+    if ((e->lim_c[bus] > 0.0f) != (ceiling > 0.0f)) e->lim_restart[bus] = 1;
+    e->lim_c[bus] = ceiling;
+    e->lim_r[bus] = release;
+    return JF_OK;
+    });
+}
+
+int jf_bus_limiter(const jf_engine *e, int bus, float *ceiling, float *release) {
+    return jf_guard([&]() -> int {
+    if (!e || !ceiling || !release) return JF_ERR_ARG;
+    jf_engine *m = const_cast<jf_engine *>(e);
+    std::lock_guard<std::mutex> lk(m->pos_mu);
+    if (!bus_ok(e, bus)) return JF_ERR_ARG;
+    *ceiling = e->lim_c.empty() ? 0.0f : e->lim_c[bus];
+    *release = e->lim_r.empty() ? 1.0f : e->lim_r[bus];
+    return JF_OK;
+    });
+}
+
+int jf_engine_set_meters(jf_engine *e, int on) {
+    return jf_guard([&]() -> int {
+    if (!e) return JF_ERR_ARG;
+    std::lock_guard<std::mutex> lk(e->pos_mu);
+    if (e->meters_want == (on != 0)) return JF_OK;
+    e->meters_want = on != 0;
+    e->meters_blocks = 0;  // (on: nothing has been rendered with them yet; off: they are gone)
+    return JF_OK;
+    });
+}
+
+int jf_bus_meters(jf_engine *e, int n_blocks, float *out) {
+    return jf_guard([&]() -> int {
+    DeviceGuard bind(e);
+    if (!e || !out) return JF_ERR_ARG;
+    {
+        std::lock_guard<std::mutex> lk(e->pos_mu);
+        if (!e->meters_want) return fail(e, JF_ERR_STATE, "meters are off (jf_engine_set_meters)");
+    }
+    {
+        const int rc = master_meters_fetch(e);  // (a jf_batch_run's, still on the device)
+        if (rc) return rc;
+    }
+    std::lock_guard<std::mutex> lk(e->pos_mu);
+    if (e->meters_blocks <= 0) return fail(e, JF_ERR_STATE, "no call has been rendered with meters yet");
+    if (n_blocks != e->meters_blocks)
+        return fail(e, JF_ERR_ARG, "the last rendered call had " + std::to_string(e->meters_blocks) + " blocks");
+    memcpy(out, e->meters_last.data(), sizeof(float) * e->meters_last.size());
+    return JF_OK;
+    });
+}
+
+// The rule for ONE block on the host: x [B][2] interleaved, *g_state the limiter gain before the block and after it.  The block
+// counts as a call's first: it ramps iff m_prev != m_new.  sumsq_out is summed sample by sample in float32.
+int jf_debug_master_block(const float *x, int B, float m_prev, float m_new, float ceiling, float release, float *g_state, float *out,
+                          float meters[4]) {
+    if (!x || !g_state || !out || !meters || B <= 0) return JF_ERR_ARG;
+    const float inv_B = 1.0f / (float)B;
+    const bool ramp = m_prev != m_new;
+    float p = 0.0f;
+    for (int n = 0; n < B; n++) {
+        const float m = master_gain_at(m_prev, m_new, ramp, master_frac(n, inv_B));
+        for (int ch = 0; ch < 2; ch++) {
+            const float v = m * x[2 * n + ch];
+            out[2 * n + ch] = v;
+            p = master_max(p, master_abs(v));
+        }
+    }
+    const float g0 = *g_state;
+    const float g = master_step(master_target(p, ceiling), g0, release, ceiling);
+    float peak = 0.0f, sumsq = 0.0f;
+    for (int n = 0; n < B; n++) {
+        const float a = master_env(g0, g, master_frac(n, inv_B));
+        for (int ch = 0; ch < 2; ch++) {
+            const float y = master_out(a, out[2 * n + ch], ceiling);
+            out[2 * n + ch] = y;
+            peak = master_max(peak, master_abs(y));
+            sumsq = sumsq + y * y;
+        }
+    }
+    meters[0] = p;
+    meters[1] = peak;
+    meters[2] = sumsq;
+    meters[3] = g;
+    *g_state = g;
+    return JF_OK;
+}
+
+int jf_profile_read_master(jf_engine *e, double *master_ms) {
+    return jf_guard([&]() -> int {
+    DeviceGuard bind(e);
+    if (!e || !master_ms) return JF_ERR_ARG;
+    JF_HIP(e, hipStreamSynchronize(e->stream));
+    double r = 0;
+    for (size_t i = 0; e->profiling >= 2 && i < e->ev_used && i < e->ev_master_on.size() && i < e->ev_master.size(); i++) {
+        if (!e->ev_master_on[i]) continue;
+        float ms = 0;
+        JF_HIP(e, hipEventElapsedTime(&ms, e->ev_master[i].a, e->ev_master[i].b));
+        r += ms;
+    }
+    *master_ms = r;
+    return JF_OK;
+    });
+}
+
+}  // extern "C"
