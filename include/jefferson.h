@@ -479,7 +479,9 @@ int jf_source_bus(const jf_engine *e, int src);
  * jf_source_input_of: the source whose input src plays; src itself if it follows nobody.  JF_ERR_ARG for a bad index.
  *
  * jf_source_set_signal / jf_source_set_live on a ROOT act on the whole group: the followers follow the new input.  On a
- *   FOLLOWER they detach it first and then act on it alone.  Only roots and unshared sources are live channels
+ *   FOLLOWER they detach it first and then act on it alone -- the detach is jf_source_share_input's, so on a follower the
+ *   two calls return JF_ERR_STATE while a block is in flight (jf_callback's form), with nothing changed; on a root or an
+ *   unshared source they do not.  Only roots and unshared sources are live channels
  *   (jf_num_live_sources counts them, the *_in calls are fed for them); a follower of a live root hears that channel.
  * jf_source_reset on a member resets the input state (window, play position) of every member of its group -- they stay
  *   equal -- and the crossfade state of that member only.
@@ -530,8 +532,10 @@ int jf_source_input_of(const jf_engine *e, int src);
  *
  * Paused blocks are silence on every bus and the room does not advance: after the pause the tail continues as if those calls
  * had not happened.  jf_source_reset leaves the room's tail alone (the tail is the bus's, not the source's).  An engine that
- * never calls jf_room_set_ir allocates nothing for it and renders the same bits; with a room set, a bus nobody sends to is bit
- * for bit the bus of the engine without the room, and the per-block calls go through the batch pipeline with one block (as
+ * never calls jf_room_set_ir allocates nothing for it and renders the same bits; with a room set, a bus nobody HAS SENT TO
+ * SINCE THE ROOM WAS SET is bit for bit the bus of the engine without the room (after a bus's last send the float32 transforms
+ * of the partitioned convolution leave values of the order of 1e-11 of the send for as long as its delay line still holds
+ * those samples, also where the exact convolution is zero), and the per-block calls go through the batch pipeline with one block (as
  * with more than one bus).  The wet part is deterministic -- no atomics, one association -- and the same bits however a run
  * is cut into calls.  DESIGN.md 4.13 has the stage and its cost.
  * jefferson_group.h does not offer a room; jf_render and jf_ctest have no option for it.

@@ -1,0 +1,210 @@
+"""Conference sessions: every feature of the conference engine at once -- output buses, shared and live inputs, room sends,
+per-source gains, bus masters, listener poses, objects -- in seeded random orders, applied in lockstep to the HIP engine and to
+tests/conference_model.py, ONE float64 reference composed from the references the single features are held to.  Every bus of
+every block is compared.  The feature tests compare compositions engine against engine (a twin without the feature); a fault
+in code both twins run passes there and fails here.  tests/conference_sessions.py generates the ops (the same list with and
+without a GPU); tests/test_conference_model.py shows on the CPU that every clause of the model counts in every session.
+
+THE BOUND of bus b at block k is the project's rules added together, nothing new and nothing measured from the engine: with n
+sources on the bus and a room of P partitions
+    pre = (sum_tol(2e-7, n) + (wet_tol(P) if a room is set else 0)) * max(1, |want|_inf)         want: the model's dry + wet
+    limiter off:  pre * max(m) over the block's master ramp
+    limiter on:   twice that.  Let d = pre * max(m) bound the error of the limiter's input v.  It moves the block's peak p by at
+                  most d, hence t = c / p, and with it g, by at most g d / p.  The output is a v with a <= g <= 1: the error
+                  of v contributes a d <= d, the error da <= g d / p of the envelope contributes |v| da <= p g d / p = g d
+                  <= d (because |v| <= p).  Together at most 2 d.  (The rule is continuous in its input: at p == c, t is 1
+                  either way, and at g == g_prev the attack and the release form coincide.)
+Also asserted, where meters are on: peak_in within the bound of the model's p; gain bit for bit master_model's float32
+recurrence fed the engine's own peak_in sequence; peak_out <= ceiling on a limited bus; sumsq_out within sumsq_bound of the
+float64 sum over the engine's own output.  A bus without sources that nobody has
+sent to since the room was set is exact zeros, a paused call silence on every bus.
+With JF_BOUNDS_LOG=<file> every call's worst error / bound is appended to that file (profiles/conference/bounds.txt)."""
+import collections
+import os
+
+import numpy as np
+import pytest
+
+import conference_sessions as cs
+import master_model
+
+pytestmark = pytest.mark.gpu
+
+F = np.float32
+
+
+def _apply(jf, eng, op, want, code):
+    """the op on the engine -> the call's output as [n_buses][K][2B], or None; refusals and return codes as the model predicts"""
+    name, args = op[0], op[1:]
+    if name == "knob":
+        getattr(eng, args[0])(args[1])
+        return None
+    if code:
+        with pytest.raises(jf.JfError) as ei:
+            getattr(eng, name)(*args)
+        assert ei.value.code == code, (name, ei.value.code, code)
+        return None
+    if name in ("set_spherical", "set_cartesian"):
+        rc = getattr(eng, name)(*args)
+        assert rc == want, (name, args, rc, want)
+        return None
+    if name == "batch_run":
+        eng.batch_run(args[0], args[1])
+        eng.synchronize()
+        got = eng.batch_fetch(args[1])
+    elif name == "collect_block":
+        rc, got = eng.collect_block()
+        assert rc == 0
+    else:
+        got = getattr(eng, name)(*args)
+    if name not in cs.AUDIO:
+        return None
+    nb = eng.n_buses
+    return np.asarray(got).reshape(nb, -1, 2 * eng.B)
+
+
+def _log_ratio(label, err, bound):
+    path = os.environ.get("JF_BOUNDS_LOG")
+    if path:
+        with open(path, "a") as f:
+            f.write(f"{err:.3e} {bound:.3e} {err / bound:.3f} {label}\n")
+
+
+class _Limiters:
+    """master_model.master_block's float32 recurrence per bus, fed the engine's own peak_in (already m x: the rule is asked at
+    m = 1): the state machine is exact on its own inputs.
+    A bus's state is known from the moment its limiter is turned on (g = 1) for as long as every rendered block is metered."""
+
+    def __init__(self):
+        self.g, self.on = {}, {}
+
+    def op(self, op):
+        if op[0] == "set_limiter":
+            b, on = op[1], op[2] > 0
+            if self.on.get(b, False) != on:
+                self.g[b] = F(1)
+            self.on[b] = on
+        elif op[0] == "set_buses":
+            for b in [b for b in self.on if b >= op[1]]:
+                self.on.pop(b), self.g.pop(b, None)
+
+    def unseen(self):
+        self.g = {}
+
+    def block(self, b, p, c, r):
+        """the gain the engine must report for a block of peak p, or None while the state is not known"""
+        if not c > 0:
+            return F(1)
+        if b not in self.g:
+            return None
+        # master_model's own rule on a block whose peak is p: at m = 1 the gain depends on the block through p alone
+        _, info = master_model.master_block(np.array([p, 0], np.float32), 1, 1.0, 1.0, False, c, r, self.g[b])
+        self.g[b] = info["g"]
+        return self.g[b]
+
+
+def _check(n, label, got, want, last, meters, lim, model_c, model_r, worst, tally=None):
+    """one call's blocks against the model's; meters [n_buses][K][4] or None"""
+    tally = collections.Counter() if tally is None else tally
+    nb, K = want.shape[:2]
+    assert got.shape == want.shape, (got.shape, want.shape)
+    if last.get("paused"):
+        assert not got.any(), "a paused call is silence on every bus"
+        return
+    bound = cs.bounds(last, nb, K)
+    err = np.abs(got - want).max(axis=2)
+    k = np.unravel_index(np.argmax(err / bound), err.shape)
+    worst[0] = max(worst[0], float(err[k] / bound[k]))
+    _log_ratio(f"conference session {n} {label} bus {k[0]} block {k[1]}", float(err[k]), float(bound[k]))
+    assert (err <= bound).all(), (label, k, float(err[k]), float(bound[k]))
+    for b in range(nb):
+        for j in range(K):
+            if last["n_on"][b, j] == 0 and last["quiet"][b]:
+                assert not got[b, j].any(), ("a bus without sources that nobody sent to is exact zeros", b, j)
+    if meters is None:
+        lim.unseen()
+        return
+    B = got.shape[2] // 2
+    for b in range(nb):
+        c, r = model_c[b], model_r[b]
+        for j in range(K):
+            i = last["infos"][b][j]
+            peak_in, peak_out, sumsq, gain = meters[b, j]
+            assert abs(float(peak_in) - i["p"]) <= bound[b, j] / (2.0 if i["limited"] else 1.0), ("peak_in", b, j, peak_in, i["p"])
+            g = lim.block(b, peak_in, c, r)
+            assert g is None or gain == g, ("gain", b, j, gain, g)
+            tally["limiter gains checked bit for bit"] += g is not None and c > 0
+            if c > 0:
+                assert peak_out <= F(c), ("peak_out above the ceiling", b, j, peak_out, c)
+            tally["metered bus blocks"] += 1
+            ref = master_model.sumsq64(got[b, j])
+            assert abs(float(sumsq) - ref) <= master_model.sumsq_bound(ref, B), ("sumsq_out", b, j, sumsq, ref)
+
+
+@pytest.mark.parametrize("n", sorted(cs.SESSIONS))
+def test_conference_session_against_the_composed_model(jf, hrir, castanets, n):
+    eng = cs.make_engine(n, hrir, jf)
+    log, worst, lim = [], [0.0], _Limiters()
+    families, drawn = collections.Counter(), collections.Counter()
+    blocks, peak, limited = 0, 0.0, False
+    late = None             # the callback form hands a block out one call late: (want, last, metered, c, r) of that block
+    first_callback, deferred = True, []
+    try:
+        for op, want, code, model, gen in cs.generate(n, hrir, castanets, jf):
+            log.append(cs.describe(op) + (f" -> refused {code}" if code else ""))
+            drawn[op[0]] += 1
+            if not code:
+                if first_callback:
+                    lim.op(op)
+                else:               # the callback form checks a block a call late: so are the ops that follow its submission
+                    deferred.append(op)
+                limited = limited or (op[0] == "set_limiter" and op[2] > 0)
+            got = _apply(jf, eng, op, want, code)
+            if got is None:
+                continue
+            last = model.last
+            if op[0] in ("callback", "collect_block"):
+                now = None if op[0] == "collect_block" else (want, last, model.meters_on, list(model.lim_c), list(model.lim_r))
+                if late is None:
+                    assert first_callback and not got.any(), "jf_callback hands out zeros before the first block"
+                else:
+                    w, l, metered, c, r = late
+                    m = eng.meters(1) if metered and model.meters_on and not l.get("paused") else None
+                    _check(n, f"step {len(log)} callback", got, w, l, m, lim, c, r, worst, families)
+                    blocks, peak = blocks + 1, max(peak, float(np.abs(w).max()))
+                for o in deferred:
+                    lim.op(o)
+                late, first_callback, deferred = now, False, []
+                continue
+            K = want.shape[1]
+            if not last.get("paused"):
+                names = eng.last_kernels()
+                ks = ";".join(names)
+                for fam in ("rt_block_kernel", "fused_block_kernel", "fused_pair_kernel", "fused2048_kernel", ",shared", "desc_gain_kernel",
+                            "room_mac_kernel", "master_apply_kernel", "pose_kernel", "pose_object_kernel", "live_ingest_kernel"):
+                    families[fam] += fam in ks
+                ahead = op[0] == "batch_run" and "prep_kernel" not in names      # the run found its descriptors prepared
+                families["descriptors prepared ahead"] += ahead
+                families["... with a gain active"] += ahead and "desc_gain_kernel" in ks
+            m = eng.meters(K) if model.meters_on and not last.get("paused") else None
+            _check(n, f"step {len(log)} {op[0]} K={K}", got, want, last, m, lim, model.lim_c, model.lim_r, worst, families)
+            blocks, peak = blocks + K, max(peak, float(np.abs(want).max()))
+    except BaseException:
+        print("\n".join(log[-40:]))     # (pytest shows it with the failure)
+        raise
+    finally:
+        eng.close()
+    print(f"session {n} kernels: {dict(families)}")
+    print(f"session {n} ops: {dict(sorted(drawn.items()))}")
+    print(f"session {n}: {blocks} blocks, peak {peak:.3f}, worst error / bound {worst[0]:.3f}, limiter blocks {model.limiter_blocks}")
+    assert blocks >= 150 and peak > 0.02, (blocks, peak)
+    if n == 6:      # the runs that follow their predecessor take its descriptors, and desc_gain_kernel rewrites those as well
+        assert families["... with a gain active"] >= 1, dict(families)
+        # windows of every kind of uploaded trajectory, and the session's first blocks through the one-launch kernel
+        assert drawn["upload_world"] >= 1 and drawn["upload_objects"] >= 1 and drawn["upload_positions"] >= 1, dict(drawn)
+        assert families["rt_block_kernel"] >= 3, dict(families)
+    assert families["metered bus blocks"] >= 50, dict(families)
+    if limited:
+        assert families["limiter gains checked bit for bit"] >= 10, dict(families)
+    if limited:
+        assert model.limiter_blocks["attack"] >= 1 and model.limiter_blocks["release"] >= 2, model.limiter_blocks
