@@ -666,6 +666,61 @@ int jf_bus_limiter(const jf_engine *e, int bus, float *ceiling, float *release);
 int jf_engine_set_meters(jf_engine *e, int on);
 int jf_bus_meters(jf_engine *e, int n_blocks, float *out /* [n_buses][n_blocks][4] */);
 
+/* ---- HRTF sets: several sets in one engine, chosen per source or per bus -------- */
+
+/*
+ * The reference has ONE set for everybody: one global fft_hrtf, filled once by read_hrtf_signals() / transform_hrtfs()
+ * (main.cu:60-75, hrtf_signals.cu:90-98, hrtf_signals.cu:107-153).  Here an engine holds n_sets >= 1 sets, so that every
+ * listener of a session (an output bus) can hear through their own ears -- their own SOFA file -- inside one engine, with its
+ * shared inputs, its room and its group sizes.
+ *
+ * SET 0 is the one the engine was created with.  A FURTHER SET has the engine's own directions -- the same grid of rings or
+ * the same cloud, hence jf_table_rows rows in the same order -- and the engine's hrtf_len; it is given as
+ * hrir [jf_table_rows][2][taps], exactly as at creation.  At most JF_MAX_HRTF_SETS sets.  A set cannot be removed.
+ *
+ * EVERY SOURCE has a current set, 0 until it is given another.  In steady state a source on set j is rendered exactly as an
+ * engine created with set j renders it: the same bits.  A source whose set changed with fade != 0 renders, on the FIRST BLOCK
+ * OF THE NEXT PROCESSING CALL THAT IS NOT PAUSED, the reference's own crossfade (kernels.cu:132-137) between the two sets,
+ *     out[n] = (1 - fn) y(old position, old set)[n] + fn y(new position, new set)[n],    fn = n / (B - 1),
+ * which coincides with the position crossfade when the source also moves and composes with a gain fade on the same block (the
+ * old set is weighted with g[k - 1], the new one with g[k]).  With fade == 0 the source is on the new set from that block on,
+ * with no transition of its own (for a source that has not started yet).  Window, play position and crossfade state do not
+ * change.  After a call in which a block was rendered the new sets are the standing ones; a call longer than
+ * max_batch_blocks switches in its first block only.
+ *
+ * jf_engine_add_hrtf_set(e, hrir, taps): returns the new set's index (>= 1).  The table is re-allocated with room for one more
+ *   set; the engine's stream is waited for (call it from the thread that makes the processing calls, between calls, as
+ *   jf_reverb_set_ir).  JF_ERR_ARG: NULL, taps <= 0 or taps > hrtf_len; JF_ERR_STATE: the engine holds JF_MAX_HRTF_SETS
+ *   sets, or a block is in flight; JF_ERR_NOMEM: no device memory -- the engine is as it was and goes on with the sets it has.
+ * jf_engine_add_hrtf_sofa(e, path, tol_deg): the same from a SOFA file, for engines on rings (jf_sofa_read + jf_sofa_table).
+ *   Refused as jf_engine_create_sofa refuses a file (JF_ERR_IO, JF_ERR_ARG), and with JF_ERR_ARG unless the file's ring layout
+ *   equals the engine's and its taps fit hrtf_len.  A cloud engine takes jf_sofa_cloud's hrir through jf_engine_add_hrtf_set:
+ *   the host vouches for the directions.
+ * jf_num_hrtf_sets: n_sets.
+ * jf_source_set_hrtf(e, src, set, fade) / jf_source_hrtf (the set last asked for; JF_ERR_ARG, negative, for a bad index).
+ * jf_bus_set_hrtf(e, bus, set, fade): every source that is on the bus NOW; a source that joins the bus later keeps its set.
+ * The setters are setters like jf_source_set_cartesian: callable from another thread, latched by the next processing call
+ * that is not paused.  JF_ERR_ARG for a bad source, bus or set index; on every refusal nothing changes and the stream
+ * continues bit for bit.  jf_source_set_signal, jf_source_reset and jf_source_set_bus leave a source's set alone.
+ *
+ * COST.  An engine that never adds a set allocates nothing, launches what it launched and renders the same bits.  An engine
+ * that has added a set no longer builds or reads the pre-interpolated rows (its further sets live where they would): whole-
+ * degree positions are weighted per block, bit-identical.  While every source is on set 0 nothing else changes.  While some
+ * source is on another set, one small kernel rewrites the row indices of every batch run's descriptors ahead of the
+ * spatialiser and the per-block calls go through the batch pipeline with one block (as with more than one
+ * bus, a room or a gain).
+ *
+ * Not offered: sets on directions other than the engine's; sets inside the one-launch real-time kernel; jefferson_group.h,
+ * jf_render and jf_ctest have no option for sets.
+ */
+#define JF_MAX_HRTF_SETS 64
+int jf_engine_add_hrtf_set(jf_engine *e, const float *hrir /* [jf_table_rows][2][taps] */, int taps);
+int jf_engine_add_hrtf_sofa(jf_engine *e, const char *path, float tol_deg);
+int jf_num_hrtf_sets(const jf_engine *e);
+int jf_source_set_hrtf(jf_engine *e, int src, int set, int fade);
+int jf_source_hrtf(const jf_engine *e, int src);
+int jf_bus_set_hrtf(jf_engine *e, int bus, int set, int fade);
+
 /* ---- listener poses: head position and orientation per output bus --------------- */
 
 /*

@@ -277,6 +277,23 @@ int jf_debug_master_block(const float *x, int B, float m_prev, float m_new, floa
  * jf_profile_read's mix_ms too (the stage runs inside the mix's event pair); 0 while no master was active. */
 int jf_profile_read_master(jf_engine *e, double *master_ms);
 
+/* HRTF sets (include/jefferson.h).  jf_debug_read_hrtf_set: the rows of ONE set in jf_debug_read_table's form,
+ * out [rows][2][Nc] complex (set 0: what jf_debug_read_table reads); JF_ERR_ARG for a set the engine does not hold.
+ * jf_debug_set_record: the rule desc_set_kernel applies to ONE descriptor, on the host -- the header the kernel compiles
+ * (csrc/jf_set_rule.h), so the CPU suite checks every case of it.  The arrays are a record's rows and weights of the new and
+ * the old set, *n_new / *n_old their term counts, *flags the pair-kernel layout's bits; off0 = set_prev * rows and off1 =
+ * set_new * rows are the row offsets of the source's set in the block before and in this one, canon != 0 the pair kernel's
+ * layout.  Pure host code: no engine, no GPU.  Returns 1 if the record changed, 0 if it is as it was, JF_ERR_ARG for a NULL
+ * pointer.
+ * jf_debug_last_set_stage: 1 if the last run launched desc_set_kernel (jf_debug_last_kernels names it too), else 0. */
+int jf_debug_read_hrtf_set(jf_engine *e, int set, float *out);
+int jf_debug_set_record(int rows_new[4], float w_new[4], int rows_old[4], float w_old[4], int *n_new, int *n_old, int *flags,
+                        int off0, int off1, int canon);
+int jf_debug_last_set_stage(const jf_engine *e);
+/* ms in desc_set_kernel since jf_profile_enable(e, 2) (beside jf_profile_read's prep_ms: the kernel runs right behind
+ * prep_kernel); 0 while every source was on set 0. */
+int jf_profile_read_sets(jf_engine *e, double *set_ms);
+
 /* ---- libjefferson_group.so (jefferson_group.h): test support ------------------------------------------------------------ */
 
 typedef struct jf_group jf_group;

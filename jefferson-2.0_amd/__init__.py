@@ -42,6 +42,7 @@ class JfHrtfGrid(C.Structure):
 JF_MAX_RINGS = 40
 JF_MAX_BUSES = 1024
 JF_ROOM_MAX_TAPS = 262144
+JF_MAX_HRTF_SETS = 64
 
 
 class JfGridLayout(C.Structure):
@@ -135,6 +136,16 @@ _SIGS = {
     "jf_bus_meters": (C.c_int, [C.c_void_p, C.c_int, _f]),
     "jf_debug_master_block": (C.c_int, [_f, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, _f, _f, _f]),
     "jf_profile_read_master": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "jf_engine_add_hrtf_set": (C.c_int, [C.c_void_p, _f, C.c_int]),
+    "jf_engine_add_hrtf_sofa": (C.c_int, [C.c_void_p, C.c_char_p, C.c_float]),
+    "jf_num_hrtf_sets": (C.c_int, [C.c_void_p]),
+    "jf_source_set_hrtf": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "jf_source_hrtf": (C.c_int, [C.c_void_p, C.c_int]),
+    "jf_bus_set_hrtf": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "jf_debug_read_hrtf_set": (C.c_int, [C.c_void_p, C.c_int, _f]),
+    "jf_debug_set_record": (C.c_int, [_i, _f, _i, _f, _i, _i, _i, C.c_int, C.c_int, C.c_int]),
+    "jf_debug_last_set_stage": (C.c_int, [C.c_void_p]),
+    "jf_profile_read_sets": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "jf_listener_set_pose": (C.c_int, [C.c_void_p, C.c_int, _f, _f]),
     "jf_listener_get_pose": (C.c_int, [C.c_void_p, C.c_int, _f]),
     "jf_source_set_world": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float]),
@@ -346,6 +357,21 @@ def gain_record(rows_new, w_new, rows_old, w_old, n_new, n_old, flags, g0, g1, c
                                     float(g0), float(g1), int(canon))
     if rc < 0:
         raise JfError(rc, "gain_record")
+    return bool(rc), rn, wn, ro, wo, int(c[0]), int(c[1]), int(c[2])
+
+
+def set_record(rows_new, w_new, rows_old, w_old, n_new, n_old, flags, off0, off1, canon):
+    """jf_debug_set_record (host logic only): the HRTF-set rule on one descriptor ->
+    (changed, rows_new, w_new, rows_old, w_old, n_new, n_old, flags)"""
+    rn = np.ascontiguousarray(rows_new, np.int32).copy()
+    wn = np.ascontiguousarray(w_new, np.float32).copy()
+    ro = np.ascontiguousarray(rows_old, np.int32).copy()
+    wo = np.ascontiguousarray(w_old, np.float32).copy()
+    c = np.array([n_new, n_old, flags], np.int32)
+    rc = lib().jf_debug_set_record(_ip(rn), _fp(wn), _ip(ro), _fp(wo), _ip(c[0:1]), _ip(c[1:2]), _ip(c[2:3]),
+                                   int(off0), int(off1), int(canon))
+    if rc < 0:
+        raise JfError(rc, "set_record")
     return bool(rc), rn, wn, ro, wo, int(c[0]), int(c[1]), int(c[2])
 
 
@@ -785,6 +811,56 @@ class Engine:
         """ms in desc_gain_kernel since profile_enable(2)"""
         r = C.c_double()
         self._chk(lib().jf_profile_read_gain(self.h, C.byref(r)))
+        return r.value
+
+    # ---- HRTF sets (include/jefferson.h: "HRTF sets") ----
+    def add_hrtf_set(self, hrir):
+        """a further set on the engine's own directions, hrir [table_rows][2][taps] -> its index (jf_engine_add_hrtf_set)"""
+        hrir = np.ascontiguousarray(hrir, np.float32)
+        assert hrir.ndim == 3 and hrir.shape[0] == self.table_rows() and hrir.shape[1] == 2  # the C side reads rows x 2 x taps floats
+        rc = lib().jf_engine_add_hrtf_set(self.h, _fp(hrir), hrir.shape[2])
+        if rc < 0:
+            self._chk(rc)
+        return rc
+
+    def add_hrtf_sofa(self, path, tol_deg=0.05):
+        """a further set from a SOFA file on the engine's rings -> its index (jf_engine_add_hrtf_sofa)"""
+        rc = lib().jf_engine_add_hrtf_sofa(self.h, os.fsencode(path), tol_deg)
+        if rc < 0:
+            self._chk(rc)
+        return rc
+
+    def n_hrtf_sets(self):
+        return lib().jf_num_hrtf_sets(self.h)
+
+    def set_hrtf(self, s, hrtf_set, fade=True):
+        """source s hears through `hrtf_set`: crossfaded over the next call's first block, or (fade=False) at once"""
+        self._chk(lib().jf_source_set_hrtf(self.h, int(s), int(hrtf_set), int(bool(fade))))
+
+    def hrtf_of(self, s):
+        r = lib().jf_source_hrtf(self.h, int(s))
+        if r < 0:
+            self._chk(r)
+        return r
+
+    def set_bus_hrtf(self, bus, hrtf_set, fade=True):
+        """every source that is on `bus` now (jf_bus_set_hrtf)"""
+        self._chk(lib().jf_bus_set_hrtf(self.h, int(bus), int(hrtf_set), int(bool(fade))))
+
+    def read_hrtf_set(self, hrtf_set):
+        """one set's rows as read_table gives set 0's"""
+        t = np.zeros((self.table_rows(), 2, self.N // 2 + 1, 2), np.float32)
+        self._chk(lib().jf_debug_read_hrtf_set(self.h, int(hrtf_set), _fp(t)))
+        return t.view(np.complex64)[..., 0]
+
+    def last_set_stage(self):
+        """the last run launched desc_set_kernel"""
+        return bool(lib().jf_debug_last_set_stage(self.h))
+
+    def profile_read_sets(self):
+        """ms in desc_set_kernel since profile_enable(2)"""
+        r = C.c_double()
+        self._chk(lib().jf_profile_read_sets(self.h, C.byref(r)))
         return r.value
 
     # ---- bus masters (include/jefferson.h: "bus masters") ----

@@ -95,6 +95,8 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
         e->ev_gain_on[e->ev_used] = 0;  // (run_gain_stage says otherwise)
         e->ev_master_on.resize(e->ev_used + 1, 0);
         e->ev_master_on[e->ev_used] = 0;  // (run_master_stage says otherwise)
+        e->ev_set_on.resize(e->ev_used + 1, 0);
+        e->ev_set_on[e->ev_used] = 0;  // (run_set_stage says otherwise)
         if (shared) {
             while (e->ev_spec.size() <= e->ev_used) {
                 EventPair q;
@@ -141,6 +143,13 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
     if (ep) JF_HIP(e, hipEventRecord(ep->a, e->stream));
     if (!have) JF_HIP(e, launch_prep(e->rt, mode_now, d_pos, e->d_state[p], e->d_desc, e->S, K, canon, e->Nc, e->stream));
     if (ep) JF_HIP(e, hipEventRecord(ep->b, e->stream));
+    // HRTF sets: the row indices of the settled descriptors into the sources' sets (desc_set_kernel), AHEAD of the gains -- the
+    // gain rule scales whatever sets the set rule left, so a gain fade and a set switch on the same block compose
+    e->last_set = false;
+    if (e->sets_on) {
+        const int rc = run_set_stage(e, K, canon, timed);
+        if (rc) return rc;
+    }
     // per-source gain: the run's descriptors are settled (prepared just now, or ahead and swapped in: plain ones either way) --
     // desc_gain_kernel rewrites them once, the kernels below read them as they read any
     e->last_gain = false;
@@ -378,7 +387,7 @@ void destroy_engine(jf_engine *e) {
     DeviceGuard bind(e);  // (outlives the delete: the buffers are freed on the engine's device)
     if (e->rv_side) (void)hipStreamSynchronize(e->rv_side);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
-    for (auto *pool : {&e->ev_prep, &e->ev_fused, &e->ev_mix, &e->ev_reverb, &e->ev_spec, &e->ev_pose, &e->ev_gain, &e->ev_master})
+    for (auto *pool : {&e->ev_prep, &e->ev_fused, &e->ev_mix, &e->ev_reverb, &e->ev_spec, &e->ev_pose, &e->ev_gain, &e->ev_master, &e->ev_set})
         for (auto &p : *pool) {
             (void)hipEventDestroy(p.a);
             (void)hipEventDestroy(p.b);
@@ -388,6 +397,8 @@ void destroy_engine(jf_engine *e) {
     for (hipEvent_t ev : e->ev_g_copy)
         if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->ev_m_copy)
+        if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : e->ev_s_copy)
         if (ev) (void)hipEventDestroy(ev);
     if (e->rv_side) (void)hipStreamDestroy(e->rv_side);
     if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -1374,12 +1385,17 @@ static int submit_block(jf_engine *e, const float *in, bool interleaved) {
         }
         GainCall gains(e);  // (nothing to settle where the call is not active: the one-launch path below)
         {
+            const int rc = sets_latch(e);  // the sources' HRTF sets (jf_engine_sets.cpp)
+            if (rc) return rc;
+        }
+        SetCall sets(e);
+        {
             const int rc = master_latch(e);  // the bus masters the setters hold (jf_engine_master.cpp)
             if (rc) return rc;
         }
         MasterCall masters(e);
         e->meters_stage_blocks = 0;
-        if (e->S <= e->rt_max_sources && !e->profiling && e->N == kN && e->n_buses == 1 && e->room.P == 0 && !e->gain_on && !e->master_on) {  // (PAD_LEN 2048, buses, a room, an active gain or master: the batch path with K = 1)
+        if (e->S <= e->rt_max_sources && !e->profiling && e->N == kN && e->n_buses == 1 && e->room.P == 0 && !e->gain_on && !e->master_on && !e->sets_on) {  // (PAD_LEN 2048, buses, a room, an active gain or master, a source on another HRTF set: the batch path with K = 1)
             // few sources: ONE launch does descriptors, spatialisation and mix, reading the positions
             // from and writing the stereo block to pinned host memory -- no copies, one sync
             const int p = e->cur;
@@ -1844,6 +1860,9 @@ int jf_batch_run(jf_engine *e, int first_block, int n_blocks, float *d_out_mix) 
     int rc = gain_latch(e);
     if (rc) return rc;
     GainCall gains(e);
+    rc = sets_latch(e);  // (asynchronous copies as the gains': the call does not wait for the stream)
+    if (rc) return rc;
+    SetCall sets(e);
     rc = master_latch(e);  // (its parameter copies are asynchronous as well: the call does not wait for the stream)
     if (rc) return rc;
     MasterCall masters(e);
@@ -1949,6 +1968,9 @@ static int process_batch(jf_engine *e, int n_blocks, const float *in, const floa
     rc = gain_latch(e, n_blocks);
     if (rc) return rc;
     GainCall gains(e);  // a failure below settles the blocks that were launched
+    rc = sets_latch(e);
+    if (rc) return rc;
+    SetCall sets(e);  // (only the call's first run switches: run_set_stage)
     rc = master_latch(e);
     if (rc) return rc;
     MasterCall masters(e);  // (the limiter's state carries from run to run on the device; only the first run ramps)

@@ -216,6 +216,7 @@ int jf_debug_set_interp_table(jf_engine *e, int on) {
     if (on < 0 || on > 2) return fail(e, JF_ERR_ARG, "0 = never, 1 = always, 2 = decided per run");
     if (on && e->N != kN) return fail(e, JF_ERR_ARG, "no pre-interpolated rows at PAD_LEN 2048");
     if (on && e->rt.cloud.tri) return fail(e, JF_ERR_ARG, "no pre-interpolated rows on a cloud engine");
+    if (on && e->n_sets > 1) return fail(e, JF_ERR_STATE, "no pre-interpolated rows on an engine that has added an HRTF set");
     if (on && !e->interp_avail) return fail(e, JF_ERR_STATE, "this engine was created without the pre-interpolated rows");
     e->interp_use = on;  // the mode word of the next run changes with it: descriptors prepared ahead no longer match
     if (on == 1) {       // "always" builds them now (a run under "per run" builds them when it first takes them)
@@ -482,6 +483,7 @@ const char *jf_debug_last_kernels(jf_engine *e) {
         if (e->last_pose) k = e->last_pose == 2 ? "pose_object_kernel;" : "pose_kernel;";
         if (e->last_ingest) k += "live_ingest_kernel;";
         if (!e->last_rt && !e->last_prep_skipped) k += "prep_kernel;";
+        if (!e->last_rt && e->last_set) k += "desc_set_kernel;";
         if (!e->last_rt && e->last_gain) k += "desc_gain_kernel;";
         const bool room = e->room.P > 0 && !e->last_rt && e->room.last_K > 0;  // (jf_engine_room.cpp)
         if (room) k += "room_send_kernel<" + bs + ">;room_fft_kernel<" + bs + ">;room_mac_kernel<" + bs + "," + std::to_string(room_mac_waves(e->B)) + ">;";

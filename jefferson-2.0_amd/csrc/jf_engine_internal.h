@@ -12,6 +12,9 @@
 //                         them to a run's descriptors (run_gain_stage, jf_gain.hip) and jf_source_set_gain / jf_batch_set_gains
 //   jf_engine_master.cpp  bus masters: the per-bus master gains, limiters and meters, what a processing call latches of them, the
 //                         stage behind the mix (run_master_stage, jf_master.hip) and jf_bus_set_master / jf_bus_meters
+//   jf_engine_sets.cpp    HRTF sets: further sets behind the engine's own in the table, the sources' sets, what a processing call
+//                         latches of them, the stage that moves a run's descriptors into them (run_set_stage, jf_sets.hip) and
+//                         jf_engine_add_hrtf_set / jf_source_set_hrtf
 //   jf_engine_debug.cpp   every entry point of include/jefferson_debug.h (taps, timing hooks, tuning switches, accessors)
 // Not part of any interface: nothing outside csrc/ includes this file.
 #ifndef JF_ENGINE_INTERNAL_H
@@ -94,6 +97,9 @@ hipError_t launch_pose_objects(const float *d_objects, const int *d_object_of, c
 // per-source gain (jf_gain.hip): the gains of a run onto its descriptors, behind prep_kernel
 hipError_t launch_desc_gain(ItemDesc *d_desc, const float *d_g_prev, const float *d_g_new, const float *d_g_traj, int S, int K,
                             int canon, hipStream_t st);
+// HRTF sets (jf_sets.hip): the row indices of a run's descriptors into the sources' sets, behind prep_kernel
+hipError_t launch_desc_set(ItemDesc *d_desc, const int *d_set_prev, const int *d_set_new, int S, int K, int n_rows, int canon,
+                           hipStream_t st);
 // bus masters (jf_master.hip): master gain, limiter and meters on a run's finished mix, in place
 hipError_t launch_master(float *d_mix, const float *d_par, float *d_state, float *d_t, float *d_gg, float *d_meters, int B, int K,
                          int n_buses, int ramp, hipStream_t st);
@@ -448,6 +454,31 @@ struct jf_engine : ReverbSetup {
     std::vector<EventPair> ev_master;         // profiling 2: around the stage (jf_profile_read_master)
     std::vector<char> ev_master_on;           // ... of the timed runs that launched it
 
+    // HRTF SETS (jf_engine_add_hrtf_set, jf_source_set_hrtf).  d_htab holds n_sets sets one behind the other,
+    // set j in rows j n_rows .. (j + 1) n_rows - 1 (no pre-interpolated rows once n_sets > 1: interp_avail is false for good).
+    // Every source has a current set: hs_new is what the setters ask for, hs_prev what the last rendered block used.
+    // desc_set_kernel (jf_sets.hip) moves the row indices of a run's descriptors behind prep_kernel and ahead of
+    // desc_gain_kernel; the spatialiser kernels are the ones of an engine with one set.  The host state is under pos_mu like
+    // `pos` and empty until a source is first given a set; the device buffers do not exist before the first ACTIVE call: one
+    // that finds an hs_prev or hs_new other than 0 (sets_latch).
+    std::atomic<int> n_sets{1};               // written by the processing thread (jf_engine_add_hrtf_set), read by the setters
+    std::vector<int> hs_prev, hs_new;         // [S] (empty: every source is on set 0)
+    std::vector<char> hs_snapped;             // [S] hs_prev was set at once (fade == 0) since the last call latched the sets
+    // what the processing call in hand latched (its thread's alone)
+    bool sets_on = false;                     // the call is active
+    bool set_switch = false;                  // the call's next run is its first and some source changes its set
+    bool set_rendered = false;                // a run of the call has launched the stage (sets_settle: hs_prev := hs_new)
+    std::vector<int> run_s0, run_s1;          // [S] the sets of the block before the call, and the call's
+    DevBuf<int> d_set_prev, d_set_new;        // [S]
+    std::vector<int> dev_set_prev, dev_set_new;  // what they hold (empty: nothing yet)
+    PinnedBuf<int> h_s_stage;                 // [kGainStageSlots][2][S] pinned staging of the asynchronous copies to them
+    hipEvent_t ev_s_copy[kGainStageSlots] = {};  // ... as ev_g_copy
+    bool s_copy_pending[kGainStageSlots] = {};
+    int s_stage_slot = 0;
+    bool last_set = false;                    // the last run launched desc_set_kernel (jf_debug_last_kernels)
+    std::vector<EventPair> ev_set;            // profiling 2: around desc_set_kernel (jf_profile_read_sets)
+    std::vector<char> ev_set_on;              // ... of the timed runs that launched it
+
     PinnedBuf<float> h_pos_pinned;  // [S][5]   pinned + mapped: the real-time kernel reads it in place
     PinnedBuf<float> h_out_pinned;  // [kRtMaxWgs][2B] pinned + mapped: ... and writes its workgroups' stereo blocks in place
     int rt_wgs = 0;                 // partial blocks the block in flight left there (0: one finished block)
@@ -713,6 +744,20 @@ struct MasterCall {
     MasterCall(const MasterCall &) = delete;
     MasterCall &operator=(const MasterCall &) = delete;
 };  // level 1, not muted, at once (jf_source_set_signal)
+// HRTF sets (jf_engine_sets.cpp).  sets_latch: at the start of a processing call that is not paused, beside gain_latch -- what
+// the setters hold becomes the call's (e->sets_on, run_s0, run_s1), the device copies that differ are enqueued.
+// run_set_stage: from run_blocks right behind the descriptor preparation and AHEAD of run_gain_stage, while e->sets_on.
+// sets_settle: when the call is over, however it ends (SetCall) -- hs_prev := hs_new if a run was launched.
+JF_INTERNAL int sets_latch(jf_engine *e);
+JF_INTERNAL int run_set_stage(jf_engine *e, int K, int canon, bool timed);
+JF_INTERNAL void sets_settle(jf_engine *e);
+struct SetCall {
+    jf_engine *e;
+    explicit SetCall(jf_engine *e_) : e(e_) {}
+    ~SetCall() { sets_settle(e); }
+    SetCall(const SetCall &) = delete;
+    SetCall &operator=(const SetCall &) = delete;
+};
 JF_INTERNAL int ensure_interp_rows(jf_engine *e);
 JF_INTERNAL int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int first_block = -1);
 JF_INTERNAL int reset_sources(jf_engine *e, int src);
