@@ -73,7 +73,7 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
     }
     const int p = e->cur;
     const bool n1024 = e->N == kN;
-    EventPair *ep = nullptr, *ef = nullptr, *em = nullptr, *es = nullptr;
+    EventPair *ep = nullptr, *ef = nullptr, *em = nullptr;
     // shared inputs: the groups' forward transforms once per block, ahead of the fused kernel's SHARED instantiation (the
     // reverb stage keeps per-source state and refuses followers; PAD_LEN 2048 runs them as aliases)
     const bool shared = n1024 && e->rv_P == 0 && e->n_slots > 0;
@@ -89,22 +89,7 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
         ep = next_events(e, e->ev_prep);
         em = next_events(e, e->ev_mix);
         if (!ep || !em) return fail(e, JF_ERR_DEVICE, "hipEventCreate failed");
-        e->ev_spec_on.resize(e->ev_used + 1, 0);
-        e->ev_spec_on[e->ev_used] = shared;
-        e->ev_gain_on.resize(e->ev_used + 1, 0);
-        e->ev_gain_on[e->ev_used] = 0;  // (run_gain_stage says otherwise)
-        e->ev_master_on.resize(e->ev_used + 1, 0);
-        e->ev_master_on[e->ev_used] = 0;  // (run_master_stage says otherwise)
-        e->ev_set_on.resize(e->ev_used + 1, 0);
-        e->ev_set_on[e->ev_used] = 0;  // (run_set_stage says otherwise)
-        if (shared) {
-            while (e->ev_spec.size() <= e->ev_used) {
-                EventPair q;
-                if (hipEventCreate(&q.a) != hipSuccess || hipEventCreate(&q.b) != hipSuccess) return fail(e, JF_ERR_DEVICE, "hipEventCreate failed");
-                e->ev_spec.push_back(q);
-            }
-            es = &e->ev_spec[e->ev_used];
-        }
+        for (StageTimer *t : {&e->tm_spec, &e->tm_set, &e->tm_gain, &e->tm_master}) t->arm(e->ev_used);  // (the stage that runs says otherwise)
     }
     const long long n_items = (long long)K * e->S;
     int G = 1;
@@ -197,9 +182,11 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
         int max_wgs = e->resident_wgs[(G > 1 ? (rows ? 2 : 1) : 0) + (shared ? 3 : 0)];
         if (e->grid_limit > 0 && e->grid_limit < max_wgs) max_wgs = e->grid_limit;
         if (shared) {
-            if (es) JF_HIP(e, hipEventRecord(es->a, e->stream));
+            int rc = e->tm_spec.begin(e, timed);
+            if (rc) return rc;
             JF_HIP(e, launch_shared_spectrum(P, e->stream));
-            if (es) JF_HIP(e, hipEventRecord(es->b, e->stream));
+            rc = e->tm_spec.end(e, timed);
+            if (rc) return rc;
         }
         JF_HIP(e, launch_fused(P, max_wgs, e->stream));
     } else {
@@ -387,22 +374,16 @@ void destroy_engine(jf_engine *e) {
     DeviceGuard bind(e);  // (outlives the delete: the buffers are freed on the engine's device)
     if (e->rv_side) (void)hipStreamSynchronize(e->rv_side);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
-    for (auto *pool : {&e->ev_prep, &e->ev_fused, &e->ev_mix, &e->ev_reverb, &e->ev_spec, &e->ev_pose, &e->ev_gain, &e->ev_master, &e->ev_set})
+    for (auto *pool : {&e->ev_prep, &e->ev_fused, &e->ev_mix, &e->ev_reverb, &e->ev_pose, &e->tm_spec.ev, &e->tm_gain.ev, &e->tm_master.ev, &e->tm_set.ev})
         for (auto &p : *pool) {
             (void)hipEventDestroy(p.a);
             (void)hipEventDestroy(p.b);
         }
     if (e->rv_ev_main) (void)hipEventDestroy(e->rv_ev_main);
     if (e->rv_ev_side) (void)hipEventDestroy(e->rv_ev_side);
-    for (hipEvent_t ev : e->ev_g_copy)
-        if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : e->ev_m_copy)
-        if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : e->ev_s_copy)
-        if (ev) (void)hipEventDestroy(ev);
     if (e->rv_side) (void)hipStreamDestroy(e->rv_side);
     if (e->stream) (void)hipStreamDestroy(e->stream);
-    delete e;  // every buffer goes with its owner (DevBuf, PinnedBuf), after the streams have been waited for
+    delete e;  // every buffer goes with its owner (DevBuf, PinnedBuf; the staging rings with their events), after the streams have been waited for
 }
 
 int check_config(const jf_config *cfg, const float *hrir, int taps, jf_engine **out, int *pad_len) {
@@ -1379,21 +1360,11 @@ static int submit_block(jf_engine *e, const float *in, bool interleaved) {
         e->meters_stage_blocks = 0;  // (a paused call leaves the masters and the meters alone)
     } else {
         snapshot_positions(e, e->h_pos_pinned);
+        CallLatches call(e);  // the gains, HRTF sets and bus masters the setters hold (nothing to settle where none is active: the one-launch path below)
         {
-            const int rc = gain_latch(e);  // the levels and mutes the setters hold (jf_engine_gain.cpp)
+            const int rc = call.latch();
             if (rc) return rc;
         }
-        GainCall gains(e);  // (nothing to settle where the call is not active: the one-launch path below)
-        {
-            const int rc = sets_latch(e);  // the sources' HRTF sets (jf_engine_sets.cpp)
-            if (rc) return rc;
-        }
-        SetCall sets(e);
-        {
-            const int rc = master_latch(e);  // the bus masters the setters hold (jf_engine_master.cpp)
-            if (rc) return rc;
-        }
-        MasterCall masters(e);
         e->meters_stage_blocks = 0;
         if (e->S <= e->rt_max_sources && !e->profiling && e->N == kN && e->n_buses == 1 && e->room.P == 0 && !e->gain_on && !e->master_on && !e->sets_on) {  // (PAD_LEN 2048, buses, a room, an active gain or master, a source on another HRTF set: the batch path with K = 1)
             // few sources: ONE launch does descriptors, spatialisation and mix, reading the positions
@@ -1464,7 +1435,7 @@ static int submit_block(jf_engine *e, const float *in, bool interleaved) {
         e->own_mix_blocks = 0;  // (d_mix no longer holds the last jf_batch_run's blocks)
         int rc = run_blocks(e, e->d_pos_rt, 1, e->d_mix);
         if (rc) return rc;
-        gains.settle();
+        call.settle();
         if (e->master_on && e->master_meters) {  // the block's meters come with the block (jf_collect_block)
             rc = master_meters_copy(e, 1);
             if (rc) return rc;
@@ -1857,17 +1828,11 @@ int jf_batch_run(jf_engine *e, int first_block, int n_blocks, float *d_out_mix) 
     return jf_guard([&]() -> int {
     DeviceGuard bind(e);
     if (!e) return JF_ERR_ARG;
-    int rc = gain_latch(e);
+    CallLatches call(e);
+    int rc = call.latch();  // (their device copies are asynchronous: the call does not wait for the stream)
     if (rc) return rc;
-    GainCall gains(e);
-    rc = sets_latch(e);  // (asynchronous copies as the gains': the call does not wait for the stream)
-    if (rc) return rc;
-    SetCall sets(e);
-    rc = master_latch(e);  // (its parameter copies are asynchronous as well: the call does not wait for the stream)
-    if (rc) return rc;
-    MasterCall masters(e);
     rc = batch_run(e, first_block, n_blocks, d_out_mix);
-    if (rc == JF_OK) gains.settle();
+    if (rc == JF_OK) call.settle();
     // the run's meters stay on the device until jf_batch_fetch or jf_bus_meters brings them over
     if (rc == JF_OK && e->master_on && e->master_meters) {
         e->meters_dev_blocks = n_blocks;
@@ -1965,15 +1930,11 @@ static int process_batch(jf_engine *e, int n_blocks, const float *in, const floa
     rc = positions ? upload_positions(e, n_blocks, positions) : upload_world(e, n_blocks, world, poses, by_object);
     if (rc) return rc;
     // the gains of the call: the standing ones, or the staged trajectory (kept if the positions were refused above)
-    rc = gain_latch(e, n_blocks);
+    // (a failure below settles the blocks that were launched; only the call's first run switches sets and ramps the masters,
+    // the limiter's state carries from run to run on the device)
+    CallLatches call(e);
+    rc = call.latch(n_blocks);
     if (rc) return rc;
-    GainCall gains(e);  // a failure below settles the blocks that were launched
-    rc = sets_latch(e);
-    if (rc) return rc;
-    SetCall sets(e);  // (only the call's first run switches: run_set_stage)
-    rc = master_latch(e);
-    if (rc) return rc;
-    MasterCall masters(e);  // (the limiter's state carries from run to run on the device; only the first run ramps)
     e->last_pose = positions ? 0 : by_object ? 2 : 1;
     const size_t blk = (size_t)2 * e->B;
     std::vector<float> last_rec;  // a world call: the last block's records by the host twin
@@ -1988,7 +1949,7 @@ static int process_batch(jf_engine *e, int n_blocks, const float *in, const floa
         }
         rc = batch_run(e, b0, k, nullptr);
         if (rc) return rc;
-        gains.rendered = b0 + k;
+        call.rendered = b0 + k;
         if (e->n_buses == 1)
             JF_HIP(e, hipMemcpyAsync(out_mix + (size_t)b0 * blk, e->d_mix, sizeof(float) * blk * k, hipMemcpyDeviceToHost,
                                      e->stream));
@@ -2010,7 +1971,7 @@ static int process_batch(jf_engine *e, int n_blocks, const float *in, const floa
         if (device_fault(e)) return fail(e, JF_ERR_DEVICE, kHandOffMsg);
         if (metered) master_meters_land(e, k, b0, n_blocks);
     }
-    gains.settle(n_blocks);
+    call.settle(n_blocks);
     // n_blocks callbacks have run: the sources stand where the last of them read them
     if (positions) return jf_sources_set_latched(e, positions + (size_t)(n_blocks - 1) * e->S * JF_POS_FLOATS);
     // ... every source world-placed at the last block's position (a position of its own: no object has it any more), every

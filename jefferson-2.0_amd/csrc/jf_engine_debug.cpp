@@ -56,16 +56,7 @@ int jf_profile_read_spectrum(jf_engine *e, double *spectrum_ms) {
     return jf_guard([&]() -> int {
     DeviceGuard bind(e);
     if (!e || !spectrum_ms) return JF_ERR_ARG;
-    JF_HIP(e, hipStreamSynchronize(e->stream));
-    double r = 0;
-    for (size_t i = 0; e->profiling >= 2 && i < e->ev_used && i < e->ev_spec_on.size() && i < e->ev_spec.size(); i++) {
-        if (!e->ev_spec_on[i]) continue;
-        float ms = 0;
-        JF_HIP(e, hipEventElapsedTime(&ms, e->ev_spec[i].a, e->ev_spec[i].b));
-        r += ms;
-    }
-    *spectrum_ms = r;
-    return JF_OK;
+    return e->tm_spec.sum(e, spectrum_ms);
     });
 }
 

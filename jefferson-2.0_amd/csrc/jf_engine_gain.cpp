@@ -1,7 +1,7 @@
 // jf_engine_gain.cpp -- the host side of per-source gain (include/jefferson.h: "per-source gain"): levels, mutes
 // and fades applied to the DESCRIPTORS of a batch run.  The setters (jf_source_set_gain, jf_source_set_mute,
 // jf_sources_set_gains, jf_batch_set_gains) only write host state under the positions' mutex; a processing call latches it
-// (gain_latch), run_blocks applies it to the descriptors it has settled on (run_gain_stage: desc_gain_kernel, jf_gain.hip) and
+// (gain_latch), run_blocks applies it to the descriptors it has settled on (run_gain_stage: desc_gain_kernel, jf_desc_edit.hip) and
 // the call gives the gains of its last block back as g_prev (gain_settle).  jf_debug_gain_record is the rule for one record on
 // the host -- the header the kernel compiles (jf_gain_rule.h).
 //
@@ -57,36 +57,29 @@ int gain_traj_check(jf_engine *e, int traj_blocks) {
     return traj_mismatch(e, traj_blocks);
 }
 
-// The device copies of the call's g[-1] and standing gains, where they differ from what the device holds: asynchronous copies
-// out of a pinned staging, enqueued by gain_latch BEFORE anything of the call -- the host never waits for the stream's work
-// (an otherwise asynchronous jf_batch_run stays one).  The staging has kGainStageSlots slots taken in turn; a slot is reused
-// only when the copy out of it has run, so the host waits only with that many level changes still in line.
+// The device copies of the call's g[-1] and standing gains, where they differ from what the device holds, out of the staging
+// ring (StagedRing), enqueued by gain_latch BEFORE anything of the call.
 static int gain_upload(jf_engine *e, bool traj) {
     const size_t S = (size_t)e->S;
     const bool need_new = !traj && e->dev_g_new != e->run_g1;  // (a trajectory call reads its gains from d_g_traj)
     const bool need_prev = (traj || e->gain_ramp) && e->dev_g_prev != e->run_g0;
     if (!need_new && !need_prev) return JF_OK;
-    if (!e->h_g_stage) {
-        JF_HIP(e, e->h_g_stage.alloc(kGainStageSlots * 2 * S));
-        for (int i = 0; i < kGainStageSlots; i++) JF_HIP(e, hipEventCreateWithFlags(&e->ev_g_copy[i], hipEventDisableTiming));
-    }
-    const int slot = e->g_stage_slot;
-    e->g_stage_slot = (slot + 1) % kGainStageSlots;
-    if (e->g_copy_pending[slot]) JF_HIP(e, hipEventSynchronize(e->ev_g_copy[slot]));
-    float *stage = e->h_g_stage + (size_t)slot * 2 * S;
+    float *stage = nullptr;
+    const int rc = e->g_ring.take(e, 2 * S, &stage);
+    if (rc) return rc;
     if (need_new) {
         memcpy(stage, e->run_g1.data(), sizeof(float) * S);
+        e->dev_g_new.clear();  // (nothing, should the copy fail)
         JF_HIP(e, hipMemcpyAsync(e->d_g_new, stage, sizeof(float) * S, hipMemcpyHostToDevice, e->stream));
         e->dev_g_new = e->run_g1;
     }
     if (need_prev) {
         memcpy(stage + S, e->run_g0.data(), sizeof(float) * S);
+        e->dev_g_prev.clear();
         JF_HIP(e, hipMemcpyAsync(e->d_g_prev, stage + S, sizeof(float) * S, hipMemcpyHostToDevice, e->stream));
         e->dev_g_prev = e->run_g0;
     }
-    JF_HIP(e, hipEventRecord(e->ev_g_copy[slot], e->stream));
-    e->g_copy_pending[slot] = true;
-    return JF_OK;
+    return e->g_ring.sent(e);
 }
 
 int gain_latch(jf_engine *e, int traj_blocks) {
@@ -157,20 +150,11 @@ int run_gain_stage(jf_engine *e, int K, int canon, bool timed) {
     } else if (e->gain_ramp) {
         g_prev = e->d_g_prev;
     }
-    EventPair *eg = nullptr;
-    if (timed && e->profiling >= 2) {
-        while (e->ev_gain.size() <= e->ev_used) {
-            EventPair q;
-            if (hipEventCreate(&q.a) != hipSuccess || hipEventCreate(&q.b) != hipSuccess) return fail(e, JF_ERR_DEVICE, "hipEventCreate failed");
-            e->ev_gain.push_back(q);
-        }
-        e->ev_gain_on.resize(e->ev_used + 1, 0);
-        e->ev_gain_on[e->ev_used] = 1;
-        eg = &e->ev_gain[e->ev_used];
-    }
-    if (eg) JF_HIP(e, hipEventRecord(eg->a, e->stream));
+    int rc = e->tm_gain.begin(e, timed);
+    if (rc) return rc;
     JF_HIP(e, launch_desc_gain(e->d_desc, g_prev, g_new, g_traj, e->S, K, canon, e->stream));
-    if (eg) JF_HIP(e, hipEventRecord(eg->b, e->stream));
+    rc = e->tm_gain.end(e, timed);
+    if (rc) return rc;
     e->last_gain = true;
     // the run that follows in this call continues from this one's last block
     if (traj)
@@ -302,44 +286,15 @@ int jf_batch_set_gains(jf_engine *e, int n_blocks, const float *gains) {
 
 int jf_debug_gain_record(int rows_new[4], float w_new[4], int rows_old[4], float w_old[4], int *n_new, int *n_old, int *flags,
                          float g0, float g1, int canon) {
-    if (!rows_new || !w_new || !rows_old || !w_old || !n_new || !n_old || !flags) return JF_ERR_ARG;
-    GainRecord d;
-    for (int t = 0; t < 4; t++) {
-        d.rows_new[t] = rows_new[t];
-        d.w_new[t] = w_new[t];
-        d.rows_old[t] = rows_old[t];
-        d.w_old[t] = w_old[t];
-    }
-    d.n_new = *n_new;
-    d.n_old = *n_old;
-    d.flags = *flags;
-    const bool changed = gain_rule(d, g0, g1, canon);
-    for (int t = 0; t < 4; t++) {
-        rows_new[t] = d.rows_new[t];
-        w_new[t] = d.w_new[t];
-        rows_old[t] = d.rows_old[t];
-        w_old[t] = d.w_old[t];
-    }
-    *n_new = d.n_new;
-    *n_old = d.n_old;
-    *flags = d.flags;
-    return changed ? 1 : 0;
+    return debug_record_rule(rows_new, w_new, rows_old, w_old, n_new, n_old, flags,
+                             [&](DescRecord &d) { return gain_rule(d, g0, g1, canon); });
 }
 
 int jf_profile_read_gain(jf_engine *e, double *gain_ms) {
     return jf_guard([&]() -> int {
     DeviceGuard bind(e);
     if (!e || !gain_ms) return JF_ERR_ARG;
-    JF_HIP(e, hipStreamSynchronize(e->stream));
-    double r = 0;
-    for (size_t i = 0; e->profiling >= 2 && i < e->ev_used && i < e->ev_gain_on.size() && i < e->ev_gain.size(); i++) {
-        if (!e->ev_gain_on[i]) continue;
-        float ms = 0;
-        JF_HIP(e, hipEventElapsedTime(&ms, e->ev_gain[i].a, e->ev_gain[i].b));
-        r += ms;
-    }
-    *gain_ms = r;
-    return JF_OK;
+    return e->tm_gain.sum(e, gain_ms);
     });
 }
 

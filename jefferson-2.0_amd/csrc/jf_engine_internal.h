@@ -9,13 +9,15 @@
 //   jf_engine_room.cpp    the room stage's schedule (run_room_stage, run_room_add: an auxiliary send per output bus, jf_room.hip)
 //                         and jf_room_set_ir / jf_source_set_send
 //   jf_engine_gain.cpp    per-source gain: the levels and mutes, what a processing call latches of them, the stage that applies
-//                         them to a run's descriptors (run_gain_stage, jf_gain.hip) and jf_source_set_gain / jf_batch_set_gains
+//                         them to a run's descriptors (run_gain_stage, jf_desc_edit.hip) and jf_source_set_gain / jf_batch_set_gains
 //   jf_engine_master.cpp  bus masters: the per-bus master gains, limiters and meters, what a processing call latches of them, the
 //                         stage behind the mix (run_master_stage, jf_master.hip) and jf_bus_set_master / jf_bus_meters
 //   jf_engine_sets.cpp    HRTF sets: further sets behind the engine's own in the table, the sources' sets, what a processing call
-//                         latches of them, the stage that moves a run's descriptors into them (run_set_stage, jf_sets.hip) and
-//                         jf_engine_add_hrtf_set / jf_source_set_hrtf
+//                         latches of them, the stage that moves a run's descriptors into them (run_set_stage, jf_desc_edit.hip)
+//                         and jf_engine_add_hrtf_set / jf_source_set_hrtf
 //   jf_engine_debug.cpp   every entry point of include/jefferson_debug.h (taps, timing hooks, tuning switches, accessors)
+// What the three latched controls (gain, masters, sets) share is here once: StagedRing (their asynchronous uploads), StageTimer
+// (the event pairs of a stage that only some runs launch), CallLatches (a processing call's latch and settlement of all three).
 // Not part of any interface: nothing outside csrc/ includes this file.
 #ifndef JF_ENGINE_INTERNAL_H
 #define JF_ENGINE_INTERNAL_H
@@ -94,10 +96,10 @@ hipError_t launch_pose(const float *d_world, const int *d_bus, const float *d_po
 // ... the same from objects[K][n_objects][3] and the sources' object map (pose_object_kernel)
 hipError_t launch_pose_objects(const float *d_objects, const int *d_object_of, const int *d_bus, const float *d_poses, float *d_pos,
                                int S, int K, int n_buses, int n_objects, hipStream_t st);
-// per-source gain (jf_gain.hip): the gains of a run onto its descriptors, behind prep_kernel
+// per-source gain (jf_desc_edit.hip): the gains of a run onto its descriptors, behind prep_kernel
 hipError_t launch_desc_gain(ItemDesc *d_desc, const float *d_g_prev, const float *d_g_new, const float *d_g_traj, int S, int K,
                             int canon, hipStream_t st);
-// HRTF sets (jf_sets.hip): the row indices of a run's descriptors into the sources' sets, behind prep_kernel
+// HRTF sets (jf_desc_edit.hip): the row indices of a run's descriptors into the sources' sets, behind prep_kernel
 hipError_t launch_desc_set(ItemDesc *d_desc, const int *d_set_prev, const int *d_set_new, int S, int K, int n_rows, int canon,
                            hipStream_t st);
 // bus masters (jf_master.hip): master gain, limiter and meters on a run's finished mix, in place
@@ -165,10 +167,53 @@ constexpr long kRtPollNs = 2000000;  // jf_collect_block polls the real-time ker
 constexpr int kRvFusedHeadMax = 64;  // partitions of B a wave takes a block through by itself (rv_head_wave)
 constexpr int kRtMaxWgs = 128;  // workgroups (8 or 16 waves, a source per wave and turn) of the one-launch real-time kernel: 64 and 256 measure slower
 
+constexpr int kGainStageSlots = 4;  // changes of a latched control whose device copies may be in line before a setter-to-run sequence waits
+
+struct jf_engine;
+
+// The pinned staging of a latched control's asynchronous copies to the device (gain_upload, master_upload, sets_upload): a
+// processing call enqueues them out of here BEFORE anything else of the call, so the host never waits for the stream's work and
+// an otherwise asynchronous jf_batch_run stays one.  kGainStageSlots slots of slot_len taken in turn; an event is recorded
+// behind a slot's copies and the slot is reused only once it has passed, so the host waits only with that many uploads still in
+// line.  take(): the next slot's memory; whatever is missing is created, each piece on its own -- a call that failed part-way
+// through leaves nothing half-made for the next one to trust.  sent(): the caller has enqueued its copies out of that slot.
+// Callers clear their mirror of the device's words before they enqueue and set it afterwards: a failed enqueue is never trusted.
+template <class T>
+struct StagedRing {
+    PinnedBuf<T> h;                          // [kGainStageSlots][slot_len]
+    hipEvent_t ev[kGainStageSlots] = {};     // recorded behind a slot's copies
+    bool pending[kGainStageSlots] = {};
+    int next = 0, cur = 0;                   // the slot the next take() hands out, and the one the last did
+    StagedRing() = default;
+    StagedRing(const StagedRing &) = delete;
+    StagedRing &operator=(const StagedRing &) = delete;
+    // The engine's streams have been waited for when the engine goes (destroy_engine), so every event here has passed; an event
+    // is not tied to the stream it was recorded on, so it does not matter that the streams are destroyed first.
+    ~StagedRing() {
+        for (hipEvent_t v : ev)
+            if (v) (void)hipEventDestroy(v);
+    }
+    inline int take(jf_engine *e, size_t slot_len, T **slot);
+    inline int sent(jf_engine *e);
+};
+
+// The event pairs around a stage that only some timed runs launch (profiling 2): a pair per timed run (index jf_engine::ev_used)
+// and whether that run launched the stage.  run_blocks arms every timer for the run; the stage brackets its launch with begin
+// and end (both nothing unless the run is timed at profiling 2); sum is what the jf_profile_read_* entries return.
+struct StageTimer {
+    std::vector<EventPair> ev;
+    std::vector<char> on;
+    void arm(size_t run) {
+        on.resize(run + 1, 0);
+        on[run] = 0;
+    }
+    inline int begin(jf_engine *e, bool timed);
+    inline int end(jf_engine *e, bool timed);
+    inline int sum(jf_engine *e, double *ms);  // waits for the engine's stream
+};
+
 // The convolution reverb as jf_reverb_set_ir set it up: buffers and dimensions, all empty / 0 while the reverb is off
 // (free_reverb: `= {}`).  Off while rv_P == 0.
-constexpr int kGainStageSlots = 4;  // level changes whose device copies may be in line before a setter-to-run sequence waits (jf_engine_gain.cpp)
-
 struct ReverbSetup {
     int rv_P = 0, rv_Rg = 0, rv_Wr = 0;
     DevBuf<float2> d_rv_hspec;
@@ -394,7 +439,7 @@ struct jf_engine : ReverbSetup {
 
     // PER-SOURCE GAIN (jf_source_set_gain, jf_batch_set_gains).  A source's effective gain is g = muted ? 0 :
     // level; g_new is what the setters ask for, g_prev what the last rendered block used.  Block k of a call weights its new
-    // filter set with g[k] and its old set with g[k - 1] (g[-1] = g_prev): desc_gain_kernel (jf_gain.hip) rewrites the run's
+    // filter set with g[k] and its old set with g[k - 1] (g[-1] = g_prev): desc_gain_kernel (jf_desc_edit.hip) rewrites the run's
     // descriptors behind prep_kernel, the spatialiser kernels are the ones of an engine without gains.  The host state is under
     // pos_mu like `pos`; all of it is empty in an engine that never set a gain, and the device buffers do not exist before the
     // first ACTIVE call: one that finds a g_prev or g_new other than 1, or a staged trajectory (gain_latch).
@@ -409,17 +454,13 @@ struct jf_engine : ReverbSetup {
     int gain_traj_first = -1;                 // the next run's first block in d_g_traj; -1: the call has no trajectory
     std::vector<float> run_traj;              // the call's trajectory on the host (what gain_abort settles a failed call from)
     bool gain_ramp = false;                   // the call's next run is its first and g[-1] differs from the standing gains
-    PinnedBuf<float> h_g_stage;               // [kGainStageSlots][2][S] pinned staging of the asynchronous copies to d_g_new / d_g_prev
-    hipEvent_t ev_g_copy[kGainStageSlots] = {};  // ... recorded behind a slot's copies: the slot is free once its event has passed
-    bool g_copy_pending[kGainStageSlots] = {};
-    int g_stage_slot = 0;                     // the slot the next upload takes
+    StagedRing<float> g_ring;                 // slots of [2][S]: the asynchronous copies to d_g_new / d_g_prev
     DevBuf<float> d_g_prev, d_g_new;          // [S]
     std::vector<float> dev_g_prev, dev_g_new; // what they hold (empty: nothing yet)
     DevBuf<float> d_g_traj;                   // [gain_traj_cap / S][S] the trajectory of the jf_process_batch* call in hand
     size_t gain_traj_cap = 0;                 // floats it holds
     bool last_gain = false;                   // the last run launched desc_gain_kernel (jf_debug_last_kernels)
-    std::vector<EventPair> ev_gain;           // profiling 2: around desc_gain_kernel (jf_profile_read_gain)
-    std::vector<char> ev_gain_on;             // ... of the timed runs that launched it
+    StageTimer tm_gain;                       // profiling 2: around desc_gain_kernel (jf_profile_read_gain)
 
     // BUS MASTERS (jf_bus_set_master, jf_bus_set_limiter, jf_engine_set_meters).  Per bus a master gain (m_prev
     // the last rendered block ended on, m_new asked for), a limiter (ceiling c, 0: off; release r) and meters; the rule for a
@@ -445,19 +486,15 @@ struct jf_engine : ReverbSetup {
     DevBuf<float> d_mt, d_mgg, d_meters;      // [master_cap][1], [..][2], [..][4]: per (bus, block) of a run
     size_t master_cap = 0;                    // items they hold (n_buses maxK when they were allocated)
     std::vector<float> dev_mpar;              // what d_mpar holds (empty: nothing yet)
-    PinnedBuf<float> h_m_stage;               // [kGainStageSlots][JF_MAX_BUSES][4] pinned staging of the asynchronous copies to d_mpar
-    hipEvent_t ev_m_copy[kGainStageSlots] = {};  // ... as ev_g_copy
-    bool m_copy_pending[kGainStageSlots] = {};
-    int m_stage_slot = 0;
+    StagedRing<float> m_ring;                 // slots of [JF_MAX_BUSES][4]: the asynchronous copies to d_mpar
     PinnedBuf<float> h_meters;                // [master_cap][4] where a call's meters land on the host
     bool last_master = false;                 // the last run launched the stage (jf_debug_last_kernels)
-    std::vector<EventPair> ev_master;         // profiling 2: around the stage (jf_profile_read_master)
-    std::vector<char> ev_master_on;           // ... of the timed runs that launched it
+    StageTimer tm_master;                     // profiling 2: around the stage (jf_profile_read_master)
 
     // HRTF SETS (jf_engine_add_hrtf_set, jf_source_set_hrtf).  d_htab holds n_sets sets one behind the other,
     // set j in rows j n_rows .. (j + 1) n_rows - 1 (no pre-interpolated rows once n_sets > 1: interp_avail is false for good).
     // Every source has a current set: hs_new is what the setters ask for, hs_prev what the last rendered block used.
-    // desc_set_kernel (jf_sets.hip) moves the row indices of a run's descriptors behind prep_kernel and ahead of
+    // desc_set_kernel (jf_desc_edit.hip) moves the row indices of a run's descriptors behind prep_kernel and ahead of
     // desc_gain_kernel; the spatialiser kernels are the ones of an engine with one set.  The host state is under pos_mu like
     // `pos` and empty until a source is first given a set; the device buffers do not exist before the first ACTIVE call: one
     // that finds an hs_prev or hs_new other than 0 (sets_latch).
@@ -471,13 +508,9 @@ struct jf_engine : ReverbSetup {
     std::vector<int> run_s0, run_s1;          // [S] the sets of the block before the call, and the call's
     DevBuf<int> d_set_prev, d_set_new;        // [S]
     std::vector<int> dev_set_prev, dev_set_new;  // what they hold (empty: nothing yet)
-    PinnedBuf<int> h_s_stage;                 // [kGainStageSlots][2][S] pinned staging of the asynchronous copies to them
-    hipEvent_t ev_s_copy[kGainStageSlots] = {};  // ... as ev_g_copy
-    bool s_copy_pending[kGainStageSlots] = {};
-    int s_stage_slot = 0;
+    StagedRing<int> s_ring;                   // slots of [2][S]: the asynchronous copies to them
     bool last_set = false;                    // the last run launched desc_set_kernel (jf_debug_last_kernels)
-    std::vector<EventPair> ev_set;            // profiling 2: around desc_set_kernel (jf_profile_read_sets)
-    std::vector<char> ev_set_on;              // ... of the timed runs that launched it
+    StageTimer tm_set;                        // profiling 2: around desc_set_kernel (jf_profile_read_sets)
 
     PinnedBuf<float> h_pos_pinned;  // [S][5]   pinned + mapped: the real-time kernel reads it in place
     PinnedBuf<float> h_out_pinned;  // [kRtMaxWgs][2B] pinned + mapped: ... and writes its workgroups' stereo blocks in place
@@ -500,8 +533,7 @@ struct jf_engine : ReverbSetup {
     long profile_calls = 0;
     bool timed_now = false;    // this batch run carries event records
     std::vector<EventPair> ev_prep, ev_fused, ev_mix, ev_reverb;
-    std::vector<EventPair> ev_spec;   // profiling 2: around shared_spectrum_kernel (inside the fused kernel's pair)
-    std::vector<char> ev_spec_on;     // ... of the timed runs that launched it (jf_profile_read_spectrum)
+    StageTimer tm_spec;        // profiling 2: around shared_spectrum_kernel, inside the fused kernel's pair (jf_profile_read_spectrum)
     size_t ev_used = 0;
 
     // convolution reverb stage (jf_reverb.hip): its buffers and dimensions are the base ReverbSetup, what it advances is
@@ -581,6 +613,53 @@ inline int fail(jf_engine *e, int code, const std::string &msg) {
         if (_s != hipSuccess)                                                                  \
             return fail((e), JF_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(_s)); \
     } while (0)
+
+template <class T>
+inline int StagedRing<T>::take(jf_engine *e, size_t slot_len, T **slot) {
+    for (hipEvent_t &v : ev)
+        if (!v) JF_HIP(e, hipEventCreateWithFlags(&v, hipEventDisableTiming));
+    if (!h) JF_HIP(e, h.alloc(kGainStageSlots * slot_len));
+    cur = next;
+    next = (cur + 1) % kGainStageSlots;
+    if (pending[cur]) JF_HIP(e, hipEventSynchronize(ev[cur]));
+    *slot = h + (size_t)cur * slot_len;
+    return JF_OK;
+}
+template <class T>
+inline int StagedRing<T>::sent(jf_engine *e) {
+    JF_HIP(e, hipEventRecord(ev[cur], e->stream));
+    pending[cur] = true;
+    return JF_OK;
+}
+
+inline int StageTimer::begin(jf_engine *e, bool timed) {
+    if (!timed || e->profiling < 2) return JF_OK;
+    while (ev.size() <= e->ev_used) {
+        EventPair q;
+        if (hipEventCreate(&q.a) != hipSuccess || hipEventCreate(&q.b) != hipSuccess) return fail(e, JF_ERR_DEVICE, "hipEventCreate failed");
+        ev.push_back(q);
+    }
+    on.resize(e->ev_used + 1, 0);
+    on[e->ev_used] = 1;
+    JF_HIP(e, hipEventRecord(ev[e->ev_used].a, e->stream));
+    return JF_OK;
+}
+inline int StageTimer::end(jf_engine *e, bool timed) {
+    if (timed && e->profiling >= 2) JF_HIP(e, hipEventRecord(ev[e->ev_used].b, e->stream));
+    return JF_OK;
+}
+inline int StageTimer::sum(jf_engine *e, double *ms) {
+    JF_HIP(e, hipStreamSynchronize(e->stream));
+    double r = 0;
+    for (size_t i = 0; e->profiling >= 2 && i < e->ev_used && i < on.size() && i < ev.size(); i++) {
+        if (!on[i]) continue;
+        float t = 0;
+        JF_HIP(e, hipEventElapsedTime(&t, ev[i].a, ev[i].b));
+        r += t;
+    }
+    *ms = r;
+    return JF_OK;
+}
 
 inline bool valid_src(const jf_engine *e, int s) { return e && s >= 0 && s < e->S; }
 inline int root_of(const jf_engine *e, int s) { return e->root.empty() ? s : e->root[s]; }  // jf_engine::root
@@ -706,28 +785,11 @@ JF_INTERNAL int gain_latch(jf_engine *e, int traj_blocks = -1);
 JF_INTERNAL int run_gain_stage(jf_engine *e, int K, int canon, bool timed);
 JF_INTERNAL void gain_settle(jf_engine *e, int traj_blocks = -1);
 JF_INTERNAL void gain_abort(jf_engine *e, int rendered);
-// a processing call between gain_latch and its end: settles the gains when the call succeeds, and on every other way out
-// settles what was rendered (gain_abort)
-struct GainCall {
-    jf_engine *e;
-    int rendered = 0;  // blocks of the call launched so far
-    bool done = false;
-    explicit GainCall(jf_engine *e_) : e(e_) {}
-    ~GainCall() {
-        if (!done) gain_abort(e, rendered);
-    }
-    void settle(int traj_blocks = -1) {
-        gain_settle(e, traj_blocks);
-        done = true;
-    }
-    GainCall(const GainCall &) = delete;
-    GainCall &operator=(const GainCall &) = delete;
-};
-JF_INTERNAL void gain_reset_source(jf_engine *e, int src);
+JF_INTERNAL void gain_reset_source(jf_engine *e, int src);  // level 1, not muted, at once (jf_source_set_signal)
 // bus masters (jf_engine_master.cpp).  master_latch: at the start of a processing call that is not paused, beside gain_latch --
 // what the setters hold becomes the call's (e->master_on, run_mpar), the device copies that differ are enqueued.
 // run_master_stage: from run_blocks behind run_room_add, while e->master_on.  master_settle: when the call is over, however
-// it ends (MasterCall) -- m_prev := m_new if a run was launched.  master_meters_copy enqueues the copy of a run's meters to
+// it ends (CallLatches) -- m_prev := m_new if a run was launched.  master_meters_copy enqueues the copy of a run's meters to
 // the pinned staging, master_meters_land takes them from there (the stream has been waited for) into the call's host copy
 // at block b0 of n_blocks; master_meters_fetch does both for what a jf_batch_run left on the device.
 JF_INTERNAL int master_latch(jf_engine *e);
@@ -737,27 +799,64 @@ JF_INTERNAL int master_meters_copy(jf_engine *e, int K);
 JF_INTERNAL void master_meters_land(jf_engine *e, int K, int b0, int n_blocks);
 JF_INTERNAL int master_meters_fetch(jf_engine *e);
 JF_INTERNAL void master_set_buses(jf_engine *e, int n_buses);  // under pos_mu: the buses that remain keep their sections
-struct MasterCall {
-    jf_engine *e;
-    explicit MasterCall(jf_engine *e_) : e(e_) {}
-    ~MasterCall() { master_settle(e); }
-    MasterCall(const MasterCall &) = delete;
-    MasterCall &operator=(const MasterCall &) = delete;
-};  // level 1, not muted, at once (jf_source_set_signal)
 // HRTF sets (jf_engine_sets.cpp).  sets_latch: at the start of a processing call that is not paused, beside gain_latch -- what
 // the setters hold becomes the call's (e->sets_on, run_s0, run_s1), the device copies that differ are enqueued.
 // run_set_stage: from run_blocks right behind the descriptor preparation and AHEAD of run_gain_stage, while e->sets_on.
-// sets_settle: when the call is over, however it ends (SetCall) -- hs_prev := hs_new if a run was launched.
+// sets_settle: when the call is over, however it ends (CallLatches) -- hs_prev := hs_new if a run was launched.
 JF_INTERNAL int sets_latch(jf_engine *e);
 JF_INTERNAL int run_set_stage(jf_engine *e, int K, int canon, bool timed);
 JF_INTERNAL void sets_settle(jf_engine *e);
-struct SetCall {
+// A processing call between its latches and its end.  latch: the gains, the sets, the masters, in that order, up to the first
+// that fails.  On every way out, of what was latched: the masters and the sets are settled, then the gains -- as the call
+// settled them (settle: it succeeded), else as far as its blocks were launched (gain_abort, `rendered`).
+struct CallLatches {
     jf_engine *e;
-    explicit SetCall(jf_engine *e_) : e(e_) {}
-    ~SetCall() { sets_settle(e); }
-    SetCall(const SetCall &) = delete;
-    SetCall &operator=(const SetCall &) = delete;
+    int latched = 0;   // of gain, sets, masters
+    int rendered = 0;  // blocks of the call launched so far
+    bool settled = false;
+    explicit CallLatches(jf_engine *e_) : e(e_) {}
+    int latch(int traj_blocks = -1) {
+        int rc = gain_latch(e, traj_blocks);
+        if (rc == JF_OK) latched = 1, rc = sets_latch(e);
+        if (rc == JF_OK) latched = 2, rc = master_latch(e);
+        if (rc == JF_OK) latched = 3;
+        return rc;
+    }
+    void settle(int traj_blocks = -1) {
+        gain_settle(e, traj_blocks);
+        settled = true;
+    }
+    ~CallLatches() {
+        if (latched >= 3) master_settle(e);
+        if (latched >= 2) sets_settle(e);
+        if (latched >= 1 && !settled) gain_abort(e, rendered);
+    }
+    CallLatches(const CallLatches &) = delete;
+    CallLatches &operator=(const CallLatches &) = delete;
 };
+// jf_debug_gain_record / jf_debug_set_record: one record, as the boundary's arrays, through a rule (bool(DescRecord &)); 1: changed
+template <class Rule>
+inline int debug_record_rule(int rows_new[4], float w_new[4], int rows_old[4], float w_old[4], int *n_new, int *n_old, int *flags,
+                             Rule rule) {
+    if (!rows_new || !w_new || !rows_old || !w_old || !n_new || !n_old || !flags) return JF_ERR_ARG;
+    DescRecord d;
+    memcpy(d.rows_new, rows_new, sizeof d.rows_new);
+    memcpy(d.w_new, w_new, sizeof d.w_new);
+    memcpy(d.rows_old, rows_old, sizeof d.rows_old);
+    memcpy(d.w_old, w_old, sizeof d.w_old);
+    d.n_new = *n_new;
+    d.n_old = *n_old;
+    d.flags = *flags;
+    const bool changed = rule(d);
+    memcpy(rows_new, d.rows_new, sizeof d.rows_new);
+    memcpy(w_new, d.w_new, sizeof d.w_new);
+    memcpy(rows_old, d.rows_old, sizeof d.rows_old);
+    memcpy(w_old, d.w_old, sizeof d.w_old);
+    *n_new = d.n_new;
+    *n_old = d.n_old;
+    *flags = d.flags;
+    return changed ? 1 : 0;
+}
 JF_INTERNAL int ensure_interp_rows(jf_engine *e);
 JF_INTERNAL int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int first_block = -1);
 JF_INTERNAL int reset_sources(jf_engine *e, int src);

@@ -42,29 +42,22 @@ void master_set_buses(jf_engine *e, int n_buses) {
     e->meters_stage_blocks = 0;
 }
 
-// The device copy of the call's parameters, where it differs from what the device holds: an asynchronous copy out of a pinned
-// staging, enqueued by master_latch BEFORE anything of the call -- the host never waits for the stream's work (gain_upload's
-// scheme: kGainStageSlots slots taken in turn, a slot reused only when the copy out of it has run).  m_prev matters only to a
-// call that ramps: a call that does not leaves the device's alone.
+// The device copy of the call's parameters, where it differs from what the device holds, out of the staging ring (StagedRing),
+// enqueued by master_latch BEFORE anything of the call.  m_prev matters only to a call that ramps: a call that does not leaves
+// the device's alone.
 static int master_upload(jf_engine *e) {
     const size_t n = e->run_mpar.size();
     bool need = e->dev_mpar.size() != n;
     for (size_t i = 0; i < n && !need; i++) need = (e->master_ramp || i % 4 != 0) && e->dev_mpar[i] != e->run_mpar[i];
     if (!need) return JF_OK;
-    if (!e->h_m_stage) {
-        JF_HIP(e, e->h_m_stage.alloc((size_t)kGainStageSlots * 4 * JF_MAX_BUSES));
-        for (int i = 0; i < kGainStageSlots; i++) JF_HIP(e, hipEventCreateWithFlags(&e->ev_m_copy[i], hipEventDisableTiming));
-    }
-    const int slot = e->m_stage_slot;
-    e->m_stage_slot = (slot + 1) % kGainStageSlots;
-    if (e->m_copy_pending[slot]) JF_HIP(e, hipEventSynchronize(e->ev_m_copy[slot]));
-    float *stage = e->h_m_stage + (size_t)slot * 4 * JF_MAX_BUSES;
+    float *stage = nullptr;
+    const int rc = e->m_ring.take(e, (size_t)4 * JF_MAX_BUSES, &stage);
+    if (rc) return rc;
     memcpy(stage, e->run_mpar.data(), sizeof(float) * n);
+    e->dev_mpar.clear();  // (nothing, should the copy fail)
     JF_HIP(e, hipMemcpyAsync(e->d_mpar, stage, sizeof(float) * n, hipMemcpyHostToDevice, e->stream));
-    JF_HIP(e, hipEventRecord(e->ev_m_copy[slot], e->stream));
-    e->m_copy_pending[slot] = true;
     e->dev_mpar = e->run_mpar;
-    return JF_OK;
+    return e->m_ring.sent(e);
 }
 
 int master_latch(jf_engine *e) {
@@ -129,21 +122,12 @@ int master_latch(jf_engine *e) {
 // inside the mix's event pair; an event pair of its own at profiling >= 2.
 int run_master_stage(jf_engine *e, int K, float *d_mix_out, bool timed) {
     if ((size_t)K * (size_t)e->n_buses > e->master_cap) return fail(e, JF_ERR_STATE, "bus masters: the run has more blocks than the stage holds");
-    EventPair *eg = nullptr;
-    if (timed && e->profiling >= 2) {
-        while (e->ev_master.size() <= e->ev_used) {
-            EventPair q;
-            if (hipEventCreate(&q.a) != hipSuccess || hipEventCreate(&q.b) != hipSuccess) return fail(e, JF_ERR_DEVICE, "hipEventCreate failed");
-            e->ev_master.push_back(q);
-        }
-        e->ev_master_on.resize(e->ev_used + 1, 0);
-        e->ev_master_on[e->ev_used] = 1;
-        eg = &e->ev_master[e->ev_used];
-    }
-    if (eg) JF_HIP(e, hipEventRecord(eg->a, e->stream));
+    int rc = e->tm_master.begin(e, timed);
+    if (rc) return rc;
     JF_HIP(e, launch_master(d_mix_out, e->d_mpar, e->d_mstate, e->d_mt, e->d_mgg, e->d_meters, e->B, K, e->n_buses, e->master_ramp ? 1 : 0,
                             e->stream));
-    if (eg) JF_HIP(e, hipEventRecord(eg->b, e->stream));
+    rc = e->tm_master.end(e, timed);
+    if (rc) return rc;
     e->last_master = true;
     e->master_ramp = false;  // the run that follows in this call continues at m_new
     e->master_rendered = true;
@@ -323,16 +307,7 @@ int jf_profile_read_master(jf_engine *e, double *master_ms) {
     return jf_guard([&]() -> int {
     DeviceGuard bind(e);
     if (!e || !master_ms) return JF_ERR_ARG;
-    JF_HIP(e, hipStreamSynchronize(e->stream));
-    double r = 0;
-    for (size_t i = 0; e->profiling >= 2 && i < e->ev_used && i < e->ev_master_on.size() && i < e->ev_master.size(); i++) {
-        if (!e->ev_master_on[i]) continue;
-        float ms = 0;
-        JF_HIP(e, hipEventElapsedTime(&ms, e->ev_master[i].a, e->ev_master[i].b));
-        r += ms;
-    }
-    *master_ms = r;
-    return JF_OK;
+    return e->tm_master.sum(e, master_ms);
     });
 }
 

@@ -2,7 +2,7 @@
 // engine, chosen per source or per bus.  jf_engine_add_hrtf_set / jf_engine_add_hrtf_sofa put a further set behind the ones
 // the table holds (the table is re-allocated: the pattern of ensure_interp_rows).  The setters (jf_source_set_hrtf,
 // jf_bus_set_hrtf) only write host state under the positions' mutex; a processing call latches it (sets_latch), run_blocks
-// applies it to the descriptors it has settled on (run_set_stage: desc_set_kernel, jf_sets.hip) and the call's end makes the
+// applies it to the descriptors it has settled on (run_set_stage: desc_set_kernel, jf_desc_edit.hip) and the call's end makes the
 // new sets the standing ones (sets_settle).  jf_debug_set_record is the rule for one record on the host -- the header the
 // kernel compiles (jf_set_rule.h).
 //
@@ -34,22 +34,16 @@ static void set_apply(jf_engine *e, int s, int set, int fade) {
     }
 }
 
-// The device copies of the call's sets, where they differ from what the device holds: asynchronous copies out of a pinned
-// staging, enqueued by sets_latch BEFORE anything of the call (gain_upload's scheme, jf_engine_gain.cpp: an otherwise
-// asynchronous jf_batch_run stays one).
+// The device copies of the call's sets, where they differ from what the device holds, out of the staging ring (StagedRing),
+// enqueued by sets_latch BEFORE anything of the call.
 static int sets_upload(jf_engine *e) {
     const size_t S = (size_t)e->S;
     const bool need_new = e->dev_set_new != e->run_s1;
     const bool need_prev = e->set_switch && e->dev_set_prev != e->run_s0;
     if (!need_new && !need_prev) return JF_OK;
-    // (each on its own: a call that failed part-way through this leaves nothing half-made for the next one to trust)
-    for (int i = 0; i < kGainStageSlots; i++)
-        if (!e->ev_s_copy[i]) JF_HIP(e, hipEventCreateWithFlags(&e->ev_s_copy[i], hipEventDisableTiming));
-    if (!e->h_s_stage) JF_HIP(e, e->h_s_stage.alloc(kGainStageSlots * 2 * S));
-    const int slot = e->s_stage_slot;
-    e->s_stage_slot = (slot + 1) % kGainStageSlots;
-    if (e->s_copy_pending[slot]) JF_HIP(e, hipEventSynchronize(e->ev_s_copy[slot]));
-    int *stage = e->h_s_stage + (size_t)slot * 2 * S;
+    int *stage = nullptr;
+    const int rc = e->s_ring.take(e, 2 * S, &stage);
+    if (rc) return rc;
     if (need_new) {
         memcpy(stage, e->run_s1.data(), sizeof(int) * S);
         e->dev_set_new.clear();  // (nothing, should the copy fail)
@@ -62,9 +56,7 @@ static int sets_upload(jf_engine *e) {
         JF_HIP(e, hipMemcpyAsync(e->d_set_prev, stage + S, sizeof(int) * S, hipMemcpyHostToDevice, e->stream));
         e->dev_set_prev = e->run_s0;
     }
-    JF_HIP(e, hipEventRecord(e->ev_s_copy[slot], e->stream));
-    e->s_copy_pending[slot] = true;
-    return JF_OK;
+    return e->s_ring.sent(e);
 }
 
 int sets_latch(jf_engine *e) {
@@ -94,21 +86,12 @@ int sets_latch(jf_engine *e) {
 // The sets of this run onto e->d_desc, the buffer the run has settled on.  Only the first run of a call sees the sets of the
 // block before it (d_set_prev), and only where some source changes; the device copies were enqueued by sets_latch.
 int run_set_stage(jf_engine *e, int K, int canon, bool timed) {
-    EventPair *eg = nullptr;
-    if (timed && e->profiling >= 2) {
-        while (e->ev_set.size() <= e->ev_used) {
-            EventPair q;
-            if (hipEventCreate(&q.a) != hipSuccess || hipEventCreate(&q.b) != hipSuccess) return fail(e, JF_ERR_DEVICE, "hipEventCreate failed");
-            e->ev_set.push_back(q);
-        }
-        e->ev_set_on.resize(e->ev_used + 1, 0);
-        e->ev_set_on[e->ev_used] = 1;
-        eg = &e->ev_set[e->ev_used];
-    }
-    if (eg) JF_HIP(e, hipEventRecord(eg->a, e->stream));
+    int rc = e->tm_set.begin(e, timed);
+    if (rc) return rc;
     JF_HIP(e, launch_desc_set(e->d_desc, e->set_switch ? e->d_set_prev.p : nullptr, e->d_set_new, e->S, K, e->rt.n_rows, canon,
                               e->stream));
-    if (eg) JF_HIP(e, hipEventRecord(eg->b, e->stream));
+    rc = e->tm_set.end(e, timed);
+    if (rc) return rc;
     e->last_set = true;
     e->set_switch = false;  // the run that follows in this call continues on the new sets
     e->set_rendered = true;
@@ -284,28 +267,8 @@ int jf_debug_read_hrtf_set(jf_engine *e, int set, float *out) {
 
 int jf_debug_set_record(int rows_new[4], float w_new[4], int rows_old[4], float w_old[4], int *n_new, int *n_old, int *flags,
                         int off0, int off1, int canon) {
-    if (!rows_new || !w_new || !rows_old || !w_old || !n_new || !n_old || !flags) return JF_ERR_ARG;
-    SetRecord d;
-    for (int t = 0; t < 4; t++) {
-        d.rows_new[t] = rows_new[t];
-        d.w_new[t] = w_new[t];
-        d.rows_old[t] = rows_old[t];
-        d.w_old[t] = w_old[t];
-    }
-    d.n_new = *n_new;
-    d.n_old = *n_old;
-    d.flags = *flags;
-    const bool changed = set_rule(d, off0, off1, canon);
-    for (int t = 0; t < 4; t++) {
-        rows_new[t] = d.rows_new[t];
-        w_new[t] = d.w_new[t];
-        rows_old[t] = d.rows_old[t];
-        w_old[t] = d.w_old[t];
-    }
-    *n_new = d.n_new;
-    *n_old = d.n_old;
-    *flags = d.flags;
-    return changed ? 1 : 0;
+    return debug_record_rule(rows_new, w_new, rows_old, w_old, n_new, n_old, flags,
+                             [&](DescRecord &d) { return set_rule(d, off0, off1, canon); });
 }
 
 int jf_debug_last_set_stage(const jf_engine *e) { return e ? (!e->last_rt && e->last_set ? 1 : 0) : JF_ERR_ARG; }
@@ -314,16 +277,7 @@ int jf_profile_read_sets(jf_engine *e, double *set_ms) {
     return jf_guard([&]() -> int {
     DeviceGuard bind(e);
     if (!e || !set_ms) return JF_ERR_ARG;
-    JF_HIP(e, hipStreamSynchronize(e->stream));
-    double r = 0;
-    for (size_t i = 0; e->profiling >= 2 && i < e->ev_used && i < e->ev_set_on.size() && i < e->ev_set.size(); i++) {
-        if (!e->ev_set_on[i]) continue;
-        float ms = 0;
-        JF_HIP(e, hipEventElapsedTime(&ms, e->ev_set[i].a, e->ev_set[i].b));
-        r += ms;
-    }
-    *set_ms = r;
-    return JF_OK;
+    return e->tm_set.sum(e, set_ms);
     });
 }
 

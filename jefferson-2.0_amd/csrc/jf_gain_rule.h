@@ -1,6 +1,6 @@
 // jf_gain_rule.h -- the PER-SOURCE GAIN rule (include/jefferson.h: "per-source gain"): what a source's gain
 // does to its work item's descriptor.  Compiled for BOTH sides in the manner of jf_ring_rule.h and jf_pose_rule.h: the kernel
-// (jf_gain.hip: desc_gain_kernel, behind prep_kernel in the batch pipeline) and the host (jf_debug_gain_record, which the CPU
+// (jf_desc_edit.hip: desc_gain_kernel, behind prep_kernel in the batch pipeline) and the host (jf_debug_gain_record, which the CPU
 // suite checks case by case) include this one file and get the same bits.  Self-contained: a plain C++ compiler can build it.
 //
 // Every filter set of the spatialiser is sum_t w_t H[row_t], and the kernels blend an item's old and new set by the
@@ -30,6 +30,8 @@
 // FD_BASIC records (one row, w_new[0] = 1) go through the same rule.
 #pragma once
 
+#include "jf_desc_record.h"
+
 #if defined(__HIPCC__) || defined(__HIP__)
 #define JF_GAIN_HD __host__ __device__ __forceinline__
 #else
@@ -43,13 +45,7 @@
 
 namespace jf {
 
-struct GainRecord {
-    int rows_new[4];
-    float w_new[4];
-    int rows_old[4];
-    float w_old[4];
-    int n_new, n_old, flags;
-};
+using GainRecord = DescRecord;
 
 // true: the record changed (rows_new never does)
 JF_GAIN_HD bool gain_rule(GainRecord &d, float g0, float g1, int canon) {

@@ -1,5 +1,5 @@
 // jf_set_rule.h -- the HRTF-SET rule (include/jefferson.h: "HRTF sets"): what a source's set does to its work
-// item's descriptor.  Compiled for BOTH sides in the manner of jf_gain_rule.h: the kernel (jf_sets.hip: desc_set_kernel, behind
+// item's descriptor.  Compiled for BOTH sides in the manner of jf_gain_rule.h: the kernel (jf_desc_edit.hip: desc_set_kernel, behind
 // prep_kernel and ahead of desc_gain_kernel in the batch pipeline) and the host (jf_debug_set_record, which the CPU suite checks
 // case by case) include this one file and get the same words.  Self-contained: a plain C++ compiler can build it.
 //
@@ -31,6 +31,8 @@
 // FD_BASIC records (one row, w_new[0] = 1) go through the same rule.
 #pragma once
 
+#include "jf_desc_record.h"
+
 #if defined(__HIPCC__) || defined(__HIP__)
 #define JF_SET_HD __host__ __device__ __forceinline__
 #else
@@ -46,13 +48,7 @@
 
 namespace jf {
 
-struct SetRecord {
-    int rows_new[4];
-    float w_new[4];  // read only
-    int rows_old[4];
-    float w_old[4];
-    int n_new /* read only */, n_old, flags;
-};
+using SetRecord = DescRecord;  // (w_new and n_new are read only)
 
 // true: the record changed.  Written as ONE path of selects over the four entries (the cases above, folded): on the device the
 // record then stays in registers.
