@@ -721,6 +721,63 @@ int jf_source_set_hrtf(jf_engine *e, int src, int set, int fade);
 int jf_source_hrtf(const jf_engine *e, int src);
 int jf_bus_set_hrtf(jf_engine *e, int bus, int set, int fade);
 
+/* ---- voice gates: input meters per source, gates that skip the silent ----------- */
+
+/*
+ * The reference renders every SoundSource in every block whether or not it has anything to say (the callback's loop over the
+ * sources, Audio.cu:98; their sum, Audio.cu:109-113; the window each of them slides on, GPUSoundSource.cu:481-513).  In a
+ * conference of 32 people one to three speak at a time.  Here a source can carry a GATE that opens on the level of its own
+ * input and closes when it falls silent; a block that is closed at both ends is skipped by the spatialiser (its window and
+ * play position slide on), and the engine can report who is talking.
+ *
+ * THE RULE (csrc/jf_gate_rule.h; float32 comparisons of values as stored, no arithmetic).  Per source: open, a linear peak
+ * (0: no gate, always heard); close, 0 <= close <= open; hold, whole blocks, 0 .. 1 048 576; and the state {is_open,
+ * hold_left}, closed with hold_left = 0 at first.  The LEVEL of block k is p = max |x| over the B samples the block appends to
+ * the source's INPUT -- pre-fader; the looped signal at the play position, a live source's samples of that block, a follower's
+ * root's level; an empty signal has level 0.  Per block, in this order:
+ *   1. p >= open                        is_open = 1, hold_left = hold
+ *   2. else is_open and p >= close      hold_left = hold
+ *   3. else is_open and hold_left > 0   hold_left -= 1
+ *   4. else                             is_open = 0
+ * gate[k] = is_open after the step; a source without a gate has gate[k] = 1 and its state is not touched.  The gain stage sees
+ * g_eff[k] = gate[k] ? g[k] : 0, where g[k] is the gain it would have applied (the standing gains, a staged jf_batch_set_gains
+ * trajectory, or 1), and g_eff[-1] = (open before the call ? g[-1] : 0).  By the gain rule as it stands: an OPENING gate is the
+ * reference's one-block crossfade from 0 (kernels.cu:132-137), a closing gate the same ramp to 0, an open gate multiplies by
+ * nothing -- with every gate open the output is the ungated engine's, bit for bit.  Room sends are pre-fader and not gated.
+ * THE RAMP ON OPENING IS ACCEPTED: the block whose level opens the gate fades in over its B samples.  The state lives on the
+ * device and every run continues from the one before: a stream gives the same bits however it is cut into calls, jf_batch_run
+ * included.
+ *
+ * jf_source_set_gate(e, src, open, close, hold_blocks) / jf_source_gate (reads them back; 0, 0, 0 before anything was set);
+ *   jf_sources_set_gate gives every source the same gate.  Setting a gate does not touch its state: a gate set on a playing
+ *   source is closed until a level opens it, and a gate taken away (open = 0) while closed lets the source in at once.
+ * jf_engine_set_input_meters(e, on): the input meters of every rendered call are kept.  jf_source_levels(e, n_blocks, out): of
+ *   the LAST RENDERED CALL, out[n_sources][n_blocks][3] = {peak = p, sumsq = the float32 sum of x^2 over the block, open =
+ *   gate[k] as 0 or 1}; a follower reports its root's level and its own gate.  n_blocks is 1 for the per-block calls, else the
+ *   call's.  After a jf_batch_run it brings them over from the device itself (it waits for the engine's stream).  JF_ERR_STATE
+ *   if input meters are off or nothing has been rendered with them; JF_ERR_ARG for another count.
+ * The setters are setters like jf_source_set_cartesian: callable from another thread, latched by the next processing call that
+ * is not paused.  Refusals change nothing: JF_ERR_ARG for a bad source index, a negative or non-finite threshold, a threshold
+ * above 2^24 (144 dB over full scale: no input reaches it, and a call with garbage arguments must not silence every source for
+ * good -- the thresholds outlive jf_source_set_signal), close > open or hold outside its range; JF_ERR_STATE for a gate or input meters while a jf_reverb_set_ir response is set, and for
+ * jf_reverb_set_ir while a source has a gate or input meters are on (the wet tail outlives the dry level).  jf_source_reset,
+ * jf_source_set_signal and jf_source_set_live close the source's gate (hold_left = 0); the thresholds stay.  Paused calls
+ * latch nothing and leave the state alone.  A call that fails after some of its runs leaves the state where those runs left it.
+ *
+ * COST.  An engine is ACTIVE while some source has open > 0 or input meters are on.  An engine that is not active allocates
+ * nothing for gates, launches exactly what it launched and renders the same bits.  While active, two small kernels run ahead
+ * of desc_gain_kernel in every batch run, whole-degree positions are weighted per block instead of read as
+ * pre-interpolated rows (as with a gain) and the per-block calls go through the batch pipeline with one block.
+ *
+ * Not offered: look-ahead or pre-roll; attack or release times other than one block; gates inside the one-launch real-time
+ * kernel; jefferson_group.h, jf_render and jf_ctest have no option for gates.
+ */
+int jf_source_set_gate(jf_engine *e, int src, float open, float close, int hold_blocks);
+int jf_source_gate(const jf_engine *e, int src, float *open, float *close, int *hold_blocks);
+int jf_sources_set_gate(jf_engine *e, float open, float close, int hold_blocks);
+int jf_engine_set_input_meters(jf_engine *e, int on);
+int jf_source_levels(jf_engine *e, int n_blocks, float *out /* [n_sources][n_blocks][3] */);
+
 /* ---- listener poses: head position and orientation per output bus --------------- */
 
 /*

@@ -294,6 +294,16 @@ int jf_debug_last_set_stage(const jf_engine *e);
  * prep_kernel); 0 while every source was on set 0. */
 int jf_profile_read_sets(jf_engine *e, double *set_ms);
 
+/* Voice gates (include/jefferson.h): the rule gate_scan_kernel applies to ONE source, on the host -- the header
+ * the kernels compile (csrc/jf_gate_rule.h), so the CPU suite checks it against a NumPy model.  peaks are the levels of n
+ * consecutive blocks, state_io = {is_open, hold_left} before the first of them and, on return, after the last; gate_out[k] is
+ * the gate of block k.  open == 0: every gate is 1 and the state is not touched.  Pure host code: no engine, no GPU.
+ * JF_ERR_ARG for a NULL pointer, n < 0 or parameters jf_source_set_gate would refuse. */
+int jf_debug_gate_scan(const float *peaks, int n, float open, float close, int hold, int state_io[2], int *gate_out);
+/* ms in the gate stage (input_level_kernel, gate_scan_kernel) since jf_profile_enable(e, 2), the event pair's own ~7 us per
+ * run included; desc_gain_kernel behind it is in jf_profile_read_gain's figure.  0 while no gate or input meter was active. */
+int jf_profile_read_gate(jf_engine *e, double *gate_ms);
+
 /* ---- libjefferson_group.so (jefferson_group.h): test support ------------------------------------------------------------ */
 
 typedef struct jf_group jf_group;

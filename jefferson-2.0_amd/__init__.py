@@ -136,6 +136,13 @@ _SIGS = {
     "jf_bus_meters": (C.c_int, [C.c_void_p, C.c_int, _f]),
     "jf_debug_master_block": (C.c_int, [_f, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, _f, _f, _f]),
     "jf_profile_read_master": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "jf_source_set_gate": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int]),
+    "jf_source_gate": (C.c_int, [C.c_void_p, C.c_int, _f, _f, _i]),
+    "jf_sources_set_gate": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_int]),
+    "jf_engine_set_input_meters": (C.c_int, [C.c_void_p, C.c_int]),
+    "jf_source_levels": (C.c_int, [C.c_void_p, C.c_int, _f]),
+    "jf_debug_gate_scan": (C.c_int, [_f, C.c_int, C.c_float, C.c_float, C.c_int, _i, _i]),
+    "jf_profile_read_gate": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "jf_engine_add_hrtf_set": (C.c_int, [C.c_void_p, _f, C.c_int]),
     "jf_engine_add_hrtf_sofa": (C.c_int, [C.c_void_p, C.c_char_p, C.c_float]),
     "jf_num_hrtf_sets": (C.c_int, [C.c_void_p]),
@@ -424,6 +431,17 @@ def master_block(x, m_prev=1.0, m_new=1.0, ceiling=0.0, release=1.0, g_prev=1.0)
     if rc:
         raise JfError(rc, "master_block")
     return out, m, g[0]
+
+
+def gate_scan(peaks, open, close, hold, state=(0, 0)):
+    """jf_debug_gate_scan (host logic only): the voice-gate rule over a sequence of block levels ->
+    (gates [n] int32, the state (is_open, hold_left) after the sequence)"""
+    peaks = np.ascontiguousarray(peaks, np.float32).ravel()
+    st, out = np.array(state, np.int32), np.zeros(max(len(peaks), 1), np.int32)
+    rc = lib().jf_debug_gate_scan(_fp(peaks), len(peaks), open, close, int(hold), _ip(st), _ip(out))
+    if rc:
+        raise JfError(rc, "gate_scan")
+    return out[:len(peaks)], (int(st[0]), int(st[1]))
 
 
 def reverb_rms_gain(signal, ir):
@@ -896,6 +914,41 @@ class Engine:
         """ms in the master stage's kernels since profile_enable(2)"""
         r = C.c_double()
         self._chk(lib().jf_profile_read_master(self.h, C.byref(r)))
+        return r.value
+
+    # ---- voice gates and input meters (include/jefferson.h: "voice gates") ----
+    def set_gate(self, s, open, close=None, hold_blocks=0):
+        """source s's gate: opens at input peak >= `open` (0: no gate), stays open while >= `close` (default: open) and for
+        `hold_blocks` blocks after (jf_source_set_gate)"""
+        close = open if close is None else close
+        self._chk(lib().jf_source_set_gate(self.h, int(s), float(open), float(close), int(hold_blocks)))
+
+    def gate(self, s):
+        """(open, close, hold_blocks)"""
+        o, c, h = np.zeros(1, np.float32), np.zeros(1, np.float32), np.zeros(1, np.int32)
+        self._chk(lib().jf_source_gate(self.h, int(s), _fp(o), _fp(c), _ip(h)))
+        return float(o[0]), float(c[0]), int(h[0])
+
+    def set_gates(self, open, close=None, hold_blocks=0):
+        """every source the same gate (jf_sources_set_gate)"""
+        close = open if close is None else close
+        self._chk(lib().jf_sources_set_gate(self.h, float(open), float(close), int(hold_blocks)))
+
+    def set_input_meters(self, on=True):
+        self._chk(lib().jf_engine_set_input_meters(self.h, int(bool(on))))
+
+    def levels(self, n_blocks=1):
+        """the last rendered call's input meters, [S][n_blocks][3] = {peak, sumsq, open} (jf_source_levels)"""
+        out = np.zeros((self.S, int(n_blocks), 3), np.float32)
+        self._chk(lib().jf_source_levels(self.h, int(n_blocks), _fp(out)))
+        return out
+
+    gate_scan = staticmethod(gate_scan)
+
+    def profile_read_gate(self):
+        """ms in the gate stage's two kernels since profile_enable(2)"""
+        r = C.c_double()
+        self._chk(lib().jf_profile_read_gate(self.h, C.byref(r)))
         return r.value
 
     def room_wet(self, n_blocks):

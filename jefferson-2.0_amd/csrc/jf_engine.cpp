@@ -89,7 +89,7 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
         ep = next_events(e, e->ev_prep);
         em = next_events(e, e->ev_mix);
         if (!ep || !em) return fail(e, JF_ERR_DEVICE, "hipEventCreate failed");
-        for (StageTimer *t : {&e->tm_spec, &e->tm_set, &e->tm_gain, &e->tm_master}) t->arm(e->ev_used);  // (the stage that runs says otherwise)
+        for (StageTimer *t : {&e->tm_spec, &e->tm_set, &e->tm_gain, &e->tm_master, &e->tm_gate}) t->arm(e->ev_used);  // (the stage that runs says otherwise)
     }
     const long long n_items = (long long)K * e->S;
     int G = 1;
@@ -102,7 +102,7 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
     bool rows = canon && e->interp_avail && e->interp_use != 0;
     // ... and never while a gain is active (jf_engine_gain.cpp): a whole row is read without its weight.  Descriptors prepared
     // ahead WITH rows then differ in `mode` below and are prepared again
-    if (e->gain_on) rows = false;
+    if (e->gain_on || e->gate_on) rows = false;  // (a gate is a gain the engine sets itself: jf_engine_gate.cpp)
     if (rows && e->interp_use == 2 && first_block >= 0 && (size_t)(first_block + K) < e->traj_moved.size()) {
         const double moved = (double)(e->traj_moved[first_block + K] - e->traj_moved[first_block]) / (double)n_items;
         rows = moved <= kInterpMovedMax;
@@ -137,8 +137,13 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
     }
     // per-source gain: the run's descriptors are settled (prepared just now, or ahead and swapped in: plain ones either way) --
     // desc_gain_kernel rewrites them once, the kernels below read them as they read any
-    e->last_gain = false;
-    if (e->gain_on) {
+    // Voice gates: while some source has a gate or input meters are on, the gate stage takes the gain stage's place -- it forms
+    // g_eff[k][s] = gate ? g[k][s] : 0 from the inputs' levels and the same gains, and desc_gain_kernel applies that
+    e->last_gain = e->last_gate = false;
+    if (e->gate_on) {
+        const int rc = run_gate_stage(e, p, K, canon, timed);
+        if (rc) return rc;
+    } else if (e->gain_on) {
         const int rc = run_gain_stage(e, K, canon, timed);
         if (rc) return rc;
     }
@@ -294,7 +299,7 @@ int reset_sources(jf_engine *e, int src) {
             JF_HIP(e, hipMemsetAsync(e->d_rv_fut + s0 * e->rv_Fn * B1, 0, sizeof(float) * e->rv_Fn * B1 * ns, e->stream));
         }
     }
-    return JF_OK;
+    return gate_close_source(e, src);  // a source that starts over has its gate closed; the thresholds stay
 }
 
 // ---- live input (jf_engine::live) -----------------------------------------------------------------------
@@ -374,7 +379,7 @@ void destroy_engine(jf_engine *e) {
     DeviceGuard bind(e);  // (outlives the delete: the buffers are freed on the engine's device)
     if (e->rv_side) (void)hipStreamSynchronize(e->rv_side);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
-    for (auto *pool : {&e->ev_prep, &e->ev_fused, &e->ev_mix, &e->ev_reverb, &e->ev_pose, &e->tm_spec.ev, &e->tm_gain.ev, &e->tm_master.ev, &e->tm_set.ev})
+    for (auto *pool : {&e->ev_prep, &e->ev_fused, &e->ev_mix, &e->ev_reverb, &e->ev_pose, &e->tm_spec.ev, &e->tm_gain.ev, &e->tm_master.ev, &e->tm_set.ev, &e->tm_gate.ev})
         for (auto &p : *pool) {
             (void)hipEventDestroy(p.a);
             (void)hipEventDestroy(p.b);
@@ -856,6 +861,10 @@ static int swap_signal(jf_engine *e, int src, DevBuf<float> d_new, int n_dev, bo
             JF_HIP(e, h2d(e, e->d_rv_count[e->cur] + s, &zero, sizeof(int)));
         else
             JF_HIP(e, h2d(e, &e->d_state[e->cur][s].count, &zero, sizeof(int)));
+    }
+    {
+        const int rc = gate_close_source(e, src);  // a new input is a new start: the source's gate is closed, its thresholds stay
+        if (rc) return rc;
     }
     return live_refresh(e);  // (the real-time kernel's records follow)
 }
@@ -1358,6 +1367,7 @@ static int submit_block(jf_engine *e, const float *in, bool interleaved) {
         JF_HIP(e, hipMemsetAsync(e->d_mix, 0, sizeof(float) * 2 * e->B * e->n_buses, e->stream));
         e->own_mix_blocks = 0;  // (d_mix no longer holds the last jf_batch_run's blocks)
         e->meters_stage_blocks = 0;  // (a paused call leaves the masters and the meters alone)
+        e->levels_stage_blocks = 0;  // (... and the gates and the input meters)
     } else {
         snapshot_positions(e, e->h_pos_pinned);
         CallLatches call(e);  // the gains, HRTF sets and bus masters the setters hold (nothing to settle where none is active: the one-launch path below)
@@ -1366,7 +1376,8 @@ static int submit_block(jf_engine *e, const float *in, bool interleaved) {
             if (rc) return rc;
         }
         e->meters_stage_blocks = 0;
-        if (e->S <= e->rt_max_sources && !e->profiling && e->N == kN && e->n_buses == 1 && e->room.P == 0 && !e->gain_on && !e->master_on && !e->sets_on) {  // (PAD_LEN 2048, buses, a room, an active gain or master, a source on another HRTF set: the batch path with K = 1)
+        e->levels_stage_blocks = 0;
+        if (e->S <= e->rt_max_sources && !e->profiling && e->N == kN && e->n_buses == 1 && e->room.P == 0 && !e->gain_on && !e->master_on && !e->sets_on && !e->gate_on) {  // (PAD_LEN 2048, buses, a room, an active gain, master or gate, a source on another HRTF set: the batch path with K = 1)
             // few sources: ONE launch does descriptors, spatialisation and mix, reading the positions
             // from and writing the stereo block to pinned host memory -- no copies, one sync
             const int p = e->cur;
@@ -1441,6 +1452,11 @@ static int submit_block(jf_engine *e, const float *in, bool interleaved) {
             if (rc) return rc;
             e->meters_stage_blocks = 1;
         }
+        if (e->gate_on && e->gate_meters) {  // ... and so do its input meters
+            rc = gate_levels_copy(e, 1);
+            if (rc) return rc;
+            e->levels_stage_blocks = 1;
+        }
     }
     JF_HIP(e, hipMemcpyAsync(e->h_out_pinned, e->d_mix, sizeof(float) * 2 * e->B * e->n_buses, hipMemcpyDeviceToHost, e->stream));
     e->rt_wgs = 0;
@@ -1489,6 +1505,10 @@ int jf_collect_block(jf_engine *e, float *out) {
     if (e->meters_stage_blocks > 0) {
         master_meters_land(e, 1, 0, 1);
         e->meters_stage_blocks = 0;
+    }
+    if (e->levels_stage_blocks > 0) {
+        gate_levels_land(e, 1, 0, 1);
+        e->levels_stage_blocks = 0;
     }
     const int n_out = 2 * e->B * e->n_buses;  // [n_buses][2B] (the real-time kernel: one bus)
     memcpy(out, e->h_out_pinned, sizeof(float) * n_out);
@@ -1839,6 +1859,11 @@ int jf_batch_run(jf_engine *e, int first_block, int n_blocks, float *d_out_mix) 
         std::lock_guard<std::mutex> lk(e->pos_mu);
         e->meters_blocks = 0;
     }
+    if (rc == JF_OK && e->gate_on && e->gate_meters) {  // ... and so do its input meters (jf_source_levels)
+        e->levels_dev_blocks = n_blocks;
+        std::lock_guard<std::mutex> lk(e->pos_mu);
+        e->levels_blocks = 0;
+    }
     return rc;
     });
 }
@@ -1961,6 +1986,11 @@ static int process_batch(jf_engine *e, int n_blocks, const float *in, const floa
             rc = master_meters_copy(e, k);
             if (rc) return rc;
         }
+        const bool levelled = e->gate_on && e->gate_meters;
+        if (levelled) {
+            rc = gate_levels_copy(e, k);
+            if (rc) return rc;
+        }
         if (!positions && b0 + k == n_blocks) {
             // while the last window runs: where the sources will stand afterwards (what the pose kernel wrote for the last
             // block, bit for bit)
@@ -1970,6 +2000,7 @@ static int process_batch(jf_engine *e, int n_blocks, const float *in, const floa
         JF_HIP(e, hipStreamSynchronize(e->stream));
         if (device_fault(e)) return fail(e, JF_ERR_DEVICE, kHandOffMsg);
         if (metered) master_meters_land(e, k, b0, n_blocks);
+        if (levelled) gate_levels_land(e, k, b0, n_blocks);
     }
     call.settle(n_blocks);
     // n_blocks callbacks have run: the sources stand where the last of them read them

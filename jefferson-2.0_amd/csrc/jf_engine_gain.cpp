@@ -140,27 +140,38 @@ int gain_latch(jf_engine *e, int traj_blocks) {
 // The gains of this run onto e->d_desc, the buffer the run has settled on.  g[-1] of the run: the trajectory's block before
 // its first one, else d_g_prev -- or d_g_new itself where the two are equal (every run of a call but the first).  The
 // device copies were enqueued by gain_latch.
-int run_gain_stage(jf_engine *e, int K, int canon, bool timed) {
+void gain_run_gains(const jf_engine *e, const float **g_prev, const float **g_new, const float **g_traj) {
+    *g_prev = *g_new = *g_traj = nullptr;
+    if (!e->gain_on) return;  // (the gate stage asks whether or not a gain is active: every gain is 1)
     const size_t S = (size_t)e->S;
-    const bool traj = e->gain_traj_first >= 0;
-    const float *g_new = e->d_g_new, *g_prev = e->d_g_new, *g_traj = nullptr;
-    if (traj) {
-        g_traj = e->d_g_traj + (size_t)e->gain_traj_first * S;
-        g_prev = e->gain_traj_first > 0 ? g_traj - S : e->d_g_prev.p;
+    *g_new = *g_prev = e->d_g_new;
+    if (e->gain_traj_first >= 0) {
+        *g_traj = e->d_g_traj + (size_t)e->gain_traj_first * S;
+        *g_prev = e->gain_traj_first > 0 ? *g_traj - S : e->d_g_prev.p;
     } else if (e->gain_ramp) {
-        g_prev = e->d_g_prev;
+        *g_prev = e->d_g_prev;
     }
+}
+
+// the run that follows in this call continues from this one's last block
+void gain_run_advance(jf_engine *e, int K) {
+    if (!e->gain_on) return;
+    if (e->gain_traj_first >= 0)
+        e->gain_traj_first += K;
+    else
+        e->gain_ramp = false;
+}
+
+int run_gain_stage(jf_engine *e, int K, int canon, bool timed) {
+    const float *g_new, *g_prev, *g_traj;
+    gain_run_gains(e, &g_prev, &g_new, &g_traj);
     int rc = e->tm_gain.begin(e, timed);
     if (rc) return rc;
     JF_HIP(e, launch_desc_gain(e->d_desc, g_prev, g_new, g_traj, e->S, K, canon, e->stream));
     rc = e->tm_gain.end(e, timed);
     if (rc) return rc;
     e->last_gain = true;
-    // the run that follows in this call continues from this one's last block
-    if (traj)
-        e->gain_traj_first += K;
-    else
-        e->gain_ramp = false;
+    gain_run_advance(e, K);
     return JF_OK;
 }
 

@@ -15,9 +15,12 @@
 //   jf_engine_sets.cpp    HRTF sets: further sets behind the engine's own in the table, the sources' sets, what a processing call
 //                         latches of them, the stage that moves a run's descriptors into them (run_set_stage, jf_desc_edit.hip)
 //                         and jf_engine_add_hrtf_set / jf_source_set_hrtf
+//   jf_engine_gate.cpp    voice gates and input meters: the sources' thresholds, what a processing call latches of them, the stage
+//                         that writes a run's gain trajectory from the inputs' levels (run_gate_stage, jf_gate.hip) and
+//                         jf_source_set_gate / jf_source_levels
 //   jf_engine_debug.cpp   every entry point of include/jefferson_debug.h (taps, timing hooks, tuning switches, accessors)
-// What the three latched controls (gain, masters, sets) share is here once: StagedRing (their asynchronous uploads), StageTimer
-// (the event pairs of a stage that only some runs launch), CallLatches (a processing call's latch and settlement of all three).
+// What the four latched controls (gain, masters, sets, gates) share is here once: StagedRing (their asynchronous uploads), StageTimer
+// (the event pairs of a stage that only some runs launch), CallLatches (a processing call's latch and settlement of all four).
 // Not part of any interface: nothing outside csrc/ includes this file.
 #ifndef JF_ENGINE_INTERNAL_H
 #define JF_ENGINE_INTERNAL_H
@@ -42,6 +45,7 @@
 #include "../../include/jefferson_debug.h"
 #include "jf_device.h"
 #include "jf_gain_rule.h"
+#include "jf_gate_rule.h"
 #include "jf_host.h"
 #include "jf_pose_rule.h"
 #include "jf_room.h"
@@ -105,6 +109,12 @@ hipError_t launch_desc_set(ItemDesc *d_desc, const int *d_set_prev, const int *d
 // bus masters (jf_master.hip): master gain, limiter and meters on a run's finished mix, in place
 hipError_t launch_master(float *d_mix, const float *d_par, float *d_state, float *d_t, float *d_gg, float *d_meters, int B, int K,
                          int n_buses, int ramp, hipStream_t st);
+// voice gates and input meters (jf_gate.hip): the inputs' levels per (block, source), then the gates and the run's effective gains
+hipError_t launch_input_level(const SrcSignal *d_sigs, const SrcState *d_state, const int *d_root, float *d_peak, float *d_sumsq,
+                              int S, int K, int B, hipStream_t st);
+hipError_t launch_gate_scan(const GatePar *d_par, GateState *d_state, const int *d_root, float *d_peak, float *d_sumsq,
+                            const float *d_g_prev, const float *d_g_new, const float *d_g_traj, float *d_g_eff, float *d_g_eff_prev,
+                            float *d_gate, int S, int K, hipStream_t st);
 }  // namespace jf
 
 using namespace jf;
@@ -512,6 +522,34 @@ struct jf_engine : ReverbSetup {
     bool last_set = false;                    // the last run launched desc_set_kernel (jf_debug_last_kernels)
     StageTimer tm_set;                        // profiling 2: around desc_set_kernel (jf_profile_read_sets)
 
+    // VOICE GATES AND INPUT METERS (jf_source_set_gate, jf_engine_set_input_meters).  Per source a gate (open,
+    // close, hold: jf_gate_rule.h) whose state {is_open, hold_left} depends on the audio and lives on the device ONLY (d_gt_state:
+    // no host mirror).  While the engine is ACTIVE -- some source has open > 0 or input meters are on -- run_blocks runs the gate
+    // stage in place of the plain gain stage: input_level_kernel and gate_scan_kernel (jf_gate.hip) write g_eff[K][S] and
+    // desc_gain_kernel applies it.  The host state is under pos_mu like `pos` and empty until first use; an engine that is not
+    // active allocates nothing below and launches nothing (gate_latch).
+    std::vector<GatePar> gt_par;              // [S] (empty: no gate was ever set, every open 0)
+    bool levels_want = false;                 // jf_engine_set_input_meters
+    std::vector<float> levels_last;           // [S][levels_blocks][3] the last rendered call's input meters on the host
+    int levels_blocks = 0;                    // (0: none)
+    // what the processing call in hand latched (its thread's alone)
+    bool gate_on = false;                     // the call is active
+    bool gate_meters = false;                 // ... with input meters
+    std::vector<GatePar> run_gpar;            // [S] the call's parameters
+    int levels_dev_blocks = 0;                // blocks whose meters the last jf_batch_run left on the device, not yet fetched (0: none)
+    int levels_stage_blocks = 0;              // blocks whose meters a submitted block's copy brings to h_levels (jf_collect_block)
+    DevBuf<GatePar> d_gt_par;                 // [S]
+    DevBuf<GateState> d_gt_state;             // [S]
+    DevBuf<int> d_gt_root;                    // [S] the source whose input s plays
+    DevBuf<float> d_gt_lv;                    // [3][maxK][S]: peak, sumsq, gate of a run
+    DevBuf<float> d_gt_geff;                  // [maxK + 1][S]: g_eff of a run, then g_eff_prev
+    std::vector<GatePar> dev_gt_par;          // what d_gt_par holds (empty: nothing yet)
+    std::vector<int> dev_gt_root;             // what d_gt_root holds (empty: nothing yet)
+    StagedRing<int> gt_ring;                  // slots of [5][S] words: the asynchronous copies to d_gt_par and d_gt_root
+    PinnedBuf<float> h_levels;                // [3][maxK][S] where a run's meters land on the host
+    bool last_gate = false;                   // the last run launched the stage (jf_debug_last_kernels)
+    StageTimer tm_gate;                       // profiling 2: around the two kernels (jf_profile_read_gate)
+
     PinnedBuf<float> h_pos_pinned;  // [S][5]   pinned + mapped: the real-time kernel reads it in place
     PinnedBuf<float> h_out_pinned;  // [kRtMaxWgs][2B] pinned + mapped: ... and writes its workgroups' stereo blocks in place
     int rt_wgs = 0;                 // partial blocks the block in flight left there (0: one finished block)
@@ -806,12 +844,30 @@ JF_INTERNAL void master_set_buses(jf_engine *e, int n_buses);  // under pos_mu: 
 JF_INTERNAL int sets_latch(jf_engine *e);
 JF_INTERNAL int run_set_stage(jf_engine *e, int K, int canon, bool timed);
 JF_INTERNAL void sets_settle(jf_engine *e);
-// A processing call between its latches and its end.  latch: the gains, the sets, the masters, in that order, up to the first
-// that fails.  On every way out, of what was latched: the masters and the sets are settled, then the gains -- as the call
+// voice gates and input meters (jf_engine_gate.cpp).  gate_latch: at the start of a processing call that is not paused, behind
+// the other three -- what the setters hold becomes the call's (e->gate_on, gate_meters, run_gpar), the device copies that differ
+// are enqueued.  run_gate_stage: from run_blocks IN PLACE OF run_gain_stage while e->gate_on (it reads the gains the call latched
+// through gain_run_gains and moves them on as run_gain_stage does).  gate_settle: when the call is over, however it ends.  The
+// state is the device's alone: nothing to give back.  gate_close_source: a reset or a new signal closes the source's gate (src <
+// 0: every one) through the engine's stream.  gate_levels_*: as the masters' meters.  gate_wanted: some source has a gate or
+// input meters are on (jf_reverb_set_ir refuses then).
+JF_INTERNAL int gate_latch(jf_engine *e);
+JF_INTERNAL int run_gate_stage(jf_engine *e, int p, int K, int canon, bool timed);
+JF_INTERNAL void gate_settle(jf_engine *e);
+JF_INTERNAL int gate_close_source(jf_engine *e, int src);
+JF_INTERNAL int gate_levels_copy(jf_engine *e, int K);
+JF_INTERNAL void gate_levels_land(jf_engine *e, int K, int b0, int n_blocks);
+JF_INTERNAL bool gate_wanted(jf_engine *e);
+// the three pointers run_gain_stage hands desc_gain_kernel for the next run of K blocks (all null unless e->gain_on), and the
+// step to the run after it (jf_engine_gain.cpp)
+JF_INTERNAL void gain_run_gains(const jf_engine *e, const float **g_prev, const float **g_new, const float **g_traj);
+JF_INTERNAL void gain_run_advance(jf_engine *e, int K);
+// A processing call between its latches and its end.  latch: the gains, the sets, the masters, the gates, in that order, up to the
+// first that fails.  On every way out, of what was latched: the gates, the masters and the sets are settled, then the gains -- as the call
 // settled them (settle: it succeeded), else as far as its blocks were launched (gain_abort, `rendered`).
 struct CallLatches {
     jf_engine *e;
-    int latched = 0;   // of gain, sets, masters
+    int latched = 0;   // of gain, sets, masters, gates
     int rendered = 0;  // blocks of the call launched so far
     bool settled = false;
     explicit CallLatches(jf_engine *e_) : e(e_) {}
@@ -819,7 +875,8 @@ struct CallLatches {
         int rc = gain_latch(e, traj_blocks);
         if (rc == JF_OK) latched = 1, rc = sets_latch(e);
         if (rc == JF_OK) latched = 2, rc = master_latch(e);
-        if (rc == JF_OK) latched = 3;
+        if (rc == JF_OK) latched = 3, rc = gate_latch(e);
+        if (rc == JF_OK) latched = 4;
         return rc;
     }
     void settle(int traj_blocks = -1) {
@@ -827,6 +884,7 @@ struct CallLatches {
         settled = true;
     }
     ~CallLatches() {
+        if (latched >= 4) gate_settle(e);
         if (latched >= 3) master_settle(e);
         if (latched >= 2) sets_settle(e);
         if (latched >= 1 && !settled) gain_abort(e, rendered);
