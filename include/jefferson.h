@@ -778,6 +778,71 @@ int jf_sources_set_gate(jf_engine *e, float open, float close, int hold_blocks);
 int jf_engine_set_input_meters(jf_engine *e, int on);
 int jf_source_levels(jf_engine *e, int n_blocks, float *out /* [n_sources][n_blocks][3] */);
 
+/* ---- voice limits: the N loudest talkers per bus, chosen on the GPU -------------- */
+
+/*
+ * The reference's callback loops over every SoundSource (Audio.cu:98), adds them all (Audio.cu:109-110) and reports clipping
+ * afterwards (Audio.cu:111-113): what a bus costs, and how intelligible it is, follows whoever has a microphone open.  A
+ * conference mixer renders the N loudest talkers per listener -- three is the usual figure -- and drops the rest.  Here every
+ * output bus can carry a VOICE LIMIT: in every block at most max_voices of the bus's sources are heard, the loudest by an
+ * envelope of their input level; the others are turned down by the gain stage as it stands.
+ *
+ * THE RULE (csrc/jf_voice_rule.h; one float32 product and float32 comparisons of values as stored).  Per bus b: max_voices N_b
+ * (0: no limit, the default; 0 .. 65 536) and release rho_b (0 <= rho < 1, default 0).  Per source: a priority 0 .. 255 (default
+ * 0; JF_VOICE_ALWAYS = 255: always heard, takes no place) and, on the device only, the state {env_prev, initially 0;
+ * heard_prev, initially 1: before a limit existed everybody was heard}.
+ *   Envelope.  p[k] is the level the voice gates measure: the peak of what block k appends to the source's input (a follower
+ *   reads its root's).  With b the source's bus in this run:  d = fl32(env[k - 1] * rho_b);  env[k] = p >= d ? p : d;  below
+ *   2^-60 it is stored as 0, so it is never a denormal.  rho = 0: the block's own peak.  The envelope of EVERY source advances
+ *   in every run of an active engine, whatever its bus.
+ *   Candidates.  Source s is a candidate in block k if g_eff[k][s] != 0 -- the gain the gate stage hands on: a closed gate, a
+ *   mute or a zero gain is no candidate -- and its priority is below 255.
+ *   Ranking of one bus's candidates: priority, higher first; then env[k], higher first; then the source index, lower first.
+ *   rank = the candidates on the bus that come before the source.
+ *   keep[k][s] = 1 on a bus with N_b = 0; 1 for an ALWAYS source; candidate && rank < N_b on a limited bus.
+ *   The gain stage sees g_out[k][s] = keep[k][s] ? g_eff[k][s] : 0 and g_out[-1][s] = (N_b == 0 || ALWAYS || heard_prev[s]) ?
+ *   g_eff[-1][s] : 0; after the run heard_prev := keep of its last block, env_prev := env of that block.  With every keep at 1
+ *   the output is the unlimited engine's, bit for bit.
+ * CONSEQUENCES.  Raising N, or a louder talker, ramps the new winner in from 0 over one block (the reference's crossfade,
+ * kernels.cu:132-137): the gates' "the ramp on opening is accepted" applies.  A loser ramps out over one block; a block unheard
+ * at both ends is skipped by the spatialiser (its window and play position slide on).  Taking a limit away (N = 0) lets
+ * everybody in at once, as taking a gate away does.  Room sends are pre-fader and are not limited.  A tie is only possible
+ * between sources that play one input, or by coincidence of peaks: the lower index wins it, the same way every block.  The
+ * state lives on the device and every run continues from the one before: a stream gives the same bits however it is cut into
+ * calls, jf_batch_run included (calls longer than max_batch_blocks are several runs of one stream).
+ *
+ * jf_bus_set_voices(e, bus, max_voices, release, fade) / jf_bus_voices (reads them back; 0 and 0 before anything was set).
+ *   fade != 0 leaves the state alone: sources that were heard ramp out.  With fade == 0 the first run that latches the setting
+ *   takes heard_prev as 0 for every source of that bus that is not ALWAYS: losers are silent from the first sample, winners ramp
+ *   in -- for a bus that has not started, so that the losers do not blip in its first block.  The flag is consumed by that run.
+ * jf_source_set_priority(e, src, priority) / jf_source_priority (JF_ERR_ARG, negative, for a bad index).
+ * jf_source_heard(e, n_blocks, out): of the LAST RENDERED CALL, out[n_sources][n_blocks][2] = {env[k], keep[k] as 0 or 1}.  Kept
+ *   while jf_engine_set_input_meters is on and some bus has a limit; it travels like jf_source_levels, a jf_batch_run's results
+ *   included.  JF_ERR_STATE if input meters are off, no bus is limited or nothing has been rendered so; JF_ERR_ARG for another
+ *   count.
+ * The setters are setters like jf_source_set_cartesian: callable from another thread, latched by the next processing call that
+ * is not paused.  Refusals change nothing: JF_ERR_ARG for a bad index, max_voices outside 0 .. 65 536, a release outside [0, 1)
+ * or not finite, a priority outside 0 .. 255; JF_ERR_STATE for a limit while a jf_reverb_set_ir response is set, and for
+ * jf_reverb_set_ir while a bus has a limit.  jf_source_reset, jf_source_set_signal and jf_source_set_live take the source's
+ * envelope back to 0 and leave heard_prev alone.  jf_source_set_bus and jf_engine_set_buses follow through: the buses that
+ * remain keep their limits, new ones have none.  Paused calls latch nothing and advance nothing.  A call that fails after some
+ * of its runs leaves the state where those runs left it.
+ *
+ * COST.  An engine is ACTIVE for voices while some bus has N > 0; it then counts as active for the voice gates (above) whether
+ * or not a source has a gate, and two more small kernels run between gate_scan_kernel and desc_gain_kernel.
+ * An engine whose buses all have N = 0 allocates nothing for voices, launches exactly what it launched and renders the same
+ * bits.
+ *
+ * Not offered: hysteresis beyond the envelope; voices inside the one-launch real-time kernel; jefferson_group.h, jf_render and
+ * jf_ctest have no option for voices.
+ */
+#define JF_VOICE_ALWAYS 255
+int jf_bus_set_voices(jf_engine *e, int bus, int max_voices, float release, int fade);
+int jf_bus_voices(const jf_engine *e, int bus, int *max_voices, float *release);
+int jf_source_set_priority(jf_engine *e, int src, int priority);
+int jf_source_priority(const jf_engine *e, int src);
+int jf_source_heard(jf_engine *e, int n_blocks, float *out /* [n_sources][n_blocks][2] = {env, keep as 0 or 1} */);
+
 /* ---- listener poses: head position and orientation per output bus --------------- */
 
 /*

@@ -304,6 +304,21 @@ int jf_debug_gate_scan(const float *peaks, int n, float open, float close, int h
  * run included; desc_gain_kernel behind it is in jf_profile_read_gain's figure.  0 while no gate or input meter was active. */
 int jf_profile_read_gate(jf_engine *e, double *gate_ms);
 
+/* Voice limits (include/jefferson.h): the rule voice_env_kernel and voice_select_kernel apply to ONE RUN, on the
+ * host -- the header the kernels compile (csrc/jf_voice_rule.h), so the CPU suite checks it against a NumPy model.  peak
+ * [n_blocks][n_sources] are the levels (read through root [n_sources]), bus and priority [n_sources] the sources' buses and
+ * priorities, bus_max_voices / bus_release / bus_snap [n_buses] the buses' parameters and whether this run is the first to latch
+ * a setting made with fade == 0 (NULL: none).  g_eff [n_blocks][n_sources] and g_eff_prev [n_sources] are rewritten in place by
+ * the rule; env_io and heard_io [n_sources] hold the state before the run and, on return, after it; env_out and keep_out
+ * [n_blocks][n_sources] receive the envelopes and the keep flags.  Pure host code: no engine, no GPU.  JF_ERR_ARG for a NULL
+ * pointer, a count that is not positive (n_blocks may be 0), an index out of range or parameters the setters would refuse. */
+int jf_debug_voice_select(const float *peak, const int *root, const int *bus, const int *priority, const int *bus_max_voices,
+                          const float *bus_release, const int *bus_snap, int n_sources, int n_blocks, int n_buses, float *g_eff,
+                          float *g_eff_prev, float *env_io, int *heard_io, float *env_out, int *keep_out);
+/* ms in the two kernels of the voice limits (voice_env_kernel, voice_select_kernel) since jf_profile_enable(e, 2), the event
+ * pair's own ~7 us per run included; 0 while no bus had a limit. */
+int jf_profile_read_voices(jf_engine *e, double *voice_ms);
+
 /* ---- libjefferson_group.so (jefferson_group.h): test support ------------------------------------------------------------ */
 
 typedef struct jf_group jf_group;

@@ -43,6 +43,7 @@ JF_MAX_RINGS = 40
 JF_MAX_BUSES = 1024
 JF_ROOM_MAX_TAPS = 262144
 JF_MAX_HRTF_SETS = 64
+JF_VOICE_ALWAYS = 255
 
 
 class JfGridLayout(C.Structure):
@@ -143,6 +144,13 @@ _SIGS = {
     "jf_source_levels": (C.c_int, [C.c_void_p, C.c_int, _f]),
     "jf_debug_gate_scan": (C.c_int, [_f, C.c_int, C.c_float, C.c_float, C.c_int, _i, _i]),
     "jf_profile_read_gate": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "jf_bus_set_voices": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int]),
+    "jf_bus_voices": (C.c_int, [C.c_void_p, C.c_int, _i, _f]),
+    "jf_source_set_priority": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "jf_source_priority": (C.c_int, [C.c_void_p, C.c_int]),
+    "jf_source_heard": (C.c_int, [C.c_void_p, C.c_int, _f]),
+    "jf_debug_voice_select": (C.c_int, [_f, _i, _i, _i, _i, _f, _i, C.c_int, C.c_int, C.c_int, _f, _f, _f, _i, _f, _i]),
+    "jf_profile_read_voices": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "jf_engine_add_hrtf_set": (C.c_int, [C.c_void_p, _f, C.c_int]),
     "jf_engine_add_hrtf_sofa": (C.c_int, [C.c_void_p, C.c_char_p, C.c_float]),
     "jf_num_hrtf_sets": (C.c_int, [C.c_void_p]),
@@ -442,6 +450,32 @@ def gate_scan(peaks, open, close, hold, state=(0, 0)):
     if rc:
         raise JfError(rc, "gate_scan")
     return out[:len(peaks)], (int(st[0]), int(st[1]))
+
+
+def voice_select(peak, root, bus, priority, max_voices, release, g_eff, g_eff_prev, env_prev=None, heard_prev=None, snap=None):
+    """jf_debug_voice_select (host logic only): the voice-limit rule over one run.  peak, g_eff [K][S]; root, bus, priority,
+    g_eff_prev [S]; max_voices, release, snap [n_buses]; the state env_prev (zeros), heard_prev (ones) [S] ->
+    (g_out [K][S], g_out_prev [S], env [K][S], keep [K][S] int32, (env_prev, heard_prev) after the run)"""
+    g_out = np.array(g_eff, np.float32, ndmin=2)
+    K, S = g_out.shape
+    g_out = np.ascontiguousarray(g_out)
+    peak = np.ascontiguousarray(np.asarray(peak, np.float32).reshape(K, S))
+    g_prev = np.array(g_eff_prev, np.float32).reshape(S).copy()
+    ints = lambda a: np.ascontiguousarray(np.asarray(a, np.int32).ravel())
+    root, bus, priority, max_voices = ints(root), ints(bus), ints(priority), ints(max_voices)
+    release = np.ascontiguousarray(np.asarray(release, np.float32).ravel())
+    nb = len(max_voices)
+    snap = np.zeros(nb, np.int32) if snap is None else ints(snap)
+    env_io = np.zeros(S, np.float32) if env_prev is None else np.array(env_prev, np.float32).reshape(S).copy()
+    heard_io = np.ones(S, np.int32) if heard_prev is None else np.array(heard_prev, np.int32).reshape(S).copy()
+    if not (len(root) == len(bus) == len(priority) == S and len(release) == len(snap) == nb):
+        raise JfError(JF_ERR_ARG, "voice_select: array lengths")
+    env, keep = np.zeros((max(K, 1), S), np.float32), np.zeros((max(K, 1), S), np.int32)
+    rc = lib().jf_debug_voice_select(_fp(peak), _ip(root), _ip(bus), _ip(priority), _ip(max_voices), _fp(release), _ip(snap), S, K,
+                                     nb, _fp(g_out), _fp(g_prev), _fp(env_io), _ip(heard_io), _fp(env), _ip(keep))
+    if rc:
+        raise JfError(rc, "voice_select")
+    return g_out, g_prev, env[:K], keep[:K], (env_io, heard_io)
 
 
 def reverb_rms_gain(signal, ir):
@@ -949,6 +983,42 @@ class Engine:
         """ms in the gate stage's two kernels since profile_enable(2)"""
         r = C.c_double()
         self._chk(lib().jf_profile_read_gate(self.h, C.byref(r)))
+        return r.value
+
+    # ---- voice limits (include/jefferson.h: "voice limits") ----
+    def set_voices(self, bus, max_voices, release=0.0, fade=True):
+        """bus `bus` renders at most `max_voices` of its sources a block, the loudest by an envelope that falls by `release`
+        per block (0: no limit) (jf_bus_set_voices)"""
+        self._chk(lib().jf_bus_set_voices(self.h, int(bus), int(max_voices), float(release), int(bool(fade))))
+
+    def voices(self, bus):
+        """(max_voices, release)"""
+        n, r = np.zeros(1, np.int32), np.zeros(1, np.float32)
+        self._chk(lib().jf_bus_voices(self.h, int(bus), _ip(n), _fp(r)))
+        return int(n[0]), float(r[0])
+
+    def set_priority(self, s, priority):
+        """0 .. 255; JF_VOICE_ALWAYS (255): always heard, takes no place (jf_source_set_priority)"""
+        self._chk(lib().jf_source_set_priority(self.h, int(s), int(priority)))
+
+    def priority(self, s):
+        r = lib().jf_source_priority(self.h, int(s))
+        if r < 0:
+            raise JfError(r, "priority")
+        return r
+
+    def heard(self, n_blocks=1):
+        """the last rendered call's voices, [S][n_blocks][2] = {env, keep} (jf_source_heard)"""
+        out = np.zeros((self.S, int(n_blocks), 2), np.float32)
+        self._chk(lib().jf_source_heard(self.h, int(n_blocks), _fp(out)))
+        return out
+
+    voice_select = staticmethod(voice_select)
+
+    def profile_read_voices(self):
+        """ms in the voice limits' two kernels since profile_enable(2)"""
+        r = C.c_double()
+        self._chk(lib().jf_profile_read_voices(self.h, C.byref(r)))
         return r.value
 
     def room_wet(self, n_blocks):

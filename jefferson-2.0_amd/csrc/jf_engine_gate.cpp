@@ -17,6 +17,8 @@ bool gate_wanted(jf_engine *e) {
     if (e->levels_want) return true;
     for (const GatePar &g : e->gt_par)
         if (g.open > 0.0f) return true;
+    for (const int n : e->vc_N)
+        if (n > 0) return true;  // (a voice limit counts as a gate: jf_engine_voice.cpp)
     return false;
 }
 
@@ -70,11 +72,13 @@ static int gate_latch_active(jf_engine *e) {
 }
 
 int gate_latch(jf_engine *e) {
-    e->gate_on = e->gate_meters = false;
+    e->gate_on = e->gate_meters = e->voice_on = false;
+    bool voices = false;
     {
         std::lock_guard<std::mutex> lk(e->pos_mu);
-        if (e->gt_par.empty() && !e->levels_want) return JF_OK;  // nothing was ever set
-        bool active = e->levels_want;
+        voices = voice_latch_host(e);  // a bus with a voice limit: the stage runs whether or not a source has a gate
+        if (e->gt_par.empty() && !e->levels_want && !voices) return JF_OK;  // nothing was ever set
+        bool active = e->levels_want || voices;
         for (size_t s = 0; s < e->gt_par.size() && !active; s++) active = e->gt_par[s].open > 0.0f;
         if (!active) return JF_OK;  // every gate was set back to open = 0, no meters
         if (e->gt_par.empty())
@@ -83,8 +87,10 @@ int gate_latch(jf_engine *e) {
             e->run_gpar = e->gt_par;
         e->gate_meters = e->levels_want;
     }
-    const int rc = gate_latch_active(e);
+    int rc = gate_latch_active(e);
+    if (rc == JF_OK && voices) rc = voice_latch_active(e);
     e->gate_on = rc == JF_OK;
+    e->voice_on = e->gate_on && voices;
     return rc;
 }
 
@@ -106,6 +112,12 @@ int run_gate_stage(jf_engine *e, int p, int K, int canon, bool timed) {
     rc = e->tm_gate.end(e, timed);
     if (rc) return rc;
     e->last_gate = true;
+    e->last_voice = e->vc_reported = false;
+    if (e->voice_on) {  // the buses' voice limits: g_eff and g_eff_prev rewritten in place (jf_engine_voice.cpp)
+        rc = run_voice_stage(e, peak, g_eff, g_eff_prev, K, timed);
+        if (rc) return rc;
+        e->vc_reported = e->gate_meters;
+    }
     rc = e->tm_gain.begin(e, timed);
     if (rc) return rc;
     JF_HIP(e, launch_desc_gain(e->d_desc, g_eff_prev, g_eff_prev, g_eff, e->S, K, canon, e->stream));
@@ -116,10 +128,15 @@ int run_gate_stage(jf_engine *e, int p, int K, int canon, bool timed) {
     return JF_OK;
 }
 
-void gate_settle(jf_engine *e) { e->gate_on = false; }
+void gate_settle(jf_engine *e) { e->gate_on = e->voice_on = false; }
 
-// src < 0: every source.  Nothing to close in an engine that never ran the stage: every gate is closed there.
+// src < 0: every source.  Nothing to close in an engine that never ran the stage: every gate is closed there.  The source's
+// voice envelope starts over with it.
 int gate_close_source(jf_engine *e, int src) {
+    {
+        const int rc = voice_reset_source(e, src);
+        if (rc) return rc;
+    }
     if (!e->d_gt_state) return JF_OK;
     if (src < 0)
         JF_HIP(e, hipMemsetAsync(e->d_gt_state, 0, sizeof(GateState) * (size_t)e->S, e->stream));
@@ -133,7 +150,7 @@ int gate_levels_copy(jf_engine *e, int K) {
     const size_t KS = (size_t)e->maxK * (size_t)e->S, n = (size_t)K * (size_t)e->S;
     for (size_t a = 0; a < 3; a++)
         JF_HIP(e, hipMemcpyAsync(e->h_levels + a * KS, e->d_gt_lv + a * KS, sizeof(float) * n, hipMemcpyDeviceToHost, e->stream));
-    return JF_OK;
+    return e->vc_reported ? voice_heard_copy(e, K) : JF_OK;
 }
 
 // h_levels holds a run: blocks b0 .. b0 + K of a call of n_blocks, into the call's [S][n_blocks][3]
@@ -145,10 +162,14 @@ void gate_levels_land(jf_engine *e, int K, int b0, int n_blocks) {
         for (size_t s = 0; s < S; s++)
             for (size_t a = 0; a < 3; a++) e->levels_last[(s * nb + (size_t)b0 + k) * 3 + a] = e->h_levels[a * KS + k * S + s];
     e->levels_blocks = b0 + K == n_blocks ? n_blocks : 0;
+    if (e->vc_reported)
+        voice_heard_land(e, K, b0, n_blocks);
+    else
+        e->heard_blocks = 0;
 }
 
 // what the last jf_batch_run left on the device: brought over once, the stream waited for
-static int gate_levels_fetch(jf_engine *e) {
+int gate_levels_fetch(jf_engine *e) {
     const int K = e->levels_dev_blocks;
     if (K <= 0) return JF_OK;
     const int rc = gate_levels_copy(e, K);

@@ -18,8 +18,11 @@
 //   jf_engine_gate.cpp    voice gates and input meters: the sources' thresholds, what a processing call latches of them, the stage
 //                         that writes a run's gain trajectory from the inputs' levels (run_gate_stage, jf_gate.hip) and
 //                         jf_source_set_gate / jf_source_levels
+//   jf_engine_voice.cpp   voice limits: the buses' limits and the sources' priorities, what a processing call latches of them
+//                         (inside gate_latch), the two kernels run_gate_stage launches between its scan and desc_gain_kernel
+//                         (run_voice_stage, jf_voice.hip) and jf_bus_set_voices / jf_source_heard
 //   jf_engine_debug.cpp   every entry point of include/jefferson_debug.h (taps, timing hooks, tuning switches, accessors)
-// What the four latched controls (gain, masters, sets, gates) share is here once: StagedRing (their asynchronous uploads), StageTimer
+// What the five latched controls (gain, masters, sets, gates, voice limits) share is here once: StagedRing (their asynchronous uploads), StageTimer
 // (the event pairs of a stage that only some runs launch), CallLatches (a processing call's latch and settlement of all four).
 // Not part of any interface: nothing outside csrc/ includes this file.
 #ifndef JF_ENGINE_INTERNAL_H
@@ -49,6 +52,7 @@
 #include "jf_host.h"
 #include "jf_pose_rule.h"
 #include "jf_room.h"
+#include "jf_voice_rule.h"
 
 namespace jf {
 hipError_t launch_table_build(const float *d_hrir, int n_rows, int taps, const float2 *d_tw, float4 *d_htab, hipStream_t st);
@@ -115,6 +119,12 @@ hipError_t launch_input_level(const SrcSignal *d_sigs, const SrcState *d_state, 
 hipError_t launch_gate_scan(const GatePar *d_par, GateState *d_state, const int *d_root, float *d_peak, float *d_sumsq,
                             const float *d_g_prev, const float *d_g_new, const float *d_g_traj, float *d_g_eff, float *d_g_eff_prev,
                             float *d_gate, int S, int K, hipStream_t st);
+// voice limits (jf_voice.hip): the envelopes of a run's levels, then who is heard on every bus with a limit (g_eff in place)
+hipError_t launch_voice_env(const float *d_peak, const int *d_root, const int *d_bus, const int *d_prio, const VoiceBus *d_par,
+                            float *d_env_prev, const int *d_heard_prev, float *d_env, float *d_g_eff_prev, float *d_heard, int S,
+                            int K, int n_buses, int use_snap, hipStream_t st);
+hipError_t launch_voice_select(const int *d_members, const int *d_seg, const int *d_prio, const VoiceBus *d_par, const float *d_env,
+                               float *d_g_eff, int *d_heard_prev, float *d_heard, int S, int K, int n_buses, hipStream_t st);
 }  // namespace jf
 
 using namespace jf;
@@ -550,6 +560,33 @@ struct jf_engine : ReverbSetup {
     bool last_gate = false;                   // the last run launched the stage (jf_debug_last_kernels)
     StageTimer tm_gate;                       // profiling 2: around the two kernels (jf_profile_read_gate)
 
+    // VOICE LIMITS (jf_bus_set_voices, jf_source_set_priority).  Per bus max_voices N (0: no limit) and a release;
+    // per source a priority and, on the device ONLY, the state {env_prev, heard_prev} (jf_voice_rule.h).  While the engine is
+    // ACTIVE for voices -- some bus has N > 0 -- it counts as gate-active, and run_gate_stage launches voice_env_kernel and
+    // voice_select_kernel (jf_voice.hip) between gate_scan_kernel and desc_gain_kernel: they rewrite g_eff in place.  The host
+    // state is under pos_mu like `pos` and empty until first use; an engine whose buses all have N = 0 allocates nothing below
+    // and launches nothing (gate_latch: voice_latch_host).
+    std::vector<int> vc_N;                    // [n_buses] (empty: no limit was ever set, every one 0)
+    std::vector<float> vc_rho;                // [n_buses]
+    std::vector<char> vc_snap;                // [n_buses] the limit was set with fade == 0 since the last call latched the limits
+    std::vector<int> vc_prio;                 // [S] (empty: every priority 0)
+    std::vector<float> heard_last;            // [S][heard_blocks][2] = {env, keep} of the last rendered call, on the host
+    int heard_blocks = 0;                     // (0: none; valid while it equals levels_blocks)
+    // what the processing call in hand latched (its thread's alone)
+    bool voice_on = false;                    // the call is active for voices
+    std::vector<int> run_vc;                  // the call's tables as the device holds them (jf_engine_voice.cpp: image_len)
+    bool run_vc_snap = false;                 // the call's next run is its first and some bus was set with fade == 0
+    bool vc_reported = false;                 // the last run of the gate stage left env and heard for the input meters' copies
+    DevBuf<int> d_vc_tab;                     // the tables: bus [S], priority [S], members [S], VoiceBus [JF_MAX_BUSES], seg
+    std::vector<int> dev_vc;                  // what it holds (empty: nothing yet)
+    DevBuf<float> d_vc_env;                   // [2][maxK][S]: env, heard of a run
+    DevBuf<float> d_vc_envprev;               // [S]
+    DevBuf<int> d_vc_heardprev;               // [S]
+    StagedRing<int> vc_ring;                  // slots of one image: the asynchronous copy to d_vc_tab
+    PinnedBuf<float> h_heard;                 // [2][maxK][S] where a run's env and heard land on the host
+    bool last_voice = false;                  // the last run of the gate stage launched the two kernels (jf_debug_last_kernels)
+    StageTimer tm_voice;                      // profiling 2: around the two kernels (jf_profile_read_voices)
+
     PinnedBuf<float> h_pos_pinned;  // [S][5]   pinned + mapped: the real-time kernel reads it in place
     PinnedBuf<float> h_out_pinned;  // [kRtMaxWgs][2B] pinned + mapped: ... and writes its workgroups' stereo blocks in place
     int rt_wgs = 0;                 // partial blocks the block in flight left there (0: one finished block)
@@ -858,6 +895,21 @@ JF_INTERNAL int gate_close_source(jf_engine *e, int src);
 JF_INTERNAL int gate_levels_copy(jf_engine *e, int K);
 JF_INTERNAL void gate_levels_land(jf_engine *e, int K, int b0, int n_blocks);
 JF_INTERNAL bool gate_wanted(jf_engine *e);
+JF_INTERNAL int gate_levels_fetch(jf_engine *e);  // what the last jf_batch_run left on the device (jf_source_levels, jf_source_heard)
+// voice limits (jf_engine_voice.cpp).  gate_latch calls voice_latch_host under pos_mu (the call's tables; true while some bus
+// has a limit: the engine then counts as gate-active) and voice_latch_active behind the gates' own buffers (allocation, the
+// copy that differs).  run_voice_stage: from run_gate_stage between gate_scan_kernel and desc_gain_kernel, while e->voice_on.
+// voice_reset_source: a reset or a new signal takes the source's envelope to 0 through the engine's stream (src < 0: every one).
+// voice_heard_copy / voice_heard_land travel with gate_levels_copy / gate_levels_land.  voice_set_buses: under pos_mu, beside
+// master_set_buses.  voice_wanted: some bus has a limit (jf_reverb_set_ir refuses then, through gate_wanted).
+JF_INTERNAL bool voice_latch_host(jf_engine *e);
+JF_INTERNAL int voice_latch_active(jf_engine *e);
+JF_INTERNAL int run_voice_stage(jf_engine *e, const float *peak, float *g_eff, float *g_eff_prev, int K, bool timed);
+JF_INTERNAL int voice_reset_source(jf_engine *e, int src);
+JF_INTERNAL int voice_heard_copy(jf_engine *e, int K);
+JF_INTERNAL void voice_heard_land(jf_engine *e, int K, int b0, int n_blocks);
+JF_INTERNAL void voice_set_buses(jf_engine *e, int n_buses);
+JF_INTERNAL bool voice_wanted(jf_engine *e);
 // the three pointers run_gain_stage hands desc_gain_kernel for the next run of K blocks (all null unless e->gain_on), and the
 // step to the run after it (jf_engine_gain.cpp)
 JF_INTERNAL void gain_run_gains(const jf_engine *e, const float **g_prev, const float **g_new, const float **g_traj);

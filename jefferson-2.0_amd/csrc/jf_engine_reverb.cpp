@@ -293,8 +293,8 @@ int jf_reverb_set_ir(jf_engine *e, const float *ir, size_t n_ir, float gain) {
         return fail(e, JF_ERR_STATE, "the convolution reverb is not offered while a room is set");
     if (n_ir && e->n_followers > 0)  // (jf_source_share_input)
         return fail(e, JF_ERR_STATE, "the convolution reverb is not offered while a source follows another's input (it keeps per-source state)");
-    if (n_ir && gate_wanted(e))  // (jf_source_set_gate, jf_engine_set_input_meters)
-        return fail(e, JF_ERR_STATE, "the convolution reverb is not offered while a source has a voice gate or input meters are on (its wet tail outlives the dry level)");
+    if (n_ir && gate_wanted(e))  // (jf_source_set_gate, jf_engine_set_input_meters, jf_bus_set_voices)
+        return fail(e, JF_ERR_STATE, "the convolution reverb is not offered while a source has a voice gate, a bus has a voice limit or input meters are on (its wet tail outlives the dry level)");
     {
         const int rc = rv_ahead_discard(e);
         if (rc) return rc;
