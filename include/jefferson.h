@@ -311,6 +311,78 @@ int jf_source_set_signal(jf_engine *e, int src, const float *mono, size_t n);
 int jf_source_set_live(jf_engine *e, int src, int live);
 int jf_num_live_sources(const jf_engine *e);
 
+/*
+ * STREAM SOURCES: packets at the codec's rate, queued and resampled on the GPU.  The reference runs at 44 100 Hz and nothing else
+ * (main.cu:79 writes its file at that rate, main.cu:93 opens PortAudio with SAMPLE_RATE), has no input at all (Audio.cu:32-33;
+ * paCallback ignores `input`, Audio.cu:164-175) and plays whole blocks of a resident buffer (copyIncomingBlock,
+ * GPUSoundSource.cu:481-513).  A live source (above) wants exactly B samples at 44 100 Hz per block; a decoder hands out 10 or
+ * 20 ms packets at 48 000, 32 000, 16 000 or 8 000 Hz.  A STREAM SOURCE takes packets of any size at the codec's own rate: the
+ * engine queues them in a FIFO, converts them to 44 100 Hz on the GPU (one kernel per processing call for all stream sources,
+ * ahead of everything else) and feeds the result to everything that works on a live source.
+ *
+ * THE RULE (csrc/jf_stream_rule.h, compiled for the kernel and for the host twins below).  g = gcd(rate, 44100), L = 44100 / g,
+ * M = rate / g.  Accepted: 8000 <= rate <= 48000 with L <= 441 -- every multiple of 100 Hz in range, 11 025 and 22 050; anything
+ * else is JF_ERR_RANGE.  Output sample t (a 64-bit count since the stream was started or reset) stands at input frame
+ * i(t) = floor(t M / L) with phase p(t) = t M mod L, i(-1) := -1.  y[t] = sum_{k < 64} h[p][k] x[i - k] with x[j] = 0 for j < 0:
+ * 64 taps, a delay of 31 input frames; h[p][k] = c sinc(c tau) w(tau), tau = k - 31 + p / L, c = 0.94 min(1, L / M), w a Kaiser
+ * window (beta 9) of half-width 33; every row normalised in double to sum 1 and rounded once to float32.  The sum is taken in
+ * float32 in a fixed order (four accumulators, tap k into accumulator k mod 4 in ascending k, (a0 + a1) + (a2 + a3)), the same
+ * on the host and on the device.  rate == 44100 is a pure FIFO: no filter, no delay, the samples pass unchanged.  A call of n
+ * outputs from t0 consumes need(t0, n) = i(t0 + n - 1) - i(t0 - 1) frames: 278 or 279 for a block of 256 at 48 000 Hz.
+ *
+ *   jf_source_set_stream(e, s, rate_hz, capacity_frames): source s becomes a stream source with a FIFO of capacity_frames at
+ *     rate_hz; rate_hz == 0 makes it resident and silent again (nothing to do on a source that does not stream).  Like
+ *     jf_source_set_live it waits for the engine's stream and is called between blocks; the window stays as it is, the play
+ *     position and the resampler start at 0.  capacity_frames must be at least jf_stream_min_capacity(e, rate_hz) -- the most
+ *     frames a call of max(max_batch_blocks, 1) blocks can need, plus 64 of history -- else JF_ERR_RANGE; a host that pushes 20 ms
+ *     packets wants that plus a packet or two.  JF_ERR_ARG for a bad index, JF_ERR_STATE while a block is in flight.  A stream
+ *     source is NOT counted by jf_num_live_sources and takes no row of any `in` argument: the live contract is unchanged.
+ *     jf_source_set_signal, jf_source_set_live and jf_source_share_input (as a follower) end the stream and drop its queue; a
+ *     follower of a stream source hears the resampled signal.
+ *   jf_source_push(e, s, frames, n): appends n float32 frames.  It takes all of them, or returns JF_ERR_RANGE and takes nothing.
+ *     CALLED FROM THE THREAD THAT PROCESSES BLOCKS, or serialised with it by the host: it is not a setter and takes no lock.  It
+ *     is allowed while a submitted block is in flight: free space is counted against the oldest frame a queued, uncollected
+ *     call may still read.  JF_ERR_STATE on a source that is not a stream source.
+ *   jf_source_stream_need(e, s, n_blocks): the frames still to be pushed so that the next call of n_blocks blocks finds all it
+ *     needs (>= 0; negative: an error code).
+ *   jf_source_stream_stats(e, s, out): {pushed, consumed, zeros_inserted, queued} in frames, since the stream was set or reset.
+ *   jf_source_stream_rate: the source's rate, 0 if it does not stream.
+ *
+ * UNDERRUNS.  A call of n outputs that needs `need` frames and finds have < need queued consumes the `have` frames, and the
+ * missing need - have frames ARE ZEROS APPENDED TO THE STREAM: written into the FIFO by the processing call, counted in
+ * zeros_inserted, history for later calls; later pushes follow them.  So the stream's input sequence X is well defined -- the
+ * pushes in order, with those zeros where they fell -- and every output is the rule applied to X.  While the engine is paused
+ * nothing is consumed.  jf_source_reset drops the queue and restarts the resampler (t = 0, zero history).  The position
+ * advances only when a call is actually queued.
+ *
+ * THE CONTRACT.  A stream source renders BIT FOR BIT what a live source renders when fed y = jf_stream_resample(rate, X, ...)
+ * cut into blocks, however the pushes and the calls are cut: no spatialiser, reverb, gate or live kernel knows of it.  Per-block
+ * calls of an engine with a stream source take the batch pipeline with one block (as with buses, rooms and gains); the
+ * device-resident batch form (jf_batch_upload_*, jf_batch_run) returns JF_ERR_STATE, as for live sources.  An engine that never
+ * sets a stream source allocates nothing, launches what it launched and renders the same bits; after the last stream source has
+ * gone the per-block call is one launch again.
+ *
+ * The host twins need no engine:
+ *   jf_stream_ratio(rate, &L, &M); jf_stream_table(rate, out[L][64]); jf_stream_frames_needed(rate, t0, n_out) = need(t0, n_out)
+ *   (negative: an error code); jf_stream_resample(rate, x, n_in, t0, n_out, y): the rule on x as the WHOLE input since t = 0,
+ *   frames at or beyond n_in count as 0; jf_stream_resample_from(rate, x, x0, n_in, ...): the same with x[0] standing at frame x0
+ *   and every frame outside [x0, x0 + n_in) counting as 0 -- for output positions whose whole input would not fit in memory.
+ *
+ * Not offered: jefferson_group.h and jf_ctest have no stream sources; int16 pushes; rates above 48 000 Hz; output buses at
+ * another rate than 44 100 Hz; pushes from a second thread; stream sources inside the one-launch real-time kernel.
+ */
+int jf_source_set_stream(jf_engine *e, int src, int rate_hz, int capacity_frames);
+int jf_stream_min_capacity(const jf_engine *e, int rate_hz);
+int jf_source_push(jf_engine *e, int src, const float *frames, int n);
+long long jf_source_stream_need(jf_engine *e, int src, int n_blocks);
+int jf_source_stream_stats(jf_engine *e, int src, unsigned long long out[4] /* pushed, consumed, zeros_inserted, queued */);
+int jf_source_stream_rate(const jf_engine *e, int src);
+int jf_stream_ratio(int rate_hz, int *L, int *M);
+int jf_stream_table(int rate_hz, float *out /* [L][64] */);
+long long jf_stream_frames_needed(int rate_hz, long long t0, long long n_out);
+int jf_stream_resample(int rate_hz, const float *x, long long n_in, long long t0, long long n_out, float *y);
+int jf_stream_resample_from(int rate_hz, const float *x, long long x0, long long n_in, long long t0, long long n_out, float *y);
+
 /* SoundSource::updateFromCartesian(float3) (SoundSource.cu:20-36); callable from a
  * different thread than the audio thread; latched at the next block boundary. */
 int jf_source_set_cartesian(jf_engine *e, int src, float x, float y, float z);
@@ -986,7 +1058,7 @@ int jf_sources_set_latched(jf_engine *e, const float *records);
  * whose norm is further than 1e-3 from 1.
  * jf_batch_upload_world is jf_batch_upload_positions for such a trajectory (total_blocks of world positions and poses; the
  * records are formed on the device); jf_batch_run / jf_batch_fetch are used unchanged and, as there, do not move the sources or
- * the listeners.  JF_ERR_STATE while the engine has a live source.
+ * the listeners.  JF_ERR_STATE while the engine has a live or a stream source.
  */
 int jf_process_batch_world(jf_engine *e, int n_blocks, const float *in, const float *world, const float *poses, float *out_mix);
 int jf_batch_upload_world(jf_engine *e, int total_blocks, const float *world, const float *poses);
@@ -1006,7 +1078,8 @@ int jf_batch_upload_world(jf_engine *e, int total_blocks, const float *world, co
  * JF_ERR_ARG, checked on the host before anything is launched: NULL arrays, n_blocks <= 0, an engine without objects, a
  * non-finite value, a quaternion whose norm is further than 1e-3 from 1.
  * jf_batch_upload_objects is jf_batch_upload_world for such a trajectory, with exactly its rules; jf_batch_run / jf_batch_fetch
- * are used unchanged and do not move the objects, the sources or the listeners.  JF_ERR_STATE while the engine has a live source.
+ * are used unchanged and do not move the objects, the sources or the listeners.  JF_ERR_STATE while the engine has a live or a
+ * stream source.
  */
 int jf_process_batch_objects(jf_engine *e, int n_blocks, const float *in, const float *objects, const float *poses, float *out_mix);
 int jf_batch_upload_objects(jf_engine *e, int total_blocks, const float *objects, const float *poses);
@@ -1019,8 +1092,8 @@ int jf_batch_upload_objects(jf_engine *e, int total_blocks, const float *objects
  * to [n_blocks][2*B] floats, or NULL -> the engine's own buffer, which
  * jf_batch_fetch below copies to the host.  Blocks first_block .. first_block + n_blocks - 1 of
  * the uploaded trajectory are consumed.
- * The signals must be on the device already: while the engine has a live source (jf_source_set_live) jf_batch_upload_positions
- * and jf_batch_run return JF_ERR_STATE.
+ * The signals must be on the device already: while the engine has a live source (jf_source_set_live) or a stream source
+ * (jf_source_set_stream) jf_batch_upload_positions and jf_batch_run return JF_ERR_STATE.
  */
 int jf_batch_upload_positions(jf_engine *e, int total_blocks, const float *positions);
 int jf_batch_run(jf_engine *e, int first_block, int n_blocks, float *d_out_mix);

@@ -319,6 +319,20 @@ int jf_debug_voice_select(const float *peak, const int *root, const int *bus, co
  * pair's own ~7 us per run included; 0 while no bus had a limit. */
 int jf_profile_read_voices(jf_engine *e, double *voice_ms);
 
+/* Stream sources (include/jefferson.h).  jf_debug_stream_seek: the stream source's next output is t_out (up to
+ * 2^53); the queue is dropped, the history is zeros and the next push is frame i(t_out - 1) + 1 of the stream -- what a stream
+ * that has run for t_out samples and has been fed zeros so far looks like (positions beyond 2^31 without hours of audio).
+ * Waits for the engine's stream; JF_ERR_STATE on a source that does not stream or while a block is in flight.
+ * jf_debug_input_buffer: the first n floats of the device buffer a live or stream source's samples are put into (the kernels
+ * read a call's new samples there at the source's play position, which starts at 0 and advances by whole blocks modulo the
+ * buffer's length); returns that length.  Waits for the engine's stream. */
+int jf_debug_stream_seek(jf_engine *e, int src, long long t_out);
+int jf_debug_input_buffer(jf_engine *e, int src, float *out, int n);
+/* bytes of device and pinned memory the engine holds for stream sources: the rates' tables, the FIFOs and the jobs' staging (the
+ * sources' device buffers are their signals, as a live source's is).  0 in an engine that never had a stream source; the tables
+ * and the staging stay when the last one goes. */
+long long jf_debug_stream_bytes(const jf_engine *e);
+
 /* ---- libjefferson_group.so (jefferson_group.h): test support ------------------------------------------------------------ */
 
 typedef struct jf_group jf_group;

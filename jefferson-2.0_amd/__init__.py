@@ -108,6 +108,20 @@ _SIGS = {
     "jf_source_set_signal": (C.c_int, [C.c_void_p, C.c_int, _f, C.c_size_t]),
     "jf_source_set_live": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "jf_num_live_sources": (C.c_int, [C.c_void_p]),
+    "jf_source_set_stream": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "jf_stream_min_capacity": (C.c_int, [C.c_void_p, C.c_int]),
+    "jf_source_push": (C.c_int, [C.c_void_p, C.c_int, _f, C.c_int]),
+    "jf_source_stream_need": (C.c_longlong, [C.c_void_p, C.c_int, C.c_int]),
+    "jf_source_stream_stats": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_ulonglong)]),
+    "jf_source_stream_rate": (C.c_int, [C.c_void_p, C.c_int]),
+    "jf_stream_ratio": (C.c_int, [C.c_int, _i, _i]),
+    "jf_stream_table": (C.c_int, [C.c_int, _f]),
+    "jf_stream_frames_needed": (C.c_longlong, [C.c_int, C.c_longlong, C.c_longlong]),
+    "jf_stream_resample": (C.c_int, [C.c_int, _f, C.c_longlong, C.c_longlong, C.c_longlong, _f]),
+    "jf_stream_resample_from": (C.c_int, [C.c_int, _f, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, _f]),
+    "jf_debug_stream_seek": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong]),
+    "jf_debug_input_buffer": (C.c_int, [C.c_void_p, C.c_int, _f, C.c_int]),
+    "jf_debug_stream_bytes": (C.c_longlong, [C.c_void_p]),
     "jf_engine_set_buses": (C.c_int, [C.c_void_p, C.c_int]),
     "jf_num_buses": (C.c_int, [C.c_void_p]),
     "jf_source_set_bus": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
@@ -297,6 +311,48 @@ def device_numa_node(device=0):
 def pin_thread_to_device(device=0):
     """Restrict the calling thread to the CPUs of the device's NUMA node (include/jefferson.h); False if that is not possible."""
     return lib().jf_pin_thread_to_device(int(device)) == 0
+
+
+def stream_ratio(rate):
+    """(L, M) of a stream source's rate: L = 44100 / gcd, M = rate / gcd (jf_stream_ratio); JfError for a rate it refuses"""
+    L, M = C.c_int(0), C.c_int(0)
+    rc = lib().jf_stream_ratio(int(rate), C.byref(L), C.byref(M))
+    if rc:
+        raise JfError(rc, "stream_ratio")
+    return L.value, M.value
+
+
+def stream_table(rate):
+    """the rate's polyphase table, float32 [L][64] (jf_stream_table)"""
+    L, _ = stream_ratio(rate)
+    out = np.zeros((L, 64), np.float32)
+    rc = lib().jf_stream_table(int(rate), _fp(out))
+    if rc:
+        raise JfError(rc, "stream_table")
+    return out
+
+
+def stream_frames_needed(rate, t0, n_out):
+    """input frames a call of n_out outputs from output position t0 consumes (jf_stream_frames_needed)"""
+    n = lib().jf_stream_frames_needed(int(rate), int(t0), int(n_out))
+    if n < 0:
+        raise JfError(int(n), "stream_frames_needed")
+    return int(n)
+
+
+def stream_resample(rate, x, t0, n_out, x0=0):
+    """outputs t0 .. t0 + n_out - 1 of the stream rule on x (jf_stream_resample: the host twin of stream_resample_kernel); x is
+    the whole input since t = 0, or with x0 the frames from x0 on (jf_stream_resample_from); every other frame counts as 0"""
+    x = np.ascontiguousarray(x, np.float32)
+    y = np.zeros(int(n_out), np.float32)
+    xp = _fp(x) if x.size else None
+    if x0:
+        rc = lib().jf_stream_resample_from(int(rate), xp, int(x0), x.size, int(t0), int(n_out), _fp(y))
+    else:
+        rc = lib().jf_stream_resample(int(rate), xp, x.size, int(t0), int(n_out), _fp(y))
+    if rc:
+        raise JfError(rc, "stream_resample")
+    return y
 
 
 def position_from_spherical(ele, azi, r):
@@ -775,6 +831,53 @@ class Engine:
 
     def n_live(self):
         return lib().jf_num_live_sources(self.h)
+
+    def stream_min_capacity(self, rate):
+        c = lib().jf_stream_min_capacity(self.h, int(rate))
+        if c < 0:
+            raise JfError(c, "stream_min_capacity")
+        return c
+
+    def set_stream(self, s, rate, capacity=None):
+        """source s takes packets at `rate` Hz through push() (include/jefferson.h: jf_source_set_stream); rate 0: resident and
+        silent again.  capacity None: the minimum plus a tenth of a second"""
+        if capacity is None:
+            capacity = 0 if not rate else self.stream_min_capacity(rate) + int(rate) // 10
+        self._chk(lib().jf_source_set_stream(self.h, int(s), int(rate), int(capacity)))
+
+    def push(self, s, frames):
+        frames = np.ascontiguousarray(frames, np.float32).reshape(-1)
+        self._chk(lib().jf_source_push(self.h, int(s), _fp(frames) if frames.size else None, frames.size))
+
+    def stream_need(self, s, n_blocks=1):
+        n = lib().jf_source_stream_need(self.h, int(s), int(n_blocks))
+        if n < 0:
+            raise JfError(int(n), "stream_need")
+        return int(n)
+
+    def stream_stats(self, s):
+        """{pushed, consumed, zeros_inserted, queued} (jf_source_stream_stats)"""
+        o = (C.c_ulonglong * 4)()
+        self._chk(lib().jf_source_stream_stats(self.h, int(s), o))
+        return dict(zip(("pushed", "consumed", "zeros_inserted", "queued"), (int(v) for v in o)))
+
+    def stream_rate(self, s):
+        return lib().jf_source_stream_rate(self.h, int(s))
+
+    def stream_seek(self, s, t_out):
+        self._chk(lib().jf_debug_stream_seek(self.h, int(s), int(t_out)))
+
+    def stream_bytes(self):
+        return int(lib().jf_debug_stream_bytes(self.h))
+
+    def input_buffer(self, s):
+        """the device buffer a live or stream source's samples are put into (jf_debug_input_buffer)"""
+        n = lib().jf_debug_input_buffer(self.h, int(s), None, 0)
+        if n < 0:
+            self._chk(n)
+        out = np.zeros(n, np.float32)
+        self._chk(min(0, lib().jf_debug_input_buffer(self.h, int(s), _fp(out), n)))
+        return out
 
     def set_buses(self, n):
         """n stereo mixes (include/jefferson.h: jf_engine_set_buses); with more than one, every array a processing call

@@ -299,6 +299,7 @@ int reset_sources(jf_engine *e, int src) {
             JF_HIP(e, hipMemsetAsync(e->d_rv_fut + s0 * e->rv_Fn * B1, 0, sizeof(float) * e->rv_Fn * B1 * ns, e->stream));
         }
     }
+    stream_reset_source(e, src);  // a stream source: the queue dropped, the resampler at t = 0 (the engine's stream is idle)
     return gate_close_source(e, src);  // a source that starts over has its gate closed; the thresholds stay
 }
 
@@ -849,6 +850,7 @@ static int swap_signal(jf_engine *e, int src, DevBuf<float> d_new, int n_dev, bo
     JF_HIP(e, hipStreamSynchronize(e->stream));
     if (e->rv_side && e->rv_side_busy) JF_HIP(e, hipStreamSynchronize(e->rv_side));
     if (live && e->live.empty()) e->live.assign((size_t)e->S, 0);
+    stream_clear_source(e, src);  // (a stream source: its FIFO goes with the old input; jf_source_set_stream attaches a new one behind this)
     e->d_signal[src] = std::move(d_new);  // the old signal is released; the source's window stays as it is
     const SrcSignal rec = e->d_signal[src] ? SrcSignal{e->d_signal[src], n_dev, 0} : SrcSignal{e->d_zero, e->N, 0};
     if (!e->live.empty()) e->live[src] = live;
@@ -935,6 +937,7 @@ int jf_source_share_input(jf_engine *e, int src, int of) {
     }
     e->root[src] = r;
     e->d_signal[src].reset();  // its own signal (or live buffer) is released: its record names the root's from now on
+    stream_clear_source(e, src);
     e->h_sigs[src] = e->h_sigs[r];
     if (!e->live.empty()) e->live[src] = 0;  // only roots and unshared sources are live channels
     JF_HIP(e, h2d(e, e->d_sigs + src, &e->h_sigs[src], sizeof(SrcSignal)));
@@ -954,7 +957,7 @@ int jf_source_share_input(jf_engine *e, int src, int of) {
 int jf_source_input_of(const jf_engine *e, int src) { return valid_src(e, src) ? root_of(e, src) : JF_ERR_ARG; }
 
 // jf_source_set_signal without what it means for the source's level (jf_source_set_live turns a live source resident through it)
-static int set_signal(jf_engine *e, int src, const float *mono, size_t n) {
+extern "C++" int set_signal(jf_engine *e, int src, const float *mono, size_t n) {
     return jf_guard([&]() -> int {
     DeviceGuard bind(e);
     if (!valid_src(e, src) || (n && !mono) || n > 0x7fffffffu) return fail(e, JF_ERR_ARG, "bad source or signal");
@@ -1002,6 +1005,13 @@ int jf_source_set_live(jf_engine *e, int src, int live) {
     const bool is_live = !e->live.empty() && e->live[src];
     if (is_live == (live != 0)) return JF_OK;
     if (!live) return set_signal(e, src, nullptr, 0);  // resident again, and silent
+    return attach_input_buffer(e, src, true);
+    });
+}
+
+// A fresh, zeroed buffer of live_len floats as the source's signal: a live channel (live), or a stream source's (it takes no row
+// of `in`: jf_engine_stream.cpp)
+extern "C++" int attach_input_buffer(jf_engine *e, int src, bool live) {
     if (e->live_len == 0) {
         // a multiple of B that holds a window's worth (the kernels wrap with one conditional subtract) and a whole batch call
         const long long need = std::max<long long>(e->N, (long long)e->maxK * e->B);
@@ -1013,8 +1023,7 @@ int jf_source_set_live(jf_engine *e, int src, int live) {
     JF_HIP(e, d_new.alloc((size_t)e->live_len));
     JF_HIP(e, hipMemsetAsync(d_new, 0, sizeof(float) * (size_t)e->live_len, e->stream));
     JF_HIP(e, hipStreamSynchronize(e->stream));
-    return swap_signal(e, src, std::move(d_new), e->live_len, true);
-    });
+    return swap_signal(e, src, std::move(d_new), e->live_len, live);
 }
 
 int jf_num_live_sources(const jf_engine *e) { return e ? e->n_live : JF_ERR_ARG; }
@@ -1363,6 +1372,7 @@ static int submit_block(jf_engine *e, const float *in, bool interleaved) {
     if (e->in_flight) return fail(e, JF_ERR_STATE, "a block is already in flight");
     if (device_fault(e)) return fail(e, JF_ERR_DEVICE, kHandOffMsg);
     e->last_ingest = false;
+    e->last_stream = false;
     e->last_pose = 0;
     if (e->paused.load(std::memory_order_relaxed)) {  // Audio.cu:101: nothing is consumed (live input is dropped), output is silence
         JF_HIP(e, hipMemsetAsync(e->d_mix, 0, sizeof(float) * 2 * e->B * e->n_buses, e->stream));
@@ -1378,7 +1388,7 @@ static int submit_block(jf_engine *e, const float *in, bool interleaved) {
         }
         e->meters_stage_blocks = 0;
         e->levels_stage_blocks = 0;
-        if (e->S <= e->rt_max_sources && !e->profiling && e->N == kN && e->n_buses == 1 && e->room.P == 0 && !e->gain_on && !e->master_on && !e->sets_on && !e->gate_on) {  // (PAD_LEN 2048, buses, a room, an active gain, master or gate, a source on another HRTF set: the batch path with K = 1)
+        if (e->S <= e->rt_max_sources && !e->profiling && e->N == kN && e->n_buses == 1 && e->room.P == 0 && !e->gain_on && !e->master_on && !e->sets_on && !e->gate_on && e->n_stream == 0) {  // (PAD_LEN 2048, buses, a room, an active gain, master or gate, a source on another HRTF set, a stream source: the batch path with K = 1)
             // few sources: ONE launch does descriptors, spatialisation and mix, reading the positions
             // from and writing the stereo block to pinned host memory -- no copies, one sync
             const int p = e->cur;
@@ -1440,6 +1450,10 @@ static int submit_block(jf_engine *e, const float *in, bool interleaved) {
         }
         if (e->n_live > 0) {
             const int rc = live_ingest(e, in, interleaved, e->B, (size_t)e->B);
+            if (rc) return rc;
+        }
+        if (e->n_stream > 0) {
+            const int rc = stream_ingest(e, e->B);
             if (rc) return rc;
         }
         JF_HIP(e, hipMemcpyAsync(e->d_pos_rt, e->h_pos_pinned, sizeof(float) * 5 * e->S, hipMemcpyHostToDevice,
@@ -1822,27 +1836,33 @@ static int batch_run(jf_engine *e, int first_block, int n_blocks, float *d_out_m
 
 // The device-resident form works on signals that are on the device already: not while a source waits for its samples.
 static const char *kLiveResidentMsg = "the device-resident batch form does not take live sources (jf_process_batch_in does)";
+static const char *kStreamResidentMsg = "the device-resident batch form does not take stream sources (jf_process_batch does)";
 
 int jf_batch_upload_positions(jf_engine *e, int total_blocks, const float *positions) {
     if (e && e->n_live > 0) return jf_guard([&]() -> int { return fail(e, JF_ERR_STATE, kLiveResidentMsg); });
+    if (e && e->n_stream > 0) return jf_guard([&]() -> int { return fail(e, JF_ERR_STATE, kStreamResidentMsg); });
     if (e) e->last_pose = 0;
     return upload_positions(e, total_blocks, positions);
 }
 
 int jf_batch_upload_world(jf_engine *e, int total_blocks, const float *world, const float *poses) {
     if (e && e->n_live > 0) return jf_guard([&]() -> int { return fail(e, JF_ERR_STATE, kLiveResidentMsg); });
+    if (e && e->n_stream > 0) return jf_guard([&]() -> int { return fail(e, JF_ERR_STATE, kStreamResidentMsg); });
     return upload_world(e, total_blocks, world, poses, false);
 }
 
 int jf_batch_upload_objects(jf_engine *e, int total_blocks, const float *objects, const float *poses) {
     if (e && e->n_live > 0) return jf_guard([&]() -> int { return fail(e, JF_ERR_STATE, kLiveResidentMsg); });
+    if (e && e->n_stream > 0) return jf_guard([&]() -> int { return fail(e, JF_ERR_STATE, kStreamResidentMsg); });
     return upload_world(e, total_blocks, objects, poses, true);
 }
 
 int jf_batch_run(jf_engine *e, int first_block, int n_blocks, float *d_out_mix) {
     if (e && e->n_live > 0) return jf_guard([&]() -> int { return fail(e, JF_ERR_STATE, kLiveResidentMsg); });
+    if (e && e->n_stream > 0) return jf_guard([&]() -> int { return fail(e, JF_ERR_STATE, kStreamResidentMsg); });
     if (e) {
         e->last_ingest = false;
+        e->last_stream = false;
         e->last_pose = 0;
     }
     // the standing gains (no trajectory of gains here): a level that changed ramps over the run's first block
@@ -1949,7 +1969,7 @@ static int process_batch(jf_engine *e, int n_blocks, const float *in, const floa
     return jf_guard([&]() -> int {
     DeviceGuard bind(e);
     if (!e || (!positions && (!world || !poses)) || !out_mix || n_blocks <= 0) return fail(e, JF_ERR_ARG, "bad batch arguments");
-    if (e->n_live > 0 && e->in_flight) return fail(e, JF_ERR_STATE, "a per-block call is in flight");  // (before its input is touched)
+    if ((e->n_live > 0 || e->n_stream > 0) && e->in_flight) return fail(e, JF_ERR_STATE, "a per-block call is in flight");  // (before its input is touched)
     // a trajectory jf_batch_set_gains staged for another number of blocks: refused with nothing uploaded or rendered
     int rc = gain_traj_check(e, n_blocks);
     if (rc) return rc;
@@ -1971,6 +1991,11 @@ static int process_batch(jf_engine *e, int n_blocks, const float *in, const floa
             // this window's samples of every live source, ahead of its kernels (the staging is free: the window before
             // has been waited for below)
             rc = live_ingest(e, in ? in + (size_t)b0 * e->B : nullptr, false, k * e->B, (size_t)n_blocks * e->B);
+            if (rc) return rc;
+        }
+        e->last_stream = false;
+        if (e->n_stream > 0) {  // ... and this window's outputs of every stream source, from what their FIFOs hold
+            rc = stream_ingest(e, k * e->B);
             if (rc) return rc;
         }
         rc = batch_run(e, b0, k, nullptr);

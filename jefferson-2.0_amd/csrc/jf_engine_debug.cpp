@@ -473,6 +473,7 @@ const char *jf_debug_last_kernels(jf_engine *e) {
         std::string k;
         if (e->last_pose) k = e->last_pose == 2 ? "pose_object_kernel;" : "pose_kernel;";
         if (e->last_ingest) k += "live_ingest_kernel;";
+        if (e->last_stream) k += "stream_resample_kernel;";
         if (!e->last_rt && !e->last_prep_skipped) k += "prep_kernel;";
         if (!e->last_rt && e->last_set) k += "desc_set_kernel;";
         if (!e->last_rt && e->last_gate) k += "input_level_kernel;gate_scan_kernel;";

@@ -21,6 +21,9 @@
 //   jf_engine_voice.cpp   voice limits: the buses' limits and the sources' priorities, what a processing call latches of them
 //                         (inside gate_latch), the two kernels run_gate_stage launches between its scan and desc_gain_kernel
 //                         (run_voice_stage, jf_voice.hip) and jf_bus_set_voices / jf_source_heard
+//   jf_engine_stream.cpp  stream sources: the sources' FIFOs and resampler positions, the jobs a processing call writes for the one
+//                         kernel ahead of everything else (stream_ingest, jf_stream.hip), the host twins of the rule and
+//                         jf_source_set_stream / jf_source_push
 //   jf_engine_debug.cpp   every entry point of include/jefferson_debug.h (taps, timing hooks, tuning switches, accessors)
 // What the five latched controls (gain, masters, sets, gates, voice limits) share is here once: StagedRing (their asynchronous uploads), StageTimer
 // (the event pairs of a stage that only some runs launch), CallLatches (a processing call's latch and settlement of all four).
@@ -52,6 +55,7 @@
 #include "jf_host.h"
 #include "jf_pose_rule.h"
 #include "jf_room.h"
+#include "jf_stream.h"
 #include "jf_voice_rule.h"
 
 namespace jf {
@@ -587,6 +591,36 @@ struct jf_engine : ReverbSetup {
     bool last_voice = false;                  // the last run of the gate stage launched the two kernels (jf_debug_last_kernels)
     StageTimer tm_voice;                      // profiling 2: around the two kernels (jf_profile_read_voices)
 
+    // STREAM SOURCES (jf_source_set_stream, jf_source_push).  A stream source is internally a live source that
+    // takes no row of `in`: the same live_len device buffer named by its record in d_sigs, filled at the source's play position
+    // by stream_resample_kernel (jf_stream.hip) from the source's FIFO -- pinned, mapped host memory the pushes write and the
+    // kernel reads in place -- through the rule of jf_stream_rule.h.  Frame j of the stream's input sequence (pushes in order,
+    // an underrun's zeros where they fell) lies at fifo[j mod cap].  Positions are the processing thread's alone (the pushes are
+    // its own, or serialised with it).  Nothing below exists in an engine that never had a stream source.
+    struct StreamSrc {
+        int rate = 0;                // 0: not a stream source
+        int L = 1, M = 1, cap = 0;
+        PinnedBuf<float> fifo;
+        float *hd_fifo = nullptr;    // its device address
+        const float *d_table = nullptr;  // the rate's table (stream_tables); null at 44 100 Hz
+        long long t = 0;             // outputs queued so far: the next call's t0
+        long long r = 0;             // frames consumed so far: i(t - 1) + 1
+        long long w = 0;             // frames appended so far (pushes and zeros); queued = w - r
+        long long hold = 0;          // r before the last queued call: while that call is in flight it may read back to hold - 64
+        unsigned long long pushed = 0, consumed = 0, zeros = 0;
+    };
+    struct StreamTable {
+        int rate = 0;
+        DevBuf<float> d;             // [L][64]
+    };
+    std::vector<StreamSrc> streams;          // [S] (empty: no source ever streamed)
+    std::vector<int> stream_idx;             // the stream sources, ascending
+    int n_stream = 0;
+    std::vector<StreamTable> stream_tables;  // one per rate in use so far, kept until the engine goes
+    PinnedBuf<StreamJob> h_sjobs;            // [S] the jobs of the call in hand (only one call is ever in flight)
+    StreamJob *hd_sjobs = nullptr;           // its device address
+    bool last_stream = false;                // the last call launched stream_resample_kernel (jf_debug_last_kernels)
+
     PinnedBuf<float> h_pos_pinned;  // [S][5]   pinned + mapped: the real-time kernel reads it in place
     PinnedBuf<float> h_out_pinned;  // [kRtMaxWgs][2B] pinned + mapped: ... and writes its workgroups' stereo blocks in place
     int rt_wgs = 0;                 // partial blocks the block in flight left there (0: one finished block)
@@ -967,6 +1001,17 @@ inline int debug_record_rule(int rows_new[4], float w_new[4], int rows_old[4], f
     *flags = d.flags;
     return changed ? 1 : 0;
 }
+// stream sources (jf_engine_stream.cpp).  stream_ingest: from the per-block and the batch calls where live_ingest stands, while
+// e->n_stream > 0 -- the jobs of n = K B outputs of every stream source, an underrun's zeros into the FIFOs, the one launch; the
+// positions advance once the launch is queued.  stream_clear_source: the source gets another input (swap_signal, a share): its
+// FIFO goes (the engine's stream is idle).  stream_reset_source: jf_source_reset -- the queue dropped, t = 0, zero history (src
+// < 0: every one).  attach_input_buffer / set_signal (jf_engine.cpp): a fresh zeroed live_len buffer as the source's signal,
+// counted as a live channel or not; a resident signal (null: silence) without touching the source's level.
+JF_INTERNAL int stream_ingest(jf_engine *e, int n);
+JF_INTERNAL void stream_clear_source(jf_engine *e, int src);
+JF_INTERNAL void stream_reset_source(jf_engine *e, int src);
+JF_INTERNAL int attach_input_buffer(jf_engine *e, int src, bool live);
+JF_INTERNAL int set_signal(jf_engine *e, int src, const float *mono, size_t n);
 JF_INTERNAL int ensure_interp_rows(jf_engine *e);
 JF_INTERNAL int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int first_block = -1);
 JF_INTERNAL int reset_sources(jf_engine *e, int src);

@@ -33,6 +33,9 @@
  *              a mixer bus does) instead of making it resident (jf_source_set_signal); same blocks bit for bit, so the
  *              written file is byte-identical to the plain render as long as the input does not loop (a live feed that
  *              runs out goes on with zeros; a resident signal starts over).  Works with --latency, --batch and --script.
+ *              An input at another rate the engine takes (8000 .. 48000 Hz, jf_stream_ratio) is fed through a STREAM SOURCE
+ *              in 20 ms packets at the file's rate (jf_source_set_stream, jf_source_push): the engine resamples it on the
+ *              GPU and the output is written at 44 100 Hz.  A 44 100 Hz file does what it did before.
  *   --batch N  hand the engine N callbacks at a time (jf_process_batch: the same blocks, the positions the
  *              audio thread would have latched given up front) -- what an offline render should use: a
  *              single source cannot fill a GPU one block at a time
@@ -82,7 +85,18 @@ static size_t script_debugmode2(size_t length, int block, float radius, float **
 static const float *g_feed_sig = NULL;
 static size_t g_feed_n = 0, g_feed_at = 0;
 static float *g_feed_buf = NULL;
+/* ... or, when the file's rate is not 44 100 Hz, through a stream source (jf_source_set_stream): 20 ms packets at the file's
+ * rate until the call of `count` outputs finds all it needs, as a host with a decoder pushes them; the engine resamples */
+static jf_engine *g_stream_e = NULL;
+static int g_stream_block = 0, g_stream_packet = 0;
 static const float *feed(size_t count) {
+    if (g_stream_e) {
+        while (jf_source_stream_need(g_stream_e, 0, (int)(count / (size_t)g_stream_block)) > 0) {
+            for (int i = 0; i < g_stream_packet; i++, g_feed_at++) g_feed_buf[i] = g_feed_at < g_feed_n ? g_feed_sig[g_feed_at] : 0.0f;
+            if (jf_source_push(g_stream_e, 0, g_feed_buf, g_stream_packet) != JF_OK) break; /* (the call then underruns: zeros) */
+        }
+        return NULL;
+    }
     if (!g_feed_buf) return NULL;
     for (size_t i = 0; i < count; i++, g_feed_at++) g_feed_buf[i] = g_feed_at < g_feed_n ? g_feed_sig[g_feed_at] : 0.0f;
     return g_feed_buf;
@@ -99,7 +113,8 @@ int main(int argc, char **argv) {
         fprintf(stderr, "usage: %s <hrir_dir | set.sofa> <in.wav> <out.wav> [--block B] [--azi A] [--ele E] "
                         "[--dwell N] [--rounds R] [--step D] [--radius r] [--latency] [--batch N] [--script debugmode2] [--no-pin] "
                         "[--sofa-tol T] [--cloud-tol T] [--live]\n"
-                        "  --live: feed the input block by block (jf_source_set_live) instead of making it resident\n"
+                        "  --live: feed the input block by block (jf_source_set_live) instead of making it resident;\n"
+                        "          an input at 8000 .. 48000 Hz other than 44100 goes through a stream source in 20 ms packets\n"
                         "  set.sofa: rings of uniform azimuth steps (the ring rule), or any other directions (the cloud rule: "
                         "barycentric weights on their triangulation)\n", argv[0]);
         return 2;
@@ -157,7 +172,23 @@ int main(int argc, char **argv) {
         fprintf(stderr, "engine: %s\n", jf_last_error(NULL));
         return 1;
     }
-    if (live) {
+    int stream_L = 0, stream_M = 0;
+    if (live && fs != 44100 && block > 0 && jf_stream_ratio(fs, &stream_L, &stream_M) == JF_OK) {
+        /* a file at a codec's rate: through a stream source in 20 ms packets; the output is written at 44 100 Hz */
+        const int packet = fs / 50;
+        if (jf_source_set_stream(e, 0, fs, jf_stream_min_capacity(e, fs) + 2 * packet) != JF_OK) {
+            fprintf(stderr, "stream: %s\n", jf_last_error(e));
+            return 1;
+        }
+        g_feed_sig = sig;
+        g_feed_n = n;
+        g_feed_buf = (float *)malloc(sizeof(float) * (size_t)packet);
+        if (!g_feed_buf) return 1;
+        g_stream_e = e;
+        g_stream_block = block;
+        g_stream_packet = packet;
+        fs = 44100;
+    } else if (live) {
         if (block <= 0 || jf_source_set_live(e, 0, 1) != JF_OK) {
             fprintf(stderr, "live: %s\n", jf_last_error(e));
             return 1;
