@@ -368,8 +368,8 @@ int jf_num_live_sources(const jf_engine *e);
  *   frames at or beyond n_in count as 0; jf_stream_resample_from(rate, x, x0, n_in, ...): the same with x[0] standing at frame x0
  *   and every frame outside [x0, x0 + n_in) counting as 0 -- for output positions whose whole input would not fit in memory.
  *
- * Not offered: jefferson_group.h and jf_ctest have no stream sources; int16 pushes; rates above 48 000 Hz; output buses at
- * another rate than 44 100 Hz; pushes from a second thread; stream sources inside the one-launch real-time kernel.
+ * Not offered: jefferson_group.h and jf_ctest have no stream sources; int16 pushes; rates above 48 000 Hz; pushes from a
+ * second thread; stream sources inside the one-launch real-time kernel.  (Buses at the codec's rate: "bus outputs" below.)
  */
 int jf_source_set_stream(jf_engine *e, int src, int rate_hz, int capacity_frames);
 int jf_stream_min_capacity(const jf_engine *e, int rate_hz);
@@ -382,6 +382,82 @@ int jf_stream_table(int rate_hz, float *out /* [L][64] */);
 long long jf_stream_frames_needed(int rate_hz, long long t0, long long n_out);
 int jf_stream_resample(int rate_hz, const float *x, long long n_in, long long t0, long long n_out, float *y);
 int jf_stream_resample_from(int rate_hz, const float *x, long long x0, long long n_in, long long t0, long long n_out, float *y);
+
+/* ---- bus outputs: each mix as packets at the codec's rate -------------------- */
+
+/*
+ * BUS OUTPUTS: every bus's mix once more at a rate of its own, resampled on the GPU and pulled in packets.  The reference runs at
+ * 44 100 Hz and nothing else (main.cu:79 writes its file at that rate, main.cu:93 opens PortAudio with SAMPLE_RATE) and hands
+ * its one mix to the sound card block by block (Audio.cu:26: the callback's float *output).  An encoder wants 48 000 Hz, a
+ * narrow-band leg 16 000 or 8 000 Hz, in packets of 10 or 20 ms: a bus with an OUTPUT gets every finished block of its mix -- dry
+ * sum, the room's wet part, through the master section: exactly the samples the processing call hands out -- converted to its
+ * rate by one kernel per processing call for all buses, into a ring of pinned host memory that jf_bus_pull reads.  The mirror
+ * image of a stream source: packet in, packet out.
+ *
+ * THE RULE (csrc/jf_output_rule.h, compiled for the kernel and for the host twins below).  g = gcd(R, 44100), L = R / g phases,
+ * M = 44100 / g.  Accepted: 8000 <= R <= 48000 with L <= 480 and M <= 441 -- every multiple of 100 Hz in range, 11 025 and 22 050,
+ * the rates a stream source takes; anything else is JF_ERR_RANGE.  Output frame u (a 64-bit count since the output was set or reset) stands at input frame
+ * i(u) = floor(u M / L) with phase p(u) = u M mod L.  The first N input frames determine produced(N) = ceil(N L / M) outputs; a
+ * call that renders n frames after N0 yields produced(N0 + n) - produced(N0): 278 or 279 for a block of 256 at 48 000 Hz.
+ * T = 64 s taps, s the smallest power of two with s L >= M (s = 1 at 48 000 Hz, 2 at 32 000 / 24 000 / 22 050, 4 at 16 000 /
+ * 12 000 / 11 025, 8 at 8 000: T <= 512), a delay of D = T / 2 - 1 input frames (0.7 ms at 48 000 Hz, 5.8 ms at 8 000 Hz).  Per
+ * channel y[u] = sum_{k < T} h[p][k] x[i - k] with x[j] = 0 for j < 0; h[p][k] = c sinc(c tau) w(tau), tau = k - D + p / L,
+ * c = 0.94 min(1, L / M), w a Kaiser window (beta 9) of half-width T / 2 + 1; every row normalised in double to sum 1 and
+ * rounded once to float32.  The sum is taken in float32 in a fixed order (four accumulators, tap k into accumulator k mod 4 in
+ * ascending k, (a0 + a1) + (a2 + a3)), the same on the host and on the device; left and right use the same row.  R == 44100 is a
+ * pure FIFO: no table, no delay.
+ *
+ *   jf_bus_set_output(e, bus, rate_hz, capacity_frames): the bus gets an output at rate_hz with a ring of capacity_frames stereo
+ *     frames; on a bus that has one it starts over (u = 0, zero history, an empty ring); rate_hz == 0 takes it away (nothing to
+ *     do on a bus without one).  It waits for the engine's stream and is called between blocks.  capacity_frames must be at least
+ *     jf_output_min_capacity(e, rate_hz) -- the most frames a call of max(max_batch_blocks, 1) blocks can yield, plus 1 -- a host
+ *     that pulls 20 ms packets wants that plus a packet or two.  JF_ERR_ARG for a bad bus or a capacity below the minimum,
+ *     JF_ERR_RANGE for a rate that is not accepted, JF_ERR_STATE while a block is in flight.
+ *   jf_bus_pull(e, bus, frames, n): copies up to n interleaved stereo frames, oldest first; returns how many (0: none ready;
+ *     negative: an error code, JF_ERR_STATE on a bus without an output).  CALLED FROM THE THREAD THAT PROCESSES BLOCKS, or
+ *     serialised with it by the host: it takes no lock.  It is allowed while a submitted block is in flight and then hands out
+ *     collected frames only.
+ *   jf_bus_output_ready(e, bus): the frames a pull would find.
+ *   jf_bus_output_stats(e, bus, out): {produced, pulled, dropped, queued} in frames since the output was set or reset.
+ *   jf_bus_output_rate: the bus's output rate, 0 without one.
+ *
+ * WHEN FRAMES BECOME PULLABLE.  The frames of a block become pullable when the call that hands the block out has returned:
+ * jf_process_block*, jf_process_batch*, jf_collect_block; for jf_callback* (and jf_pa_callback) the call that hands that block
+ * out, one call after the one that queued it.  A paused call renders nothing and appends nothing.  OVERRUN: a call whose outputs
+ * do not fit beside the unpulled frames overwrites the oldest of them; they count in `dropped`, and the next pull starts at the
+ * oldest surviving frame.  jf_source_reset leaves the outputs alone; jf_engine_set_buses keeps the outputs of the buses that
+ * remain, new buses have none.
+ *
+ * THE CONTRACT.  What jf_bus_pull hands out for a bus is BIT FOR BIT jf_output_resample(rate, X, ...), X the concatenation of the
+ * blocks the engine handed out for that bus since the output was set or reset (a paused call's silence not among them) --
+ * however the run is cut into calls and pulls.  The filter's history lives on the device.  The 44 100 Hz arrays every call hands
+ * out, and jf_pa_callback, are unchanged.  THE LIMITER'S CEILING (jf_bus_set_limiter) HOLDS FOR THE 44 100 Hz SAMPLES: resampled
+ * frames may overshoot it between samples and are not clamped.  Per-block calls of an engine with an output take the batch
+ * pipeline with one block (as with stream sources); jf_batch_upload_positions and jf_batch_run return JF_ERR_STATE while a bus
+ * has an output: the device-resident form hands nothing out to pull.  An engine that never sets an output allocates nothing,
+ * launches what it launched and renders the same bits; after the last output has gone the per-block call is one launch again.
+ *
+ * The host twins need no engine:
+ *   jf_output_ratio(rate, &L, &M, &T); jf_output_table(rate, out[L][T]); jf_output_frames(rate, n0, n) = produced(n0 + n) -
+ *   produced(n0) (negative: an error code); jf_output_resample(rate, x, n_in, u0, n_out, y): outputs u0 .. u0 + n_out - 1 of the
+ *   rule on the stereo frames x[n_in][2] as the WHOLE input since frame 0, frames at or beyond n_in count as 0;
+ *   jf_output_resample_from(rate, x, x0, n_in, ...): the same with x[0] standing at frame x0 and every frame outside
+ *   [x0, x0 + n_in) counting as 0 -- for positions whose whole input would not fit in memory.
+ *
+ * Not offered: int16 pulls; rates above 48 000 Hz; pulls from a second thread; outputs inside the one-launch real-time kernel;
+ * outputs for jf_batch_run; jefferson_group.h and jf_ctest have no bus outputs.
+ */
+int jf_bus_set_output(jf_engine *e, int bus, int rate_hz, int capacity_frames);
+int jf_output_min_capacity(const jf_engine *e, int rate_hz);
+long long jf_bus_pull(jf_engine *e, int bus, float *frames /* [n][2] */, long long n);
+long long jf_bus_output_ready(jf_engine *e, int bus);
+int jf_bus_output_stats(jf_engine *e, int bus, unsigned long long out[4] /* produced, pulled, dropped, queued */);
+int jf_bus_output_rate(const jf_engine *e, int bus);
+int jf_output_ratio(int rate_hz, int *L, int *M, int *T);
+int jf_output_table(int rate_hz, float *out /* [L][T] */);
+long long jf_output_frames(int rate_hz, long long n0, long long n);
+int jf_output_resample(int rate_hz, const float *x /* [n_in][2] */, long long n_in, long long u0, long long n_out, float *y);
+int jf_output_resample_from(int rate_hz, const float *x, long long x0, long long n_in, long long u0, long long n_out, float *y);
 
 /* SoundSource::updateFromCartesian(float3) (SoundSource.cu:20-36); callable from a
  * different thread than the audio thread; latched at the next block boundary. */

@@ -333,6 +333,19 @@ int jf_debug_input_buffer(jf_engine *e, int src, float *out, int n);
  * and the staging stay when the last one goes. */
 long long jf_debug_stream_bytes(const jf_engine *e);
 
+/* Bus outputs (include/jefferson.h).  jf_debug_output_feed: runs ONLY the output stage on a caller's mix
+ * x[n_buses][K][2B] (any K >= 1 whose outputs fit the rings, else JF_ERR_RANGE) -- as if a processing call had handed those
+ * blocks out; the frames are pullable when it returns.  JF_ERR_STATE without an output or while a block is in flight.
+ * jf_debug_output_seek: the bus's output has rendered N input frames of zeros (up to 2^52): zero history, an empty ring, the
+ * next output frame is produced(N) -- positions beyond 2^31 without hours of audio.  Waits for the engine's stream; JF_ERR_STATE
+ * on a bus without an output or while a block is in flight.
+ * jf_debug_output_bytes: bytes of device and pinned memory the engine holds for bus outputs: the rates' tables, the rings, the
+ * two halves of the history and the jobs' staging.  0 in an engine that never set an output; the tables, the history and the
+ * staging stay when the last output goes. */
+int jf_debug_output_feed(jf_engine *e, int K, const float *x);
+int jf_debug_output_seek(jf_engine *e, int bus, long long N);
+long long jf_debug_output_bytes(const jf_engine *e);
+
 /* ---- libjefferson_group.so (jefferson_group.h): test support ------------------------------------------------------------ */
 
 typedef struct jf_group jf_group;

@@ -122,6 +122,20 @@ _SIGS = {
     "jf_debug_stream_seek": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong]),
     "jf_debug_input_buffer": (C.c_int, [C.c_void_p, C.c_int, _f, C.c_int]),
     "jf_debug_stream_bytes": (C.c_longlong, [C.c_void_p]),
+    "jf_bus_set_output": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "jf_output_min_capacity": (C.c_int, [C.c_void_p, C.c_int]),
+    "jf_bus_pull": (C.c_longlong, [C.c_void_p, C.c_int, _f, C.c_longlong]),
+    "jf_bus_output_ready": (C.c_longlong, [C.c_void_p, C.c_int]),
+    "jf_bus_output_stats": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_ulonglong)]),
+    "jf_bus_output_rate": (C.c_int, [C.c_void_p, C.c_int]),
+    "jf_output_ratio": (C.c_int, [C.c_int, _i, _i, _i]),
+    "jf_output_table": (C.c_int, [C.c_int, _f]),
+    "jf_output_frames": (C.c_longlong, [C.c_int, C.c_longlong, C.c_longlong]),
+    "jf_output_resample": (C.c_int, [C.c_int, _f, C.c_longlong, C.c_longlong, C.c_longlong, _f]),
+    "jf_output_resample_from": (C.c_int, [C.c_int, _f, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, _f]),
+    "jf_debug_output_feed": (C.c_int, [C.c_void_p, C.c_int, _f]),
+    "jf_debug_output_seek": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong]),
+    "jf_debug_output_bytes": (C.c_longlong, [C.c_void_p]),
     "jf_engine_set_buses": (C.c_int, [C.c_void_p, C.c_int]),
     "jf_num_buses": (C.c_int, [C.c_void_p]),
     "jf_source_set_bus": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
@@ -352,6 +366,51 @@ def stream_resample(rate, x, t0, n_out, x0=0):
         rc = lib().jf_stream_resample(int(rate), xp, x.size, int(t0), int(n_out), _fp(y))
     if rc:
         raise JfError(rc, "stream_resample")
+    return y
+
+
+def output_ratio(rate):
+    """(L, M, T) of a bus output's rate: L = rate / gcd phases, M = 44100 / gcd, T taps (jf_output_ratio); JfError for a rate it
+    refuses"""
+    L, M, T = C.c_int(0), C.c_int(0), C.c_int(0)
+    rc = lib().jf_output_ratio(int(rate), C.byref(L), C.byref(M), C.byref(T))
+    if rc:
+        raise JfError(rc, "output_ratio")
+    return L.value, M.value, T.value
+
+
+def output_table(rate):
+    """the rate's polyphase table, float32 [L][T] (jf_output_table)"""
+    L, _, T = output_ratio(rate)
+    out = np.zeros((L, T), np.float32)
+    rc = lib().jf_output_table(int(rate), _fp(out))
+    if rc:
+        raise JfError(rc, "output_table")
+    return out
+
+
+def output_frames(rate, n0, n):
+    """output frames a call that renders n frames after n0 yields: produced(n0 + n) - produced(n0) (jf_output_frames)"""
+    r = lib().jf_output_frames(int(rate), int(n0), int(n))
+    if r < 0:
+        raise JfError(int(r), "output_frames")
+    return int(r)
+
+
+def output_resample(rate, x, u0, n_out, x0=0):
+    """output frames u0 .. u0 + n_out - 1, [n_out][2], of the bus output rule on the stereo frames x[n][2] (jf_output_resample:
+    the host twin of output_resample_kernel); x is the whole input since frame 0, or with x0 the frames from x0 on
+    (jf_output_resample_from); every other frame counts as 0"""
+    x = np.ascontiguousarray(x, np.float32).reshape(-1, 2)
+    y = np.zeros((int(n_out), 2), np.float32)
+    xp = _fp(x) if x.size else None
+    yp = _fp(y) if y.size else None
+    if x0:
+        rc = lib().jf_output_resample_from(int(rate), xp, int(x0), x.shape[0], int(u0), int(n_out), yp)
+    else:
+        rc = lib().jf_output_resample(int(rate), xp, x.shape[0], int(u0), int(n_out), yp)
+    if rc:
+        raise JfError(rc, "output_resample")
     return y
 
 
@@ -878,6 +937,53 @@ class Engine:
         out = np.zeros(n, np.float32)
         self._chk(min(0, lib().jf_debug_input_buffer(self.h, int(s), _fp(out), n)))
         return out
+
+    def output_min_capacity(self, rate):
+        c = lib().jf_output_min_capacity(self.h, int(rate))
+        if c < 0:
+            raise JfError(c, "output_min_capacity")
+        return c
+
+    def set_output(self, bus, rate, capacity=None):
+        """bus's mix once more at `rate` Hz, pulled through pull() (include/jefferson.h: jf_bus_set_output); rate 0: no output.
+        capacity None: the minimum plus a tenth of a second"""
+        if capacity is None:
+            capacity = 0 if not rate else self.output_min_capacity(rate) + int(rate) // 10
+        self._chk(lib().jf_bus_set_output(self.h, int(bus), int(rate), int(capacity)))
+
+    def pull(self, bus, n):
+        """up to n stereo frames of the bus's output, [m][2] with m <= n (jf_bus_pull)"""
+        out = np.zeros((max(int(n), 0), 2), np.float32)
+        m = lib().jf_bus_pull(self.h, int(bus), _fp(out) if out.size else None, int(n))
+        if m < 0:
+            self._chk(int(m))
+        return out[:m]
+
+    def output_ready(self, bus):
+        n = lib().jf_bus_output_ready(self.h, int(bus))
+        if n < 0:
+            raise JfError(int(n), "output_ready")
+        return int(n)
+
+    def output_stats(self, bus):
+        """{produced, pulled, dropped, queued} (jf_bus_output_stats)"""
+        o = (C.c_ulonglong * 4)()
+        self._chk(lib().jf_bus_output_stats(self.h, int(bus), o))
+        return dict(zip(("produced", "pulled", "dropped", "queued"), (int(v) for v in o)))
+
+    def output_rate(self, bus):
+        return lib().jf_bus_output_rate(self.h, int(bus))
+
+    def output_bytes(self):
+        return int(lib().jf_debug_output_bytes(self.h))
+
+    def output_feed(self, x):
+        """runs only the output stage on the mix x[n_buses][K][2B] (jf_debug_output_feed)"""
+        x = np.ascontiguousarray(x, np.float32).reshape(self.n_buses, -1, 2 * self.B)
+        self._chk(lib().jf_debug_output_feed(self.h, x.shape[1], _fp(x)))
+
+    def output_seek(self, bus, n_in):
+        self._chk(lib().jf_debug_output_seek(self.h, int(bus), int(n_in)))
 
     def set_buses(self, n):
         """n stereo mixes (include/jefferson.h: jf_engine_set_buses); with more than one, every array a processing call

@@ -220,6 +220,12 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
         const int rc = run_master_stage(e, K, d_mix_out, timed);
         if (rc) return rc;
     }
+    // bus outputs: the mix as it is handed out, once more at the buses' own rates into their rings (jf_engine_output.cpp)
+    e->last_output = false;
+    if (e->n_out > 0) {
+        const int rc = run_output_stage(e, K, d_mix_out);
+        if (rc) return rc;
+    }
     if (ahead_ok) {
         e->ahead.valid = true;
         e->ahead.first = first_block + K;
@@ -1075,6 +1081,7 @@ int jf_engine_set_buses(jf_engine *e, int n_buses) {
         }
         master_set_buses(e, n_buses);  // ... and their master sections, new ones are neutral
         voice_set_buses(e, n_buses);   // ... and their voice limits, new ones have none
+        output_set_buses(e, n_buses);  // ... and their outputs, new ones have none
         e->n_buses = n_buses;
     }
     e->own_mix_blocks = 0;
@@ -1388,7 +1395,7 @@ static int submit_block(jf_engine *e, const float *in, bool interleaved) {
         }
         e->meters_stage_blocks = 0;
         e->levels_stage_blocks = 0;
-        if (e->S <= e->rt_max_sources && !e->profiling && e->N == kN && e->n_buses == 1 && e->room.P == 0 && !e->gain_on && !e->master_on && !e->sets_on && !e->gate_on && e->n_stream == 0) {  // (PAD_LEN 2048, buses, a room, an active gain, master or gate, a source on another HRTF set, a stream source: the batch path with K = 1)
+        if (e->S <= e->rt_max_sources && !e->profiling && e->N == kN && e->n_buses == 1 && e->room.P == 0 && !e->gain_on && !e->master_on && !e->sets_on && !e->gate_on && e->n_stream == 0 && e->n_out == 0) {  // (PAD_LEN 2048, buses, a room, an active gain, master or gate, a source on another HRTF set, a stream source, a bus output: the batch path with K = 1)
             // few sources: ONE launch does descriptors, spatialisation and mix, reading the positions
             // from and writing the stereo block to pinned host memory -- no copies, one sync
             const int p = e->cur;
@@ -1525,6 +1532,7 @@ int jf_collect_block(jf_engine *e, float *out) {
         gate_levels_land(e, 1, 0, 1);
         e->levels_stage_blocks = 0;
     }
+    output_land(e);  // the block is handed out: its frames at the buses' output rates become pullable
     const int n_out = 2 * e->B * e->n_buses;  // [n_buses][2B] (the real-time kernel: one bus)
     memcpy(out, e->h_out_pinned, sizeof(float) * n_out);
     // the real-time kernel's workgroups each left the sum of their sources: add them in workgroup order
@@ -1837,10 +1845,12 @@ static int batch_run(jf_engine *e, int first_block, int n_blocks, float *d_out_m
 // The device-resident form works on signals that are on the device already: not while a source waits for its samples.
 static const char *kLiveResidentMsg = "the device-resident batch form does not take live sources (jf_process_batch_in does)";
 static const char *kStreamResidentMsg = "the device-resident batch form does not take stream sources (jf_process_batch does)";
+static const char *kOutputResidentMsg = "the device-resident batch form hands nothing out for a bus output to pull (jf_process_batch does)";
 
 int jf_batch_upload_positions(jf_engine *e, int total_blocks, const float *positions) {
     if (e && e->n_live > 0) return jf_guard([&]() -> int { return fail(e, JF_ERR_STATE, kLiveResidentMsg); });
     if (e && e->n_stream > 0) return jf_guard([&]() -> int { return fail(e, JF_ERR_STATE, kStreamResidentMsg); });
+    if (e && e->n_out > 0) return jf_guard([&]() -> int { return fail(e, JF_ERR_STATE, kOutputResidentMsg); });
     if (e) e->last_pose = 0;
     return upload_positions(e, total_blocks, positions);
 }
@@ -1860,6 +1870,7 @@ int jf_batch_upload_objects(jf_engine *e, int total_blocks, const float *objects
 int jf_batch_run(jf_engine *e, int first_block, int n_blocks, float *d_out_mix) {
     if (e && e->n_live > 0) return jf_guard([&]() -> int { return fail(e, JF_ERR_STATE, kLiveResidentMsg); });
     if (e && e->n_stream > 0) return jf_guard([&]() -> int { return fail(e, JF_ERR_STATE, kStreamResidentMsg); });
+    if (e && e->n_out > 0) return jf_guard([&]() -> int { return fail(e, JF_ERR_STATE, kOutputResidentMsg); });
     if (e) {
         e->last_ingest = false;
         e->last_stream = false;
@@ -2027,6 +2038,7 @@ static int process_batch(jf_engine *e, int n_blocks, const float *in, const floa
         if (device_fault(e)) return fail(e, JF_ERR_DEVICE, kHandOffMsg);
         if (metered) master_meters_land(e, k, b0, n_blocks);
         if (levelled) gate_levels_land(e, k, b0, n_blocks);
+        output_land(e);
     }
     call.settle(n_blocks);
     // n_blocks callbacks have run: the sources stand where the last of them read them

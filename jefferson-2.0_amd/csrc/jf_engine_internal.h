@@ -24,6 +24,9 @@
 //   jf_engine_stream.cpp  stream sources: the sources' FIFOs and resampler positions, the jobs a processing call writes for the one
 //                         kernel ahead of everything else (stream_ingest, jf_stream.hip), the host twins of the rule and
 //                         jf_source_set_stream / jf_source_push
+//   jf_engine_output.cpp bus outputs: the buses' rings and resampler positions, the jobs a processing call writes for the one
+//                         kernel behind the master section (run_output_stage, jf_output.hip), the host twins of the rule and
+//                         jf_bus_set_output / jf_bus_pull
 //   jf_engine_debug.cpp   every entry point of include/jefferson_debug.h (taps, timing hooks, tuning switches, accessors)
 // What the five latched controls (gain, masters, sets, gates, voice limits) share is here once: StagedRing (their asynchronous uploads), StageTimer
 // (the event pairs of a stage that only some runs launch), CallLatches (a processing call's latch and settlement of all four).
@@ -53,6 +56,7 @@
 #include "jf_gain_rule.h"
 #include "jf_gate_rule.h"
 #include "jf_host.h"
+#include "jf_output.h"
 #include "jf_pose_rule.h"
 #include "jf_room.h"
 #include "jf_stream.h"
@@ -621,6 +625,39 @@ struct jf_engine : ReverbSetup {
     StreamJob *hd_sjobs = nullptr;           // its device address
     bool last_stream = false;                // the last call launched stream_resample_kernel (jf_debug_last_kernels)
 
+    // BUS OUTPUTS (jf_bus_set_output, jf_bus_pull).  A bus with an output gets every call's finished mix once more
+    // at its own rate: output_resample_kernel (jf_output.hip) runs behind the master section on the run's mix and writes into the
+    // bus's ring -- pinned, mapped host memory the kernel writes and the pulls read in place -- through the rule of
+    // jf_output_rule.h.  Output frame u lies at ring[u mod cap].  The filter's history is the device's alone (d_out_hist, ping-pong
+    // like d_hist: out_par names the valid half).  Positions are the processing thread's alone.  Nothing below exists in an engine
+    // that never set an output.
+    struct BusOut {
+        int rate = 0;                // 0: no output
+        int L = 1, M = 1, T = 1, cap = 0;
+        PinnedBuf<float> ring;       // [cap][2]
+        float *hd_ring = nullptr;    // its device address
+        const float *d_table = nullptr;  // the rate's table (out_tables); null at 44 100 Hz
+        long long N = 0;             // input frames rendered so far
+        long long w = 0;             // output frames queued so far: produced(N)
+        long long vis = 0;           // ... of which the calls that hand their blocks out have returned: pullable up to here
+        long long r = 0;             // the next frame a pull hands out
+        unsigned long long produced = 0, pulled = 0, dropped = 0;
+    };
+    struct OutTable {
+        int rate = 0;
+        size_t floats = 0;
+        DevBuf<float> d;             // [L][T]
+    };
+    std::vector<BusOut> outs;                // [JF_MAX_BUSES] (empty: no bus ever had an output)
+    int n_out = 0;                           // buses with an output
+    std::vector<OutTable> out_tables;        // one per rate in use so far, kept until the engine goes
+    DevBuf<float> d_out_hist[2];             // [out_hist_buses][kOutputHist][2]
+    int out_hist_buses = 0;                  // rows they hold: n_buses when an output was last set with more buses than before
+    int out_par = 0;                         // the half that holds the buses' histories
+    PinnedBuf<OutputJob> h_ojobs;            // [JF_MAX_BUSES] the jobs of the call in hand (only one call is ever in flight)
+    OutputJob *hd_ojobs = nullptr;           // its device address
+    bool last_output = false;                // the last run launched output_resample_kernel (jf_debug_last_kernels)
+
     PinnedBuf<float> h_pos_pinned;  // [S][5]   pinned + mapped: the real-time kernel reads it in place
     PinnedBuf<float> h_out_pinned;  // [kRtMaxWgs][2B] pinned + mapped: ... and writes its workgroups' stereo blocks in place
     int rt_wgs = 0;                 // partial blocks the block in flight left there (0: one finished block)
@@ -1012,6 +1049,14 @@ JF_INTERNAL void stream_clear_source(jf_engine *e, int src);
 JF_INTERNAL void stream_reset_source(jf_engine *e, int src);
 JF_INTERNAL int attach_input_buffer(jf_engine *e, int src, bool live);
 JF_INTERNAL int set_signal(jf_engine *e, int src, const float *mono, size_t n);
+// bus outputs (jf_engine_output.cpp).  run_output_stage: from run_blocks behind run_master_stage, while e->n_out > 0 -- the jobs of
+// the run's n = K B frames of every bus with an output, the one launch; the positions advance, and an overrun is accounted for,
+// once the launch is queued.  output_land: the stream has been waited for behind a call that hands its blocks out -- what was
+// queued becomes pullable.  output_set_buses: jf_engine_set_buses -- the outputs of the buses that go are dropped (the engine's
+// stream is idle).
+JF_INTERNAL int run_output_stage(jf_engine *e, int K, const float *d_mix);
+JF_INTERNAL void output_land(jf_engine *e);
+JF_INTERNAL void output_set_buses(jf_engine *e, int n_buses);
 JF_INTERNAL int ensure_interp_rows(jf_engine *e);
 JF_INTERNAL int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int first_block = -1);
 JF_INTERNAL int reset_sources(jf_engine *e, int src);

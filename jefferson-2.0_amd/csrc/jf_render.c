@@ -36,6 +36,10 @@
  *              An input at another rate the engine takes (8000 .. 48000 Hz, jf_stream_ratio) is fed through a STREAM SOURCE
  *              in 20 ms packets at the file's rate (jf_source_set_stream, jf_source_push): the engine resamples it on the
  *              GPU and the output is written at 44 100 Hz.  A 44 100 Hz file does what it did before.
+ *   --out-rate R  write the mix at R Hz instead of 44 100 (8000 .. 48000, jf_output_ratio): bus 0 gets an output at that rate
+ *              (jf_bus_set_output), the frames are pulled after every processing call (jf_bus_pull) and the file is written
+ *              with that sample rate -- the engine resamples on the GPU.  With --latency the file holds the blocks that were
+ *              handed out: one fewer than were queued.
  *   --batch N  hand the engine N callbacks at a time (jf_process_batch: the same blocks, the positions the
  *              audio thread would have latched given up front) -- what an offline render should use: a
  *              single source cannot fill a GPU one block at a time
@@ -102,6 +106,27 @@ static const float *feed(size_t count) {
     return g_feed_buf;
 }
 
+/* --out-rate: everything pulled from bus 0's output so far, as interleaved stereo frames */
+static jf_engine *g_pull_e = NULL;
+static float *g_pull = NULL;
+static size_t g_pull_n = 0, g_pull_cap = 0;
+static int drain(void) {
+    if (!g_pull_e) return JF_OK;
+    const long long ready = jf_bus_output_ready(g_pull_e, 0);
+    if (ready < 0) return (int)ready;
+    if (g_pull_n + (size_t)ready > g_pull_cap) {
+        const size_t cap = 2 * (g_pull_n + (size_t)ready) + 4096;
+        float *p = (float *)realloc(g_pull, sizeof(float) * 2 * cap);
+        if (!p) return JF_ERR_NOMEM;
+        g_pull = p;
+        g_pull_cap = cap;
+    }
+    const long long got = jf_bus_pull(g_pull_e, 0, g_pull + 2 * g_pull_n, ready);
+    if (got < 0) return (int)got;
+    g_pull_n += (size_t)got;
+    return JF_OK;
+}
+
 static double now_s(void) {
     struct timespec ts;
     clock_gettime(CLOCK_MONOTONIC, &ts);
@@ -112,14 +137,15 @@ int main(int argc, char **argv) {
     if (argc < 4) {
         fprintf(stderr, "usage: %s <hrir_dir | set.sofa> <in.wav> <out.wav> [--block B] [--azi A] [--ele E] "
                         "[--dwell N] [--rounds R] [--step D] [--radius r] [--latency] [--batch N] [--script debugmode2] [--no-pin] "
-                        "[--sofa-tol T] [--cloud-tol T] [--live]\n"
+                        "[--sofa-tol T] [--cloud-tol T] [--live] [--out-rate R]\n"
+                        "  --out-rate R: write the mix at R Hz (8000 .. 48000), pulled from a bus output the engine resamples on the GPU\n"
                         "  --live: feed the input block by block (jf_source_set_live) instead of making it resident;\n"
                         "          an input at 8000 .. 48000 Hz other than 44100 goes through a stream source in 20 ms packets\n"
                         "  set.sofa: rings of uniform azimuth steps (the ring rule), or any other directions (the cloud rule: "
                         "barycentric weights on their triangulation)\n", argv[0]);
         return 2;
     }
-    int block = 256, dwell = 172, rounds = 72, latency = 0, batch = 0, script = 0, pin = 1, live = 0;
+    int block = 256, dwell = 172, rounds = 72, latency = 0, batch = 0, script = 0, pin = 1, live = 0, out_rate = 0;
     float azi = 3, ele = 5, step = 5, radius = 0.5f, sofa_tol = 0.51f, cloud_tol = 0.05f;
     for (int i = 4; i < argc; i++) {
         if (!strcmp(argv[i], "--latency")) latency = 1;
@@ -127,6 +153,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--live")) live = 1;
         else if (i + 1 < argc && !strcmp(argv[i], "--block")) block = atoi(argv[++i]);
         else if (i + 1 < argc && !strcmp(argv[i], "--batch")) batch = atoi(argv[++i]);
+        else if (i + 1 < argc && !strcmp(argv[i], "--out-rate")) out_rate = atoi(argv[++i]);
         else if (i + 1 < argc && !strcmp(argv[i], "--azi")) azi = (float)atof(argv[++i]);
         else if (i + 1 < argc && !strcmp(argv[i], "--ele")) ele = (float)atof(argv[++i]);
         else if (i + 1 < argc && !strcmp(argv[i], "--dwell")) dwell = atoi(argv[++i]);
@@ -201,6 +228,16 @@ int main(int argc, char **argv) {
         jf_source_set_signal(e, 0, sig, n);
     }
 
+    if (out_rate != 0) {
+        /* the mix at the codec's rate: a bus output with room for a call's frames and two 20 ms packets */
+        const int min_cap = jf_output_min_capacity(e, out_rate);
+        if (min_cap < 0 || jf_bus_set_output(e, 0, out_rate, min_cap + 2 * (out_rate / 50)) != JF_OK) {
+            fprintf(stderr, "out-rate: %s\n", min_cap < 0 ? "8000 .. 48000 Hz, a multiple of 100 Hz (or 11025, 22050)" : jf_last_error(e));
+            return 1;
+        }
+        g_pull_e = e;
+    }
+
     if (script) {
         /* DEBUGMODE 2: the way-points as the blocks latch them; per block through the setter (what the main thread calls,
          * SoundSource::updateFromSpherical) or, with --batch, as records handed over up front */
@@ -218,6 +255,7 @@ int main(int argc, char **argv) {
             for (size_t k0 = 0; k0 < nb && src == JF_OK; k0 += (size_t)batch) {
                 const int kb = nb - k0 < (size_t)batch ? (int)(nb - k0) : batch;
                 src = jf_process_batch_in(e, kb, feed((size_t)kb * (size_t)block), spos + JF_POS_FLOATS * k0, sout + 2 * (size_t)block * k0);
+                if (src == JF_OK) src = drain();
             }
         } else {
             if (latency) src = jf_callback_in(e, feed((size_t)block), sout); /* priming call: the CUDA path hands out block k - 1 */
@@ -228,6 +266,7 @@ int main(int argc, char **argv) {
                     const float *in = feed((size_t)block); /* NULL unless --live; an engine without live sources ignores it */
                     src = latency ? jf_callback_in(e, in, sout + 2 * (size_t)block * k0)
                                   : jf_process_block_in(e, in, sout + 2 * (size_t)block * k0);
+                    if (src == JF_OK) src = drain();
                 }
             }
         }
@@ -236,7 +275,8 @@ int main(int argc, char **argv) {
             fprintf(stderr, "processing: %s\n", jf_last_error(e));
             return 1;
         }
-        if (jf_wav_write_stereo24(argv[3], sout, (size_t)block * nb, fs ? fs : 44100) != JF_OK) {
+        if ((g_pull_e ? jf_wav_write_stereo24(argv[3], g_pull, g_pull_n, out_rate)
+                      : jf_wav_write_stereo24(argv[3], sout, (size_t)block * nb, fs ? fs : 44100)) != JF_OK) {
             fprintf(stderr, "output: %s\n", jf_last_error(NULL));
             return 1;
         }
@@ -244,6 +284,7 @@ int main(int argc, char **argv) {
                 ds, 1e6 * ds / (double)nb, ((double)nb * block / 44100.0) / ds);
         free(spos);
         free(sout);
+        free(g_pull);
         free(g_feed_buf);
         jf_free(sig);
         jf_engine_destroy(e);
@@ -278,6 +319,7 @@ int main(int argc, char **argv) {
         for (k = 0; k < total && rc == JF_OK; k += (size_t)batch) {
             const int nb = total - k < (size_t)batch ? (int)(total - k) : batch;
             rc = jf_process_batch_in(e, nb, feed((size_t)nb * (size_t)block), pos + JF_POS_FLOATS * k, out + 2 * (size_t)block * k);
+            if (rc == JF_OK) rc = drain();
         }
         free(pos);
         rounds = -1; /* done: skip the per-block loop */
@@ -293,6 +335,7 @@ int main(int argc, char **argv) {
             const float *in = feed((size_t)block); /* NULL unless --live */
             rc = latency ? jf_callback_in(e, in, out + 2 * (size_t)block * k)
                          : jf_process_block_in(e, in, out + 2 * (size_t)block * k);
+            if (rc == JF_OK) rc = drain();
         }
     }
     const double dt = now_s() - t0;
@@ -300,13 +343,15 @@ int main(int argc, char **argv) {
         fprintf(stderr, "processing: %s\n", jf_last_error(e));
         return 1;
     }
-    if (jf_wav_write_stereo24(argv[3], out, (size_t)block * total, fs ? fs : 44100) != JF_OK) {
+    if ((g_pull_e ? jf_wav_write_stereo24(argv[3], g_pull, g_pull_n, out_rate)
+                  : jf_wav_write_stereo24(argv[3], out, (size_t)block * total, fs ? fs : 44100)) != JF_OK) {
         fprintf(stderr, "output: %s\n", jf_last_error(NULL));
         return 1;
     }
     fprintf(stderr, "%zu blocks of %d frames in %.3f s: %.1f us per block, real-time factor %.1f\n", total, block, dt,
             1e6 * dt / (double)total, ((double)total * block / 44100.0) / dt);
     free(out);
+    free(g_pull);
     free(g_feed_buf);
     jf_free(sig);
     jf_engine_destroy(e);
