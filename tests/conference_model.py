@@ -1,5 +1,6 @@
 """One float64 reference for the whole conference contract (include/jefferson.h: output buses, shared inputs, room sends,
-per-source gain, bus masters, listener poses, objects, live input) -- TEST INFRASTRUCTURE ONLY, plain NumPy, no GPU.
+per-source gain, bus masters, listener poses, objects, live input, HRTF sets, voice gates, voice limits) -- TEST INFRASTRUCTURE
+ONLY, plain NumPy, no GPU.
 
 ConferenceModel takes the calls jf.Engine takes (same method names and arguments) and predicts every bus of every block.  It is
 COMPOSED from the references the project already trusts and adds only what none of them knows about:
@@ -14,24 +15,56 @@ COMPOSED from the references the project already trusts and adds only what none 
   room                 send_b[t] with room_model.level_track's ramp, the wet part a streaming float64 linear convolution in
                        probes.wet_stream's order (tap by tap over the non-zero taps), a delay line per bus.
   masters              jf_master_rule.h restated in float64 on the model's own dry + wet.
+  HRTF sets            sets_model.SetsModel's identity: one gain model per set; a block is the sum over the sets the source is on
+                       before or in this block, the old set at g_prev and the new one at g.  The models the source is not on add
+                       exact zeros and are skipped; windows and play positions are the first model's.
+  voice gates          the level of a block is the exact float32 peak of the B samples the block appends to the source's input
+                       (the model's own input state; a follower has its root's), gate_model.gate_scan is the rule, and g_eff
+                       goes where g went.  The send line does not know about it.
+  voice limits         voices_model.voice_rule on those peaks and g_eff, with the model's own buses, priorities and state
+                       {env_prev, heard_prev, the fade == 0 flags}; g_out replaces g_eff.
+  stream sources       a stream source is a live source whose input is stream_model.resample32, on the library's exported table
+                       (tests/test_stream.py holds that table to table64), of X: the pushes in order with the underruns' zeros
+                       where they fell -- the float32 order, because gates and rankings compare that very signal.  stream_stats
+                       is predicted.
+  bus outputs          per bus with an output, pull() is output_model.resample64 of the model's own mastered blocks since the
+                       output was set or reset; a paused call's silence is not among them.
 
 `fault` names ONE deliberate misreading of the header (FAULTS); tests/test_conference_model.py shows that each of them moves
 the prediction by 100 bounds in every session that uses the feature -- every clause the model implements counts.
 
-Every call returns [n_buses][K][2B] float64; `last` holds what the bound of a block is made of.
+Every call returns [n_buses][K][2B] float64; `last` holds what the bound of a block is made of and, while input meters are on,
+`levels` [S][K][3] and (with a limited bus) `heard` [S][K][2] as jf_source_levels and jf_source_heard report them.
 """
 import numpy as np
 
 import model64
+import output_model
 import pose_model
+import stream_model
 from gain_model import CloudGainModel, GainModel
+from gate_model import gate_scan
 from model64 import f32
+from voices_model import ALWAYS, voice_rule
 
 JF_OK, JF_ERR_ARG, JF_ERR_RANGE, JF_ERR_STATE = 0, -1, -2, -5
 
 FAULTS = ("send_post_fader", "follower_own_position", "reset_one_window", "signal_keeps_level", "set_bus_old_listener",
           "set_bus_old_send", "detach_jumps", "pause_advances_gain", "pause_advances_send", "pause_advances_limiter",
-          "limiter_restarts_each_call", "master_ramp_every_block", "set_room_keeps_tail")
+          "limiter_restarts_each_call", "master_ramp_every_block", "set_room_keeps_tail",
+          # voice gates
+          "gate_post_fader", "gate_gates_send", "follower_roots_gate", "set_gate_touches_state", "signal_keeps_gate_open",
+          "pause_advances_gate", "gate_restarts_each_call", "skipped_block_freezes_window",
+          # voice limits
+          "limit_limits_send", "env_on_limited_bus_only", "set_bus_old_limit", "signal_resets_heard", "muted_takes_a_place",
+          "always_takes_a_place", "snap_not_consumed", "pause_advances_env",
+          # HRTF sets
+          "bus_set_reaches_joiners", "set_bus_resets_set", "paused_call_takes_switch", "switch_in_every_run",
+          # stream sources
+          "pause_consumes_stream", "reset_keeps_stream_history", "underrun_zeros_not_history", "follower_hears_raw_packets",
+          # bus outputs
+          "output_pre_master", "output_misses_wet", "paused_silence_appended", "set_buses_drops_outputs")
+MAX_HRTF_SETS = 64
 
 IDENTITY = np.array([0, 0, 0, 1, 0, 0, 0], np.float32)
 
@@ -65,11 +98,37 @@ def master_block64(x, B, m_prev, m_new, ramp, c, r, g_prev):
 
 
 class ConferenceModel:
-    def __init__(self, B, hrtf_len, S, hrir, cloud=None, fault=None):
+    def __init__(self, B, hrtf_len, S, hrir, cloud=None, fault=None, max_batch_blocks=None):
         assert fault is None or fault in FAULTS, fault
         self.fault = fault
-        self.gm = GainModel(B, hrtf_len, S, hrir) if cloud is None else CloudGainModel(B, hrtf_len, S, hrir, cloud)
+        self._make = (lambda h: GainModel(B, hrtf_len, S, h)) if cloud is None else (lambda h: CloudGainModel(B, hrtf_len, S, h, cloud))
+        self.gm = self._make(hrir)
         self.kemar = cloud is None
+        self.max_k = max_batch_blocks   # a call longer than this is several runs of one stream (None: one run)
+        # HRTF sets (sets_model.SetsModel's identity): one gain model per set; windows, play positions and gains are the
+        # first model's, the further ones render on its sources' state
+        self.models = [self.gm]
+        self.set_prev, self.set_new = [0] * S, [0] * S
+        self.bus_set = {}               # (fault bus_set_reaches_joiners: what jf_bus_set_hrtf last gave a bus)
+        self.switches = {"fade": 0, "snap": 0}
+        # voice gates (gate_model.gate_scan is the rule) and input meters
+        self.gate_par = [(f32(0), f32(0), 0)] * S
+        self.gate_state = [(0, 0)] * S
+        self.input_meters = False
+        self.gate_hist = [[] for _ in range(S)]      # per source: gate[k] of every rendered block while it had a gate
+        # voice limits (voices_model.voice_rule is the rule)
+        self.vbus = [0] * S             # the bus whose limit holds for the source: the bus it is on (kept apart for a fault)
+        self.prio = [0] * S
+        self.vc_N, self.vc_rho, self.vc_snap = [0], [f32(0)], [0]
+        self.env_prev, self.heard_prev = np.zeros(S, np.float32), np.ones(S, np.int32)
+        self.stream = [None] * S        # per source: None, or the stream's state (set_stream)
+        self.stream_table = None        # rate -> the library's exported float32 table [L][64] (the sessions set it)
+        self.outputs = {}               # bus -> the output's state (set_output)
+        self.stream_totals = [[0, 0] for _ in range(S)]     # per source, over the session: underruns, zeros inserted
+        self.pull_counts = {}           # per bus, over the session
+        self.ties = 0                   # candidates of one bus with equal envelopes above 0 on different inputs: none is wanted
+        self.skipped = 0               # source blocks unheard at both ends because of a gate or a limit
+        self.ramps = {"out": 0, "in": 0}     # on limited buses: blocks with a loser ramping out / a winner ramping in
         self.B, self.S, self.N = B, S, self.gm.N
         self.n_buses = 1
         self.bus = [0] * S              # where the dry block goes
@@ -94,6 +153,7 @@ class ConferenceModel:
         self.lim_c, self.lim_r, self.lim_g = [0.0], [1.0], [1.0]
         self.meters_on = False
         self.paused = False
+        self.late = False
         self.last = None
         self.limiter_blocks = {"attack": 0, "release": 0}
 
@@ -114,10 +174,21 @@ class ConferenceModel:
     def _swap_signal(self, s, buf, live):
         """the source and, with a root, its followers: the new input from its start; the windows stay"""
         self.live[s] = live
+        self.stream[s] = None           # (jf_source_set_stream attaches its FIFO behind this)
+        self._starts_over(s, self.fault != "signal_keeps_gate_open")
         for m in self.members(s):
             self.src[m].buf = buf
             if m == s or self.fault != "follower_own_position":
                 self.src[m].count = 0
+
+    def _starts_over(self, s, close=True):
+        """a new input or a reset: the source's own gate is closed (the thresholds stay), its envelope back at 0; heard_prev
+        is left alone"""
+        if close:
+            self.gate_state[s] = (0, 0)
+        self.env_prev[s] = 0
+        if self.fault == "signal_resets_heard":
+            self.heard_prev[s] = 1
 
     def _detach_input(self, s):
         if self.root[s] == s:
@@ -146,13 +217,19 @@ class ConferenceModel:
         r = self.root[of]
         if self.root[s] == r:
             return
-        self.root[s], self.live[s] = r, False
+        self.root[s], self.live[s], self.stream[s] = r, False, None
         q, qr = self.src[s], self.src[r]
         q.buf, q.count, q.x = qr.buf, qr.count, qr.x.copy()
 
     def reset(self, s):
         q = self.src[s]
         q.old_ele, q.old_azi = f32(0), f32(0)
+        self._starts_over(s)
+        z = self.stream[s]
+        if z is not None:               # the queue dropped, the resampler at t = 0 with zero history, the statistics from 0
+            keep = self.fault == "reset_keeps_stream_history"
+            z.update(X=z["X"][:len(z["X"]) - z["queued"]] if keep else np.zeros(0, np.float32), t=z["t"] if keep else 0,
+                     pushed=0, consumed=0, zeros_inserted=0, queued=0)
         for m in self.members(self.root[s]):
             if m == s or self.fault != "reset_one_window":
                 self.src[m].x[:] = 0
@@ -260,11 +337,21 @@ class ConferenceModel:
         for name, neutral in (("m_prev", 1.0), ("m_new", 1.0), ("lim_c", 0.0), ("lim_r", 1.0), ("lim_g", 1.0)):
             v = getattr(self, name)
             setattr(self, name, (v + [neutral] * n)[:n])
+        # the buses that remain keep their voice limits, new ones have none
+        self.vc_N, self.vc_rho, self.vc_snap = (self.vc_N + [0] * n)[:n], (self.vc_rho + [f32(0)] * n)[:n], (self.vc_snap + [0] * n)[:n]
         self.n_buses = n
+        # the outputs of the buses that remain are kept
+        self.outputs = {} if self.fault == "set_buses_drops_outputs" else {b: o for b, o in self.outputs.items() if b < n}
 
     def set_bus(self, s, b):
         assert 0 <= b < self.n_buses
         self.bus[s] = b
+        if self.fault != "set_bus_old_limit":
+            self.vbus[s] = b
+        if self.fault == "set_bus_resets_set":
+            self.set_new[s] = 0
+        if self.fault == "bus_set_reaches_joiners" and b in self.bus_set:     # (the true joiner keeps its set)
+            self.set_new[s] = self.bus_set[b]
         if self.fault != "set_bus_old_send":
             self.send_bus[s] = b
         if self.fault != "set_bus_old_listener":
@@ -331,6 +418,287 @@ class ConferenceModel:
     def stage_gains(self, gains):
         self.staged = None if gains is None or len(gains) == 0 else np.asarray(gains, np.float32).copy()
 
+    # ------------------------------------------------------------------------------------------------- sets --
+    def add_hrtf_set(self, hrir):
+        """a further set on the engine's own directions -> its index"""
+        if len(self.models) >= MAX_HRTF_SETS:
+            raise Refused(JF_ERR_STATE, "the engine holds JF_MAX_HRTF_SETS sets")
+        m = self._make(hrir)
+        m.mode = self.gm.mode
+        self.models.append(m)
+        return len(self.models) - 1
+
+    def _set_apply(self, s, j, fade):
+        if not fade and self.set_prev[s] != j:
+            self.switches["snap"] += 1
+        self.set_new[s] = j
+        if not fade:
+            self.set_prev[s] = j
+
+    def set_hrtf(self, s, hrtf_set, fade=True):
+        if not 0 <= hrtf_set < len(self.models):
+            raise Refused(JF_ERR_ARG, "no such HRTF set")
+        self._set_apply(s, int(hrtf_set), fade)
+
+    def set_bus_hrtf(self, bus, hrtf_set, fade=True):
+        """every source that is on the bus NOW; a source that joins the bus later keeps its set"""
+        if not 0 <= bus < self.n_buses:
+            raise Refused(JF_ERR_ARG, "bad bus index")
+        if not 0 <= hrtf_set < len(self.models):
+            raise Refused(JF_ERR_ARG, "no such HRTF set")
+        self.bus_set[bus] = int(hrtf_set)
+        for s in range(self.S):
+            if self.bus[s] == bus:
+                self._set_apply(s, int(hrtf_set), fade)
+
+    def _set_block(self, s, q, ele, azi, coords, g_prev, g, j0, j1):
+        """one block of source s through the sets: the old set at g_prev, the new one at g (SetsModel's identity).  The models
+        the source is not on would add exact zeros and are skipped; the state (window, play position, old position) is q's"""
+        if j0 == j1:
+            return self.models[j1].source_block(q, ele, azi, coords, g_prev, g)
+        self.switches["fade"] += 1
+        old = model64.Source(self.N)
+        old.buf, old.count, old.old_ele, old.old_azi = q.buf, q.count, q.old_ele, q.old_azi
+        old.x[:] = q.x
+        a = self.models[j0].source_block(old, ele, azi, coords, g_prev, 0.0)
+        b = self.models[j1].source_block(q, ele, azi, coords, 0.0, g)
+        return a + b if j0 < j1 else b + a      # (ascending set index, as SetsModel adds its models)
+
+    # ------------------------------------------------------------------------------------------------ gates --
+    def set_gate(self, s, open, close=None, hold_blocks=0):
+        close = open if close is None else close
+        o, c = f32(open), f32(close)
+        if not (np.isfinite(o) and np.isfinite(c) and 0 <= c <= o <= f32(2.0 ** 24) and 0 <= int(hold_blocks) <= 1048576):
+            raise Refused(JF_ERR_ARG, "gate: 0 <= close <= open <= 2^24, hold within 0 .. 1048576 blocks")
+        self.gate_par[s] = (o, c, int(hold_blocks))      # the state is not touched
+        if self.fault == "set_gate_touches_state":
+            self.gate_state[s] = (0, 0)
+
+    def set_gates(self, open, close=None, hold_blocks=0):
+        self.set_gate(0, open, close, hold_blocks)       # (refused for all or for none)
+        for s in range(1, self.S):
+            self.set_gate(s, open, close, hold_blocks)
+
+    def set_input_meters(self, on=True):
+        self.input_meters = bool(on)
+
+    # ----------------------------------------------------------------------------------------------- limits --
+    def set_voices(self, bus, max_voices, release=0.0, fade=True):
+        rho = f32(release)
+        if not 0 <= bus < self.n_buses:
+            raise Refused(JF_ERR_ARG, "bad bus index")
+        if not (0 <= int(max_voices) <= 65536 and np.isfinite(rho) and 0 <= rho < 1):
+            raise Refused(JF_ERR_ARG, "voices: max_voices within 0 .. 65536, release within [0, 1)")
+        self.vc_N[bus], self.vc_rho[bus] = int(max_voices), rho
+        self.vc_snap[bus] = int(not fade and max_voices > 0)
+
+    def set_priority(self, s, priority):
+        if not 0 <= int(priority) <= 255:
+            raise Refused(JF_ERR_ARG, "priority must lie within 0 .. 255")
+        self.prio[s] = int(priority)
+
+    def _input_levels(self, K):
+        """(peak [K][S] float32 exact, sumsq [K][S] float64) of the B samples every block of the call appends to the sources'
+        inputs -- pre-fader; a follower has its root's level; an empty signal has level 0"""
+        B = self.B
+        peak, sumsq = np.zeros((K, self.S), np.float32), np.zeros((K, self.S))
+        for r in range(self.S):
+            q = self.src[r]
+            if self.root[r] != r or len(q.buf) == 0:
+                continue
+            x = q.buf[(q.count + np.arange(K * B)) % len(q.buf)].reshape(K, B)
+            peak[:, r], sumsq[:, r] = np.abs(x).max(axis=1), (x.astype(np.float64) ** 2).sum(axis=1)
+        for s in range(self.S):
+            peak[:, s], sumsq[:, s] = peak[:, self.root[s]], sumsq[:, self.root[s]]
+        return peak, sumsq
+
+    def _gains_heard(self, K, g_raw):
+        """The gains the gain stage sees in this call -- g_raw [K][S] through the gates (g_eff) and the limits (g_out) -- as
+        (g [K][S], g_prev [S], gate [K][S], keep [K][S]); the state of both moves on; `levels` and `heard` as the engine
+        reports them are left in self._reports"""
+        S, fault = self.S, self.fault
+        peak, sumsq = self._input_levels(K)
+        g_raw = np.asarray(g_raw, np.float32)
+        g_prev = np.array(self.gm.g_prev, np.float32)
+        gate = np.ones((K, S), np.int32)
+        g_eff_prev = g_prev.copy()
+        if fault == "gate_restarts_each_call":
+            self.gate_state = [(0, 0)] * S
+        new_state = list(self.gate_state)
+        for s in range(S):
+            o, c, h = self.gate_par[s]
+            if not o > 0:
+                continue
+            lv = peak[:, s]
+            if fault == "gate_post_fader":
+                lv = (lv * np.abs(g_raw[:, s])).astype(np.float32)
+            if not self.gate_state[s][0]:
+                g_eff_prev[s] = 0
+            gate[:, s], new_state[s] = gate_scan(lv, o, c, h, self.gate_state[s])
+        if fault == "follower_roots_gate":
+            for s in range(S):
+                r = self.root[s]
+                if r != s and self.gate_par[s][0] > 0:
+                    gate[:, s] = gate[:, r]
+                    g_eff_prev[s] = g_prev[s] if (self.gate_state[r][0] or not self.gate_par[r][0] > 0) else 0
+                    new_state[s] = new_state[r] if self.gate_par[r][0] > 0 else (1, 0)
+        self.gate_state = new_state
+        for s in range(S):
+            if self.gate_par[s][0] > 0:
+                self.gate_hist[s].extend(int(v) for v in gate[:, s])
+        g_eff = np.where(gate != 0, g_raw, f32(0)).astype(np.float32)
+        levels = np.stack([peak.T.astype(np.float64), sumsq.T, gate.T.astype(np.float64)], axis=2)       # [S][K][3]
+        keep, heard = np.ones((K, S), np.int32), None
+        g_out, g_out_prev = g_eff, g_eff_prev
+        if any(n > 0 for n in self.vc_N):
+            vbus = [min(b, self.n_buses - 1) for b in self.vbus]
+            g_rank, prio = g_eff, list(self.prio)
+            if fault == "muted_takes_a_place":
+                g_rank = np.ones_like(g_eff)
+            if fault == "always_takes_a_place":
+                prio = [min(p, ALWAYS - 1) for p in prio]
+            env_in = self.env_prev.copy()
+            _, g_out_prev, env, keep, (self.env_prev, self.heard_prev) = voice_rule(
+                peak, list(range(S)), vbus, prio, self.vc_N, self.vc_rho, g_rank, g_eff_prev, self.env_prev, self.heard_prev,
+                self.vc_snap)
+            for s in range(S):
+                if self.prio[s] >= ALWAYS:            # (always_takes_a_place: it took a place, and is heard as ever)
+                    keep[:, s] = 1
+                    g_out_prev[s] = g_eff_prev[s]
+                    self.heard_prev[s] = 1
+                if fault == "env_on_limited_bus_only" and self.vc_N[vbus[s]] == 0:
+                    self.env_prev[s] = env_in[s]
+            g_out = np.where(keep != 0, g_eff, f32(0)).astype(np.float32)
+            for b in range(self.n_buses):     # candidates of one limited bus with equal envelopes that do not play one input
+                mine = [s for s in range(S) if vbus[s] == b and self.prio[s] < ALWAYS]
+                for i, s in enumerate(mine if self.vc_N[b] > 0 else []):
+                    for t in mine[i + 1:]:
+                        if self.root[s] != self.root[t] and self.prio[s] == self.prio[t]:
+                            self.ties += int(((env[:, s] == env[:, t]) & (env[:, s] > 0) & (g_eff[:, s] != 0) & (g_eff[:, t] != 0)).sum())
+            if fault != "snap_not_consumed":
+                self.vc_snap = [0] * self.n_buses
+            heard = np.stack([env.T.astype(np.float64), keep.T.astype(np.float64)], axis=2)              # [S][K][2]
+            before = np.vstack([g_out_prev[None], g_out[:-1]])
+            eff_before = np.vstack([g_eff_prev[None], g_eff[:-1]])
+            for s in range(S):
+                if self.vc_N[vbus[s]] > 0:
+                    self.ramps["out"] += int(((before[:, s] != 0) & (g_out[:, s] == 0) & (g_eff[:, s] != 0)).sum())
+                    self.ramps["in"] += int(((before[:, s] == 0) & (g_out[:, s] != 0) & (eff_before[:, s] != 0)).sum())
+        raw_before = np.vstack([g_prev[None], g_raw[:-1]])
+        out_before = np.vstack([g_out_prev[None], g_out[:-1]])
+        self.skipped += int(((out_before == 0) & (g_out == 0) & ((raw_before != 0) | (g_raw != 0))).sum())
+        self._reports = (levels if self.input_meters else None, heard if self.input_meters else None)
+        return g_out, g_out_prev, gate, keep
+
+    # ---------------------------------------------------------------------------------------------- streams --
+    def _call_frames(self):
+        return max(self.max_k or 1, 1) * self.B
+
+    def set_stream(self, s, rate, capacity=None):
+        """a stream source is a live source whose input is stream_model.resample32, on the library's exported table, of X: the
+        pushes in order with the underruns' zeros where they fell"""
+        if rate == 0:
+            if self.stream[s] is not None:
+                self._swap_signal(s, np.zeros(0, np.float32), False)      # resident again, and silent
+            return
+        if not stream_model.accepted(rate):
+            raise Refused(JF_ERR_RANGE, "a rate that is not accepted")
+        L, M = stream_model.ratio(rate)
+        cap_min = -(-self._call_frames() * M // L) + stream_model.TAPS        # the most a call can need, plus 64 of history
+        if capacity is not None and capacity < cap_min:
+            raise Refused(JF_ERR_RANGE, "a capacity below the minimum")
+        self._detach_input(s)
+        self._swap_signal(s, np.zeros(0, np.float32), False)
+        self.stream[s] = {"rate": int(rate), "X": np.zeros(0, np.float32), "t": 0, "pushed": 0, "consumed": 0, "zeros_inserted": 0,
+                          "queued": 0, "cap": cap_min + int(rate) // 10 if capacity is None else int(capacity), "underruns": 0}
+
+    def push(self, s, frames):
+        z = self.stream[s]
+        if z is None:
+            raise Refused(JF_ERR_STATE, "not a stream source")
+        frames = np.asarray(frames, np.float32).reshape(-1)
+        z["X"] = np.concatenate([z["X"], frames])
+        z["pushed"] += len(frames)
+        z["queued"] += len(frames)
+
+    def stream_stats(self, s):
+        z = self.stream[s]
+        return {k: z[k] for k in ("pushed", "consumed", "zeros_inserted", "queued")}
+
+    def _stream_take(self, s, n):
+        """the n samples at 44 100 Hz the call appends to stream source s's input (float32, the library's order); the stream
+        moves on: an underrun's zeros become history"""
+        z = self.stream[s]
+        need = stream_model.need(z["rate"], z["t"], n)
+        have = min(z["queued"], need)
+        if have < need:
+            z["underruns"] += 1
+            self.stream_totals[s][0] += 1
+            self.stream_totals[s][1] += need - have
+            z["zeros_inserted"] += need - have
+            if self.fault != "underrun_zeros_not_history":
+                z["X"] = np.concatenate([z["X"], np.zeros(need - have, np.float32)])
+        y = stream_model.resample32(self.stream_table(z["rate"]), z["rate"], z["X"], z["t"], n)
+        raw = np.zeros(n, np.float32)                 # (fault follower_hears_raw_packets: the frames as they were pushed)
+        i0 = int(stream_model.index(z["t"], *stream_model.ratio(z["rate"])))
+        seg = z["X"][max(i0, 0):max(i0, 0) + n]
+        raw[:len(seg)] = seg
+        z["consumed"] += have
+        z["queued"] -= have
+        z["t"] += n
+        return y, raw
+
+    # ---------------------------------------------------------------------------------------------- outputs --
+    def set_output(self, bus, rate, capacity=None):
+        """the bus's mastered mix once more at `rate`: on a bus that has one it starts over; 0 takes it away"""
+        if not 0 <= bus < self.n_buses:
+            raise Refused(JF_ERR_ARG, "bad bus index")
+        if rate == 0:
+            self.outputs.pop(bus, None)
+            return
+        if not output_model.accepted(rate):
+            raise Refused(JF_ERR_RANGE, "a rate that is not accepted")
+        L, M, _ = output_model.ratio(rate)
+        cap_min = output_model.produced(self._call_frames(), L, M) + 1
+        if capacity is not None and capacity < cap_min:
+            raise Refused(JF_ERR_ARG, "a capacity below the minimum")
+        self.outputs[bus] = {"rate": int(rate), "blocks": [], "visible": 0, "pulled": 0, "pulls": 0,
+                             "cap": cap_min + int(rate) // 10 if capacity is None else int(capacity)}
+
+    def output_ready(self, bus):
+        o = self.outputs[bus]
+        L, M, _ = output_model.ratio(o["rate"])
+        return output_model.produced(o["visible"], L, M) - o["pulled"]
+
+    def output_queued_after(self, bus, blocks):
+        """the unpulled frames there would be after a call of `blocks` more blocks (the generator keeps clear of an overrun)"""
+        o = self.outputs[bus]
+        L, M, _ = output_model.ratio(o["rate"])
+        return output_model.produced((len(o["blocks"]) + blocks) * self.B, L, M) - o["pulled"]
+
+    def pull(self, bus, n):
+        """-> up to n frames [m][2] float64: output_model.resample64 of the model's own mastered blocks since the output was set"""
+        if bus not in self.outputs:
+            raise Refused(JF_ERR_STATE, "the bus has no output")
+        o = self.outputs[bus]
+        m = max(0, min(int(n), self.output_ready(bus)))
+        x = np.concatenate(o["blocks"]).reshape(-1, 2) if o["blocks"] else np.zeros((0, 2))
+        y = output_model.resample64(o["rate"], x, o["pulled"], m)
+        o["pulled"] += m
+        o["pulls"] += 1
+        self.pull_counts[bus] = self.pull_counts.get(bus, 0) + 1
+        return y
+
+    def _outputs_take(self, blocks, late):
+        """blocks {bus: [K][2B]} of a rendered call go into the outputs; late: the callback form hands a block out (and makes
+        its frames pullable) one call after the one that queued it"""
+        for b, o in self.outputs.items():
+            o["visible"] = len(o["blocks"]) * self.B if late else o["visible"]
+            if blocks is not None:
+                o["blocks"].extend(np.array(x) for x in blocks[b])
+            if not late:
+                o["visible"] = len(o["blocks"]) * self.B
+
     # ----------------------------------------------------------------------------------------------- masters --
     def set_master(self, bus, gain, fade=True):
         self.m_new[bus] = float(f32(gain))
@@ -347,7 +715,8 @@ class ConferenceModel:
         self.meters_on = bool(on)
 
     def set_mode(self, mode):
-        self.gm.mode = (self.gm.mode & ~1) | (int(mode) & 1)
+        for m in self.models:
+            m.mode = (m.mode & ~1) | (int(mode) & 1)
 
     def set_pause(self, p):
         self.paused = bool(p)
@@ -364,28 +733,50 @@ class ConferenceModel:
             for m in self.members(r):
                 self.src[m].buf = np.zeros(0, np.float32) if fed is None else fed[j]
                 self.src[m].count = 0
+        streams = [s for s in range(S) if self.stream[s] is not None]
+        for r in streams:               # a stream source takes no row of `inp`: its samples are its queue's, resampled
+            y, raw = self._stream_take(r, K * B)
+            for m in self.members(r):
+                self.src[m].buf = raw if m != r and self.fault == "follower_hears_raw_packets" else y
+                self.src[m].count = 0
         dry = np.zeros((nb, K, 2 * B))
         send = np.zeros((nb, K * B))
         n_on = np.zeros((nb, K), np.int64)
         frac = (np.arange(B) + 1.0) / B
         if self.fault == "limiter_restarts_each_call":
             self.lim_g = [1.0] * nb
+        # the gains the gain stage would have applied, then what the gates and the limits leave of them
+        g_raw = np.array([[gm.g[s] if gains is None else f32(gains[k][s]) for s in range(S)] for k in range(K)], np.float32)
+        g_out, g_out_prev, gate, keep = self._gains_heard(K, g_raw)
+        set_before = list(self.set_prev)
         for k in range(K):
             for s, q in enumerate(self.src):
                 p = records[k][s]
                 ele, azi, coords = f32(p[0]), f32(p[1]), (f32(p[2]), f32(p[3]), f32(p[4]))
-                g = gm.g[s] if gains is None else f32(gains[k][s])
-                blk = gm.source_block(q, ele, azi, coords, gm.g_prev[s], g)
-                gm.g_prev[s] = g
+                g = f32(g_raw[k, s])
+                gp, gn = f32(g_out_prev[s] if k == 0 else g_out[k - 1, s]), f32(g_out[k, s])
+                again = self.fault == "switch_in_every_run" and self.max_k and k % self.max_k == 0
+                j0 = set_before[s] if k == 0 or again else self.set_new[s]     # a set switches in the call's first block only
+                frozen = q.x.copy() if self.fault == "skipped_block_freezes_window" and gp == 0 and gn == 0 and g != 0 else None
+                blk = self._set_block(s, q, ele, azi, coords, gp, gn, j0, self.set_new[s])
+                if frozen is not None:
+                    q.x[:] = frozen
                 dry[self.bus[s], k] += blk
                 n_on[self.bus[s], k] += 1
                 lp, ln = self.send_prev[s], self.send_new[s]
-                if self.room is not None and (lp != 0.0 or ln != 0.0):
+                if self.room is not None and (lp != 0.0 or ln != 0.0):      # pre-fader, and neither gated nor limited
                     l = lp + (ln - lp) * frac if k == 0 else np.full(B, ln)
                     if self.fault == "send_post_fader":
                         l = l * float(g)
+                    if self.fault == "gate_gates_send":
+                        l = l * float(gate[k, s])
+                    if self.fault == "limit_limits_send":
+                        l = l * float(keep[k, s])
                     send[self.send_bus[s], k * B:(k + 1) * B] += l * q.x[N - 2 * B:N - B]
-        for r in live:
+        for s in range(S):
+            gm.g_prev[s] = f32(g_raw[K - 1, s])
+        self.set_prev = list(self.set_new)
+        for r in live + streams:
             for m in self.members(r):
                 self.src[m].buf, self.src[m].count = np.zeros(0, np.float32), 0
         if gains is not None:
@@ -400,19 +791,26 @@ class ConferenceModel:
             pre = dry + self._wet(send)
             self.send_prev = list(self.send_new)
         out = np.zeros_like(pre)
+        tapped = {b: [None] * K for b in self.outputs}      # (fault output_misses_wet: what such an output would read)
         infos = [[None] * K for _ in range(nb)]
         for b in range(nb):
             for k in range(K):
                 ramp = k == 0 or self.fault == "master_ramp_every_block"
                 out[b, k], i = master_block64(pre[b, k], B, self.m_prev[b], self.m_new[b], ramp, self.lim_c[b], self.lim_r[b],
                                               self.lim_g[b])
+                if self.fault == "output_misses_wet" and b in self.outputs:
+                    tapped[b][k] = master_block64(dry[b, k], B, self.m_prev[b], self.m_new[b], ramp, self.lim_c[b], self.lim_r[b],
+                                                  self.lim_g[b])[0]
                 self.lim_g[b] = i["g"]
                 self.limiter_blocks["attack"] += i["attack"]
                 self.limiter_blocks["release"] += i["release"]
                 infos[b][k] = i
         self.m_prev = list(self.m_new)
+        # an output reads the mastered mix, wet part included: exactly the samples the call hands out
+        self._outputs_take({b: pre[b] if self.fault == "output_pre_master" else tapped[b] if self.fault == "output_misses_wet"
+                            else out[b] for b in self.outputs}, self.late)
         self.last = {"pre": pre, "n_on": n_on, "infos": infos, "P": 0 if self.room is None else -(-self.room[3] // B),
-                     "quiet": quiet, "paused": False}
+                     "quiet": quiet, "paused": False, "levels": self._reports[0], "heard": self._reports[1]}
         return out
 
     def _paused_call(self):
@@ -423,6 +821,24 @@ class ConferenceModel:
             self.send_prev = list(self.send_new)
         if self.fault == "pause_advances_limiter":
             self.lim_g = [min(1.0, g + r) if c > 0 else g for g, r, c in zip(self.lim_g, self.lim_r, self.lim_c)]
+        # a paused call latches nothing and advances nothing: no gate, no envelope, no set
+        if self.fault == "pause_advances_gate":      # (a block of silence through every gate)
+            for s in range(self.S):
+                o, c, h = self.gate_par[s]
+                if o > 0:
+                    self.gate_state[s] = gate_scan([0.0], o, c, h, self.gate_state[s])[1]
+        if self.fault == "pause_advances_env" and any(n > 0 for n in self.vc_N):
+            for s in range(self.S):
+                self.env_prev[s] = f32(self.env_prev[s] * self.vc_rho[min(self.vbus[s], self.n_buses - 1)])
+        if self.fault == "paused_call_takes_switch":
+            self.set_prev = list(self.set_new)
+        # ... consumes nothing of a stream and appends nothing to an output
+        if self.fault == "pause_consumes_stream":
+            for s in range(self.S):
+                if self.stream[s] is not None:
+                    self._stream_take(s, self.B)
+        self._outputs_take({b: np.zeros((1, 2 * self.B)) for b in self.outputs} if self.fault == "paused_silence_appended" else None,
+                           self.late)
         self.last = {"paused": True}
         return np.zeros((self.n_buses, 1, 2 * self.B))
 
@@ -432,7 +848,18 @@ class ConferenceModel:
             raise Refused(JF_ERR_STATE, "the staged gain trajectory has another number of blocks")
         return gains
 
-    def process_block(self, inp=None):
+    def process_block(self, inp=None, late=False):
+        """late: the callback form -- the block is handed out, and its output frames become pullable, one call later"""
+        self.late = late
+        try:
+            return self._process_block(inp)
+        finally:
+            self.late = False
+
+    def collect_block(self):
+        self._outputs_take(None, False)
+
+    def _process_block(self, inp=None):
         if self.paused:
             return self._paused_call()
         rec = self._standing_records()
@@ -482,6 +909,14 @@ class ConferenceModel:
         self.objects, self.pose = objects[-1].copy(), poses[-1].copy()
         return out
 
+    def device_form(self, call="batch_run"):
+        """jf_batch_upload_* and jf_batch_run are refused with a stream or a live source present, jf_batch_upload_positions and
+        jf_batch_run with an output"""
+        if any(z is not None for z in self.stream) or any(self.live) or \
+                (self.outputs and call in ("batch_run", "upload_positions")):
+            raise Refused(JF_ERR_STATE, "the device-resident form takes no input and hands nothing out to pull")
+
     # jf_batch_upload_* + jf_batch_run: a window of an uploaded trajectory; the sources, listeners and objects do not move
     def run_records(self, records):
+        self.device_form()
         return self._render(np.asarray(records, np.float32), None)

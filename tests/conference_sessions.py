@@ -6,6 +6,13 @@ An op is a tuple (name, *args): `name` is the method of jf.Engine AND of Confere
 model between ops -- which calls the engine will refuse, the running peak of a bus for a limiter's ceiling, whether a pose draw
 lands on a half degree -- and never the engine, so a session is the same list of ops with and without a GPU.
 
+Sessions 1 to 6 are frozen: tests/test_conference_model.py holds digest() of their op lists.  Sessions 7 and 8 (NEW) add HRTF
+sets, voice gates and voice limits through code paths of their own (ops_new, new_setter, new_motif), so nothing they draw
+moves the random stream of the first six.  Sessions 9 and 10 (STREAMS) add stream sources and bus outputs the same way
+(ops_streams, stream_setter, stream_motif): pushes of 1 to 3 blocks' need ahead of every call -- now and then too little, so that
+an underrun falls, now and then a surplus inside the capacity --, pulls of 0 frames, a packet or everything ready after it, never
+an overrun.  A pull's result is held to pull_bound, THE OUTPUT BOUND.
+
 THE BOUND of bus b, block k (nothing new, nothing measured from the code under test): with n sources on the bus at that block
 and a room of P partitions,  pre = (sum_tol(2e-7, n) + (wet_tol(P) if a room is set else 0)) max(1, |want|_inf), want the
 model's dry + wet;  limiter off: pre max(m) over the block's master ramp;  limiter on: twice that (test_gpu_conference_sessions).
@@ -30,14 +37,43 @@ SESSIONS = {
     4: dict(seed=4, B=256, L=1024, S=5, buses=2, taps=256, steps=80, hrir="long", note="PAD_LEN 2048: followers as aliases"),
     5: dict(seed=5, B=128, L=512, S=6, buses=2, taps=0, steps=80, hrir="cloud", note="a set on arbitrary directions"),
     6: dict(seed=6, B=256, L=512, S=8, buses=2, taps=0, steps=80, hrir="kemar", note="upload + batch_run windows"),
+    # voice gates, voice limits and HRTF sets (KEMAR + 2 sets of sets_model.make_sets) on top of everything above
+    7: dict(seed=7, B=64, L=512, S=8, buses=2, taps=300, steps=80, hrir="kemar", sets=2, note="group pinned to 2, then free"),
+    8: dict(seed=8, B=256, L=512, S=8, buses=2, taps=0, steps=80, hrir="kemar", sets=2, note="upload + batch_run windows"),
+    # stream sources and bus outputs: packets in at the codec's rate, packets out
+    9: dict(seed=9, B=128, L=1024, S=5, buses=2, taps=256, steps=80, hrir="long", streams=(48000, 16000), outputs=(48000, 8000),
+            note="PAD_LEN 2048; two streams and a live source, per-block and batch calls"),
+    10: dict(seed=10, B=64, L=512, S=6, buses=3, taps=0, steps=80, hrir="cloud", sets=1, streams=(22050, 44100),
+             outputs=(47900, 44100), note="cloud + 1 set; callback form in the last phase"),
 }
-FEATURES = {     # fault -> the feature a session must use for the fault to show
-    "send_post_fader": "room", "set_bus_old_send": "room", "pause_advances_send": "room", "set_room_keeps_tail": "room",
+NEW = (7, 8)          # the sessions with gates, limits and sets
+STREAMS = (9, 10)     # the sessions with stream sources and bus outputs (and gates and limits on them)
+_STREAMF = ("pause_consumes_stream", "reset_keeps_stream_history", "underrun_zeros_not_history", "follower_hears_raw_packets")
+OUTPUT_FAULTS = ("output_pre_master", "output_misses_wet", "paused_silence_appended", "set_buses_drops_outputs")
+WINDOWS = (6, 8)      # ... in session 6's form: uploads and batch_run windows
+_GATES = ("gate_post_fader", "follower_roots_gate", "set_gate_touches_state", "signal_keeps_gate_open", "pause_advances_gate",
+          "gate_restarts_each_call", "skipped_block_freezes_window")
+_LIMITS = ("env_on_limited_bus_only", "set_bus_old_limit", "signal_resets_heard", "muted_takes_a_place", "always_takes_a_place",
+           "snap_not_consumed", "pause_advances_env")
+_SETS = ("bus_set_reaches_joiners", "set_bus_resets_set", "paused_call_takes_switch")
+FEATURES = {     # fault -> the features a session must use for the fault to show
+    "send_post_fader": ("room",), "set_bus_old_send": ("room",), "pause_advances_send": ("room",), "set_room_keeps_tail": ("room",),
+    "gate_gates_send": ("gates", "room"), "limit_limits_send": ("limits", "room"),
+    "switch_in_every_run": ("sets", "long calls"),      # (a jf_batch_run is never longer than max_batch_blocks)
+    **{f: ("streams",) for f in _STREAMF}, **{f: ("outputs",) for f in OUTPUT_FAULTS}, "output_misses_wet": ("outputs", "room"),
+    **{f: ("gates",) for f in _GATES}, **{f: ("limits",) for f in _LIMITS}, **{f: ("sets",) for f in _SETS},
 }
+
+
+def features(n):
+    c = SESSIONS[n]
+    return ({"room"} if c["taps"] else set()) | ({"gates", "limits"} if n in NEW + STREAMS else set()) | \
+           ({"sets"} if c.get("sets") else set()) | \
+           ({"long calls"} if n not in WINDOWS else set()) | ({"streams", "outputs"} if n in STREAMS else set())
 
 
 def uses(n, fault):
-    return FEATURES.get(fault) != "room" or SESSIONS[n]["taps"] > 0
+    return set(FEATURES.get(fault, ())) <= features(n)
 
 
 def long_hrir(hrir, taps, seed=11):
@@ -85,7 +121,19 @@ def hrir_set(kind, hrir, jf=None):
 def make_model(n, hrir, jf=None, fault=None):
     c = SESSIONS[n]
     table, cloud = hrir_set(c["hrir"], hrir, jf)
-    return ConferenceModel(c["B"], c["L"], c["S"], table, cloud=cloud, fault=fault)
+    model = ConferenceModel(c["B"], c["L"], c["S"], table, cloud=cloud, fault=fault, max_batch_blocks=MAX_K)
+    if jf is not None:      # the library's exported tables (tests/test_stream.py holds them to stream_model.table64)
+        model.stream_table = lambda rate: _sets.setdefault(("stream table", rate), jf.stream_table(rate))
+    return model
+
+
+def further_sets(n, hrir, jf=None):
+    """the sets a new session adds to its engine (the ops carry them): sets_model.make_sets of the session's own table"""
+    key = ("sets", SESSIONS[n]["hrir"], SESSIONS[n].get("sets", 0))
+    if key not in _sets:
+        import sets_model
+        _sets[key] = sets_model.make_sets(hrir_set(SESSIONS[n]["hrir"], hrir, jf)[0], 1 + key[2])[1:]
+    return _sets[key]
 
 
 def make_engine(n, hrir, jf):
@@ -109,16 +157,22 @@ def bounds(last, nb, K):
 
 # --------------------------------------------------------------------------------------------------- the generator --
 class Generator:
-    def __init__(self, n, model, castanets):
+    def __init__(self, n, model, castanets, sets=(), redraw=0):
         self.n, self.c, self.m, self.x = n, SESSIONS[n], model, castanets
-        self.rng = np.random.default_rng(7000 + self.c["seed"])
+        self.new, self.windows, self.sets = n in NEW, n in WINDOWS, list(sets)
+        self.pulled = []
+        self.force_long = False        # a motif asks for a batch call of more than MAX_K blocks
+        if n in STREAMS:
+            self.GATED = len(self.c["streams"])      # the stream sources carry the gates
+        # (redraw: the session's signals drawn again, because two candidates of one bus tied in the draw before: generate)
+        self.rng = np.random.default_rng(7000 + self.c["seed"] if not redraw else [7000 + self.c["seed"], redraw])
         self.draws = self.redraws = 0
         self.peak = {}                 # bus -> the peak of its last audible block ahead of the limiter
         self.traj = None               # session 6: the uploaded trajectory's length
         self.nxt = 0
         self.callback = False          # session 3's last phase
         self.room_seed = 0
-        self.run = {2: 2, 6: 4}.get(n, 1)       # sources are first put on the buses in aligned runs of this many
+        self.run = {2: 2, 6: 4, 7: 2, 8: 4}.get(n, 1)      # sources are first put on the buses in aligned runs of this many
         self.amp = 1.4 if self.c["hrir"] == "cloud" else 0.8     # (the castanets peak at 0.66)
         self.stage = False             # a gain trajectory goes ahead of the next batch call
         self.pending = None            # ... the op that stages it
@@ -284,7 +338,7 @@ class Generator:
             if cb and m.root[s] != s:     # (on a follower the call detaches first, which a block in flight refuses)
                 s = m.root[s]
             yield ("set_signal", s, self.signal())
-        elif op < 66 and not cb and self.n != 6:
+        elif op < 66 and not cb and not self.windows:
             yield ("set_live", s, bool(rng.integers(0, 2)))
         elif op < 69:
             yield ("reset", s)
@@ -324,11 +378,11 @@ class Generator:
             if k == 0:
                 yield ("knob", "set_rt_max_sources", int(rng.choice([0, 2, 8192])))
             elif k == 1:
-                groups = {1: [1, 0], 2: [2, 4, S], 6: [2, 2, 4]}.get(self.n, [1, S, 0])
+                groups = {1: [1, 0], 2: [2, 4, S], 6: [2, 2, 4], 7: [2, 0, S], 8: [2, 2, 4]}.get(self.n, [1, S, 0])
                 yield ("knob", "set_source_group", int(rng.choice(groups)))
             elif k == 2 and c["hrir"] == "kemar":
                 yield ("knob", "set_interp_table", int(rng.integers(0, 3)))
-            elif self.n != 6:
+            elif not self.windows:
                 yield ("knob", "set_prep_ahead", bool(rng.integers(0, 2)))
 
     def _elevation_ok(self, s):
@@ -367,6 +421,12 @@ class Generator:
         S = m.S
         loud = [x for x in range(S) if len(m.src[m.root[x]].buf) >= 300 and m.gm.g[x] != 0 and self._elevation_ok(x)]
         s = int(rng.choice(loud)) if loud else int(rng.integers(0, S))
+        if self.new or self.n in STREAMS:        # the motif's source is heard whatever the gates and limits do: no gate, and a place of its own
+            heard = [x for x in loud if x >= self.GATED]
+            s = int(rng.choice(heard)) if heard else int(rng.integers(self.GATED, S))
+            if not heard:
+                yield ("set_signal", s, self.speech())
+            yield ("set_priority", s, 255)
         if m.paused:
             yield ("set_pause", False)
         if which == 0:      # a pause over a level, a send and a master change; the limiter mid-release
@@ -449,6 +509,8 @@ class Generator:
             self.force_block = True
         elif which == 4:    # a master change ahead of a batch call; a limiter that attacks and releases over calls
             b = int(rng.integers(0, m.n_buses))
+            if self.n in STREAMS:       # (few sources: the fullest bus, so that the ramp is heard)
+                b = int(np.argmax(np.bincount(m.bus, minlength=m.n_buses)))
             yield ("set_master", b, float(np.float32(rng.uniform(0.4, 0.6) if m.m_new[b] > 0.65 else rng.uniform(0.8, 1.0))), True)
             if self.peak.get(b, 0.0) > 1e-3:
                 yield ("set_limiter", b, float(np.float32(rng.uniform(0.5, 0.8) * self.peak[b])), 0.125)
@@ -484,8 +546,12 @@ class Generator:
         if self.force_block:
             self.force_block = False
             return ("process_block", self.inp(1))
-        if self.n == 6:
+        if self.windows:
             return None                                      # (ops(): upload + batch_run)
+        if self.force_long:                                  # more than max_batch_blocks: several runs of one stream
+            self.force_long = False
+            K = MAX_K + int(rng.integers(1, 5))
+            return ("process_batch", self.records(K), self.inp(K))
         if self.force_batch:
             self.force_batch, u, K = False, max(u, 0.42), max(K, 3)
         if self.force_objects:
@@ -539,6 +605,12 @@ class Generator:
         """the session: ("audio" ops render; everything else is a setter)"""
         c, m, rng = self.c, self.m, self.rng
         S = m.S
+        if self.new:
+            yield from self.ops_new()
+            return
+        if self.n in STREAMS:
+            yield from self.ops_streams()
+            return
         for s in range(S):
             yield ("set_signal", s, self.signal(2) if s < 3 else self.signal())
             yield ("set_spherical", s, 0.0, float(40 * s), 1.0)
@@ -590,6 +662,606 @@ class Generator:
         if self.callback:
             yield ("collect_block",)
 
+    # ---- sessions 7 and 8: gates, limits and sets on top of the above (their own code paths: sessions 1 to 6 draw nothing here) --
+    GATED = 6            # sources 0 .. 5 carry a gate for the whole session, the others never
+    CYCLE = (7, 0, 8, 9, 4, 10, 11, 1, 12, 13, 2, 3, 5, 6)
+
+    def speech(self):
+        """a talker: the castanets over a noise floor, loud for 2 to 5 blocks and 50 times quieter for 2 to 6 in turn, at a level
+        of its own; the loop is no multiple of B.  A loud block peaks above 0.07 level, a quiet one below 0.013 level."""
+        rng, B = self.rng, self.c["B"]
+        n = int(rng.integers(16, 48)) * B + int(rng.integers(1, B))
+        a = int(rng.integers(0, len(self.x) - n))
+        env = np.zeros(0)
+        while len(env) < n:
+            env = np.concatenate([env, np.ones(int(rng.integers(2, 6)) * B), np.full(int(rng.integers(2, 7)) * B, 0.02)])
+        level = float(rng.uniform(0.4, 1.0))
+        return ((self.amp * self.x[a:a + n] + 0.08 * rng.uniform(-1, 1, n)) * env[:n] * level).astype(np.float32)
+
+    def talk(self, loud, quiet, level, quiet_first=False):
+        """noise in whole blocks: `loud` blocks at `level`, `quiet` blocks 100 times quieter (a motif's script)"""
+        B = self.c["B"]
+        a = self.rng.uniform(-1, 1, loud * B) * level
+        q = self.rng.uniform(-1, 1, quiet * B) * 0.01 * level
+        return np.concatenate([q, a] if quiet_first else [a, q]).astype(np.float32)
+
+    def thresholds(self, s):
+        """(open, close, hold) from the model's own block peaks of the source's input: `open` in the widest gap between its
+        quiet and its loud blocks, `close` at or below it"""
+        m, rng, B = self.m, self.rng, self.c["B"]
+        q = m.src[m.root[s]]
+        close, hold = float(rng.choice([1.0, 0.5, 0.25])), int(rng.choice([0, 0, 1, 2, 3]))
+        n = len(q.buf)
+        p = np.zeros(0)
+        if n and not m.live[m.root[s]]:
+            k = min(96, 2 * (n // B) + 2)
+            p = np.sort(np.abs(q.buf[(q.count + np.arange(k * B)) % n]).reshape(k, B).max(axis=1).astype(np.float64))
+            p = p[p > 0]
+        if len(p) < 2:
+            return 0.05, float(np.float32(0.05 * close)), hold
+        i = int(np.argmax(p[1:] / p[:-1]))
+        o = float(np.float32(np.sqrt(p[i] * p[i + 1])))
+        return o, float(np.float32(o * close)), hold
+
+    def to_bus(self, s, b, whole=True):
+        """source s to bus b -- with the other source of its aligned pair (whole), so that a pinned group of two still holds"""
+        for x in ((s - s % 2, s - s % 2 + 1) if whole and self.run > 1 else (s,)):
+            def apply(x=x):
+                self.m.set_bus(x, b)
+                return ("set_bus", x, b)
+            yield self.settle(apply)
+
+    def heal(self):
+        """the pairs that single moves have split are joined again (a pinned group falls back to 1 while one is split)"""
+        for a in range(0, self.m.S - 1, 2):
+            if self.m.bus[a] != self.m.bus[a + 1]:
+                yield from self.to_bus(a + 1, self.m.bus[a], whole=False)
+
+    def new_setter(self):
+        m, rng = self.m, self.rng
+        S, nb, n_sets = m.S, m.n_buses, len(m.models)
+        s, b = int(rng.integers(0, S)), int(rng.integers(0, nb))
+        u = int(rng.integers(0, 100))
+        if u < 20:
+            s = int(rng.integers(0, self.GATED))
+            yield ("set_gate", s) + self.thresholds(s)
+        elif u < 27:
+            yield ("set_input_meters", bool(rng.random() < 0.85))
+        elif u < 45:
+            yield ("set_voices", b, int(rng.choice([0, 1, 2, 2, 3])), float(rng.choice([0.0, 0.5])), bool(rng.random() < 0.7))
+        elif u < 55:
+            yield ("set_priority", s, int(rng.choice([0, 0, 1, 2, 255])))
+        elif u < 72:
+            yield ("set_hrtf", s, int(rng.integers(0, n_sets)), bool(rng.random() < 0.75))
+        elif u < 80:
+            yield ("set_bus_hrtf", b, int(rng.integers(0, n_sets)), bool(rng.random() < 0.75))
+        elif u < 92:
+            if m.root[s] != s and self.windows:
+                s = m.root[s]
+            yield ("set_signal", s, self.speech())
+            if s < self.GATED:
+                yield ("set_gate", s) + self.thresholds(s)
+        else:         # what the header refuses, with nothing changed
+            yield [("set_hrtf", s, n_sets, True), ("set_bus_hrtf", nb, 0, True), ("set_voices", b, 2, 1.0, True),
+                   ("set_voices", b, 65537, 0.0, True), ("set_gate", s, 0.1, 0.2, 0), ("set_gate", s, -0.1, -0.1, 0),
+                   ("set_priority", s, 256)][int(rng.integers(0, 7))]
+
+    def new_motif(self, which):
+        """the orders the clauses about gates, limits and sets are about"""
+        m, rng = self.m, self.rng
+        S, nb = m.S, m.n_buses
+        if which < 7:
+            yield from self.motif(which)
+            return
+        if m.paused:
+            yield ("set_pause", False)
+        free = [x for x in range(self.GATED, S)]                      # the sources without a gate
+        if which == 7:      # a pause across an open gate in its hold, on a limited bus mid-release; a switch latched by no paused call
+            s = int(rng.integers(0, self.GATED))
+            t = int(rng.choice([x for x in free if x != s]))
+            b = m.bus[s]
+            yield ("set_signal", s, self.talk(3, 9, 0.5))
+            yield ("set_signal", t, self.talk(6, 0, 0.1))
+            if m.bus[t] != b:
+                yield from self.to_bus(t, b)
+            yield ("set_spherical", s, 10.0, 60.0, 0.6)
+            yield ("set_spherical", t, 0.0, 300.0, 0.6)
+            yield ("set_gate", s, 0.25, 0.25, 3)
+            yield ("set_voices", b, 1, 0.5, True)
+            yield ("set_priority", s, 9)
+            yield ("set_priority", t, 9)
+            for _ in range(4):                     # three loud blocks, then the first quiet one: the hold begins
+                self.force_block = True
+                yield ("audio",)
+            yield ("set_gate", s, 0.25, 0.25, 3)   # set again: the state is not touched
+            yield ("set_pause", True)
+            yield ("set_hrtf", s, (m.set_new[s] + 1) % len(m.models), True)
+            yield ("audio",)
+            yield ("audio",)
+            yield ("set_pause", False)
+            for _ in range(2):
+                self.force_block = True
+                yield ("audio",)
+            yield ("set_voices", b, 0, 0.0, True)
+            yield ("set_signal", s, self.talk(3, 4, 0.5, quiet_first=True))     # a new start: closed until a level opens it
+            for _ in range(2):
+                self.force_block = True
+                yield ("audio",)
+            self.force_block = False
+            yield ("set_priority", s, 0)
+            yield ("set_priority", t, 0)
+            yield ("set_signal", s, self.speech())
+            yield ("set_gate", s) + self.thresholds(s)
+        elif which == 8:    # a share group whose root is closed while a follower on another bus, at a lower threshold, is open and sends
+            single = [x for x in range(self.GATED) if m.root[x] == x and not any(m.root[y] == x for y in range(S) if y != x)]
+            if len(single) < 2 or nb < 2:
+                return
+            r, f = (int(x) for x in rng.choice(single, 2, replace=False))
+            if m.live[r]:
+                yield ("set_live", r, False)
+            yield ("set_signal", r, self.speech())
+            yield ("share_input", f, r)
+            yield from self.to_bus(f, (m.bus[r] + 1) % nb)
+            yield ("set_spherical", f, 20.0, 120.0, 0.5)
+            yield ("set_gate", r, 4.0, 4.0, 0)
+            yield ("set_gate", f) + self.thresholds(f)
+            yield ("set_gain", f, 0.1, False)          # (the gate listens ahead of the fader: the level it sees is the input's)
+            yield ("set_priority", f, 9)
+            if m.room is not None:
+                yield ("set_send", f, 0.5)
+            self.force_batch = True
+            yield ("audio",)
+            self.force_batch = True
+            yield ("audio",)
+            self.force_batch = False
+            yield ("set_gate", r) + self.thresholds(r)
+            yield ("set_priority", f, 0)
+        elif which == 9 and nb > 1:     # a quiet source carried to a limited bus with rho = 0.5 right after a loud block
+            s, t = int(rng.choice(free)), int(rng.integers(0, self.GATED))     # (of two pairs: they meet on b1 only)
+            b0 = m.bus[s]
+            b1 = (b0 + 1) % nb
+            yield ("set_voices", b0, 0, 0.0, True)
+            yield ("set_voices", b1, 1, 0.5, True)
+            yield ("set_signal", s, self.talk(2, 9, 0.6))
+            yield ("set_signal", t, self.talk(6, 0, 0.15))
+            yield ("set_gate", t, 0.01, 0.01, 0)       # (open on every block of this signal)
+            if m.bus[t] != b1:
+                yield from self.to_bus(t, b1)
+            yield ("set_spherical", s, 0.0, 90.0, 0.5)
+            yield ("set_spherical", t, 0.0, 270.0, 0.5)
+            yield ("set_priority", s, 9)
+            yield ("set_priority", t, 9)
+            for _ in range(2):
+                self.force_block = True
+                yield ("audio",)
+            yield from self.to_bus(s, b1)
+            for _ in range(2):
+                self.force_block = True
+                yield ("audio",)
+            self.force_block = False
+            yield ("set_priority", s, 0)
+            yield ("set_priority", t, 0)
+            yield ("set_signal", t, self.speech())
+            yield ("set_gate", t) + self.thresholds(t)
+        elif which == 10:   # jf_source_set_signal on a loser; a muted source and an ALWAYS source take no place
+            l, w = (int(x) for x in rng.permutation(free)[:2])       # the two ungated sources: w wins the one place, l loses
+            if m.bus[l] != m.bus[w]:
+                yield from (self.heal() if self.run > 1 else self.to_bus(w, m.bus[l]))
+            b = m.bus[l]
+            yield ("set_signal", w, self.talk(6, 0, 0.5))
+            yield ("set_signal", l, self.talk(6, 0, 0.2))
+            yield ("set_priority", w, 9)
+            yield ("set_priority", l, 0)
+            yield ("set_voices", b, 1, 0.0, True)
+            for _ in range(2):
+                self.force_block = True
+                yield ("audio",)
+            self.force_block = False
+            if m.bus[l] != b or m.heard_prev[l] != 0:
+                return
+            yield ("set_signal", l, self.talk(6, 0, 0.7))
+            yield ("set_spherical", l, 0.0, 45.0, 0.5)
+            yield ("set_priority", l, 9)
+            self.force_block = True
+            yield ("audio",)
+            yield ("set_mute", l, True, True)
+            yield ("audio",)
+            self.force_block = True
+            yield ("audio",)
+            yield ("set_mute", l, False, True)
+            yield ("set_priority", l, 255)
+            self.force_block = True
+            yield ("audio",)
+            self.force_block = False
+            yield ("set_priority", l, 0)
+            yield ("set_priority", w, 0)
+        elif which == 11:   # a limit set at once: the flag is consumed by the first run
+            b = int(rng.integers(0, nb))
+            if self.n in STREAMS:       # few sources per bus: the fullest bus, and one place on it
+                b = int(np.argmax(np.bincount(m.bus, minlength=nb)))
+            yield ("set_voices", b, 0, 0.0, True)
+            yield ("audio",)
+            yield ("set_voices", b, 1 if self.n in STREAMS else int(rng.integers(1, 3)), 0.5, False)
+            yield ("audio",)
+            yield ("audio",)
+        elif which == 12 and nb > 1:    # jf_bus_set_hrtf, then a joiner: it keeps its set
+            s = int(rng.choice(free))
+            b = (m.bus[s] + 1) % nb
+            j = 1 + int(rng.integers(0, len(m.models) - 1))
+            k = 1 + j % (len(m.models) - 1)
+            if len(m.models) == 2:      # one further set: the joiner is on it, the bus is given set 0
+                j, k = 0, 1
+            if len(m.src[s].buf) < 300 or m.root[s] != s:
+                yield ("set_signal", s, self.speech())
+            yield ("set_priority", s, 255)
+            yield ("set_hrtf", s, k, False)
+            yield ("set_bus_hrtf", b, j, True)
+            yield ("audio",)
+            yield from self.to_bus(s, b)
+            yield ("audio",)
+            yield ("audio",)
+        elif which == 13:   # a set switch ahead of a call of more than max_batch_blocks (several runs), or ahead of a window
+            s = int(rng.choice(free))
+            if len(m.src[s].buf) < 300 or m.root[s] != s:
+                yield ("set_signal", s, self.speech())
+            yield ("set_priority", s, 255)
+            yield ("set_gain", s, 1.0, False)
+            yield ("set_hrtf", s, (m.set_new[s] + 1) % len(m.models), True)
+            self.force_long = not self.windows
+            yield ("audio",)
+            self.force_long = False
+            for _ in range(3 if self.windows else 0):     # windows with no setter between them: descriptors prepared ahead
+                yield ("audio",)
+
+    def ops_new(self):
+        c, m, rng = self.c, self.m, self.rng
+        S = m.S
+        for h in self.sets:
+            yield ("add_hrtf_set", h)
+        for s in range(S):
+            yield ("set_signal", s, self.speech())
+            yield ("set_spherical", s, 0.0, float(40 * s), 1.0)
+        yield ("set_buses", c["buses"])
+        for s in range(S):
+            yield ("set_bus", s, (s // self.run) % c["buses"])
+        for b in range(m.n_buses):
+            p = self.a_pose()
+            yield ("set_listener", b, p[:3].copy(), p[3:].copy())
+        yield ("set_meters", True)
+        yield ("set_input_meters", True)
+        yield ("knob", "set_source_group", 2)
+        if self.windows:
+            yield ("knob", "set_prep_ahead", True)
+        if c["taps"]:
+            yield self.room_op(0)
+            for s in range(0, S, 2):
+                yield ("set_send", s, 0.4)
+        yield ("set_gates", 0.03, 0.03, 1)
+        for s in range(S):
+            yield ("set_gate", s) + (self.thresholds(s) if s < self.GATED else (0.0, 0.0, 0))
+        yield ("set_voices", 0, 2, 0.5, True)
+        yield ("set_voices", 1, 1, 0.0, True)
+        yield ("set_priority", S - 1, 255)
+        yield ("set_priority", 2, 1)
+        yield ("set_hrtf", 1, 1, False)
+        yield ("set_hrtf", 4, 2, False)
+        plan = {7: {55: 3}}.get(self.n, {})
+        turn, held = 0, 0
+        for step in range(c["steps"]):
+            self.pending = None
+            held = held + 1 if m.paused else 0
+            if held > 2:
+                yield ("set_pause", False)
+                held = 0
+            if step in (12, 16):
+                yield ("set_mode", int(step == 12))
+            if self.n == 7 and step == 40:
+                yield ("knob", "set_source_group", 0)         # the group size is free from here on
+            if step % 4 == 0:
+                yield from self.heal()
+            if step in plan:
+                src = self.rebus(plan[step])
+            elif step % 3 == 1:
+                src, turn = self.new_motif(self.CYCLE[turn % len(self.CYCLE)]), turn + 1
+            elif rng.random() < 0.5:
+                src = self.new_setter()
+            else:
+                src = self.setter()
+            for op in src:
+                if op == ("audio",):
+                    yield from self.render()
+                else:
+                    yield op
+            yield from self.render()
+
+    # ---- sessions 9 and 10: stream sources and bus outputs on top of the above (their own code paths again) --
+    STREAM_CYCLE = (20, 27, 0, 29, 21, 109, 2, 110, 22, 111, 4, 112, 23, 113, 3, 24, 1, 25, 5, 26)     # 1xx: new_motif(xx)
+
+    def feed(self, s, n):
+        """the next n frames of the talk that is pushed to stream source s: speech() at the codec's rate, looped"""
+        if s not in self.talks:
+            self.talks[s], self.at[s] = self.speech(), 0
+        x = self.talks[s]
+        idx = (self.at[s] + np.arange(n)) % len(x)
+        self.at[s] = int((self.at[s] + n) % len(x))
+        return x[idx].astype(np.float32)
+
+    def pushes(self, K, how=None):
+        """ahead of a call of K blocks: a packet of 1 to 3 blocks' need per stream source -- now and then too little, so that an
+        underrun falls, now and then a surplus inside the capacity"""
+        import stream_model
+        m, rng, B = self.m, self.rng, self.c["B"]
+        for s in range(m.S):
+            z = m.stream[s]
+            if z is None:
+                continue
+            need = stream_model.need(z["rate"], z["t"], K * B)
+            u = rng.random() if how is None else how
+            if u < 0.14:
+                n = int(rng.integers(0, max(1, need - z["queued"])))                    # too little: an underrun
+            elif u < 0.8:
+                n = max(0, need - z["queued"]) + int(rng.integers(0, 3))
+            else:
+                n = max(0, need - z["queued"]) + int(rng.integers(1, 3) * stream_model.need(z["rate"], z["t"], B))
+            n = max(0, min(n, z["cap"] - stream_model.TAPS - 8 - z["queued"]))          # never more than the FIFO has room for
+            if n or rng.random() < 0.1:
+                yield ("push", s, self.feed(s, n))
+
+    def pulls(self, everything=False):
+        """after a call: 0 frames, a packet of 10 ms or everything that is ready -- and everything before an overrun could fall"""
+        m, rng = self.m, self.rng
+        for b in sorted(m.outputs):
+            o = m.outputs[b]
+            tight = m.output_queued_after(b, MAX_K + 5) > o["cap"] - 1
+            u = rng.random()
+            if everything or tight or u < 0.45:
+                yield ("pull", b, m.output_ready(b) + int(rng.integers(0, 3)))
+            elif u < 0.8:
+                yield ("pull", b, o["rate"] // 100)
+            elif u < 0.9:
+                yield ("pull", b, 0)
+
+    def stream_gate(self, s):
+        """a gate for a stream source whose talk is speech(): open between its quiet (< 0.013) and its loud (> 0.028) blocks"""
+        return ("set_gate", s, 0.02, float(np.float32(0.02 * self.rng.choice([1.0, 0.5]))), int(self.rng.choice([0, 1, 2])))
+
+    def stream_setter(self):
+        m, rng, c = self.m, self.rng, self.c
+        s, b = int(rng.integers(0, m.S)), int(rng.integers(0, m.n_buses))
+        cb = self.callback           # a block is in flight: set_stream and set_output are refused then, and not drawn
+        u = int(rng.integers(0, 100))
+        if u < 20 and not cb:
+            b = int(rng.integers(0, len(c["outputs"])))
+            yield ("set_output", b, c["outputs"][b])               # on a bus that has one: it starts over
+        elif u < 30 and not cb:
+            s = int(rng.integers(0, len(c["streams"])))
+            yield ("set_stream", s, 0)
+            yield ("audio",)
+            yield ("set_stream", s, c["streams"][s])
+            yield self.stream_gate(s)
+        elif u < 45:
+            s = int(rng.integers(0, len(c["streams"])))
+            yield ("reset", s)
+        elif u < 60:
+            s = int(rng.integers(0, len(c["streams"])))
+            yield self.stream_gate(s)
+        elif u < 75:
+            yield ("set_voices", b, int(rng.choice([0, 1, 2])), float(rng.choice([0.0, 0.5])), bool(rng.random() < 0.7))
+        elif not cb:                 # what the header refuses, with nothing changed
+            free = [x for x in range(m.S) if m.stream[x] is None]
+            ops = [("set_stream", s, 44101), ("set_stream", s, 7900), ("set_stream", s, 48000, 1), ("set_output", b, 7000),
+                   ("set_output", b, 48000, 1), ("upload_positions", self.records(2)), ("batch_run", 0, 1)]
+            if free:
+                ops.append(("push", int(free[0]), np.zeros(4, np.float32)))
+            if len(m.outputs) < m.n_buses:
+                ops.append(("pull", [x for x in range(m.n_buses) if x not in m.outputs][0], 4))
+            yield ops[int(rng.integers(0, len(ops)))]
+
+    def stream_motif(self, which):
+        m, rng, c = self.m, self.rng, self.c
+        if which < 20:
+            yield from self.motif(which)
+            return
+        if which >= 100:    # the motifs of sessions 7 and 8 about limits and sets, on the sources that do not stream
+            if not self.callback and (which < 112 or len(m.models) > 1):
+                yield from self.new_motif(which - 100)
+            return
+        if m.paused:
+            yield ("set_pause", False)
+        live = [s for s in range(len(c["streams"])) if m.stream[s] is not None]
+        if not live:
+            return
+        s = int(rng.choice(live))
+        blocks = lambda k: ("blocks", k)
+        if which == 20:     # an underrun, then pushes: the zeros are history, the pushes follow them
+            yield blocks(1) + (0.0,)
+            yield blocks(2) + (0.9,)
+            yield blocks(1) + (0.5,)
+        elif which == 21 and not self.callback:   # a reset of a stream source mid-packet
+            yield blocks(1) + (0.9,)
+            yield ("reset", s)
+            yield blocks(1) + (0.5,)
+            yield blocks(2) + (0.5,)
+        elif which == 22 and not self.callback:   # a master ramp and a limiter attack while an output is running
+            count = np.bincount(m.bus, minlength=m.n_buses)
+            b = max(sorted(m.outputs), key=lambda x: count[x]) if m.outputs else 0      # the fuller of the buses with an output
+            yield ("set_master", b, float(np.float32(0.5 if m.m_new[b] > 0.7 else 1.0)), True)
+            if self.peak.get(b, 0.0) > 1e-3:
+                yield ("set_limiter", b, float(np.float32(0.5 * self.peak[b])), 0.125)
+            yield blocks(3) + (0.5,)
+            yield from self.pulls(True)
+        elif which == 23 and not self.callback:   # jf_engine_set_buses that keeps a bus with an output and a limit
+            yield ("set_voices", 0, 2, 0.5, True)
+            yield from self.rebus(m.n_buses + 1 if m.n_buses <= c["buses"] else c["buses"])
+            yield blocks(2) + (0.5,)
+            yield from self.pulls(True)
+        elif which == 24:   # a pause: nothing is consumed, nothing is appended
+            yield blocks(1) + (0.5,)
+            yield ("set_pause", True)
+            yield ("audio",)
+            yield ("audio",)
+            yield ("set_pause", False)
+            yield blocks(1) + (0.5,)
+            yield blocks(1) + (0.5,)
+            yield from self.pulls(True)
+        elif which == 25 and not self.callback:   # a follower of a stream source hears the resampled signal
+            f = [x for x in range(len(c["streams"]), m.S) if m.root[x] == x and not m.live[x] and
+                 not any(m.root[y] == x for y in range(m.S) if y != x)]
+            resampled = [x for x in live if c["streams"][x] != 44100]      # (at 44 100 Hz the packets ARE the signal)
+            if f and resampled:
+                s = int(rng.choice(resampled))
+                yield ("share_input", int(f[0]), s)
+                yield ("set_gain", int(f[0]), 1.0, False)
+                yield ("set_priority", int(f[0]), 255)
+                yield blocks(2) + (0.5,)
+                yield blocks(1) + (0.5,)
+        elif which == 27 and not self.callback:   # a pause across a STREAM's open gate in its hold, its bus limited and mid-release
+            import stream_model
+            rate = c["streams"][s]
+            per = stream_model.need(rate, 0, 8 * c["B"]) // 8 + 1          # a block's worth of frames at the codec's rate
+            t = int(rng.choice([x for x in range(self.GATED, m.S) if not m.live[x]]))
+            b = m.bus[s]
+            yield ("reset", s)                                             # the queue dropped: the script starts at t = 0
+            kept = self.talks.get(s), self.at.get(s, 0)
+            self.talks[s], self.at[s] = np.concatenate([rng.uniform(-1, 1, 3 * per) * 0.6, rng.uniform(-1, 1, 9 * per) * 0.006]), 0
+            yield ("set_signal", t, self.talk(6, 0, 0.1))
+            if m.bus[t] != b:
+                yield from self.to_bus(t, b)
+            yield ("set_spherical", s, 10.0, 60.0, 0.6)
+            yield ("set_spherical", t, 0.0, 300.0, 0.6)
+            yield ("set_gain", s, 1.0, False)
+            yield ("set_gate", s, 0.2, 0.2, 3)
+            yield ("set_voices", b, 1, 0.5, True)
+            yield ("set_priority", s, 9)
+            yield ("set_priority", t, 9)
+            # three loud blocks, one that still holds the filter's tail of them (none at 44 100 Hz), the first quiet one
+            for _ in range(4 if rate == 44100 else 5):
+                yield blocks(1) + (0.5,)
+            yield ("set_gate", s, 0.2, 0.2, 3)       # set again: the state is not touched
+            yield ("set_pause", True)
+            if len(m.models) > 1:
+                yield ("set_hrtf", s, (m.set_new[s] + 1) % len(m.models), True)
+            yield ("audio",)
+            yield ("audio",)
+            yield ("set_pause", False)
+            yield blocks(1) + (0.5,)
+            yield blocks(1) + (0.5,)
+            yield ("set_priority", s, 0)
+            yield ("set_priority", t, 0)
+            yield ("set_voices", b, 2, 0.5, True)
+            if kept[0] is not None:
+                self.talks[s], self.at[s] = kept
+            yield self.stream_gate(s)
+        elif which == 29 and not self.callback and m.n_buses > 1:   # a stream root whose gate is closed, a follower on another bus that hears it
+            f = [x for x in range(len(c["streams"]), m.S) if m.root[x] == x and not m.live[x] and
+                 not any(m.root[y] == x for y in range(m.S) if y != x)]
+            if f:
+                f = int(f[0])
+                yield ("share_input", f, s)
+                yield from self.to_bus(f, (m.bus[s] + 1) % m.n_buses)
+                yield ("set_spherical", f, 20.0, 120.0, 0.5)
+                yield ("set_gate", s, 4.0, 4.0, 0)
+                yield ("set_gate", f, 0.02, 0.02, 1)
+                yield ("set_gain", f, 1.0, False)
+                yield ("set_priority", f, 255)
+                yield blocks(3) + (0.5,)
+                yield blocks(1) + (0.5,)
+                yield self.stream_gate(s)
+                yield ("set_gate", f, 0.0, 0.0, 0)
+                yield ("set_priority", f, 0)
+        elif which == 26 and not self.callback:   # the streams and outputs that other ops have ended are set again
+            for x, rate in enumerate(c["streams"]):
+                if m.stream[x] is None:
+                    yield ("set_stream", x, rate)
+                    yield self.stream_gate(x)
+            for b, rate in enumerate(c["outputs"]):
+                if b not in m.outputs and b < m.n_buses:
+                    yield ("set_output", b, rate)
+
+    def stream_render(self, K=None, how=None):
+        """pushes, the call, pulls.  K: a motif's call of so many blocks (one per-block call, or a batch call)"""
+        m = self.m
+        if K is not None and not self.callback:
+            self.force_block, self.force_batch = K == 1, K > 1
+        a = self.audio()
+        self.force_block = self.force_batch = False
+        n = 1 if a[0] in ("process_block", "callback") else len(a[1])
+        if not m.paused:
+            yield from self.pushes(n, how)
+        if self.pending is not None:
+            yield self.pending
+            self.pending = None
+        yield a
+        yield from self.pulls()
+
+    def ops_streams(self):
+        c, m, rng = self.c, self.m, self.rng
+        S = m.S
+        self.talks, self.at = {}, {}
+        for h in self.sets:
+            yield ("add_hrtf_set", h)
+        for s in range(S):
+            yield ("set_signal", s, self.speech())
+            yield ("set_spherical", s, 0.0, float(40 * s), 1.0)
+        yield ("set_buses", c["buses"])
+        for s in range(S):
+            yield ("set_bus", s, s % c["buses"])
+        for b in range(m.n_buses):
+            p = self.a_pose()
+            yield ("set_listener", b, p[:3].copy(), p[3:].copy())
+        yield ("set_meters", True)
+        yield ("set_input_meters", True)
+        if c["taps"]:
+            yield self.room_op(0)
+            for s in range(0, S, 2):
+                yield ("set_send", s, 0.4)
+        for s, rate in enumerate(c["streams"]):
+            yield ("set_stream", s, rate)
+            yield self.stream_gate(s)
+        if self.n == 9:
+            yield ("set_live", len(c["streams"]), True)
+        for b, rate in enumerate(c["outputs"]):
+            yield ("set_output", b, rate)
+        yield ("set_voices", 0, 2, 0.5, True)
+        if self.sets:
+            yield ("set_hrtf", S - 1, 1, False)
+        turn, held = 0, 0
+        for step in range(c["steps"]):
+            self.pending = None
+            if self.n == 10 and step == c["steps"] - 25:
+                self.callback = True
+                if m.paused:
+                    yield ("set_pause", False)
+            held = held + 1 if m.paused else 0
+            if held > 2:
+                yield ("set_pause", False)
+                held = 0
+            if not self.callback:          # a stream that another op has ended (a new signal, a live switch, a share) is set again
+                for x, rate in enumerate(c["streams"]):
+                    if m.stream[x] is None and rng.random() < 0.7:
+                        yield ("set_stream", x, rate)
+                        yield self.stream_gate(x)
+            u = rng.random()
+            if step % 2 == 1:
+                src, turn = self.stream_motif(self.STREAM_CYCLE[turn % len(self.STREAM_CYCLE)]), turn + 1
+            elif u < 0.4:
+                src = self.stream_setter()
+            elif u < 0.55 and not self.callback:
+                src = self.new_setter()
+            else:
+                src = self.setter()
+            for op in src:
+                if op == ("audio",):
+                    yield from self.stream_render()
+                elif op[0] == "blocks":
+                    yield from self.stream_render(op[1], op[2])
+                else:
+                    yield op
+            yield from self.stream_render()
+        if self.callback:
+            yield ("collect_block",)
+            yield from self.pulls(True)
+
     def one_launch(self):
         """Before buses, gains, masters and meters: per-block calls of one bus go through the one-launch real-time kernel -- with
         a follower (an alias there) and a world-placed source -- then a gain takes the calls to the batch pipeline and, settled
@@ -636,6 +1308,18 @@ def describe(op):
     return op[0] + " " + " ".join(f"[{'x'.join(map(str, a.shape))}]" if isinstance(a, np.ndarray) else str(a) for a in op[1:])
 
 
+def digest(ops):
+    """SHA-256 over describe(op) and the bytes of every array argument, op by op: the identity of a session's op list"""
+    import hashlib
+    h = hashlib.sha256()
+    for op in ops:
+        h.update(describe(op).encode())
+        for a in op[1:]:
+            if isinstance(a, np.ndarray):
+                h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
+
+
 class Trajectory:
     """what jf_batch_upload_* left on the device: the records, formed at the upload from the buses and objects of that moment"""
 
@@ -656,24 +1340,65 @@ def apply_model(model, traj, op):
         if name == "knob":
             return None, 0
         if name.startswith("upload_"):
+            model.device_form(name)
             traj.upload(model, op)
             return None, 0
         if name == "batch_run":
+            model.device_form()
             return model.run_records(traj.rec[op[1]:op[1] + op[2]]), 0
         if name == "callback":
-            return model.process_block(op[1]), 0
+            res = model.process_block(op[1], late=True)
+            if not model.last.get("paused") and not model.fault:
+                for b, o in model.outputs.items():
+                    o.setdefault("bounds", []).extend(float(v) for v in bounds(model.last, *res.shape[:2])[b])
+            return res, 0
         if name == "collect_block":
-            return None, 0
-        return getattr(model, name)(*op[1:]), 0
+            return model.collect_block(), 0
+        if name == "pull" and op[1] in model.outputs:
+            o = model.outputs[op[1]]
+            u0 = o["pulled"]
+            want = model.pull(*op[1:])
+            model.last_pull = (op[1], o["rate"], u0, pull_bound(o, model.B, u0, want) if not model.fault else None)
+            return want, 0
+        res = getattr(model, name)(*op[1:])
+        if name in AUDIO and not model.last.get("paused") and not model.fault:
+            for b, o in model.outputs.items():
+                o.setdefault("bounds", []).extend(float(v) for v in bounds(model.last, *res.shape[:2])[b])
+        return res, 0
     except Refused as r:
         return None, r.code
+
+
+_gain = {}
+
+
+def pull_bound(o, B, u0, want):
+    """THE OUTPUT BOUND per pulled frame [m]: A times the largest block bound among the blocks under the frame's taps, plus
+    (T + 2) EPS A |want|_inf (tests/test_output.py's rule); A = max over the phases p of sum_k |h[p][k]| from
+    output_model.table64.  Nothing in it is measured from the engine."""
+    import output_model
+    rate = o["rate"]
+    L, M, T = output_model.ratio(rate)
+    if rate not in _gain:
+        _gain[rate] = float(np.abs(output_model.table64(rate)).sum(axis=1).max())
+    A, m = _gain[rate], len(want)
+    if m == 0:
+        return np.zeros(0)
+    i = output_model.index(u0 + np.arange(m, dtype=np.int64), L, M)
+    lo, hi = np.maximum(i - T + 1, 0) // B, i // B
+    bb = np.asarray(o["bounds"])
+    worst = np.array([bb[a:b + 1].max() for a, b in zip(lo, hi)])
+    return A * worst + (T + 2) * float(np.finfo(np.float32).eps) * A * float(np.abs(want).max())
 
 
 def replay(n, hrir, ops, jf=None, fault=None):
     """the session's op list on a (faulty) model: [(out, bounds or None)] of its audio ops"""
     model, traj, outs = make_model(n, hrir, jf, fault), Trajectory(), []
+    model.pulled = []           # what every pull of the session handed out (None: refused)
     for op in ops:
-        res, _ = apply_model(model, traj, op)
+        res, code = apply_model(model, traj, op)
+        if op[0] == "pull":
+            model.pulled.append(None if code else res)
         if op[0] in AUDIO and res is not None:
             outs.append((res, None if model.last.get("paused") else bounds(model.last, *res.shape[:2])))
     return outs, model
@@ -681,13 +1406,19 @@ def replay(n, hrir, ops, jf=None, fault=None):
 
 def generate(n, hrir, castanets, jf=None):
     """The session in lockstep: yields (op, want, refusal, model, gen) after the op has been applied to the model; the caller
-    applies it to the engine.  Without a caller that stops it, it is the CPU's run of the session."""
+    applies it to the engine.  Without a caller that stops it, it is the CPU's run of the session.
+    No two candidates of one bus may have equal envelopes unless they play one input: a session whose draw has such a tie
+    (tests/test_conference_model.py asserts that there is none, and says which ties count) is drawn again by raising its
+    "redraw" in SESSIONS -- another seed for all of its signals."""
+    redraw = SESSIONS[n].get("redraw", 0)
     model, traj = make_model(n, hrir, jf), Trajectory()
-    gen = Generator(n, model, castanets)
+    gen = Generator(n, model, castanets, further_sets(n, hrir, jf) if SESSIONS[n].get("sets") else (), redraw)
     for op in gen.ops():
         res, code = apply_model(model, traj, op)
         if op[0] in AUDIO and res is not None:
             gen.saw(res)
+        if op[0] == "pull":         # (frames, the output bound of each) of every pull, None where the pull is refused
+            gen.pulled.append(None if code else (res, model.last_pull[3]))
         yield op, res, code, model, gen
 
 

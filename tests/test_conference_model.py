@@ -2,18 +2,25 @@
 references the feature tests already hold the kernels to; (2) its dry buses agree with the float32 C oracle within the rule of
 tests/test_probes.py; (3) every clause counts: a copy of the model with ONE clause of the header misread differs from the true
 model by at least 100 bounds in at least one block of every GPU session that uses the feature (the sessions' op lists are
-replayed here: tests/conference_sessions.py generates them without a GPU); (4) the pose draws.  Each test prints its figures
-(pytest -s, or -rP)."""
+replayed here: tests/conference_sessions.py generates them without a GPU); (4) the pose draws; (5) the op lists of sessions 1 to
+6 are byte for byte what they were before sessions 7 and 8 were added.  In (1) HRTF sets, voice gates and voice limits reduce
+EXACTLY to sets_model.SetsModel, gate_model.GateModel fed GateTrack's g_eff and voices_model.VoiceModel fed VoiceTrack's g_out.
+Each test prints its figures (pytest -s, or -rP)."""
 import numpy as np
 import pytest
 
 import conference_sessions as cs
+import gate_model
 import master_model
+import output_model
+import stream_model
 import model64
 import oracle_lib
 import pose_model
 import probes
 import room_model
+import sets_model
+import voices_model
 from conference_model import FAULTS, ConferenceModel, master_block64
 from conftest import sum_tol
 from gain_model import GainModel
@@ -162,6 +169,160 @@ def test_a_model_bus_is_the_master_rule_on_its_mix(hrir):
     assert seen == {"attack", "release"}, seen
 
 
+def _bursts(n_sources, blocks=9, seed=31):
+    """noise in bursts three blocks long, loud (a level of its own per source) and quiet in turn, every source with an offset of
+    its own and a length that is no multiple of B: gates open and close, envelopes cross"""
+    rng = np.random.default_rng(seed)
+    out = []
+    for s in range(n_sources):
+        n = blocks * B + 37 * (s + 1)
+        loud = ((np.arange(n) + s * 2 * B) // (3 * B)) % 2 == 0
+        out.append((rng.uniform(-1, 1, n) * np.where(loud, 0.3 + 0.1 * s, 0.01)).astype(np.float32))
+    return out
+
+
+def test_gates_alone_are_the_gate_model(hrir):
+    """gated sources, an ungated one and a follower with a threshold of its own, two calls (standing gains with a fade, then a
+    staged trajectory): GateModel fed GateTrack's g_eff, exactly; the levels are GateTrack's"""
+    sigs, pos = _bursts(S), room_model.positions(S, 14)
+    track, ref, m = gate_model.GateTrack(B, S), gate_model.GateModel(B, L, S, hrir), _model(hrir, sigs)
+    for s in range(S):
+        track.set_signal(s, sigs[s])
+        ref.set_signal(s, sigs[0 if s == 3 else s])
+    track.share_input(3, 0)
+    m.share_input(3, 0)
+    m.set_input_meters(True)
+    for x in (track, m):
+        x.set_gate(0, 0.2, 0.05, 1)
+        x.set_gate(1, 0.25)
+        x.set_gate(3, 0.02, 0.02, 0)
+    m.set_gain(1, 0.5, fade=True)
+    traj = np.random.default_rng(6).uniform(-1, 1, (8, S)).astype(np.float32)
+    traj[2:4, 0] = 0
+    calls = [(pos[:6], np.array([1, 0.5, 1, 1], np.float32), np.ones(S, np.float32)), (pos[6:], traj, None)]
+    opened = closed = 0
+    for p, g, g_prev in calls:
+        K = len(p)
+        if g.ndim == 2:
+            m.stage_gains(g)
+            g_prev = np.array([1, 0.5, 1, 1], np.float32)
+        g_eff, g_eff_prev, lv = track.run(K, g, g_prev)
+        want = ref.process_batch(p, g_eff, g_eff_prev)[0]
+        assert np.array_equal(m.process_batch(p)[0], want)
+        assert np.array_equal(m.last["levels"], lv)
+        d = np.diff(lv[:, :, 2], axis=1)
+        opened, closed = opened + int((d == 1).sum()), closed + int((d == -1).sum())
+    assert opened >= 3 and closed >= 3 and m.skipped >= 5, (opened, closed, m.skipped)
+
+
+def test_limits_alone_are_the_voice_model(hrir):
+    """two buses, one limited to 2 voices with a release, then both; priorities and an ALWAYS source; a limit set with
+    fade == 0: VoiceModel fed VoiceTrack's g_out, bus by bus, exactly; env and keep are VoiceTrack's"""
+    sigs, pos = _bursts(S, seed=32), room_model.positions(S, 14)
+    bus = [0, 0, 0, 1]
+    track, ref, m = voices_model.VoiceTrack(B, S, 2), voices_model.VoiceModel(B, L, S, hrir), _model(hrir, sigs, 2, bus)
+    for s in range(S):
+        track.set_signal(s, sigs[s])
+        track.set_bus(s, bus[s])
+        ref.set_signal(s, sigs[s])
+    m.set_input_meters(True)
+    lost = 0
+    for a, b in ((0, 5), (5, 9), (9, 14)):
+        for x in (track, m):
+            if a == 0:
+                x.set_voices(0, 2, 0.5)
+                x.set_priority(2, 3)
+            elif a == 5:
+                x.set_voices(0, 1, 0.0, fade=False)
+                x.set_voices(1, 1, 0.25)
+                x.set_priority(2, 0)
+                x.set_priority(1, 255)
+            else:
+                x.set_voices(0, 0)
+        g_out, g_out_prev, env, keep, lv = track.run(b - a)
+        partial = ref.process_batch(pos[a:b], g_out, g_out_prev)[1]
+        got = m.process_batch(pos[a:b])
+        for j in (0, 1):
+            assert np.array_equal(got[j], partial[[s for s in range(S) if bus[s] == j]].sum(axis=0)), (a, j)
+        assert np.array_equal(m.last["heard"][:, :, 0], env.T) and np.array_equal(m.last["heard"][:, :, 1], keep.T)
+        assert np.array_equal(m.last["levels"], lv)
+        lost += int((keep == 0).sum())
+    assert lost >= 8 and m.ramps["out"] >= 1 and m.ramps["in"] >= 1, (lost, m.ramps)
+
+
+def test_sets_alone_are_the_sets_model(hrir):
+    """three sets; switches with and without fade, one ahead of every call, with a gain fade on the same block and through
+    jf_bus_set_hrtf: SetsModel, exactly"""
+    sigs, pos = _sigs(), room_model.positions(S, 9)
+    hrirs = sets_model.make_sets(hrir, 3)
+    ref, m = sets_model.SetsModel(B, L, S, hrirs), _model(hrir, sigs)
+    for s in range(S):
+        ref.set_signal(s, sigs[s])
+    assert [m.add_hrtf_set(h) for h in hrirs[1:]] == [1, 2]
+    m.set_hrtf(3, 2, fade=False)
+    ref.start_on(3, 2)
+    on = np.array([0, 0, 0, 2])
+    gains = np.ones((9, S), np.float32)
+    gains[3:, 1] = 0.5
+    plan = {0: lambda: m.set_hrtf(0, 1), 3: lambda: (m.set_bus_hrtf(0, 2), m.set_gain(1, 0.5, fade=True)), 6: lambda: m.set_hrtf(2, 1)}
+    after = {0: [1, 0, 0, 2], 3: [2, 2, 2, 2], 6: [2, 2, 1, 2]}
+    for a in (0, 3, 6):
+        plan[a]()
+        on = np.array(after[a])
+        want = ref.process_batch(pos[a:a + 3], np.tile(on, (3, 1)), gains[a:a + 3])[0]
+        assert np.array_equal(m.process_batch(pos[a:a + 3])[0], want), a
+    assert m.switches == {"fade": 5, "snap": 1}, m.switches
+
+
+def test_a_stream_source_alone_is_a_live_source_fed_resample32(hrir, jf_lib):
+    """pushes of odd sizes with an underrun among them, batch calls of several sizes: the blocks are, exactly, those of a model
+    whose source is live and is fed stream_model.resample32 (the library's table) of X, the pushes with the zeros where they
+    fell; the statistics are the sums of what was pushed, consumed and missing"""
+    rng = np.random.default_rng(41)
+    sigs, pos = _sigs(), room_model.positions(S, 9)
+    m, ref = _model(hrir, sigs), _model(hrir, sigs)
+    m.stream_table = jf_lib.stream_table
+    rate = 16000
+    m.set_stream(1, rate)
+    ref.set_live(1, True)
+    X, t, queued, zeros = np.zeros(0, np.float32), 0, 0, 0
+    for (a, b), n_push in zip(((0, 1), (1, 4), (4, 5), (5, 9)), (71, 150, 0, 333)):
+        x = rng.uniform(-0.5, 0.5, n_push).astype(np.float32)
+        m.push(1, x)
+        X, queued = np.concatenate([X, x]), queued + n_push
+        n = (b - a) * B
+        need = stream_model.need(rate, t, n)
+        missing = max(0, need - queued)
+        X, zeros, queued = np.concatenate([X, np.zeros(missing, np.float32)]), zeros + missing, max(0, queued - need)
+        y = stream_model.resample32(jf_lib.stream_table(rate), rate, X, t, n)
+        t += n
+        assert np.array_equal(m.process_batch(pos[a:b]), ref.process_batch(pos[a:b], y[None])), (a, b)
+    assert zeros > 0 and m.stream_stats(1) == {"pushed": 554, "consumed": 554 - queued, "zeros_inserted": zeros, "queued": queued}
+
+
+def test_an_output_alone_is_resample64_of_the_blocks_returned(hrir):
+    """pulls of odd sizes between calls: output_model.resample64 of the blocks the model returned, exactly; a paused call's
+    silence is not among them, and an output set again starts over"""
+    sigs, pos = _sigs(), room_model.positions(S, 8)
+    m = _model(hrir, sigs)
+    m.set_master(0, 0.5, fade=True)
+    for rate in (48000, 8000):
+        m.set_output(0, rate)
+        blocks, got = [], []
+        for a, b, n in ((0, 3, 100), (3, 4, 0), (4, 8, 10 ** 6)):
+            blocks.append(m.process_batch(pos[a:b])[0])
+            m.set_pause(True)
+            assert not m.process_block().any()
+            m.set_pause(False)
+            got.append(m.pull(0, n))
+        x = np.concatenate(blocks).reshape(-1, 2)
+        L, M, _ = output_model.ratio(rate)
+        total = output_model.produced(len(x), L, M)
+        got = np.concatenate(got)
+        assert len(got) == total and np.array_equal(got, output_model.resample64(rate, x, 0, total))
+        assert float(np.abs(got).max()) > 0.02
+
+
 # ---------------------------------------------------------------------------------------------------- the C oracle --
 def test_dry_buses_against_the_float32_oracle(hrir):
     """per-bus oracle engines holding the bus's sources at unit gain against the model's dry buses: sum_tol(4e-7, n)"""
@@ -180,27 +341,71 @@ def test_dry_buses_against_the_float32_oracle(hrir):
         assert err <= bound and float(np.abs(want).max()) > 0.02
 
 
+# ------------------------------------------------------------------------------------- sessions 1 to 6 stay as they were --
+DIGESTS = {      # conference_sessions.digest of the op lists as they were before sessions 7 and up existed
+    1: "6dc0074323b5c50586aecb1fc714d66e28acf35464b2c1505c580b08caf39d53",
+    2: "0bbba3ea2aa9e5bcbce3a3f93bd1fa90ffc54d2be8127c5e06d7b6fc83d16057",
+    3: "52711f033f907bb8bcd36a983d266fb1849ae782dd3da7d1495f538d924618ae",
+    4: "25915d527af6295c4a1695ffb7c6c85d2b2ec9ae42c354accaf6e263377a2950",
+    5: "ed634bef8a102e847daa7caac1c428dea4bda72a62c889565b5e39f8c1ba3cdc",
+    6: "a21b383f584d068e6bb983a5e003d2873d6b65f75d5ec63db7e4d6d4cc3f2767",
+}
+
+
+@pytest.mark.parametrize("n", sorted(DIGESTS))
+def test_the_first_six_sessions_are_byte_identical(hrir, castanets, jf_lib, n):
+    assert cs.digest(cs.session_on_cpu(n, hrir, castanets, jf_lib)[0]) == DIGESTS[n]
+
+
 # ---------------------------------------------------------------------------------------------- every clause counts --
 @pytest.mark.parametrize("n", sorted(cs.SESSIONS))
 def test_every_clause_counts_in_session(hrir, castanets, jf_lib, n):
     """Each fault's copy of the model replays the session's op list; the largest |faulty - true| / bound over the session's
     blocks must reach MARGIN for every fault whose feature the session uses.  Also what the GPU session asserts about its own
-    inputs: enough blocks, audible, a limiter that attacks and releases."""
+    inputs: enough blocks, audible, a limiter that attacks and releases; in sessions 7 and 8 gates that cycle, blocks skipped,
+    losers ramping out and winners ramping in, set switches with and without fade, no tie between two inputs."""
     ops, outs, model, gen = cs.session_on_cpu(n, hrir, castanets, jf_lib)
     blocks = sum(o.shape[1] for o, _ in outs)
     peak = max(float(np.abs(o).max()) for o, _ in outs)
     print(f"session {n}: {len(ops)} ops, {blocks} blocks, peak {peak:.3f}, limiter blocks {model.limiter_blocks}")
     assert blocks >= 150 and peak > 0.02, (blocks, peak)
     assert model.limiter_blocks["attack"] >= 1 and model.limiter_blocks["release"] >= 2, model.limiter_blocks
+    if n in cs.NEW:       # conditions on the inputs of the sessions with gates, limits and sets, not measurements
+        cycles = {s: (int((np.diff([0] + h) == 1).sum()), int((np.diff([0] + h) == -1).sum())) for s, h in enumerate(model.gate_hist) if h}
+        print(f"  gates (opened, closed) {cycles}; skipped {model.skipped}, ramps {model.ramps}, switches {model.switches}, ties {model.ties}")
+        assert len(cycles) >= 4 and all(o >= 2 and c >= 1 for o, c in cycles.values()), cycles
+        assert model.skipped >= 20 and model.ramps["out"] >= 10 and model.ramps["in"] >= 10, (model.skipped, model.ramps)
+        assert model.switches["fade"] >= 3 and model.switches["snap"] >= 1, model.switches
+        # (ties: candidates of one bus, of one priority, on different inputs, with equal envelopes ABOVE 0.  Only such a tie could
+        # hang on how a float32 envelope was rounded: across priorities the priority ranks first, and envelopes of exactly 0 --
+        # empty signals -- are equal in the engine and in the model alike, where the lower index wins by the rule)
+        assert model.ties == 0, (model.ties, "draw the session again: raise its 'redraw' in conference_sessions.SESSIONS")
+    if n in cs.STREAMS:   # ... and of the sessions with stream sources and bus outputs
+        c = cs.SESSIONS[n]
+        hist = {s: h for s, h in enumerate(model.gate_hist) if h and s < len(c["streams"])}     # (the stream sources' gates)
+        cycles = {s: (int((np.diff([0] + h) == 1).sum()), int((np.diff([0] + h) == -1).sum())) for s, h in hist.items()}
+        print(f"  streams (underruns, zeros inserted) {model.stream_totals[:len(c['streams'])]}, pulls {model.pull_counts}, gates {cycles}")
+        assert all(u >= 1 and z > 0 for u, z in model.stream_totals[:len(c["streams"])]), model.stream_totals
+        assert all(model.pull_counts.get(b, 0) >= 10 for b in range(len(c["outputs"]))), model.pull_counts
+        assert all(o >= 2 and cl >= 1 for o, cl in cycles.values()) and len(cycles) >= len(c["streams"]), cycles
+        assert model.ties == 0, (model.ties, "draw the session again: raise its 'redraw' in conference_sessions.SESSIONS")
     short = []
     for fault in FAULTS:
         if not cs.uses(n, fault):
             continue
-        bad, _ = cs.replay(n, hrir, ops, jf_lib, fault)
+        bad, faulty = cs.replay(n, hrir, ops, jf_lib, fault)
         assert len(bad) == len(outs)
-        worst = 0.0
+        worst = same = 0.0
+        if fault in cs.OUTPUT_FAULTS:       # measured on the output frames, in units of the output bound
+            for a, t in zip(faulty.pulled, gen.pulled):
+                if (a is None) != (t is None) or (t is not None and len(a) != len(t[0])):
+                    worst = float("inf")    # (frames that are not there at all)
+                elif t is not None and len(a):
+                    same = max(same, float((np.abs(a - t[0]).max(axis=1) / t[1]).max()))
+            worst = max(worst, same)
+            print(f"  {fault}: on the pulls of equal length {same:.0f} output bounds")
         for (a, _), (t, bound) in zip(bad, outs):
-            if bound is not None:
+            if bound is not None and fault not in cs.OUTPUT_FAULTS:
                 worst = max(worst, float((np.abs(a - t).max(axis=2) / bound).max()))
         print(f"  {fault}: {worst:.0f} bounds")
         if worst < MARGIN:

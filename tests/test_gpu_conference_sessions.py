@@ -18,15 +18,27 @@ Also asserted, where meters are on: peak_in within the bound of the model's p; g
 recurrence fed the engine's own peak_in sequence; peak_out <= ceiling on a limited bus; sumsq_out within sumsq_bound of the
 float64 sum over the engine's own output.  A bus without sources that nobody has
 sent to since the room was set is exact zeros, a paused call silence on every bus.
+Sessions 7 and 8 add HRTF sets, voice gates and voice limits (tests/conference_model.py composes sets_model, gate_model and
+voices_model): a gated or limited source still counts in n, and with input meters on every rendered call's jf_source_levels
+(peak and open exact, sumsq within B 2^-23 relative: tests/test_gpu_gate.py's rule) and jf_source_heard (env and keep exact) are
+the model's.
+Sessions 9 and 10 add stream sources and bus outputs.  After every call, paused ones included, jf_source_stream_stats and the
+outputs' counts are the model's (a paused call consumes nothing and appends nothing).  What jf_bus_pull hands out is (a) bit for
+bit output_model.resample32, on the library's table, of the blocks the engine itself handed out since the output was set, and
+(b) within THE OUTPUT BOUND of the model's resample64: A times the largest block bound among the blocks under the frame's taps
+plus (T + 2) EPS A |want|_inf (tests/test_output.py's rule), A = max_p sum_k |h[p][k]| of output_model.table64
+(conference_sessions.pull_bound).  In the callback form a block's levels and heard are compared one call late, like the block.
 With JF_BOUNDS_LOG=<file> every call's worst error / bound is appended to that file (profiles/conference/bounds.txt)."""
 import collections
 import os
+import time
 
 import numpy as np
 import pytest
 
 import conference_sessions as cs
 import master_model
+import output_model
 
 pytestmark = pytest.mark.gpu
 
@@ -141,10 +153,88 @@ def _check(n, label, got, want, last, meters, lim, model_c, model_r, worst, tall
             assert abs(float(sumsq) - ref) <= master_model.sumsq_bound(ref, B), ("sumsq_out", b, j, sumsq, ref)
 
 
+NEW_KERNELS = ("input_level_kernel", "gate_scan_kernel", "voice_env_kernel", "voice_select_kernel", "desc_set_kernel")
+STREAM_KERNELS = ("stream_resample_kernel", "output_resample_kernel")
+
+
+class _Outputs:
+    """What the engine itself handed out per bus since the bus's output was set, and how much of it was pulled: a pull is held
+    (a) bit for bit to output_model.resample32, on the library's table, of exactly those blocks (a paused call's silence is not
+    among them) and (b) to the model's resample64 within conference_sessions.pull_bound."""
+
+    def __init__(self, jf):
+        self.jf, self.blocks, self.pulled = jf, {}, {}
+
+    def op(self, op):
+        if op[0] == "set_output":
+            self.blocks.pop(op[1], None), self.pulled.pop(op[1], None)
+            if op[2]:
+                self.blocks[op[1]], self.pulled[op[1]] = [], 0
+        elif op[0] == "set_buses":
+            for b in [b for b in self.blocks if b >= op[1]]:
+                self.blocks.pop(b), self.pulled.pop(b)
+
+    def handed(self, got):
+        for b in self.blocks:
+            self.blocks[b].extend(np.array(x, np.float32) for x in got[b])
+
+    def pull(self, eng, model, op, want, tally, worst):
+        b = op[1]
+        frames = eng.pull(b, op[2])
+        _, rate, u0, bound = model.last_pull
+        assert u0 == self.pulled[b] and frames.shape == want.shape, (op[:3], u0, self.pulled[b], frames.shape, want.shape)
+        x = np.concatenate(self.blocks[b]).reshape(-1, 2) if self.blocks[b] else np.zeros((0, 2), np.float32)
+        own = output_model.resample32(self.jf.output_table(rate), rate, x, u0, len(frames))
+        assert np.array_equal(frames, own), ("pulled frames are not the rule on the blocks handed out", b, rate, u0, len(frames))
+        if len(frames):
+            err = np.abs(frames - want).max(axis=1)
+            k = int(np.argmax(err / bound))
+            worst[0] = max(worst[0], float(err[k] / bound[k]))
+            _log_ratio(f"conference output bus {b} at {rate} Hz frame {u0 + k}", float(err[k]), float(bound[k]))
+            assert (err <= bound).all(), ("pulled frames against the model", b, rate, u0 + k, float(err[k]), float(bound[k]))
+        self.pulled[b] += len(frames)
+        tally["pulls"] += 1
+        tally["frames pulled"] += len(frames)
+
+
+def _check_streams(eng, model, label, callback):
+    """after every call, paused ones included: a stream's statistics and an output's counts are the model's -- a paused call
+    consumes nothing of a stream and appends nothing to an output"""
+    for s in range(model.S):
+        if model.stream[s] is not None:
+            assert eng.stream_stats(s) == model.stream_stats(s), (label, s, eng.stream_stats(s), model.stream_stats(s))
+    for b, o in model.outputs.items():
+        assert eng.output_ready(b) == model.output_ready(b), (label, b, eng.output_ready(b), model.output_ready(b))
+        if not callback:
+            L, M, _ = output_model.ratio(o["rate"])
+            want = output_model.produced(len(o["blocks"]) * model.B, L, M)
+            assert eng.output_stats(b)["produced"] == want, (label, b, eng.output_stats(b), want)
+
+
+def _check_reports(eng, last, K, label, tally):
+    """jf_source_levels and jf_source_heard of a rendered call against the model's: peak, open, env and keep exact, sumsq within
+    tests/test_gpu_gate.py's rule (a float32 sum of B rounded squares in any order: B 2^-23 relative)"""
+    want = last.get("levels")
+    if want is not None:
+        lv = eng.levels(K)
+        assert np.array_equal(lv[..., 0], want[..., 0].astype(F)), (label, "peak")
+        assert np.array_equal(lv[..., 2], want[..., 2].astype(F)), (label, "open", lv[..., 2].T.tolist(), want[..., 2].T.tolist())
+        assert (np.abs(lv[..., 1] - want[..., 1]) <= eng.B * 2.0 ** -23 * want[..., 1]).all(), (label, "sumsq")
+        tally["calls with levels checked"] += 1
+    want = last.get("heard")
+    if want is not None:
+        hd = eng.heard(K)
+        assert np.array_equal(hd[..., 0], want[..., 0].astype(F)), (label, "env")
+        assert np.array_equal(hd[..., 1], want[..., 1].astype(F)), (label, "keep", hd[..., 1].T.tolist(), want[..., 1].T.tolist())
+        tally["calls with heard checked"] += 1
+
+
 @pytest.mark.parametrize("n", sorted(cs.SESSIONS))
 def test_conference_session_against_the_composed_model(jf, hrir, castanets, n):
+    t0 = time.perf_counter()
     eng = cs.make_engine(n, hrir, jf)
     log, worst, lim = [], [0.0], _Limiters()
+    outs, worst_out = _Outputs(jf), [0.0]
     families, drawn = collections.Counter(), collections.Counter()
     blocks, peak, limited = 0, 0.0, False
     late = None             # the callback form hands a block out one call late: (want, last, metered, c, r) of that block
@@ -159,7 +249,12 @@ def test_conference_session_against_the_composed_model(jf, hrir, castanets, n):
                 else:               # the callback form checks a block a call late: so are the ops that follow its submission
                     deferred.append(op)
                 limited = limited or (op[0] == "set_limiter" and op[2] > 0)
+            if op[0] == "pull" and not code:
+                outs.pull(eng, model, op, want, families, worst_out)
+                continue
             got = _apply(jf, eng, op, want, code)
+            if not code:
+                outs.op(op)
             if got is None:
                 continue
             last = model.last
@@ -171,6 +266,15 @@ def test_conference_session_against_the_composed_model(jf, hrir, castanets, n):
                     w, l, metered, c, r = late
                     m = eng.meters(1) if metered and model.meters_on and not l.get("paused") else None
                     _check(n, f"step {len(log)} callback", got, w, l, m, lim, c, r, worst, families)
+                    if not l.get("paused"):
+                        outs.handed(got)
+                        # the block's input meters and voices, one call late like the block (while they are still kept)
+                        limited = any(v > 0 for v in model.vc_N)
+                        _check_reports(eng, {"levels": l.get("levels") if model.input_meters else None,
+                                             "heard": l.get("heard") if model.input_meters and limited else None}, 1,
+                                       f"step {len(log)} callback", families)
+                _check_streams(eng, model, f"step {len(log)} {op[0]}", True)
+                if late is not None:
                     blocks, peak = blocks + 1, max(peak, float(np.abs(w).max()))
                 for o in deferred:
                     lim.op(o)
@@ -181,13 +285,18 @@ def test_conference_session_against_the_composed_model(jf, hrir, castanets, n):
                 names = eng.last_kernels()
                 ks = ";".join(names)
                 for fam in ("rt_block_kernel", "fused_block_kernel", "fused_pair_kernel", "fused2048_kernel", ",shared", "desc_gain_kernel",
-                            "room_mac_kernel", "master_apply_kernel", "pose_kernel", "pose_object_kernel", "live_ingest_kernel"):
+                            "room_mac_kernel", "master_apply_kernel", "pose_kernel", "pose_object_kernel", "live_ingest_kernel") + NEW_KERNELS + STREAM_KERNELS:
                     families[fam] += fam in ks
                 ahead = op[0] == "batch_run" and "prep_kernel" not in names      # the run found its descriptors prepared
                 families["descriptors prepared ahead"] += ahead
                 families["... with a gain active"] += ahead and "desc_gain_kernel" in ks
+                families["... with a gate or a set active"] += ahead and ("gate_scan_kernel" in ks or "desc_set_kernel" in ks)
             m = eng.meters(K) if model.meters_on and not last.get("paused") else None
             _check(n, f"step {len(log)} {op[0]} K={K}", got, want, last, m, lim, model.lim_c, model.lim_r, worst, families)
+            if not last.get("paused"):
+                _check_reports(eng, last, K, f"step {len(log)} {op[0]} K={K}", families)
+                outs.handed(got)
+            _check_streams(eng, model, f"step {len(log)} {op[0]} K={K}", False)
             blocks, peak = blocks + K, max(peak, float(np.abs(want).max()))
     except BaseException:
         print("\n".join(log[-40:]))     # (pytest shows it with the failure)
@@ -196,13 +305,27 @@ def test_conference_session_against_the_composed_model(jf, hrir, castanets, n):
         eng.close()
     print(f"session {n} kernels: {dict(families)}")
     print(f"session {n} ops: {dict(sorted(drawn.items()))}")
-    print(f"session {n}: {blocks} blocks, peak {peak:.3f}, worst error / bound {worst[0]:.3f}, limiter blocks {model.limiter_blocks}")
+    print(f"session {n}: {blocks} blocks, peak {peak:.3f}, worst error / bound {worst[0]:.3f}, limiter blocks {model.limiter_blocks}, "
+          f"{time.perf_counter() - t0:.1f} s with the model")
     assert blocks >= 150 and peak > 0.02, (blocks, peak)
     if n == 6:      # the runs that follow their predecessor take its descriptors, and desc_gain_kernel rewrites those as well
         assert families["... with a gain active"] >= 1, dict(families)
         # windows of every kind of uploaded trajectory, and the session's first blocks through the one-launch kernel
         assert drawn["upload_world"] >= 1 and drawn["upload_objects"] >= 1 and drawn["upload_positions"] >= 1, dict(drawn)
         assert families["rt_block_kernel"] >= 3, dict(families)
+    if n in cs.NEW:
+        for fam in NEW_KERNELS:
+            assert families[fam] >= 1, (fam, dict(families))
+        assert families["calls with levels checked"] >= 50 and families["calls with heard checked"] >= 30, dict(families)
+    if n in cs.STREAMS:
+        for fam in STREAM_KERNELS + NEW_KERNELS[:4] + (NEW_KERNELS[4:] if cs.SESSIONS[n].get("sets") else ()):
+            assert families[fam] >= 1, (fam, dict(families))
+        assert families["calls with levels checked"] >= 50 and families["calls with heard checked"] >= 30, dict(families)
+        print(f"session {n} outputs: {families['pulls']} pulls, {families['frames pulled']} frames, worst error / output bound "
+              f"{worst_out[0]:.3f}; streams (underruns, zeros) {model.stream_totals[:2]}")
+        assert families["pulls"] >= 20 and families["frames pulled"] >= 5000, dict(families)
+    if n == 8:      # ... and the gate stage and desc_set_kernel rewrite descriptors that were prepared ahead
+        assert families["... with a gate or a set active"] >= 1, dict(families)
     assert families["metered bus blocks"] >= 50, dict(families)
     if limited:
         assert families["limiter gains checked bit for bit"] >= 10, dict(families)

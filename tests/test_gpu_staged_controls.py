@@ -7,7 +7,7 @@ caller-owned device tensor; engine B, the same configuration under the same scri
 twelve outputs and the last run's meters must be equal bit for bit, every run of A must have launched desc_set_kernel and
 desc_gain_kernel, and B's first and last run are held, bus by bus, to tests/conference_model.py within the bound of
 tests/test_gpu_conference_sessions.py (conference_sessions.bounds), so that an error A and B share cannot pass.  The model hears
-through sets by tests/sets_model.py's identity: a GainModel per set, a source's gain on the sets it is not on 0.
+through sets as tests/conference_model.py composes them (tests/sets_model.py's identity).
 
 NOT a race detector: on runs this short the host need not get four uploads ahead of the device, so the event wait that keeps a
 slot from being overwritten while its copy is still in line may never be exercised here; that wait is checked by review.
@@ -19,7 +19,6 @@ import pytest
 
 import conference_sessions as cs
 from conference_model import ConferenceModel
-from gain_model import GainModel
 from sets_model import make_sets
 
 pytestmark = pytest.mark.gpu
@@ -32,38 +31,6 @@ CEILING, RELEASE = 0.05, 0.25                    # bus 1's limiter: below that b
 @pytest.fixture(scope="module")
 def sets(hrir):
     return make_sets(hrir, 4)
-
-
-class _Model(ConferenceModel):
-    """ConferenceModel with HRTF sets: a block of source s is the sum over the sets of a GainModel created with that set, at the
-    source's gain where the source is on the set (before / in this block) and at 0 elsewhere -- SetsModel's identity.  Windows
-    and play positions do not depend on the set: the further models take them from the first before every block."""
-
-    def __init__(self, hrirs):
-        super().__init__(B, L, S, hrirs[0])
-        self.further = [GainModel(B, L, S, h) for h in hrirs[1:]]
-        self.set_prev, self.set_new = [0] * S, [0] * S
-        first = self.gm.source_block
-
-        def source_block(q, ele, azi, coords, g_prev, g):
-            s = next(i for i, x in enumerate(self.gm.src) if x is q)
-            j0, j1 = self.set_prev[s], self.set_new[s]
-            blk = np.zeros(2 * B)
-            for j, m in enumerate(self.further, 1):
-                p = m.src[s]
-                p.buf, p.count, p.old_ele, p.old_azi = q.buf, q.count, q.old_ele, q.old_azi
-                p.x[:] = q.x
-                blk += m.source_block(p, ele, azi, coords, g_prev if j0 == j else 0.0, g if j1 == j else 0.0)
-            blk += first(q, ele, azi, coords, g_prev if j0 == 0 else 0.0, g if j1 == 0 else 0.0)
-            self.set_prev[s] = j1
-            return blk
-
-        self.gm.source_block = source_block
-
-    def set_hrtf(self, s, j, fade=True):
-        self.set_new[s] = j
-        if not fade:
-            self.set_prev[s] = j
 
 
 def _signals(castanets):
@@ -151,7 +118,8 @@ def test_twelve_changes_of_every_control_back_to_back(jf, sets, castanets):
     for i, ks in enumerate(names_a):
         assert "desc_set_kernel" in ks and "desc_gain_kernel" in ks, (i, ks)
 
-    model = _Model(sets[:2])
+    model = ConferenceModel(B, L, S, sets[0])
+    assert model.add_hrtf_set(sets[1]) == 1
     _setup(model, sigs)
     limited = False
     for i in range(RUNS):
