@@ -768,7 +768,8 @@ int jf_batch_set_gains(jf_engine *e, int n_blocks, const float *gains /* [n_bloc
  *
  * THE LIMITER IS A SAFETY DEVICE, NOT A MASTERING TOOL: a brick-wall limiter at BLOCK granularity.  It looks at the peak of a
  * whole block, turns the whole block down at once when that peak is over the ceiling, and lets the gain return by `release`
- * per block, ramped inside the block.  No look-ahead, no knee.  Its contract: NO SAMPLE OF A LIMITED BUS EXCEEDS ITS CEILING.
+ * per block, ramped inside the block.  No knee; look-ahead is an option per bus (below).  Its contract: NO SAMPLE OF A LIMITED
+ * BUS EXCEEDS ITS CEILING.
  *
  * THE RULE (csrc/jf_master_rule.h, float32, one rounding per written operation).  Per bus: m_prev, the master gain the last
  * rendered block ended on; m_new, the gain asked for; c, the ceiling (0: limiter off); r, the release (0 < r <= 1); and the
@@ -804,8 +805,33 @@ int jf_batch_set_gains(jf_engine *e, int n_blocks, const float *gains /* [n_bloc
  * While active, three small kernels run on the mix behind the mix step of every batch run and the per-block
  * calls go through the batch pipeline with one block (as with more than one bus, a room or a gain).
  *
- * Not offered: look-ahead; masters inside the one-launch real-time kernel; jefferson_group.h, jf_render and jf_ctest have no
- * option for masters.
+ * LOOK-AHEAD.  The rule above turns an attacking block down AT ONCE: between the last frame of the block before and its first
+ * frame the gain drops by g_prev - g in one sample, a click, exactly when ten people talk at once.  With look-ahead on, a bus's
+ * mix is handed out ONE BLOCK LATE, and the limiter gain of the block that goes out runs as a ramp from the gain the block
+ * before ended on to a gain that is already low enough for the block that comes AFTER it: no gain step anywhere, no overshoot.
+ * Further state per bus: the held block h (zeros at first) and its peak p_h (0).  For a block x (csrc/jf_master_rule.h):
+ *   v = m[n] x and p = max |v| as above;  t_h = (p_h > c ? c / p_h : 1) and t = (p > c ? c / p : 1), both with the ceiling that
+ *   is current;  e = min(min(t_h, t), g_prev + r) (limiter off: 1);  a[n] = g_prev + (e - g_prev) ((n + 1) (1 / B)), kept
+ *   between g_prev and e;  out = min(max(a[n] h, -c), c) -- the HELD block;  meters {peak_in = p, peak_out = max |out|,
+ *   sumsq_out, gain = e}: peak_in is of the block that came in, the others of the block that goes out;  h := v, p_h := p,
+ *   g_prev := e.
+ * The largest gain change between neighbouring frames is |e - g_prev| / B, across block boundaries too; with the limiter off
+ * and m = 1 the output is the input bit for bit, one block late.
+ * jf_bus_set_lookahead(e, bus, on): on is 0 or 1 (anything else: JF_ERR_ARG); latched by the next processing call that is not
+ *   paused, like the other setters.  TURNING ON: the held block is zeros, so ONE BLOCK OF SILENCE enters the bus's stream; g is
+ *   kept.  TURNING OFF: the held block is dropped; g is kept.  A limiter turned off and on again starts from g = 1 as above and
+ *   leaves the held block alone.  The delay is there whenever look-ahead is on, with the limiter on or off: switching a
+ *   ceiling never shifts a listener's audio.  jf_bus_lookahead: the value last set; 0 for a bad index.
+ * jf_bus_latency(e, bus): the frames by which the bus's handed-out mix lags the engine: the block size while look-ahead is
+ *   latched on, else 0 (and 0 for a bad index).  A host that must hand out everything it fed in renders ONE MORE BLOCK when this is
+ *   not 0 (its sources at their ends or muted): that call hands out the held block.  A paused call does not flush.
+ * Everything behind the master section -- bus outputs, jf_last_block_peak, jf_batch_fetch -- sees the delayed, limited block.
+ * An engine in which no bus ever turned look-ahead on allocates nothing for it and launches exactly what it launched; while
+ * some bus has it on the engine is active in the sense above, and jf_engine_set_buses keeps the held blocks of the buses that
+ * remain.
+ *
+ * Not offered: a look-ahead window other than one block; masters inside the one-launch real-time kernel; jefferson_group.h,
+ * jf_render and jf_ctest have no option for masters.
  */
 int jf_bus_set_master(jf_engine *e, int bus, float gain, int fade);
 float jf_bus_master(const jf_engine *e, int bus); /* the gain last set; 1 for a bad index */
@@ -813,6 +839,9 @@ int jf_bus_set_limiter(jf_engine *e, int bus, float ceiling, float release);
 int jf_bus_limiter(const jf_engine *e, int bus, float *ceiling, float *release);
 int jf_engine_set_meters(jf_engine *e, int on);
 int jf_bus_meters(jf_engine *e, int n_blocks, float *out /* [n_buses][n_blocks][4] */);
+int jf_bus_set_lookahead(jf_engine *e, int bus, int on);
+int jf_bus_lookahead(const jf_engine *e, int bus); /* the value last set; 0 for a bad index */
+int jf_bus_latency(const jf_engine *e, int bus);   /* frames the handed-out mix lags by: B with look-ahead latched on, else 0 */
 
 /* ---- HRTF sets: several sets in one engine, chosen per source or per bus -------- */
 

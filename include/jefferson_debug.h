@@ -273,6 +273,12 @@ int jf_profile_read_gain(jf_engine *e, double *gain_ms);
  * summed sample by sample in float32.  Pure host code: no engine, no GPU.  JF_ERR_ARG for a NULL pointer or B <= 0. */
 int jf_debug_master_block(const float *x, int B, float m_prev, float m_new, float ceiling, float release, float *g_state, float *out,
                           float meters[4]);
+/* ... and its look-ahead form (jf_bus_set_lookahead): x [B][2] comes in; held [B][2] -- the block that came in before, master
+ * gain applied -- goes OUT through the limiter and is replaced by x with the master gain on it; *p_held is the held block's
+ * peak and *g_state the limiter gain, each before the block and after it (zeros, 0 and 1 at the start of a stream).  meters =
+ * {peak_in of x, peak_out and sumsq_out of out, gain}.  x, held and out may not overlap. */
+int jf_debug_master_look_block(const float *x, int B, float m_prev, float m_new, float ceiling, float release, float *held,
+                               float *p_held, float *g_state, float *out, float meters[4]);
 /* ms in the master stage (master_peak_kernel, master_gain_kernel, master_apply_kernel) since jf_profile_enable(e, 2): part of
  * jf_profile_read's mix_ms too (the stage runs inside the mix's event pair); 0 while no master was active. */
 int jf_profile_read_master(jf_engine *e, double *master_ms);

@@ -165,6 +165,10 @@ _SIGS = {
     "jf_bus_meters": (C.c_int, [C.c_void_p, C.c_int, _f]),
     "jf_debug_master_block": (C.c_int, [_f, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, _f, _f, _f]),
     "jf_profile_read_master": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "jf_bus_set_lookahead": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "jf_bus_lookahead": (C.c_int, [C.c_void_p, C.c_int]),
+    "jf_bus_latency": (C.c_int, [C.c_void_p, C.c_int]),
+    "jf_debug_master_look_block": (C.c_int, [_f, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, _f, _f, _f, _f, _f]),
     "jf_source_set_gate": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int]),
     "jf_source_gate": (C.c_int, [C.c_void_p, C.c_int, _f, _f, _i]),
     "jf_sources_set_gate": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_int]),
@@ -554,6 +558,21 @@ def master_block(x, m_prev=1.0, m_new=1.0, ceiling=0.0, release=1.0, g_prev=1.0)
     if rc:
         raise JfError(rc, "master_block")
     return out, m, g[0]
+
+
+def master_look_block(x, held, p_held=0.0, m_prev=1.0, m_new=1.0, ceiling=0.0, release=1.0, g_prev=1.0):
+    """jf_debug_master_look_block (host logic only): the look-ahead form of the bus-master rule.  x [2B] comes in, held [2B]
+    (the block before, master gain applied; zeros at the start) goes out -> (out [2B], meters [4], the new held block [2B], its
+    peak, the limiter gain after the block)"""
+    x = np.ascontiguousarray(x, np.float32).ravel()
+    h = np.array(held, np.float32).ravel()
+    assert x.size % 2 == 0 and h.size == x.size
+    out, m = np.zeros_like(x), np.zeros(4, np.float32)
+    p, g = np.array([p_held], np.float32), np.array([g_prev], np.float32)
+    rc = lib().jf_debug_master_look_block(_fp(x), x.size // 2, m_prev, m_new, ceiling, release, _fp(h), _fp(p), _fp(g), _fp(out), _fp(m))
+    if rc:
+        raise JfError(rc, "master_look_block")
+    return out, m, h, p[0], g[0]
 
 
 def gate_scan(peaks, open, close, hold, state=(0, 0)):
@@ -1152,6 +1171,19 @@ class Engine:
         return out
 
     master_block = staticmethod(master_block)
+
+    def set_lookahead(self, bus, on=True):
+        """bus's limiter look-ahead: the bus is handed out one block late and the limiter's gain never steps (jf_bus_set_lookahead)"""
+        self._chk(lib().jf_bus_set_lookahead(self.h, int(bus), int(bool(on))))
+
+    def lookahead(self, bus):
+        return bool(lib().jf_bus_lookahead(self.h, int(bus)))
+
+    def bus_latency(self, bus):
+        """frames by which bus's handed-out mix lags the engine: B with look-ahead latched on, else 0 (jf_bus_latency)"""
+        return int(lib().jf_bus_latency(self.h, int(bus)))
+
+    master_look_block = staticmethod(master_look_block)
 
     def profile_read_master(self):
         """ms in the master stage's kernels since profile_enable(2)"""

@@ -540,7 +540,9 @@ const char *jf_debug_last_kernels(jf_engine *e) {
                   (e->last_group > 1 ? "fused_pair_kernel<" : "fused_block_kernel<") + nb + (e->last_shared ? ",shared" : "") +
                   (e->last_fused_prep ? ">+prep" : ">") + (e->last_mix_prep ? ";mix_prep_kernel" : mix_name);
         if (room) k += ";room_add_kernel";
-        if (!e->last_rt && e->last_master) k += ";master_peak_kernel<" + nb + ">;master_gain_kernel;master_apply_kernel<" + nb + ">";
+        if (!e->last_rt && e->last_master)
+            k += e->last_look ? ";look_peak_kernel<" + nb + ">;look_gain_kernel;look_apply_kernel<" + nb + ">"
+                              : ";master_peak_kernel<" + nb + ">;master_gain_kernel;master_apply_kernel<" + nb + ">";
         if (!e->last_rt && e->last_output) k += ";output_resample_kernel";
         e->kernels = k;
         return e->kernels.c_str();

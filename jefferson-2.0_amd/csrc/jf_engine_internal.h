@@ -11,7 +11,8 @@
 //   jf_engine_gain.cpp    per-source gain: the levels and mutes, what a processing call latches of them, the stage that applies
 //                         them to a run's descriptors (run_gain_stage, jf_desc_edit.hip) and jf_source_set_gain / jf_batch_set_gains
 //   jf_engine_master.cpp  bus masters: the per-bus master gains, limiters and meters, what a processing call latches of them, the
-//                         stage behind the mix (run_master_stage, jf_master.hip) and jf_bus_set_master / jf_bus_meters
+//                         stage behind the mix (run_master_stage, jf_master.hip) and jf_bus_set_master / jf_bus_meters; the
+//                         limiter's look-ahead (jf_bus_set_lookahead: the stage is jf_lookahead.hip's while a bus has it on)
 //   jf_engine_sets.cpp    HRTF sets: further sets behind the engine's own in the table, the sources' sets, what a processing call
 //                         latches of them, the stage that moves a run's descriptors into them (run_set_stage, jf_desc_edit.hip)
 //                         and jf_engine_add_hrtf_set / jf_source_set_hrtf
@@ -121,6 +122,12 @@ hipError_t launch_desc_set(ItemDesc *d_desc, const int *d_set_prev, const int *d
 // bus masters (jf_master.hip): master gain, limiter and meters on a run's finished mix, in place
 hipError_t launch_master(float *d_mix, const float *d_par, float *d_state, float *d_t, float *d_gg, float *d_meters, int B, int K,
                          int n_buses, int ramp, hipStream_t st);
+// ... with look-ahead on some bus (jf_lookahead.hip): d_lrow [n_buses] the buses' rows (-1: none), d_hold [rows][2][look_hold_floats(B)],
+// d_stage [rows][K - 1][2B]
+int look_hold_floats(int B);
+hipError_t launch_master_look(float *d_mix, const float *d_par, const int *d_lrow, float *d_state, float *d_t, float *d_gg,
+                              float *d_meters, float *d_hold, float *d_stage, int B, int K, int n_buses, int ramp, int parity,
+                              hipStream_t st);
 // voice gates and input meters (jf_gate.hip): the inputs' levels per (block, source), then the gates and the run's effective gains
 hipError_t launch_input_level(const SrcSignal *d_sigs, const SrcState *d_state, const int *d_root, float *d_peak, float *d_sumsq,
                               int S, int K, int B, hipStream_t st);
@@ -518,6 +525,25 @@ struct jf_engine : ReverbSetup {
     PinnedBuf<float> h_meters;                // [master_cap][4] where a call's meters land on the host
     bool last_master = false;                 // the last run launched the stage (jf_debug_last_kernels)
     StageTimer tm_master;                     // profiling 2: around the stage (jf_profile_read_master)
+    // LOOK-AHEAD of the limiter (jf_bus_set_lookahead): a bus with it is handed out one block late.  It rides
+    // with the masters: look_want is the setters' (empty until a bus first turns it on), master_latch gives a bus that turns
+    // it on a ROW of the look-ahead buffers and takes it back when it is turned off; an engine with a row is ACTIVE, and its
+    // stage is jf_lookahead.hip's in place of jf_master.hip's.  Nothing below exists in an engine that never turned it on.
+    std::vector<char> look_want;              // [n_buses] under pos_mu: what jf_bus_set_lookahead last set (empty: every bus off)
+    std::vector<int> look_row;                // [n_buses] under pos_mu: the row of a bus whose look-ahead is LATCHED on, else -1
+    std::vector<int> look_free;               // rows below look_rows that no bus has; under pos_mu
+    int look_rows = 0;                        // rows handed out so far; under pos_mu
+    // (the processing thread's)
+    std::vector<int> run_lrow;                // look_row of the call in hand (empty: no bus has a row)
+    std::vector<int> dev_lrow;                // what d_lrow holds (empty: nothing yet)
+    DevBuf<int> d_lrow;                       // [JF_MAX_BUSES]
+    StagedRing<int> l_ring;                   // slots of [JF_MAX_BUSES]: the asynchronous copies to d_lrow
+    DevBuf<float> d_lhold;                    // [look_hold_rows][2][2B + 4]: per row two held blocks taken in turn, each with its peak
+    int look_hold_rows = 0;                   // rows d_lhold has
+    int look_parity = 0;                      // which of a row's two held blocks the last run left
+    DevBuf<float> d_lstage;                   // [rows][K - 1][2B] of the run in hand: scratch
+    size_t look_stage_cap = 0;                // floats it holds
+    bool last_look = false;                   // the last run's stage was the look-ahead one (jf_debug_last_kernels)
 
     // HRTF SETS (jf_engine_add_hrtf_set, jf_source_set_hrtf).  d_htab holds n_sets sets one behind the other,
     // set j in rows j n_rows .. (j + 1) n_rows - 1 (no pre-interpolated rows once n_sets > 1: interp_avail is false for good).

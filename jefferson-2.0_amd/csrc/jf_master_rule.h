@@ -8,8 +8,8 @@
 // The section is, in order, a master gain, a SAFETY limiter and meters.  The limiter is a brick-wall limiter at BLOCK
 // granularity: it looks at the peak of a whole block, turns the whole block down at once when that peak is over the ceiling
 // (nothing of an attacking block escapes) and lets the gain come back by `r` per block, ramped inside the block.  It keeps a
-// listener's mix below full scale when ten people talk at once; it has no look-ahead, no knee and no programme-dependent
-// release, and is not a mastering tool.
+// listener's mix below full scale when ten people talk at once; it has no look-ahead (that is the per-bus option at the end
+// of this file), no knee and no programme-dependent release, and is not a mastering tool.
 //
 // Per bus: m_prev (the master gain the last rendered block ended on), m_new (the gain asked for), c (the ceiling; 0: limiter
 // off), r (release: gain regained per block, 0 < r <= 1), and the state g_prev (the limiter gain at the end of the last
@@ -93,6 +93,29 @@ JF_MASTER_HD float master_out(float a, float v, float c) {
     if (!(c > 0.0f)) return v;
     const float y = a * v;
     return master_min(master_max(y, -c), c);
+}
+
+// LOOK-AHEAD (jf_bus_set_lookahead): the bus's output is ONE BLOCK LATE, and the limiter gain of the block that
+// goes out runs as a ramp from the gain the block before ended on to a gain that is already low enough for the block that comes
+// after it -- no gain step on an attack.  Further state per bus: the held block h [2B] (zeros at first) and its peak p_h (0).
+// Block k of the stream, x[n][ch]:
+//   1. v = m[n] * x                                  (step 1 above, the ramp on a call's first block included)
+//   2. p = max |v|
+//   3. t_h = master_target(p_h, c), t = master_target(p, c)        (both with the CURRENT ceiling)
+//   4. e = master_step(min(t_h, t), g_prev, r, c)                  (limiter off: 1)
+//   5. a[n] = master_look_env(g_prev, e, f[n]):  d = e - g_prev, s = d * f, a = g_prev + s;  e < g_prev: a = max(e, a), else
+//      a = min(e, a) -- a never leaves the interval between g_prev and e, and ends the block on e
+//   6. out[n][ch] = master_out(a[n], h[n][ch], c)                  (the HELD block; the clamp stays)
+//   7. meters {peak_in = p, peak_out = max |out|, sumsq_out, gain = e}
+//   8. h := v, p_h := p, g_prev := e
+// g_prev <= t_h always (the step before took the min with it) and e <= t_h, so a |h| <= t_h p_h <= c up to rounding, which the
+// clamp removes.  With c = 0 and m = 1 out is the block before, bit for bit.  The recurrence of step 4 is sequential in float32.
+JF_MASTER_HD float master_look_env(float g_prev, float e, float f) {
+    JF_MASTER_NO_CONTRACT
+    const float d = e - g_prev;
+    const float s = d * f;
+    const float a = g_prev + s;
+    return e < g_prev ? master_max(e, a) : master_min(e, a);
 }
 
 }  // namespace jf
