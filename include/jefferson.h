@@ -1020,6 +1020,65 @@ int jf_source_set_priority(jf_engine *e, int src, int priority);
 int jf_source_priority(const jf_engine *e, int src);
 int jf_source_heard(jf_engine *e, int n_blocks, float *out /* [n_sources][n_blocks][2] = {env, keep as 0 or 1} */);
 
+/* ---- talker levelling: a per-source automatic gain, run on the GPU --------------- */
+
+/*
+ * The reference's callback loops over every SoundSource (Audio.cu:98), adds each at unit weight (Audio.cu:109-110) and reports
+ * clipping afterwards (Audio.cu:111-113): a quiet microphone stays quiet and a hot one stays hot.  Here every source can carry a
+ * LEVELLER: a gain a[k] per block that follows target / level of the source's own input, bounded in range and in speed, applied
+ * by the gain stage as it stands.
+ *
+ * THE RULE (csrc/jf_level_rule.h; float32 throughout, one rounding per written operation, the division correctly rounded, never
+ * fused).  Per source: jf_leveller {target T: a linear peak, 0 = off, the default; floor F: the gain is frozen below it;
+ * min_gain; max_gain; fall: the factor per block when turning down; rise: the factor per block when turning up} and, on the
+ * device only, the state {a_prev, initially 1}.  p[k] is the level the voice gates measure: the peak of what block k appends to
+ * the source's input (a follower reads its root's).  For each block, in this order:
+ *     T == 0                      a[k] = 1                       (and the state is set to 1)
+ *     !(p >= F)                   a[k] = a[k-1]                  (hold: silence and noise are not pumped up; a NaN level holds)
+ *     else  w = T / p;  w = min(max(w, min_gain), max_gain)
+ *           w <  a[k-1]:  d = fl32(a[k-1] * fall);  a[k] = w >= d ? w : d
+ *           else          u = fl32(a[k-1] * rise);  a[k] = w <= u ? w : u
+ *   The gain stage sees g_lv[k][s] = fl32(g_in[k][s] * a[k]) and g_lv[-1][s] = fl32(g_in[-1][s] * a_prev), g_in being what the
+ *   stage before handed on (the gain the gates left, or what a voice limit left of it); after the run a_prev := a[K-1].
+ * CONSEQUENCES.  a[k] is reached at the END of block k -- the reference's crossfade (kernels.cu:132-137) ramps g_lv[k-1] ->
+ * g_lv[k] -- so there is no gain step anywhere.  An onset into a high gain overshoots for one block, by construction: there is
+ * no look-ahead, because a block's level is known only when the block is there; the bus limiter (jf_bus_set_limiter) is the
+ * safety for that.  With every a at 1, g_lv is g_in bit for bit.  The gain is the SOURCE's: parameters and state are per
+ * source, like a gate's, so two followers of one talker may be levelled differently.  Room sends stay pre-fader and are not
+ * levelled; the voice ranking keeps reading the raw level; a block whose gate is closed at both ends is still skipped.  A
+ * leveller taken away (T = 0) while another keeps the engine active ramps back to 1 over one block; when the last one goes,
+ * every gain is 1 at once, as taking a gate away does.  The state lives on the device and every run continues from the one
+ * before: a stream gives the same bits however it is cut into calls, jf_batch_run included.
+ *
+ * jf_source_set_leveller(e, src, lv) / jf_sources_set_leveller(e, lv) (every source) / jf_source_leveller (reads them back;
+ *   target is 0 before anything was set).  Accepted only if every value is finite; T == 0, or 2^-60 <= F <= T <= 2^24;
+ *   0 < min_gain <= 1 <= max_gain <= 1024; 0 < fall < 1 < rise <= 2 -- T / p is then never a division by zero and never
+ *   overflows.  Anything else, a NULL or a bad index: JF_ERR_ARG, and nothing changes.
+ * jf_source_level_gains(e, n_blocks, out): of the LAST RENDERED CALL, out[n_sources][n_blocks] = a[k].  Kept while
+ *   jf_engine_set_input_meters is on and some source has a leveller; it travels like jf_source_levels, a jf_batch_run's results
+ *   included.  JF_ERR_STATE if input meters are off, no source has a leveller or nothing has been rendered so; JF_ERR_ARG for
+ *   another count.
+ * The setters are setters like jf_source_set_cartesian: callable from another thread, latched by the next processing call that
+ * is not paused.  JF_ERR_STATE for a leveller while a jf_reverb_set_ir response is set, and for jf_reverb_set_ir while a source
+ * has one.  jf_source_reset, jf_source_set_signal and jf_source_set_live take the source's a_prev back to 1; the parameters
+ * stay.  Paused calls latch nothing and advance nothing.
+ *
+ * COST.  An engine is ACTIVE for levelling while some source has T > 0; it then counts as active for the voice gates (above)
+ * whether or not a source has a gate, its per-block calls take the batch pipeline with one block, and one more small kernel
+ * runs ahead of desc_gain_kernel.  An engine in which no source has T > 0 allocates nothing for levelling,
+ * launches exactly what it launched and renders the same bits.
+ *
+ * Not offered: look-ahead; an RMS or loudness-weighted detector; ranking by the levelled level; levelled room sends; levelling
+ * inside the one-launch real-time kernel; jefferson_group.h, jf_render and jf_ctest have no option for it.
+ */
+typedef struct jf_leveller {
+    float target, floor, min_gain, max_gain, fall, rise;
+} jf_leveller;
+int jf_source_set_leveller(jf_engine *e, int src, const jf_leveller *lv);
+int jf_sources_set_leveller(jf_engine *e, const jf_leveller *lv);
+int jf_source_leveller(const jf_engine *e, int src, jf_leveller *out);
+int jf_source_level_gains(jf_engine *e, int n_blocks, float *out /* [n_sources][n_blocks] */);
+
 /* ---- listener poses: head position and orientation per output bus --------------- */
 
 /*

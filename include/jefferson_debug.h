@@ -325,6 +325,16 @@ int jf_debug_voice_select(const float *peak, const int *root, const int *bus, co
  * pair's own ~7 us per run included; 0 while no bus had a limit. */
 int jf_profile_read_voices(jf_engine *e, double *voice_ms);
 
+/* Talker levelling (include/jefferson.h): the rule level_scan_kernel applies to ONE source, on the host -- the
+ * header the kernel compiles (csrc/jf_level_rule.h), so the CPU suite checks it against a NumPy model.  peaks [n] are the block
+ * levels, lv the source's parameters; *a_io is the state a_prev before the sequence and, on return, after it (1 for a source
+ * that starts); a_out [n] receives a[k].  With target == 0 every a_out is 1 and the state becomes 1.  Pure host code: no engine,
+ * no GPU.  JF_ERR_ARG for a NULL pointer, a negative n (n may be 0) or parameters the setters would refuse. */
+int jf_debug_level_scan(const float *peaks, int n, const jf_leveller *lv, float *a_io, float *a_out);
+/* ms in level_scan_kernel since jf_profile_enable(e, 2), the event pair's own ~7 us per run included; 0 while no source had a
+ * leveller. */
+int jf_profile_read_level(jf_engine *e, double *level_ms);
+
 /* Stream sources (include/jefferson.h).  jf_debug_stream_seek: the stream source's next output is t_out (up to
  * 2^53); the queue is dropped, the history is zeros and the next push is frame i(t_out - 1) + 1 of the stream -- what a stream
  * that has run for t_out samples and has been fed zeros so far looks like (positions beyond 2^31 without hours of audio).

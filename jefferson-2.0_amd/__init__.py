@@ -183,6 +183,12 @@ _SIGS = {
     "jf_source_heard": (C.c_int, [C.c_void_p, C.c_int, _f]),
     "jf_debug_voice_select": (C.c_int, [_f, _i, _i, _i, _i, _f, _i, C.c_int, C.c_int, C.c_int, _f, _f, _f, _i, _f, _i]),
     "jf_profile_read_voices": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "jf_source_set_leveller": (C.c_int, [C.c_void_p, C.c_int, _f]),        # (jf_leveller is six floats)
+    "jf_sources_set_leveller": (C.c_int, [C.c_void_p, _f]),
+    "jf_source_leveller": (C.c_int, [C.c_void_p, C.c_int, _f]),
+    "jf_source_level_gains": (C.c_int, [C.c_void_p, C.c_int, _f]),
+    "jf_debug_level_scan": (C.c_int, [_f, C.c_int, _f, _f, _f]),
+    "jf_profile_read_level": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "jf_engine_add_hrtf_set": (C.c_int, [C.c_void_p, _f, C.c_int]),
     "jf_engine_add_hrtf_sofa": (C.c_int, [C.c_void_p, C.c_char_p, C.c_float]),
     "jf_num_hrtf_sets": (C.c_int, [C.c_void_p]),
@@ -584,6 +590,25 @@ def gate_scan(peaks, open, close, hold, state=(0, 0)):
     if rc:
         raise JfError(rc, "gate_scan")
     return out[:len(peaks)], (int(st[0]), int(st[1]))
+
+
+LEVELLER_FIELDS = ("target", "floor", "min_gain", "max_gain", "fall", "rise")
+
+
+def _leveller(target, floor=0.0, min_gain=1.0, max_gain=1.0, fall=0.5, rise=2.0):
+    """jf_leveller as the six float32 the boundary takes"""
+    return np.array([target, floor, min_gain, max_gain, fall, rise], np.float32)
+
+
+def level_scan(peaks, target, floor=0.0, min_gain=1.0, max_gain=1.0, fall=0.5, rise=2.0, a_prev=1.0):
+    """jf_debug_level_scan (host logic only): the levelling rule over a sequence of block levels ->
+    (a [n] float32, a_prev after the sequence)"""
+    peaks = np.ascontiguousarray(peaks, np.float32).ravel()
+    st, out = np.array([a_prev], np.float32), np.zeros(max(len(peaks), 1), np.float32)
+    rc = lib().jf_debug_level_scan(_fp(peaks), len(peaks), _fp(_leveller(target, floor, min_gain, max_gain, fall, rise)), _fp(st), _fp(out))
+    if rc:
+        raise JfError(rc, "level_scan")
+    return out[:len(peaks)], st[0]
 
 
 def voice_select(peak, root, bus, priority, max_voices, release, g_eff, g_eff_prev, env_prev=None, heard_prev=None, snap=None):
@@ -1260,6 +1285,36 @@ class Engine:
         """ms in the voice limits' two kernels since profile_enable(2)"""
         r = C.c_double()
         self._chk(lib().jf_profile_read_voices(self.h, C.byref(r)))
+        return r.value
+
+    # ---- talker levelling (include/jefferson.h: "talker levelling") ----
+    def set_leveller(self, s, target, floor=0.0, min_gain=1.0, max_gain=1.0, fall=0.5, rise=2.0):
+        """source s is levelled towards the linear peak `target` (0: off): frozen below `floor`, within min_gain .. max_gain, by at
+        most `fall` / `rise` a block (jf_source_set_leveller)"""
+        self._chk(lib().jf_source_set_leveller(self.h, int(s), _fp(_leveller(target, floor, min_gain, max_gain, fall, rise))))
+
+    def set_levellers(self, target, floor=0.0, min_gain=1.0, max_gain=1.0, fall=0.5, rise=2.0):
+        """every source (jf_sources_set_leveller)"""
+        self._chk(lib().jf_sources_set_leveller(self.h, _fp(_leveller(target, floor, min_gain, max_gain, fall, rise))))
+
+    def leveller(self, s):
+        """dict(target, floor, min_gain, max_gain, fall, rise); target is 0 before anything was set"""
+        out = np.zeros(6, np.float32)
+        self._chk(lib().jf_source_leveller(self.h, int(s), _fp(out)))
+        return dict(zip(LEVELLER_FIELDS, (float(v) for v in out)))
+
+    def level_gains(self, n_blocks=1):
+        """the last rendered call's levelling gains a[k], [S][n_blocks] (jf_source_level_gains)"""
+        out = np.zeros((self.S, int(n_blocks)), np.float32)
+        self._chk(lib().jf_source_level_gains(self.h, int(n_blocks), _fp(out)))
+        return out
+
+    level_scan = staticmethod(level_scan)
+
+    def profile_read_level(self):
+        """ms in level_scan_kernel since profile_enable(2)"""
+        r = C.c_double()
+        self._chk(lib().jf_profile_read_level(self.h, C.byref(r)))
         return r.value
 
     def room_wet(self, n_blocks):

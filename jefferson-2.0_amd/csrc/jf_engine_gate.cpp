@@ -19,6 +19,8 @@ bool gate_wanted(jf_engine *e) {
         if (g.open > 0.0f) return true;
     for (const int n : e->vc_N)
         if (n > 0) return true;  // (a voice limit counts as a gate: jf_engine_voice.cpp)
+    for (const LevelPar &lp : e->lv_par)
+        if (lp.target > 0.0f) return true;  // (and so does a leveller: jf_engine_level.cpp)
     return false;
 }
 
@@ -72,13 +74,14 @@ static int gate_latch_active(jf_engine *e) {
 }
 
 int gate_latch(jf_engine *e) {
-    e->gate_on = e->gate_meters = e->voice_on = false;
-    bool voices = false;
+    e->gate_on = e->gate_meters = e->voice_on = e->level_on = false;
+    bool voices = false, levellers = false;
     {
         std::lock_guard<std::mutex> lk(e->pos_mu);
         voices = voice_latch_host(e);  // a bus with a voice limit: the stage runs whether or not a source has a gate
-        if (e->gt_par.empty() && !e->levels_want && !voices) return JF_OK;  // nothing was ever set
-        bool active = e->levels_want || voices;
+        levellers = level_latch_host(e);  // ... and so it does for a source with a leveller
+        if (e->gt_par.empty() && !e->levels_want && !voices && !levellers) return JF_OK;  // nothing was ever set
+        bool active = e->levels_want || voices || levellers;
         for (size_t s = 0; s < e->gt_par.size() && !active; s++) active = e->gt_par[s].open > 0.0f;
         if (!active) return JF_OK;  // every gate was set back to open = 0, no meters
         if (e->gt_par.empty())
@@ -89,8 +92,10 @@ int gate_latch(jf_engine *e) {
     }
     int rc = gate_latch_active(e);
     if (rc == JF_OK && voices) rc = voice_latch_active(e);
+    if (rc == JF_OK && levellers) rc = level_latch_active(e);
     e->gate_on = rc == JF_OK;
     e->voice_on = e->gate_on && voices;
+    e->level_on = e->gate_on && levellers;
     return rc;
 }
 
@@ -118,6 +123,12 @@ int run_gate_stage(jf_engine *e, int p, int K, int canon, bool timed) {
         if (rc) return rc;
         e->vc_reported = e->gate_meters;
     }
+    e->last_level = e->lv_reported = false;
+    if (e->level_on) {  // the sources' levellers: g_eff and g_eff_prev times a, in place (jf_engine_level.cpp)
+        rc = run_level_stage(e, peak, g_eff, g_eff_prev, K, timed);
+        if (rc) return rc;
+        e->lv_reported = e->gate_meters;
+    }
     rc = e->tm_gain.begin(e, timed);
     if (rc) return rc;
     JF_HIP(e, launch_desc_gain(e->d_desc, g_eff_prev, g_eff_prev, g_eff, e->S, K, canon, e->stream));
@@ -128,13 +139,14 @@ int run_gate_stage(jf_engine *e, int p, int K, int canon, bool timed) {
     return JF_OK;
 }
 
-void gate_settle(jf_engine *e) { e->gate_on = e->voice_on = false; }
+void gate_settle(jf_engine *e) { e->gate_on = e->voice_on = e->level_on = false; }
 
 // src < 0: every source.  Nothing to close in an engine that never ran the stage: every gate is closed there.  The source's
-// voice envelope starts over with it.
+// voice envelope starts over with it, and it is levelled from 1 again.
 int gate_close_source(jf_engine *e, int src) {
     {
-        const int rc = voice_reset_source(e, src);
+        int rc = voice_reset_source(e, src);
+        if (rc == JF_OK) rc = level_reset_source(e, src);
         if (rc) return rc;
     }
     if (!e->d_gt_state) return JF_OK;
@@ -150,7 +162,11 @@ int gate_levels_copy(jf_engine *e, int K) {
     const size_t KS = (size_t)e->maxK * (size_t)e->S, n = (size_t)K * (size_t)e->S;
     for (size_t a = 0; a < 3; a++)
         JF_HIP(e, hipMemcpyAsync(e->h_levels + a * KS, e->d_gt_lv + a * KS, sizeof(float) * n, hipMemcpyDeviceToHost, e->stream));
-    return e->vc_reported ? voice_heard_copy(e, K) : JF_OK;
+    if (e->vc_reported) {
+        const int rc = voice_heard_copy(e, K);
+        if (rc) return rc;
+    }
+    return e->lv_reported ? level_gains_copy(e, K) : JF_OK;
 }
 
 // h_levels holds a run: blocks b0 .. b0 + K of a call of n_blocks, into the call's [S][n_blocks][3]
@@ -166,6 +182,10 @@ void gate_levels_land(jf_engine *e, int K, int b0, int n_blocks) {
         voice_heard_land(e, K, b0, n_blocks);
     else
         e->heard_blocks = 0;
+    if (e->lv_reported)
+        level_gains_land(e, K, b0, n_blocks);
+    else
+        e->gains_blocks = 0;
 }
 
 // what the last jf_batch_run left on the device: brought over once, the stream waited for

@@ -28,8 +28,11 @@
 //   jf_engine_output.cpp bus outputs: the buses' rings and resampler positions, the jobs a processing call writes for the one
 //                         kernel behind the master section (run_output_stage, jf_output.hip), the host twins of the rule and
 //                         jf_bus_set_output / jf_bus_pull
+//   jf_engine_level.cpp   talker levelling: the sources' levellers, what a processing call latches of them (inside gate_latch), the
+//                         kernel run_gate_stage launches ahead of desc_gain_kernel (run_level_stage, jf_level.hip) and
+//                         jf_source_set_leveller / jf_source_level_gains
 //   jf_engine_debug.cpp   every entry point of include/jefferson_debug.h (taps, timing hooks, tuning switches, accessors)
-// What the five latched controls (gain, masters, sets, gates, voice limits) share is here once: StagedRing (their asynchronous uploads), StageTimer
+// What the six latched controls (gain, masters, sets, gates, voice limits, levellers) share is here once: StagedRing (their asynchronous uploads), StageTimer
 // (the event pairs of a stage that only some runs launch), CallLatches (a processing call's latch and settlement of all four).
 // Not part of any interface: nothing outside csrc/ includes this file.
 #ifndef JF_ENGINE_INTERNAL_H
@@ -57,6 +60,7 @@
 #include "jf_gain_rule.h"
 #include "jf_gate_rule.h"
 #include "jf_host.h"
+#include "jf_level_rule.h"
 #include "jf_output.h"
 #include "jf_pose_rule.h"
 #include "jf_room.h"
@@ -140,6 +144,9 @@ hipError_t launch_voice_env(const float *d_peak, const int *d_root, const int *d
                             int K, int n_buses, int use_snap, hipStream_t st);
 hipError_t launch_voice_select(const int *d_members, const int *d_seg, const int *d_prio, const VoiceBus *d_par, const float *d_env,
                                float *d_g_eff, int *d_heard_prev, float *d_heard, int S, int K, int n_buses, hipStream_t st);
+// talker levelling (jf_level.hip): g_eff and g_eff_prev times every source's automatic gain, in place; d_par is six planes of [S]
+hipError_t launch_level_scan(const float *d_par, const int *d_root, const float *d_peak, float *d_g_eff, float *d_g_eff_prev,
+                             float *d_a_prev, float *d_a, int S, int K, hipStream_t st);
 }  // namespace jf
 
 using namespace jf;
@@ -621,6 +628,28 @@ struct jf_engine : ReverbSetup {
     bool last_voice = false;                  // the last run of the gate stage launched the two kernels (jf_debug_last_kernels)
     StageTimer tm_voice;                      // profiling 2: around the two kernels (jf_profile_read_voices)
 
+    // TALKER LEVELLING (jf_source_set_leveller).  Per source a leveller (LevelPar: jf_level_rule.h) and, on the
+    // device ONLY, the state {a_prev}.  While the engine is ACTIVE for levelling -- some source has target > 0 -- it counts as
+    // gate-active, and run_gate_stage launches level_scan_kernel (jf_level.hip) behind the scan and the voice stage and ahead of
+    // desc_gain_kernel: it rewrites g_eff in place.  The host state is under pos_mu like `pos` and empty until first use; an
+    // engine in which no source has target > 0 allocates nothing below and launches nothing (gate_latch: level_latch_host).
+    std::vector<LevelPar> lv_par;             // [S] (empty: no leveller was ever set, every target 0)
+    std::vector<float> gains_last;            // [S][gains_blocks] a[k] of the last rendered call, on the host
+    int gains_blocks = 0;                     // (0: none; valid while it equals levels_blocks)
+    // what the processing call in hand latched (its thread's alone)
+    bool level_on = false;                    // the call is active for levelling
+    std::vector<float> run_lv;                // [6][S] the call's parameters as the device holds them, a plane per field
+    bool lv_idle = false;                     // a call was latched without a leveller since the stage last ran: every state is 1 again
+    bool lv_reported = false;                 // the last run of the gate stage left a[K][S] for the input meters' copies
+    DevBuf<float> d_lv_par;                   // [6][S]
+    std::vector<float> dev_lv;                // what it holds (empty: nothing yet)
+    DevBuf<float> d_lv_a;                     // [maxK][S]: a of a run
+    DevBuf<float> d_lv_aprev;                 // [S]
+    StagedRing<float> lv_ring;                // slots of [6][S]: the asynchronous copy to d_lv_par
+    PinnedBuf<float> h_lv_a;                  // [maxK][S] where a run's a lands on the host
+    bool last_level = false;                  // the last run of the gate stage launched the kernel (jf_debug_last_kernels)
+    StageTimer tm_level;                      // profiling 2: around the kernel (jf_profile_read_level)
+
     // STREAM SOURCES (jf_source_set_stream, jf_source_push).  A stream source is internally a live source that
     // takes no row of `in`: the same live_len device buffer named by its record in d_sigs, filled at the source's play position
     // by stream_resample_kernel (jf_stream.hip) from the source's FIFO -- pinned, mapped host memory the pushes write and the
@@ -1007,6 +1036,20 @@ JF_INTERNAL int voice_heard_copy(jf_engine *e, int K);
 JF_INTERNAL void voice_heard_land(jf_engine *e, int K, int b0, int n_blocks);
 JF_INTERNAL void voice_set_buses(jf_engine *e, int n_buses);
 JF_INTERNAL bool voice_wanted(jf_engine *e);
+// talker levelling (jf_engine_level.cpp), wired like the voice limits.  gate_latch calls level_latch_host under pos_mu (the
+// call's parameters; true while some source has target > 0: the engine then counts as gate-active) and level_latch_active behind
+// the gates' own buffers (allocation, the copy that differs).  run_level_stage: from run_gate_stage behind the scan and the
+// voice stage, ahead of desc_gain_kernel, while e->level_on.  level_reset_source: a reset or a new signal takes the source's
+// a_prev back to 1 through the engine's stream (src < 0: every one).  level_gains_copy / level_gains_land travel with
+// gate_levels_copy / gate_levels_land.  level_wanted: some source has a leveller (jf_reverb_set_ir refuses then, through
+// gate_wanted).
+JF_INTERNAL bool level_latch_host(jf_engine *e);
+JF_INTERNAL int level_latch_active(jf_engine *e);
+JF_INTERNAL int run_level_stage(jf_engine *e, const float *peak, float *g_eff, float *g_eff_prev, int K, bool timed);
+JF_INTERNAL int level_reset_source(jf_engine *e, int src);
+JF_INTERNAL int level_gains_copy(jf_engine *e, int K);
+JF_INTERNAL void level_gains_land(jf_engine *e, int K, int b0, int n_blocks);
+JF_INTERNAL bool level_wanted(jf_engine *e);
 // the three pointers run_gain_stage hands desc_gain_kernel for the next run of K blocks (all null unless e->gain_on), and the
 // step to the run after it (jf_engine_gain.cpp)
 JF_INTERNAL void gain_run_gains(const jf_engine *e, const float **g_prev, const float **g_new, const float **g_traj);
