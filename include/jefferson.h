@@ -1079,6 +1079,65 @@ int jf_sources_set_leveller(jf_engine *e, const jf_leveller *lv);
 int jf_source_leveller(const jf_engine *e, int src, jf_leveller *out);
 int jf_source_level_gains(jf_engine *e, int n_blocks, float *out /* [n_sources][n_blocks] */);
 
+/* ---- hearing range: talkers out of earshot fade out and are skipped --------------- */
+
+/*
+ * The reference's callback loops over every SoundSource (Audio.cu:98) and adds each one, however far away it stands
+ * (Audio.cu:109-113): its distance law only makes a far talker quiet, at the full cost of rendering it.  Here every output bus
+ * can carry a HEARING RANGE {near, far} of its listener, in the units of the positions: a talker within `near` is heard in full,
+ * one beyond `far` not at all -- and costs nothing -- and in between the gain falls linearly.
+ *
+ * THE RULE (csrc/jf_range_rule.h; double arithmetic on the record's floats, one rounding to float, never fused).  For block k
+ * and source s on a bus with a range, with (x, y, z) the HEAD-RELATIVE position of the record the spatialiser reads -- whether
+ * jf_process_batch handed it over, a setter latched it, or the GPU formed it from a world position and the listener's pose:
+ *     r = sqrt(x x + y y + z z)
+ *     r <= near     h[k][s] = 1
+ *     !(r < far)    h[k][s] = 0                               (NaN and infinite coordinates are here: the rule is total)
+ *     else          h[k][s] = (far - r) / (far - near)
+ *   h = 1 for a source that is EXEMPT (a moderator, an announcement), for a bus without a range (far == 0, the default) and for
+ *   a source in the head's centre.  The gain stage sees g[k][s] h[k][s] and, for the block before the run, g[-1][s] h_prev[s];
+ *   h_prev is device state, the h of the last rendered block, 1 at the start.
+ * CONSEQUENCES.  h[k] is reached at the END of block k -- the reference's crossfade (kernels.cu:132-137) ramps to it -- so
+ * nothing ever steps: a talker who walks out of range fades over the ramp and is then skipped by the spatialiser, one who walks
+ * in fades in from 0.  The range is applied AHEAD of the voice limits (jf_bus_set_voices): a talker out of earshot takes no
+ * place, so the N loudest are the N loudest within earshot -- the ranking itself keeps reading the raw envelope.  The leveller
+ * keeps reading the raw level; room sends stay pre-fader: a talker out of range still excites the room.  The built-in distance
+ * law is untouched and applies on top.  A range taken away while another bus keeps the stage running ramps back to 1 over one
+ * block; when the last one goes, every h is 1 at once, as taking a leveller away does.  The state lives on the device and every
+ * run continues from the one before: a stream gives the same bits however it is cut into calls, jf_batch_run included.
+ *
+ * jf_bus_set_range(e, bus, near, far) / jf_bus_range (reads them back; both 0 before anything was set).  Accepted only if both
+ *   are finite and near == far == 0 (off) or 0 <= near < far <= 2^20.  Anything else, a NULL or a bad index: JF_ERR_ARG, and
+ *   nothing changes.
+ * jf_source_set_range_exempt(e, src, on) / jf_source_range_exempt (0 or 1; JF_ERR_ARG for a bad index): an exempt source is
+ *   heard at any distance on whatever bus it is.
+ * jf_source_range_gains(e, n_blocks, out): of the LAST RENDERED CALL, out[n_sources][n_blocks] = h[k].  Kept while
+ *   jf_engine_set_input_meters is on and some bus has a range; it travels like jf_source_levels, a jf_batch_run's results
+ *   included.  JF_ERR_STATE if input meters are off, no bus has a range or nothing has been rendered so; JF_ERR_ARG for another
+ *   count.
+ * jf_range_gain(near, far, x, y, z, h_out): the rule without an engine -- the host twin of the GPU's kernel, as
+ *   jf_position_from_world is for the poses.  JF_ERR_ARG for a NULL or a range the setter would refuse; *h_out is then untouched.
+ * The setters are setters like jf_source_set_cartesian: callable from another thread, latched by the next processing call that
+ * is not paused.  JF_ERR_STATE for a range while a jf_reverb_set_ir response is set, and for jf_reverb_set_ir while a bus has
+ * one.  jf_source_reset, jf_source_set_signal and jf_source_set_live take the source's h_prev back to 1; the ranges stay.
+ * Paused calls latch nothing and advance nothing.
+ *
+ * COST.  An engine is ACTIVE for ranges while some bus has far > 0; it then counts as active for the voice gates (above)
+ * whether or not a source has a gate, its per-block calls take the batch pipeline with one block, and one more small kernel
+ * runs behind gate_scan_kernel.  An engine in which no bus has far > 0 allocates nothing for ranges, launches
+ * exactly what it launched and renders the same bits.
+ *
+ * Not offered: a directivity cone per talker; a range per (listener, talker) pair; ranking by distance-weighted level;
+ * range-gated room sends; a curve other than the linear ramp; a replacement of the built-in distance law; ranges inside the
+ * one-launch real-time kernel; jefferson_group.h, jf_render and jf_ctest have no option for it.
+ */
+int jf_bus_set_range(jf_engine *e, int bus, float range_near, float range_far);
+int jf_bus_range(const jf_engine *e, int bus, float *range_near, float *range_far);
+int jf_source_set_range_exempt(jf_engine *e, int src, int on);
+int jf_source_range_exempt(const jf_engine *e, int src);
+int jf_source_range_gains(jf_engine *e, int n_blocks, float *out /* [n_sources][n_blocks] */);
+int jf_range_gain(float range_near, float range_far, float x, float y, float z, float *h_out);
+
 /* ---- listener poses: head position and orientation per output bus --------------- */
 
 /*

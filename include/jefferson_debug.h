@@ -335,6 +335,22 @@ int jf_debug_level_scan(const float *peaks, int n, const jf_leveller *lv, float 
  * leveller. */
 int jf_profile_read_level(jf_engine *e, double *level_ms);
 
+/* Hearing range (include/jefferson.h): the rule range_gain_kernel applies to one run, on the host -- the header
+ * the kernel compiles (csrc/jf_range_rule.h), so the CPU suite checks it against a NumPy model.  pos [n_blocks][n_sources][5]
+ * are the run's records {ele, azi, x, y, z}; par [2][n_sources] is near, then far, per SOURCE as the engine resolves them ({0, 0}
+ * for an exempt source or a bus without a range); h_prev_io [n_sources] is the state before the run and, on return, after it (1
+ * for a source that starts; n_blocks == 0 leaves it); h_out [n_blocks][n_sources] receives h.  What the gain stage then sees is
+ * g[k][s] h[k][s] and g[-1][s] h_prev[s].  Pure host code: no engine, no GPU.  JF_ERR_ARG for a NULL pointer, a negative
+ * n_blocks, n_sources <= 0 or a pair the setter would refuse; nothing is written then. */
+int jf_debug_range_scan(const float *pos, int n_blocks, int n_sources, const float *par, float *h_prev_io, float *h_out);
+/* jf_debug_range_bytes: bytes of device and pinned memory the engine holds for ranges -- the two planes, the state's two, a
+ * run's h and where it lands on the host.  0 in an engine in which no processing call was ever latched with a range; they stay
+ * when the last range goes. */
+long long jf_debug_range_bytes(const jf_engine *e);
+/* ms in range_gain_kernel since jf_profile_enable(e, 2), the event pair's own ~7 us per run included; 0 while no bus had a
+ * range. */
+int jf_profile_read_range(jf_engine *e, double *range_ms);
+
 /* Stream sources (include/jefferson.h).  jf_debug_stream_seek: the stream source's next output is t_out (up to
  * 2^53); the queue is dropped, the history is zeros and the next push is frame i(t_out - 1) + 1 of the stream -- what a stream
  * that has run for t_out samples and has been fed zeros so far looks like (positions beyond 2^31 without hours of audio).

@@ -189,6 +189,15 @@ _SIGS = {
     "jf_source_level_gains": (C.c_int, [C.c_void_p, C.c_int, _f]),
     "jf_debug_level_scan": (C.c_int, [_f, C.c_int, _f, _f, _f]),
     "jf_profile_read_level": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "jf_bus_set_range": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float]),
+    "jf_bus_range": (C.c_int, [C.c_void_p, C.c_int, _f, _f]),
+    "jf_source_set_range_exempt": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "jf_source_range_exempt": (C.c_int, [C.c_void_p, C.c_int]),
+    "jf_source_range_gains": (C.c_int, [C.c_void_p, C.c_int, _f]),
+    "jf_range_gain": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _f]),
+    "jf_debug_range_scan": (C.c_int, [_f, C.c_int, C.c_int, _f, _f, _f]),
+    "jf_profile_read_range": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "jf_debug_range_bytes": (C.c_longlong, [C.c_void_p]),
     "jf_engine_add_hrtf_set": (C.c_int, [C.c_void_p, _f, C.c_int]),
     "jf_engine_add_hrtf_sofa": (C.c_int, [C.c_void_p, C.c_char_p, C.c_float]),
     "jf_num_hrtf_sets": (C.c_int, [C.c_void_p]),
@@ -609,6 +618,31 @@ def level_scan(peaks, target, floor=0.0, min_gain=1.0, max_gain=1.0, fall=0.5, r
     if rc:
         raise JfError(rc, "level_scan")
     return out[:len(peaks)], st[0]
+
+
+def range_gain(near, far, x, y, z):
+    """jf_range_gain (host logic only): how much a listener with the hearing range {near, far} hears of a talker at the
+    head-relative (x, y, z) -> float32; JfError for a range the setter would refuse"""
+    out = np.zeros(1, np.float32)
+    rc = lib().jf_range_gain(float(near), float(far), float(x), float(y), float(z), _fp(out))
+    if rc:
+        raise JfError(rc, "range_gain")
+    return out[0]
+
+
+def range_scan(pos, near, far, h_prev=None):
+    """jf_debug_range_scan (host logic only): the hearing-range rule over one run.  pos [K][S][5] records; near, far [S] per
+    source ({0, 0}: exempt or no range); h_prev [S] (ones) -> (h [K][S] float32, h_prev after the run)"""
+    pos = np.ascontiguousarray(pos, np.float32)
+    K, S = pos.shape[0], pos.shape[1]
+    par = np.ascontiguousarray(np.stack([np.broadcast_to(np.asarray(near, np.float32), (S,)),
+                                         np.broadcast_to(np.asarray(far, np.float32), (S,))]), np.float32)
+    st = np.ones(S, np.float32) if h_prev is None else np.array(h_prev, np.float32).reshape(S).copy()
+    out = np.zeros((max(K, 1), S), np.float32)
+    rc = lib().jf_debug_range_scan(_fp(pos), K, S, _fp(par), _fp(st), _fp(out))
+    if rc:
+        raise JfError(rc, "range_scan")
+    return out[:K], st
 
 
 def voice_select(peak, root, bus, priority, max_voices, release, g_eff, g_eff_prev, env_prev=None, heard_prev=None, snap=None):
@@ -1315,6 +1349,45 @@ class Engine:
         """ms in level_scan_kernel since profile_enable(2)"""
         r = C.c_double()
         self._chk(lib().jf_profile_read_level(self.h, C.byref(r)))
+        return r.value
+
+    # ---- hearing range (include/jefferson.h: "hearing range") ----
+    def set_range(self, bus, near, far):
+        """the listener of `bus` hears talkers within `near` in full and none beyond `far` (far = 0: off) (jf_bus_set_range)"""
+        self._chk(lib().jf_bus_set_range(self.h, int(bus), float(near), float(far)))
+
+    def range(self, bus):
+        """(near, far); both 0 before anything was set (jf_bus_range)"""
+        a, b = np.zeros(1, np.float32), np.zeros(1, np.float32)
+        self._chk(lib().jf_bus_range(self.h, int(bus), _fp(a), _fp(b)))
+        return float(a[0]), float(b[0])
+
+    def set_range_exempt(self, s, on=True):
+        """source s is heard at any distance (jf_source_set_range_exempt)"""
+        self._chk(lib().jf_source_set_range_exempt(self.h, int(s), 1 if on else 0))
+
+    def range_exempt(self, s):
+        rc = lib().jf_source_range_exempt(self.h, int(s))
+        if rc < 0:
+            self._chk(rc)
+        return bool(rc)
+
+    def range_gains(self, n_blocks=1):
+        """the last rendered call's hearing-range gains h[k], [S][n_blocks] (jf_source_range_gains)"""
+        out = np.zeros((self.S, int(n_blocks)), np.float32)
+        self._chk(lib().jf_source_range_gains(self.h, int(n_blocks), _fp(out)))
+        return out
+
+    range_scan = staticmethod(range_scan)
+
+    def range_bytes(self):
+        """device and pinned memory held for ranges (0 until a call is latched with one)"""
+        return int(lib().jf_debug_range_bytes(self.h))
+
+    def profile_read_range(self):
+        """ms in range_gain_kernel since profile_enable(2)"""
+        r = C.c_double()
+        self._chk(lib().jf_profile_read_range(self.h, C.byref(r)))
         return r.value
 
     def room_wet(self, n_blocks):

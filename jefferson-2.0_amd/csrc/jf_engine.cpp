@@ -89,7 +89,7 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
         ep = next_events(e, e->ev_prep);
         em = next_events(e, e->ev_mix);
         if (!ep || !em) return fail(e, JF_ERR_DEVICE, "hipEventCreate failed");
-        for (StageTimer *t : {&e->tm_spec, &e->tm_set, &e->tm_gain, &e->tm_master, &e->tm_gate, &e->tm_voice, &e->tm_level}) t->arm(e->ev_used);  // (the stage that runs says otherwise)
+        for (StageTimer *t : {&e->tm_spec, &e->tm_set, &e->tm_gain, &e->tm_master, &e->tm_gate, &e->tm_voice, &e->tm_level, &e->tm_range}) t->arm(e->ev_used);  // (the stage that runs says otherwise)
     }
     const long long n_items = (long long)K * e->S;
     int G = 1;
@@ -141,7 +141,7 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
     // g_eff[k][s] = gate ? g[k][s] : 0 from the inputs' levels and the same gains, and desc_gain_kernel applies that
     e->last_gain = e->last_gate = false;
     if (e->gate_on) {
-        const int rc = run_gate_stage(e, p, K, canon, timed);
+        const int rc = run_gate_stage(e, d_pos, p, K, canon, timed);
         if (rc) return rc;
     } else if (e->gain_on) {
         const int rc = run_gain_stage(e, K, canon, timed);
@@ -386,7 +386,7 @@ void destroy_engine(jf_engine *e) {
     DeviceGuard bind(e);  // (outlives the delete: the buffers are freed on the engine's device)
     if (e->rv_side) (void)hipStreamSynchronize(e->rv_side);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
-    for (auto *pool : {&e->ev_prep, &e->ev_fused, &e->ev_mix, &e->ev_reverb, &e->ev_pose, &e->tm_spec.ev, &e->tm_gain.ev, &e->tm_master.ev, &e->tm_set.ev, &e->tm_gate.ev, &e->tm_voice.ev, &e->tm_level.ev})
+    for (auto *pool : {&e->ev_prep, &e->ev_fused, &e->ev_mix, &e->ev_reverb, &e->ev_pose, &e->tm_spec.ev, &e->tm_gain.ev, &e->tm_master.ev, &e->tm_set.ev, &e->tm_gate.ev, &e->tm_voice.ev, &e->tm_level.ev, &e->tm_range.ev})
         for (auto &p : *pool) {
             (void)hipEventDestroy(p.a);
             (void)hipEventDestroy(p.b);
@@ -1081,6 +1081,7 @@ int jf_engine_set_buses(jf_engine *e, int n_buses) {
         }
         master_set_buses(e, n_buses);  // ... and their master sections, new ones are neutral
         voice_set_buses(e, n_buses);   // ... and their voice limits, new ones have none
+        range_set_buses(e, n_buses);   // ... and their hearing ranges, new ones have none
         output_set_buses(e, n_buses);  // ... and their outputs, new ones have none
         e->n_buses = n_buses;
     }

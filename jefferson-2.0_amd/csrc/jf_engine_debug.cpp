@@ -477,6 +477,7 @@ const char *jf_debug_last_kernels(jf_engine *e) {
         if (!e->last_rt && !e->last_prep_skipped) k += "prep_kernel;";
         if (!e->last_rt && e->last_set) k += "desc_set_kernel;";
         if (!e->last_rt && e->last_gate) k += "input_level_kernel;gate_scan_kernel;";
+        if (!e->last_rt && e->last_gate && e->last_range) k += "range_gain_kernel;";
         if (!e->last_rt && e->last_gate && e->last_voice) k += "voice_env_kernel;voice_select_kernel;";
         if (!e->last_rt && e->last_gate && e->last_level) k += "level_scan_kernel;";
         if (!e->last_rt && e->last_gain) k += "desc_gain_kernel;";

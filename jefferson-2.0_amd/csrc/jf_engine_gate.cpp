@@ -21,6 +21,8 @@ bool gate_wanted(jf_engine *e) {
         if (n > 0) return true;  // (a voice limit counts as a gate: jf_engine_voice.cpp)
     for (const LevelPar &lp : e->lv_par)
         if (lp.target > 0.0f) return true;  // (and so does a leveller: jf_engine_level.cpp)
+    for (size_t b = 0; 2 * b + 1 < e->rg_range.size(); b++)
+        if (e->rg_range[2 * b + 1] > 0.0f) return true;  // (and a hearing range: jf_engine_range.cpp)
     return false;
 }
 
@@ -74,14 +76,15 @@ static int gate_latch_active(jf_engine *e) {
 }
 
 int gate_latch(jf_engine *e) {
-    e->gate_on = e->gate_meters = e->voice_on = e->level_on = false;
-    bool voices = false, levellers = false;
+    e->gate_on = e->gate_meters = e->voice_on = e->level_on = e->range_on = false;
+    bool voices = false, levellers = false, ranges = false;
     {
         std::lock_guard<std::mutex> lk(e->pos_mu);
         voices = voice_latch_host(e);  // a bus with a voice limit: the stage runs whether or not a source has a gate
         levellers = level_latch_host(e);  // ... and so it does for a source with a leveller
-        if (e->gt_par.empty() && !e->levels_want && !voices && !levellers) return JF_OK;  // nothing was ever set
-        bool active = e->levels_want || voices || levellers;
+        ranges = range_latch_host(e);     // ... and for a bus with a hearing range
+        if (e->gt_par.empty() && !e->levels_want && !voices && !levellers && !ranges) return JF_OK;  // nothing was ever set
+        bool active = e->levels_want || voices || levellers || ranges;
         for (size_t s = 0; s < e->gt_par.size() && !active; s++) active = e->gt_par[s].open > 0.0f;
         if (!active) return JF_OK;  // every gate was set back to open = 0, no meters
         if (e->gt_par.empty())
@@ -93,16 +96,18 @@ int gate_latch(jf_engine *e) {
     int rc = gate_latch_active(e);
     if (rc == JF_OK && voices) rc = voice_latch_active(e);
     if (rc == JF_OK && levellers) rc = level_latch_active(e);
+    if (rc == JF_OK && ranges) rc = range_latch_active(e);
     e->gate_on = rc == JF_OK;
     e->voice_on = e->gate_on && voices;
     e->level_on = e->gate_on && levellers;
+    e->range_on = e->gate_on && ranges;
     return rc;
 }
 
 // The stage of this run, behind the descriptor preparation, the set stage and the live ingest: the levels of the K blocks the
 // run appends to every distinct input (read where the spatialiser launch will read them: d_sigs and d_state[p]), the gates and
 // g_eff, then desc_gain_kernel on g_eff as on any trajectory.  The gains g[k][s] are the ones the plain gain stage would apply.
-int run_gate_stage(jf_engine *e, int p, int K, int canon, bool timed) {
+int run_gate_stage(jf_engine *e, const float *d_pos, int p, int K, int canon, bool timed) {
     const size_t S = (size_t)e->S, KS = (size_t)e->maxK * S;
     if (K > e->maxK || e->rv_P > 0) return fail(e, JF_ERR_STATE, "voice gates: the run does not fit the stage");
     float *peak = e->d_gt_lv, *sumsq = e->gate_meters ? e->d_gt_lv + KS : nullptr, *gate = e->gate_meters ? e->d_gt_lv + 2 * KS : nullptr;
@@ -117,6 +122,13 @@ int run_gate_stage(jf_engine *e, int p, int K, int canon, bool timed) {
     rc = e->tm_gate.end(e, timed);
     if (rc) return rc;
     e->last_gate = true;
+    e->last_range = e->rg_reported = false;
+    if (e->range_on) {  // the buses' hearing ranges: g_eff and g_eff_prev times h, in place, AHEAD of the voice limits -- who is out
+                        // of earshot is no candidate for a place (jf_engine_range.cpp)
+        rc = run_range_stage(e, d_pos, g_eff, g_eff_prev, K, timed);
+        if (rc) return rc;
+        e->rg_reported = e->gate_meters;
+    }
     e->last_voice = e->vc_reported = false;
     if (e->voice_on) {  // the buses' voice limits: g_eff and g_eff_prev rewritten in place (jf_engine_voice.cpp)
         rc = run_voice_stage(e, peak, g_eff, g_eff_prev, K, timed);
@@ -139,14 +151,15 @@ int run_gate_stage(jf_engine *e, int p, int K, int canon, bool timed) {
     return JF_OK;
 }
 
-void gate_settle(jf_engine *e) { e->gate_on = e->voice_on = e->level_on = false; }
+void gate_settle(jf_engine *e) { e->gate_on = e->voice_on = e->level_on = e->range_on = false; }
 
 // src < 0: every source.  Nothing to close in an engine that never ran the stage: every gate is closed there.  The source's
-// voice envelope starts over with it, and it is levelled from 1 again.
+// voice envelope starts over with it, it is levelled from 1 again, and its hearing-range state is 1 again.
 int gate_close_source(jf_engine *e, int src) {
     {
         int rc = voice_reset_source(e, src);
         if (rc == JF_OK) rc = level_reset_source(e, src);
+        if (rc == JF_OK) rc = range_reset_source(e, src);
         if (rc) return rc;
     }
     if (!e->d_gt_state) return JF_OK;
@@ -166,7 +179,11 @@ int gate_levels_copy(jf_engine *e, int K) {
         const int rc = voice_heard_copy(e, K);
         if (rc) return rc;
     }
-    return e->lv_reported ? level_gains_copy(e, K) : JF_OK;
+    if (e->lv_reported) {
+        const int rc = level_gains_copy(e, K);
+        if (rc) return rc;
+    }
+    return e->rg_reported ? range_gains_copy(e, K) : JF_OK;
 }
 
 // h_levels holds a run: blocks b0 .. b0 + K of a call of n_blocks, into the call's [S][n_blocks][3]
@@ -186,6 +203,10 @@ void gate_levels_land(jf_engine *e, int K, int b0, int n_blocks) {
         level_gains_land(e, K, b0, n_blocks);
     else
         e->gains_blocks = 0;
+    if (e->rg_reported)
+        range_gains_land(e, K, b0, n_blocks);
+    else
+        e->range_blocks = 0;
 }
 
 // what the last jf_batch_run left on the device: brought over once, the stream waited for

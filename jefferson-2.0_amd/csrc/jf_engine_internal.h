@@ -31,8 +31,11 @@
 //   jf_engine_level.cpp   talker levelling: the sources' levellers, what a processing call latches of them (inside gate_latch), the
 //                         kernel run_gate_stage launches ahead of desc_gain_kernel (run_level_stage, jf_level.hip) and
 //                         jf_source_set_leveller / jf_source_level_gains
+//   jf_engine_range.cpp   hearing range: the buses' ranges and the sources' exempt flags, what a processing call latches of them
+//                         (inside gate_latch), the kernel run_gate_stage launches behind its scan and ahead of the voice limits
+//                         (run_range_stage, jf_range.hip) and jf_bus_set_range / jf_source_range_gains
 //   jf_engine_debug.cpp   every entry point of include/jefferson_debug.h (taps, timing hooks, tuning switches, accessors)
-// What the six latched controls (gain, masters, sets, gates, voice limits, levellers) share is here once: StagedRing (their asynchronous uploads), StageTimer
+// What the seven latched controls (gain, masters, sets, gates, voice limits, levellers, hearing ranges) share is here once: StagedRing (their asynchronous uploads), StageTimer
 // (the event pairs of a stage that only some runs launch), CallLatches (a processing call's latch and settlement of all four).
 // Not part of any interface: nothing outside csrc/ includes this file.
 #ifndef JF_ENGINE_INTERNAL_H
@@ -63,6 +66,7 @@
 #include "jf_level_rule.h"
 #include "jf_output.h"
 #include "jf_pose_rule.h"
+#include "jf_range_rule.h"
 #include "jf_room.h"
 #include "jf_stream.h"
 #include "jf_voice_rule.h"
@@ -147,6 +151,10 @@ hipError_t launch_voice_select(const int *d_members, const int *d_seg, const int
 // talker levelling (jf_level.hip): g_eff and g_eff_prev times every source's automatic gain, in place; d_par is six planes of [S]
 hipError_t launch_level_scan(const float *d_par, const int *d_root, const float *d_peak, float *d_g_eff, float *d_g_eff_prev,
                              float *d_a_prev, float *d_a, int S, int K, hipStream_t st);
+// hearing range (jf_range.hip): g_eff and g_eff_prev times how much of every source its listener hears, in place; d_par is two
+// planes of [S], d_pos the run's records [K][S][5]; the state is read from one plane and written to the other
+hipError_t launch_range_gain(const float *d_par, const float *d_pos, float *d_g_eff, float *d_g_eff_prev, const float *d_h_prev_in,
+                             float *d_h_prev_out, float *d_h, int S, int K, hipStream_t st);
 }  // namespace jf
 
 using namespace jf;
@@ -650,6 +658,30 @@ struct jf_engine : ReverbSetup {
     bool last_level = false;                  // the last run of the gate stage launched the kernel (jf_debug_last_kernels)
     StageTimer tm_level;                      // profiling 2: around the kernel (jf_profile_read_level)
 
+    // HEARING RANGE (jf_bus_set_range).  Per bus a range {near, far} (far == 0: none), per source an exempt flag
+    // and, on the device ONLY, the state {h_prev}.  While the engine is ACTIVE for ranges -- some bus has far > 0 -- it counts as
+    // gate-active, and run_gate_stage launches range_gain_kernel (jf_range.hip) behind the scan and ahead of the voice stage: it
+    // rewrites g_eff in place from the run's records.  The host state is under pos_mu like `pos` and empty until first use; an
+    // engine in which no bus has far > 0 allocates nothing below and launches nothing (gate_latch: range_latch_host).
+    std::vector<float> rg_range;              // [n_buses][2] = {near, far} (empty: no range was ever set)
+    std::vector<unsigned char> rg_exempt;     // [S] (empty: no source is exempt)
+    std::vector<float> range_last;            // [S][range_blocks] h[k] of the last rendered call, on the host
+    int range_blocks = 0;                     // (0: none; valid while it equals levels_blocks)
+    // what the processing call in hand latched (its thread's alone)
+    bool range_on = false;                    // the call is active for ranges
+    std::vector<float> run_rg;                // [2][S] the call's parameters as the device holds them: near, then far, per SOURCE
+    bool rg_idle = false;                     // a call was latched without a range since the stage last ran: every state is 1 again
+    bool rg_reported = false;                 // the last run of the gate stage left h[K][S] for the input meters' copies
+    DevBuf<float> d_rg_par;                   // [2][S]
+    std::vector<float> dev_rg;                // what it holds (empty: nothing yet)
+    DevBuf<float> d_rg_h;                     // [maxK][S]: h of a run
+    DevBuf<float> d_rg_hprev;                 // [2][S]: the state, two planes taken in turn per run (read one, write the other)
+    int rg_cur = 0;                           // the plane the next run reads
+    StagedRing<float> rg_ring;                // slots of [2][S]: the asynchronous copy to d_rg_par
+    PinnedBuf<float> h_rg_h;                  // [maxK][S] where a run's h lands on the host
+    bool last_range = false;                  // the last run of the gate stage launched the kernel (jf_debug_last_kernels)
+    StageTimer tm_range;                      // profiling 2: around the kernel (jf_profile_read_range)
+
     // STREAM SOURCES (jf_source_set_stream, jf_source_push).  A stream source is internally a live source that
     // takes no row of `in`: the same live_len device buffer named by its record in d_sigs, filled at the source's play position
     // by stream_resample_kernel (jf_stream.hip) from the source's FIFO -- pinned, mapped host memory the pushes write and the
@@ -1015,7 +1047,7 @@ JF_INTERNAL void sets_settle(jf_engine *e);
 // 0: every one) through the engine's stream.  gate_levels_*: as the masters' meters.  gate_wanted: some source has a gate or
 // input meters are on (jf_reverb_set_ir refuses then).
 JF_INTERNAL int gate_latch(jf_engine *e);
-JF_INTERNAL int run_gate_stage(jf_engine *e, int p, int K, int canon, bool timed);
+JF_INTERNAL int run_gate_stage(jf_engine *e, const float *d_pos, int p, int K, int canon, bool timed);
 JF_INTERNAL void gate_settle(jf_engine *e);
 JF_INTERNAL int gate_close_source(jf_engine *e, int src);
 JF_INTERNAL int gate_levels_copy(jf_engine *e, int K);
@@ -1050,6 +1082,20 @@ JF_INTERNAL int level_reset_source(jf_engine *e, int src);
 JF_INTERNAL int level_gains_copy(jf_engine *e, int K);
 JF_INTERNAL void level_gains_land(jf_engine *e, int K, int b0, int n_blocks);
 JF_INTERNAL bool level_wanted(jf_engine *e);
+// hearing range (jf_engine_range.cpp), wired like the levellers.  gate_latch calls range_latch_host under pos_mu (the call's
+// planes, resolved per source from its bus and its exempt flag -- so a source that changed its bus is resolved anew; true while
+// some bus has far > 0: the engine then counts as gate-active) and range_latch_active behind the gates' own buffers
+// (allocation, the copy that differs).  run_range_stage: from run_gate_stage behind the scan and AHEAD of the voice stage, while
+// e->range_on; d_pos is the run's records, whoever wrote them.  range_reset_source: a reset or a new signal takes the source's
+// h_prev back to 1 through the engine's stream (src < 0: every one).  range_gains_copy / range_gains_land travel with
+// gate_levels_copy / gate_levels_land.  range_set_buses: under pos_mu, beside voice_set_buses.
+JF_INTERNAL bool range_latch_host(jf_engine *e);
+JF_INTERNAL int range_latch_active(jf_engine *e);
+JF_INTERNAL int run_range_stage(jf_engine *e, const float *d_pos, float *g_eff, float *g_eff_prev, int K, bool timed);
+JF_INTERNAL int range_reset_source(jf_engine *e, int src);
+JF_INTERNAL int range_gains_copy(jf_engine *e, int K);
+JF_INTERNAL void range_gains_land(jf_engine *e, int K, int b0, int n_blocks);
+JF_INTERNAL void range_set_buses(jf_engine *e, int n_buses);
 // the three pointers run_gain_stage hands desc_gain_kernel for the next run of K blocks (all null unless e->gain_on), and the
 // step to the run after it (jf_engine_gain.cpp)
 JF_INTERNAL void gain_run_gains(const jf_engine *e, const float **g_prev, const float **g_new, const float **g_traj);
