@@ -1,6 +1,6 @@
 """One float64 reference for the whole conference contract (include/jefferson.h: output buses, shared inputs, room sends,
-per-source gain, bus masters, listener poses, objects, live input, HRTF sets, voice gates, voice limits) -- TEST INFRASTRUCTURE
-ONLY, plain NumPy, no GPU.
+per-source gain, bus masters, listener poses, objects, live input, HRTF sets, voice gates, voice limits, hearing range, talker
+levelling, limiter look-ahead) -- TEST INFRASTRUCTURE ONLY, plain NumPy, no GPU.
 
 ConferenceModel takes the calls jf.Engine takes (same method names and arguments) and predicts every bus of every block.  It is
 COMPOSED from the references the project already trusts and adds only what none of them knows about:
@@ -29,18 +29,40 @@ COMPOSED from the references the project already trusts and adds only what none 
                        is predicted.
   bus outputs          per bus with an output, pull() is output_model.resample64 of the model's own mastered blocks since the
                        output was set or reset; a paused call's silence is not among them.
+  hearing range        range_model.range_gain on the float32 head-relative x, y, z of the record the model forms for each (block,
+                       source) -- latched by a setter, handed over by a trajectory or formed by pose_model.records.  The planes
+                       {near, far} are resolved at every latch from each source's bus as it is then ({0, 0} for an exempt source
+                       and for a bus without a range); the state is h_prev [S], 1 at the start.  g_rg[k] = fl32(g_eff[k] h[k]) and
+                       g_rg[-1] = fl32(g_eff[-1] h_prev) sit BETWEEN the gate scan and voice_rule: a source with h = 0 is no
+                       candidate and takes no place; the ranking reads the raw envelope, the send line does not know.  A call
+                       latched without any range leaves every h and every state at 1 at once.
+  talker levelling     level_model.level_step in float32 on the same exact block peaks the gates read (a follower has its root's
+                       level and parameters and state of its own); the state is a_prev [S], 1 at the start.  g_lv[k] =
+                       fl32(g_in[k] a[k]) and g_lv[-1] = fl32(g_in[-1] a_prev) with g_in what voice_rule left: the last stage ahead
+                       of the gain stage.  Sends and the ranking read nothing of it.  A call latched without any leveller leaves
+                       every a and every state at 1 at once.
+  limiter look-ahead   look_block64, jf_master_rule.h's look-ahead rule restated in float64 beside master_block64: per bus the
+                       value last set, the value latched, the held block and its peak.  Turning on inserts one block of zeros,
+                       turning off drops the held block, both keep g; the delay is there with the limiter on or off; everything
+                       behind the master section -- what a call returns, pull(), the meters' peak_out -- sees the delayed block.
 
 `fault` names ONE deliberate misreading of the header (FAULTS); tests/test_conference_model.py shows that each of them moves
 the prediction by 100 bounds in every session that uses the feature -- every clause the model implements counts.
 
 Every call returns [n_buses][K][2B] float64; `last` holds what the bound of a block is made of and, while input meters are on,
-`levels` [S][K][3] and (with a limited bus) `heard` [S][K][2] as jf_source_levels and jf_source_heard report them.
+`levels` [S][K][3] and (with a limited bus) `heard` [S][K][2] as jf_source_levels and jf_source_heard report them, `range_gains`
+and `level_gains` [S][K] (None where the engine keeps none).  On a look-ahead bus infos[b][k] has "look": True and "parts" /
+"held_parts", what the bound of the incoming and of the held block is made of.
 """
+import collections
+
 import numpy as np
 
 import model64
 import output_model
 import pose_model
+import level_model
+import range_model
 import stream_model
 from gain_model import CloudGainModel, GainModel
 from gate_model import gate_scan
@@ -63,7 +85,17 @@ FAULTS = ("send_post_fader", "follower_own_position", "reset_one_window", "signa
           # stream sources
           "pause_consumes_stream", "reset_keeps_stream_history", "underrun_zeros_not_history", "follower_hears_raw_packets",
           # bus outputs
-          "output_pre_master", "output_misses_wet", "paused_silence_appended", "set_buses_drops_outputs")
+          "output_pre_master", "output_misses_wet", "paused_silence_appended", "set_buses_drops_outputs",
+          # hearing range
+          "range_after_limit", "range_gates_send", "set_bus_old_range", "range_from_world_origin", "signal_keeps_h_prev",
+          "pause_advances_range", "last_range_ramps", "range_restarts_each_call",
+          # talker levelling
+          "leveller_post_fader", "leveller_levels_send", "follower_roots_leveller", "signal_keeps_a_prev", "pause_advances_leveller",
+          "leveller_pumps_below_floor", "ranking_reads_levelled", "leveller_before_limit", "leveller_restarts_each_call",
+          "last_leveller_ramps",
+          # limiter look-ahead
+          "look_only_while_limited", "look_off_flushes", "look_on_no_silence", "pause_flushes_held", "limiter_restart_clears_held",
+          "set_buses_drops_held", "look_ignores_incoming", "output_ahead_of_lookahead")
 MAX_HRTF_SETS = 64
 
 IDENTITY = np.array([0, 0, 0, 1, 0, 0, 0], np.float32)
@@ -95,6 +127,31 @@ def master_block64(x, B, m_prev, m_new, ramp, c, r, g_prev):
             "release": bool(c > 0 and g > g_prev), "ramp": bool(ramp and m_prev != m_new), "limited": bool(c > 0),
             "m_max": float(np.abs(m).max())}
     return out.reshape(2 * B), info
+
+
+def look_block64(x, B, m_prev, m_new, ramp, c, r, held, p_held, g_prev, ignore_incoming=False):
+    """jf_master_rule.h's LOOK-AHEAD rule in float64: x [2B] comes in, held [2B] goes out -> (out [2B], v [2B] the new held block,
+    info as lookahead_model.look_block's plus m_max).  e = min(min(t_h, t), g_prev + r); the gain ramps from g_prev to e over the
+    HELD block, kept between the two; the clamp; the caller then takes h := v, p_h := info["p"], g_prev := info["g"]."""
+    x = np.asarray(x, np.float64).reshape(B, 2)
+    h = np.asarray(held, np.float64).reshape(B, 2)
+    frac = (np.arange(B) + 1.0) * (1.0 / B)
+    m = m_prev + (m_new - m_prev) * frac if ramp and m_prev != m_new else np.full(B, float(m_new))
+    v = m[:, None] * x
+    p = float(np.abs(v).max())
+    if c > 0:
+        t_h = c / p_held if p_held > c else 1.0
+        t = c / p if p > c else 1.0
+        e = min(t_h if ignore_incoming else min(t_h, t), g_prev + r)
+        a = g_prev + (e - g_prev) * frac
+        a = np.maximum(e, a) if e < g_prev else np.minimum(e, a)
+        out = np.minimum(np.maximum(a[:, None] * h, -c), c)
+    else:
+        t_h, t, e, out = 1.0, 1.0, 1.0, h.copy()
+    info = {"p": p, "peak_out": float(np.abs(out).max()), "g": e, "t_h": t_h, "t": t, "attack": bool(c > 0 and e < g_prev),
+            "release": bool(c > 0 and e > g_prev), "ramp": bool(ramp and m_prev != m_new), "limited": bool(c > 0),
+            "m_max": float(np.abs(m).max()), "look": True, "g_prev": g_prev, "p_held": p_held}
+    return out.reshape(2 * B), v.reshape(2 * B), info
 
 
 class ConferenceModel:
@@ -156,6 +213,24 @@ class ConferenceModel:
         self.late = False
         self.last = None
         self.limiter_blocks = {"attack": 0, "release": 0}
+        # hearing range (range_model.range_gain is the rule)
+        self.rng_par = np.zeros((1, 2), np.float32)     # per bus {near, far}
+        self.rbus = [0] * S             # the bus whose range holds for the source: the bus it is on (kept apart for a fault)
+        self.exempt = [False] * S
+        self.h_prev = np.ones(S, np.float32)
+        self.range_counts = collections.Counter()   # source blocks inside / ramp / beyond, crossings, skipped by a range alone ...
+        # talker levelling (level_model.level_step is the rule)
+        self.lv_par = [dict(level_model.OFF) for _ in range(S)]
+        self.a_prev = np.ones(S, np.float32)
+        self.level_counts = collections.Counter()   # blocks of every line of the rule, over all levelled sources
+        self.levelled = set()           # the sources that were ever rendered with a leveller
+        self.peak_hist = [[] for _ in range(S)]     # the input peaks of the blocks the source's window holds
+        self.worst_product = 0.0        # max |g_lv[k]| times the largest input peak in the window (window noise: <= 1 is wanted)
+        # limiter look-ahead (look_block64 is the rule)
+        self.look_set, self.look_on = [False], [False]
+        self.held, self.p_held, self.held_parts = [None], [0.0], [None]
+        self.look_counts = collections.Counter()    # turn-ons, turn-offs, blocks decided by the incoming / the held block ...
+        self._rel_run = [0]             # per bus: the release blocks in a row so far
 
     # ------------------------------------------------------------------------------------------------ inputs --
     @property
@@ -189,6 +264,10 @@ class ConferenceModel:
         self.env_prev[s] = 0
         if self.fault == "signal_resets_heard":
             self.heard_prev[s] = 1
+        if self.fault != "signal_keeps_h_prev":     # the source was heard in full before, and is levelled from 1 again
+            self.h_prev[s] = 1
+        if self.fault != "signal_keeps_a_prev":
+            self.a_prev[s] = 1
 
     def _detach_input(self, s):
         if self.root[s] == s:
@@ -233,6 +312,7 @@ class ConferenceModel:
         for m in self.members(self.root[s]):
             if m == s or self.fault != "reset_one_window":
                 self.src[m].x[:] = 0
+                self.peak_hist[m] = []
             self.src[m].count = 0
 
     # --------------------------------------------------------------------------------------------- positions --
@@ -339,6 +419,16 @@ class ConferenceModel:
             setattr(self, name, (v + [neutral] * n)[:n])
         # the buses that remain keep their voice limits, new ones have none
         self.vc_N, self.vc_rho, self.vc_snap = (self.vc_N + [0] * n)[:n], (self.vc_rho + [f32(0)] * n)[:n], (self.vc_snap + [0] * n)[:n]
+        # ... their ranges and their look-ahead, held blocks included
+        rp = np.zeros((n, 2), np.float32)
+        rp[:keep] = self.rng_par[:keep]
+        self.rng_par = rp
+        for name, neutral in (("look_set", False), ("look_on", False), ("held", None), ("p_held", 0.0), ("held_parts", None), ("_rel_run", 0)):
+            v = getattr(self, name)
+            setattr(self, name, (v + [neutral] * n)[:n])
+        if self.fault == "set_buses_drops_held":
+            self.held = [None if h is None else np.zeros_like(h) for h in self.held]
+            self.p_held, self.held_parts = [0.0] * n, [None] * n
         self.n_buses = n
         # the outputs of the buses that remain are kept
         self.outputs = {} if self.fault == "set_buses_drops_outputs" else {b: o for b, o in self.outputs.items() if b < n}
@@ -348,6 +438,8 @@ class ConferenceModel:
         self.bus[s] = b
         if self.fault != "set_bus_old_limit":
             self.vbus[s] = b
+        if self.fault != "set_bus_old_range":
+            self.rbus[s] = b
         if self.fault == "set_bus_resets_set":
             self.set_new[s] = 0
         if self.fault == "bus_set_reaches_joiners" and b in self.bus_set:     # (the true joiner keeps its set)
@@ -497,6 +589,89 @@ class ConferenceModel:
             raise Refused(JF_ERR_ARG, "priority must lie within 0 .. 255")
         self.prio[s] = int(priority)
 
+    # ------------------------------------------------------------------------------------------------ ranges --
+    def set_range(self, bus, near, far):
+        if not 0 <= bus < self.n_buses:
+            raise Refused(JF_ERR_ARG, "bad bus index")
+        if not range_model.params_ok(near, far):
+            raise Refused(JF_ERR_ARG, "range: both finite; near == far == 0, or 0 <= near < far <= 2^20")
+        self.rng_par[bus] = (near, far) if f32(far) != 0 else (0, 0)
+
+    def set_range_exempt(self, s, on=True):
+        self.exempt[s] = bool(on)
+
+    def ranged(self):
+        return bool((self.rng_par[:, 1] > 0).any())
+
+    def _range_planes(self):
+        """near [S], far [S] as a latch resolves them: from the bus each source is on NOW; {0, 0} for an exempt source"""
+        rbus = [min(b, self.n_buses - 1) for b in self.rbus]
+        near, far = self.rng_par[rbus, 0].copy(), self.rng_par[rbus, 1].copy()
+        near[self.exempt], far[self.exempt] = 0, 0
+        return near, far
+
+    def _range_h(self, near, far, rec, pts=None):
+        """h [K][S] of records rec [K][S][5] (fault range_from_world_origin: of the world points pts [K][S][3] where a record
+        was formed from one -- the listener's pose ignored)"""
+        K = len(rec)
+        h = np.ones((K, self.S), np.float32)
+        for s in range(self.S):
+            if far[s] == 0:
+                continue
+            for k in range(K):
+                x, y, z = rec[k][s][2:5]
+                if self.fault == "range_from_world_origin" and pts is not None and not np.isnan(pts[k][s][0]):
+                    x, y, z = pts[k][s]
+                h[k, s] = range_model.range_gain(near[s], far[s], x, y, z)
+        return h
+
+    # --------------------------------------------------------------------------------------------- levellers --
+    def set_leveller(self, s, target, floor=0.0, min_gain=1.0, max_gain=1.0, fall=0.5, rise=2.0):
+        par = level_model.params(target, floor, min_gain, max_gain, fall, rise)
+        if not level_model.params_ok(par):
+            raise Refused(JF_ERR_ARG, "leveller: a set of parameters the header refuses")
+        self.lv_par[s] = par
+
+    def set_levellers(self, target, floor=0.0, min_gain=1.0, max_gain=1.0, fall=0.5, rise=2.0):
+        self.set_leveller(0, target, floor, min_gain, max_gain, fall, rise)       # (refused for all or for none)
+        for s in range(1, self.S):
+            self.set_leveller(s, target, floor, min_gain, max_gain, fall, rise)
+
+    def levelling(self):
+        return any(p["target"] > 0 for p in self.lv_par)
+
+    def _level_scan(self, peak, g_raw):
+        """a [K][S] and the state after the run, from the raw block peaks [K][S]; the lines of the rule are counted"""
+        K, S, fault = len(peak), self.S, self.fault
+        a, a_end = np.ones((K, S), np.float32), self.a_prev.copy()
+        for s in range(S):
+            own = self.root[s] if fault == "follower_roots_leveller" else s
+            par = self.lv_par[own]
+            if fault == "leveller_pumps_below_floor" and par["target"] > 0:
+                par = dict(par, floor=f32(2.0 ** -60))
+            lv = peak[:, s]
+            if fault == "leveller_post_fader":
+                lv = (lv * np.abs(g_raw[:, s])).astype(np.float32)
+            a[:, s], br, a_end[s] = level_model.level_scan(lv, par, self.a_prev[own])
+            if par["target"] > 0 and fault is None:
+                self.levelled.add(s)
+                for k in range(K):
+                    self.level_counts[("off", "hold", "fall_limited", "fall_reached", "rise_limited", "rise_reached")[br[k]]] += 1
+                    if br[k] in (level_model.BR_FALL_REACHED, level_model.BR_RISE_REACHED):
+                        with np.errstate(all="ignore"):
+                            w = f32(par["target"] / lv[k])
+                        self.level_counts["clamp_min"] += int(w <= par["min_gain"] and a[k, s] == par["min_gain"])
+                        self.level_counts["clamp_max"] += int(w >= par["max_gain"] and a[k, s] == par["max_gain"])
+        if fault == "follower_roots_leveller":
+            a_end = np.array([a_end[self.root[s]] for s in range(S)], np.float32)
+        return a, a_end
+
+    def level_gains(self, K=None):
+        return self.last.get("level_gains")
+
+    def range_gains(self, K=None):
+        return self.last.get("range_gains")
+
     def _input_levels(self, K):
         """(peak [K][S] float32 exact, sumsq [K][S] float64) of the B samples every block of the call appends to the sources'
         inputs -- pre-fader; a follower has its root's level; an empty signal has level 0"""
@@ -512,10 +687,11 @@ class ConferenceModel:
             peak[:, s], sumsq[:, s] = peak[:, self.root[s]], sumsq[:, self.root[s]]
         return peak, sumsq
 
-    def _gains_heard(self, K, g_raw):
-        """The gains the gain stage sees in this call -- g_raw [K][S] through the gates (g_eff) and the limits (g_out) -- as
-        (g [K][S], g_prev [S], gate [K][S], keep [K][S]); the state of both moves on; `levels` and `heard` as the engine
-        reports them are left in self._reports"""
+    def _gains_heard(self, K, g_raw, rec=None, pts=None):
+        """The gains the gain stage sees in this call -- g_raw [K][S] through the gates (g_eff), the hearing ranges (g_rg), the
+        limits (g_out) and the levellers (g_lv) -- as (g [K][S], g_prev [S], gate [K][S], keep [K][S], h [K][S], a [K][S]); the
+        state of all four moves on; `levels`, `heard`, `range_gains` and `level_gains` as the engine reports them are left in
+        self._reports"""
         S, fault = self.S, self.fault
         peak, sumsq = self._input_levels(K)
         g_raw = np.asarray(g_raw, np.float32)
@@ -549,10 +725,54 @@ class ConferenceModel:
         g_eff = np.where(gate != 0, g_raw, f32(0)).astype(np.float32)
         levels = np.stack([peak.T.astype(np.float64), sumsq.T, gate.T.astype(np.float64)], axis=2)       # [S][K][3]
         keep, heard = np.ones((K, S), np.int32), None
+        # the hearing ranges, between the gate scan and the limits: who is out of earshot is no candidate
+        g_gate, g_gate_prev = g_eff, g_eff_prev
+        h, ranged = np.ones((K, S), np.float32), self.ranged()
+        if fault == "range_restarts_each_call":
+            self.h_prev[:] = 1
+        self._h_before = self.h_prev.copy()
+        if ranged:
+            near, far = self._range_planes()
+            h = self._range_h(near, far, rec, pts)
+            g_rg_prev, g_rg = (g_eff_prev * self.h_prev).astype(np.float32), (g_eff * h).astype(np.float32)
+            if fault is None:
+                on = far > 0
+                hb = np.vstack([self.h_prev[None], h[:-1]])
+                c = self.range_counts
+                c["inside"], c["ramp"] = c["inside"] + int((h[:, on] == 1).sum()), c["ramp"] + int(((h[:, on] > 0) & (h[:, on] < 1)).sum())
+                c["beyond"] += int((h[:, on] == 0).sum())
+                c["crossings_in"] += int(((hb[:, on] == 0) & (h[:, on] > 0)).sum())
+                c["crossings_out"] += int(((hb[:, on] > 0) & (h[:, on] == 0)).sum())
+                eb = np.vstack([g_eff_prev[None], g_eff[:-1]])
+                rb = np.vstack([g_rg_prev[None], g_rg[:-1]])
+                c["skipped"] += int(((rb == 0) & (g_rg == 0) & ((eb != 0) | (g_eff != 0))).sum())
+            self.h_prev = h[K - 1].copy()
+            if fault != "range_after_limit":
+                g_eff, g_eff_prev = g_rg, g_rg_prev
+        else:           # a call latched without a range: every h is 1 at once, and so is every state
+            if fault == "last_range_ramps":
+                g_eff_prev = (g_eff_prev * self.h_prev).astype(np.float32)
+            self.h_prev[:] = 1
+        # the levellers' gains: from the raw levels alone (the stage itself comes behind the limits)
+        levelling = self.levelling()
+        if fault == "leveller_restarts_each_call":
+            self.a_prev[:] = 1
+        a, a_before = np.ones((K, S), np.float32), self.a_prev.copy()
+        if levelling:
+            a, self.a_prev = self._level_scan(peak, g_raw)
+        else:
+            self.a_prev[:] = 1
         g_out, g_out_prev = g_eff, g_eff_prev
         if any(n > 0 for n in self.vc_N):
             vbus = [min(b, self.n_buses - 1) for b in self.vbus]
             g_rank, prio = g_eff, list(self.prio)
+            if fault is None and ranged:      # on a limited bus: would the limit ahead of the range have kept somebody else?
+                shadow = voice_rule(peak, list(range(S)), vbus, prio, self.vc_N, self.vc_rho, g_gate, g_gate_prev, self.env_prev,
+                                    self.heard_prev, self.vc_snap)[3]
+            else:
+                shadow = None
+            if fault == "ranking_reads_levelled":
+                peak = (peak * a).astype(np.float32)
             if fault == "muted_takes_a_place":
                 g_rank = np.ones_like(g_eff)
             if fault == "always_takes_a_place":
@@ -578,17 +798,40 @@ class ConferenceModel:
             if fault != "snap_not_consumed":
                 self.vc_snap = [0] * self.n_buses
             heard = np.stack([env.T.astype(np.float64), keep.T.astype(np.float64)], axis=2)              # [S][K][2]
+            if shadow is not None:
+                self.range_counts["limit_differs"] += int(((keep == 1) & (shadow == 0)).any(axis=1).sum())
             before = np.vstack([g_out_prev[None], g_out[:-1]])
             eff_before = np.vstack([g_eff_prev[None], g_eff[:-1]])
             for s in range(S):
                 if self.vc_N[vbus[s]] > 0:
                     self.ramps["out"] += int(((before[:, s] != 0) & (g_out[:, s] == 0) & (g_eff[:, s] != 0)).sum())
                     self.ramps["in"] += int(((before[:, s] == 0) & (g_out[:, s] != 0) & (eff_before[:, s] != 0)).sum())
+        if fault == "range_after_limit" and ranged:       # (a talker out of earshot has taken a place)
+            g_out, g_out_prev = (g_out * h).astype(np.float32), (g_out_prev * self._h_before).astype(np.float32)
         raw_before = np.vstack([g_prev[None], g_raw[:-1]])
         out_before = np.vstack([g_out_prev[None], g_out[:-1]])
         self.skipped += int(((out_before == 0) & (g_out == 0) & ((raw_before != 0) | (g_raw != 0))).sum())
-        self._reports = (levels if self.input_meters else None, heard if self.input_meters else None)
-        return g_out, g_out_prev, gate, keep
+        # the levellers: the last stage ahead of the gain stage, on what the limits left
+        if levelling:
+            g_in, g_in_prev = (g_eff, g_eff_prev) if fault == "leveller_before_limit" else (g_out, g_out_prev)
+            if fault == "leveller_before_limit":      # (only a levelled source's gain is taken from ahead of the limits)
+                on = np.array([p["target"] > 0 for p in self.lv_par])
+                g_in, g_in_prev = np.where(on[None], g_eff, g_out), np.where(on, g_eff_prev, g_out_prev)
+            g_out, g_out_prev = (g_in * a).astype(np.float32), (g_in_prev * a_before).astype(np.float32)
+        elif fault == "last_leveller_ramps":
+            g_out_prev = (g_out_prev * a_before).astype(np.float32)
+        if fault is None:       # window noise: |g| times the largest input peak among the blocks the source's window holds
+            n_win = max(1, self.N // self.B)
+            for s in range(S):
+                for k in range(K):
+                    self.peak_hist[s] = (self.peak_hist[s] + [float(peak[k, s])])[-n_win:]
+                    w = abs(float(g_out[k, s])) * max(self.peak_hist[s])
+                    if w > self.worst_product:
+                        self.worst_product, self.worst_at = w, (s, float(g_out[k, s]), float(a[k, s]), max(self.peak_hist[s]))
+        self._reports = (levels if self.input_meters else None, heard if self.input_meters else None,
+                         h.T.copy() if self.input_meters and ranged else None, a.T.copy() if self.input_meters and levelling else None)
+        self.gains_seen = (g_out, g_out_prev)     # what the gain stage sees: g[k] [K][S] and g[-1] [S]
+        return g_out, g_out_prev, gate, keep, h, a
 
     # ---------------------------------------------------------------------------------------------- streams --
     def _call_frames(self):
@@ -708,8 +951,39 @@ class ConferenceModel:
     def set_limiter(self, bus, ceiling, release=1.0):
         c = float(f32(ceiling))
         if (self.lim_c[bus] > 0) != (c > 0):
-            self.lim_g[bus] = 1.0
+            self.lim_g[bus] = 1.0           # (the held block of a look-ahead bus is left alone)
+            if self.fault == "limiter_restart_clears_held" and self.held[bus] is not None:
+                self.held[bus], self.p_held[bus], self.held_parts[bus] = np.zeros(2 * self.B), 0.0, None
         self.lim_c[bus], self.lim_r[bus] = c, float(f32(release))
+
+    def set_lookahead(self, bus, on=True):
+        if not 0 <= bus < self.n_buses:
+            raise Refused(JF_ERR_ARG, "bad bus index")
+        self.look_set[bus] = bool(on)       # (jf.Engine hands the C call int(bool(on)): 0 or 1)
+
+    def lookahead(self, bus):
+        return self.look_set[bus]
+
+    def bus_latency(self, bus):
+        return self.B if self.look_on[bus] else 0
+
+    def _look_latch(self):
+        """-> the buses whose look-ahead this call turns off (fault look_off_flushes hands their held block out once more)"""
+        off = []
+        for b in range(self.n_buses):
+            if self.look_set[b] and not self.look_on[b]:        # one block of silence enters the bus's stream; g is kept
+                self.held[b], self.p_held[b], self.held_parts[b] = np.zeros(2 * self.B), 0.0, None
+                self.look_counts["turned on"] += 1
+                self.look_counts["turned on mid-stream"] += int(self.last is not None)
+                self._fresh[b] = True
+            elif self.look_on[b] and not self.look_set[b]:      # the held block is dropped; g is kept
+                self.look_counts["turned off"] += 1
+                self.look_counts["turned off over a loud block"] += int(self.lim_c[b] > 0 and self.p_held[b] > self.lim_c[b])
+                off.append(b)
+                if self.fault != "look_off_flushes":
+                    self.held[b], self.held_parts[b] = None, None
+            self.look_on[b] = self.look_set[b]
+        return off
 
     def set_meters(self, on=True):
         self.meters_on = bool(on)
@@ -722,9 +996,12 @@ class ConferenceModel:
         self.paused = bool(p)
 
     # ------------------------------------------------------------------------------------------------- audio --
-    def _render(self, records, inp, gains=None, hear=None):
-        """K blocks: records [K][S][5]; inp None or [n_live][K B]; gains None (the standing ones) or [K][S]"""
+    def _render(self, records, inp, gains=None, pts=None):
+        """K blocks: records [K][S][5]; inp None or [n_live][K B]; gains None (the standing ones) or [K][S]; pts None or
+        [K][S][3], the world points the records were formed from (NaN: none) -- a fault's reading only"""
         B, S, nb, N = self.B, self.S, self.n_buses, self.N
+        self._fresh = {}
+        turned_off = self._look_latch()
         K = len(records)
         gm = self.gm
         live = self.live_roots()
@@ -747,7 +1024,7 @@ class ConferenceModel:
             self.lim_g = [1.0] * nb
         # the gains the gain stage would have applied, then what the gates and the limits leave of them
         g_raw = np.array([[gm.g[s] if gains is None else f32(gains[k][s]) for s in range(S)] for k in range(K)], np.float32)
-        g_out, g_out_prev, gate, keep = self._gains_heard(K, g_raw)
+        g_out, g_out_prev, gate, keep, h_rg, a_lv = self._gains_heard(K, g_raw, records, pts)
         set_before = list(self.set_prev)
         for k in range(K):
             for s, q in enumerate(self.src):
@@ -772,6 +1049,10 @@ class ConferenceModel:
                         l = l * float(gate[k, s])
                     if self.fault == "limit_limits_send":
                         l = l * float(keep[k, s])
+                    if self.fault == "range_gates_send":
+                        l = l * float(h_rg[k, s])
+                    if self.fault == "leveller_levels_send":
+                        l = l * float(a_lv[k, s])
                     send[self.send_bus[s], k * B:(k + 1) * B] += l * q.x[N - 2 * B:N - B]
         for s in range(S):
             gm.g_prev[s] = f32(g_raw[K - 1, s])
@@ -793,11 +1074,40 @@ class ConferenceModel:
         out = np.zeros_like(pre)
         tapped = {b: [None] * K for b in self.outputs}      # (fault output_misses_wet: what such an output would read)
         infos = [[None] * K for _ in range(nb)]
+        P = 0 if self.room is None else -(-self.room[3] // B)
         for b in range(nb):
             for k in range(K):
                 ramp = k == 0 or self.fault == "master_ramp_every_block"
-                out[b, k], i = master_block64(pre[b, k], B, self.m_prev[b], self.m_new[b], ramp, self.lim_c[b], self.lim_r[b],
-                                              self.lim_g[b])
+                args = (B, self.m_prev[b], self.m_new[b], ramp, self.lim_c[b], self.lim_r[b], self.lim_g[b])
+                parts = {"n": int(n_on[b, k]), "pre_max": float(np.abs(pre[b, k]).max()), "P": P,
+                         "silent": bool(n_on[b, k] == 0 and quiet[b])}
+                look = self.look_on[b] and not (self.fault == "look_only_while_limited" and not self.lim_c[b] > 0)
+                flush = self.fault == "look_off_flushes" and b in turned_off and k == 0 and self.held[b] is not None
+                if look or flush:       # the held block goes out, the block that came in is held
+                    out[b, k], v, i = look_block64(pre[b, k], *args[:6], self.held[b], self.p_held[b], self.lim_g[b],
+                                                   self.fault == "look_ignores_incoming")
+                    parts["m_max"] = i["m_max"]
+                    i["parts"], i["held_parts"] = parts, self.held_parts[b]
+                    i["silent"] = self.held_parts[b] is None or self.held_parts[b]["silent"]
+                    if self.fault == "look_on_no_silence" and self._fresh.get(b) and k == 0:
+                        out[b, k] = master_block64(pre[b, k], *args)[0]
+                    if self.fault == "output_ahead_of_lookahead" and b in self.outputs:
+                        tapped[b][k] = master_block64(pre[b, k], *args)[0]
+                    if self.fault is None and self.lim_c[b] > 0:
+                        c = self.look_counts
+                        c["decided by the incoming block"] += int(i["t"] < i["t_h"] and i["t"] < self.lim_g[b] + self.lim_r[b])
+                        c["decided by the held block"] += int(i["t_h"] < i["t"] and i["t_h"] < self.lim_g[b] + self.lim_r[b])
+                        self._rel_run[b] = self._rel_run[b] + 1 if i["release"] else 0
+                        c["releases over 3 blocks or more"] += int(self._rel_run[b] == 3)
+                        c["blocks on a limited bus"] += 1
+                    if flush:
+                        self.held[b], self.held_parts[b] = None, None
+                    else:
+                        self.held[b], self.p_held[b], self.held_parts[b] = v, i["p"], parts
+                else:
+                    out[b, k], i = master_block64(pre[b, k], *args)
+                if self.lim_c[b] > 0 and self.fault is None:
+                    self.look_counts["near the ceiling"] += int(abs(i["p"] / self.lim_c[b] - 1) < 1e-6)
                 if self.fault == "output_misses_wet" and b in self.outputs:
                     tapped[b][k] = master_block64(dry[b, k], B, self.m_prev[b], self.m_new[b], ramp, self.lim_c[b], self.lim_r[b],
                                                   self.lim_g[b])[0]
@@ -807,10 +1117,13 @@ class ConferenceModel:
                 infos[b][k] = i
         self.m_prev = list(self.m_new)
         # an output reads the mastered mix, wet part included: exactly the samples the call hands out
-        self._outputs_take({b: pre[b] if self.fault == "output_pre_master" else tapped[b] if self.fault == "output_misses_wet"
-                            else out[b] for b in self.outputs}, self.late)
-        self.last = {"pre": pre, "n_on": n_on, "infos": infos, "P": 0 if self.room is None else -(-self.room[3] // B),
-                     "quiet": quiet, "paused": False, "levels": self._reports[0], "heard": self._reports[1]}
+        if self.fault == "output_ahead_of_lookahead":
+            tapped = {b: [out[b, k] if x is None else x for k, x in enumerate(tapped[b])] for b in self.outputs}
+        self._outputs_take({b: pre[b] if self.fault == "output_pre_master" else tapped[b]
+                            if self.fault in ("output_misses_wet", "output_ahead_of_lookahead") else out[b] for b in self.outputs}, self.late)
+        self.last = {"pre": pre, "n_on": n_on, "infos": infos, "P": P,
+                     "quiet": quiet, "paused": False, "levels": self._reports[0], "heard": self._reports[1],
+                     "range_gains": self._reports[2], "level_gains": self._reports[3]}
         return out
 
     def _paused_call(self):
@@ -832,6 +1145,15 @@ class ConferenceModel:
                 self.env_prev[s] = f32(self.env_prev[s] * self.vc_rho[min(self.vbus[s], self.n_buses - 1)])
         if self.fault == "paused_call_takes_switch":
             self.set_prev = list(self.set_new)
+        # ... no range, no leveller, no look-ahead: the held block stays held
+        if self.fault == "pause_advances_range" and self.ranged():      # (the standing records through the ranges)
+            self.h_prev = self._range_h(*self._range_planes(), self._standing_records()[None])[0]
+        if self.fault == "pause_advances_leveller" and self.levelling():    # (the block the call would have appended)
+            self.a_prev = self._level_scan(self._input_levels(1)[0], np.ones((1, self.S), np.float32))[1]
+        if self.fault == "pause_flushes_held":
+            for b in range(self.n_buses):
+                if self.held[b] is not None:
+                    self.held[b], self.p_held[b], self.held_parts[b] = np.zeros(2 * self.B), 0.0, None
         # ... consumes nothing of a stream and appends nothing to an output
         if self.fault == "pause_consumes_stream":
             for s in range(self.S):
@@ -863,7 +1185,8 @@ class ConferenceModel:
         if self.paused:
             return self._paused_call()
         rec = self._standing_records()
-        out = self._render(rec[None], inp)
+        pts = np.array([self.world_point(s) if self.world_on[s] else [np.nan] * 3 for s in range(self.S)], np.float64)
+        out = self._render(rec[None], inp, None, pts[None])
         self._latch(rec)
         return out
 
@@ -890,7 +1213,7 @@ class ConferenceModel:
             if self.fault != "set_bus_old_listener" or not self.world_on[s]:
                 self.hear_bus[s] = self.bus[s]
         rec = self._world_records(world, poses)
-        out = self._render(rec, inp, self._take_staged(len(world)))
+        out = self._render(rec, inp, self._take_staged(len(world)), world)
         self._latch(rec[-1])
         self.world, self.pose = world[-1].copy(), poses[-1].copy()
         for s in range(self.S):
@@ -904,7 +1227,7 @@ class ConferenceModel:
         if any(o < 0 for o in self.object_of):
             raise Refused(JF_ERR_STATE, "a source is not attached to an object")
         rec = self._world_records(objects, poses, self.object_of)
-        out = self._render(rec, inp, self._take_staged(len(objects)))
+        out = self._render(rec, inp, self._take_staged(len(objects)), objects[:, self.object_of])
         self._latch(rec[-1])
         self.objects, self.pose = objects[-1].copy(), poses[-1].copy()
         return out
@@ -917,6 +1240,6 @@ class ConferenceModel:
             raise Refused(JF_ERR_STATE, "the device-resident form takes no input and hands nothing out to pull")
 
     # jf_batch_upload_* + jf_batch_run: a window of an uploaded trajectory; the sources, listeners and objects do not move
-    def run_records(self, records):
+    def run_records(self, records, pts=None):
         self.device_form()
-        return self._render(np.asarray(records, np.float32), None)
+        return self._render(np.asarray(records, np.float32), None, None, pts)

@@ -11,7 +11,14 @@ sets, voice gates and voice limits through code paths of their own (ops_new, new
 moves the random stream of the first six.  Sessions 9 and 10 (STREAMS) add stream sources and bus outputs the same way
 (ops_streams, stream_setter, stream_motif): pushes of 1 to 3 blocks' need ahead of every call -- now and then too little, so that
 an underrun falls, now and then a surplus inside the capacity --, pulls of 0 frames, a packet or everything ready after it, never
-an overrun.  A pull's result is held to pull_bound, THE OUTPUT BOUND.
+an overrun.  A pull's result is held to pull_bound, THE OUTPUT BOUND.  Sessions 1 to 10 are frozen by their digests.
+Sessions 11 to 13 (LATE) add limiter look-ahead, talker levelling and hearing ranges, again through code paths of their own
+(ops_late, late_setter, late_motif): 11 in session 7's form with the callback form in its last 25 steps, 12 in session 8's
+(uploads and batch_run windows), 13 in session 9's (streams, a live source, outputs on look-ahead buses).  Ranges are drawn from
+the model's own radii, leveller targets from the model's own block peaks, and a leveller's max_gain so that max_gain times the
+loudest block its source's window can hold stays below 1 (window noise: ensure).  Where the library is there on the CPU, a
+(pose, point) draw whose float32 x, y, z differ between jf_position_from_world and pose_model.records is drawn again, so that a
+range's h may be compared exactly.  On a look-ahead bus THE BOUND is derived in bounds().
 
 THE BOUND of bus b, block k (nothing new, nothing measured from the code under test): with n sources on the bus at that block
 and a room of P partitions,  pre = (sum_tol(2e-7, n) + (wet_tol(P) if a room is set else 0)) max(1, |want|_inf), want the
@@ -22,7 +29,7 @@ import numpy as np
 import model64
 import pose_model
 import room_model
-from conference_model import ConferenceModel, Refused
+from conference_model import JF_ERR_STATE, ConferenceModel, Refused
 from conftest import sum_tol
 
 TOL64 = 2e-7
@@ -45,29 +52,48 @@ SESSIONS = {
             note="PAD_LEN 2048; two streams and a live source, per-block and batch calls"),
     10: dict(seed=10, B=64, L=512, S=6, buses=3, taps=0, steps=80, hrir="cloud", sets=1, streams=(22050, 44100),
              outputs=(47900, 44100), note="cloud + 1 set; callback form in the last phase"),
+    # limiter look-ahead, talker levelling and hearing ranges on top of everything above
+    11: dict(seed=11, B=64, L=512, S=8, buses=2, taps=300, steps=80, hrir="kemar", sets=1,
+             note="group pinned to 2, then free; buses 2 -> 3 -> 2; callback form in the last 25 steps"),
+    12: dict(seed=12, B=256, L=512, S=8, buses=2, taps=0, steps=80, hrir="kemar", note="upload + batch_run windows"),
+    13: dict(seed=13, B=128, L=1024, S=5, buses=2, taps=256, steps=80, hrir="long", streams=(48000, 16000), outputs=(48000, 8000),
+             note="PAD_LEN 2048; two streams and a live source; outputs on look-ahead buses"),
 }
 NEW = (7, 8)          # the sessions with gates, limits and sets
-STREAMS = (9, 10)     # the sessions with stream sources and bus outputs (and gates and limits on them)
+STREAMS = (9, 10, 13)     # the sessions with stream sources and bus outputs (and gates and limits on them)
+LATE = (11, 12, 13)   # the sessions with look-ahead, levellers and ranges (their own code paths: ops_late, late_setter, late_motif)
 _STREAMF = ("pause_consumes_stream", "reset_keeps_stream_history", "underrun_zeros_not_history", "follower_hears_raw_packets")
-OUTPUT_FAULTS = ("output_pre_master", "output_misses_wet", "paused_silence_appended", "set_buses_drops_outputs")
-WINDOWS = (6, 8)      # ... in session 6's form: uploads and batch_run windows
+OUTPUT_FAULTS = ("output_pre_master", "output_misses_wet", "paused_silence_appended", "set_buses_drops_outputs",
+                 "output_ahead_of_lookahead")
+WINDOWS = (6, 8, 12)  # ... in session 6's form: uploads and batch_run windows
 _GATES = ("gate_post_fader", "follower_roots_gate", "set_gate_touches_state", "signal_keeps_gate_open", "pause_advances_gate",
           "gate_restarts_each_call", "skipped_block_freezes_window")
 _LIMITS = ("env_on_limited_bus_only", "set_bus_old_limit", "signal_resets_heard", "muted_takes_a_place", "always_takes_a_place",
            "snap_not_consumed", "pause_advances_env")
 _SETS = ("bus_set_reaches_joiners", "set_bus_resets_set", "paused_call_takes_switch")
+_RANGES = ("set_bus_old_range", "range_from_world_origin", "signal_keeps_h_prev", "pause_advances_range", "last_range_ramps",
+           "range_restarts_each_call")
+_LEVELLERS = ("leveller_post_fader", "follower_roots_leveller", "signal_keeps_a_prev", "pause_advances_leveller",
+              "leveller_pumps_below_floor", "leveller_restarts_each_call", "last_leveller_ramps")
+_LOOK = ("look_only_while_limited", "look_off_flushes", "look_on_no_silence", "pause_flushes_held", "limiter_restart_clears_held",
+         "set_buses_drops_held", "look_ignores_incoming")
 FEATURES = {     # fault -> the features a session must use for the fault to show
     "send_post_fader": ("room",), "set_bus_old_send": ("room",), "pause_advances_send": ("room",), "set_room_keeps_tail": ("room",),
     "gate_gates_send": ("gates", "room"), "limit_limits_send": ("limits", "room"),
     "switch_in_every_run": ("sets", "long calls"),      # (a jf_batch_run is never longer than max_batch_blocks)
     **{f: ("streams",) for f in _STREAMF}, **{f: ("outputs",) for f in OUTPUT_FAULTS}, "output_misses_wet": ("outputs", "room"),
     **{f: ("gates",) for f in _GATES}, **{f: ("limits",) for f in _LIMITS}, **{f: ("sets",) for f in _SETS},
+    **{f: ("ranges",) for f in _RANGES}, "range_after_limit": ("ranges", "limits"), "range_gates_send": ("ranges", "room"),
+    **{f: ("levellers",) for f in _LEVELLERS}, "leveller_levels_send": ("levellers", "room"),
+    "ranking_reads_levelled": ("levellers", "limits"), "leveller_before_limit": ("levellers", "limits"),
+    **{f: ("lookahead",) for f in _LOOK}, "output_ahead_of_lookahead": ("lookahead", "outputs"),
 }
 
 
 def features(n):
     c = SESSIONS[n]
-    return ({"room"} if c["taps"] else set()) | ({"gates", "limits"} if n in NEW + STREAMS else set()) | \
+    return ({"room"} if c["taps"] else set()) | ({"gates", "limits"} if n in NEW + STREAMS + LATE else set()) | \
+           ({"lookahead", "levellers", "ranges"} if n in LATE else set()) | \
            ({"sets"} if c.get("sets") else set()) | \
            ({"long calls"} if n not in WINDOWS else set()) | ({"streams", "outputs"} if n in STREAMS else set())
 
@@ -143,23 +169,57 @@ def make_engine(n, hrir, jf):
 
 
 # ------------------------------------------------------------------------------------------------------- the bound --
+def block_d(parts):
+    """pre m_max of one block from what the model kept of it (None: the block of zeros a look-ahead bus starts on -- exact)"""
+    if parts is None:
+        return 0.0
+    pre = sum_tol(TOL64, parts["n"]) + (room_model.wet_tol(parts["P"]) if parts["P"] else 0.0)
+    return pre * max(1.0, parts["pre_max"]) * parts["m_max"]
+
+
 def bounds(last, nb, K):
-    """[n_buses][K] from what the model left in `last` for its last rendered call"""
+    """[n_buses][K] from what the model left in `last` for its last rendered call.
+
+    On a LOOK-AHEAD bus the block handed out is the held block h, a block late; let d_h and d be the pre m_max of the held and of
+    the incoming block.  Limiter off: out = h, so the bound is the held block's own d_h.  Limiter on: 2 max(d_h, d).  out = a h
+    with a <= max(g_prev, e) <= 1, so the error of h contributes at most d_h.  e = min(t_h, t, g_prev + r) moves by at most
+    t_h d_h / p_h (p_h moved by d_h) or t d / p.  When t decides, t <= t_h means p >= p_h, so |h| de <= p_h t d / p <= d; when
+    t_h decides, |h| de <= p_h t_h d_h / p_h <= d_h; g_prev + r carries the same error as the block before, already counted
+    there.  The ramp between g_prev and e and the clamp are 1-Lipschitz.  Together at most d_h + max(d_h, d) <= 2 max(d_h, d)."""
     out = np.zeros((nb, K))
     for b in range(nb):
         for k in range(K):
             i = last["infos"][b][k]
+            if i.get("look"):
+                d_h, d = block_d(i["held_parts"]), block_d(i["parts"])
+                out[b, k] = 2.0 * max(d_h, d) if i["limited"] else d_h
+                continue
             pre = sum_tol(TOL64, int(last["n_on"][b, k])) + (room_model.wet_tol(last["P"]) if last["P"] else 0.0)
             pre *= max(1.0, float(np.abs(last["pre"][b, k]).max()))
             out[b, k] = pre * i["m_max"] * (2.0 if i["limited"] else 1.0)
     return out
 
 
+def peak_in_bound(last, b, k):
+    """the bound of the block that CAME IN (jf_bus_meters' peak_in): pre m_max of that block"""
+    i = last["infos"][b][k]
+    if i.get("look"):
+        return block_d(i["parts"])
+    return bounds_one(last, b, k) / (2.0 if i["limited"] else 1.0)
+
+
+def bounds_one(last, b, k):
+    pre = sum_tol(TOL64, int(last["n_on"][b, k])) + (room_model.wet_tol(last["P"]) if last["P"] else 0.0)
+    return pre * max(1.0, float(np.abs(last["pre"][b, k]).max())) * last["infos"][b][k]["m_max"] * (2.0 if last["infos"][b][k]["limited"] else 1.0)
+
+
 # --------------------------------------------------------------------------------------------------- the generator --
 class Generator:
-    def __init__(self, n, model, castanets, sets=(), redraw=0):
+    def __init__(self, n, model, castanets, sets=(), redraw=0, jf=None):
         self.n, self.c, self.m, self.x = n, SESSIONS[n], model, castanets
-        self.new, self.windows, self.sets = n in NEW, n in WINDOWS, list(sets)
+        self.late, self.jf = n in LATE, jf
+        self.new, self.windows, self.sets = n in NEW or (self.late and n not in STREAMS), n in WINDOWS, list(sets)
+        self.xyz_draws = self.xyz_redraws = 0     # the late sessions: (pose, point) draws held to the library's float32 x, y, z
         self.pulled = []
         self.force_long = False        # a motif asks for a batch call of more than MAX_K blocks
         if n in STREAMS:
@@ -172,7 +232,7 @@ class Generator:
         self.nxt = 0
         self.callback = False          # session 3's last phase
         self.room_seed = 0
-        self.run = {2: 2, 6: 4, 7: 2, 8: 4}.get(n, 1)      # sources are first put on the buses in aligned runs of this many
+        self.run = {2: 2, 6: 4, 7: 2, 8: 4, 11: 2, 12: 4}.get(n, 1)      # sources are first put on the buses in aligned runs of this many
         self.amp = 1.4 if self.c["hrir"] == "cloud" else 0.8     # (the castanets peak at 0.66)
         self.stage = False             # a gain trajectory goes ahead of the next batch call
         self.pending = None            # ... the op that stages it
@@ -209,8 +269,21 @@ class Generator:
         self.draws += int(np.size(ele))
         return float(min(np.min(pose_model.off_half(ele)), np.min(pose_model.off_half(azi)))) >= HALF_EPS
 
+    def xyz_ok(self, poses, pts):
+        """the late sessions: the library's own float32 x, y, z of these (pose, point) pairs (jf_position_from_world, the host
+        twin of the GPU's kernels) are pose_model.records' -- so that a hearing range's h may be compared exactly"""
+        if not self.late or self.jf is None:
+            return True
+        poses, pts = np.asarray(poses, np.float32).reshape(-1, 7), np.asarray(pts, np.float32).reshape(-1, 3)
+        self.xyz_draws += len(pts)
+        return bool(np.array_equal(self.jf.positions_from_world(poses, pts)[..., 2:], pose_model.records(poses, pts)[0][..., 2:]))
+
     def standing_ok(self):
-        w = self.m.world_angles()
+        m = self.m
+        w = m.world_angles()
+        if w and not self.xyz_ok([m.pose[m.hear_bus[s]] for s, _, _ in w], [m.world_point(s) for s, _, _ in w]):
+            self.xyz_redraws += 1
+            return False
         return not w or self.off_half([e for _, e, _ in w], [a for _, _, a in w])
 
     def settle(self, apply):
@@ -241,6 +314,8 @@ class Generator:
                 pt = pts[:, s] if kind == "world" else pts[:, m.object_of[s]]
                 _, ele, azi = pose_model.records(poses[:, m.bus[s]], pt)
                 rec_ok = rec_ok and self.off_half(ele, azi)
+                if rec_ok and not self.xyz_ok(poses[:, m.bus[s]], pt):
+                    rec_ok, self.xyz_redraws = False, self.xyz_redraws + 1
             if rec_ok:
                 return pts, poses.astype(np.float32)
             self.redraws += 1
@@ -378,7 +453,7 @@ class Generator:
             if k == 0:
                 yield ("knob", "set_rt_max_sources", int(rng.choice([0, 2, 8192])))
             elif k == 1:
-                groups = {1: [1, 0], 2: [2, 4, S], 6: [2, 2, 4], 7: [2, 0, S], 8: [2, 2, 4]}.get(self.n, [1, S, 0])
+                groups = {1: [1, 0], 2: [2, 4, S], 6: [2, 2, 4], 7: [2, 0, S], 8: [2, 2, 4], 11: [2, 0, S], 12: [2, 2, 4]}.get(self.n, [1, S, 0])
                 yield ("knob", "set_source_group", int(rng.choice(groups)))
             elif k == 2 and c["hrir"] == "kemar":
                 yield ("knob", "set_interp_table", int(rng.integers(0, 3)))
@@ -427,6 +502,8 @@ class Generator:
             if not heard:
                 yield ("set_signal", s, self.speech())
             yield ("set_priority", s, 255)
+            if self.late:        # ... and whatever the ranges do
+                yield ("set_range_exempt", s, True)
         if m.paused:
             yield ("set_pause", False)
         if which == 0:      # a pause over a level, a send and a master change; the limiter mid-release
@@ -605,6 +682,9 @@ class Generator:
         """the session: ("audio" ops render; everything else is a setter)"""
         c, m, rng = self.c, self.m, self.rng
         S = m.S
+        if self.late:
+            yield from self.ops_late()
+            return
         if self.new:
             yield from self.ops_new()
             return
@@ -1262,6 +1342,580 @@ class Generator:
             yield ("collect_block",)
             yield from self.pulls(True)
 
+    # ---- sessions 11 to 13: look-ahead, levellers and ranges on top of the above (their own code paths again) --
+    LATE_CYCLE = {11: (38, 30, 7, 31, 0, 32, 8, 44, 34, 9, 35, 4, 36, 10, 37, 11, 39, 12, 40, 13, 42, 1, 2, 3, 5, 6),
+                  12: (38, 30, 7, 31, 0, 32, 8, 44, 34, 9, 35, 4, 36, 10, 37, 11, 39, 43, 40, 13, 1, 2, 3, 6),
+                  13: (38, 30, 20, 31, 27, 32, 0, 44, 29, 34, 21, 35, 109, 36, 2, 37, 110, 39, 22, 40, 111, 41, 4, 42, 23, 113, 3, 24,
+                       1, 25, 5, 26)}
+    ROLES = {8: {1: "A", 3: "B", 5: "C", 6: "D"}, 5: {0: "A", 1: "B", 3: "C", 4: "D"}}      # S -> the levelled sources
+
+    def peaks_of(self, s):
+        """(the loudest, the quietest above 0) block peak of source s's input as the model holds it; for a live or a stream
+        source and for an empty signal what a feed can reach"""
+        m, B = self.m, self.c["B"]
+        r = m.root[s]
+        q = m.src[r]
+        if m.stream[r] is not None:       # (resampled noise overshoots its packets' peak: such a talker is never levelled up)
+            return 1.0, 0.01
+        if m.live[r] or len(q.buf) == 0:
+            return 0.7, 0.01
+        n = len(q.buf)
+        k = min(96, 2 * (n // B) + 2)
+        p = np.abs(q.buf[(q.count + np.arange(k * B)) % n]).reshape(k, B).max(axis=1).astype(np.float64)
+        p = p[p > 0]
+        return (float(p.max()), float(p.min())) if len(p) else (0.7, 0.01)
+
+    def top_of(self, s):
+        """the loudest block source s's window holds or can come to hold"""
+        m = self.m
+        return max([self.peaks_of(s)[0]] + m.peak_hist[s] + m.peak_hist[m.root[s]])
+
+    def leveller(self, s, kind):
+        """source s's leveller from the model's own block peaks of its input.  A: towards half the loudest block, at once; B: the
+        same, slowly (fall and rise limit); C: far down, onto min_gain; D: up, onto max_gain.  WINDOW NOISE: max_gain times the
+        loudest block the source's window can hold stays below 1, so only a quiet talker is levelled up."""
+        loud, quiet = self.peaks_of(s)
+        cap = float(max(1.0, min(4.0, 0.95 / self.top_of(s))))
+        floor = float(np.sqrt(loud * quiet)) if quiet < 0.5 * loud else 0.5 * loud
+        par = {"A": (0.5 * loud, floor, 0.25, cap, 0.5, 2.0), "B": (0.5 * loud, floor, 0.25, cap, 0.9, 1.1),
+               "C": (0.2 * loud, floor, 0.5, 1.0, 0.5, 2.0), "D": (1.5 * cap * loud, floor, 1.0, cap, 0.5, 2.0)}[kind]
+        par = (par[0], max(min(par[1], par[0]), 2.0 ** -50)) + par[2:]
+        return ("set_leveller", s) + tuple(float(np.float32(v)) for v in par)
+
+    def a_range(self, b):
+        """{near, far} of bus b from the model's own radii: they bracket the distances its talkers stand at"""
+        import range_model
+        m, rng = self.m, self.rng
+        rec = m._standing_records()
+        rs = sorted(float(range_model.radius(*rec[s, 2:5])) for s in range(m.S) if m.bus[s] == b)
+        rs = [r for r in rs if 0.05 < r < 100.0] or [0.5, 1.5]
+        mid = rs[len(rs) // 2]
+        near = 0.5 * (rs[0] + mid) * float(rng.uniform(0.9, 1.1))
+        far = max(1.2 * near + 0.1, 0.5 * (mid + rs[-1]) * float(rng.uniform(0.9, 1.1)))
+        return ("set_range", b, float(np.float32(near)), float(np.float32(far)))
+
+    def ensure(self):
+        """ahead of every call: a leveller whose max_gain has become too much for what its source's window can hold (a new
+        signal, a share, a live switch) is fitted again"""
+        m = self.m
+        for s in range(m.S):
+            par = m.lv_par[s]
+            if par["target"] > 0 and float(par["max_gain"]) * self.top_of(s) > 1.0:
+                yield self.leveller(s, self.roles.get(s, "A"))
+
+    def restore(self):
+        """what the op mix and the motifs have taken away comes back: ranges, look-ahead, the roles' levellers"""
+        m, rng = self.m, self.rng
+        for x in range(m.S):
+            if m.exempt[x] and rng.random() < 0.7:
+                yield ("set_range_exempt", x, False)
+        for b in range(m.n_buses):
+            if not m.rng_par[b, 1] > 0 and rng.random() < 0.6:
+                yield self.a_range(b)
+            if not m.look_set[b] and rng.random() < 0.6:
+                yield ("set_lookahead", b, True)
+        for s, kind in self.roles.items():
+            if not m.lv_par[s]["target"] > 0 and rng.random() < 0.6:
+                yield self.leveller(s, kind)
+
+    def late_setter(self):
+        m, rng = self.m, self.rng
+        S, nb = m.S, m.n_buses
+        s, b = int(rng.integers(0, S)), int(rng.integers(0, nb))
+        u = int(rng.integers(0, 100))
+        if u < 14:
+            yield self.a_range(b)
+        elif u < 18:
+            yield ("set_range", b, 0.0, 0.0)
+        elif u < 25:
+            yield ("set_range_exempt", s, bool(rng.random() < 0.3))
+        elif u < 36:
+            s = int(rng.choice(sorted(self.roles)))
+            yield self.leveller(s, self.roles[s])
+        elif u < 40:
+            yield ("set_leveller", int(rng.choice(sorted(self.roles))), 0.0)
+        elif u < 42:
+            yield ("set_levellers", 0.05, 0.01, 0.5, 1.0, 0.5, 2.0)        # (every source, never up)
+        elif u < 54:
+            yield ("set_lookahead", b, bool(rng.random() < 0.7))
+        elif u < 78:      # a talker at a distance of its own: inside, in the ramp and beyond all occur
+            yield ("set_spherical", s, float(rng.integers(-40, 91)), float(rng.integers(0, 360)), float(np.float32(rng.uniform(0.2, 3.0))))
+        elif u < 86:
+            if not self.callback:
+                yield ("set_input_meters", bool(rng.random() < 0.85))
+        else:             # what the header refuses, with nothing changed
+            yield [("set_range", b, 2.0, 1.0), ("set_range", nb, 0.5, 1.0), ("set_range", b, -0.5, 1.0), ("set_range", b, 1.0, 0.0),
+                   ("set_leveller", s, 0.25, 0.5), ("set_leveller", s, 0.25, 0.01, 0.0), ("set_leveller", s, 0.25, 0.01, 1.0, 1.0, 0.5, 2.5),
+                   ("set_lookahead", nb, 1), ("set_lookahead", -1, 0)][int(rng.integers(0, 9))]
+
+    def actors(self):
+        """two resident sources without a gate for a motif's script, each its own root"""
+        m = self.m
+        two = [x for x in range(self.GATED, m.S) if m.stream[x] is None][-2:]
+        for x in two:
+            if m.live[x] and not self.callback:
+                yield ("set_live", x, False)
+        self.t0, self.t1 = two
+
+    def late_motif(self, which):
+        """the orders the clauses about ranges, levellers and look-ahead are about"""
+        m, rng, c = self.m, self.rng, self.c
+        cb = self.callback
+        if which < 30 or which >= 100:
+            if cb and which >= 7:        # (the gate, limit and set motifs give followers new signals and move sources: not
+                return                   # with a block in flight)
+            if which == 2:               # (its world-placed source must still be one when it changes buses: a per-block call)
+                self.force_block = True
+            for x in range(m.S):         # the older motifs' talkers are heard wherever they stand: their clauses are about
+                if not m.exempt[x]:      # other things (restore() takes the exemptions away again)
+                    yield ("set_range_exempt", x, True)
+            if self.n in STREAMS:
+                yield from self.stream_motif(which)
+            else:
+                yield from self.new_motif(which)
+            return
+        if m.paused:
+            yield ("set_pause", False)
+        if cb and which in (35, 40, 41, 42):     # (shares, set_buses, set_output and batch calls: not with a block in flight)
+            return
+        yield from self.actors()
+        t0, t1 = self.t0, self.t1
+        if cb and (m.live[t0] or m.live[t1] or m.root[t0] != t0 or m.root[t1] != t1 or (which in (31, 44) and m.bus[t0] != m.bus[t1])):
+            return              # (set_live, a follower's set_signal and set_bus: not with a block in flight)
+        A = lambda k=1: ("blocks", 1 if cb else k, 0.5)
+        b = m.bus[t0]
+        role = lambda x: self.leveller(x, self.roles[x]) if x in self.roles else ("set_leveller", x, 0.0)
+        if which == 30:     # a talker walks out of range over three calls and back: by setter, by trajectory, by a listener who walks
+            yield ("set_signal", t0, self.talk(60, 0, 0.4))
+            yield ("set_gain", t0, 1.0, False)
+            yield ("set_priority", t0, 255)
+            yield ("set_range_exempt", t0, False)
+            yield ("set_range", b, 0.5, 1.0)
+            for r in (0.4, 0.75, 1.2, 1.3, 0.8, 0.45):
+                yield ("set_spherical", t0, 0.0, 90.0, r)
+                yield A()
+            if not cb:
+                K = 7
+                rec = np.repeat(m._standing_records()[None], K, axis=0)
+                for k, r in enumerate((0.45, 0.7, 0.95, 1.25, 0.9, 0.6, 0.4)):
+                    rec[k, t0] = (0.0, 270.0) + tuple(model64.from_spherical(0.0, 270.0, r)[2])
+                yield ("records", rec)
+            for d in (0.4, 0.8, 1.3, 1.4, 0.8, 0.4):       # the talker stands, the listener walks away along x and comes back
+                def apply(d=d):
+                    p = np.array([d + rng.uniform(-0.03, 0.03), rng.uniform(-0.03, 0.03), 0.0], np.float32)
+                    m.set_world(t0, 0.0, 0.25, -0.1)
+                    m.set_listener(b, p, np.array([1.0, 0.0, 0.0, 0.0], np.float32))
+                    return ("set_listener", b, p.copy(), np.array([1.0, 0.0, 0.0, 0.0], np.float32))
+                yield ("set_world", t0, 0.0, 0.25, -0.1)
+                yield self.settle(apply)
+                yield A()
+            yield ("set_spherical", t0, 0.0, 90.0, 1.4)    # beyond far, and exempt: heard in full
+            yield ("set_range_exempt", t0, True)
+            yield A()
+            yield A()
+            yield ("set_range_exempt", t0, False)
+            yield A()
+            yield ("set_priority", t0, 0)
+        elif which == 31:   # a loud talker beyond far and a quiet one inside near on a bus with one place; then the range taken away
+            if m.bus[t1] != b:
+                yield from self.to_bus(t1, b)
+            yield ("set_signal", t0, self.talk(30, 0, 0.5))
+            yield ("set_signal", t1, self.talk(30, 0, 0.1))
+            for x, r, azi in ((t0, 1.4, 60.0), (t1, 0.3, 300.0)):
+                yield ("set_spherical", x, 0.0, azi, r)
+                yield ("set_gain", x, 1.0, False)
+                yield ("set_priority", x, 9)
+                yield ("set_range_exempt", x, False)
+                yield ("set_leveller", x, 0.0)
+            if m.room is not None and not cb:
+                yield ("set_send", t0, 0.5)
+            yield ("set_voices", b, 1, 0.5, True)
+            yield ("set_range", b, 0.5, 1.0)
+            for _ in range(3):
+                yield A()
+            yield A(3)
+            yield ("set_range", b, 0.0, 0.0)
+            yield A()
+            yield A()
+            yield self.a_range(b)
+            yield ("set_voices", b, 2, 0.5, True)
+            yield ("set_priority", t0, 0)
+            yield ("set_priority", t1, 0)
+            yield role(t0)
+            yield role(t1)
+        elif which == 32 and m.n_buses > 1 and not cb:    # set_bus to a bus with another range, mid-ramp
+            b1 = (b + 1) % m.n_buses
+            yield ("set_signal", t0, self.talk(30, 0, 0.4))
+            yield ("set_gain", t0, 1.0, False)
+            yield ("set_priority", t0, 255)
+            yield ("set_range_exempt", t0, False)
+            yield ("set_spherical", t0, 0.0, 120.0, 0.75)
+            yield ("set_range", b, 0.5, 1.0)
+            yield ("set_range", b1, 0.2, 0.6)
+            yield A()
+            yield from self.to_bus(t0, b1, whole=False)
+            yield A()
+            yield A()
+            yield from self.to_bus(t0, b, whole=False)
+            yield A()
+            yield self.a_range(b1)
+            yield ("set_priority", t0, 0)
+        elif which == 34:   # the last range set back to far = 0 with a source at h = 0.3, then set again; the same for the last leveller
+            yield ("set_signal", t0, self.talk(40, 0, 0.4))
+            yield ("set_gain", t0, 1.0, False)
+            yield ("set_priority", t0, 255)
+            yield ("set_range_exempt", t0, False)
+            yield ("set_spherical", t0, 0.0, 45.0, 0.85)
+            for x in range(m.n_buses):
+                yield ("set_range", x, 0.5, 1.0) if x == b else ("set_range", x, 0.0, 0.0)
+            yield A()
+            yield A()
+            yield ("set_range", b, 0.0, 0.0)
+            yield A()
+            yield ("set_range", b, 0.5, 1.0)
+            yield A()
+            yield A()
+            for x in range(m.S):
+                if x != t0 and m.lv_par[x]["target"] > 0:
+                    yield ("set_leveller", x, 0.0)
+            yield ("set_leveller", t0, 0.08, 0.01, 0.5, 1.0, 0.5, 2.0)      # (a loud talker, far down: a = 0.5)
+            yield A()
+            yield A()
+            yield ("set_leveller", t0, 0.0)
+            yield A()
+            yield ("set_leveller", t0, 0.08, 0.01, 0.5, 1.0, 0.5, 2.0)
+            yield A()
+            yield A()
+            yield ("set_priority", t0, 0)
+            for x in sorted(self.roles):
+                yield self.leveller(x, self.roles[x])
+            for x in range(m.n_buses):
+                yield self.a_range(x)
+        elif which == 35:   # a root with two followers on two buses, each levelled differently, one below its floor
+            f = [x for x in range(m.S) if x != t0 and m.stream[x] is None and m.root[x] == x and
+                 not any(m.root[y] == x for y in range(m.S) if y != x)][-2:]
+            was_live = [x for x in f if m.live[x]]
+            yield ("set_signal", t0, self.talk(40, 0, 0.3))
+            for i, x in enumerate(f):
+                if m.live[x]:
+                    yield ("set_live", x, False)
+                yield ("share_input", x, t0)
+                yield ("reset", x)               # (levelled from 1 again: a leveller that holds keeps whatever gain it had)
+                yield ("set_gate", x, 0.0, 0.0, 0)
+                if i == 0 and m.n_buses > 1:
+                    yield from self.to_bus(x, (b + 1) % m.n_buses, whole=False)
+            for i, x in enumerate([t0] + f):
+                yield ("set_spherical", x, 0.0, float(60 + 100 * i), 0.4)
+                yield ("set_gain", x, 1.0, False)
+                yield ("set_priority", x, 255)
+                yield ("set_range_exempt", x, True)
+            yield ("set_leveller", t0, 0.15, 0.01, 0.25, 1.0, 0.5, 2.0)
+            if f:
+                yield ("set_leveller", f[0], 0.05, 0.01, 0.5, 1.0, 0.9, 1.1)
+            if len(f) > 1:
+                yield ("set_leveller", f[1], 0.6, 0.6, 0.5, 1.5, 0.5, 2.0)          # (its floor lies above the talk: held at 1)
+            yield A(4)
+            yield A()
+            for x in f:
+                yield ("share_input", x, -1)
+                yield ("set_signal", x, self.speech())
+                yield ("set_priority", x, 0)
+                yield ("set_range_exempt", x, False)
+                if x < self.GATED:
+                    yield ("set_gate", x) + self.thresholds(x)
+                yield role(x)
+            for x in was_live:
+                yield ("set_live", x, True)
+            yield ("set_priority", t0, 0)
+            yield ("set_range_exempt", t0, False)
+            yield role(t0)
+        elif which == 36:   # set_signal and reset on a source at a = max_gain and h = 0
+            yield ("set_signal", t0, self.talk(60, 0, 0.05))
+            yield ("reset", t0)                                  # (its window holds nothing loud: it may be levelled up)
+            yield ("set_gain", t0, 1.0, False)
+            yield ("set_priority", t0, 255)
+            yield ("set_range_exempt", t0, False)
+            yield ("set_range", b, 0.5, 1.0)
+            yield ("set_spherical", t0, 0.0, 200.0, 0.3)
+            yield ("set_leveller", t0, 0.5, 0.005, 1.0, 4.0, 0.5, 2.0)
+            for _ in range(3):
+                yield A()
+            yield ("set_spherical", t0, 0.0, 200.0, 1.4)
+            yield A()
+            yield A()
+            yield ("set_signal", t0, self.talk(60, 0, 0.05))
+            yield A()
+            yield A()
+            yield ("reset", t0)
+            yield A()
+            yield A()
+            yield ("set_spherical", t0, 0.0, 200.0, 0.3)
+            yield A()
+            yield ("set_priority", t0, 0)
+            yield role(t0)
+        elif which == 37:   # a pause across a source in its leveller's rise and a held loud block; setters asked for during the pause
+            yield ("set_signal", t0, self.talk(60, 0, 0.05))
+            yield ("reset", t0)
+            yield ("set_gain", t0, 1.0, False)
+            yield ("set_priority", t0, 255)
+            yield ("set_range_exempt", t0, False)
+            yield ("set_range", b, 0.5, 1.0)
+            yield ("set_spherical", t0, 0.0, 150.0, 0.3)
+            yield ("set_signal", t1, self.talk(60, 0, 0.3))      # (t0 is in its leveller's rise, t1 walks out of range while paused)
+            yield ("set_gain", t1, 1.0, False)
+            yield ("set_priority", t1, 255)
+            yield ("set_range_exempt", t1, False)
+            yield ("set_range", m.bus[t1], 0.5, 1.0)
+            yield ("set_spherical", t1, 0.0, 250.0, 0.3)
+            yield ("set_lookahead", b, True)
+            yield ("set_master", b, 1.0, False)
+            yield A()
+            yield ("set_leveller", t0, 0.5, 0.005, 1.0, 4.0, 0.5, 2.0)
+            if self.peak.get(b, 0.0) > 1e-3:
+                yield ("set_limiter", b, float(np.float32(0.4 * self.peak[b])), 0.125)
+            yield A()
+            yield ("set_pause", True)
+            yield ("set_spherical", t1, 0.0, 250.0, 1.4)       # (out of range while paused: h_prev is still 1 afterwards)
+            yield ("set_lookahead", b, False)
+            yield ("set_range", b, 0.05, 0.1)
+            yield ("set_leveller", t0, 0.0)
+            yield ("audio",)
+            yield ("set_lookahead", b, True)
+            yield ("set_range", b, 0.5, 1.0)
+            yield ("set_leveller", t0, 0.5, 0.005, 1.0, 4.0, 0.5, 2.0)
+            yield ("audio",)
+            yield ("set_pause", False)
+            yield A()
+            yield A()
+            yield ("set_priority", t0, 0)
+            yield ("set_priority", t1, 0)
+            yield role(t0)
+        elif which == 38:   # look-ahead turned on mid-stream; quiet blocks, blocks at three times the ceiling, then the release
+            yield ("set_signal", t0, self.talk(60, 0, 0.4))
+            yield ("set_gain", t0, 1.0, False)
+            yield ("set_priority", t0, 255)
+            yield ("set_range_exempt", t0, True)
+            yield ("set_leveller", t0, 0.0)
+            yield ("set_spherical", t0, 0.0, 30.0, 0.4)
+            yield ("set_lookahead", b, False)
+            yield ("set_master", b, 1.0, False)
+            yield A()
+            yield ("set_lookahead", b, True)
+            for _ in range(2):
+                if self.peak.get(b, 0.0) > 1e-3:
+                    yield ("set_limiter", b, float(np.float32(rng.uniform(0.3, 0.36) * self.peak[b] / max(m.m_new[b], 1e-3))), 0.125)
+                yield ("set_master", b, 0.1, False)
+                yield A()
+                yield A()
+                yield ("set_master", b, 1.0, False)
+                yield A()
+                yield A()
+                yield ("set_master", b, 0.1, False)
+                for _ in range(6):
+                    yield A()
+                yield ("set_master", b, 1.0, False)
+                yield A()
+            yield ("set_priority", t0, 0)
+            yield ("set_range_exempt", t0, False)
+            yield role(t0)
+        elif which == 39:   # look-ahead off while a loud block is held; the limiter off and on again while a loud block is held
+            yield ("set_lookahead", b, True)
+            yield ("set_master", b, 1.0, False)
+            yield A()
+            c0 = float(np.float32(0.4 * self.peak[b])) if self.peak.get(b, 0.0) > 1e-3 else 0.0
+            yield ("set_limiter", b, c0, 0.125)
+            yield A()
+            yield A()
+            yield ("set_lookahead", b, False)
+            yield A()
+            yield A()
+            yield ("set_lookahead", b, True)
+            yield A()
+            yield A()
+            yield ("set_limiter", b, 0.0, 1.0)
+            yield ("set_limiter", b, c0, 0.125)
+            yield A()
+            yield A()
+            yield ("set_limiter", b, 0.0, 1.0)
+            yield A()
+            yield ("set_limiter", b, c0, 0.125)
+            yield A()
+            yield A()
+        elif which == 40:   # jf_engine_set_buses growing and shrinking around a bus with a held block
+            yield ("set_lookahead", b, True)
+            yield A()
+            yield A()
+            yield from self.rebus(m.n_buses + 1 if m.n_buses <= c["buses"] else c["buses"])
+            yield A()
+            yield A()
+            yield from self.rebus(c["buses"])
+            yield A()
+        elif which == 41 and self.n in STREAMS:     # set_output on a bus while its held block is loud
+            outs = [x for x in range(len(c["outputs"])) if x < m.n_buses]
+            if outs:
+                x = int(rng.choice(outs))
+                yield ("set_lookahead", x, True)
+                yield A()
+                yield A()
+                yield ("set_output", x, c["outputs"][x])
+                yield A()
+                yield A(3)
+        elif which == 42:   # a call longer than max_batch_blocks with all three on
+            self.force_long = True
+            yield ("audio",)
+            self.force_long = False
+        elif which == 43:   # four windows with no setter between them
+            for _ in range(4):
+                yield ("audio",)
+        elif which == 44:   # a limited bus: the loud talker levelled far down still wins its place; the loser is levelled too
+            if m.bus[t1] != b:
+                yield from self.to_bus(t1, b)
+            yield ("set_signal", t0, self.talk(30, 0, 0.5))
+            yield ("set_signal", t1, self.talk(30, 0, 0.2))
+            for x, azi in ((t0, 80.0), (t1, 280.0)):
+                yield ("set_spherical", x, 0.0, azi, 0.4)
+                yield ("set_priority", x, 9)
+                yield ("set_range_exempt", x, True)
+            yield ("set_gain", t0, 0.5, False)
+            yield ("set_gain", t1, 1.0, False)
+            yield ("set_leveller", t0, 0.05, 0.01, 0.05, 1.0, 0.5, 2.0)
+            yield ("set_leveller", t1, 0.2, 0.01, 0.5, 1.0, 0.5, 2.0)
+            if m.room is not None and not cb:
+                yield ("set_send", t0, 0.5)
+            yield ("set_voices", b, 1, 0.0, True)
+            for _ in range(3):
+                yield A()
+            yield A(3)
+            yield ("set_voices", b, 2, 0.5, True)
+            for x in (t0, t1):
+                yield ("set_priority", x, 0)
+                yield ("set_range_exempt", x, False)
+                yield role(x)
+
+    def late_render(self, K=None, how=None, rec=None):
+        """the levellers fitted, then the call in the session's form.  K: a motif's call of so many blocks; rec: its records"""
+        m = self.m
+        if not m.paused:
+            yield from self.ensure()
+        if rec is not None and not self.callback and not m.paused:      # a motif's own trajectory
+            if self.windows:
+                yield ("upload_positions", rec)
+                self.traj, self.nxt, self.last_n = len(rec), len(rec), len(rec)
+                yield ("batch_run", 0, len(rec))
+                return
+            if self.n in STREAMS:
+                yield from self.pushes(len(rec), 0.5)
+            yield ("process_batch", rec, self.inp(len(rec)))
+            if self.n in STREAMS:
+                yield from self.pulls()
+            return
+        if self.n in STREAMS:
+            yield from self.stream_render(K, how)
+            return
+        if K is not None and not self.callback:
+            self.force_block, self.force_batch = K == 1, K > 1
+        yield from self.render()
+        self.force_block = self.force_batch = False
+
+    def ops_late(self):
+        c, m, rng = self.c, self.m, self.rng
+        S = m.S
+        streams = c.get("streams", ())
+        self.talks, self.at = {}, {}
+        self.roles = dict(self.ROLES[S])
+        for h in self.sets:
+            yield ("add_hrtf_set", h)
+        for s in range(S):
+            yield ("set_signal", s, self.speech())
+            yield ("set_spherical", s, 0.0, float(40 * s), float(np.float32(0.3 + 0.2 * s)))
+        yield ("set_buses", c["buses"])
+        for s in range(S):
+            yield ("set_bus", s, (s // self.run) % c["buses"] if self.run > 1 else s % c["buses"])
+        for b in range(m.n_buses):
+            p = self.a_pose()
+            yield ("set_listener", b, p[:3].copy(), p[3:].copy())
+        yield ("set_meters", True)
+        yield ("set_input_meters", True)
+        if self.run > 1:
+            yield ("knob", "set_source_group", 2)
+        if self.windows:
+            yield ("knob", "set_prep_ahead", True)
+        if c["taps"]:
+            yield self.room_op(0)
+            for s in range(0, S, 2):
+                yield ("set_send", s, 0.4)
+        for s, rate in enumerate(streams):
+            yield ("set_stream", s, rate)
+            yield self.stream_gate(s)
+        if streams:
+            yield ("set_live", len(streams), True)
+        else:
+            for s in range(self.GATED):
+                yield ("set_gate", s) + self.thresholds(s)
+        for b, rate in enumerate(c.get("outputs", ())):
+            yield ("set_output", b, rate)
+        yield ("set_voices", 0, 2, 0.5, True)
+        if self.sets:
+            yield ("set_hrtf", S - 1, 1, False)
+        # the three features, on from the start
+        for b in range(m.n_buses):
+            yield ("set_lookahead", b, True)
+            yield self.a_range(b)
+        for s, kind in self.roles.items():
+            yield self.leveller(s, kind)
+        plan = {11: {28: 3, 52: 2}}.get(self.n, {})
+        cycle = self.LATE_CYCLE[self.n]
+        turn, held = 0, 0
+        for step in range(c["steps"]):
+            self.pending = None
+            if self.n == 11 and step == c["steps"] - 25:
+                self.callback = True
+                if m.paused:
+                    yield ("set_pause", False)
+            held = held + 1 if m.paused else 0
+            if held > 2:
+                yield ("set_pause", False)
+                held = 0
+            if step in (12, 16):
+                yield ("set_mode", int(step == 12))
+            if self.n == 11 and step == 40:
+                yield ("knob", "set_source_group", 0)         # the group size is free from here on
+            if self.run > 1 and step % 4 == 0 and not self.callback:
+                yield from self.heal()
+            if not self.callback:
+                for x, rate in enumerate(streams):
+                    if m.stream[x] is None and rng.random() < 0.7:
+                        yield ("set_stream", x, rate)
+                        yield self.stream_gate(x)
+            yield from self.restore()
+            u = rng.random()
+            if step in plan and not self.callback:
+                src = self.rebus(plan[step])
+            elif step % 2 == 1:
+                src, turn = self.late_motif(cycle[turn % len(cycle)]), turn + 1
+            elif u < 0.45:
+                src = self.late_setter()
+            elif u < 0.6 and streams:
+                src = self.stream_setter()
+            elif u < 0.75 and not self.callback:
+                src = self.new_setter()
+            else:
+                src = self.setter()
+            for op in src:
+                if op == ("audio",):
+                    yield from self.late_render()
+                elif op[0] == "blocks":
+                    yield from self.late_render(op[1], op[2])
+                elif op[0] == "records":
+                    yield from self.late_render(rec=op[1])
+                else:
+                    yield op
+            yield from self.late_render()
+        if self.callback:
+            yield ("collect_block",)
+        if streams:
+            yield from self.pulls(True)
+
     def one_launch(self):
         """Before buses, gains, masters and meters: per-block calls of one bus go through the one-launch real-time kernel -- with
         a follower (an alias there) and a world-placed source -- then a gain takes the calls to the batch pipeline and, settled
@@ -1324,13 +1978,14 @@ class Trajectory:
     """what jf_batch_upload_* left on the device: the records, formed at the upload from the buses and objects of that moment"""
 
     def __init__(self):
-        self.rec = None
+        self.rec = self.pts = None      # (pts: the world points the records were formed from -- a fault's reading only)
 
     def upload(self, model, op):
         if op[0] == "upload_positions":
-            self.rec = np.asarray(op[1], np.float32)
+            self.rec, self.pts = np.asarray(op[1], np.float32), None
         else:
             self.rec = model._world_records(op[1], op[2], list(model.object_of) if op[0] == "upload_objects" else None)
+            self.pts = np.asarray(op[1], np.float32)[:, list(model.object_of)] if op[0] == "upload_objects" else np.asarray(op[1], np.float32)
 
 
 def apply_model(model, traj, op):
@@ -1345,7 +2000,7 @@ def apply_model(model, traj, op):
             return None, 0
         if name == "batch_run":
             model.device_form()
-            return model.run_records(traj.rec[op[1]:op[1] + op[2]]), 0
+            return model.run_records(traj.rec[op[1]:op[1] + op[2]], None if traj.pts is None else traj.pts[op[1]:op[1] + op[2]]), 0
         if name == "callback":
             res = model.process_block(op[1], late=True)
             if not model.last.get("paused") and not model.fault:
@@ -1412,7 +2067,7 @@ def generate(n, hrir, castanets, jf=None):
     "redraw" in SESSIONS -- another seed for all of its signals."""
     redraw = SESSIONS[n].get("redraw", 0)
     model, traj = make_model(n, hrir, jf), Trajectory()
-    gen = Generator(n, model, castanets, further_sets(n, hrir, jf) if SESSIONS[n].get("sets") else (), redraw)
+    gen = Generator(n, model, castanets, further_sets(n, hrir, jf) if SESSIONS[n].get("sets") else (), redraw, jf)
     for op in gen.ops():
         res, code = apply_model(model, traj, op)
         if op[0] in AUDIO and res is not None:

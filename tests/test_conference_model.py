@@ -3,14 +3,18 @@ references the feature tests already hold the kernels to; (2) its dry buses agre
 tests/test_probes.py; (3) every clause counts: a copy of the model with ONE clause of the header misread differs from the true
 model by at least 100 bounds in at least one block of every GPU session that uses the feature (the sessions' op lists are
 replayed here: tests/conference_sessions.py generates them without a GPU); (4) the pose draws; (5) the op lists of sessions 1 to
-6 are byte for byte what they were before sessions 7 and 8 were added.  In (1) HRTF sets, voice gates and voice limits reduce
-EXACTLY to sets_model.SetsModel, gate_model.GateModel fed GateTrack's g_eff and voices_model.VoiceModel fed VoiceTrack's g_out.
+10 are byte for byte what they were before sessions 11 to 13 were added.  In (1) HRTF sets, voice gates and voice limits reduce
+EXACTLY to sets_model.SetsModel, gate_model.GateModel fed GateTrack's g_eff and voices_model.VoiceModel fed VoiceTrack's g_out;
+hearing ranges and levellers to range_model.RangeTrack and level_model.LevelTrack bit for bit, the look-ahead rule in float64
+to lookahead_model.look_block within 4 float32 ulps of the block's peak and on every decision.
 Each test prints its figures (pytest -s, or -rP)."""
 import numpy as np
 import pytest
 
 import conference_sessions as cs
 import gate_model
+import level_model
+import lookahead_model
 import master_model
 import output_model
 import stream_model
@@ -18,10 +22,11 @@ import model64
 import oracle_lib
 import pose_model
 import probes
+import range_model
 import room_model
 import sets_model
 import voices_model
-from conference_model import FAULTS, ConferenceModel, master_block64
+from conference_model import FAULTS, ConferenceModel, look_block64, master_block64
 from conftest import sum_tol
 from gain_model import GainModel
 
@@ -250,6 +255,149 @@ def test_limits_alone_are_the_voice_model(hrir):
     assert lost >= 8 and m.ramps["out"] >= 1 and m.ramps["in"] >= 1, (lost, m.ramps)
 
 
+def test_ranges_alone_are_the_range_model(hrir):
+    """range_model's scene (eight talkers of every kind on three buses, one exempt, one bus without a range) cut into three calls,
+    with a gain fade, a reset, a source carried to a bus with another range, and a range taken away while another bus keeps
+    one: h, g_rg and g_rg_prev are RangeTrack's bit for bit, the buses LevelModel's (GainModel fed those gains) exactly"""
+    S8 = range_model.SCENE_S
+    sigs, xyz = room_model.signals(S8, 3), range_model.scene_tracks()
+    pos = np.zeros(xyz.shape[:2] + (5,), np.float32)
+    pos[..., 0], pos[..., 1], pos[..., 2:] = 0.0, 40.0 * np.arange(S8), xyz
+    track, ref = range_model.scene_track(3), level_model.LevelModel(B, L, S8, hrir)
+    m = ConferenceModel(B, L, S8, hrir)
+    m.set_buses(3)
+    m.set_input_meters(True)
+    for s in range(S8):
+        m.set_signal(s, sigs[s])
+        ref.set_signal(s, sigs[s])
+        m.set_bus(s, range_model.SCENE_BUS[s])
+    for b, (near, far) in range_model.SCENE_RANGES.items():
+        m.set_range(b, near, far)
+    for s in range_model.SCENE_EXEMPT:
+        m.set_range_exempt(s)
+    bus = list(range_model.SCENE_BUS)
+    g, g_prev = np.ones(S8, np.float32), np.ones(S8, np.float32)
+    seen = set()
+    for a, b in ((0, 5), (5, 8), (8, 12)):
+        if a == 5:        # a fade on a talker in the ramp, a reset of one beyond, one carried to the bus with the other range
+            m.set_gain(1, 0.5, fade=True)
+            g[1] = 0.5
+            m.reset(3), track.reset(3), ref.reset(3)
+            m.set_bus(5, 0), track.set_bus(5, 0)
+            bus[5] = 0
+        if a == 8:        # a range taken away while another bus keeps one: back to 1 over one block
+            m.set_range(1, 0.0, 0.0), track.set_range(1, 0.0, 0.0)
+        want = track.run(pos[a:b], np.tile(g, (b - a, 1)), g_prev)
+        got = m.process_batch(pos[a:b])
+        assert np.array_equal(m.last["range_gains"], want["h"].T), (a, m.last["range_gains"].T.tolist(), want["h"].tolist())
+        assert np.array_equal(m.gains_seen[0], want["g_rg"]) and np.array_equal(m.gains_seen[1], want["g_rg_prev"]), a
+        partial = ref.process_batch(pos[a:b], want["g_rg"], want["g_rg_prev"])[1]
+        for j in range(3):
+            assert np.array_equal(got[j], partial[[s for s in range(S8) if bus[s] == j]].sum(axis=0)), (a, j)
+        seen |= {"inside"} if (want["h"] == 1).any() else set()
+        seen |= {"ramp"} if ((want["h"] > 0) & (want["h"] < 1)).any() else set()
+        seen |= {"beyond"} if (want["h"] == 0).any() else set()
+        g_prev = g.copy()
+    assert seen == {"inside", "ramp", "beyond"} and m.range_counts["skipped"] >= 5, (seen, dict(m.range_counts))
+    # the last range gone: every h is 1 at once, no getter any more
+    m.set_range(0, 0.0, 0.0)
+    m.process_batch(pos[:2])
+    assert m.last["range_gains"] is None and np.array_equal(m.gains_seen[1], g) and (m.h_prev == 1).all()
+
+
+def test_levellers_alone_are_the_level_model(hrir):
+    """bursts through levellers of every kind -- at once, slowly, onto min_gain, a follower with parameters of its own held below
+    its floor -- behind a gate and a voice limit, three calls with one leveller taken away before the last: a, g_lv and g_lv_prev
+    are LevelTrack's bit for bit, the bus LevelModel's exactly"""
+    sigs, pos = _bursts(S, blocks=12, seed=33), room_model.positions(S, 14)
+    track, ref, m = level_model.LevelTrack(B, S), level_model.LevelModel(B, L, S, hrir), _model(hrir, sigs)
+    for s in range(S):
+        track.set_signal(s, sigs[s])
+        ref.set_signal(s, sigs[0 if s == 3 else s])
+    track.share_input(3, 0)
+    m.share_input(3, 0)
+    m.set_input_meters(True)
+    for x in (track, m):
+        x.set_gate(1, 0.2, 0.05, 1)
+        x.set_voices(0, 3, 0.5)
+        x.set_leveller(0, target=0.15, floor=0.05, min_gain=0.25, max_gain=2.0, fall=0.5, rise=2.0)
+        x.set_leveller(1, target=0.2, floor=0.005, min_gain=0.25, max_gain=2.0, fall=0.9, rise=1.1)
+        x.set_leveller(2, target=0.05, floor=0.02, min_gain=0.5, max_gain=1.0, fall=0.5, rise=2.0)
+        x.set_leveller(3, target=0.9, floor=0.9, min_gain=0.5, max_gain=4.0, fall=0.5, rise=2.0)
+    lines = set()
+    for a, b in ((0, 6), (6, 9), (9, 14)):
+        if a == 9:        # taken away while others remain: back to 1 over one block
+            for x in (track, m):
+                x.set_leveller(0, target=0.0)
+        want = track.run(b - a)
+        got = m.process_batch(pos[a:b])
+        assert np.array_equal(m.last["level_gains"], want["a"].T), (a, m.last["level_gains"].T.tolist(), want["a"].tolist())
+        assert np.array_equal(m.gains_seen[0], want["g_lv"]) and np.array_equal(m.gains_seen[1], want["g_lv_prev"]), a
+        assert np.array_equal(got[0], ref.process_batch(pos[a:b], want["g_lv"], want["g_lv_prev"])[0]), a
+        lines |= set(int(v) for v in want["branch"].ravel())
+    assert lines == set(range(6)), lines
+    assert (m.last["level_gains"][3] == 1).all() and m.level_counts["clamp_min"] >= 1, dict(m.level_counts)
+
+
+def test_lookahead_alone_is_the_lookahead_rule(hrir):
+    """look_block64 against lookahead_model.look_block on float32 inputs: the same decisions (attack, release, ramp), e and p
+    within 2 float32 ulps, the block handed out within 4 float32 ulps of the held block's peak, for inputs whose peaks are not
+    within 1e-6 relative of the ceiling (test_masters_alone_are_the_master_rule's tolerance).  The delay is exact: the new held
+    block is m x, with the limiter off the held block goes out bit for bit, and a model bus with look-ahead on hands out the
+    blocks of one without, one block late behind a block of zeros."""
+    rng = np.random.default_rng(19)
+    eps = float(np.finfo(np.float32).eps)
+    decided = {"incoming": 0, "held": 0, "release": 0}
+    for trial in range(300):
+        x = (rng.uniform(-1, 1, 2 * B) * rng.uniform(0.05, 1.0)).astype(np.float32)
+        held = (rng.uniform(-1, 1, 2 * B) * rng.uniform(0.05, 1.0)).astype(np.float32)
+        if trial % 7 == 0:
+            held[:] = 0
+        p_held = np.float32(np.abs(held).max())
+        m_prev, m_new = (np.float32(v) for v in rng.uniform(0.3, 1.0, 2))
+        c = np.float32(rng.uniform(0.3, 0.9) * max(np.abs(x).max(), p_held)) if trial % 3 else np.float32(0)
+        r, g_prev = np.float32(0.125), np.float32(rng.uniform(0.3, 1.0))
+        ramp = bool(trial % 2)
+        o32, v32, i32 = lookahead_model.look_block(x, B, m_prev, m_new, ramp, c, r, held, p_held, g_prev)
+        o64, v64, i64 = look_block64(x, B, float(m_prev), float(m_new), ramp, float(c), float(r), held, float(p_held), float(g_prev))
+        if c > 0 and (abs(i64["p"] / float(c) - 1) < 1e-6 or abs(float(p_held) / float(c) - 1) < 1e-6):
+            continue
+        if not ramp:
+            assert np.array_equal(v64.astype(np.float32), v32)
+        if c == 0:
+            assert np.array_equal(o64.astype(np.float32), held) and np.array_equal(o32, held)
+        assert (i32["attack"], i32["release"], i32["ramp"]) == (i64["attack"], i64["release"], i64["ramp"])
+        assert abs(float(i32["g"]) - i64["g"]) <= 2 * eps and abs(float(i32["p"]) - i64["p"]) <= 2 * eps * i64["p"]
+        assert np.abs(v64 - v32).max() <= 4 * eps * max(i64["p"], 1e-30)
+        assert np.abs(o64 - o32).max() <= 4 * eps * max(float(p_held), 1e-30)
+        if c > 0:
+            assert float(np.abs(o64).max()) <= float(c)
+            decided["incoming"] += i64["t"] < i64["t_h"] and i64["g"] == i64["t"]
+            decided["held"] += i64["t_h"] < i64["t"] and i64["g"] == i64["t_h"]
+            decided["release"] += i64["release"]
+    assert min(decided.values()) >= 10, decided
+    # a model bus: the delay is exact, with the limiter off and on; turning off drops the held block, turning on again holds zeros
+    sigs, pos = _sigs(), room_model.positions(S, K)
+    plain, m = _model(hrir, sigs), _model(hrir, sigs)
+    x = plain.process_batch(pos)[0]
+    m.set_lookahead(0, True)
+    assert m.bus_latency(0) == 0 and m.lookahead(0)
+    got = m.process_batch(pos[:3])[0]
+    assert m.bus_latency(0) == B and not got[0].any() and np.array_equal(got[1:], x[:2])
+    assert m.last["infos"][0][0]["silent"] and not m.last["infos"][0][1]["silent"]
+    c = 0.45 * float(np.abs(x[2:5]).max())
+    m.set_limiter(0, c, 0.125)
+    got = m.process_batch(pos[3:5])[0]
+    g, h, p_h = 1.0, x[2], float(np.abs(x[2]).max())
+    for k in (3, 4):
+        want, h, i = look_block64(x[k], B, 1.0, 1.0, k == 3, float(np.float32(c)), 0.125, h, p_h, g)
+        g, p_h = i["g"], i["p"]
+        assert np.array_equal(got[k - 3], want) and float(np.abs(want).max()) <= float(np.float32(c))
+    m.set_lookahead(0, False)
+    m.set_limiter(0, 0.0)
+    assert np.array_equal(m.process_batch(pos[5:])[0], x[5:]) and m.bus_latency(0) == 0      # (block 4, held, is dropped)
+
+
 def test_sets_alone_are_the_sets_model(hrir):
     """three sets; switches with and without fade, one ahead of every call, with a gain fade on the same block and through
     jf_bus_set_hrtf: SetsModel, exactly"""
@@ -341,19 +489,23 @@ def test_dry_buses_against_the_float32_oracle(hrir):
         assert err <= bound and float(np.abs(want).max()) > 0.02
 
 
-# ------------------------------------------------------------------------------------- sessions 1 to 6 stay as they were --
-DIGESTS = {      # conference_sessions.digest of the op lists as they were before sessions 7 and up existed
+# ------------------------------------------------------------------------------------ sessions 1 to 10 stay as they were --
+DIGESTS = {      # conference_sessions.digest of the op lists as they were before sessions 11 and up existed
     1: "6dc0074323b5c50586aecb1fc714d66e28acf35464b2c1505c580b08caf39d53",
     2: "0bbba3ea2aa9e5bcbce3a3f93bd1fa90ffc54d2be8127c5e06d7b6fc83d16057",
     3: "52711f033f907bb8bcd36a983d266fb1849ae782dd3da7d1495f538d924618ae",
     4: "25915d527af6295c4a1695ffb7c6c85d2b2ec9ae42c354accaf6e263377a2950",
     5: "ed634bef8a102e847daa7caac1c428dea4bda72a62c889565b5e39f8c1ba3cdc",
     6: "a21b383f584d068e6bb983a5e003d2873d6b65f75d5ec63db7e4d6d4cc3f2767",
+    7: "62d89909b19e25dcebb1c9274543f76d9ae911befe4184d4c42a655a7885d42e",
+    8: "7bbba0d623f7d99167ccf3bf2ec03c07471ceac17842bb19445d10b5d2ae9fd0",
+    9: "9aabd4fad7da2ee8ecbb733797a41d173cf71f1870ef0bbc2e676565440070a0",
+    10: "87a6d402fca5225df7628db8b1bf9308e94ad81d90f994e39b05adb053631f29",
 }
 
 
 @pytest.mark.parametrize("n", sorted(DIGESTS))
-def test_the_first_six_sessions_are_byte_identical(hrir, castanets, jf_lib, n):
+def test_the_first_ten_sessions_are_byte_identical(hrir, castanets, jf_lib, n):
     assert cs.digest(cs.session_on_cpu(n, hrir, castanets, jf_lib)[0]) == DIGESTS[n]
 
 
@@ -363,7 +515,10 @@ def test_every_clause_counts_in_session(hrir, castanets, jf_lib, n):
     """Each fault's copy of the model replays the session's op list; the largest |faulty - true| / bound over the session's
     blocks must reach MARGIN for every fault whose feature the session uses.  Also what the GPU session asserts about its own
     inputs: enough blocks, audible, a limiter that attacks and releases; in sessions 7 and 8 gates that cycle, blocks skipped,
-    losers ramping out and winners ramping in, set switches with and without fade, no tie between two inputs."""
+    losers ramping out and winners ramping in, set switches with and without fade, no tie between two inputs; in sessions 11 to
+    13 window noise (no rendered gain times the loudest block in its source's window above 1), every line of the leveller's
+    rule, every kind of range, blocks where the order of range and limit matters, look-ahead turned on and off mid-stream,
+    blocks decided by the incoming and by the held block, long releases, and world-formed records that are the library's."""
     ops, outs, model, gen = cs.session_on_cpu(n, hrir, castanets, jf_lib)
     blocks = sum(o.shape[1] for o, _ in outs)
     peak = max(float(np.abs(o).max()) for o, _ in outs)
@@ -389,6 +544,23 @@ def test_every_clause_counts_in_session(hrir, castanets, jf_lib, n):
         assert all(model.pull_counts.get(b, 0) >= 10 for b in range(len(c["outputs"]))), model.pull_counts
         assert all(o >= 2 and cl >= 1 for o, cl in cycles.values()) and len(cycles) >= len(c["streams"]), cycles
         assert model.ties == 0, (model.ties, "draw the session again: raise its 'redraw' in conference_sessions.SESSIONS")
+    if n in cs.LATE:      # ... and of the sessions with look-ahead, levellers and ranges
+        rc, lc, kc = model.range_counts, model.level_counts, model.look_counts
+        print(f"  ranges {dict(rc)}\n  levellers {dict(lc)} on sources {sorted(model.levelled)}\n  look-ahead {dict(kc)}")
+        print(f"  window noise: worst |g_lv| x loudest block in the window {model.worst_product:.3f}; "
+              f"world-formed records {gen.xyz_draws} drawn, {gen.xyz_redraws} redrawn")
+        # window noise: the block bound stays sum_tol(2e-7, n) per unit of level, so no rendered block's gain times the loudest
+        # block its source's window holds may exceed 1
+        assert model.worst_product <= 1.0, model.worst_product
+        assert len(model.levelled) >= 3 and all(lc[k] >= 5 for k in ("hold", "fall_reached", "fall_limited", "rise_reached",
+                                                                      "rise_limited", "clamp_min", "clamp_max")), dict(lc)
+        assert all(rc[k] >= 10 for k in ("inside", "ramp", "beyond")) and rc["crossings_in"] >= 3 and rc["crossings_out"] >= 3, dict(rc)
+        assert rc["skipped"] >= 20 and rc["limit_differs"] >= 5, dict(rc)
+        assert kc["turned on mid-stream"] >= 2 and kc["turned off"] >= 1, dict(kc)
+        assert kc["decided by the incoming block"] >= 3 and kc["decided by the held block"] >= 3, dict(kc)
+        assert kc["releases over 3 blocks or more"] >= 2 and kc["near the ceiling"] == 0, dict(kc)
+        assert gen.xyz_draws > 100 and gen.xyz_redraws < 0.01 * gen.xyz_draws, (gen.xyz_draws, gen.xyz_redraws)
+        assert model.ties == 0, (model.ties, "draw the session again: raise its 'redraw' in conference_sessions.SESSIONS")
     short = []
     for fault in FAULTS:
         if not cs.uses(n, fault):
@@ -401,12 +573,12 @@ def test_every_clause_counts_in_session(hrir, castanets, jf_lib, n):
                 if (a is None) != (t is None) or (t is not None and len(a) != len(t[0])):
                     worst = float("inf")    # (frames that are not there at all)
                 elif t is not None and len(a):
-                    same = max(same, float((np.abs(a - t[0]).max(axis=1) / t[1]).max()))
+                    same = max(same, float((np.abs(a - t[0]).max(axis=1) / np.where(t[1] > 0, t[1], np.inf)).max()))
             worst = max(worst, same)
             print(f"  {fault}: on the pulls of equal length {same:.0f} output bounds")
         for (a, _), (t, bound) in zip(bad, outs):
-            if bound is not None and fault not in cs.OUTPUT_FAULTS:
-                worst = max(worst, float((np.abs(a - t).max(axis=2) / bound).max()))
+            if bound is not None and fault not in cs.OUTPUT_FAULTS:     # (a block whose bound is 0 -- exact zeros -- is left out)
+                worst = max(worst, float((np.abs(a - t).max(axis=2) / np.where(bound > 0, bound, np.inf)).max()))
         print(f"  {fault}: {worst:.0f} bounds")
         if worst < MARGIN:
             short.append((fault, worst))

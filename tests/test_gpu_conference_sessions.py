@@ -28,6 +28,14 @@ bit output_model.resample32, on the library's table, of the blocks the engine it
 (b) within THE OUTPUT BOUND of the model's resample64: A times the largest block bound among the blocks under the frame's taps
 plus (T + 2) EPS A |want|_inf (tests/test_output.py's rule), A = max_p sum_k |h[p][k]| of output_model.table64
 (conference_sessions.pull_bound).  In the callback form a block's levels and heard are compared one call late, like the block.
+Sessions 11 to 13 add limiter look-ahead, talker levelling and hearing ranges.  On a look-ahead bus the block handed out is the
+block that came in one block before: conference_sessions.bounds derives its bound (limiter off: the held block's own; on:
+twice the larger of the held and the incoming block's); peak_in is held to the model's INCOMING block, gain bit for bit to
+lookahead_model.look_block's float32 e fed the engine's own peak_in sequence (p_h: the peak_in before, 0 after a turn-on),
+peak_out and sumsq_out are of the block handed out.  jf_source_level_gains and jf_source_range_gains are the model's a and h
+EXACTLY on every rendered call where the model says they are kept (one call late in the callback form) and refused with
+JF_ERR_STATE where it says they are not; after every call, paused ones included, jf_bus_latency and jf_bus_lookahead of every
+bus are the model's.
 With JF_BOUNDS_LOG=<file> every call's worst error / bound is appended to that file (profiles/conference/bounds.txt)."""
 import collections
 import os
@@ -37,6 +45,7 @@ import numpy as np
 import pytest
 
 import conference_sessions as cs
+import lookahead_model
 import master_model
 import output_model
 
@@ -89,6 +98,7 @@ class _Limiters:
 
     def __init__(self):
         self.g, self.on = {}, {}
+        self.p_last = {}        # per bus: the engine's peak_in of the last rendered block (a look-ahead bus's p_h), while metered
 
     def op(self, op):
         if op[0] == "set_limiter":
@@ -101,14 +111,26 @@ class _Limiters:
                 self.on.pop(b), self.g.pop(b, None)
 
     def unseen(self):
-        self.g = {}
+        self.g, self.p_last = {}, {}
 
-    def block(self, b, p, c, r):
-        """the gain the engine must report for a block of peak p, or None while the state is not known"""
+    def block(self, b, p, c, r, look=False, fresh=False):
+        """the gain the engine must report for a block of peak p, or None while the state is not known.  look: the bus is handed
+        out a block late -- lookahead_model.look_block's e from p and the peak_in before (fresh: the held block is the zeros of
+        a turn-on, p_h = 0)"""
+        p_h = F(0) if fresh else self.p_last.get(b)
+        self.p_last[b] = F(p)
         if not c > 0:
             return F(1)
         if b not in self.g:
             return None
+        if look:
+            if p_h is None:
+                self.g.pop(b)
+                return None
+            info = lookahead_model.look_block(np.array([p, 0], np.float32), 1, 1.0, 1.0, False, c, r, np.array([p_h, 0], np.float32),
+                                              p_h, self.g[b])[2]
+            self.g[b] = info["g"]
+            return self.g[b]
         # master_model's own rule on a block whose peak is p: at m = 1 the gain depends on the block through p alone
         _, info = master_model.master_block(np.array([p, 0], np.float32), 1, 1.0, 1.0, False, c, r, self.g[b])
         self.g[b] = info["g"]
@@ -125,13 +147,17 @@ def _check(n, label, got, want, last, meters, lim, model_c, model_r, worst, tall
         return
     bound = cs.bounds(last, nb, K)
     err = np.abs(got - want).max(axis=2)
-    k = np.unravel_index(np.argmax(err / bound), err.shape)
-    worst[0] = max(worst[0], float(err[k] / bound[k]))
-    _log_ratio(f"conference session {n} {label} bus {k[0]} block {k[1]}", float(err[k]), float(bound[k]))
-    assert (err <= bound).all(), (label, k, float(err[k]), float(bound[k]))
+    assert (err <= bound).all(), (label, np.argwhere(err > bound).tolist(), err[err > bound].tolist(), bound[err > bound].tolist())
+    ratio = err / np.where(bound > 0, bound, 1.0)      # (a bound of 0 -- the zeros a look-ahead bus starts on -- was met exactly)
+    k = np.unravel_index(np.argmax(ratio), err.shape)
+    worst[0] = max(worst[0], float(ratio[k]))
+    if bound[k] > 0:
+        _log_ratio(f"conference session {n} {label} bus {k[0]} block {k[1]}", float(err[k]), float(bound[k]))
     for b in range(nb):
         for j in range(K):
-            if last["n_on"][b, j] == 0 and last["quiet"][b]:
+            i = last["infos"][b][j]
+            # (on a look-ahead bus: of the block that goes out, the held one -- or the zeros of a turn-on)
+            if i["silent"] if i.get("look") else (last["n_on"][b, j] == 0 and last["quiet"][b]):
                 assert not got[b, j].any(), ("a bus without sources that nobody sent to is exact zeros", b, j)
     if meters is None:
         lim.unseen()
@@ -142,10 +168,12 @@ def _check(n, label, got, want, last, meters, lim, model_c, model_r, worst, tall
         for j in range(K):
             i = last["infos"][b][j]
             peak_in, peak_out, sumsq, gain = meters[b, j]
-            assert abs(float(peak_in) - i["p"]) <= bound[b, j] / (2.0 if i["limited"] else 1.0), ("peak_in", b, j, peak_in, i["p"])
-            g = lim.block(b, peak_in, c, r)
-            assert g is None or gain == g, ("gain", b, j, gain, g)
+            assert abs(float(peak_in) - i["p"]) <= cs.peak_in_bound(last, b, j), ("peak_in", b, j, peak_in, i["p"])
+            look = bool(i.get("look"))
+            g = lim.block(b, peak_in, c, r, look, look and i["held_parts"] is None)
+            assert g is None or gain == g, ("gain", b, j, gain, g, look)
             tally["limiter gains checked bit for bit"] += g is not None and c > 0
+            tally["... on a look-ahead bus"] += g is not None and c > 0 and look
             if c > 0:
                 assert peak_out <= F(c), ("peak_out above the ceiling", b, j, peak_out, c)
             tally["metered bus blocks"] += 1
@@ -153,6 +181,7 @@ def _check(n, label, got, want, last, meters, lim, model_c, model_r, worst, tall
             assert abs(float(sumsq) - ref) <= master_model.sumsq_bound(ref, B), ("sumsq_out", b, j, sumsq, ref)
 
 
+LATE_KERNELS = ("range_gain_kernel", "level_scan_kernel", "look_peak_kernel", "look_gain_kernel", "look_apply_kernel")
 NEW_KERNELS = ("input_level_kernel", "gate_scan_kernel", "voice_env_kernel", "voice_select_kernel", "desc_set_kernel")
 STREAM_KERNELS = ("stream_resample_kernel", "output_resample_kernel")
 
@@ -188,12 +217,15 @@ class _Outputs:
         assert np.array_equal(frames, own), ("pulled frames are not the rule on the blocks handed out", b, rate, u0, len(frames))
         if len(frames):
             err = np.abs(frames - want).max(axis=1)
-            k = int(np.argmax(err / bound))
-            worst[0] = max(worst[0], float(err[k] / bound[k]))
-            _log_ratio(f"conference output bus {b} at {rate} Hz frame {u0 + k}", float(err[k]), float(bound[k]))
+            ratio = err / np.where(bound > 0, bound, 1.0)      # (a bound of 0: frames of the zeros a look-ahead bus starts on)
+            k = int(np.argmax(ratio))
+            worst[0] = max(worst[0], float(ratio[k]))
+            if bound[k] > 0:
+                _log_ratio(f"conference output bus {b} at {rate} Hz frame {u0 + k}", float(err[k]), float(bound[k]))
             assert (err <= bound).all(), ("pulled frames against the model", b, rate, u0 + k, float(err[k]), float(bound[k]))
         self.pulled[b] += len(frames)
         tally["pulls"] += 1
+        tally["pulls on a look-ahead bus"] += bool(len(frames)) and model.bus_latency(b) > 0
         tally["frames pulled"] += len(frames)
 
 
@@ -209,6 +241,29 @@ def _check_streams(eng, model, label, callback):
             L, M, _ = output_model.ratio(o["rate"])
             want = output_model.produced(len(o["blocks"]) * model.B, L, M)
             assert eng.output_stats(b)["produced"] == want, (label, b, eng.output_stats(b), want)
+
+
+def _check_late_reports(jf, eng, last, K, label, tally, refusals):
+    """jf_source_level_gains and jf_source_range_gains of a rendered call: the model's a and h EXACTLY where the model says they
+    are kept; refusals: where it says they are not, the getter is refused with JF_ERR_STATE"""
+    for name, getter in (("level_gains", eng.level_gains), ("range_gains", eng.range_gains)):
+        want = last.get(name)
+        if want is not None:
+            got = getter(K)
+            assert np.array_equal(got, want.astype(F)), (label, name, got.T.tolist(), want.T.tolist())
+            tally[f"calls with {name} checked"] += 1
+        elif refusals:
+            with pytest.raises(jf.JfError) as ei:
+                getter(K)
+            assert ei.value.code == cs.JF_ERR_STATE, (label, name, ei.value.code)
+            tally[f"calls with {name} refused"] += 1
+
+
+def _check_look(eng, model, label):
+    """after every call, paused ones included: jf_bus_latency and jf_bus_lookahead of every bus are the model's"""
+    for b in range(model.n_buses):
+        assert eng.bus_latency(b) == model.bus_latency(b), (label, b, eng.bus_latency(b), model.bus_latency(b))
+        assert eng.lookahead(b) == model.lookahead(b), (label, b, eng.lookahead(b), model.lookahead(b))
 
 
 def _check_reports(eng, last, K, label, tally):
@@ -273,7 +328,13 @@ def test_conference_session_against_the_composed_model(jf, hrir, castanets, n):
                         _check_reports(eng, {"levels": l.get("levels") if model.input_meters else None,
                                              "heard": l.get("heard") if model.input_meters and limited else None}, 1,
                                        f"step {len(log)} callback", families)
+                        if n in cs.LATE:
+                            _check_late_reports(jf, eng, {"level_gains": l.get("level_gains") if model.input_meters and model.levelling() else None,
+                                                          "range_gains": l.get("range_gains") if model.input_meters and model.ranged() else None},
+                                                1, f"step {len(log)} callback", families, False)
                 _check_streams(eng, model, f"step {len(log)} {op[0]}", True)
+                if n in cs.LATE:
+                    _check_look(eng, model, f"step {len(log)} {op[0]}")
                 if late is not None:
                     blocks, peak = blocks + 1, max(peak, float(np.abs(w).max()))
                 for o in deferred:
@@ -285,18 +346,23 @@ def test_conference_session_against_the_composed_model(jf, hrir, castanets, n):
                 names = eng.last_kernels()
                 ks = ";".join(names)
                 for fam in ("rt_block_kernel", "fused_block_kernel", "fused_pair_kernel", "fused2048_kernel", ",shared", "desc_gain_kernel",
-                            "room_mac_kernel", "master_apply_kernel", "pose_kernel", "pose_object_kernel", "live_ingest_kernel") + NEW_KERNELS + STREAM_KERNELS:
+                            "room_mac_kernel", "master_apply_kernel", "pose_kernel", "pose_object_kernel", "live_ingest_kernel") + NEW_KERNELS + STREAM_KERNELS + LATE_KERNELS:
                     families[fam] += fam in ks
                 ahead = op[0] == "batch_run" and "prep_kernel" not in names      # the run found its descriptors prepared
                 families["descriptors prepared ahead"] += ahead
                 families["... with a gain active"] += ahead and "desc_gain_kernel" in ks
                 families["... with a gate or a set active"] += ahead and ("gate_scan_kernel" in ks or "desc_set_kernel" in ks)
+                families["... with a range or a leveller active"] += ahead and ("range_gain_kernel" in ks or "level_scan_kernel" in ks)
             m = eng.meters(K) if model.meters_on and not last.get("paused") else None
             _check(n, f"step {len(log)} {op[0]} K={K}", got, want, last, m, lim, model.lim_c, model.lim_r, worst, families)
             if not last.get("paused"):
                 _check_reports(eng, last, K, f"step {len(log)} {op[0]} K={K}", families)
+                if n in cs.LATE:
+                    _check_late_reports(jf, eng, last, K, f"step {len(log)} {op[0]} K={K}", families, True)
                 outs.handed(got)
             _check_streams(eng, model, f"step {len(log)} {op[0]} K={K}", False)
+            if n in cs.LATE:
+                _check_look(eng, model, f"step {len(log)} {op[0]} K={K}")
             blocks, peak = blocks + K, max(peak, float(np.abs(want).max()))
     except BaseException:
         print("\n".join(log[-40:]))     # (pytest shows it with the failure)
@@ -324,6 +390,16 @@ def test_conference_session_against_the_composed_model(jf, hrir, castanets, n):
         print(f"session {n} outputs: {families['pulls']} pulls, {families['frames pulled']} frames, worst error / output bound "
               f"{worst_out[0]:.3f}; streams (underruns, zeros) {model.stream_totals[:2]}")
         assert families["pulls"] >= 20 and families["frames pulled"] >= 5000, dict(families)
+    if n in cs.LATE:
+        for fam in LATE_KERNELS:
+            assert families[fam] >= 1, (fam, dict(families))
+        assert families["calls with level_gains checked"] >= 50 and families["calls with range_gains checked"] >= 50, dict(families)
+        assert families["... on a look-ahead bus"] >= 10, dict(families)
+        print(f"session {n}: look-ahead {dict(model.look_counts)}, ranges {dict(model.range_counts)}, levellers {dict(model.level_counts)}")
+    if n == 12:     # ... the range and level stages rewrite descriptors that were prepared ahead
+        assert families["... with a range or a leveller active"] >= 1, dict(families)
+    if n == 13:     # ... and the outputs of look-ahead buses were pulled, within the output bound (_Outputs.pull)
+        assert families["pulls on a look-ahead bus"] >= 20, dict(families)
     if n == 8:      # ... and the gate stage and desc_set_kernel rewrite descriptors that were prepared ahead
         assert families["... with a gate or a set active"] >= 1, dict(families)
     assert families["metered bus blocks"] >= 50, dict(families)
