@@ -279,7 +279,19 @@ JF_DEV void mirror8(float2 *buf, const float2 (&in)[8], float2 (&out)[8], int la
 //      the caller's scale factor: a power of two, so nothing rounds differently); on lane 0, X[0] is
 //      packed as 2 (X[0].re, X[512].re) (both bins are real).
 // buf: >= 576 float2 of this wave's LDS; tw: the twiddle pack (jf_device.h) in LDS.
+// The twiddles of passes B and C depend on the lane alone and are REQUESTED A PASS AHEAD, the seven of a pass together: they
+// land under the butterflies and the exchange in front of their use (pass B's, in the pair kernel, under the wait for the
+// window itself).  The sched_barriers pin the requests where they are written: left to itself the compiler reads each
+// twiddle right in front of its product and waits for it alone, nine LDS round trips one after the other (with
+// distance_factors' grouped reads 1.0-2.4 % of the batch kernel's time in four visits, bit-identical: profiles/front_lds/README.md).
+// tried: the split pass's eight requested ahead of pass C's butterflies as well -- the compiler already keeps several of
+// them in flight, and with it rt_block_kernel<3,16,false,true> and <4,16,false,true> spill 20 and 32 B instead of 0 and 16
 JF_DEV void rfft1024_wave(float2 (&z)[8], float2 (&X)[8], float2 *buf, const float2 *tw, int lane) {
+    const int k = lane & 7;
+    float2 wb[8], wc[8];  // [0] unused: w^0
+#pragma unroll
+    for (int r = 1; r < 8; r++) wb[r] = tw[kTwWB + 8 * r + k];
+    __builtin_amdgcn_sched_barrier(0);
     // pass A (sub-length 1): no twiddles; store 8 contiguous, row padded 8 -> 9
     fft8<-1>(z);
 #pragma unroll
@@ -291,9 +303,11 @@ JF_DEV void rfft1024_wave(float2 (&z)[8], float2 (&X)[8], float2 *buf, const flo
         const int base = lane + (lane >> 3);
 #pragma unroll
         for (int r = 0; r < 8; r++) u[r] = buf[base + 72 * r];
-        const int k = lane & 7;
 #pragma unroll
-        for (int r = 1; r < 8; r++) u[r] = cmulc_pk(u[r], tw[kTwWB + 8 * r + k]);
+        for (int r = 1; r < 8; r++) wc[r] = tw[kTwWC + 64 * r + lane];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int r = 1; r < 8; r++) u[r] = cmulc_pk(u[r], wb[r]);
         fft8<-1>(u);
         JF_WAVE_LDS_SYNC();
         const int wbase = 72 * (lane >> 3) + k;
@@ -305,7 +319,7 @@ JF_DEV void rfft1024_wave(float2 (&z)[8], float2 (&X)[8], float2 *buf, const flo
 #pragma unroll
     for (int r = 0; r < 8; r++) u[r] = buf[lane + 72 * r];
 #pragma unroll
-    for (int r = 1; r < 8; r++) u[r] = cmulc_pk(u[r], tw[kTwWC + 64 * r + lane]);
+    for (int r = 1; r < 8; r++) u[r] = cmulc_pk(u[r], wc[r]);
     fft8<-1>(u);
     JF_WAVE_LDS_SYNC();
     // split: 2 X[k] = E + (-i) W^k O, E = Z[k] + conj Z[512-k], O = Z[k] - conj Z[512-k]
@@ -336,6 +350,9 @@ template <int NOUT, bool SPLIT>
 JF_DEV void ifft1024_lastq_wave(float2 (&v)[16], float2 (&out)[NOUT], float2 *buf, const float2 *tw, int lane) {
     const int a = lane & 3, i = lane >> 2;
     // lane (i, a) holds S_a[i + 16 r] = Z[4 (i + 16 r) + a]: 16-point inverse over r
+    // tried: the fifteen kTwW2 twiddles requested ahead of the first fft16 (the pair kernel reads them in eight round trips, each
+    // alone in flight) -- once per unit, no time won (0.2429 against 0.2422 ms), and the compiler then contracts the products
+    // below differently: the output differs in the last bit (tests/test_gpu_front_half_bits.py)
     fft16<+1>(v);
 #pragma unroll
     for (int m = 1; m < 16; m++) v[m] = cmul(v[m], tw[kTwW2 + 16 * m + i]);
@@ -397,21 +414,33 @@ JF_DEV void ifft1024_lastq_wave(float2 (&v)[16], float2 (&out)[NOUT], float2 *bu
 // cos x - 1 = -x^2/2 (next term 4e-12) and sin x = x - x^3/6 (next term 2e-15) as small addends to it -- one rounding
 // on top of the table's, the argument needs no second float (x is known to 1.8e-10), 20 instructions and one LDS read
 // instead of 33.
-JF_DEV float2 distance_from_phase_tab(unsigned p, float inv_frac, const float2 *tw) {
+// The evaluation in the three parts distance_factors interleaves over a group of bins: the table entry's index (the read
+// is the caller's), the terms of the remainder, and the tail that needs the entry.
+struct DistanceRem {
+    float sd, eh, sf;  // sin x, 1 - cos x of the remainder x; inv_frac with the half turn's sign
+};
+JF_DEV unsigned distance_tab_index(unsigned p) {
     const unsigned p2 = p + 0x200000u;  // + 1/2048 turn: round to the nearest table entry
+    return kTwU + ((p2 >> 22) & 511u);  // (cos, sin) of entry j mod 512; entry j + 512 is its negative
+}
+JF_DEV DistanceRem distance_remainder(unsigned p, float inv_frac) {
+    const unsigned p2 = p + 0x200000u;
     // the remainder is the low 22 bits of p read as a signed number: ((p + 2^21) mod 2^22) - 2^21, one v_bfe_i32
     const int rem = (int)(p << 10) >> 10;
-    const float2 t = tw[kTwU + ((p2 >> 22) & 511u)];  // (cos, sin) of entry j mod 512; entry j + 512 is its negative
     const float x = (float)rem * 0x1.921fb6p-30f;      // 2 pi / 2^32
     const float x2 = x * x;
-    const float sd = x * fmaf(x2, -0x1.555556p-3f, 1.0f);  // sin x
-    const float eh = 0.5f * x2;                            // 1 - cos x
-    const float sf = __uint_as_float(__float_as_uint(inv_frac) | (p2 & 0x80000000u));  // inv_frac > 0; second half turn: -
+    DistanceRem d;
+    d.sd = x * fmaf(x2, -0x1.555556p-3f, 1.0f);  // sin x
+    d.eh = 0.5f * x2;                            // 1 - cos x
+    d.sf = __uint_as_float(__float_as_uint(inv_frac) | (p2 & 0x80000000u));  // inv_frac > 0; second half turn: -
+    return d;
+}
+JF_DEV float2 distance_tail(float2 t, const DistanceRem &d) {
     // tried: the tail below as four packed instructions on the pair (cos a, sin a) (JF_PACKED_DTAIL) -- bit-identical and
     // 0.4 % slower (0.2488 against 0.2478 ms): the four are one dependent chain, these eight are two -- in-source note only
-    const float re = t.x - fmaf(t.y, sd, t.x * eh);
-    const float im = t.y - fmaf(-t.x, sd, t.y * eh);
-    return make_float2(re * sf, -im * sf);
+    const float re = t.x - fmaf(t.y, d.sd, t.x * d.eh);
+    const float im = t.y - fmaf(-t.x, d.sd, t.y * d.eh);
+    return make_float2(re * d.sf, -im * d.sf);
 }
 
 // D of this lane's bins lane + 64 q, q = 0..7, and Re D[512].  Phase words by 64-bit accumulation (two adds per bin
@@ -428,13 +457,33 @@ JF_DEV void distance_factors(unsigned c_hi, unsigned c_lo, float inv_frac, int l
     const unsigned long long c64 = ((unsigned long long)c_hi << 32) | c_lo;
     unsigned long long ph = (unsigned long long)(unsigned)lane * c64;
     const unsigned long long step = c64 << 6;
+    unsigned p[8];
 #pragma unroll
     for (int q = 0; q < 8; q++) {
-        unsigned p = (unsigned)(ph >> 32);
-        if (q == 0) p = lane == 0 ? (unsigned)((c64 << 9) >> 32) : p;
-        dq[q] = distance_from_phase_tab(p, inv_frac, tw);
-        if (q & 1) __builtin_amdgcn_sched_barrier(0);  // two table reads in flight, not eight (registers)
+        p[q] = (unsigned)(ph >> 32);
+        if (q == 0) p[q] = lane == 0 ? (unsigned)((c64 << 9) >> 32) : p[q];
         ph += step;
+    }
+    // The table reads of four bins are requested together (four in flight, not eight: registers); the four remainders, which
+    // need no table entry, are worked out while they are in flight, then the four tails.  One read at a time, as the compiler
+    // orders it when left alone, is eight LDS round trips one after the other.
+    constexpr int GR = 4;
+#pragma unroll
+    for (int g = 0; g < 8; g += GR) {
+        unsigned idx[GR];
+        float2 t[GR];
+        DistanceRem d[GR];
+#pragma unroll
+        for (int i = 0; i < GR; i++) idx[i] = distance_tab_index(p[g + i]);
+#pragma unroll
+        for (int i = 0; i < GR; i++) t[i] = tw[idx[i]];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < GR; i++) d[i] = distance_remainder(p[g + i], inv_frac);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < GR; i++) dq[g + i] = distance_tail(t[i], d[i]);
+        __builtin_amdgcn_sched_barrier(0);
     }
     d512x = dq[0].x;  // on lane 0 (the only lane that uses it)
 }
@@ -948,6 +997,10 @@ JF_DEV void mac_ears(int q, bool special, float2 x, c2 heL, c2 heR, c2 &sL, c2 &
         sL = pfma_lo_rot(xb, heL, pfma_each(xa, heL, sL));
         sR = pfma_lo_rot(xb, heR, pfma_each(xa, heR, sR));
     } else {
+        // tried: both ears' first FMAs, then both second ones, so that no dependent pair is issued back to back (the compiler
+        // puts an s_nop 0 between such a pair: 159 fewer of them in the pair kernel) -- bit-identical and not faster: 0.2438
+        // against 0.2422 ms on top of the front half's reordered reads, 0.2452 against 0.2483 ms alone, inside the parent's
+        // spread (profiles/front_lds/README.md)
         const c2 xc = c2_of(x);
         sL = pcmac(xc, heL, sL);
         sR = pcmac(xc, heR, sR);
