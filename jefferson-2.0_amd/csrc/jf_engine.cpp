@@ -89,7 +89,7 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
         ep = next_events(e, e->ev_prep);
         em = next_events(e, e->ev_mix);
         if (!ep || !em) return fail(e, JF_ERR_DEVICE, "hipEventCreate failed");
-        for (StageTimer *t : {&e->tm_spec, &e->tm_set, &e->tm_gain, &e->tm_master, &e->tm_gate, &e->tm_voice, &e->tm_level, &e->tm_range}) t->arm(e->ev_used);  // (the stage that runs says otherwise)
+        for (StageTimer *t : {&e->tm_spec, &e->tm_set, &e->tm_gain, &e->tm_master, &e->tm_gate, &e->vc.tm, &e->lv.tm, &e->rg.tm}) t->arm(e->ev_used);  // (the stage that runs says otherwise)
     }
     const long long n_items = (long long)K * e->S;
     int G = 1;
@@ -309,6 +309,40 @@ int reset_sources(jf_engine *e, int src) {
     return gate_close_source(e, src);  // a source that starts over has its gate closed; the thresholds stay
 }
 
+// ---- the reports of a call (jf_engine_internal.h: reports_on) --------------------------------------------------------------
+// The bus meters first, then the input meters with what the gate stage's followers left: the order of the copies in the stream.
+int reports_copy(jf_engine *e, int which, int K) {
+    int rc = which & kReportMeters ? master_meters_copy(e, K) : JF_OK;
+    if (rc == JF_OK && (which & kReportLevels)) rc = gate_levels_copy(e, K);
+    return rc;
+}
+
+void reports_land(jf_engine *e, int which, int K, int b0, int n_blocks) {
+    if (which & kReportMeters) master_meters_land(e, K, b0, n_blocks);
+    if (which & kReportLevels) gate_levels_land(e, K, b0, n_blocks);
+}
+
+void reports_left(jf_engine *e, int which, int n_blocks) {
+    if (!which) return;
+    if (which & kReportMeters) e->meters_dev_blocks = n_blocks;
+    if (which & kReportLevels) e->levels_dev_blocks = n_blocks;
+    std::lock_guard<std::mutex> lk(e->pos_mu);
+    if (which & kReportMeters) e->meters_blocks = 0;
+    if (which & kReportLevels) e->input_levels.blocks = 0;
+}
+
+int reports_fetch(jf_engine *e, int kind) {
+    int &left = kind == kReportMeters ? e->meters_dev_blocks : e->levels_dev_blocks;
+    const int K = left;
+    if (K <= 0) return JF_OK;
+    const int rc = reports_copy(e, kind, K);
+    if (rc) return rc;
+    JF_HIP(e, hipStreamSynchronize(e->stream));
+    left = 0;
+    reports_land(e, kind, K, 0, K);
+    return JF_OK;
+}
+
 // ---- live input (jf_engine::live) -----------------------------------------------------------------------
 // After any change of which sources are live or of a signal record: the list of live sources, the staging (grown to hold a
 // whole batch window of every live source) and the real-time kernel's records.  The engine's stream is idle (the callers
@@ -386,7 +420,7 @@ void destroy_engine(jf_engine *e) {
     DeviceGuard bind(e);  // (outlives the delete: the buffers are freed on the engine's device)
     if (e->rv_side) (void)hipStreamSynchronize(e->rv_side);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
-    for (auto *pool : {&e->ev_prep, &e->ev_fused, &e->ev_mix, &e->ev_reverb, &e->ev_pose, &e->tm_spec.ev, &e->tm_gain.ev, &e->tm_master.ev, &e->tm_set.ev, &e->tm_gate.ev, &e->tm_voice.ev, &e->tm_level.ev, &e->tm_range.ev})
+    for (auto *pool : {&e->ev_prep, &e->ev_fused, &e->ev_mix, &e->ev_reverb, &e->ev_pose, &e->tm_spec.ev, &e->tm_gain.ev, &e->tm_master.ev, &e->tm_set.ev, &e->tm_gate.ev, &e->vc.tm.ev, &e->lv.tm.ev, &e->rg.tm.ev})
         for (auto &p : *pool) {
             (void)hipEventDestroy(p.a);
             (void)hipEventDestroy(p.b);
@@ -1385,8 +1419,7 @@ static int submit_block(jf_engine *e, const float *in, bool interleaved) {
     if (e->paused.load(std::memory_order_relaxed)) {  // Audio.cu:101: nothing is consumed (live input is dropped), output is silence
         JF_HIP(e, hipMemsetAsync(e->d_mix, 0, sizeof(float) * 2 * e->B * e->n_buses, e->stream));
         e->own_mix_blocks = 0;  // (d_mix no longer holds the last jf_batch_run's blocks)
-        e->meters_stage_blocks = 0;  // (a paused call leaves the masters and the meters alone)
-        e->levels_stage_blocks = 0;  // (... and the gates and the input meters)
+        e->staged_reports = 0;  // (a paused call leaves the masters, the gates and their meters alone)
     } else {
         snapshot_positions(e, e->h_pos_pinned);
         CallLatches call(e);  // the gains, HRTF sets and bus masters the setters hold (nothing to settle where none is active: the one-launch path below)
@@ -1394,8 +1427,7 @@ static int submit_block(jf_engine *e, const float *in, bool interleaved) {
             const int rc = call.latch();
             if (rc) return rc;
         }
-        e->meters_stage_blocks = 0;
-        e->levels_stage_blocks = 0;
+        e->staged_reports = 0;
         if (e->S <= e->rt_max_sources && !e->profiling && e->N == kN && e->n_buses == 1 && e->room.P == 0 && !e->gain_on && !e->master_on && !e->sets_on && !e->gate_on && e->n_stream == 0 && e->n_out == 0) {  // (PAD_LEN 2048, buses, a room, an active gain, master or gate, a source on another HRTF set, a stream source, a bus output: the batch path with K = 1)
             // few sources: ONE launch does descriptors, spatialisation and mix, reading the positions
             // from and writing the stereo block to pinned host memory -- no copies, one sync
@@ -1470,16 +1502,9 @@ static int submit_block(jf_engine *e, const float *in, bool interleaved) {
         int rc = run_blocks(e, e->d_pos_rt, 1, e->d_mix);
         if (rc) return rc;
         call.settle();
-        if (e->master_on && e->master_meters) {  // the block's meters come with the block (jf_collect_block)
-            rc = master_meters_copy(e, 1);
-            if (rc) return rc;
-            e->meters_stage_blocks = 1;
-        }
-        if (e->gate_on && e->gate_meters) {  // ... and so do its input meters
-            rc = gate_levels_copy(e, 1);
-            if (rc) return rc;
-            e->levels_stage_blocks = 1;
-        }
+        rc = reports_copy(e, reports_on(e), 1);  // the block's meters and input meters come with the block (jf_collect_block)
+        if (rc) return rc;
+        e->staged_reports = reports_on(e);
     }
     JF_HIP(e, hipMemcpyAsync(e->h_out_pinned, e->d_mix, sizeof(float) * 2 * e->B * e->n_buses, hipMemcpyDeviceToHost, e->stream));
     e->rt_wgs = 0;
@@ -1525,14 +1550,8 @@ int jf_collect_block(jf_engine *e, float *out) {
         e->in_flight = false;
         return fail(e, JF_ERR_DEVICE, kHandOffMsg);
     }
-    if (e->meters_stage_blocks > 0) {
-        master_meters_land(e, 1, 0, 1);
-        e->meters_stage_blocks = 0;
-    }
-    if (e->levels_stage_blocks > 0) {
-        gate_levels_land(e, 1, 0, 1);
-        e->levels_stage_blocks = 0;
-    }
+    reports_land(e, e->staged_reports, 1, 0, 1);
+    e->staged_reports = 0;
     output_land(e);  // the block is handed out: its frames at the buses' output rates become pullable
     const int n_out = 2 * e->B * e->n_buses;  // [n_buses][2B] (the real-time kernel: one bus)
     memcpy(out, e->h_out_pinned, sizeof(float) * n_out);
@@ -1886,17 +1905,9 @@ int jf_batch_run(jf_engine *e, int first_block, int n_blocks, float *d_out_mix) 
     if (rc) return rc;
     rc = batch_run(e, first_block, n_blocks, d_out_mix);
     if (rc == JF_OK) call.settle();
-    // the run's meters stay on the device until jf_batch_fetch or jf_bus_meters brings them over
-    if (rc == JF_OK && e->master_on && e->master_meters) {
-        e->meters_dev_blocks = n_blocks;
-        std::lock_guard<std::mutex> lk(e->pos_mu);
-        e->meters_blocks = 0;
-    }
-    if (rc == JF_OK && e->gate_on && e->gate_meters) {  // ... and so do its input meters (jf_source_levels)
-        e->levels_dev_blocks = n_blocks;
-        std::lock_guard<std::mutex> lk(e->pos_mu);
-        e->levels_blocks = 0;
-    }
+    // the run's meters stay on the device until jf_batch_fetch or jf_bus_meters brings them over, its input meters until a
+    // getter of theirs does (jf_source_levels)
+    if (rc == JF_OK) reports_left(e, reports_on(e), n_blocks);
     return rc;
     });
 }
@@ -2019,16 +2030,9 @@ static int process_batch(jf_engine *e, int n_blocks, const float *in, const floa
         else  // this window's [n_buses][k][2B] into the call's [n_buses][n_blocks][2B]: a row per bus
             JF_HIP(e, hipMemcpy2DAsync(out_mix + (size_t)b0 * blk, sizeof(float) * blk * n_blocks, e->d_mix, sizeof(float) * blk * k,
                                        sizeof(float) * blk * k, (size_t)e->n_buses, hipMemcpyDeviceToHost, e->stream));
-        const bool metered = e->master_on && e->master_meters;
-        if (metered) {
-            rc = master_meters_copy(e, k);
-            if (rc) return rc;
-        }
-        const bool levelled = e->gate_on && e->gate_meters;
-        if (levelled) {
-            rc = gate_levels_copy(e, k);
-            if (rc) return rc;
-        }
+        const int reports = reports_on(e);  // the window's meters and input meters
+        rc = reports_copy(e, reports, k);
+        if (rc) return rc;
         if (!positions && b0 + k == n_blocks) {
             // while the last window runs: where the sources will stand afterwards (what the pose kernel wrote for the last
             // block, bit for bit)
@@ -2037,8 +2041,7 @@ static int process_batch(jf_engine *e, int n_blocks, const float *in, const floa
         }
         JF_HIP(e, hipStreamSynchronize(e->stream));
         if (device_fault(e)) return fail(e, JF_ERR_DEVICE, kHandOffMsg);
-        if (metered) master_meters_land(e, k, b0, n_blocks);
-        if (levelled) gate_levels_land(e, k, b0, n_blocks);
+        reports_land(e, reports, k, b0, n_blocks);
         output_land(e);
     }
     call.settle(n_blocks);
@@ -2115,7 +2118,7 @@ int jf_batch_fetch(jf_engine *e, int n_blocks, float *out_mix) {
                                    sizeof(float) * 2 * e->B * n_blocks, (size_t)e->n_buses, hipMemcpyDeviceToHost, e->stream));
     JF_HIP(e, hipStreamSynchronize(e->stream));
     if (device_fault(e)) return fail(e, JF_ERR_DEVICE, kHandOffMsg);
-    return master_meters_fetch(e);  // the run's meters come with its mix (none: nothing to do)
+    return reports_fetch(e, kReportMeters);  // the run's meters come with its mix (none: nothing to do)
     });
 }
 

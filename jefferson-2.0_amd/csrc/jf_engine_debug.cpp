@@ -477,9 +477,9 @@ const char *jf_debug_last_kernels(jf_engine *e) {
         if (!e->last_rt && !e->last_prep_skipped) k += "prep_kernel;";
         if (!e->last_rt && e->last_set) k += "desc_set_kernel;";
         if (!e->last_rt && e->last_gate) k += "input_level_kernel;gate_scan_kernel;";
-        if (!e->last_rt && e->last_gate && e->last_range) k += "range_gain_kernel;";
-        if (!e->last_rt && e->last_gate && e->last_voice) k += "voice_env_kernel;voice_select_kernel;";
-        if (!e->last_rt && e->last_gate && e->last_level) k += "level_scan_kernel;";
+        if (!e->last_rt && e->last_gate && e->rg.last) k += "range_gain_kernel;";
+        if (!e->last_rt && e->last_gate && e->vc.last) k += "voice_env_kernel;voice_select_kernel;";
+        if (!e->last_rt && e->last_gate && e->lv.last) k += "level_scan_kernel;";
         if (!e->last_rt && e->last_gain) k += "desc_gain_kernel;";
         const bool room = e->room.P > 0 && !e->last_rt && e->room.last_K > 0;  // (jf_engine_room.cpp)
         if (room) k += "room_send_kernel<" + bs + ">;room_fft_kernel<" + bs + ">;room_mac_kernel<" + bs + "," + std::to_string(room_mac_waves(e->B)) + ">;";

@@ -57,29 +57,14 @@ int gain_traj_check(jf_engine *e, int traj_blocks) {
     return traj_mismatch(e, traj_blocks);
 }
 
-// The device copies of the call's g[-1] and standing gains, where they differ from what the device holds, out of the staging
-// ring (StagedRing), enqueued by gain_latch BEFORE anything of the call.
+// The device copies of the call's g[-1] and standing gains, where they differ from what the device holds (staged_upload),
+// enqueued by gain_latch BEFORE anything of the call.
 static int gain_upload(jf_engine *e, bool traj) {
     const size_t S = (size_t)e->S;
     const bool need_new = !traj && e->dev_g_new != e->run_g1;  // (a trajectory call reads its gains from d_g_traj)
     const bool need_prev = (traj || e->gain_ramp) && e->dev_g_prev != e->run_g0;
-    if (!need_new && !need_prev) return JF_OK;
-    float *stage = nullptr;
-    const int rc = e->g_ring.take(e, 2 * S, &stage);
-    if (rc) return rc;
-    if (need_new) {
-        memcpy(stage, e->run_g1.data(), sizeof(float) * S);
-        e->dev_g_new.clear();  // (nothing, should the copy fail)
-        JF_HIP(e, hipMemcpyAsync(e->d_g_new, stage, sizeof(float) * S, hipMemcpyHostToDevice, e->stream));
-        e->dev_g_new = e->run_g1;
-    }
-    if (need_prev) {
-        memcpy(stage + S, e->run_g0.data(), sizeof(float) * S);
-        e->dev_g_prev.clear();
-        JF_HIP(e, hipMemcpyAsync(e->d_g_prev, stage + S, sizeof(float) * S, hipMemcpyHostToDevice, e->stream));
-        e->dev_g_prev = e->run_g0;
-    }
-    return e->g_ring.sent(e);
+    return staged_upload(e, e->g_ring, 2 * S, StagedPart<float>{e->d_g_new, e->dev_g_new, e->run_g1, 0, need_new},
+                         StagedPart<float>{e->d_g_prev, e->dev_g_prev, e->run_g0, S, need_prev});
 }
 
 int gain_latch(jf_engine *e, int traj_blocks) {

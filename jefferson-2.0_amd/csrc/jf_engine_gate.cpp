@@ -5,10 +5,13 @@
 // (run_gate_stage: jf_gate.hip, then desc_gain_kernel on the trajectory the stage wrote).  jf_debug_gate_scan is the rule for a
 // sequence of levels on the host -- the header the kernels compile (jf_gate_rule.h).
 //
-// Who reads what: gt_par / levels_want / levels_last / levels_blocks are touched under pos_mu only; gate_on, gate_meters,
+// Who reads what: gt_par / levels_want / input_levels.last / .blocks are touched under pos_mu only; gate_on, gate_meters,
 // run_gpar and the device buffers belong to the thread that makes the processing calls.  A gate's state is on the device only
 // (d_gt_state): it depends on the audio, and every run continues from what the run before left there.
 #include "jf_engine_internal.h"
+
+static_assert(sizeof(GateState) == 2 * sizeof(unsigned), "GateState layout");
+constexpr size_t kGateStateWords = 2;  // a closed gate is {0, 0} (state_fill)
 
 static bool same_par(const GatePar &a, const GatePar &b) { return a.open == b.open && a.close == b.close && a.hold == b.hold; }
 
@@ -17,76 +20,55 @@ bool gate_wanted(jf_engine *e) {
     if (e->levels_want) return true;
     for (const GatePar &g : e->gt_par)
         if (g.open > 0.0f) return true;
-    for (const int n : e->vc_N)
-        if (n > 0) return true;  // (a voice limit counts as a gate: jf_engine_voice.cpp)
-    for (const LevelPar &lp : e->lv_par)
-        if (lp.target > 0.0f) return true;  // (and so does a leveller: jf_engine_level.cpp)
-    for (size_t b = 0; 2 * b + 1 < e->rg_range.size(); b++)
-        if (e->rg_range[2 * b + 1] > 0.0f) return true;  // (and a hearing range: jf_engine_range.cpp)
-    return false;
+    return voices_limited(e) || levelled(e) || ranged(e);  // (a follower counts as a gate)
 }
 
-// The device copies of the call's parameters and of the root map, where they differ from what the device holds, out of the
-// staging ring (StagedRing), enqueued by gate_latch BEFORE anything of the call.  The map follows the share plan: compared at
-// every latch of an active engine, uploaded when it has changed.
+// The device copies of the call's parameters and of the root map, where they differ from what the device holds (staged_upload),
+// enqueued by gate_latch BEFORE anything of the call.  The map follows the share plan: compared at every latch of an active
+// engine, uploaded when it has changed.
 static int gate_upload(jf_engine *e) {
     const size_t S = (size_t)e->S;
     bool need_par = e->dev_gt_par.size() != S;
     for (size_t s = 0; s < S && !need_par; s++) need_par = !same_par(e->dev_gt_par[s], e->run_gpar[s]);
     bool need_root = e->dev_gt_root.size() != S;
     for (size_t s = 0; s < S && !need_root; s++) need_root = e->dev_gt_root[s] != root_of(e, (int)s);
-    if (!need_par && !need_root) return JF_OK;
     static_assert(sizeof(GatePar) == 4 * sizeof(int), "GatePar layout");
-    int *stage = nullptr;
-    const int rc = e->gt_ring.take(e, 5 * S, &stage);
-    if (rc) return rc;
-    if (need_par) {
-        memcpy(stage, e->run_gpar.data(), sizeof(GatePar) * S);
-        e->dev_gt_par.clear();  // (nothing, should the copy fail)
-        JF_HIP(e, hipMemcpyAsync(e->d_gt_par, stage, sizeof(GatePar) * S, hipMemcpyHostToDevice, e->stream));
-        e->dev_gt_par = e->run_gpar;
-    }
-    if (need_root) {
-        std::vector<int> map(S);
-        for (size_t s = 0; s < S; s++) map[s] = root_of(e, (int)s);
-        memcpy(stage + 4 * S, map.data(), sizeof(int) * S);
-        e->dev_gt_root.clear();
-        JF_HIP(e, hipMemcpyAsync(e->d_gt_root, stage + 4 * S, sizeof(int) * S, hipMemcpyHostToDevice, e->stream));
-        e->dev_gt_root.swap(map);
-    }
-    return e->gt_ring.sent(e);
+    std::vector<int> map(need_root ? S : 0);
+    for (size_t s = 0; s < map.size(); s++) map[s] = root_of(e, (int)s);
+    return staged_upload(e, e->gt_ring, 5 * S, StagedPart<GatePar>{e->d_gt_par, e->dev_gt_par, e->run_gpar, 0, need_par},
+                         StagedPart<int>{e->d_gt_root, e->dev_gt_root, map, 4 * S, need_root});
 }
 
 static int gate_latch_active(jf_engine *e) {
-    const size_t S = (size_t)e->S, KS = (size_t)e->maxK * S;
+    const size_t S = (size_t)e->S;
     if (e->rv_P > 0) return fail(e, JF_ERR_STATE, "voice gates and input meters are not offered while a reverb response is set");
     e->levels_dev_blocks = 0;  // (what a jf_batch_run left on the device is overwritten by this call)
     if (!e->d_gt_state) {
         JF_HIP(e, e->d_gt_par.alloc(S));
         JF_HIP(e, e->d_gt_root.alloc(S));
-        JF_HIP(e, e->d_gt_lv.alloc(3 * KS));
-        JF_HIP(e, e->d_gt_geff.alloc(KS + S));
-        JF_HIP(e, e->h_levels.alloc(3 * KS));
+        int rc = e->input_levels.alloc(e);
+        if (rc) return rc;
+        JF_HIP(e, e->d_gt_geff.alloc((size_t)e->maxK * S + S));
         DevBuf<GateState> st;
         JF_HIP(e, st.alloc(S));
-        JF_HIP(e, hipMemsetAsync(st, 0, sizeof(GateState) * S, e->stream));  // every gate closed, in stream order
+        rc = state_fill(e, st, 0, kGateStateWords, -1);  // every gate closed, in stream order
+        if (rc) return rc;
         e->d_gt_state = std::move(st);
     }
     return gate_upload(e);
 }
 
 int gate_latch(jf_engine *e) {
-    e->gate_on = e->gate_meters = e->voice_on = e->level_on = e->range_on = false;
-    bool voices = false, levellers = false, ranges = false;
+    gate_settle(e);
+    e->gate_meters = false;
     {
         std::lock_guard<std::mutex> lk(e->pos_mu);
-        voices = voice_latch_host(e);  // a bus with a voice limit: the stage runs whether or not a source has a gate
-        levellers = level_latch_host(e);  // ... and so it does for a source with a leveller
-        ranges = range_latch_host(e);     // ... and for a bus with a hearing range
-        if (e->gt_par.empty() && !e->levels_want && !voices && !levellers && !ranges) return JF_OK;  // nothing was ever set
-        bool active = e->levels_want || voices || levellers || ranges;
+        e->vc.on = voice_latch_host(e);  // a bus with a voice limit: the stage runs whether or not a source has a gate
+        e->lv.on = level_latch_host(e);  // ... and so it does for a source with a leveller
+        e->rg.on = range_latch_host(e);  // ... and for a bus with a hearing range
+        bool active = e->levels_want || e->vc.on || e->lv.on || e->rg.on;
         for (size_t s = 0; s < e->gt_par.size() && !active; s++) active = e->gt_par[s].open > 0.0f;
-        if (!active) return JF_OK;  // every gate was set back to open = 0, no meters
+        if (!active) return JF_OK;  // nothing was ever set, or every gate was set back to open = 0: no meters, no follower
         if (e->gt_par.empty())
             e->run_gpar.assign((size_t)e->S, GatePar{0.0f, 0.0f, 0, 0});
         else
@@ -94,13 +76,11 @@ int gate_latch(jf_engine *e) {
         e->gate_meters = e->levels_want;
     }
     int rc = gate_latch_active(e);
-    if (rc == JF_OK && voices) rc = voice_latch_active(e);
-    if (rc == JF_OK && levellers) rc = level_latch_active(e);
-    if (rc == JF_OK && ranges) rc = range_latch_active(e);
+    if (rc == JF_OK && e->vc.on) rc = voice_latch_active(e);
+    if (rc == JF_OK && e->lv.on) rc = level_latch_active(e);
+    if (rc == JF_OK && e->rg.on) rc = range_latch_active(e);
+    if (rc) gate_settle(e);  // (nothing of a call that failed to latch is on)
     e->gate_on = rc == JF_OK;
-    e->voice_on = e->gate_on && voices;
-    e->level_on = e->gate_on && levellers;
-    e->range_on = e->gate_on && ranges;
     return rc;
 }
 
@@ -110,7 +90,8 @@ int gate_latch(jf_engine *e) {
 int run_gate_stage(jf_engine *e, const float *d_pos, int p, int K, int canon, bool timed) {
     const size_t S = (size_t)e->S, KS = (size_t)e->maxK * S;
     if (K > e->maxK || e->rv_P > 0) return fail(e, JF_ERR_STATE, "voice gates: the run does not fit the stage");
-    float *peak = e->d_gt_lv, *sumsq = e->gate_meters ? e->d_gt_lv + KS : nullptr, *gate = e->gate_meters ? e->d_gt_lv + 2 * KS : nullptr;
+    float *lv = e->input_levels.d;
+    float *peak = lv, *sumsq = e->gate_meters ? lv + KS : nullptr, *gate = e->gate_meters ? lv + 2 * KS : nullptr;
     float *g_eff = e->d_gt_geff, *g_eff_prev = e->d_gt_geff + KS;
     const float *g_prev, *g_new, *g_traj;
     gain_run_gains(e, &g_prev, &g_new, &g_traj);
@@ -122,24 +103,25 @@ int run_gate_stage(jf_engine *e, const float *d_pos, int p, int K, int canon, bo
     rc = e->tm_gate.end(e, timed);
     if (rc) return rc;
     e->last_gate = true;
-    e->last_range = e->rg_reported = false;
-    if (e->range_on) {  // the buses' hearing ranges: g_eff and g_eff_prev times h, in place, AHEAD of the voice limits -- who is out
-                        // of earshot is no candidate for a place (jf_engine_range.cpp)
+    // The followers, in THIS order (each sets its `last`, and leaves its report when the input meters are on):
+    e->rg.last = e->rg.reported = false;
+    if (e->rg.on) {  // the buses' hearing ranges: g_eff and g_eff_prev times h, in place, AHEAD of the voice limits -- who is out
+                     // of earshot is no candidate for a place (jf_engine_range.cpp)
         rc = run_range_stage(e, d_pos, g_eff, g_eff_prev, K, timed);
         if (rc) return rc;
-        e->rg_reported = e->gate_meters;
+        e->rg.reported = e->gate_meters;
     }
-    e->last_voice = e->vc_reported = false;
-    if (e->voice_on) {  // the buses' voice limits: g_eff and g_eff_prev rewritten in place (jf_engine_voice.cpp)
+    e->vc.last = e->vc.reported = false;
+    if (e->vc.on) {  // the buses' voice limits: g_eff and g_eff_prev rewritten in place (jf_engine_voice.cpp)
         rc = run_voice_stage(e, peak, g_eff, g_eff_prev, K, timed);
         if (rc) return rc;
-        e->vc_reported = e->gate_meters;
+        e->vc.reported = e->gate_meters;
     }
-    e->last_level = e->lv_reported = false;
-    if (e->level_on) {  // the sources' levellers: g_eff and g_eff_prev times a, in place (jf_engine_level.cpp)
+    e->lv.last = e->lv.reported = false;
+    if (e->lv.on) {  // the sources' levellers: g_eff and g_eff_prev times a, in place (jf_engine_level.cpp)
         rc = run_level_stage(e, peak, g_eff, g_eff_prev, K, timed);
         if (rc) return rc;
-        e->lv_reported = e->gate_meters;
+        e->lv.reported = e->gate_meters;
     }
     rc = e->tm_gain.begin(e, timed);
     if (rc) return rc;
@@ -151,74 +133,59 @@ int run_gate_stage(jf_engine *e, const float *d_pos, int p, int K, int canon, bo
     return JF_OK;
 }
 
-void gate_settle(jf_engine *e) { e->gate_on = e->voice_on = e->level_on = e->range_on = false; }
+void gate_settle(jf_engine *e) {
+    e->gate_on = false;
+    for (FollowerState *f : followers(e)) f->on = false;
+}
 
 // src < 0: every source.  Nothing to close in an engine that never ran the stage: every gate is closed there.  The source's
-// voice envelope starts over with it, it is levelled from 1 again, and its hearing-range state is 1 again.
+// voice envelope starts over with it, it is levelled from 1 again, and its hearing-range state is 1 again (which plane that
+// means is each unit's knowledge: three calls, not a walk).
 int gate_close_source(jf_engine *e, int src) {
-    {
-        int rc = voice_reset_source(e, src);
-        if (rc == JF_OK) rc = level_reset_source(e, src);
-        if (rc == JF_OK) rc = range_reset_source(e, src);
-        if (rc) return rc;
-    }
-    if (!e->d_gt_state) return JF_OK;
-    if (src < 0)
-        JF_HIP(e, hipMemsetAsync(e->d_gt_state, 0, sizeof(GateState) * (size_t)e->S, e->stream));
-    else
-        JF_HIP(e, hipMemsetAsync(e->d_gt_state + src, 0, sizeof(GateState), e->stream));
-    return JF_OK;
+    int rc = voice_reset_source(e, src);
+    if (rc == JF_OK) rc = level_reset_source(e, src);
+    if (rc == JF_OK) rc = range_reset_source(e, src);
+    if (rc || !e->d_gt_state) return rc;
+    return state_fill(e, e->d_gt_state, 0, kGateStateWords, src);
 }
 
-// a run's [3][K][S] (peak, sumsq, gate: each [K][S], maxK S floats apart) to the pinned staging
+// a run's input levels, and what the followers left beside them, to the pinned landing buffers
 int gate_levels_copy(jf_engine *e, int K) {
-    const size_t KS = (size_t)e->maxK * (size_t)e->S, n = (size_t)K * (size_t)e->S;
-    for (size_t a = 0; a < 3; a++)
-        JF_HIP(e, hipMemcpyAsync(e->h_levels + a * KS, e->d_gt_lv + a * KS, sizeof(float) * n, hipMemcpyDeviceToHost, e->stream));
-    if (e->vc_reported) {
-        const int rc = voice_heard_copy(e, K);
-        if (rc) return rc;
-    }
-    if (e->lv_reported) {
-        const int rc = level_gains_copy(e, K);
-        if (rc) return rc;
-    }
-    return e->rg_reported ? range_gains_copy(e, K) : JF_OK;
+    int rc = e->input_levels.copy(e, K);
+    for (FollowerState *f : followers(e))
+        if (rc == JF_OK && f->reported) rc = f->report.copy(e, K);
+    return rc;
 }
 
-// h_levels holds a run: blocks b0 .. b0 + K of a call of n_blocks, into the call's [S][n_blocks][3]
+// the landing buffers hold a run: blocks b0 .. b0 + K of a call of n_blocks.  A follower that left nothing has no report.
 void gate_levels_land(jf_engine *e, int K, int b0, int n_blocks) {
     std::lock_guard<std::mutex> lk(e->pos_mu);
-    const size_t S = (size_t)e->S, KS = (size_t)e->maxK * S, nb = (size_t)n_blocks;
-    if (b0 == 0 || e->levels_last.size() != S * nb * 3) e->levels_last.assign(S * nb * 3, 0.0f);
-    for (size_t k = 0; k < (size_t)K; k++)
-        for (size_t s = 0; s < S; s++)
-            for (size_t a = 0; a < 3; a++) e->levels_last[(s * nb + (size_t)b0 + k) * 3 + a] = e->h_levels[a * KS + k * S + s];
-    e->levels_blocks = b0 + K == n_blocks ? n_blocks : 0;
-    if (e->vc_reported)
-        voice_heard_land(e, K, b0, n_blocks);
-    else
-        e->heard_blocks = 0;
-    if (e->lv_reported)
-        level_gains_land(e, K, b0, n_blocks);
-    else
-        e->gains_blocks = 0;
-    if (e->rg_reported)
-        range_gains_land(e, K, b0, n_blocks);
-    else
-        e->range_blocks = 0;
+    e->input_levels.land(K, b0, n_blocks);
+    for (FollowerState *f : followers(e)) {
+        if (f->reported)
+            f->report.land(K, b0, n_blocks);
+        else
+            f->report.blocks = 0;
+    }
 }
 
-// what the last jf_batch_run left on the device: brought over once, the stream waited for
-int gate_levels_fetch(jf_engine *e) {
-    const int K = e->levels_dev_blocks;
-    if (K <= 0) return JF_OK;
-    const int rc = gate_levels_copy(e, K);
-    if (rc) return rc;
-    JF_HIP(e, hipStreamSynchronize(e->stream));
-    e->levels_dev_blocks = 0;
-    gate_levels_land(e, K, 0, K);
-    return JF_OK;
+int source_report(jf_engine *e, const RunReport &r, bool (*set)(const jf_engine *), const char *unset_msg, const char *none_msg,
+                  int n_blocks, float *out) {
+    return jf_guard([&]() -> int {
+    DeviceGuard bind(e);
+    if (!out) return JF_ERR_ARG;
+    {
+        std::lock_guard<std::mutex> lk(e->pos_mu);
+        if (!e->levels_want) return fail(e, JF_ERR_STATE, "input meters are off (jf_engine_set_input_meters)");
+        if (set && !set(e)) return fail(e, JF_ERR_STATE, unset_msg);
+    }
+    {
+        const int rc = reports_fetch(e, kReportLevels);  // (a jf_batch_run's, still on the device)
+        if (rc) return rc;
+    }
+    std::lock_guard<std::mutex> lk(e->pos_mu);
+    return r.get(e, e->input_levels.blocks, none_msg, n_blocks, out);
+    });
 }
 
 static const char *kGateReverbMsg = "voice gates and input meters are not offered while a reverb response is set (its wet tail outlives the dry level)";
@@ -277,30 +244,14 @@ int jf_engine_set_input_meters(jf_engine *e, int on) {
     std::lock_guard<std::mutex> lk(e->pos_mu);
     if (e->levels_want == (on != 0)) return JF_OK;
     e->levels_want = on != 0;
-    e->levels_blocks = 0;  // (on: nothing has been rendered with them yet; off: they are gone)
+    e->input_levels.blocks = 0;  // (on: nothing has been rendered with them yet; off: they are gone)
     return JF_OK;
     });
 }
 
 int jf_source_levels(jf_engine *e, int n_blocks, float *out) {
-    return jf_guard([&]() -> int {
-    DeviceGuard bind(e);
-    if (!e || !out) return JF_ERR_ARG;
-    {
-        std::lock_guard<std::mutex> lk(e->pos_mu);
-        if (!e->levels_want) return fail(e, JF_ERR_STATE, "input meters are off (jf_engine_set_input_meters)");
-    }
-    {
-        const int rc = gate_levels_fetch(e);  // (a jf_batch_run's, still on the device)
-        if (rc) return rc;
-    }
-    std::lock_guard<std::mutex> lk(e->pos_mu);
-    if (e->levels_blocks <= 0) return fail(e, JF_ERR_STATE, "no call has been rendered with input meters yet");
-    if (n_blocks != e->levels_blocks)
-        return fail(e, JF_ERR_ARG, "the last rendered call had " + std::to_string(e->levels_blocks) + " blocks");
-    memcpy(out, e->levels_last.data(), sizeof(float) * e->levels_last.size());
-    return JF_OK;
-    });
+    if (!e) return JF_ERR_ARG;
+    return source_report(e, e->input_levels, nullptr, nullptr, "no call has been rendered with input meters yet", n_blocks, out);
 }
 
 // The rule on the host: n levels through one source's gate.  state_io = {is_open, hold_left} before the sequence and after it;

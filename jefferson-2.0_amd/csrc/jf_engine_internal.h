@@ -25,7 +25,7 @@
 //   jf_engine_stream.cpp  stream sources: the sources' FIFOs and resampler positions, the jobs a processing call writes for the one
 //                         kernel ahead of everything else (stream_ingest, jf_stream.hip), the host twins of the rule and
 //                         jf_source_set_stream / jf_source_push
-//   jf_engine_output.cpp bus outputs: the buses' rings and resampler positions, the jobs a processing call writes for the one
+//   jf_engine_output.cpp  bus outputs: the buses' rings and resampler positions, the jobs a processing call writes for the one
 //                         kernel behind the master section (run_output_stage, jf_output.hip), the host twins of the rule and
 //                         jf_bus_set_output / jf_bus_pull
 //   jf_engine_level.cpp   talker levelling: the sources' levellers, what a processing call latches of them (inside gate_latch), the
@@ -35,8 +35,13 @@
 //                         (inside gate_latch), the kernel run_gate_stage launches behind its scan and ahead of the voice limits
 //                         (run_range_stage, jf_range.hip) and jf_bus_set_range / jf_source_range_gains
 //   jf_engine_debug.cpp   every entry point of include/jefferson_debug.h (taps, timing hooks, tuning switches, accessors)
-// What the seven latched controls (gain, masters, sets, gates, voice limits, levellers, hearing ranges) share is here once: StagedRing (their asynchronous uploads), StageTimer
-// (the event pairs of a stage that only some runs launch), CallLatches (a processing call's latch and settlement of all four).
+// and, without HIP, jf_report.h: the landing of a run's per-(block, source) report in the host copy of its call.
+// What the seven latched controls (gain, masters, sets, gates, voice limits, levellers, hearing ranges) share is here once:
+// StagedRing and staged_upload (their asynchronous uploads and the protocol of one), state_fill (the fills of state that lives
+// on the device only), StageTimer (the event pairs of a stage that only some runs launch), RunReport (what a run reports per
+// block and source, from the device to the getters; the landing itself is jf_report.h), Follower (what the voice limits, the
+// levellers and the hearing ranges each hold as followers of the gate stage), CallLatches (a processing call's latch and
+// settlement of the four that are latched in their own right: gain, sets, masters, gates -- the other three inside the gates').
 // Not part of any interface: nothing outside csrc/ includes this file.
 #ifndef JF_ENGINE_INTERNAL_H
 #define JF_ENGINE_INTERNAL_H
@@ -51,6 +56,7 @@
 #include <time.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <memory>
 #include <mutex>
@@ -67,6 +73,7 @@
 #include "jf_output.h"
 #include "jf_pose_rule.h"
 #include "jf_range_rule.h"
+#include "jf_report.h"
 #include "jf_room.h"
 #include "jf_stream.h"
 #include "jf_voice_rule.h"
@@ -221,13 +228,13 @@ constexpr int kGainStageSlots = 4;  // changes of a latched control whose device
 
 struct jf_engine;
 
-// The pinned staging of a latched control's asynchronous copies to the device (gain_upload, master_upload, sets_upload): a
-// processing call enqueues them out of here BEFORE anything else of the call, so the host never waits for the stream's work and
-// an otherwise asynchronous jf_batch_run stays one.  kGainStageSlots slots of slot_len taken in turn; an event is recorded
-// behind a slot's copies and the slot is reused only once it has passed, so the host waits only with that many uploads still in
-// line.  take(): the next slot's memory; whatever is missing is created, each piece on its own -- a call that failed part-way
-// through leaves nothing half-made for the next one to trust.  sent(): the caller has enqueued its copies out of that slot.
-// Callers clear their mirror of the device's words before they enqueue and set it afterwards: a failed enqueue is never trusted.
+// The pinned staging of a latched control's asynchronous copies to the device: a processing call enqueues them out of here
+// BEFORE anything else of the call, so the host never waits for the stream's work and an otherwise asynchronous jf_batch_run
+// stays one.  kGainStageSlots slots of slot_len taken in turn; an event is recorded behind a slot's copies and the slot is
+// reused only once it has passed, so the host waits only with that many uploads still in line.  take(): the next slot's
+// memory; whatever is missing is created, each piece on its own -- a call that failed part-way through leaves nothing half-made
+// for the next one to trust.  sent(): the copies out of that slot have been enqueued.  Every control goes through both by way
+// of staged_upload (below), and through nothing else.
 template <class T>
 struct StagedRing {
     PinnedBuf<T> h;                          // [kGainStageSlots][slot_len]
@@ -247,6 +254,43 @@ struct StagedRing {
     inline int sent(jf_engine *e);
 };
 
+// One part of a staged upload (staged_upload): the device buffer `dst` is to hold `want`; `mirror` is the host's record of what
+// it holds (empty: nothing to rely on); `at`: where the part lies in the ring's slot, in the ring's elements; `need`: the
+// caller has judged that the device's copy is not the one the call wants -- that judgement differs from control to control.
+template <class P>
+struct StagedPart {
+    P *dst;
+    std::vector<P> &mirror;
+    const std::vector<P> &want;
+    size_t at;
+    bool need;
+    template <class T>
+    inline int send(jf_engine *e, T *slot) const;
+};
+
+// What a stage reports per (block, source) of a run, on its way to a getter of include/jefferson.h: the device planes `d`
+// [planes][maxK][S] -- the stage's own working buffers, a plane per quantity --, the pinned buffer `h` of the same shape a run's
+// blocks land in, and the last rendered call's report on the host (`last`: [S][blocks][planes], under pos_mu; blocks == 0:
+// none, or a call not yet complete).  copy(): a run's K blocks of every plane to `h`, enqueued.  land(): the stream has been
+// waited for -- `h` holds blocks b0 .. b0 + K of a call of n_blocks (report_land, jf_report.h); under pos_mu.  get(): the end
+// of a getter, under pos_mu -- `valid_blocks` is what `blocks` must equal for the report to be the last rendered call's (the
+// input levels': their own; the followers': the input levels', with which they travel).
+struct RunReport {
+    const int planes;
+    const float fill;  // what a block that was not rendered reads as
+    DevBuf<float> d;
+    PinnedBuf<float> h;
+    int S = 0;          // the engine's, once alloc() has run
+    size_t stride = 0;  // floats between two planes: maxK S
+    std::vector<float> last;
+    int blocks = 0;
+    RunReport(int planes_, float fill_) : planes(planes_), fill(fill_) {}
+    inline int alloc(jf_engine *e);
+    inline int copy(jf_engine *e, int K);
+    void land(int K, int b0, int n_blocks) { blocks = report_land(h, stride, planes, S, K, b0, n_blocks, fill, last); }
+    inline int get(jf_engine *e, int valid_blocks, const char *none_msg, int n_blocks, float *out) const;
+};
+
 // The event pairs around a stage that only some timed runs launch (profiling 2): a pair per timed run (index jf_engine::ev_used)
 // and whether that run launched the stage.  run_blocks arms every timer for the run; the stage brackets its launch with begin
 // and end (both nothing unless the run is timed at profiling 2); sum is what the jf_profile_read_* entries return.
@@ -260,6 +304,26 @@ struct StageTimer {
     inline int begin(jf_engine *e, bool timed);
     inline int end(jf_engine *e, bool timed);
     inline int sum(jf_engine *e, double *ms);  // waits for the engine's stream
+};
+
+// A FOLLOWER of the gate stage: the voice limits, the levellers and the hearing ranges are each latched inside gate_latch, run
+// inside run_gate_stage on its g_eff and report beside the input meters.  What the three hold alike is here; their parameters,
+// their state on the device and their kernels are their units' (jf_engine_voice.cpp, jf_engine_level.cpp, jf_engine_range.cpp).
+struct FollowerState {
+    bool on = false;        // the processing call in hand is active for it (its thread's alone)
+    bool last = false;      // the last run of the gate stage launched its kernels (jf_debug_last_kernels)
+    bool reported = false;  // ... and left its report for the input meters' copies
+    bool idle = false;      // a call was latched without it since its stage last ran: every state is 1 again (levellers, ranges)
+    StageTimer tm;          // profiling 2: around its kernels (jf_profile_read_voices, _level, _range)
+    RunReport report;       // valid while its blocks equal the input levels'
+    FollowerState(int planes, float fill) : report(planes, fill) {}
+};
+template <class T>
+struct Follower : FollowerState {
+    using FollowerState::FollowerState;
+    DevBuf<T> d_par;     // the call's parameters as its kernels read them
+    std::vector<T> dev;  // what d_par holds (empty: nothing yet)
+    StagedRing<T> ring;  // slots of one image of the parameters: the asynchronous copy to d_par
 };
 
 // The convolution reverb as jf_reverb_set_ir set it up: buffers and dimensions, all empty / 0 while the reverb is off
@@ -531,7 +595,8 @@ struct jf_engine : ReverbSetup {
     bool master_rendered = false;             // a run of the call has launched the stage (master_settle: m_prev := m_new)
     std::vector<float> run_mpar;              // [n_buses][4] {m_prev, m_new, c, r} of the call
     int meters_dev_blocks = 0;                // blocks whose meters the last jf_batch_run left in d_meters, not yet fetched (0: none)
-    int meters_stage_blocks = 0;              // blocks whose meters a submitted block's copy brings to h_meters (jf_collect_block)
+    int staged_reports = 0;                   // the reports (kReportMeters | kReportLevels) a submitted block's copies bring to the
+                                              // pinned landing buffers (jf_collect_block)
     DevBuf<float> d_mpar, d_mstate;           // [JF_MAX_BUSES][4], [JF_MAX_BUSES]
     DevBuf<float> d_mt, d_mgg, d_meters;      // [master_cap][1], [..][2], [..][4]: per (bus, block) of a run
     size_t master_cap = 0;                    // items they hold (n_buses maxK when they were allocated)
@@ -589,23 +654,20 @@ struct jf_engine : ReverbSetup {
     // active allocates nothing below and launches nothing (gate_latch).
     std::vector<GatePar> gt_par;              // [S] (empty: no gate was ever set, every open 0)
     bool levels_want = false;                 // jf_engine_set_input_meters
-    std::vector<float> levels_last;           // [S][levels_blocks][3] the last rendered call's input meters on the host
-    int levels_blocks = 0;                    // (0: none)
+    RunReport input_levels{3, 0.0f};          // peak, sumsq, gate of a run: the input meters (its planes are the stage's working
+                                              // buffers: later kernels read peak whether or not the meters are on)
     // what the processing call in hand latched (its thread's alone)
     bool gate_on = false;                     // the call is active
     bool gate_meters = false;                 // ... with input meters
     std::vector<GatePar> run_gpar;            // [S] the call's parameters
     int levels_dev_blocks = 0;                // blocks whose meters the last jf_batch_run left on the device, not yet fetched (0: none)
-    int levels_stage_blocks = 0;              // blocks whose meters a submitted block's copy brings to h_levels (jf_collect_block)
     DevBuf<GatePar> d_gt_par;                 // [S]
     DevBuf<GateState> d_gt_state;             // [S]
     DevBuf<int> d_gt_root;                    // [S] the source whose input s plays
-    DevBuf<float> d_gt_lv;                    // [3][maxK][S]: peak, sumsq, gate of a run
     DevBuf<float> d_gt_geff;                  // [maxK + 1][S]: g_eff of a run, then g_eff_prev
     std::vector<GatePar> dev_gt_par;          // what d_gt_par holds (empty: nothing yet)
     std::vector<int> dev_gt_root;             // what d_gt_root holds (empty: nothing yet)
     StagedRing<int> gt_ring;                  // slots of [5][S] words: the asynchronous copies to d_gt_par and d_gt_root
-    PinnedBuf<float> h_levels;                // [3][maxK][S] where a run's meters land on the host
     bool last_gate = false;                   // the last run launched the stage (jf_debug_last_kernels)
     StageTimer tm_gate;                       // profiling 2: around the two kernels (jf_profile_read_gate)
 
@@ -619,22 +681,13 @@ struct jf_engine : ReverbSetup {
     std::vector<float> vc_rho;                // [n_buses]
     std::vector<char> vc_snap;                // [n_buses] the limit was set with fade == 0 since the last call latched the limits
     std::vector<int> vc_prio;                 // [S] (empty: every priority 0)
-    std::vector<float> heard_last;            // [S][heard_blocks][2] = {env, keep} of the last rendered call, on the host
-    int heard_blocks = 0;                     // (0: none; valid while it equals levels_blocks)
-    // what the processing call in hand latched (its thread's alone)
-    bool voice_on = false;                    // the call is active for voices
+    // (the processing thread's, but for vc.report.last / .blocks)
+    Follower<int> vc{2, 0.0f};                // d_par: the tables -- bus [S], priority [S], members [S], VoiceBus [JF_MAX_BUSES], seg;
+                                              // report: {env, keep} = env, heard of a run
     std::vector<int> run_vc;                  // the call's tables as the device holds them (jf_engine_voice.cpp: image_len)
     bool run_vc_snap = false;                 // the call's next run is its first and some bus was set with fade == 0
-    bool vc_reported = false;                 // the last run of the gate stage left env and heard for the input meters' copies
-    DevBuf<int> d_vc_tab;                     // the tables: bus [S], priority [S], members [S], VoiceBus [JF_MAX_BUSES], seg
-    std::vector<int> dev_vc;                  // what it holds (empty: nothing yet)
-    DevBuf<float> d_vc_env;                   // [2][maxK][S]: env, heard of a run
     DevBuf<float> d_vc_envprev;               // [S]
     DevBuf<int> d_vc_heardprev;               // [S]
-    StagedRing<int> vc_ring;                  // slots of one image: the asynchronous copy to d_vc_tab
-    PinnedBuf<float> h_heard;                 // [2][maxK][S] where a run's env and heard land on the host
-    bool last_voice = false;                  // the last run of the gate stage launched the two kernels (jf_debug_last_kernels)
-    StageTimer tm_voice;                      // profiling 2: around the two kernels (jf_profile_read_voices)
 
     // TALKER LEVELLING (jf_source_set_leveller).  Per source a leveller (LevelPar: jf_level_rule.h) and, on the
     // device ONLY, the state {a_prev}.  While the engine is ACTIVE for levelling -- some source has target > 0 -- it counts as
@@ -642,21 +695,10 @@ struct jf_engine : ReverbSetup {
     // desc_gain_kernel: it rewrites g_eff in place.  The host state is under pos_mu like `pos` and empty until first use; an
     // engine in which no source has target > 0 allocates nothing below and launches nothing (gate_latch: level_latch_host).
     std::vector<LevelPar> lv_par;             // [S] (empty: no leveller was ever set, every target 0)
-    std::vector<float> gains_last;            // [S][gains_blocks] a[k] of the last rendered call, on the host
-    int gains_blocks = 0;                     // (0: none; valid while it equals levels_blocks)
-    // what the processing call in hand latched (its thread's alone)
-    bool level_on = false;                    // the call is active for levelling
+    // (the processing thread's, but for lv.report.last / .blocks)
+    Follower<float> lv{1, 1.0f};              // d_par: [6][S]; report: a[k] of a run
     std::vector<float> run_lv;                // [6][S] the call's parameters as the device holds them, a plane per field
-    bool lv_idle = false;                     // a call was latched without a leveller since the stage last ran: every state is 1 again
-    bool lv_reported = false;                 // the last run of the gate stage left a[K][S] for the input meters' copies
-    DevBuf<float> d_lv_par;                   // [6][S]
-    std::vector<float> dev_lv;                // what it holds (empty: nothing yet)
-    DevBuf<float> d_lv_a;                     // [maxK][S]: a of a run
     DevBuf<float> d_lv_aprev;                 // [S]
-    StagedRing<float> lv_ring;                // slots of [6][S]: the asynchronous copy to d_lv_par
-    PinnedBuf<float> h_lv_a;                  // [maxK][S] where a run's a lands on the host
-    bool last_level = false;                  // the last run of the gate stage launched the kernel (jf_debug_last_kernels)
-    StageTimer tm_level;                      // profiling 2: around the kernel (jf_profile_read_level)
 
     // HEARING RANGE (jf_bus_set_range).  Per bus a range {near, far} (far == 0: none), per source an exempt flag
     // and, on the device ONLY, the state {h_prev}.  While the engine is ACTIVE for ranges -- some bus has far > 0 -- it counts as
@@ -665,22 +707,11 @@ struct jf_engine : ReverbSetup {
     // engine in which no bus has far > 0 allocates nothing below and launches nothing (gate_latch: range_latch_host).
     std::vector<float> rg_range;              // [n_buses][2] = {near, far} (empty: no range was ever set)
     std::vector<unsigned char> rg_exempt;     // [S] (empty: no source is exempt)
-    std::vector<float> range_last;            // [S][range_blocks] h[k] of the last rendered call, on the host
-    int range_blocks = 0;                     // (0: none; valid while it equals levels_blocks)
-    // what the processing call in hand latched (its thread's alone)
-    bool range_on = false;                    // the call is active for ranges
+    // (the processing thread's, but for rg.report.last / .blocks)
+    Follower<float> rg{1, 1.0f};              // d_par: [2][S]; report: h[k] of a run
     std::vector<float> run_rg;                // [2][S] the call's parameters as the device holds them: near, then far, per SOURCE
-    bool rg_idle = false;                     // a call was latched without a range since the stage last ran: every state is 1 again
-    bool rg_reported = false;                 // the last run of the gate stage left h[K][S] for the input meters' copies
-    DevBuf<float> d_rg_par;                   // [2][S]
-    std::vector<float> dev_rg;                // what it holds (empty: nothing yet)
-    DevBuf<float> d_rg_h;                     // [maxK][S]: h of a run
     DevBuf<float> d_rg_hprev;                 // [2][S]: the state, two planes taken in turn per run (read one, write the other)
     int rg_cur = 0;                           // the plane the next run reads
-    StagedRing<float> rg_ring;                // slots of [2][S]: the asynchronous copy to d_rg_par
-    PinnedBuf<float> h_rg_h;                  // [maxK][S] where a run's h lands on the host
-    bool last_range = false;                  // the last run of the gate stage launched the kernel (jf_debug_last_kernels)
-    StageTimer tm_range;                      // profiling 2: around the kernel (jf_profile_read_range)
 
     // STREAM SOURCES (jf_source_set_stream, jf_source_push).  A stream source is internally a live source that
     // takes no row of `in`: the same live_len device buffer named by its record in d_sigs, filled at the source's play position
@@ -865,6 +896,58 @@ inline int StagedRing<T>::sent(jf_engine *e) {
     return JF_OK;
 }
 
+// The mirror is cleared before the copy is enqueued and set afterwards: a failed enqueue is never trusted.
+template <class P>
+template <class T>
+inline int StagedPart<P>::send(jf_engine *e, T *slot) const {
+    if (!need) return JF_OK;
+    const size_t bytes = sizeof(P) * want.size();
+    memcpy(slot + at, want.data(), bytes);
+    mirror.clear();
+    JF_HIP(e, hipMemcpyAsync(dst, slot + at, bytes, hipMemcpyHostToDevice, e->stream));
+    mirror = want;
+    return JF_OK;
+}
+// THE upload of a latched control: nothing when no part is needed; else the ring's next slot, the needed parts out of it in
+// the order given, the slot's event.  Enqueued by the control's latch BEFORE anything of the call.
+template <class T, class... P>
+inline int staged_upload(jf_engine *e, StagedRing<T> &ring, size_t slot_len, const StagedPart<P> &...part) {
+    if (!(part.need || ...)) return JF_OK;
+    T *slot = nullptr;
+    int rc = ring.take(e, slot_len, &slot);
+    ((rc = rc ? rc : part.send(e, slot)), ...);
+    return rc ? rc : ring.sent(e);
+}
+
+// State that lives on the device only (a gate, an envelope, a leveller's or a limiter's gain, a hearing range) is started over by
+// a fill in stream order: every item of `plane` (src < 0: the engine's S sources) or item src alone, `words` 32-bit words each,
+// to the pattern `word`.  Which plane a reset means is its unit's knowledge.
+constexpr unsigned kOneBits = 0x3f800000u;  // 1.0f
+inline int state_fill(jf_engine *e, void *plane, unsigned word, size_t words, int src) {
+    unsigned *at = (unsigned *)plane + (src < 0 ? 0 : (size_t)src * words);
+    JF_HIP(e, hipMemsetD32Async((hipDeviceptr_t)at, (int)word, src < 0 ? words * (size_t)e->S : words, e->stream));
+    return JF_OK;
+}
+
+inline int RunReport::alloc(jf_engine *e) {
+    S = e->S;
+    stride = (size_t)e->maxK * (size_t)e->S;
+    JF_HIP(e, d.alloc((size_t)planes * stride));
+    JF_HIP(e, h.alloc((size_t)planes * stride));
+    return JF_OK;
+}
+inline int RunReport::copy(jf_engine *e, int K) {
+    for (size_t a = 0; a < (size_t)planes; a++)
+        JF_HIP(e, hipMemcpyAsync(h + a * stride, d + a * stride, sizeof(float) * (size_t)K * (size_t)S, hipMemcpyDeviceToHost, e->stream));
+    return JF_OK;
+}
+inline int RunReport::get(jf_engine *e, int valid_blocks, const char *none_msg, int n_blocks, float *out) const {
+    if (blocks <= 0 || blocks != valid_blocks) return fail(e, JF_ERR_STATE, none_msg);
+    if (n_blocks != blocks) return fail(e, JF_ERR_ARG, "the last rendered call had " + std::to_string(blocks) + " blocks");
+    memcpy(out, last.data(), sizeof(float) * last.size());
+    return JF_OK;
+}
+
 inline int StageTimer::begin(jf_engine *e, bool timed) {
     if (!timed || e->profiling < 2) return JF_OK;
     while (ev.size() <= e->ev_used) {
@@ -1024,13 +1107,13 @@ JF_INTERNAL void gain_reset_source(jf_engine *e, int src);  // level 1, not mute
 // run_master_stage: from run_blocks behind run_room_add, while e->master_on.  master_settle: when the call is over, however
 // it ends (CallLatches) -- m_prev := m_new if a run was launched.  master_meters_copy enqueues the copy of a run's meters to
 // the pinned staging, master_meters_land takes them from there (the stream has been waited for) into the call's host copy
-// at block b0 of n_blocks; master_meters_fetch does both for what a jf_batch_run left on the device.
+// at block b0 of n_blocks: the bus meters are records per (bus, block), not planes per (block, source), so they are no RunReport;
+// both are reached through reports_copy / reports_land (below).
 JF_INTERNAL int master_latch(jf_engine *e);
 JF_INTERNAL int run_master_stage(jf_engine *e, int K, float *d_mix_out, bool timed);
 JF_INTERNAL void master_settle(jf_engine *e);
 JF_INTERNAL int master_meters_copy(jf_engine *e, int K);
 JF_INTERNAL void master_meters_land(jf_engine *e, int K, int b0, int n_blocks);
-JF_INTERNAL int master_meters_fetch(jf_engine *e);
 JF_INTERNAL void master_set_buses(jf_engine *e, int n_buses);  // under pos_mu: the buses that remain keep their sections
 // HRTF sets (jf_engine_sets.cpp).  sets_latch: at the start of a processing call that is not paused, beside gain_latch -- what
 // the setters hold becomes the call's (e->sets_on, run_s0, run_s1), the device copies that differ are enqueued.
@@ -1044,8 +1127,11 @@ JF_INTERNAL void sets_settle(jf_engine *e);
 // are enqueued.  run_gate_stage: from run_blocks IN PLACE OF run_gain_stage while e->gate_on (it reads the gains the call latched
 // through gain_run_gains and moves them on as run_gain_stage does).  gate_settle: when the call is over, however it ends.  The
 // state is the device's alone: nothing to give back.  gate_close_source: a reset or a new signal closes the source's gate (src <
-// 0: every one) through the engine's stream.  gate_levels_*: as the masters' meters.  gate_wanted: some source has a gate or
-// input meters are on (jf_reverb_set_ir refuses then).
+// 0: every one) through the engine's stream, and starts its followers' state over.  gate_levels_copy / gate_levels_land: the
+// input levels' report and, of the followers', those the last run left (FollowerState::reported).  gate_wanted: some source has
+// a gate, input meters are on, or a follower is set (jf_reverb_set_ir refuses then).  source_report: the whole of a getter of a
+// per-source report -- `set` (null: the input levels, which need nothing but the meters) says under pos_mu whether the
+// report's control is set at all, unset_msg is the error when it is not, none_msg the one when no call has rendered it yet.
 JF_INTERNAL int gate_latch(jf_engine *e);
 JF_INTERNAL int run_gate_stage(jf_engine *e, const float *d_pos, int p, int K, int canon, bool timed);
 JF_INTERNAL void gate_settle(jf_engine *e);
@@ -1053,49 +1139,59 @@ JF_INTERNAL int gate_close_source(jf_engine *e, int src);
 JF_INTERNAL int gate_levels_copy(jf_engine *e, int K);
 JF_INTERNAL void gate_levels_land(jf_engine *e, int K, int b0, int n_blocks);
 JF_INTERNAL bool gate_wanted(jf_engine *e);
-JF_INTERNAL int gate_levels_fetch(jf_engine *e);  // what the last jf_batch_run left on the device (jf_source_levels, jf_source_heard)
+JF_INTERNAL int source_report(jf_engine *e, const RunReport &r, bool (*set)(const jf_engine *), const char *unset_msg, const char *none_msg,
+                              int n_blocks, float *out);
+// The followers, in the order in which they are latched, reset and copied (the order of their LAUNCHES is run_gate_stage's, which
+// names them: range, voice, level).
+inline std::array<FollowerState *, 3> followers(jf_engine *e) { return {&e->vc, &e->lv, &e->rg}; }
 // voice limits (jf_engine_voice.cpp).  gate_latch calls voice_latch_host under pos_mu (the call's tables; true while some bus
 // has a limit: the engine then counts as gate-active) and voice_latch_active behind the gates' own buffers (allocation, the
-// copy that differs).  run_voice_stage: from run_gate_stage between gate_scan_kernel and desc_gain_kernel, while e->voice_on.
+// copy that differs).  run_voice_stage: from run_gate_stage between gate_scan_kernel and desc_gain_kernel, while e->vc.on.
 // voice_reset_source: a reset or a new signal takes the source's envelope to 0 through the engine's stream (src < 0: every one).
-// voice_heard_copy / voice_heard_land travel with gate_levels_copy / gate_levels_land.  voice_set_buses: under pos_mu, beside
-// master_set_buses.  voice_wanted: some bus has a limit (jf_reverb_set_ir refuses then, through gate_wanted).
+// voice_set_buses: under pos_mu, beside master_set_buses.  voices_limited: under pos_mu, some bus has a limit.
 JF_INTERNAL bool voice_latch_host(jf_engine *e);
 JF_INTERNAL int voice_latch_active(jf_engine *e);
 JF_INTERNAL int run_voice_stage(jf_engine *e, const float *peak, float *g_eff, float *g_eff_prev, int K, bool timed);
 JF_INTERNAL int voice_reset_source(jf_engine *e, int src);
-JF_INTERNAL int voice_heard_copy(jf_engine *e, int K);
-JF_INTERNAL void voice_heard_land(jf_engine *e, int K, int b0, int n_blocks);
 JF_INTERNAL void voice_set_buses(jf_engine *e, int n_buses);
-JF_INTERNAL bool voice_wanted(jf_engine *e);
+JF_INTERNAL bool voices_limited(const jf_engine *e);
 // talker levelling (jf_engine_level.cpp), wired like the voice limits.  gate_latch calls level_latch_host under pos_mu (the
 // call's parameters; true while some source has target > 0: the engine then counts as gate-active) and level_latch_active behind
 // the gates' own buffers (allocation, the copy that differs).  run_level_stage: from run_gate_stage behind the scan and the
-// voice stage, ahead of desc_gain_kernel, while e->level_on.  level_reset_source: a reset or a new signal takes the source's
-// a_prev back to 1 through the engine's stream (src < 0: every one).  level_gains_copy / level_gains_land travel with
-// gate_levels_copy / gate_levels_land.  level_wanted: some source has a leveller (jf_reverb_set_ir refuses then, through
-// gate_wanted).
+// voice stage, ahead of desc_gain_kernel, while e->lv.on.  level_reset_source: a reset or a new signal takes the source's
+// a_prev back to 1 through the engine's stream (src < 0: every one).  levelled: under pos_mu, some source has a leveller.
 JF_INTERNAL bool level_latch_host(jf_engine *e);
 JF_INTERNAL int level_latch_active(jf_engine *e);
 JF_INTERNAL int run_level_stage(jf_engine *e, const float *peak, float *g_eff, float *g_eff_prev, int K, bool timed);
 JF_INTERNAL int level_reset_source(jf_engine *e, int src);
-JF_INTERNAL int level_gains_copy(jf_engine *e, int K);
-JF_INTERNAL void level_gains_land(jf_engine *e, int K, int b0, int n_blocks);
-JF_INTERNAL bool level_wanted(jf_engine *e);
+JF_INTERNAL bool levelled(const jf_engine *e);
 // hearing range (jf_engine_range.cpp), wired like the levellers.  gate_latch calls range_latch_host under pos_mu (the call's
 // planes, resolved per source from its bus and its exempt flag -- so a source that changed its bus is resolved anew; true while
 // some bus has far > 0: the engine then counts as gate-active) and range_latch_active behind the gates' own buffers
 // (allocation, the copy that differs).  run_range_stage: from run_gate_stage behind the scan and AHEAD of the voice stage, while
-// e->range_on; d_pos is the run's records, whoever wrote them.  range_reset_source: a reset or a new signal takes the source's
-// h_prev back to 1 through the engine's stream (src < 0: every one).  range_gains_copy / range_gains_land travel with
-// gate_levels_copy / gate_levels_land.  range_set_buses: under pos_mu, beside voice_set_buses.
+// e->rg.on; d_pos is the run's records, whoever wrote them.  range_reset_source: a reset or a new signal takes the source's
+// h_prev back to 1 through the engine's stream (src < 0: every one).  range_set_buses: under pos_mu, beside voice_set_buses.
+// ranged: under pos_mu, some bus has a range.
 JF_INTERNAL bool range_latch_host(jf_engine *e);
 JF_INTERNAL int range_latch_active(jf_engine *e);
 JF_INTERNAL int run_range_stage(jf_engine *e, const float *d_pos, float *g_eff, float *g_eff_prev, int K, bool timed);
 JF_INTERNAL int range_reset_source(jf_engine *e, int src);
-JF_INTERNAL int range_gains_copy(jf_engine *e, int K);
-JF_INTERNAL void range_gains_land(jf_engine *e, int K, int b0, int n_blocks);
 JF_INTERNAL void range_set_buses(jf_engine *e, int n_buses);
+JF_INTERNAL bool ranged(const jf_engine *e);
+// The two kinds of report a call can render -- the bus meters (the masters') and the input meters with the followers' reports
+// (the gates') -- have one life cycle (jf_engine.cpp).  reports_on: those the call in hand renders, as a mask.  reports_copy:
+// behind a run, the copies of its K blocks to the pinned buffers, enqueued.  reports_land: the stream has been waited for --
+// into the call's host copies at block b0 of n_blocks.  reports_left: a jf_batch_run leaves its reports on the device, the host
+// copies are void.  reports_fetch: ONE kind that a jf_batch_run left, brought over once, the stream waited for (jf_batch_fetch
+// and jf_bus_meters: the bus meters; the per-source getters: the others).
+enum { kReportMeters = 1, kReportLevels = 2 };
+inline int reports_on(const jf_engine *e) {
+    return (e->master_on && e->master_meters ? kReportMeters : 0) | (e->gate_on && e->gate_meters ? kReportLevels : 0);
+}
+JF_INTERNAL int reports_copy(jf_engine *e, int which, int K);
+JF_INTERNAL void reports_land(jf_engine *e, int which, int K, int b0, int n_blocks);
+JF_INTERNAL void reports_left(jf_engine *e, int which, int n_blocks);
+JF_INTERNAL int reports_fetch(jf_engine *e, int kind);
 // the three pointers run_gain_stage hands desc_gain_kernel for the next run of K blocks (all null unless e->gain_on), and the
 // step to the run after it (jf_engine_gain.cpp)
 JF_INTERNAL void gain_run_gains(const jf_engine *e, const float **g_prev, const float **g_new, const float **g_traj);

@@ -6,7 +6,7 @@
 // desc_gain_kernel (run_level_stage).  jf_debug_level_scan is the rule for a sequence of levels on the host -- the header the
 // kernel compiles (jf_level_rule.h).
 //
-// Who reads what: lv_par / gains_last / gains_blocks are touched under pos_mu only; level_on, run_lv, lv_idle and the device
+// Who reads what: lv_par / lv.report.last / .blocks are touched under pos_mu only; lv.on, run_lv, lv.idle and the device
 // buffers belong to the thread that makes the processing calls.  The state {a_prev} is on the device only (d_lv_aprev): it
 // depends on the audio, and every run continues from what the run before left there.
 #include "jf_engine_internal.h"
@@ -14,19 +14,13 @@
 static_assert(sizeof(LevelPar) == 6 * sizeof(float) && sizeof(jf_leveller) == sizeof(LevelPar), "jf_leveller is LevelPar, field for field");
 
 static const LevelPar kLevelOffPar{0.0f, 0.0f, 1.0f, 1.0f, 0.5f, 2.0f};  // what a source has before anything was set
-static const unsigned kOneBits = 0x3f800000u;                            // 1.0f, for the state's fills
 
 static LevelPar par_of(const jf_leveller &l) { return LevelPar{l.target, l.floor, l.min_gain, l.max_gain, l.fall, l.rise}; }
 
-static bool levelled(const jf_engine *e) {  // under pos_mu
+bool levelled(const jf_engine *e) {  // under pos_mu
     for (const LevelPar &lp : e->lv_par)
         if (lp.target > 0.0f) return true;
     return false;
-}
-
-bool level_wanted(jf_engine *e) {
-    std::lock_guard<std::mutex> lk(e->pos_mu);
-    return levelled(e);
 }
 
 // under pos_mu: the call's parameters as the device holds them (run_lv: six planes of [S]), true while some source has T > 0.
@@ -34,7 +28,7 @@ bool level_wanted(jf_engine *e) {
 // carried out by the next latch that is active.
 bool level_latch_host(jf_engine *e) {
     if (!levelled(e)) {
-        if (e->d_lv_aprev) e->lv_idle = true;
+        if (e->d_lv_aprev) e->lv.idle = true;
         return false;
     }
     const size_t S = (size_t)e->S;
@@ -48,70 +42,40 @@ bool level_latch_host(jf_engine *e) {
 }
 
 int level_latch_active(jf_engine *e) {
-    const size_t S = (size_t)e->S, KS = (size_t)e->maxK * S;
+    const size_t S = (size_t)e->S;
     if (!e->d_lv_aprev) {
-        JF_HIP(e, e->d_lv_par.alloc(6 * S));
-        JF_HIP(e, e->d_lv_a.alloc(KS));
-        JF_HIP(e, e->h_lv_a.alloc(KS));
+        JF_HIP(e, e->lv.d_par.alloc(6 * S));
+        const int rc = e->lv.report.alloc(e);
+        if (rc) return rc;
         DevBuf<float> st;
         JF_HIP(e, st.alloc(S));
-        JF_HIP(e, hipMemsetD32Async((hipDeviceptr_t)st.p, (int)kOneBits, S, e->stream));  // every gain 1, in stream order
-        e->dev_lv.clear();
-        e->lv_idle = false;
+        e->lv.dev.clear();
+        e->lv.idle = true;  // every gain 1, in stream order: the fill below
         e->d_lv_aprev = std::move(st);
     }
-    if (e->lv_idle) {
-        JF_HIP(e, hipMemsetD32Async((hipDeviceptr_t)e->d_lv_aprev.p, (int)kOneBits, S, e->stream));
-        e->lv_idle = false;
+    if (e->lv.idle) {
+        const int rc = level_reset_source(e, -1);
+        if (rc) return rc;
+        e->lv.idle = false;
     }
-    if (e->dev_lv == e->run_lv) return JF_OK;
-    float *stage = nullptr;
-    const int rc = e->lv_ring.take(e, 6 * S, &stage);
-    if (rc) return rc;
-    memcpy(stage, e->run_lv.data(), sizeof(float) * 6 * S);
-    e->dev_lv.clear();  // (nothing, should the copy fail)
-    JF_HIP(e, hipMemcpyAsync(e->d_lv_par, stage, sizeof(float) * 6 * S, hipMemcpyHostToDevice, e->stream));
-    e->dev_lv = e->run_lv;
-    return e->lv_ring.sent(e);
+    return staged_upload(e, e->lv.ring, 6 * S, StagedPart<float>{e->lv.d_par, e->lv.dev, e->run_lv, 0, e->lv.dev != e->run_lv});
 }
 
 // Behind the scan (and the voice stage) and ahead of desc_gain_kernel of this run.  g_eff / g_eff_prev are the gate stage's,
 // rewritten in place; a [K][S] is kept for the input meters' copies.
 int run_level_stage(jf_engine *e, const float *peak, float *g_eff, float *g_eff_prev, int K, bool timed) {
-    int rc = e->tm_level.begin(e, timed);
+    int rc = e->lv.tm.begin(e, timed);
     if (rc) return rc;
-    JF_HIP(e, launch_level_scan(e->d_lv_par, e->d_gt_root, peak, g_eff, g_eff_prev, e->d_lv_aprev, e->gate_meters ? e->d_lv_a.p : nullptr,
+    JF_HIP(e, launch_level_scan(e->lv.d_par, e->d_gt_root, peak, g_eff, g_eff_prev, e->d_lv_aprev, e->gate_meters ? e->lv.report.d.p : nullptr,
                                 e->S, K, e->stream));
-    rc = e->tm_level.end(e, timed);
+    rc = e->lv.tm.end(e, timed);
     if (rc) return rc;
-    e->last_level = true;
+    e->lv.last = true;
     return JF_OK;
 }
 
 // src < 0: every source.  A source that starts over is levelled from 1 again; its parameters stay.
-int level_reset_source(jf_engine *e, int src) {
-    if (!e->d_lv_aprev) return JF_OK;
-    if (src < 0)
-        JF_HIP(e, hipMemsetD32Async((hipDeviceptr_t)e->d_lv_aprev.p, (int)kOneBits, (size_t)e->S, e->stream));
-    else
-        JF_HIP(e, hipMemsetD32Async((hipDeviceptr_t)(e->d_lv_aprev.p + src), (int)kOneBits, 1, e->stream));
-    return JF_OK;
-}
-
-// a run's a [K][S] to the pinned staging
-int level_gains_copy(jf_engine *e, int K) {
-    JF_HIP(e, hipMemcpyAsync(e->h_lv_a, e->d_lv_a, sizeof(float) * (size_t)K * (size_t)e->S, hipMemcpyDeviceToHost, e->stream));
-    return JF_OK;
-}
-
-// under pos_mu.  h_lv_a holds a run: blocks b0 .. b0 + K of a call of n_blocks, into the call's [S][n_blocks]
-void level_gains_land(jf_engine *e, int K, int b0, int n_blocks) {
-    const size_t S = (size_t)e->S, nb = (size_t)n_blocks;
-    if (b0 == 0 || e->gains_last.size() != S * nb) e->gains_last.assign(S * nb, 1.0f);
-    for (size_t k = 0; k < (size_t)K; k++)
-        for (size_t s = 0; s < S; s++) e->gains_last[s * nb + (size_t)b0 + k] = e->h_lv_a[k * S + s];
-    e->gains_blocks = b0 + K == n_blocks ? n_blocks : 0;
-}
+int level_reset_source(jf_engine *e, int src) { return e->d_lv_aprev ? state_fill(e, e->d_lv_aprev, kOneBits, 1, src) : JF_OK; }
 
 static const char *kLevelArgMsg =
     "leveller: every value finite; target 0, or 2^-60 <= floor <= target <= 2^24; 0 < min_gain <= 1 <= max_gain <= 1024; 0 < fall < 1 < rise <= 2";
@@ -160,26 +124,9 @@ int jf_source_leveller(const jf_engine *e, int src, jf_leveller *out) {
 }
 
 int jf_source_level_gains(jf_engine *e, int n_blocks, float *out) {
-    return jf_guard([&]() -> int {
-    DeviceGuard bind(e);
-    if (!e || !out) return JF_ERR_ARG;
-    {
-        std::lock_guard<std::mutex> lk(e->pos_mu);
-        if (!e->levels_want) return fail(e, JF_ERR_STATE, "input meters are off (jf_engine_set_input_meters)");
-        if (!levelled(e)) return fail(e, JF_ERR_STATE, "no source has a leveller (jf_source_set_leveller)");
-    }
-    {
-        const int rc = gate_levels_fetch(e);  // (a jf_batch_run's, still on the device)
-        if (rc) return rc;
-    }
-    std::lock_guard<std::mutex> lk(e->pos_mu);
-    if (e->gains_blocks <= 0 || e->gains_blocks != e->levels_blocks)
-        return fail(e, JF_ERR_STATE, "no call has been rendered with a leveller and input meters yet");
-    if (n_blocks != e->gains_blocks)
-        return fail(e, JF_ERR_ARG, "the last rendered call had " + std::to_string(e->gains_blocks) + " blocks");
-    memcpy(out, e->gains_last.data(), sizeof(float) * e->gains_last.size());
-    return JF_OK;
-    });
+    if (!e) return JF_ERR_ARG;
+    return source_report(e, e->lv.report, levelled, "no source has a leveller (jf_source_set_leveller)",
+                         "no call has been rendered with a leveller and input meters yet", n_blocks, out);
 }
 
 // The rule on the host: n levels through one source's leveller.  *a_io is the state before the sequence and, on return, after it.
@@ -195,7 +142,7 @@ int jf_profile_read_level(jf_engine *e, double *level_ms) {
     return jf_guard([&]() -> int {
     DeviceGuard bind(e);
     if (!e || !level_ms) return JF_ERR_ARG;
-    return e->tm_level.sum(e, level_ms);
+    return e->lv.tm.sum(e, level_ms);
     });
 }
 

@@ -54,25 +54,17 @@ void master_set_buses(jf_engine *e, int n_buses) {
     e->meters_last.clear();  // (the shape of a call's meters changes with the buses)
     e->meters_blocks = 0;
     e->meters_dev_blocks = 0;
-    e->meters_stage_blocks = 0;
+    e->staged_reports &= ~kReportMeters;
 }
 
-// The device copy of the call's parameters, where it differs from what the device holds, out of the staging ring (StagedRing),
-// enqueued by master_latch BEFORE anything of the call.  m_prev matters only to a call that ramps: a call that does not leaves
+// The device copy of the call's parameters, where it differs from what the device holds (staged_upload), enqueued by
+// master_latch BEFORE anything of the call.  m_prev matters only to a call that ramps: a call that does not leaves
 // the device's alone.
 static int master_upload(jf_engine *e) {
     const size_t n = e->run_mpar.size();
     bool need = e->dev_mpar.size() != n;
     for (size_t i = 0; i < n && !need; i++) need = (e->master_ramp || i % 4 != 0) && e->dev_mpar[i] != e->run_mpar[i];
-    if (!need) return JF_OK;
-    float *stage = nullptr;
-    const int rc = e->m_ring.take(e, (size_t)4 * JF_MAX_BUSES, &stage);
-    if (rc) return rc;
-    memcpy(stage, e->run_mpar.data(), sizeof(float) * n);
-    e->dev_mpar.clear();  // (nothing, should the copy fail)
-    JF_HIP(e, hipMemcpyAsync(e->d_mpar, stage, sizeof(float) * n, hipMemcpyHostToDevice, e->stream));
-    e->dev_mpar = e->run_mpar;
-    return e->m_ring.sent(e);
+    return staged_upload(e, e->m_ring, (size_t)4 * JF_MAX_BUSES, StagedPart<float>{e->d_mpar, e->dev_mpar, e->run_mpar, 0, need});
 }
 
 // The rows of the look-ahead buffers, under pos_mu: a bus whose look-ahead was turned on takes one (a free one, else the next)
@@ -116,16 +108,7 @@ static int look_prepare(jf_engine *e, int rows, const std::vector<int> &fresh) {
     }
     for (int row : fresh)
         JF_HIP(e, hipMemsetAsync(e->d_lhold + ((size_t)row * 2 + (size_t)e->look_parity) * hf, 0, sizeof(float) * hf, e->stream));
-    const size_t n = e->run_lrow.size();
-    if (e->dev_lrow == e->run_lrow) return JF_OK;
-    int *stage = nullptr;
-    const int rc = e->l_ring.take(e, (size_t)JF_MAX_BUSES, &stage);
-    if (rc) return rc;
-    memcpy(stage, e->run_lrow.data(), sizeof(int) * n);
-    e->dev_lrow.clear();  // (nothing, should the copy fail)
-    JF_HIP(e, hipMemcpyAsync(e->d_lrow, stage, sizeof(int) * n, hipMemcpyHostToDevice, e->stream));
-    e->dev_lrow = e->run_lrow;
-    return e->l_ring.sent(e);
+    return staged_upload(e, e->l_ring, (size_t)JF_MAX_BUSES, StagedPart<int>{e->d_lrow, e->dev_lrow, e->run_lrow, 0, e->dev_lrow != e->run_lrow});
 }
 
 int master_latch(jf_engine *e) {
@@ -192,10 +175,11 @@ int master_latch(jf_engine *e) {
         const int rc = look_prepare(e, look_rows, fresh);
         if (rc) return rc;
     }
-    // a limiter that was turned on or off since the last call starts over at gain 1: 1.0f as a 32-bit pattern, in stream order
-    for (size_t b = 0; b < restart.size() && b < (size_t)e->n_buses; b++)
-        if (restart[b]) JF_HIP(e, hipMemsetD32Async((hipDeviceptr_t)(e->d_mstate + b), 0x3f800000, 1, e->stream));
-    return JF_OK;
+    // a limiter that was turned on or off since the last call starts over at gain 1, in stream order
+    int rc = JF_OK;
+    for (size_t b = 0; b < restart.size() && b < (size_t)e->n_buses && rc == JF_OK; b++)
+        if (restart[b]) rc = state_fill(e, e->d_mstate, kOneBits, 1, (int)b);
+    return rc;
 }
 
 // The stage on the run's mix, d_mix_out [n_buses][K][2B] (the engine's or a jf_batch_run caller's), behind run_room_add and
@@ -253,18 +237,6 @@ void master_meters_land(jf_engine *e, int K, int b0, int n_blocks) {
     for (size_t b = 0; b < nb; b++)
         memcpy(e->meters_last.data() + (b * (size_t)n_blocks + (size_t)b0) * rec, e->h_meters + b * (size_t)K * rec, sizeof(float) * rec * (size_t)K);
     e->meters_blocks = b0 + K == n_blocks ? n_blocks : 0;
-}
-
-// what the last jf_batch_run left in d_meters (jf_batch_fetch, jf_bus_meters): brought over once, the stream waited for
-int master_meters_fetch(jf_engine *e) {
-    const int K = e->meters_dev_blocks;
-    if (K <= 0) return JF_OK;
-    const int rc = master_meters_copy(e, K);
-    if (rc) return rc;
-    JF_HIP(e, hipStreamSynchronize(e->stream));
-    e->meters_dev_blocks = 0;
-    master_meters_land(e, K, 0, K);
-    return JF_OK;
 }
 
 static bool bus_ok(const jf_engine *e, int bus) { return bus >= 0 && bus < e->n_buses; }
@@ -388,7 +360,7 @@ int jf_bus_meters(jf_engine *e, int n_blocks, float *out) {
         if (!e->meters_want) return fail(e, JF_ERR_STATE, "meters are off (jf_engine_set_meters)");
     }
     {
-        const int rc = master_meters_fetch(e);  // (a jf_batch_run's, still on the device)
+        const int rc = reports_fetch(e, kReportMeters);  // (a jf_batch_run's, still on the device)
         if (rc) return rc;
     }
     std::lock_guard<std::mutex> lk(e->pos_mu);

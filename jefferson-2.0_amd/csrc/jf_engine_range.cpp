@@ -6,16 +6,14 @@
 // and desc_gain_kernel (run_range_stage).  jf_range_gain and jf_debug_range_scan are the rule on the host -- the header the
 // kernel compiles (jf_range_rule.h).
 //
-// Who reads what: rg_range / rg_exempt / range_last / range_blocks are touched under pos_mu only; range_on, run_rg, rg_idle,
+// Who reads what: rg_range / rg_exempt / rg.report.last / .blocks are touched under pos_mu only; rg.on, run_rg, rg.idle,
 // rg_cur and the device buffers belong to the thread that makes the processing calls.  The state {h_prev} is on the device only
 // (d_rg_hprev): it depends on where the records put the talkers, which for world positions only the GPU knows, and every run
 // continues from what the run before left there.  It is two planes: a run reads plane rg_cur and writes the other (the lane
 // that reads a source's word and the lane that writes it are different lanes of one launch), then the planes change places.
 #include "jf_engine_internal.h"
 
-static const unsigned kOneBits = 0x3f800000u;  // 1.0f, for the state's fills
-
-static bool ranged(const jf_engine *e) {  // under pos_mu
+bool ranged(const jf_engine *e) {  // under pos_mu
     for (size_t b = 0; 2 * b + 1 < e->rg_range.size(); b++)
         if (e->rg_range[2 * b + 1] > 0.0f) return true;
     return false;
@@ -26,7 +24,7 @@ static bool ranged(const jf_engine *e) {  // under pos_mu
 // every state at 1: remembered here, carried out by the next latch that is active.
 bool range_latch_host(jf_engine *e) {
     if (!ranged(e)) {
-        if (e->d_rg_hprev) e->rg_idle = true;
+        if (e->d_rg_hprev) e->rg.idle = true;
         return false;
     }
     const size_t S = (size_t)e->S, nb = e->rg_range.size() / 2;
@@ -42,32 +40,26 @@ bool range_latch_host(jf_engine *e) {
 }
 
 int range_latch_active(jf_engine *e) {
-    const size_t S = (size_t)e->S, KS = (size_t)e->maxK * S;
+    const size_t S = (size_t)e->S;
     if (!e->d_rg_hprev) {
-        JF_HIP(e, e->d_rg_par.alloc(2 * S));
-        JF_HIP(e, e->d_rg_h.alloc(KS));
-        JF_HIP(e, e->h_rg_h.alloc(KS));
+        JF_HIP(e, e->rg.d_par.alloc(2 * S));
+        int rc = e->rg.report.alloc(e);
+        if (rc) return rc;
         DevBuf<float> st;
         JF_HIP(e, st.alloc(2 * S));
-        JF_HIP(e, hipMemsetD32Async((hipDeviceptr_t)st.p, (int)kOneBits, 2 * S, e->stream));  // everybody was heard, in stream order
-        e->dev_rg.clear();
-        e->rg_idle = false;
+        rc = state_fill(e, st, kOneBits, 2, -1);  // both planes: everybody was heard, in stream order
+        if (rc) return rc;
+        e->rg.dev.clear();
+        e->rg.idle = false;
         e->rg_cur = 0;
         e->d_rg_hprev = std::move(st);
     }
-    if (e->rg_idle) {
-        JF_HIP(e, hipMemsetD32Async((hipDeviceptr_t)(e->d_rg_hprev.p + (size_t)e->rg_cur * S), (int)kOneBits, S, e->stream));
-        e->rg_idle = false;
+    if (e->rg.idle) {
+        const int rc = range_reset_source(e, -1);
+        if (rc) return rc;
+        e->rg.idle = false;
     }
-    if (e->dev_rg == e->run_rg) return JF_OK;
-    float *stage = nullptr;
-    const int rc = e->rg_ring.take(e, 2 * S, &stage);
-    if (rc) return rc;
-    memcpy(stage, e->run_rg.data(), sizeof(float) * 2 * S);
-    e->dev_rg.clear();  // (nothing, should the copy fail)
-    JF_HIP(e, hipMemcpyAsync(e->d_rg_par, stage, sizeof(float) * 2 * S, hipMemcpyHostToDevice, e->stream));
-    e->dev_rg = e->run_rg;
-    return e->rg_ring.sent(e);
+    return staged_upload(e, e->rg.ring, 2 * S, StagedPart<float>{e->rg.d_par, e->rg.dev, e->run_rg, 0, e->rg.dev != e->run_rg});
 }
 
 // Behind the scan and ahead of the voice stage of this run.  d_pos: the run's K * S records (an uploaded trajectory, the
@@ -78,40 +70,20 @@ int run_range_stage(jf_engine *e, const float *d_pos, float *g_eff, float *g_eff
     const size_t S = (size_t)e->S;
     const float *h_in = e->d_rg_hprev.p + (size_t)e->rg_cur * S;
     float *h_to = e->d_rg_hprev.p + (size_t)(e->rg_cur ^ 1) * S;
-    int rc = e->tm_range.begin(e, timed);
+    int rc = e->rg.tm.begin(e, timed);
     if (rc) return rc;
-    JF_HIP(e, launch_range_gain(e->d_rg_par, d_pos, g_eff, g_eff_prev, h_in, h_to, e->gate_meters ? e->d_rg_h.p : nullptr, e->S, K, e->stream));
-    rc = e->tm_range.end(e, timed);
+    JF_HIP(e, launch_range_gain(e->rg.d_par, d_pos, g_eff, g_eff_prev, h_in, h_to, e->gate_meters ? e->rg.report.d.p : nullptr, e->S, K, e->stream));
+    rc = e->rg.tm.end(e, timed);
     if (rc) return rc;
     e->rg_cur ^= 1;  // (the next run, and a reset in between, meet what this one wrote)
-    e->last_range = true;
+    e->rg.last = true;
     return JF_OK;
 }
 
-// src < 0: every source.  A source that starts over was heard in full before; the ranges stay.
+// src < 0: every source.  A source that starts over was heard in full before; the ranges stay.  The plane the next run reads.
 int range_reset_source(jf_engine *e, int src) {
     if (!e->d_rg_hprev) return JF_OK;
-    float *plane = e->d_rg_hprev.p + (size_t)e->rg_cur * (size_t)e->S;
-    if (src < 0)
-        JF_HIP(e, hipMemsetD32Async((hipDeviceptr_t)plane, (int)kOneBits, (size_t)e->S, e->stream));
-    else
-        JF_HIP(e, hipMemsetD32Async((hipDeviceptr_t)(plane + src), (int)kOneBits, 1, e->stream));
-    return JF_OK;
-}
-
-// a run's h [K][S] to the pinned staging
-int range_gains_copy(jf_engine *e, int K) {
-    JF_HIP(e, hipMemcpyAsync(e->h_rg_h, e->d_rg_h, sizeof(float) * (size_t)K * (size_t)e->S, hipMemcpyDeviceToHost, e->stream));
-    return JF_OK;
-}
-
-// under pos_mu.  h_rg_h holds a run: blocks b0 .. b0 + K of a call of n_blocks, into the call's [S][n_blocks]
-void range_gains_land(jf_engine *e, int K, int b0, int n_blocks) {
-    const size_t S = (size_t)e->S, nb = (size_t)n_blocks;
-    if (b0 == 0 || e->range_last.size() != S * nb) e->range_last.assign(S * nb, 1.0f);
-    for (size_t k = 0; k < (size_t)K; k++)
-        for (size_t s = 0; s < S; s++) e->range_last[s * nb + (size_t)b0 + k] = e->h_rg_h[k * S + s];
-    e->range_blocks = b0 + K == n_blocks ? n_blocks : 0;
+    return state_fill(e, e->d_rg_hprev.p + (size_t)e->rg_cur * (size_t)e->S, kOneBits, 1, src);
 }
 
 // under pos_mu: the buses that remain keep their ranges, new ones have none
@@ -172,26 +144,9 @@ int jf_source_range_exempt(const jf_engine *e, int src) {
 }
 
 int jf_source_range_gains(jf_engine *e, int n_blocks, float *out) {
-    return jf_guard([&]() -> int {
-    DeviceGuard bind(e);
-    if (!e || !out) return JF_ERR_ARG;
-    {
-        std::lock_guard<std::mutex> lk(e->pos_mu);
-        if (!e->levels_want) return fail(e, JF_ERR_STATE, "input meters are off (jf_engine_set_input_meters)");
-        if (!ranged(e)) return fail(e, JF_ERR_STATE, "no bus has a hearing range (jf_bus_set_range)");
-    }
-    {
-        const int rc = gate_levels_fetch(e);  // (a jf_batch_run's, still on the device)
-        if (rc) return rc;
-    }
-    std::lock_guard<std::mutex> lk(e->pos_mu);
-    if (e->range_blocks <= 0 || e->range_blocks != e->levels_blocks)
-        return fail(e, JF_ERR_STATE, "no call has been rendered with a hearing range and input meters yet");
-    if (n_blocks != e->range_blocks)
-        return fail(e, JF_ERR_ARG, "the last rendered call had " + std::to_string(e->range_blocks) + " blocks");
-    memcpy(out, e->range_last.data(), sizeof(float) * e->range_last.size());
-    return JF_OK;
-    });
+    if (!e) return JF_ERR_ARG;
+    return source_report(e, e->rg.report, ranged, "no bus has a hearing range (jf_bus_set_range)",
+                         "no call has been rendered with a hearing range and input meters yet", n_blocks, out);
 }
 
 // The rule without an engine: h of one record.
@@ -224,7 +179,7 @@ int jf_profile_read_range(jf_engine *e, double *range_ms) {
     return jf_guard([&]() -> int {
     DeviceGuard bind(e);
     if (!e || !range_ms) return JF_ERR_ARG;
-    return e->tm_range.sum(e, range_ms);
+    return e->rg.tm.sum(e, range_ms);
     });
 }
 

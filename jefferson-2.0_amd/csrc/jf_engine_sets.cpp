@@ -34,29 +34,14 @@ static void set_apply(jf_engine *e, int s, int set, int fade) {
     }
 }
 
-// The device copies of the call's sets, where they differ from what the device holds, out of the staging ring (StagedRing),
-// enqueued by sets_latch BEFORE anything of the call.
+// The device copies of the call's sets, where they differ from what the device holds (staged_upload), enqueued by sets_latch
+// BEFORE anything of the call.  The sets before matter only to a call that switches.
 static int sets_upload(jf_engine *e) {
     const size_t S = (size_t)e->S;
     const bool need_new = e->dev_set_new != e->run_s1;
     const bool need_prev = e->set_switch && e->dev_set_prev != e->run_s0;
-    if (!need_new && !need_prev) return JF_OK;
-    int *stage = nullptr;
-    const int rc = e->s_ring.take(e, 2 * S, &stage);
-    if (rc) return rc;
-    if (need_new) {
-        memcpy(stage, e->run_s1.data(), sizeof(int) * S);
-        e->dev_set_new.clear();  // (nothing, should the copy fail)
-        JF_HIP(e, hipMemcpyAsync(e->d_set_new, stage, sizeof(int) * S, hipMemcpyHostToDevice, e->stream));
-        e->dev_set_new = e->run_s1;
-    }
-    if (need_prev) {
-        memcpy(stage + S, e->run_s0.data(), sizeof(int) * S);
-        e->dev_set_prev.clear();
-        JF_HIP(e, hipMemcpyAsync(e->d_set_prev, stage + S, sizeof(int) * S, hipMemcpyHostToDevice, e->stream));
-        e->dev_set_prev = e->run_s0;
-    }
-    return e->s_ring.sent(e);
+    return staged_upload(e, e->s_ring, 2 * S, StagedPart<int>{e->d_set_new, e->dev_set_new, e->run_s1, 0, need_new},
+                         StagedPart<int>{e->d_set_prev, e->dev_set_prev, e->run_s0, S, need_prev});
 }
 
 int sets_latch(jf_engine *e) {

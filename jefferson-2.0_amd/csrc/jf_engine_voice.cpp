@@ -6,7 +6,7 @@
 // (run_voice_stage).  jf_debug_voice_select is the rule for one run on the host -- the header the kernels compile
 // (jf_voice_rule.h).
 //
-// Who reads what: vc_N / vc_rho / vc_snap / vc_prio / heard_last / heard_blocks are touched under pos_mu only; voice_on, run_vc
+// Who reads what: vc_N / vc_rho / vc_snap / vc_prio / vc.report.last / .blocks are touched under pos_mu only; vc.on, run_vc
 // and the device buffers belong to the thread that makes the processing calls.  The state {env_prev, heard_prev} is on the device
 // only (d_vc_envprev, d_vc_heardprev): it depends on the audio, and every run continues from what the run before left there.
 #include "jf_engine_internal.h"
@@ -18,15 +18,10 @@ static size_t image_par(const jf_engine *e) { return (3 * (size_t)e->S + 3) & ~(
 static size_t image_seg(const jf_engine *e) { return image_par(e) + 4 * (size_t)JF_MAX_BUSES; }
 static size_t image_len(const jf_engine *e) { return image_seg(e) + (size_t)JF_MAX_BUSES + 1; }
 
-static bool voices_limited(const jf_engine *e) {  // under pos_mu
+bool voices_limited(const jf_engine *e) {  // under pos_mu
     for (const int n : e->vc_N)
         if (n > 0) return true;
     return false;
-}
-
-bool voice_wanted(jf_engine *e) {
-    std::lock_guard<std::mutex> lk(e->pos_mu);
-    return voices_limited(e);
 }
 
 // under pos_mu: the call's tables (run_vc), true while some bus has a limit.  The fade == 0 marks are consumed here.
@@ -57,59 +52,45 @@ bool voice_latch_host(jf_engine *e) {
 }
 
 int voice_latch_active(jf_engine *e) {
-    const size_t S = (size_t)e->S, KS = (size_t)e->maxK * S, n = image_len(e);
-    if (!e->d_vc_tab) {
-        JF_HIP(e, e->d_vc_env.alloc(2 * KS));
-        JF_HIP(e, e->h_heard.alloc(2 * KS));
+    const size_t S = (size_t)e->S, n = image_len(e);
+    if (!e->vc.d_par) {
+        int rc = e->vc.report.alloc(e);
+        if (rc) return rc;
         JF_HIP(e, e->d_vc_envprev.alloc(S));
         JF_HIP(e, e->d_vc_heardprev.alloc(S));
         DevBuf<int> tab;
         JF_HIP(e, tab.alloc(n));
-        JF_HIP(e, hipMemsetAsync(e->d_vc_envprev, 0, sizeof(float) * S, e->stream));      // no envelope yet,
-        JF_HIP(e, hipMemsetD32Async((hipDeviceptr_t)e->d_vc_heardprev.p, 1, S, e->stream));  // and everybody was heard
-        e->dev_vc.clear();
-        e->d_vc_tab = std::move(tab);
+        rc = state_fill(e, e->d_vc_envprev, 0, 1, -1);                     // no envelope yet,
+        if (rc == JF_OK) rc = state_fill(e, e->d_vc_heardprev, 1, 1, -1);  // and everybody was heard
+        if (rc) return rc;
+        e->vc.dev.clear();
+        e->vc.d_par = std::move(tab);
     }
-    if (e->dev_vc == e->run_vc) return JF_OK;
-    int *stage = nullptr;
-    const int rc = e->vc_ring.take(e, n, &stage);
-    if (rc) return rc;
-    memcpy(stage, e->run_vc.data(), sizeof(int) * n);
-    e->dev_vc.clear();  // (nothing, should the copy fail)
-    JF_HIP(e, hipMemcpyAsync(e->d_vc_tab, stage, sizeof(int) * n, hipMemcpyHostToDevice, e->stream));
-    e->dev_vc = e->run_vc;
-    return e->vc_ring.sent(e);
+    return staged_upload(e, e->vc.ring, n, StagedPart<int>{e->vc.d_par, e->vc.dev, e->run_vc, 0, e->vc.dev != e->run_vc});
 }
 
 // Between gate_scan_kernel and desc_gain_kernel of this run: the envelopes, then who is heard.  g_eff / g_eff_prev are the gate
 // stage's, rewritten in place.
 int run_voice_stage(jf_engine *e, const float *peak, float *g_eff, float *g_eff_prev, int K, bool timed) {
     const size_t S = (size_t)e->S, KS = (size_t)e->maxK * S;
-    const int *tab = e->d_vc_tab;
+    const int *tab = e->vc.d_par;
     const int *bus = tab, *prio = tab + S, *members = tab + 2 * S, *seg = tab + image_seg(e);
     const VoiceBus *par = reinterpret_cast<const VoiceBus *>(tab + image_par(e));
-    float *env = e->d_vc_env, *heard = e->d_vc_env + KS;
-    int rc = e->tm_voice.begin(e, timed);
+    float *env = e->vc.report.d, *heard = env + KS;
+    int rc = e->vc.tm.begin(e, timed);
     if (rc) return rc;
     JF_HIP(e, launch_voice_env(peak, e->d_gt_root, bus, prio, par, e->d_vc_envprev, e->d_vc_heardprev, env, g_eff_prev, heard, e->S, K,
                                e->n_buses, e->run_vc_snap ? 1 : 0, e->stream));
     JF_HIP(e, launch_voice_select(members, seg, prio, par, env, g_eff, e->d_vc_heardprev, heard, e->S, K, e->n_buses, e->stream));
-    rc = e->tm_voice.end(e, timed);
+    rc = e->vc.tm.end(e, timed);
     if (rc) return rc;
     e->run_vc_snap = false;  // (the call's later runs continue from what this one left)
-    e->last_voice = true;
+    e->vc.last = true;
     return JF_OK;
 }
 
 // src < 0: every source.  A source that starts over has no envelope; heard_prev stays.
-int voice_reset_source(jf_engine *e, int src) {
-    if (!e->d_vc_envprev) return JF_OK;
-    if (src < 0)
-        JF_HIP(e, hipMemsetAsync(e->d_vc_envprev, 0, sizeof(float) * (size_t)e->S, e->stream));
-    else
-        JF_HIP(e, hipMemsetAsync(e->d_vc_envprev + src, 0, sizeof(float), e->stream));
-    return JF_OK;
-}
+int voice_reset_source(jf_engine *e, int src) { return e->d_vc_envprev ? state_fill(e, e->d_vc_envprev, 0, 1, src) : JF_OK; }
 
 // under pos_mu: the buses that remain keep their limits, new ones have none
 void voice_set_buses(jf_engine *e, int n_buses) {
@@ -117,24 +98,6 @@ void voice_set_buses(jf_engine *e, int n_buses) {
     e->vc_N.resize((size_t)n_buses, 0);
     e->vc_rho.resize((size_t)n_buses, 0.0f);
     e->vc_snap.resize((size_t)n_buses, 0);
-}
-
-// a run's env and heard (each [K][S], maxK S floats apart) to the pinned staging
-int voice_heard_copy(jf_engine *e, int K) {
-    const size_t KS = (size_t)e->maxK * (size_t)e->S, n = (size_t)K * (size_t)e->S;
-    for (size_t a = 0; a < 2; a++)
-        JF_HIP(e, hipMemcpyAsync(e->h_heard + a * KS, e->d_vc_env + a * KS, sizeof(float) * n, hipMemcpyDeviceToHost, e->stream));
-    return JF_OK;
-}
-
-// under pos_mu.  h_heard holds a run: blocks b0 .. b0 + K of a call of n_blocks, into the call's [S][n_blocks][2]
-void voice_heard_land(jf_engine *e, int K, int b0, int n_blocks) {
-    const size_t S = (size_t)e->S, KS = (size_t)e->maxK * S, nb = (size_t)n_blocks;
-    if (b0 == 0 || e->heard_last.size() != S * nb * 2) e->heard_last.assign(S * nb * 2, 0.0f);
-    for (size_t k = 0; k < (size_t)K; k++)
-        for (size_t s = 0; s < S; s++)
-            for (size_t a = 0; a < 2; a++) e->heard_last[(s * nb + (size_t)b0 + k) * 2 + a] = e->h_heard[a * KS + k * S + s];
-    e->heard_blocks = b0 + K == n_blocks ? n_blocks : 0;
 }
 
 static const char *kVoiceReverbMsg = "voice limits are not offered while a reverb response is set (its wet tail outlives the dry level)";
@@ -195,26 +158,9 @@ int jf_source_priority(const jf_engine *e, int src) {
 }
 
 int jf_source_heard(jf_engine *e, int n_blocks, float *out) {
-    return jf_guard([&]() -> int {
-    DeviceGuard bind(e);
-    if (!e || !out) return JF_ERR_ARG;
-    {
-        std::lock_guard<std::mutex> lk(e->pos_mu);
-        if (!e->levels_want) return fail(e, JF_ERR_STATE, "input meters are off (jf_engine_set_input_meters)");
-        if (!voices_limited(e)) return fail(e, JF_ERR_STATE, "no bus has a voice limit (jf_bus_set_voices)");
-    }
-    {
-        const int rc = gate_levels_fetch(e);  // (a jf_batch_run's, still on the device)
-        if (rc) return rc;
-    }
-    std::lock_guard<std::mutex> lk(e->pos_mu);
-    if (e->heard_blocks <= 0 || e->heard_blocks != e->levels_blocks)
-        return fail(e, JF_ERR_STATE, "no call has been rendered with a voice limit and input meters yet");
-    if (n_blocks != e->heard_blocks)
-        return fail(e, JF_ERR_ARG, "the last rendered call had " + std::to_string(e->heard_blocks) + " blocks");
-    memcpy(out, e->heard_last.data(), sizeof(float) * e->heard_last.size());
-    return JF_OK;
-    });
+    if (!e) return JF_ERR_ARG;
+    return source_report(e, e->vc.report, voices_limited, "no bus has a voice limit (jf_bus_set_voices)",
+                         "no call has been rendered with a voice limit and input meters yet", n_blocks, out);
 }
 
 // The rule on the host: one run of K blocks over S sources on n_buses buses.  g_eff [K][S] and g_eff_prev [S] are rewritten in
@@ -263,7 +209,7 @@ int jf_profile_read_voices(jf_engine *e, double *voice_ms) {
     return jf_guard([&]() -> int {
     DeviceGuard bind(e);
     if (!e || !voice_ms) return JF_ERR_ARG;
-    return e->tm_voice.sum(e, voice_ms);
+    return e->vc.tm.sum(e, voice_ms);
     });
 }
 

@@ -9,6 +9,11 @@ desc_gain_kernel, and B's first and last run are held, bus by bus, to tests/conf
 tests/test_gpu_conference_sessions.py (conference_sessions.bounds), so that an error A and B share cannot pass.  The model hears
 through sets as tests/conference_model.py composes them (tests/sets_model.py's identity).
 
+The second test does the same for the rings of the voice gates and of the gate stage's followers -- voice limits, talker
+levelling, hearing ranges -- which go through the same staged upload (csrc/jf_engine_internal.h: staged_upload): a source's gate
+thresholds, a bus's voice limit, a source's leveller target and a bus's far change before every run, input meters on, and the
+last run's levels, heard, leveller gains and range gains of A and B are equal bit for bit as well.
+
 NOT a race detector: on runs this short the host need not get four uploads ahead of the device, so the event wait that keeps a
 slot from being overwritten while its copy is still in line may never be exercised here; that wait is checked by review.
 """
@@ -133,3 +138,110 @@ def test_twelve_changes_of_every_control_back_to_back(jf, sets, castanets):
             assert np.abs(want).max(axis=(1, 2)).min() > 0.02, "a silent bus proves nothing"
             assert (err <= bound).all(), (i, err.tolist(), bound.tolist())
     assert limited, "the limiter never had anything to do"
+
+
+# ---- the rings of the gates and of the gate stage's followers: voice limits, levellers, hearing ranges ----------------------
+# (they go through the same staged upload as the three above, and had never been taken past their slot count)
+RANGES = [(0.3, 0.5), (0.5, 0.9)]                # per bus {near, far}: of either bus's sources some are inside, some in the ramp, some beyond
+
+
+def _setup_followers(x, sigs):
+    """what both engines and the model are before the first run: every follower on from the start, so that every run launches
+    every kernel of the gate stage"""
+    x.set_buses(NB)
+    for s in range(S):
+        x.set_signal(s, sigs[s])
+        x.set_bus(s, BUS[s])
+    x.set_input_meters(True)
+    x.set_gate(3, 0.14, 0.1, 1)
+    x.set_gate(6, 0.9, 0.8, 0)          # above its input's peaks: closed throughout
+    for b in range(NB):
+        x.set_voices(b, 2, 0.5, fade=False)
+        x.set_range(b, *RANGES[b])
+    x.set_leveller(1, 0.2, 0.01, 0.25, 4.0, 0.5, 2.0)
+    x.set_leveller(5, 0.1, 0.01, 0.25, 4.0, 0.5, 2.0)
+
+
+def _change_followers(x, i):
+    """what changes before run i: one source's gate thresholds, one bus's voice limit (N and fade alternating), one source's
+    leveller target and one bus's far"""
+    x.set_gate(3, 0.12 + 0.01 * i, 0.08 + 0.005 * i, i % 3)
+    x.set_voices(i % 2, 2 + i % 2, 0.5, fade=bool((i // 2) % 2))
+    x.set_leveller(1, 0.2 + 0.01 * i, 0.01, 0.25, 4.0, 0.5, 2.0)
+    x.set_range((i + 1) % 2, RANGES[(i + 1) % 2][0], RANGES[(i + 1) % 2][1] - 0.05 + 0.01 * i)
+
+
+FOLLOWER_KERNELS = ("input_level_kernel", "gate_scan_kernel", "range_gain_kernel", "voice_env_kernel", "level_scan_kernel",
+                    "desc_gain_kernel")
+
+
+def follower_model_runs(hrir, sigs, pos):
+    """the model's twelve runs: (want, last) per run, and the conditions against an empty pass, asserted here"""
+    model = ConferenceModel(B, L, S, hrir)
+    _setup_followers(model, sigs)
+    runs, seen = [], dict(closed=False, dropped=False, levelled=False, ramp=False)
+    for i in range(RUNS):
+        _change_followers(model, i)
+        want = model.run_records(pos[i * K:(i + 1) * K])
+        last = model.last
+        runs.append((want, last))
+        seen["closed"] = seen["closed"] or bool((last["levels"][..., 2] == 0).any())
+        seen["dropped"] = seen["dropped"] or bool((last["heard"][..., 1] == 0).any())
+        seen["levelled"] = seen["levelled"] or bool((last["level_gains"] != 1).any())
+        seen["ramp"] = seen["ramp"] or bool(((last["range_gains"] > 0) & (last["range_gains"] < 1)).any())
+    assert all(seen.values()), ("a follower never had anything to do", seen)
+    return runs
+
+
+def test_twelve_changes_of_the_gates_and_their_followers_back_to_back(jf, hrir, castanets):
+    """The second half of the guard above (the "NOT a race detector" paragraph holds for it as well): the rings of the gates,
+    the voice limits, the levellers and the hearing ranges over 12 uploads each, input meters on.  A's twelve runs back to back
+    against B's with a wait after each: the outputs and the last run's four per-source reports bit for bit, every kernel of the
+    gate stage in every run of A, B's first and last run within conference_sessions.bounds of the model."""
+    sigs, pos = _signals(castanets), _positions(jf)
+    hip = C.CDLL("libamdhip64.so")
+    run_floats = NB * K * 2 * B
+    bufs = []
+    for _ in range(2):
+        buf = C.c_void_p()
+        assert hip.hipMalloc(C.byref(buf), C.c_size_t(4 * RUNS * run_floats)) == 0 and buf.value
+        bufs.append(buf)
+
+    def session(buf, wait):
+        e = jf.Engine(B, L, S, hrir=hrir, max_batch_blocks=K)
+        _setup_followers(e, sigs)
+        e.upload_positions(pos)
+        names = []
+        for i in range(RUNS):
+            _change_followers(e, i)
+            e.batch_run(i * K, K, C.c_void_p(buf.value + 4 * i * run_floats))
+            names.append(e.last_kernels())
+            if wait:
+                e.synchronize()
+        e.synchronize()
+        out = e.read_device(buf, (RUNS, NB, K, 2 * B))
+        reports = dict(levels=e.levels(K), heard=e.heard(K), level_gains=e.level_gains(K), range_gains=e.range_gains(K))
+        e.close()
+        return out, reports, names
+
+    a, rep_a, names_a = session(bufs[0], False)
+    b, rep_b, _ = session(bufs[1], True)
+    for buf in bufs:
+        assert hip.hipFree(buf) == 0
+
+    for i in range(RUNS):
+        assert np.array_equal(a[i].view(np.uint32), b[i].view(np.uint32)), (i, float(np.abs(a[i] - b[i]).max()))
+    for name in rep_a:
+        assert np.array_equal(rep_a[name].view(np.uint32), rep_b[name].view(np.uint32)), (name, rep_a[name], rep_b[name])
+    for i, ks in enumerate(names_a):
+        for kernel in FOLLOWER_KERNELS:
+            assert kernel in ks, (i, kernel, ks)
+
+    runs = follower_model_runs(hrir, sigs, pos)
+    for i in (0, RUNS - 1):
+        want, last = runs[i]
+        bound = cs.bounds(last, NB, K)
+        err = np.abs(b[i] - want).max(axis=2)
+        print(f"run {i}: error / bound per (bus, block) {np.round(err / bound, 3).tolist()}, peak {np.abs(want).max(axis=(1, 2))}")
+        assert np.abs(want).max(axis=(1, 2)).min() > 0.02, "a silent bus proves nothing"
+        assert (err <= bound).all(), (i, err.tolist(), bound.tolist())

@@ -44,6 +44,19 @@ def test_host_side_under_asan_and_ubsan():
     assert "0 failed checks" in out
 
 
+@pytest.mark.skipif(not (shutil.which("g++") and _have_sanitizers("gcc")), reason="gcc with libasan/libubsan not available")
+def test_report_landing_under_asan_and_ubsan():
+    """csrc/jf_report.h, the transposition every per-source report lands through, on exactly sized heap arrays: 1, 2 and 3 planes,
+    a call of 5 blocks landed as 3 + 2 out of a run capacity of 4, the refill over an older call, a one-block call"""
+    build = os.path.join(ROOT, "tests", "build")
+    os.makedirs(build, exist_ok=True)
+    exe = os.path.join(build, "report_san")
+    _run(["g++", "-std=c++17", *SAN, "-I" + os.path.join(ROOT, "jefferson-2.0_amd", "csrc"),
+          os.path.join(ROOT, "tests", "san", "report_san_driver.cpp"), "-o", exe])
+    out = _run([exe], env=ENV)
+    assert "\n0 failed checks" in out
+
+
 @pytest.mark.skipif(not _have_sanitizers("gcc"), reason="gcc with libasan/libubsan not available")
 def test_oracle_under_asan_and_ubsan():
     build = os.path.join(ROOT, "tests", "build")
