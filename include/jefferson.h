@@ -1127,7 +1127,7 @@ int jf_source_level_gains(jf_engine *e, int n_blocks, float *out /* [n_sources][
  * runs behind gate_scan_kernel.  An engine in which no bus has far > 0 allocates nothing for ranges, launches
  * exactly what it launched and renders the same bits.
  *
- * Not offered: a directivity cone per talker; a range per (listener, talker) pair; ranking by distance-weighted level;
+ * Not offered: a range per (listener, talker) pair; ranking by distance-weighted level;
  * range-gated room sends; a curve other than the linear ramp; a replacement of the built-in distance law; ranges inside the
  * one-launch real-time kernel; jefferson_group.h, jf_render and jf_ctest have no option for it.
  */
@@ -1218,8 +1218,9 @@ int jf_position_from_world(const float pose[7], float x, float y, float z, float
  *   source.  jf_process_batch_objects and jf_batch_upload_objects are with the batch calls below.
  * On every refusal nothing changes.
  *
- * Not offered: jefferson_group.h, jf_render and jf_ctest have no option for objects; a listener whose head centre follows an
- * object (set the pose and the object from the same coordinates); a batch call that mixes attached and unattached sources.
+ * Not offered: jefferson_group.h, jf_render and jf_ctest have no option for objects; a batch call that mixes attached and
+ * unattached sources.  (A listener that follows an object, and an orientation per object, are "talker cones and heads that
+ * follow objects" below.)
  */
 #define JF_MAX_OBJECTS 65536
 int jf_engine_set_objects(jf_engine *e, int n_objects);
@@ -1228,6 +1229,82 @@ int jf_source_set_object(jf_engine *e, int src, int obj);
 int jf_source_object(const jf_engine *e, int src);
 int jf_object_set_world(jf_engine *e, int obj, float x, float y, float z);
 int jf_object_get_world(const jf_engine *e, int obj, float out[3]);
+
+/* ---- talker cones and heads that follow objects: an orientation per object ---------- */
+
+/*
+ * The reference's SoundSource is a point without a facing (SoundSource::updateFromCartesian, SoundSource.cu:20-36), heard at
+ * the level its signal has (the callback's pause switch Audio.cu:98 and its mixing loop Audio.cu:109-113 are all the gain there
+ * is).  In a room of participants each of them is a talker AND a listener: one head, with a mouth and two ears.  Here an object
+ * carries an ORIENTATION beside its position, the listener of a bus may FOLLOW an object, and an object may carry a CONE.
+ *
+ * OBJECT POSES.  jf_object_set_pose(e, obj, position[3], orientation[4] = {qw, qx, qy, qz}) / jf_object_get_pose(e, obj,
+ *   out[7]): jf_listener_set_pose's conventions -- a unit quaternion from head frame to world frame, ahead = -z -- and its
+ *   refusals (JF_ERR_ARG: a bad index, NULL, a non-finite value, a norm further than 1e-3 from 1).  The orientation is the
+ *   identity until it is set; jf_object_set_world keeps it; jf_engine_set_objects keeps those of the objects that remain.
+ *   Setters like jf_object_set_world: callable from another thread, latched at the next block boundary.
+ *
+ * FOLLOWING LISTENERS.  jf_listener_follow_object(e, bus, obj): from the next block on the pose of the bus's listener IS the
+ *   object's pose, position and orientation, at every block -- moving one avatar moves its mouth and its ears.  obj < 0
+ *   detaches: the bus keeps the pose the object holds at that moment, nothing jumps.  jf_listener_object: the object, -1 for
+ *   none (and for a bad index).  jf_listener_set_pose on a following bus detaches it first, then acts as it always does;
+ *   jf_listener_get_pose on a following bus reads the object's pose.  jf_engine_set_objects refuses (JF_ERR_STATE) to remove an
+ *   object a bus follows; jf_engine_set_buses keeps the follows of the buses that remain.  JF_ERR_ARG for a bad bus or
+ *   obj >= n_objects.
+ *   Per-block calls: the host's snapshot uses the followed object's pose -- nothing new runs on the GPU, the one-launch
+ *   real-time kernel stays, and the call renders bit for bit what it renders when the host sets that pose itself.
+ *   Batch calls: jf_process_batch_poses and jf_batch_upload_object_poses (with the batch calls below) take a pose per (block,
+ *   object).  jf_process_batch_objects and jf_batch_upload_objects keep working when a bus follows, under ONE rule: what a call
+ *   does not bring is the latched value, held for all the call's blocks.  Those calls bring positions; the orientations are the
+ *   ones latched WHEN THE TRAJECTORY IS UPLOADED (jf_process_batch_objects: when it is called; jf_batch_upload_objects: then,
+ *   not at a later jf_batch_run) -- one moment for the records and for the cones, whether or not a bus follows; a following bus
+ *   reads {position from the call, latched orientation} of its object, and its row of `poses` is ignored (not even checked).  The records are then formed by pose_follow_kernel (csrc/jf_follow.hip) from the arrays as they are given.
+ *
+ * CONES.  The cone of OpenAL and WebAudio: someone who turns their back on you gets quieter.
+ *   jf_object_set_cone(e, obj, inner_deg, outer_deg, outer_gain) / jf_object_cone.  Accepted: finite values with 0 <= inner <=
+ *   outer <= 360 and 0 <= outer_gain <= 1 (JF_ERR_ARG otherwise, and for a bad index or NULL); {360, 360, 1}, the default,
+ *   means none.
+ *   THE RULE (csrc/jf_cone_rule.h; double arithmetic on the floats, sqrt the only libm call, one rounding to float, never
+ *   fused).  For block k and source s attached to object o, on a bus whose listener's head centre is c (a following bus: the
+ *   followed object's position): v = c - p_o, f = R(q_o) (0, 0, -1), theta = atan2(|f x v|, f . v) in degrees (the pose rule's
+ *   arctangent), a = inner / 2, b = outer / 2;  d = 1 for v == 0 and for theta <= a;  d = outer_gain for !(theta < b);
+ *   d = 1 + (outer_gain - 1) (theta - a) / (b - a) between.  d = 1 for a source that is not attached to an object and for an
+ *   object with the default cone.
+ *   The gain stage sees (g h) d, in that association -- g the source's gain as the gates left it, h the hearing range's factor
+ *   -- and (g_prev h_prev) d_prev for the block before the run; d_prev is 1 at the start and after jf_source_reset,
+ *   jf_source_set_signal and jf_source_set_live.  d is reached at the END of its block (kernels.cu:132-137), so nothing steps.
+ *   A talker with outer_gain 0 who faces away is skipped by the spatialiser.  The cone acts AHEAD of the voice limits
+ *   (jf_bus_set_voices): a talker it silences takes no place; the ranking and the leveller keep reading the raw level; room
+ *   sends stay pre-fader.
+ *   Where the poses come from: a per-block call and jf_process_batch read the latched poses; jf_process_batch_objects the
+ *   positions and listener poses of the call and the latched orientations; jf_process_batch_poses all of the call's;
+ *   jf_process_batch_world places every source by itself -- no source is attached for the call, every d is 1.
+ * jf_source_cone_gains(e, n_blocks, out): of the LAST RENDERED CALL, out[n_sources][n_blocks] = d[k]; it travels like
+ *   jf_source_range_gains (input meters on and some object with a cone; JF_ERR_STATE otherwise or when nothing was rendered
+ *   so; JF_ERR_ARG for another n_blocks than the call had).
+ * jf_cone_gain(inner, outer, outer_gain, talker_pose[7], listener_centre[3], d_out): the rule without an engine, the host twin
+ *   of the GPU's kernel.  JF_ERR_ARG for a NULL, a cone or a pose the setters would refuse; *d_out is then untouched.
+ * JF_ERR_STATE for a cone while a jf_reverb_set_ir response is set, and for jf_reverb_set_ir while an object has one.  On every
+ *   refusal nothing changes.
+ *
+ * COST.  An engine is ACTIVE for cones while some object's cone is not the default; it then counts as active for the voice
+ * gates (above) and per-block calls take the batch pipeline with one block -- exactly the hearing range's behaviour.  One
+ * launch, cone_gain_kernel, a lane per (block, source), behind range_gain_kernel.  An engine that never sets an
+ * orientation, a follow or a cone allocates nothing for them, launches what it launched and renders the same bits.
+ *
+ * Not offered: cones for sources that are not attached to an object; frequency-dependent directivity; a head offset between
+ * the object and the ears; cones in the one-launch real-time kernel; cones, follows and object poses in jefferson_group.h,
+ * jf_render and jf_ctest.
+ */
+int jf_object_set_pose(jf_engine *e, int obj, const float position[3], const float orientation[4]);
+int jf_object_get_pose(const jf_engine *e, int obj, float out[7]);
+int jf_listener_follow_object(jf_engine *e, int bus, int obj);
+int jf_listener_object(const jf_engine *e, int bus);
+int jf_object_set_cone(jf_engine *e, int obj, float inner_deg, float outer_deg, float outer_gain);
+int jf_object_cone(const jf_engine *e, int obj, float *inner_deg, float *outer_deg, float *outer_gain);
+int jf_source_cone_gains(jf_engine *e, int n_blocks, float *out /* [n_sources][n_blocks] */);
+int jf_cone_gain(float inner_deg, float outer_deg, float outer_gain, const float talker_pose[7], const float listener_centre[3],
+                 float *d_out);
 
 /* ---- convolution reverb -------------------------------- */
 
@@ -1306,6 +1383,24 @@ int jf_batch_upload_world(jf_engine *e, int total_blocks, const float *world, co
  */
 int jf_process_batch_objects(jf_engine *e, int n_blocks, const float *in, const float *objects, const float *poses, float *out_mix);
 int jf_batch_upload_objects(jf_engine *e, int total_blocks, const float *objects, const float *poses);
+
+/*
+ * callback_func (Audio.cu:94-163) n_blocks times for objects that move AND turn, heard by listeners that may be objects
+ * themselves (see "talker cones and heads that follow objects" above; SoundSource.cu:20-36): object_poses is [n_blocks]
+ * [n_objects][7], a pose per object and block; listener_poses [n_blocks][n_buses][7] as for jf_process_batch_objects, or NULL.
+ * listener_poses may be NULL only when every bus follows an object (JF_ERR_ARG otherwise); where it is not NULL, the row of a
+ * following bus is ignored.  The records are formed ON THE GPU (pose_follow_kernel): record (k, s) = the rule of L(k, bus of s)
+ * and the position of the object of s at k, L being the followed object's pose for a following bus and the listener's row
+ * otherwise.  THE CONTRACT: the call renders bit for bit what jf_process_batch_objects renders when given objects[k][o] = the
+ * positions and poses[k][b] = the resolved listener poses.  Everything else -- in, out_mix, every source attached, the refusals
+ * -- is jf_process_batch_objects'; a cone (jf_object_set_cone) reads the call's orientations.
+ * Afterwards every object stands at the last block's pose, every listener that follows nothing at the last block's row, and the
+ * sources' latched records are the last block's, as after jf_process_batch_objects.
+ * jf_batch_upload_object_poses is jf_batch_upload_objects for such a trajectory, with exactly its rules.
+ */
+int jf_process_batch_poses(jf_engine *e, int n_blocks, const float *in, const float *object_poses, const float *listener_poses,
+                           float *out_mix);
+int jf_batch_upload_object_poses(jf_engine *e, int total_blocks, const float *object_poses, const float *listener_poses);
 
 /*
  * Device-resident form of the same loop of callbacks (Audio.cu:104-117; jf_synchronize is its

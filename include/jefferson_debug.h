@@ -351,6 +351,25 @@ long long jf_debug_range_bytes(const jf_engine *e);
  * range. */
 int jf_profile_read_range(jf_engine *e, double *range_ms);
 
+/* Talker cones (include/jefferson.h): the rule cone_gain_kernel applies to one run, on the host -- the header the
+ * kernel compiles (csrc/jf_cone_rule.h), so the CPU suite checks it against a NumPy model.  object_poses [n_blocks][n_objects]
+ * [7] and listener_poses [n_blocks][n_buses][7] are the run's poses; par [3][n_sources] is inner, outer, outer_gain per SOURCE as
+ * the engine resolves them ({360, 360, 1} for a source without a cone); object_of, bus and follow [n_sources] are the source's
+ * object (-1: none, d = 1), its bus, and the object the listener of that bus follows (-1: the bus's own row of listener_poses);
+ * d_prev_io [n_sources] is the state before the run and, on return, after it (1 for a source that starts; n_blocks == 0 leaves
+ * it); d_out [n_blocks][n_sources] receives d.  What the gain stage then sees is g[k][s] d[k][s] and g[-1][s] d_prev[s].  Pure
+ * host code: no engine, no GPU.  JF_ERR_ARG for a NULL pointer, a negative n_blocks, a count that is not positive, an index out
+ * of range or a cone the setter would refuse; nothing is written then. */
+int jf_debug_cone_scan(const float *object_poses, const float *listener_poses, int n_blocks, int n_sources, int n_objects, int n_buses,
+                       const float *par, const int *object_of, const int *bus, const int *follow, float *d_prev_io, float *d_out);
+/* jf_debug_cone_bytes: bytes of device and pinned memory the engine holds for cones -- the parameter and map planes, the state's
+ * two, a run's d and where it lands on the host, the latched poses.  0 in an engine in which no processing call was ever
+ * latched with a cone; they stay when the last cone goes. */
+long long jf_debug_cone_bytes(const jf_engine *e);
+/* ms in cone_gain_kernel since jf_profile_enable(e, 2), the event pair's own ~7 us per run included; 0 while no object had a
+ * cone. */
+int jf_profile_read_cone(jf_engine *e, double *cone_ms);
+
 /* Stream sources (include/jefferson.h).  jf_debug_stream_seek: the stream source's next output is t_out (up to
  * 2^53); the queue is dropped, the history is zeros and the next push is frame i(t_out - 1) + 1 of the stream -- what a stream
  * that has run for t_out samples and has been fed zeros so far looks like (positions beyond 2^31 without hours of audio).

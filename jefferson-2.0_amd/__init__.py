@@ -198,6 +198,19 @@ _SIGS = {
     "jf_debug_range_scan": (C.c_int, [_f, C.c_int, C.c_int, _f, _f, _f]),
     "jf_profile_read_range": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "jf_debug_range_bytes": (C.c_longlong, [C.c_void_p]),
+    "jf_object_set_pose": (C.c_int, [C.c_void_p, C.c_int, _f, _f]),
+    "jf_object_get_pose": (C.c_int, [C.c_void_p, C.c_int, _f]),
+    "jf_listener_follow_object": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "jf_listener_object": (C.c_int, [C.c_void_p, C.c_int]),
+    "jf_object_set_cone": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float]),
+    "jf_object_cone": (C.c_int, [C.c_void_p, C.c_int, _f, _f, _f]),
+    "jf_source_cone_gains": (C.c_int, [C.c_void_p, C.c_int, _f]),
+    "jf_cone_gain": (C.c_int, [C.c_float, C.c_float, C.c_float, _f, _f, _f]),
+    "jf_process_batch_poses": (C.c_int, [C.c_void_p, C.c_int, _f, _f, _f, _f]),
+    "jf_batch_upload_object_poses": (C.c_int, [C.c_void_p, C.c_int, _f, _f]),
+    "jf_debug_cone_scan": (C.c_int, [_f, _f, C.c_int, C.c_int, C.c_int, C.c_int, _f, _i, _i, _i, _f, _f]),
+    "jf_debug_cone_bytes": (C.c_longlong, [C.c_void_p]),
+    "jf_profile_read_cone": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "jf_engine_add_hrtf_set": (C.c_int, [C.c_void_p, _f, C.c_int]),
     "jf_engine_add_hrtf_sofa": (C.c_int, [C.c_void_p, C.c_char_p, C.c_float]),
     "jf_num_hrtf_sets": (C.c_int, [C.c_void_p]),
@@ -642,6 +655,38 @@ def range_scan(pos, near, far, h_prev=None):
     rc = lib().jf_debug_range_scan(_fp(pos), K, S, _fp(par), _fp(st), _fp(out))
     if rc:
         raise JfError(rc, "range_scan")
+    return out[:K], st
+
+
+def cone_gain(inner, outer, outer_gain, talker_pose, listener_centre):
+    """jf_cone_gain (host logic only): how much of a talker at talker_pose {x, y, z, qw, qx, qy, qz} with the cone {inner,
+    outer, outer_gain} (degrees, degrees, gain) is heard from listener_centre -> float32; JfError for a cone or a pose the
+    setters would refuse"""
+    tp = np.ascontiguousarray(talker_pose, np.float32).reshape(7)
+    c = np.ascontiguousarray(listener_centre, np.float32).reshape(3)
+    out = np.zeros(1, np.float32)
+    rc = lib().jf_cone_gain(float(inner), float(outer), float(outer_gain), _fp(tp), _fp(c), _fp(out))
+    if rc:
+        raise JfError(rc, "cone_gain")
+    return out[0]
+
+
+def cone_scan(object_poses, listener_poses, par, object_of, bus, follow, d_prev=None):
+    """jf_debug_cone_scan (host logic only): the cone rule over one run.  object_poses [K][n_obj][7], listener_poses
+    [K][n_buses][7]; par [3][S] inner, outer, outer_gain per source; object_of, bus, follow [S] (follow: the object the listener
+    of the source's bus follows, -1: none); d_prev [S] (ones) -> (d [K][S] float32, d_prev after the run)"""
+    op = np.ascontiguousarray(object_poses, np.float32)
+    lp = np.ascontiguousarray(listener_poses, np.float32)
+    K, no, nb = op.shape[0], op.shape[1], lp.shape[1]
+    par = np.ascontiguousarray(par, np.float32)
+    S = par.shape[1]
+    assert op.shape == (K, no, 7) and lp.shape == (K, nb, 7) and par.shape == (3, S)
+    m = [np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.int32), (S,)), np.int32) for a in (object_of, bus, follow)]
+    st = np.ones(S, np.float32) if d_prev is None else np.array(d_prev, np.float32).reshape(S).copy()
+    out = np.zeros((max(K, 1), S), np.float32)
+    rc = lib().jf_debug_cone_scan(_fp(op), _fp(lp), K, S, no, nb, _fp(par), _ip(m[0]), _ip(m[1]), _ip(m[2]), _fp(st), _fp(out))
+    if rc:
+        raise JfError(rc, "cone_scan")
     return out[:K], st
 
 
@@ -1564,6 +1609,79 @@ class Engine:
         """upload_world for a trajectory of object positions and poses (jf_batch_upload_objects)"""
         K, objects, poses = self._object_args(objects, poses)
         self._chk(lib().jf_batch_upload_objects(self.h, K, _fp(objects), _fp(poses)))
+
+    # ---- object poses, following listeners, talker cones (include/jefferson.h: "talker cones and heads that follow objects") ----
+    def set_object_pose(self, obj, position, orientation):
+        """object obj at `position`, facing along the unit quaternion `orientation` {qw, qx, qy, qz} (jf_object_set_pose)"""
+        p = np.ascontiguousarray(position, np.float32)
+        q = np.ascontiguousarray(orientation, np.float32)
+        assert p.shape == (3,) and q.shape == (4,)
+        self._chk(lib().jf_object_set_pose(self.h, int(obj), _fp(p), _fp(q)))
+
+    def object_pose(self, obj):
+        o = np.zeros(7, np.float32)
+        self._chk(lib().jf_object_get_pose(self.h, int(obj), _fp(o)))
+        return o
+
+    def follow_object(self, bus, obj):
+        """the listener of `bus` is object obj from the next block on; obj < 0 detaches (jf_listener_follow_object)"""
+        self._chk(lib().jf_listener_follow_object(self.h, int(bus), int(obj)))
+
+    def listener_object(self, bus):
+        """the object the listener of `bus` follows, -1: none"""
+        return int(lib().jf_listener_object(self.h, int(bus)))
+
+    def set_cone(self, obj, inner, outer, outer_gain):
+        """object obj talks into a cone: full level within `inner` degrees, `outer_gain` beyond `outer` (jf_object_set_cone)"""
+        self._chk(lib().jf_object_set_cone(self.h, int(obj), float(inner), float(outer), float(outer_gain)))
+
+    def cone(self, obj):
+        """(inner, outer, outer_gain); (360, 360, 1) before anything was set (jf_object_cone)"""
+        a, b, c = (np.zeros(1, np.float32) for _ in range(3))
+        self._chk(lib().jf_object_cone(self.h, int(obj), _fp(a), _fp(b), _fp(c)))
+        return float(a[0]), float(b[0]), float(c[0])
+
+    def cone_gains(self, n_blocks=1):
+        """the last rendered call's cone gains d[k], [S][n_blocks] (jf_source_cone_gains)"""
+        out = np.zeros((self.S, int(n_blocks)), np.float32)
+        self._chk(lib().jf_source_cone_gains(self.h, int(n_blocks), _fp(out)))
+        return out
+
+    cone_scan = staticmethod(cone_scan)
+
+    def cone_bytes(self):
+        """device and pinned memory held for cones (0 until a call is latched with one)"""
+        return int(lib().jf_debug_cone_bytes(self.h))
+
+    def profile_read_cone(self):
+        """ms in cone_gain_kernel since profile_enable(2)"""
+        r = C.c_double(0.0)
+        self._chk(lib().jf_profile_read_cone(self.h, C.byref(r)))
+        return r.value
+
+    def _object_pose_args(self, object_poses, listener_poses):
+        object_poses = np.ascontiguousarray(object_poses, np.float32)
+        K = object_poses.shape[0]
+        assert object_poses.shape == (K, self.n_objects, 7), object_poses.shape
+        if listener_poses is not None:
+            listener_poses = np.ascontiguousarray(listener_poses, np.float32)
+            assert listener_poses.shape == (K, self.n_buses, 7), listener_poses.shape
+        return K, object_poses, listener_poses
+
+    def process_batch_poses(self, object_poses, listener_poses=None, inp=None):
+        """object_poses [K][n_objects][7], listener_poses [K][n_buses][7] or None (every bus follows an object) -> the mix of K
+        blocks (jf_process_batch_poses)"""
+        K, op, lp = self._object_pose_args(object_poses, listener_poses)
+        mix = self._out(K, 2 * self.B)
+        inp = None if inp is None else self._inp(inp, K * self.B)
+        self._chk(lib().jf_process_batch_poses(self.h, K, None if inp is None else _fp(inp), _fp(op), None if lp is None else _fp(lp),
+                                               _fp(mix)))
+        return mix
+
+    def upload_object_poses(self, object_poses, listener_poses=None):
+        """upload_objects for a trajectory of object poses (jf_batch_upload_object_poses)"""
+        K, op, lp = self._object_pose_args(object_poses, listener_poses)
+        self._chk(lib().jf_batch_upload_object_poses(self.h, K, _fp(op), None if lp is None else _fp(lp)))
 
     def pose_objects_device(self, bus, object_of, objects, poses):
         """pose_object_kernel alone: bus [S] (or None), object_of [S], objects [K][n_obj][3], poses [K][n_buses][7] -> records

@@ -89,7 +89,7 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
         ep = next_events(e, e->ev_prep);
         em = next_events(e, e->ev_mix);
         if (!ep || !em) return fail(e, JF_ERR_DEVICE, "hipEventCreate failed");
-        for (StageTimer *t : {&e->tm_spec, &e->tm_set, &e->tm_gain, &e->tm_master, &e->tm_gate, &e->vc.tm, &e->lv.tm, &e->rg.tm}) t->arm(e->ev_used);  // (the stage that runs says otherwise)
+        for (StageTimer *t : {&e->tm_spec, &e->tm_set, &e->tm_gain, &e->tm_master, &e->tm_gate, &e->vc.tm, &e->lv.tm, &e->rg.tm, &e->cn.tm}) t->arm(e->ev_used);  // (the stage that runs says otherwise)
     }
     const long long n_items = (long long)K * e->S;
     int G = 1;
@@ -141,6 +141,7 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
     // g_eff[k][s] = gate ? g[k][s] : 0 from the inputs' levels and the same gains, and desc_gain_kernel applies that
     e->last_gain = e->last_gate = false;
     if (e->gate_on) {
+        e->run_first_block = first_block;
         const int rc = run_gate_stage(e, d_pos, p, K, canon, timed);
         if (rc) return rc;
     } else if (e->gain_on) {
@@ -241,12 +242,6 @@ int run_blocks(jf_engine *e, const float *d_pos, int K, float *d_mix_out, int fi
     return submit_side(e);
 }
 
-// A listener's pose (the reference's fixed listener until jf_listener_set_pose says otherwise); under pos_mu
-static const float *pose_of(const jf_engine *e, int bus) {
-    static const float identity[kPoseFloats] = {0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f};
-    return e->pose.empty() ? identity : e->pose.data() + (size_t)kPoseFloats * bus;
-}
-
 // A world-placed source as the listener of its bus hears it now: the host twin of pose_kernel (jf_pose_rule.h); under pos_mu
 // (an attached source stands where its object stands: DESIGN.md 4.15)
 static const float *world_of(const jf_engine *e, int s) {
@@ -264,7 +259,9 @@ static void detach_object(jf_engine *e, int s) {
 
 static void place_world_source(jf_engine *e, int s) {
     const float *w = world_of(e, s);
-    const PoseRecord r = pose_rule(pose_of(e, e->bus.empty() ? 0 : e->bus[s]), w[0], w[1], w[2]);
+    float q[kPoseFloats];  // (the reference's fixed listener until jf_listener_set_pose says otherwise; a followed object's pose)
+    listener_pose(e, e->bus.empty() ? 0 : e->bus[s], q);
+    const PoseRecord r = pose_rule(q, w[0], w[1], w[2]);
     e->pos[s] = HostPos{r.ele, r.azi, sqrtf(r.x * r.x + r.y * r.y + r.z * r.z), r.x, r.y, r.z};
 }
 
@@ -420,7 +417,7 @@ void destroy_engine(jf_engine *e) {
     DeviceGuard bind(e);  // (outlives the delete: the buffers are freed on the engine's device)
     if (e->rv_side) (void)hipStreamSynchronize(e->rv_side);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
-    for (auto *pool : {&e->ev_prep, &e->ev_fused, &e->ev_mix, &e->ev_reverb, &e->ev_pose, &e->tm_spec.ev, &e->tm_gain.ev, &e->tm_master.ev, &e->tm_set.ev, &e->tm_gate.ev, &e->vc.tm.ev, &e->lv.tm.ev, &e->rg.tm.ev})
+    for (auto *pool : {&e->ev_prep, &e->ev_fused, &e->ev_mix, &e->ev_reverb, &e->ev_pose, &e->tm_spec.ev, &e->tm_gain.ev, &e->tm_master.ev, &e->tm_set.ev, &e->tm_gate.ev, &e->vc.tm.ev, &e->lv.tm.ev, &e->rg.tm.ev, &e->cn.tm.ev})
         for (auto &p : *pool) {
             (void)hipEventDestroy(p.a);
             (void)hipEventDestroy(p.b);
@@ -1114,6 +1111,7 @@ int jf_engine_set_buses(jf_engine *e, int n_buses) {
             for (size_t i = have; i < e->pose.size(); i += kPoseFloats) e->pose[i + 3] = 1.0f;
         }
         master_set_buses(e, n_buses);  // ... and their master sections, new ones are neutral
+        follow_set_buses(e, n_buses);  // ... and the objects they follow, new ones follow nothing
         voice_set_buses(e, n_buses);   // ... and their voice limits, new ones have none
         range_set_buses(e, n_buses);   // ... and their hearing ranges, new ones have none
         output_set_buses(e, n_buses);  // ... and their outputs, new ones have none
@@ -1209,6 +1207,7 @@ int jf_listener_set_pose(jf_engine *e, int bus, const float position[3], const f
         for (int b = 0; b < e->n_buses; b++) e->pose[(size_t)kPoseFloats * b + 3] = 1.0f;
     }
     std::copy(p, p + kPoseFloats, e->pose.begin() + (size_t)kPoseFloats * bus);
+    if (!e->follow.empty()) e->follow[bus] = -1;  // (a bus that followed an object is detached first)
     return JF_OK;
     });
 }
@@ -1219,8 +1218,7 @@ int jf_listener_get_pose(const jf_engine *e, int bus, float out[7]) {
     jf_engine *m = const_cast<jf_engine *>(e);
     std::lock_guard<std::mutex> lk(m->pos_mu);
     if (bus < 0 || bus >= e->n_buses) return JF_ERR_ARG;
-    const float *p = pose_of(e, bus);
-    std::copy(p, p + kPoseFloats, out);
+    listener_pose(e, bus, out);  // (a following bus: its object's pose)
     return JF_OK;
     });
 }
@@ -1279,6 +1277,9 @@ int jf_engine_set_objects(jf_engine *e, int n_objects) {
     std::lock_guard<std::mutex> lk(e->pos_mu);
     for (const int o : e->object_of)
         if (o >= n_objects) return fail(e, JF_ERR_STATE, "a source is attached to an object that would disappear");
+    for (const int o : e->follow)
+        if (o >= n_objects) return fail(e, JF_ERR_STATE, "a listener follows an object that would disappear");
+    cone_set_objects(e, n_objects);  // the objects that remain keep their orientations and cones
     e->object_world.resize(3 * (size_t)n_objects, 0.0f);  // the objects that remain keep their positions
     e->n_objects = n_objects;
     return JF_OK;
@@ -1416,6 +1417,7 @@ static int submit_block(jf_engine *e, const float *in, bool interleaved) {
     e->last_ingest = false;
     e->last_stream = false;
     e->last_pose = 0;
+    e->call_geo = 0;  // (a per-block call: the latched poses)
     if (e->paused.load(std::memory_order_relaxed)) {  // Audio.cu:101: nothing is consumed (live input is dropped), output is silence
         JF_HIP(e, hipMemsetAsync(e->d_mix, 0, sizeof(float) * 2 * e->B * e->n_buses, e->stream));
         e->own_mix_blocks = 0;  // (d_mix no longer holds the last jf_batch_run's blocks)
@@ -1658,6 +1660,9 @@ static int traj_begin(jf_engine *e, int total_blocks) {
     JF_HIP(e, hipStreamSynchronize(e->stream));
     e->traj_gen++;
     e->ahead.valid = false;
+    e->traj_geo = 0;  // (records, until an upload of world positions, objects or object poses says otherwise)
+    e->traj_follow = false;
+    e->traj_dgeo = {};
     if (total_blocks > e->traj_blocks) {
         e->d_traj.reset();  // (before the larger one is allocated: the two never exist side by side)
         e->traj_blocks = 0;
@@ -1740,16 +1745,54 @@ static void twin_records(const jf_engine *e, const WorldPoints &pt, const float 
     }
 }
 
+// ... where the listener of a bus may be an object (pose_follow_kernel's twin): g holds host pointers, fsrc [S] per source the
+// object its bus's listener follows (-1: the bus's own row of g.lis)
+static void follow_pose(const jf_engine *e, const ConeGeometry &g, const int *fsrc, size_t k, int s, float out[kPoseFloats]) {
+    const int fo = fsrc[s];
+    if (fo >= 0) {
+        const float *c = g.obj_pos + k * (size_t)g.pos_stride + (size_t)fo * g.pos_pitch;
+        const float *q = g.obj_ori + k * (size_t)g.ori_stride + (size_t)fo * g.ori_pitch;
+        std::copy(c, c + 3, out);
+        std::copy(q, q + 4, out + 3);
+    } else {
+        const float *l = g.lis + k * (size_t)g.lis_stride + (size_t)kPoseFloats * (e->n_buses > 1 ? e->bus[s] : 0);
+        std::copy(l, l + kPoseFloats, out);
+    }
+}
+static void twin_records_follow(const jf_engine *e, const ConeGeometry &g, size_t k, float *rec) {
+    for (int s = 0; s < e->S; s++) {
+        float q[kPoseFloats];
+        follow_pose(e, g, e->follow_src_dev.data(), k, s, q);
+        const float *w = g.obj_pos + k * (size_t)g.pos_stride + (size_t)e->object_of_dev[s] * g.pos_pitch;
+        const PoseRecord r = pose_rule(q, w[0], w[1], w[2]);
+        float *d = rec + 5 * (size_t)s;
+        d[0] = r.ele;
+        d[1] = r.azi;
+        d[2] = r.x;
+        d[3] = r.y;
+        d[4] = r.z;
+    }
+}
+
 // jf_batch_upload_world / jf_batch_upload_objects: the trajectory formed ON THE DEVICE (pose_kernel / pose_object_kernel into
 // d_traj) from points -- world[K][S][3], or (by_object) objects[K][n_objects][3] -- and poses[K][n_buses][7].
 // Everything is checked on the host before anything is launched.
-static int upload_world(jf_engine *e, int total_blocks, const float *points, const float *poses, bool by_object) {
+// kind: 1 world positions, 2 objects, 3 object POSES -- points is then object_poses[K][n_objects][7], and poses (the listeners')
+// may be null while every bus follows an object (jf_batch_upload_object_poses).  Where a bus follows an object, or the call
+// brings orientations, pose_follow_kernel (jf_follow.hip) forms the records: positions and orientations as separate arrays
+// with their own strides, what the call does not bring being the latched value for every block.
+static int upload_world(jf_engine *e, int total_blocks, const float *points, const float *poses, int kind) {
     return jf_guard([&]() -> int {
     DeviceGuard bind(e);
-    if (!e || total_blocks <= 0 || !points || !poses) return fail(e, JF_ERR_ARG, "bad world trajectory");
+    const bool by_object = kind >= 2;
+    if (!e || total_blocks <= 0 || !points || (!poses && kind != 3)) return fail(e, JF_ERR_ARG, "bad world trajectory");
     const size_t S = (size_t)e->S, nb = (size_t)e->n_buses, K = (size_t)total_blocks;
     if (K * S > (size_t)0x7fffffff / 8) return fail(e, JF_ERR_ARG, "too many records for one call");
     std::vector<int> map;  // by_object: the sources' objects as the call finds them
+    std::vector<int> fsrc;  // ... and per source the object its bus's listener follows
+    std::vector<char> bus_follows(nb, 0);
+    std::vector<float> ori;  // an objects call with a follow: the latched orientations
+    bool follows = false;
     size_t n_pt = S;
     if (by_object) {
         std::lock_guard<std::mutex> lk(e->pos_mu);
@@ -1759,8 +1802,36 @@ static int upload_world(jf_engine *e, int total_blocks, const float *points, con
             if (e->object_of.empty() || e->object_of[s2] < 0)
                 return fail(e, JF_ERR_STATE, "source " + std::to_string(s2) + " is not attached to an object: an objects call takes every source attached");
         map = e->object_of;
+        fsrc.assign(S, -1);
+        for (size_t u = 0; u < nb; u++) bus_follows[u] = follow_of(e, (int)u) >= 0;
+        for (size_t s2 = 0; s2 < S; s2++) {
+            fsrc[s2] = follow_of(e, nb > 1 ? e->bus[s2] : 0);
+            follows = follows || fsrc[s2] >= 0;
+        }
+        if (kind == 2 && (follows || !e->object_quat.empty())) {  // (empty: every orientation is the identity)
+            ori.resize(4 * n_pt);
+            for (size_t o = 0; o < n_pt; o++) std::copy(object_quat_of(e, (int)o), object_quat_of(e, (int)o) + 4, ori.begin() + 4 * o);
+        }
     }
-    if (!world_args_ok(points, K * n_pt, poses, K * nb)) return fail(e, JF_ERR_ARG, kPoseArgMsg);
+    const bool fk = kind == 3 || follows;  // pose_follow_kernel forms the records
+    const size_t pt_floats = kind == 3 ? (size_t)kPoseFloats : 3;
+    if (!poses)
+        for (size_t u = 0; u < nb; u++)
+            if (!bus_follows[u]) return fail(e, JF_ERR_ARG, "listener_poses may be NULL only when every bus follows an object");
+    if (kind == 3) {
+        bool ok = true;
+        for (size_t i = 0; i < K * n_pt && ok; i++) ok = pose_valid(points + kPoseFloats * i);
+        for (size_t k = 0; poses && k < K && ok; k++)  // (the row of a following bus is ignored)
+            for (size_t u = 0; u < nb && ok; u++) ok = bus_follows[u] || pose_valid(poses + kPoseFloats * (k * nb + u));
+        if (!ok) return fail(e, JF_ERR_ARG, kPoseArgMsg);
+    } else if (follows) {  // (an objects call with a following bus: its row of poses is ignored here as well)
+        bool ok = world_args_ok(points, K * n_pt, poses, 0);
+        for (size_t k = 0; k < K && ok; k++)
+            for (size_t u = 0; u < nb && ok; u++) ok = bus_follows[u] || pose_valid(poses + kPoseFloats * (k * nb + u));
+        if (!ok) return fail(e, JF_ERR_ARG, kPoseArgMsg);
+    } else if (!world_args_ok(points, K * n_pt, poses, K * nb)) {
+        return fail(e, JF_ERR_ARG, kPoseArgMsg);
+    }
     {
         const int rc = traj_begin(e, total_blocks);
         if (rc) return rc;
@@ -1771,13 +1842,13 @@ static int upload_world(jf_engine *e, int total_blocks, const float *points, con
         JF_HIP(e, e->d_world.alloc(K * S * 3));
         e->pose_cap_blocks = total_blocks;
     }
-    if (by_object && K * n_pt * 3 > e->object_cap_floats) {
+    if (by_object && K * n_pt * pt_floats > e->object_cap_floats) {
         e->d_objects.reset();
         e->object_cap_floats = 0;
-        JF_HIP(e, e->d_objects.alloc(K * n_pt * 3));
-        e->object_cap_floats = K * n_pt * 3;
+        JF_HIP(e, e->d_objects.alloc(K * n_pt * pt_floats));
+        e->object_cap_floats = K * n_pt * pt_floats;
     }
-    if (K * nb * kPoseFloats > e->pose_cap_floats) {
+    if (poses && K * nb * kPoseFloats > e->pose_cap_floats) {
         e->d_poses.reset();
         e->pose_cap_floats = 0;
         JF_HIP(e, e->d_poses.alloc(K * nb * kPoseFloats));
@@ -1794,9 +1865,47 @@ static int upload_world(jf_engine *e, int total_blocks, const float *points, con
         JF_HIP(e, h2d(e, e->d_object_of, map.data(), sizeof(int) * S));  // (map is a temporary: landed when this returns)
         e->object_of_dev = map;
     }
+    if (fk && fsrc != e->follow_src_dev) {
+        if (!e->d_follow_src) JF_HIP(e, e->d_follow_src.alloc(S));
+        e->follow_src_dev.clear();
+        JF_HIP(e, h2d(e, e->d_follow_src, fsrc.data(), sizeof(int) * S));
+        e->follow_src_dev = fsrc;
+    }
+    if (fk && kind == 2 && ori != e->objects_ori_dev) {
+        if (ori.size() != e->objects_ori_dev.size()) {
+            e->objects_ori_dev.clear();
+            e->d_objects_ori.reset();
+            JF_HIP(e, e->d_objects_ori.alloc(ori.size()));
+        }
+        e->objects_ori_dev.clear();
+        JF_HIP(e, h2d(e, e->d_objects_ori, ori.data(), sizeof(float) * ori.size()));
+        e->objects_ori_dev = ori;
+    }
     float *d_points = by_object ? e->d_objects.p : e->d_world.p;
-    JF_HIP(e, hipMemcpyAsync(d_points, points, sizeof(float) * K * n_pt * 3, hipMemcpyHostToDevice, e->stream));
-    JF_HIP(e, hipMemcpyAsync(e->d_poses, poses, sizeof(float) * K * nb * kPoseFloats, hipMemcpyHostToDevice, e->stream));
+    JF_HIP(e, hipMemcpyAsync(d_points, points, sizeof(float) * K * n_pt * pt_floats, hipMemcpyHostToDevice, e->stream));
+    if (poses) JF_HIP(e, hipMemcpyAsync(e->d_poses, poses, sizeof(float) * K * nb * kPoseFloats, hipMemcpyHostToDevice, e->stream));
+    // where the call's poses lie, on the device and (the caller's arrays) on the host
+    ConeGeometry dg = {}, hg = {};
+    if (by_object) {
+        dg.obj_pos = d_points;
+        hg.obj_pos = points;
+        dg.pos_pitch = hg.pos_pitch = (int)pt_floats;
+        dg.pos_stride = hg.pos_stride = (int)(n_pt * pt_floats);
+        if (kind == 3) {
+            dg.obj_ori = d_points + 3;
+            hg.obj_ori = points + 3;
+            dg.ori_pitch = hg.ori_pitch = kPoseFloats;
+            dg.ori_stride = hg.ori_stride = (int)(n_pt * kPoseFloats);
+        } else if (fk) {
+            dg.obj_ori = e->d_objects_ori.p;
+            dg.ori_pitch = hg.ori_pitch = 4;
+        }
+        if (kind == 2) e->traj_ori = ori;  // the orientations an objects trajectory was uploaded with: its records' and its cones'
+        if (kind == 2 && fk) hg.obj_ori = e->traj_ori.data();
+        dg.lis = poses ? e->d_poses.p : nullptr;
+        hg.lis = poses;
+        dg.lis_stride = hg.lis_stride = (int)(nb * kPoseFloats);
+    }
     const bool timed = e->profiling >= 2;
     if (timed && e->ev_pose.empty()) {
         EventPair q;
@@ -1805,7 +1914,9 @@ static int upload_world(jf_engine *e, int total_blocks, const float *points, con
     }
     if (timed) JF_HIP(e, hipEventRecord(e->ev_pose[0].a, e->stream));
     const int *d_bus = nb > 1 ? e->d_pose_bus.p : nullptr;
-    if (by_object)
+    if (fk)
+        JF_HIP(e, launch_pose_follow(dg, e->d_object_of, d_bus, e->d_follow_src, e->d_traj, e->S, total_blocks, e->n_buses, (int)n_pt, e->stream));
+    else if (by_object)
         JF_HIP(e, launch_pose_objects(d_points, e->d_object_of, d_bus, e->d_poses, e->d_traj, e->S, total_blocks, e->n_buses, (int)n_pt,
                                       e->stream));
     else
@@ -1816,7 +1927,26 @@ static int upload_world(jf_engine *e, int total_blocks, const float *points, con
     // (jf_engine::interp_use; a source that moves within its whole degrees is counted as moving)
     const WorldPoints pt = world_points(e, points, by_object);
     e->traj_moved.assign(K + 1, 0u);
-    if (e->interp_avail) {
+    if (e->interp_avail && fk) {  // (the listener's pose is resolved per source: its own row, or the object it follows)
+        std::vector<char> turned(nb), moved(n_pt);  // per block: the bus's listener has another pose, the object stands or faces elsewhere
+        std::vector<int> fbus(nb, -1);
+        for (size_t s2 = 0; s2 < S; s2++) fbus[nb > 1 ? (size_t)e->bus[s2] : 0] = fsrc[s2];
+        for (size_t b = 1; b < K; b++) {
+            for (size_t o = 0; o < n_pt; o++) {
+                const float *w1 = hg.obj_pos + b * (size_t)hg.pos_stride + o * hg.pos_pitch, *w0 = w1 - hg.pos_stride;
+                const float *r1 = hg.obj_ori + b * (size_t)hg.ori_stride + o * hg.ori_pitch, *r0 = r1 - hg.ori_stride;
+                moved[o] = (memcmp(w1, w0, sizeof(float) * 3) != 0) | ((memcmp(r1, r0, sizeof(float) * 4) != 0) << 1);
+            }
+            for (size_t u = 0; u < nb; u++) {
+                const float *q1 = hg.lis ? hg.lis + b * (size_t)hg.lis_stride + u * kPoseFloats : nullptr;
+                turned[u] = fbus[u] >= 0 ? moved[(size_t)fbus[u]] != 0  // (a bus no source is on reads nothing)
+                                         : q1 != nullptr && memcmp(q1, q1 - hg.lis_stride, sizeof(float) * kPoseFloats) != 0;
+            }
+            unsigned n = 0;
+            for (size_t s2 = 0; s2 < S; s2++) n += turned[nb > 1 ? (size_t)e->bus[s2] : 0] || (moved[(size_t)map[s2]] & 1);
+            e->traj_moved[b + 1] = e->traj_moved[b] + n;
+        }
+    } else if (e->interp_avail) {
         std::vector<char> turned(nb);
         for (size_t b = 1; b < K; b++) {
             const float *q1 = poses + b * nb * kPoseFloats, *q0 = q1 - nb * kPoseFloats;
@@ -1834,7 +1964,10 @@ static int upload_world(jf_engine *e, int total_blocks, const float *points, con
     }
     // ... and block 0's records by the host twin: the sort key of automatic grouping
     std::vector<float> first(5 * S);
-    twin_records(e, pt, poses, 0, first.data());
+    if (fk)
+        twin_records_follow(e, hg, 0, first.data());
+    else
+        twin_records(e, pt, poses, 0, first.data());
     JF_HIP(e, hipStreamSynchronize(e->stream));  // (the caller's arrays are free again; form_order wants the stream idle)
     if (timed) {
         float ms = 0.0f;
@@ -1842,7 +1975,13 @@ static int upload_world(jf_engine *e, int total_blocks, const float *points, con
         e->pose_ms += ms;
         e->pose_launches++;
     }
-    e->last_pose = by_object ? 2 : 1;
+    e->last_pose = fk ? 3 : by_object ? 2 : 1;
+    e->traj_geo = kind;
+    e->traj_follow = fk;
+    e->traj_dgeo = dg;
+    e->traj_hgeo = hg;
+    e->traj_n_objects = by_object ? (int)n_pt : 0;
+    e->traj_n_buses = e->n_buses;
     return traj_order(e, first.data());
     });
 }
@@ -1878,13 +2017,19 @@ int jf_batch_upload_positions(jf_engine *e, int total_blocks, const float *posit
 int jf_batch_upload_world(jf_engine *e, int total_blocks, const float *world, const float *poses) {
     if (e && e->n_live > 0) return jf_guard([&]() -> int { return fail(e, JF_ERR_STATE, kLiveResidentMsg); });
     if (e && e->n_stream > 0) return jf_guard([&]() -> int { return fail(e, JF_ERR_STATE, kStreamResidentMsg); });
-    return upload_world(e, total_blocks, world, poses, false);
+    return upload_world(e, total_blocks, world, poses, 1);
 }
 
 int jf_batch_upload_objects(jf_engine *e, int total_blocks, const float *objects, const float *poses) {
     if (e && e->n_live > 0) return jf_guard([&]() -> int { return fail(e, JF_ERR_STATE, kLiveResidentMsg); });
     if (e && e->n_stream > 0) return jf_guard([&]() -> int { return fail(e, JF_ERR_STATE, kStreamResidentMsg); });
-    return upload_world(e, total_blocks, objects, poses, true);
+    return upload_world(e, total_blocks, objects, poses, 2);
+}
+
+int jf_batch_upload_object_poses(jf_engine *e, int total_blocks, const float *object_poses, const float *listener_poses) {
+    if (e && e->n_live > 0) return jf_guard([&]() -> int { return fail(e, JF_ERR_STATE, kLiveResidentMsg); });
+    if (e && e->n_stream > 0) return jf_guard([&]() -> int { return fail(e, JF_ERR_STATE, kStreamResidentMsg); });
+    return upload_world(e, total_blocks, object_poses, listener_poses, 3);
 }
 
 int jf_batch_run(jf_engine *e, int first_block, int n_blocks, float *d_out_mix) {
@@ -1895,6 +2040,7 @@ int jf_batch_run(jf_engine *e, int first_block, int n_blocks, float *d_out_mix) 
         e->last_ingest = false;
         e->last_stream = false;
         e->last_pose = 0;
+        e->call_geo = e->traj_geo;
     }
     // the standing gains (no trajectory of gains here): a level that changed ramps over the run's first block
     return jf_guard([&]() -> int {
@@ -1988,23 +2134,25 @@ int jf_synchronize(jf_engine *e) {
 // positions [n_blocks][S][5], or (positions == null) world [n_blocks][S][3] + poses [n_blocks][n_buses][7]: jf_process_batch_world,
 // or (by_object) world = objects [n_blocks][n_objects][3] + poses: jf_process_batch_objects
 static int process_batch(jf_engine *e, int n_blocks, const float *in, const float *positions, const float *world,
-                         const float *poses, float *out_mix, bool by_object = false) {
+                         const float *poses, float *out_mix, int kind = 1) {
     return jf_guard([&]() -> int {
     DeviceGuard bind(e);
-    if (!e || (!positions && (!world || !poses)) || !out_mix || n_blocks <= 0) return fail(e, JF_ERR_ARG, "bad batch arguments");
+    const bool by_object = kind >= 2;
+    if (!e || (!positions && (!world || (!poses && kind != 3))) || !out_mix || n_blocks <= 0) return fail(e, JF_ERR_ARG, "bad batch arguments");
     if ((e->n_live > 0 || e->n_stream > 0) && e->in_flight) return fail(e, JF_ERR_STATE, "a per-block call is in flight");  // (before its input is touched)
     // a trajectory jf_batch_set_gains staged for another number of blocks: refused with nothing uploaded or rendered
     int rc = gain_traj_check(e, n_blocks);
     if (rc) return rc;
-    rc = positions ? upload_positions(e, n_blocks, positions) : upload_world(e, n_blocks, world, poses, by_object);
+    rc = positions ? upload_positions(e, n_blocks, positions) : upload_world(e, n_blocks, world, poses, kind);
     if (rc) return rc;
+    e->call_geo = e->traj_geo;
     // the gains of the call: the standing ones, or the staged trajectory (kept if the positions were refused above)
     // (a failure below settles the blocks that were launched; only the call's first run switches sets and ramps the masters,
     // the limiter's state carries from run to run on the device)
     CallLatches call(e);
     rc = call.latch(n_blocks);
     if (rc) return rc;
-    e->last_pose = positions ? 0 : by_object ? 2 : 1;
+    e->last_pose = positions ? 0 : e->traj_follow ? 3 : by_object ? 2 : 1;
     const size_t blk = (size_t)2 * e->B;
     std::vector<float> last_rec;  // a world call: the last block's records by the host twin
     for (int b0 = 0; b0 < n_blocks; b0 += e->maxK) {
@@ -2037,7 +2185,10 @@ static int process_batch(jf_engine *e, int n_blocks, const float *in, const floa
             // while the last window runs: where the sources will stand afterwards (what the pose kernel wrote for the last
             // block, bit for bit)
             last_rec.resize((size_t)5 * e->S);
-            twin_records(e, world_points(e, world, by_object), poses, (size_t)n_blocks - 1, last_rec.data());
+            if (e->traj_follow)
+                twin_records_follow(e, e->traj_hgeo, (size_t)n_blocks - 1, last_rec.data());
+            else
+                twin_records(e, world_points(e, world, by_object), poses, (size_t)n_blocks - 1, last_rec.data());
         }
         JF_HIP(e, hipStreamSynchronize(e->stream));
         if (device_fault(e)) return fail(e, JF_ERR_DEVICE, kHandOffMsg);
@@ -2052,9 +2203,27 @@ static int process_batch(jf_engine *e, int n_blocks, const float *in, const floa
     // object at the last block's position, the sources attached as the call found them
     std::lock_guard<std::mutex> lk(e->pos_mu);
     const WorldPoints pt = world_points(e, world, by_object);
-    const float *w = pt.p + (size_t)(n_blocks - 1) * pt.n * 3, *q = poses + (size_t)(n_blocks - 1) * e->n_buses * kPoseFloats;
-    e->pose.assign(q, q + (size_t)e->n_buses * kPoseFloats);
-    if (by_object) {
+    const float *w = pt.p + (size_t)(n_blocks - 1) * pt.n * (kind == 3 ? kPoseFloats : 3);
+    const float *q = poses ? poses + (size_t)(n_blocks - 1) * e->n_buses * kPoseFloats : nullptr;
+    if (!e->traj_follow) {
+        e->pose.assign(q, q + (size_t)e->n_buses * kPoseFloats);
+    } else if (q) {  // (a following bus stays with its object: its row was ignored)
+        if (e->pose.empty()) {
+            e->pose.assign((size_t)kPoseFloats * e->n_buses, 0.0f);
+            for (int b = 0; b < e->n_buses; b++) e->pose[(size_t)kPoseFloats * b + 3] = 1.0f;
+        }
+        for (int b = 0; b < e->n_buses; b++)
+            if (follow_of(e, b) < 0) std::copy(q + (size_t)kPoseFloats * b, q + (size_t)kPoseFloats * (b + 1), e->pose.begin() + (size_t)kPoseFloats * b);
+    }
+    if (kind == 3) {  // every object at the last block's pose
+        e->object_quat.resize(4 * pt.n);
+        for (size_t o = 0; o < pt.n; o++) {
+            std::copy(w + kPoseFloats * o, w + kPoseFloats * o + 3, e->object_world.begin() + 3 * o);
+            std::copy(w + kPoseFloats * o + 3, w + kPoseFloats * (o + 1), e->object_quat.begin() + 4 * o);
+        }
+        e->object_of = e->object_of_dev;
+        if (e->world.empty()) e->world.assign((size_t)e->S * 3, 0.0f);
+    } else if (by_object) {
         e->object_world.assign(w, w + pt.n * 3);
         e->object_of = e->object_of_dev;
         if (e->world.empty()) e->world.assign((size_t)e->S * 3, 0.0f);
@@ -2086,7 +2255,12 @@ int jf_process_batch_world(jf_engine *e, int n_blocks, const float *in, const fl
 
 int jf_process_batch_objects(jf_engine *e, int n_blocks, const float *in, const float *objects, const float *poses, float *out_mix) {
     if (e && (!objects || !poses)) return jf_guard([&]() -> int { return fail(e, JF_ERR_ARG, "null object positions or poses"); });
-    return process_batch(e, n_blocks, in, nullptr, objects, poses, out_mix, true);
+    return process_batch(e, n_blocks, in, nullptr, objects, poses, out_mix, 2);
+}
+
+int jf_process_batch_poses(jf_engine *e, int n_blocks, const float *in, const float *object_poses, const float *listener_poses, float *out_mix) {
+    if (e && !object_poses) return jf_guard([&]() -> int { return fail(e, JF_ERR_ARG, "null object poses"); });
+    return process_batch(e, n_blocks, in, nullptr, object_poses, listener_poses, out_mix, 3);
 }
 
 int jf_sources_set_latched(jf_engine *e, const float *records) {

@@ -471,13 +471,14 @@ const char *jf_debug_last_kernels(jf_engine *e) {
     try {
         const std::string nb = std::to_string(e->B / 64), bs = std::to_string(e->B);
         std::string k;
-        if (e->last_pose) k = e->last_pose == 2 ? "pose_object_kernel;" : "pose_kernel;";
+        if (e->last_pose) k = e->last_pose == 3 ? "pose_follow_kernel;" : e->last_pose == 2 ? "pose_object_kernel;" : "pose_kernel;";
         if (e->last_ingest) k += "live_ingest_kernel;";
         if (e->last_stream) k += "stream_resample_kernel;";
         if (!e->last_rt && !e->last_prep_skipped) k += "prep_kernel;";
         if (!e->last_rt && e->last_set) k += "desc_set_kernel;";
         if (!e->last_rt && e->last_gate) k += "input_level_kernel;gate_scan_kernel;";
         if (!e->last_rt && e->last_gate && e->rg.last) k += "range_gain_kernel;";
+        if (!e->last_rt && e->last_gate && e->cn.last) k += "cone_gain_kernel;";
         if (!e->last_rt && e->last_gate && e->vc.last) k += "voice_env_kernel;voice_select_kernel;";
         if (!e->last_rt && e->last_gate && e->lv.last) k += "level_scan_kernel;";
         if (!e->last_rt && e->last_gain) k += "desc_gain_kernel;";

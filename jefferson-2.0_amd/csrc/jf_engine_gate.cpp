@@ -20,7 +20,7 @@ bool gate_wanted(jf_engine *e) {
     if (e->levels_want) return true;
     for (const GatePar &g : e->gt_par)
         if (g.open > 0.0f) return true;
-    return voices_limited(e) || levelled(e) || ranged(e);  // (a follower counts as a gate)
+    return voices_limited(e) || levelled(e) || ranged(e) || coned(e);  // (a follower counts as a gate)
 }
 
 // The device copies of the call's parameters and of the root map, where they differ from what the device holds (staged_upload),
@@ -66,7 +66,8 @@ int gate_latch(jf_engine *e) {
         e->vc.on = voice_latch_host(e);  // a bus with a voice limit: the stage runs whether or not a source has a gate
         e->lv.on = level_latch_host(e);  // ... and so it does for a source with a leveller
         e->rg.on = range_latch_host(e);  // ... and for a bus with a hearing range
-        bool active = e->levels_want || e->vc.on || e->lv.on || e->rg.on;
+        e->cn.on = cone_latch_host(e);   // ... and for an object with a cone
+        bool active = e->levels_want || e->vc.on || e->lv.on || e->rg.on || e->cn.on;
         for (size_t s = 0; s < e->gt_par.size() && !active; s++) active = e->gt_par[s].open > 0.0f;
         if (!active) return JF_OK;  // nothing was ever set, or every gate was set back to open = 0: no meters, no follower
         if (e->gt_par.empty())
@@ -79,6 +80,7 @@ int gate_latch(jf_engine *e) {
     if (rc == JF_OK && e->vc.on) rc = voice_latch_active(e);
     if (rc == JF_OK && e->lv.on) rc = level_latch_active(e);
     if (rc == JF_OK && e->rg.on) rc = range_latch_active(e);
+    if (rc == JF_OK && e->cn.on) rc = cone_latch_active(e);
     if (rc) gate_settle(e);  // (nothing of a call that failed to latch is on)
     e->gate_on = rc == JF_OK;
     return rc;
@@ -110,6 +112,13 @@ int run_gate_stage(jf_engine *e, const float *d_pos, int p, int K, int canon, bo
         rc = run_range_stage(e, d_pos, g_eff, g_eff_prev, K, timed);
         if (rc) return rc;
         e->rg.reported = e->gate_meters;
+    }
+    e->cn.last = e->cn.reported = false;
+    if (e->cn.on) {  // the objects' cones: g_eff and g_eff_prev times d, in place, BEHIND the range -- (g h) d -- and AHEAD of the
+                     // voice limits: a talker who faces away with outer_gain 0 is no candidate for a place (jf_engine_cone.cpp)
+        rc = run_cone_stage(e, g_eff, g_eff_prev, K, timed);
+        if (rc) return rc;
+        e->cn.reported = e->gate_meters;
     }
     e->vc.last = e->vc.reported = false;
     if (e->vc.on) {  // the buses' voice limits: g_eff and g_eff_prev rewritten in place (jf_engine_voice.cpp)
@@ -145,6 +154,7 @@ int gate_close_source(jf_engine *e, int src) {
     int rc = voice_reset_source(e, src);
     if (rc == JF_OK) rc = level_reset_source(e, src);
     if (rc == JF_OK) rc = range_reset_source(e, src);
+    if (rc == JF_OK) rc = cone_reset_source(e, src);
     if (rc || !e->d_gt_state) return rc;
     return state_fill(e, e->d_gt_state, 0, kGateStateWords, src);
 }

@@ -73,6 +73,7 @@
 #include "jf_output.h"
 #include "jf_pose_rule.h"
 #include "jf_range_rule.h"
+#include "jf_cone_rule.h"
 #include "jf_report.h"
 #include "jf_room.h"
 #include "jf_stream.h"
@@ -162,6 +163,12 @@ hipError_t launch_level_scan(const float *d_par, const int *d_root, const float 
 // planes of [S], d_pos the run's records [K][S][5]; the state is read from one plane and written to the other
 hipError_t launch_range_gain(const float *d_par, const float *d_pos, float *d_g_eff, float *d_g_eff_prev, const float *d_h_prev_in,
                              float *d_h_prev_out, float *d_h, int S, int K, hipStream_t st);
+// talker cones (jf_cone.hip): g_eff and g_eff_prev times d, in place, behind launch_range_gain; geo holds device pointers
+hipError_t launch_cone_gain(const ConeGeometry &geo, const float *d_par, const int *d_maps, float *d_g_eff, float *d_g_eff_prev,
+                            const float *d_prev_in, float *d_prev_out, float *d_d, int S, int K, hipStream_t st);
+// listeners that follow objects (jf_follow.hip): the records of an objects batch call whose poses are resolved per (block, source)
+hipError_t launch_pose_follow(const ConeGeometry &geo, const int *d_object_of, const int *d_bus, const int *d_follow, float *d_pos, int S,
+                              int K, int n_buses, int n_objects, hipStream_t st);
 }  // namespace jf
 
 using namespace jf;
@@ -713,6 +720,42 @@ struct jf_engine : ReverbSetup {
     DevBuf<float> d_rg_hprev;                 // [2][S]: the state, two planes taken in turn per run (read one, write the other)
     int rg_cur = 0;                           // the plane the next run reads
 
+    // OBJECT POSES, FOLLOWING LISTENERS AND TALKER CONES (jf_object_set_pose, jf_listener_follow_object, jf_object_set_cone;
+    // DESIGN.md 4.26).  An object has an orientation beside its position; the listener of a bus may FOLLOW an object -- its pose
+    // is then the object's, resolved on the host for the per-block calls (listener_pose) and by pose_follow_kernel (jf_follow.hip)
+    // for the objects batch calls --; an object may carry a cone {inner, outer, outer_gain}.  While the engine is ACTIVE for
+    // cones -- some object's cone is not the default -- it counts as gate-active, and run_gate_stage launches cone_gain_kernel
+    // (jf_cone.hip) behind the range stage and ahead of the voice stage.  The host state is under pos_mu like `pos` and empty
+    // until first use; an engine that never sets any of the three allocates nothing below and launches what it launched.
+    std::vector<float> object_quat;           // [n_objects][4] (empty: every orientation is the identity)
+    std::vector<int> follow;                  // [n_buses] the object the bus's listener follows, -1: none (empty: none ever did)
+    std::vector<float> cn_cone;               // [n_objects][3] (empty: every cone is the default)
+    // (the processing thread's, but for cn.report.last / .blocks)
+    DevBuf<float> d_objects_ori;              // [n_objects][4] the latched orientations of an objects batch call with a follow
+    std::vector<float> objects_ori_dev;       // what it holds
+    DevBuf<int> d_follow_src;                 // [S] per source the object its bus's listener follows, as pose_follow_kernel reads it
+    std::vector<int> follow_src_dev;          // what it holds: of the last objects batch call (empty: nothing yet)
+    int traj_geo = 0;                         // what the uploaded trajectory was formed from: 0 records, 1 world positions, 2 objects, 3 object poses
+    int call_geo = 0;                         // ... and the call in hand (a per-block call: 0)
+    int traj_n_objects = 0, traj_n_buses = 0; // the counts the arrays of a trajectory of kind 2 / 3 were laid out for
+    ConeGeometry traj_dgeo = {};              // kind 2 / 3: where block 0's poses lie on the device (obj_ori null: the latched ones)
+    int run_first_block = -1;                 // run_blocks' first_block for the gate stage's followers
+    bool traj_follow = false;                 // the trajectory's records were formed by pose_follow_kernel
+    ConeGeometry traj_hgeo = {};              // ... from these arrays of the caller's (valid inside the call that uploaded them)
+    std::vector<float> traj_ori;              // [n_objects][4] the orientations latched when an objects trajectory was uploaded (empty: the identity)
+    Follower<float> cn{1, 1.0f};              // d_par: [3][S] inner, outer, outer_gain per SOURCE; report: d[k] of a run
+    std::vector<float> run_cn;                // [3][S] the call's parameters as the device holds them
+    DevBuf<int> d_cn_map;                     // [3][S] object, bus, followed object per source
+    std::vector<int> run_cn_map, dev_cn_map;  // the call's, and what d_cn_map holds
+    StagedRing<int> cn_map_ring;
+    DevBuf<float> d_cn_geo;                   // [n_objects][3], [n_objects][4], [n_buses][7]: the latched poses
+    std::vector<float> run_cn_geo, dev_cn_geo;
+    std::unique_ptr<StagedRing<float>> cn_geo_ring;  // slots of cn_geo_len floats (made anew when the counts change)
+    size_t cn_geo_len = 0;
+    size_t cn_geo_objects = 0;                // the n_objects run_cn_geo was laid out for
+    DevBuf<float> d_cn_dprev;                 // [2][S]: the state, two planes taken in turn per run
+    int cn_cur = 0;                           // the plane the next run reads
+
     // STREAM SOURCES (jf_source_set_stream, jf_source_push).  A stream source is internally a live source that
     // takes no row of `in`: the same live_len device buffer named by its record in d_sigs, filled at the source's play position
     // by stream_resample_kernel (jf_stream.hip) from the source's FIFO -- pinned, mapped host memory the pushes write and the
@@ -1143,7 +1186,7 @@ JF_INTERNAL int source_report(jf_engine *e, const RunReport &r, bool (*set)(cons
                               int n_blocks, float *out);
 // The followers, in the order in which they are latched, reset and copied (the order of their LAUNCHES is run_gate_stage's, which
 // names them: range, voice, level).
-inline std::array<FollowerState *, 3> followers(jf_engine *e) { return {&e->vc, &e->lv, &e->rg}; }
+inline std::array<FollowerState *, 4> followers(jf_engine *e) { return {&e->vc, &e->lv, &e->rg, &e->cn}; }
 // voice limits (jf_engine_voice.cpp).  gate_latch calls voice_latch_host under pos_mu (the call's tables; true while some bus
 // has a limit: the engine then counts as gate-active) and voice_latch_active behind the gates' own buffers (allocation, the
 // copy that differs).  run_voice_stage: from run_gate_stage between gate_scan_kernel and desc_gain_kernel, while e->vc.on.
@@ -1178,6 +1221,23 @@ JF_INTERNAL int run_range_stage(jf_engine *e, const float *d_pos, float *g_eff, 
 JF_INTERNAL int range_reset_source(jf_engine *e, int src);
 JF_INTERNAL void range_set_buses(jf_engine *e, int n_buses);
 JF_INTERNAL bool ranged(const jf_engine *e);
+// talker cones (jf_engine_cone.cpp), wired like the hearing range.  gate_latch calls cone_latch_host under pos_mu (the call's
+// planes and maps, resolved per source from its object, its bus and the bus's follow, and the latched poses; true while some
+// object has a cone: the engine then counts as gate-active) and cone_latch_active behind the gates' own buffers.
+// run_cone_stage: from run_gate_stage behind the range stage and AHEAD of the voice stage, while e->cn.on.  cone_reset_source: a
+// reset or a new signal takes the source's d_prev back to 1 (src < 0: every one).  cone_set_objects / follow_set_buses: under
+// pos_mu, from jf_engine_set_objects / jf_engine_set_buses.  coned: under pos_mu, some object has a cone.  listener_pose:
+// under pos_mu, the pose of a bus's listener -- its followed object's, or its own.  object_quat_of: under pos_mu.
+JF_INTERNAL bool cone_latch_host(jf_engine *e);
+JF_INTERNAL int cone_latch_active(jf_engine *e);
+JF_INTERNAL int run_cone_stage(jf_engine *e, float *g_eff, float *g_eff_prev, int K, bool timed);
+JF_INTERNAL int cone_reset_source(jf_engine *e, int src);
+JF_INTERNAL void cone_set_objects(jf_engine *e, int n_objects);
+JF_INTERNAL void follow_set_buses(jf_engine *e, int n_buses);
+JF_INTERNAL bool coned(const jf_engine *e);
+JF_INTERNAL void listener_pose(const jf_engine *e, int bus, float out[kPoseFloats]);
+JF_INTERNAL const float *object_quat_of(const jf_engine *e, int obj);
+JF_INTERNAL int follow_of(const jf_engine *e, int bus);
 // The two kinds of report a call can render -- the bus meters (the masters') and the input meters with the followers' reports
 // (the gates') -- have one life cycle (jf_engine.cpp).  reports_on: those the call in hand renders, as a mask.  reports_copy:
 // behind a run, the copies of its K blocks to the pinned buffers, enqueued.  reports_land: the stream has been waited for --
